@@ -30,6 +30,10 @@ live with HIP events on the launch stream (priced at its in-step duration, the i
 box's host cores on a bounded sample of the same workload).  Everything else the run measured -- `roofline_step` per kernel
 family, the L = 1 and C2 legs, per-step times, the sharded run's `phases` / `graph_leg` / `parity` -- goes to the side file the
 line names under `detail` (`--detail`, default ./bench_detail.json).
+
+`--dump-outputs DIR` writes, behind the timed steps, a fixed seeded sample of what the last timed step computed (its
+outputs, the dense weights and table rows it updated) as float32 DIR/<name>.npy files: the inputs and the sampled
+positions depend only on the arguments, so two builds can be compared output for output (dump_sample).
 """
 
 from __future__ import annotations
@@ -55,6 +59,7 @@ CRITEO_VOCABS = [40000000, 39060, 17295, 7424, 20265, 3, 7122, 1543, 63, 4000000
 HBM_PEAK = 8.0e12  # MI355X_MICROARCH.md: 8 TB/s spec
 MFMA_BF16_PEAK = 2.5e15  # MI355X_MICROARCH.md: dense bf16 MFMA peak (no sparsity)
 MFMA_F32_PEAK = 157.3e12  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 (fp32 in / fp32 acc) = the fp32 vector rate
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: the sample of one step's results, all files together
 
 
 def parse():
@@ -139,6 +144,11 @@ def parse():
     ap.add_argument("--detail", default="bench_detail.json", metavar="PATH",
                     help="side file with everything the run measured (roofline_step, also, also_c2, phases, graph_leg, per-step "
                          "times); the last stdout line is a summary below %d bytes that names it" % 4096)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the primary leg's LAST timed step computed to DIR/<name>.npy (float32): "
+                         "a fixed, seeded sample of its outputs `xl` / `inter`, of the cross layers' weights after the step's "
+                         "update and (unsharded layer) of the table rows it updated -- the same positions in every run with the "
+                         "same arguments, %d MB at most; rank 0 only" % (DUMP_MAX_BYTES >> 20))
     ap.add_argument("--print-detail", action="store_true",
                     help="also print the side file's content as an earlier stdout line (KRS_BENCH_DETAIL ...)")
     ap.add_argument("--cpu-pools", default="16", metavar="LIST",
@@ -282,6 +292,47 @@ def make_inputs(a, hots, b_local, rank, dev):
     dense = (torch.rand(b_local, a.dim, device=dev, generator=g) * 0.9).to(
         torch.float32 if getattr(a, "fp32", False) else torch.bfloat16)
     return ids, dense
+
+
+def dump_sample(model, a, keep, ids, b_local, sharded):
+    """--dump-outputs: the sample of what one step computed, as float32 host arrays by file name.  `keep` holds the step's
+    outputs (`xl`, `inter`); the weights and tables are read as that step's optimizer left them.  Every position comes from
+    a fixed seed or from the (seeded) input ids, so two runs with the same arguments sample the same elements:
+      xl, inter            -- up to 1024 batch rows of the cross stack's and DotInteraction's outputs
+      cross<i>_<weight>    -- up to 65 536 elements of each FeatureCross weight (fp32 master weights)
+      table_cat_<t>        -- unsharded layer only: up to 256 rows of table t that the sampled batch rows look up"""
+    rng = np.random.default_rng(20240)
+    xl, inter = keep["xl"], keep["inter"]
+    dev = xl.device
+
+    def pick(n, k):
+        return torch.from_numpy(np.sort(rng.choice(n, k, replace=False)) if k < n else np.arange(n)).to(dev)
+
+    n_rows = max(1, min(1024, b_local, (DUMP_MAX_BYTES // 4) // (4 * xl.shape[1])))
+    rows = pick(b_local, n_rows)
+    out = {"xl": xl.index_select(0, rows)}
+    if inter is not None:
+        out["inter"] = inter.index_select(0, rows)
+    for i, layer in enumerate(model.cross):
+        for name, w in layer.named_parameters():
+            flat = w.detach().reshape(-1)
+            out["cross%d_%s" % (i, name)] = flat.index_select(0, pick(flat.numel(), 65536))
+    if not sharded:
+        tables = model.embedding.get_embedding_tables()
+        for t in range(a.tables):
+            looked_up = ids[f"cat_{t:02d}_id"].index_select(0, rows).reshape(-1).unique()[:256]
+            out[f"table_cat_{t}"] = tables[f"cat_{t}"].index_select(0, looked_up.long())
+    out = {k: v.float().cpu().numpy() for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: the sample of this configuration is %d bytes, above %d" % (total, DUMP_MAX_BYTES))
+    return out
+
+
+def write_dump(arrays, path):
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 _BLOCK = {}
@@ -441,12 +492,14 @@ def cpu_baseline(a, hots):
 
 
 def measure(model, a, hots, world, rank, dev, b_local, steps, warmup, opt_box, loader=None, probe_steps=0,
-            sustained_steps=0):
+            sustained_steps=0, dump=None):
     """Times `steps` steps of the hot path for one bag-length list.  Returns a dict: `elapsed` (wall seconds of the
     timed region, max over ranks), `k1_s` (one K1 launch, events), `step_ms` (per-step GPU time of the timed steps,
     from events recorded at the step boundaries) and, with `probe_steps`, `probe` (in-step kernel spans of that many
     EXTRA steps run after the timed region; keras_rs_amd/probe.py).
-    With `loader`, every step takes its preprocessed ids from it (host-resident inputs)."""
+    With `loader`, every step takes its preprocessed ids from it (host-resident inputs).
+    With `dump` (a dict), the last timed step keeps its outputs and `dump` receives dump_sample() of that step, taken
+    behind the timed region and before anything else runs a step."""
     from keras_rs_amd import probe as krs_probe
 
     ids, dense = make_inputs(a, hots, b_local, rank, dev)
@@ -471,8 +524,12 @@ def measure(model, a, hots, world, rank, dev, b_local, steps, warmup, opt_box, l
     prefetch = (sharded_run and loader is None and not getattr(a, "graph", False) and a.prefetch
                 and getattr(model.embedding, "exchange", None) == "static")
 
-    def step():
+    keep = {} if dump is not None else None
+
+    def step(keep=None):
         xl, inter = model(dense, pre if loader is None else next(loader))
+        if keep is not None:    # (the last timed step of a --dump-outputs run: its outputs stay alive for the sample)
+            keep.update(xl=xl.detach(), inter=None if inter is None else inter.detach())
         if prefetch:
             model.embedding.prefetch(pre)
         # loss = scale * sum(xl) + 0.1 * scale * sum(inter), taken through its (constant) output
@@ -514,7 +571,8 @@ def measure(model, a, hots, world, rank, dev, b_local, steps, warmup, opt_box, l
         #  captured with the step; every rank captures and replays the same graph)
         from keras_rs_amd.graphs import GraphedStep
 
-        step = GraphedStep(eager_step, warmup=2)
+        # (with --dump-outputs the captured step keeps its output tensors: every replay rewrites them in place)
+        step = GraphedStep(eager_step if keep is None else (lambda: eager_step(keep)), warmup=2)
     sharded = world > 1 or a.force_sharded
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     # The timed region runs without the cyclic garbage collector: a full collection of a process that has imported
@@ -536,10 +594,14 @@ def measure(model, a, hots, world, rank, dev, b_local, steps, warmup, opt_box, l
     t0 = time.perf_counter()
     marks[0].record()
     dbg = [] if os.environ.get("KRS_BENCH_DEBUG") else None
+    keep_at = steps - 1 if keep is not None and step is eager_step else -1
     for i in range(steps):
         if dbg is not None:
             th = time.perf_counter()
-        step()
+        if i == keep_at:
+            step(keep)
+        else:
+            step()
         marks[i + 1].record()     # step boundaries on the launch stream: per-step GPU time, no host wait
         if dbg is not None:
             ms = torch.cuda.memory_stats(dev)
@@ -559,6 +621,9 @@ def measure(model, a, hots, world, rank, dev, b_local, steps, warmup, opt_box, l
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)]
+    if dump is not None:
+        dump.update(dump_sample(model, a, keep, ids, b_local, sharded))
+        keep.clear()
     sustained = None
     if sustained_steps > 0:
         # `sustained`: the same step, back to back for seconds instead of K = 20 steps -- the chip clocks to its power
@@ -1218,9 +1283,13 @@ def main():
         del ids0
     wall = {"setup_build_model": time.perf_counter() - T_START}
     t_mark = time.perf_counter()
+    dumped = {} if a.dump_outputs and rank == 0 else None
     r1 = measure(model, a, primary, world, rank, dev, b_local, a.steps, a.warmup, opt_box, probe_steps=a.probe_steps,
-                 sustained_steps=a.sustained_steps)
+                 sustained_steps=a.sustained_steps, dump=dumped)
     wall["primary_leg"] = time.perf_counter() - t_mark
+    if dumped is not None:
+        write_dump(dumped, a.dump_outputs)
+        dumped = None
     t_mark = time.perf_counter()
     # the other C3 bag-length list (SURVEY.md section 8d lists both), same tables and model, shorter run.  The
     # shapes change (ids, plan workspace), so the leg gets its own warm-up of at least 5 steps: the caching

@@ -88,7 +88,7 @@ def criteo_shaped(rank, world, kl, Sharded):
 def main():
     dist.init_process_group("gloo")
     rank, world = dist.get_rank(), dist.get_world_size()
-    torch.cuda.set_device(0)
+    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)) % torch.cuda.device_count())
     import keras_rs_amd.layers as kl
     from keras_rs_amd.sharded import ShardedDistributedEmbedding
 

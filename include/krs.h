@@ -594,6 +594,42 @@ int krs_shard_unpack_static(const int32_t* packed, int n_sources, int64_t cap_lo
                             void* workspace, size_t workspace_bytes, void* stream);
 int krs_publish_i64(const int64_t* src, int n, int64_t* host_dst, int64_t seq, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K8 retrieval: exact row top-k and the fused score + top-k of
+ * BruteForceRetrieval (brute_force_retrieval.py:126-148,
+ * `top_k(matmul(query, candidates.T), k)`) and HardNegativeMining
+ * (hard_negative_mining.py:43-94, `top_k(logits + labels * MAX_FLOAT)`).
+ * Selection order, one total order: the fp32 key descending, then the index
+ * ascending; -0.0 ranks as +0.0, NaN above +inf (torch.topk).  Rows come back
+ * sorted in that order; results are bit-identical from call to call; no host
+ * synchronisation (graph-capturable).  Returned keys / scores are the fp32
+ * value (a NaN as the canonical quiet NaN, -0.0 as +0.0) rounded once to the
+ * output dtype.  Indices and ids are int32.
+ * ------------------------------------------------------------------------- */
+/* Row top-k of X[rows, cols] (fp32 or bf16, row stride ld) on the key
+ * x + boost_scale * boost, computed in fp32 (boost: same shape, dtype and
+ * stride as X, or NULL).  out_idx [rows, k] int32 column indices; out_keys
+ * [rows, k] fp32 keys or NULL.  1 <= k <= cols.  Workspace:
+ * krs_topk_rows_workspace_bytes (0 for cols <= 2048). */
+size_t krs_topk_rows_workspace_bytes(int64_t rows, int64_t cols, int k);
+int krs_topk_rows(const void* x, const void* boost, float boost_scale, int64_t ld, int dtype,
+                  int64_t rows, int64_t cols, int k, int32_t* out_idx, float* out_keys,
+                  void* workspace, size_t workspace_bytes, void* stream);
+/* Top-k of the scores Q[b, d] . C[n, d]^T per query row (both `dtype`, row
+ * strides ldq / ldc in elements): out_scores [b, k] in `dtype` (or NULL),
+ * out_ids [b, k] int32 = ids[index] when ids != NULL (int32 [n]), else the
+ * candidate index.  bf16 multiplies on v_mfma_f32_32x32x16_bf16, fp32 on
+ * v_mfma_f32_32x32x2_f32; the products accumulate in fp32.  k <= 128 and
+ * d <= 512 run fused (the scores never leave the chip); other shapes run
+ * krs_gemm into a query-chunked fp32 slab (<= about 1 GiB) and the
+ * krs_topk_rows selection.  1 <= k <= n, d >= 1, b >= 0.  Workspace:
+ * krs_retrieval_topk_workspace_bytes (always > 0 for b > 0). */
+size_t krs_retrieval_topk_workspace_bytes(int64_t b, int64_t n, int64_t d, int k, int dtype);
+int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int64_t ldc, const int32_t* ids,
+                       int dtype, int64_t b, int64_t n, int64_t d, int k,
+                       void* out_scores, int32_t* out_ids,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

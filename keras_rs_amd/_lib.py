@@ -100,6 +100,10 @@ SYMBOLS = [
     "krs_shard_unpack_static",
     "krs_publish_i64",
     "krs_bce_fwd_bwd",
+    "krs_topk_rows",
+    "krs_topk_rows_workspace_bytes",
+    "krs_retrieval_topk",
+    "krs_retrieval_topk_workspace_bytes",
 ]
 
 _lib = None
@@ -123,7 +127,8 @@ def lib() -> C.CDLL:
         for name in ("krs_embed_bag_bwd_workspace_bytes", "krs_gemm_workspace_bytes",
                      "krs_mod_bucketize_workspace_bytes", "krs_shard_route_workspace_bytes",
                      "krs_shard_unpack_workspace_bytes", "krs_colsum_workspace_bytes",
-                     "krs_gemm_cross_bwd_workspace_bytes"):
+                     "krs_gemm_cross_bwd_workspace_bytes", "krs_topk_rows_workspace_bytes",
+                     "krs_retrieval_topk_workspace_bytes"):
             getattr(_lib, name).restype = C.c_size_t
         _lib.krs_shard_static_block_words.restype = C.c_int64
     return _lib

@@ -8,6 +8,7 @@ from keras_rs_amd.layers.dot_interaction import DotInteraction
 from keras_rs_amd.layers.embed_reduce import EmbedReduce, Embedding, Ragged
 from keras_rs_amd.layers.feature_cross import FeatureCross
 from keras_rs_amd.layers.losses import BinaryCrossentropy, binary_crossentropy
+from keras_rs_amd.layers.retrieval import BruteForceRetrieval, HardNegativeMining, Retrieval
 
-__all__ = ["Adagrad", "Adam", "BinaryCrossentropy", "binary_crossentropy", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
-           "FeatureCross", "Ftrl", "Ragged", "RowwiseAdagrad", "SGD", "TableConfig", "concat_features"]
+__all__ = ["Adagrad", "Adam", "BinaryCrossentropy", "binary_crossentropy", "BruteForceRetrieval", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
+           "FeatureCross", "Ftrl", "HardNegativeMining", "Ragged", "Retrieval", "RowwiseAdagrad", "SGD", "TableConfig", "concat_features"]

@@ -1,0 +1,190 @@
+"""Retrieval layers on MI355X: drop-ins for keras_rs.layers.BruteForceRetrieval
+(keras_rs/src/layers/retrieval/brute_force_retrieval.py) and keras_rs.layers.HardNegativeMining
+(hard_negative_mining.py), both on K8's exact top-k (include/krs.h: krs_retrieval_topk, krs_topk_rows).
+
+Selection order: score descending, then candidate index ascending (-0.0 as +0.0, NaN above +inf); rows come back
+sorted.  Known divergence: for bf16 inputs keras.ops.matmul rounds the scores to bf16 before top_k, so among
+candidates whose scores round to one bf16 value the reference's order can differ from this one, which ranks the
+fp32 scores and rounds only the returned values.
+"""
+
+from __future__ import annotations
+
+from typing import Any
+
+import numpy as np
+import torch
+
+from keras_rs_amd import _lib as L
+from keras_rs_amd import retrieval_ops
+from keras_rs_amd.layers import base
+
+
+def _as_tensor(x, device=None) -> torch.Tensor:
+    if isinstance(x, torch.Tensor):
+        return x
+    return torch.as_tensor(np.asarray(x), device=device)
+
+
+class Retrieval(base.Layer):
+    """Common interface of retrieval layers (retrieval.py): `k` candidates per query, scores returned with the ids
+    when `return_scores`."""
+
+    def __init__(self, k: int = 10, return_scores: bool = True, **kwargs: Any):
+        super().__init__(**kwargs)
+        self.k = k
+        self.return_scores = return_scores
+
+    def _validate_candidate_embeddings_and_ids(self, candidate_embeddings, candidate_ids=None) -> None:
+        if candidate_embeddings is None:
+            raise ValueError("`candidate_embeddings` is required.")
+        shape = tuple(candidate_embeddings.shape)
+        if len(shape) != 2:
+            raise ValueError("`candidate_embeddings` must be a tensor of rank 2 (num_candidates, embedding_size), "
+                             f"received `candidate_embeddings` with shape {shape}")
+        if shape[0] < self.k:
+            raise ValueError(f"The number of candidates provided ({shape[0]}) is less than the number of "
+                             f"candidates to retrieve (k={self.k}).")
+        if candidate_ids is not None and candidate_ids.shape[0] != shape[0]:
+            raise ValueError("The `candidate_embeddings` and `candidate_is` tensors must have the same number of "
+                             f"rows, got tensors of shape {shape} and {tuple(candidate_ids.shape)}.")
+
+    def update_candidates(self, candidate_embeddings, candidate_ids=None) -> None:
+        raise NotImplementedError
+
+    def compute_score(self, query_embedding: torch.Tensor, candidate_embedding: torch.Tensor) -> torch.Tensor:
+        """The dot product of queries and candidates (retrieval.py compute_score)."""
+        return torch.matmul(query_embedding, candidate_embedding.transpose(0, 1))
+
+    def get_config(self) -> dict:
+        config = super().get_config()
+        # The reference stores `self.compute_score` (a bound method) under "return_scores"; the boolean is stored
+        # here on purpose, so that from_config(get_config()) rebuilds the same layer.
+        config.update({"k": self.k, "return_scores": self.return_scores})
+        return config
+
+
+class BruteForceRetrieval(Retrieval):
+    """Exact top-k retrieval over a candidate set kept on the device (brute_force_retrieval.py).
+
+    Candidates and ids are non-trainable weights; `update_candidates` with the same shape copies in place, so a graph
+    captured around `call` keeps reading the current candidates.  `call(query)` returns (top scores, top ids), or the
+    ids alone when `return_scores=False`; ids are the candidate indices when the layer has no candidate ids.
+    """
+
+    def __init__(self, candidate_embeddings=None, candidate_ids=None, k: int = 10, return_scores: bool = True,
+                 **kwargs: Any):
+        super().__init__(k=k, return_scores=return_scores, **kwargs)
+        self.register_parameter("candidate_embeddings", None)    # (weights once candidates arrive: add_weight)
+        self.register_parameter("candidate_ids", None)
+        self._converted: dict[torch.dtype, torch.Tensor] = {}   # candidates in another query dtype
+        if candidate_embeddings is None:
+            if candidate_ids is not None:
+                raise ValueError("You cannot provide `candidate_ids` without providing `candidate_embeddings`")
+        else:
+            self.update_candidates(candidate_embeddings, candidate_ids)
+
+    def update_candidates(self, candidate_embeddings, candidate_ids=None) -> None:
+        self._validate_candidate_embeddings_and_ids(candidate_embeddings, candidate_ids)
+        emb = _as_tensor(candidate_embeddings)
+        ids = None if candidate_ids is None else _as_tensor(candidate_ids)
+        if emb.dtype not in (torch.float32, torch.bfloat16):
+            emb = emb.to(torch.float32)
+        if ids is not None:
+            if ids.dim() != 1:
+                raise ValueError(f"`candidate_ids` must be a tensor of rank 1, received shape {tuple(ids.shape)}")
+            if ids.dtype != torch.int32:
+                if ids.dtype.is_floating_point or (ids.numel() and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31)):
+                    raise ValueError("`candidate_ids` must be integers that fit int32")
+                ids = ids.to(torch.int32)
+        with torch.no_grad():
+            if self.candidate_embeddings is not None:
+                # assign: the variable keeps its shape (and its storage, which a captured graph reads)
+                if tuple(emb.shape) != tuple(self.candidate_embeddings.shape):
+                    raise ValueError(f"Cannot assign candidate_embeddings of shape {tuple(emb.shape)} to a variable "
+                                     f"of shape {tuple(self.candidate_embeddings.shape)}")
+                if self.candidate_ids is None:
+                    if ids is not None:
+                        raise ValueError("New `candidate_ids` cannot be provided as previous candidates did not have "
+                                         "candidate IDs")
+                self.candidate_embeddings.copy_(emb)
+                if self.candidate_ids is not None and ids is not None:
+                    self.candidate_ids.copy_(ids)
+                for dt, conv in self._converted.items():
+                    conv.copy_(self.candidate_embeddings)
+            else:
+                self.candidate_embeddings = self.add_weight(tuple(emb.shape), "zeros", "candidate_embeddings",
+                                                            dtype=emb.dtype, trainable=False)
+                self.candidate_embeddings.copy_(emb)
+                if ids is not None:
+                    self.candidate_ids = self.add_weight(tuple(ids.shape), "zeros", "candidate_ids",
+                                                         dtype=torch.int32, trainable=False)
+                    self.candidate_ids.copy_(ids)
+        self.built = True
+
+    def _candidates_as(self, dtype: torch.dtype) -> torch.Tensor:
+        cand = self.candidate_embeddings
+        if cand.dtype == dtype:
+            return cand.detach()
+        conv = self._converted.get(dtype)
+        if conv is None:
+            conv = cand.detach().to(dtype)
+            self._converted[dtype] = conv
+        return conv
+
+    def call(self, inputs):
+        if self.candidate_embeddings is None:
+            raise ValueError("No candidates: call `update_candidates` before using the layer.")
+        q = _as_tensor(inputs)
+        if q.dim() != 2 or q.shape[1] != self.candidate_embeddings.shape[1]:
+            raise ValueError(f"The query must have shape (batch, {self.candidate_embeddings.shape[1]}), "
+                             f"received {tuple(q.shape)}")
+        L.require_device(q, "BruteForceRetrieval query")
+        L.require_device(self.candidate_embeddings, "BruteForceRetrieval candidates")
+        # keras.ops.matmul promotion: float32 x bfloat16 -> float32
+        dt = torch.promote_types(q.dtype, self.candidate_embeddings.dtype)
+        if dt not in (torch.float32, torch.bfloat16):
+            raise L.KrsError(f"BruteForceRetrieval: unsupported query dtype {q.dtype} (float32 / bfloat16)")
+        q = q.detach().to(dt)
+        ids = None if self.candidate_ids is None else self.candidate_ids.detach()
+        scores, top_ids = retrieval_ops.retrieval_topk(q, self._candidates_as(dt), self.k, ids=ids,
+                                                       want_scores=self.return_scores)
+        if self.return_scores:
+            return scores, top_ids
+        return top_ids
+
+
+class HardNegativeMining(base.Layer):
+    """Logits and labels of the `num_hard_negatives` highest-scoring negatives plus the positive of each row
+    (hard_negative_mining.py).  Output order: the key logits + labels * MAX_FLOAT descending, then the index ascending
+    (the reference's sorted=False permits any order).  The logits gradient flows through torch.gather."""
+
+    def __init__(self, num_hard_negatives: int, **kwargs: Any):
+        super().__init__(**kwargs)
+        self._num_hard_negatives = num_hard_negatives
+        self.built = True
+
+    def num_sampled(self, num_logits: int) -> int:
+        return min(self._num_hard_negatives + 1, num_logits)
+
+    def call(self, logits: torch.Tensor, labels: torch.Tensor):
+        if logits.dim() not in (1, 2, 3):
+            raise ValueError(f"`logits` must have rank 1 to 3, received shape {tuple(logits.shape)}")
+        if tuple(labels.shape) != tuple(logits.shape):
+            raise ValueError(f"`labels` shape {tuple(labels.shape)} differs from `logits` shape {tuple(logits.shape)}")
+        L.require_device(logits, "HardNegativeMining logits")
+        L.require_device(labels, "HardNegativeMining labels")
+        c = logits.shape[-1]
+        k = self.num_sampled(c)
+        x = logits.detach().reshape(-1, c)
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()
+        boost = labels.detach().reshape(-1, c).to(x.dtype)
+        idx = retrieval_ops.topk_rows(x, k, boost=boost, boost_scale=retrieval_ops.MAX_FLOAT)
+        idx = idx.to(torch.int64).reshape(*logits.shape[:-1], k)
+        return torch.gather(logits, -1, idx), torch.gather(labels, -1, idx)
+
+    def get_config(self) -> dict:
+        config = super().get_config()
+        config.update({"num_hard_negatives": self._num_hard_negatives})
+        return config

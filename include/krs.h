@@ -630,6 +630,45 @@ int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int64_t ldc, c
                        void* out_scores, int32_t* out_ids,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * K9  Ranking losses (keras_rs.losses): unreduced loss and logit gradient in one pass
+ *
+ * logits [batch, list] fp32 / bf16 with row stride ld (>= list; a column slice of a wider matrix needs no copy);
+ * labels [batch, list] fp32, mask [batch, list] uint8 (NULL = all set), both contiguous.  An item is valid when
+ * label >= 0 and its mask byte is non-zero.  x = (s_i - s_j) * inv_temperature (the reference divides by T).
+ *
+ * krs_pairwise_loss (pairwise_loss.py, pairwise_mean_squared_error.py): item_loss [batch, list] fp32 =
+ *   sum_j w_ij phi(x_ij), w_ij = I(y_i > y_j) valid_i valid_j, with phi of `kind`:
+ *     KRS_RANK_HINGE          relu(1 - x)
+ *     KRS_RANK_LOGISTIC       relu(-x) + log(1 + exp(-|x|))
+ *     KRS_RANK_SOFT_ZERO_ONE  where(x > 0, 1 - sigmoid(x), sigmoid(-x))
+ *     KRS_RANK_MSE            ((y_i - y_j) - (s_i - s_j))^2 with w_ij = valid_i valid_j (i != j); no temperature
+ * dlogits [batch, list] (logits' dtype, contiguous) = d(sum_i g_i item_loss_i) / ds, the gradient autodiff takes
+ * of the reference's expression (relu'(0) = abs'(0) = 0), with g_i = g_scale * g[i] (g [batch, list] fp32, NULL =
+ * g_scale).
+ *
+ * krs_listmle_loss (list_mle_loss.py:70-150): list_loss [batch] fp32 = sum over the valid items in the order label
+ * descending, index ascending (exact: no offset breaks ties) of log(sum_{q >= r} exp(z_q - m) + 1e-10) - (z_r - m),
+ * z = s * inv_temperature, m = the largest valid z; 0 for a list without a valid item.  dlogits = d(sum_b g_b
+ * list_loss_b) / ds with g_b = g_scale * g[b] (g [batch] fp32 or NULL), the gradient through m included.
+ *
+ * Either output may be NULL, not both.  1 <= list <= KRS_RANK_MAX_LIST (a longer list is KRS_ERR_INVALID);
+ * batch >= 0.  fp32 arithmetic in a fixed order: bit-identical from call to call; no host synchronisation.
+ * ------------------------------------------------------------------------- */
+#define KRS_RANK_MAX_LIST 4096
+typedef enum krs_rank_loss {
+  KRS_RANK_HINGE = 0,
+  KRS_RANK_LOGISTIC = 1,
+  KRS_RANK_SOFT_ZERO_ONE = 2,
+  KRS_RANK_MSE = 3
+} krs_rank_loss;
+int krs_pairwise_loss(int kind, const void* logits, int64_t ld, int dtype, const float* labels,
+                      const uint8_t* mask, const float* g, float g_scale, float inv_temperature,
+                      int64_t batch, int64_t list, float* item_loss, void* dlogits, void* stream);
+int krs_listmle_loss(const void* logits, int64_t ld, int dtype, const float* labels, const uint8_t* mask,
+                     const float* g, float g_scale, float inv_temperature, int64_t batch, int64_t list,
+                     float* list_loss, void* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,8 @@ SYMBOLS = [
     "krs_topk_rows_workspace_bytes",
     "krs_retrieval_topk",
     "krs_retrieval_topk_workspace_bytes",
+    "krs_pairwise_loss",
+    "krs_listmle_loss",
 ]
 
 _lib = None

@@ -70,6 +70,15 @@ __device__ __forceinline__ int64_t ld_index(const void* p, int is64, int64_t i) 
   return is64 ? ((const int64_t*)p)[i] : (int64_t)((const int32_t*)p)[i];
 }
 
+// fp32 -> order-preserving uint32 (the total order of K8 and K9): -0.0 counts as +0.0, NaN ranks above +inf, -inf
+// maps to 0x007fffff (so 0 is below every real value)
+__device__ __forceinline__ uint32_t order_key(float f) {
+  uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;  // NaN above +inf
+  if (u == 0x80000000u) u = 0;                               // -0.0 == +0.0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 __host__ __device__ __forceinline__ int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace krs

@@ -41,12 +41,6 @@ constexpr int kStage1Groups = 2048;                   // target workgroups of st
 constexpr int kMinSlice = 8192;                       // shortest slice once the target is met
 constexpr size_t kSlabBudget = size_t(1) << 30;       // two-step path: fp32 slab + sort lists per chunk
 
-__device__ __forceinline__ uint32_t order_key(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;  // NaN above +inf
-  if (u == 0x80000000u) u = 0;                               // -0.0 == +0.0
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 __device__ __forceinline__ float key_value(uint32_t k) {
   if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);

@@ -79,6 +79,7 @@ SYMBOLS = [
     "krs_cross_epilogue_bwd",
     "krs_gemm_cross_bwd",
     "krs_gemm_cross_bwd_workspace_bytes",
+    "krs_gemm_cross_bwd_last_route",
     "krs_colsum",
     "krs_colsum_workspace_bytes",
     "krs_cast_transpose",

@@ -234,11 +234,12 @@ def _dense_fusable_below(rel, dz, x_dtype, task) -> bool:
     act_low, bias_low = rel.lower
     if act_low == L.ACT_NONE and not bias_low:
         return False            # (nothing to do below: a plain product)
-    if rel.fused is not None and rel.fused[3] == task:
+    if rel.fused is not None and rel.fused[4] == task:
         return False            # (another consumer of that output already did it in this pass)
     out = rel.out_ref() if rel.out_ref is not None else None
-    # (somebody watches the layer's output gradient: hand autograd the real dL/dy)
-    return out is None or not (out.retains_grad or out._backward_hooks)
+    # (the output keeps its .grad: the launches of the unfused pass, so that every gradient of the step matches that pass
+    #  bit for bit, bias gradients included -- .grad itself would be the same dL/dy either way)
+    return out is None or not out.retains_grad
 
 
 def _dx_product(ctx, dh, dc, direct, dx0, x0c, task, u_own=None):
@@ -453,16 +454,19 @@ FUSE_DENSE_BWD = bool(int(__import__("os").environ.get("KRS_FUSE_DENSE_BWD", "1"
 
 class DenseActRelay:
     """Hand-off between two STACKED Dense layers (examples/ml_perf/model.py:214-262: `x = dense(x)` repeated): the upper
-    layer's data-gradient product dx = dz K^T is the lower layer's dL/dy, and the lower layer's first backward step --
-    dz_low = dL/dy * act'(y_low), dbias_low = column sums -- can ride in that product's epilogue (krs_gemm_cross_bwd, dense
-    form): no [B, units] matrix is written for dL/dy and read back.
+    layer's data-gradient product G = dz K^T is the lower layer's dL/dy, and the lower layer's first backward step --
+    dz_low = dL/dy * act'(y_low), dbias_low = column sums -- rides in that product's epilogue (krs_gemm_cross_bwd, dense
+    form): dL/dy is not read back for it.
       lower  (act, has_bias) of the layer whose output carries this relay -- set by its forward (no tensor: the output
              holds the relay as an attribute, a reference back would be a cycle that only the cyclic collector frees; the
              upper layer has that output anyway -- it is its saved input);
-      fused  (dz_low, its version, dbias_low, graph task) -- set by the upper layer's backward, taken by the lower one's.
-    What autograd hands the lower layer is then dz_low itself.  If y had ANOTHER consumer the engine has summed that
-    consumer's gradient into it: the lower backward recognises the tensor it was promised (pointer, shape, version) and
-    otherwise sends the difference through the derivative (linear in the gradient)."""
+      fused  (G, its version, dz_low, dbias_low, graph task) -- set by the upper layer's backward, taken by the lower one's.
+    What autograd receives from the upper layer is G itself, the true dL/dy, so everything that observes the output's
+    gradient -- autograd.grad / backward(inputs=...) captures, tensor and node hooks, retain_grad -- sees the right value.
+    The lower backward takes dz_low and dbias_low only when what it is handed IS that G, untouched (pointer, shape, version:
+    the relay keeps G alive, so its memory cannot be reused meanwhile); anything else -- a second consumer's gradient summed
+    in, a hook's replacement or in-place change -- goes through its own derivative.
+      out_ref  weak reference to that output (`_dense_fusable_below`: one that retains its .grad is not fused)."""
 
     __slots__ = ("lower", "fused", "out_ref")
 
@@ -502,19 +506,15 @@ class DenseFn(torch.autograd.Function):
         rel, fused = ctx.relay_out, None
         if rel is not None:
             fused, rel.fused = rel.fused, None
-            if fused is not None and fused[3] != task:
+        if fused is not None:
+            # the consumer of y ran this layer's activation backward inside its data-gradient product: right only when
+            # what arrives is that product's G, untouched (no second consumer summed in, no hook replaced or changed it)
+            G, version = fused[:2]
+            if not (fused[4] == task and g.data_ptr() == G.data_ptr() and g.shape == G.shape and g.stride() == G.stride()
+                    and g._version == version and g.dtype == G.dtype):
                 fused = None
         if fused is not None:
-            # the consumer of y ran this layer's activation backward inside its data-gradient product
-            dz_f, version, db = fused[:3]
-            if g.data_ptr() == dz_f.data_ptr() and g.shape == dz_f.shape and g._version == version and g.dtype == dz_f.dtype:
-                dz = dz_f
-            else:
-                # y had another consumer: its share of dL/dy arrived summed into dz_f and still has to meet act'(y)
-                delta = (g.float() - dz_f.float()).to(dz_f.dtype)
-                rest, _ = D.dense_act_bwd(delta, y, act, want_dbias=False)
-                dz = (dz_f.float() + (delta if rest is None else rest).float()).to(dz_f.dtype)
-                db = D.colsum(dz) if has_bias else None
+            dz, db = fused[2], fused[3]
         else:
             g = g.to(xc.dtype)
             # dz = g * act'(y) and the bias gradient in one pass (krs_dense_act_bwd)
@@ -538,11 +538,12 @@ class DenseFn(torch.autograd.Function):
                 up.fused = (dx, dx._version, dz_low, db_low, task, defer)
             elif _dense_fusable_below(ctx.dense_up, dz, x_dt, task):
                 # x is the output of a Dense layer: its activation backward and bias gradient ride in this product's epilogue;
-                # what goes back to autograd is that layer's dz (its backward recognises it)
+                # what goes back to autograd is dx itself, the true dL/dy of that output (its backward recognises it)
                 below = ctx.dense_up
                 act_low, bias_low = below.lower
-                dx, db_low = D.gemm_dense_bwd(dz, kc, xc, act_low, want_dbias=bias_low)     # (xc IS the lower layer's output y)
-                below.fused = (dx, dx._version, db_low, task)
+                # (xc IS the lower layer's output y)
+                dz_low, db_low, dx = D.gemm_dense_bwd(dz, kc, xc, act_low, want_dbias=bias_low, want_g=True)
+                below.fused = (dx, dx._version, dz_low, db_low, task)
             else:
                 dx, _ = D.gemm(dz, kc, b_is_nk=True)                               # [B, in]
                 dx = dx.to(x_dt)

@@ -754,12 +754,14 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_glds_kernel(const GemmParams p
 // stack neither writes nor this launch reads a [M, N] matrix for it (that one sum is rounded once instead of twice);
 // 3: no dL/dx0 at all from this launch (the caller hands u to the NEXT launch as its u_upper: a Dense layer above a stack).
 // X0 = false: the DENSE form (krs_gemm_cross_bwd with x0 = NULL, round 6) -- the layer below is a Dense layer, dz = G act'(y)
-// with y in the place of u, no x0 stream, no dL/dx0, and G itself is not stored (nobody reads the raw data gradient of a
-// Dense output): two streams (y in, dz out) instead of krs_dense_act_bwd's three behind a stored and re-read G.
-template <int DX0, bool HAS_R, bool X0 = true>
+// with y in the place of u, no x0 stream, no dL/dx0.  STORE_G: G is stored as well (the caller passed g_out: autograd hands
+// G, the true dL/dy, to whoever observes that output); without it two streams (y in, dz out) instead of krs_dense_act_bwd's
+// three behind a stored and re-read G.
+template <int DX0, bool HAS_R, bool X0 = true, bool STORE_G = true>
 __device__ __forceinline__ void gemm_epilogue_wave128_crossbwd(const GemmParams& p, f32x16 (&acc)[2][2][2], float* stage,
                                                                int64_t wm0, int64_t wn0, int64_t group) {
   static_assert(X0 || (DX0 == 3 && !HAS_R), "the dense form has no R and no dL/dx0");
+  static_assert(!X0 || STORE_G, "the cross forms always store G");
   const int lane = threadIdx.x & 63;
   const int frow = lane & 31, fhalf = lane >> 5;
   constexpr int SST = 68;
@@ -824,7 +826,7 @@ __device__ __forceinline__ void gemm_epilogue_wave128_crossbwd(const GemmParams&
       // G as it is stored (one rounding) is what everything below sees
       const uint4 gq = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
                                   pack_bf16x2(v[6], v[7]));
-      if constexpr (X0) {
+      if constexpr (STORE_G) {
         const u32x4 gs = {gq.x, gq.y, gq.z, gq.w};
         __builtin_nontemporal_store(gs, reinterpret_cast<u32x4*>(reinterpret_cast<uint16_t*>(p.c) + gm * p.ldc + gn));
       }
@@ -1201,9 +1203,9 @@ __global__ __launch_bounds__(512) void gemm_pp256_kernel(const GemmParams p, int
   lds_dma_retired<NPF>();
   float* stage_f = reinterpret_cast<float*>(smem) + wave * (32 * 68);
   if constexpr (EPI >= 3) {   // 3: + R, 4: + R, dx0 accumulates, 5: no R, 6: no R, dx0 accumulates, 7: + R, dx0 = R u_upper + ...,
-                              // 8: no R, no dx0, 9: the dense form (no x0, no R, no dx0, G not stored)
-    gemm_epilogue_wave128_crossbwd<(EPI == 4 || EPI == 6) ? 1 : (EPI == 7 ? 2 : ((EPI == 8 || EPI == 9) ? 3 : 0)),
-                                   EPI == 3 || EPI == 4 || EPI == 7, EPI != 9>(
+                              // 8: no R, no dx0, 9: the dense form (no x0, no R, no dx0, G not stored), 10: the dense form, G stored
+    gemm_epilogue_wave128_crossbwd<(EPI == 4 || EPI == 6) ? 1 : (EPI == 7 ? 2 : (EPI >= 8 ? 3 : 0)),
+                                   EPI == 3 || EPI == 4 || EPI == 7, EPI < 9, EPI != 9>(
         p, acc, stage_f, m0 + wm * 128, n0 + wn * 64, (m0 >> 8) * 2 + wm);
     return;
   }
@@ -1398,8 +1400,8 @@ __global__ __launch_bounds__(512) void gemm_pp64_kernel(const GemmParams p, int 
   lds_dma_retired<NPF>();
   float* stage_f = reinterpret_cast<float*>(smem) + wave * (32 * 68);
   if constexpr (EPI >= 3) {
-    gemm_epilogue_wave128_crossbwd<(EPI == 4 || EPI == 6) ? 1 : (EPI == 7 ? 2 : ((EPI == 8 || EPI == 9) ? 3 : 0)),
-                                   EPI == 3 || EPI == 4 || EPI == 7, EPI != 9>(
+    gemm_epilogue_wave128_crossbwd<(EPI == 4 || EPI == 6) ? 1 : (EPI == 7 ? 2 : (EPI >= 8 ? 3 : 0)),
+                                   EPI == 3 || EPI == 4 || EPI == 7, EPI < 9, EPI != 9>(
         p, acc, stage_f, m0 + wm * 128, n0 + wn * 64, (m0 >> 8) * 2 + wm);
     return;
   }
@@ -2014,16 +2016,29 @@ extern "C" size_t krs_gemm_cross_bwd_workspace_bytes(int64_t m, int64_t n) {
   return std::max(krs_colsum_workspace_bytes(m, n), (size_t)(2 * ceil_div(m, 256)) * (size_t)n * sizeof(float));
 }
 
+// which route the calling thread's last krs_gemm_cross_bwd took (krs_gemm_cross_bwd_last_route)
+static thread_local int cb_route = KRS_CROSS_BWD_NONE, cb_epilogue = 0;
+
+extern "C" int krs_gemm_cross_bwd_last_route(int* epilogue) {
+  if (epilogue) *epilogue = cb_epilogue;
+  return cb_route;
+}
+
 extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb, const void* r, int64_t ldr,
                                   float beta, void* g_out, int64_t ldg, const void* x0, const void* u, void* dz,
                                   void* dx0, int64_t ld, int dx0_accumulate, const void* u_upper, int fold_direct,
                                   float* dbias, int64_t m, int64_t n, int64_t k, int act, int dtype, void* workspace,
                                   size_t workspace_bytes, void* stream) {
+  cb_route = KRS_CROSS_BWD_NONE; cb_epilogue = 0;
   const bool dense_form = x0 == nullptr;    // the layer below is a Dense layer: dz = G act'(u) (u = its saved output), dbias
-  KRS_REQUIRE(a && bt && u && dz && (dense_form || g_out), "krs_gemm_cross_bwd: null operand");
+  // (an empty product may come with NULL operands: a framework's empty tensors have no storage)
+  KRS_REQUIRE((a && bt && u && dz && (dense_form || g_out)) || m == 0 || n == 0, "krs_gemm_cross_bwd: null operand");
   KRS_REQUIRE(!dense_form || (!r && !dx0 && !dx0_accumulate && !u_upper && !fold_direct),
               "krs_gemm_cross_bwd: the dense form (x0 = NULL) takes no R, dx0, u_upper or fold_direct");
-  if (dense_form && !g_out) { g_out = dz; ldg = ld; }    // (never written by the fused form; the two-call form passes through it)
+  // dense form: G is stored only where the caller asked for it (g_out != NULL), by either route; without g_out the fused
+  // route writes dz alone and the two-call route lands G in dz's buffer and applies the derivative in place
+  const bool store_g = g_out != nullptr;
+  if (dense_form && !g_out) { g_out = dz; ldg = ld; }
   if (!r) { ldr = n; beta = 0.0f; }
   KRS_REQUIRE(dx0 || (!r && !dx0_accumulate && !u_upper && !fold_direct),
               "krs_gemm_cross_bwd: dx0 = NULL (the term is left to the next launch's u_upper) is the form without R");
@@ -2031,10 +2046,13 @@ extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, in
               "krs_gemm_cross_bwd: u_upper (dx0 = R * u_upper + ...) needs R with beta = 1 and no dx0 to accumulate into");
   KRS_REQUIRE(dtype == KRS_BF16 || dtype == KRS_F32, "krs_gemm_cross_bwd: bad dtype");
   KRS_REQUIRE(m >= 0 && n >= 0 && k > 0 && ld >= n && ldg >= n && ldr >= n, "krs_gemm_cross_bwd: bad sizes");
-  if (dbias) KRS_REQUIRE(workspace && workspace_bytes >= krs_gemm_cross_bwd_workspace_bytes(m, n),
+  if (dbias) KRS_REQUIRE(workspace_bytes >= krs_gemm_cross_bwd_workspace_bytes(m, n) && (workspace || m == 0 || n == 0),
                          "krs_gemm_cross_bwd: workspace too small (krs_gemm_cross_bwd_workspace_bytes)");
-  if (m == 0 || n == 0) return KRS_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (m == 0 || n == 0) {   // (the column sums over no rows are zeros)
+    if (dbias && n > 0) KRS_HIP(hipMemsetAsync(dbias, 0, (size_t)n * sizeof(float), st));
+    return KRS_OK;
+  }
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const bool fused = dtype == KRS_BF16 && gemm_pipe() != 0 && m >= 256 && n >= 256 && k >= 256 && k % 64 == 0 &&
                      ceil_div(m, 256) * ceil_div(n, 256) >= 192 && n % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 &&
@@ -2042,6 +2060,7 @@ extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, in
                      (!x0 || al16(x0)) && al16(u) && al16(dz) && (!dx0 || al16(dx0)) && (!u_upper || al16(u_upper));
   if (!fused) {
     // any other shape / dtype: the two calls this entry stands for
+    cb_route = KRS_CROSS_BWD_TWO_CALL;
     krs_gemm_epilogue ep;
     memset(&ep, 0, sizeof(ep));
     ep.r = r; ep.ldr = ldr; ep.beta = beta;
@@ -2076,6 +2095,7 @@ extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, in
 #define KRS_CB_LAUNCH(EP)                                                                              \
   {                                                                                                    \
     auto kern = gemm_pp256_kernel<false, 4, EP>;                                                       \
+    cb_route = KRS_CROSS_BWD_PP256; cb_epilogue = EP;                                                  \
     static bool attr_set = false;                                                                      \
     if (!attr_set) {                                                                                   \
       KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                 \
@@ -2089,6 +2109,7 @@ extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, in
 #define KRS_CB64_LAUNCH(EP)                                                                            \
   {                                                                                                    \
     auto kern = gemm_pp64_kernel<EP>;                                                                  \
+    cb_route = KRS_CROSS_BWD_PP64; cb_epilogue = EP;                                                   \
     static bool attr_set = false;                                                                      \
     if (!attr_set) {                                                                                   \
       KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                 \
@@ -2097,8 +2118,10 @@ extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, in
     }                                                                                                  \
     hipLaunchKernelGGL(kern, grid256, dim3(512), pp64::NSLOT * pp64::SLOT, st, p, nt_);                \
   }
-    if (dense_form) KRS_CB64_LAUNCH(9)
-    else if (u_upper) KRS_CB64_LAUNCH(7)
+    if (dense_form) {
+      if (store_g) KRS_CB64_LAUNCH(10)
+      else KRS_CB64_LAUNCH(9)
+    } else if (u_upper) KRS_CB64_LAUNCH(7)
     else if (r) {
       if (dx0_accumulate) KRS_CB64_LAUNCH(4)
       else KRS_CB64_LAUNCH(3)
@@ -2112,8 +2135,10 @@ extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, in
     if (dbias) return finish_colsum(p.f_partial, 2 * ceil_div(m, 256), n, dbias, st);
     return KRS_OK;
   }
-  if (dense_form) KRS_CB_LAUNCH(9)
-  else if (u_upper) KRS_CB_LAUNCH(7)
+  if (dense_form) {
+    if (store_g) KRS_CB_LAUNCH(10)
+    else KRS_CB_LAUNCH(9)
+  } else if (u_upper) KRS_CB_LAUNCH(7)
   else if (r) {
     if (dx0_accumulate) KRS_CB_LAUNCH(4)
     else KRS_CB_LAUNCH(3)

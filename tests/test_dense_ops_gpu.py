@@ -483,14 +483,17 @@ def test_fused_data_gradient_and_cross_backward_equals_the_two_calls(acc, fold, 
                     D.gemm_cross_bwd(A, Bt, R, x0, u, act=a_id, want_dx0=False)
 
 
-# (k = 256, 320: whole 64-k blocks -> gemm_pp64_kernel, the 64-k ring of round 6; k = 288: not -> gemm_pp256_kernel)
-@pytest.mark.parametrize("m,n,k", [(16384 + 72, 768 + 40, 256), (24576, 512, 320), (16384 + 72, 768 + 40, 288)])
-def test_fused_cross_backward_every_epilogue_form_against_the_two_call_form_at_ragged_shapes(m, n, k):
+# (pipeline 4: whole 64-k blocks -> gemm_pp64_kernel, the 64-k ring of round 6; pipeline 5 -> gemm_pp256_kernel, the 32-k
+#  ring -- the fused gate needs k % 64 == 0 for both)
+@pytest.mark.parametrize("m,n,k,pipe", [(16384 + 72, 768 + 40, 256, 4), (24576, 512, 320, 4), (16384 + 72, 768 + 40, 320, 5)],
+                         ids=["16456-808-256", "24576-512-320", "16456-808-320-pipe5"])
+def test_fused_cross_backward_every_epilogue_form_against_the_two_call_form_at_ragged_shapes(m, n, k, pipe):
     """krs_gemm_cross_bwd's fused ring kernel (EPI 3 .. 8) against the documented two-call form, which
     krs_gemm_set_option(KRS_GEMM_OPT_PIPELINE, 0) forces inside the same entry: m and n that are NOT multiples of the
     256-wide tile (partial tiles on both edges), with / without the residual, accumulating dx0, fold_direct, u_upper
-    (EPI 7) and dx0 = NULL (EPI 8), with and without an activation.  G, dz and dx0 bit for bit (EPI 7's dx0: the fused form
-    rounds R*u_upper + G*u once, the two calls twice -- one ulp of the larger term); dbias to fp32 summation order."""
+    (EPI 7) and dx0 = NULL (EPI 8), with and without an activation, on the ring kernel `pipe` selects (the route and
+    epilogue each call took are asserted).  G, dz and dx0 bit for bit (EPI 7's dx0: the fused form rounds R*u_upper + G*u
+    once, the two calls twice -- one ulp of the larger term); dbias to fp32 summation order."""
     import ctypes as C
 
     from keras_rs_amd import _lib as L
@@ -511,13 +514,22 @@ def test_fused_cross_backward_every_epilogue_form_against_the_two_call_form_at_r
     def set_pipe(v):
         L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(v)), "krs_gemm_set_option")
 
+    def epilogue(form):
+        if form.get("u_upper") is not None:
+            return 7
+        if form["r"] is not None:
+            return 4 if form.get("acc") else 3
+        return 8 if not form.get("want_dx0", True) else (6 if form.get("acc") else 5)
+
     try:
         for act in (L.ACT_NONE, L.ACT_RELU):
             for form in forms:
-                set_pipe(4)
+                set_pipe(pipe)
                 G, dz, dx0, db = run(form, act)
+                assert D.last_cross_bwd_route() == ({4: "pp64", 5: "pp256"}[pipe], epilogue(form)), form
                 set_pipe(0)
                 G2, dz2, dx02, db2 = run(form, act)
+                assert D.last_cross_bwd_route() == ("two_call", 0)
                 tag = (act, {k_: (v is not None if k_ in ("r", "u_upper") else v) for k_, v in form.items()})
                 assert torch.equal(G, G2), tag
                 assert torch.equal(dz, dz2), tag

@@ -1196,11 +1196,31 @@ def test_dense_layer_above_a_cross_stack_runs_the_top_layers_elementwise_backwar
         D.gemm_cross_bwd = real
 
 
-def test_dense_above_a_cross_stack_whose_top_output_has_a_second_consumer():
+def _spy_cross_bwd_routes(monkeypatch):
+    """Records (route, epilogue) of every krs_gemm_cross_bwd the autograd functions make (dense_ops.last_cross_bwd_route,
+    read on the thread that made the call: the backward pass runs on autograd's device thread)."""
+    from keras_rs_amd import dense_ops as D
+
+    routes = []
+    for name in ("gemm_cross_bwd", "gemm_dense_bwd"):
+        real = getattr(D, name)
+
+        def spy(*a, _real=real, **kw):
+            out = _real(*a, **kw)
+            routes.append(D.last_cross_bwd_route())
+            return out
+
+        monkeypatch.setattr(D, name, spy)
+    return routes
+
+
+@pytest.mark.parametrize("units", [64, 256])
+def test_dense_above_a_cross_stack_whose_top_output_has_a_second_consumer(units, monkeypatch):
     """The Dense layer's launch ran the top cross layer's elementwise backward and LEFT its term of dL/dx0 to that layer's
     own product (deferred); when the top output has another consumer, the gradient autograd hands that layer is not the
     Dense layer's G: the layer must notice (another tensor / a moved version) and redo its backward from the summed
-    gradient.  Same gradients as the unfused passes, to the rounding of the two ways of summing."""
+    gradient.  Same gradients as the unfused passes, to the rounding of the two ways of summing.  Dense(256): its
+    data-gradient product (k = 256) takes the fused ring kernel (route asserted); Dense(64) the two-call form."""
     from keras_rs_amd import autograd as A
     from keras_rs_amd.layers import base as kl_base
 
@@ -1215,7 +1235,7 @@ def test_dense_above_a_cross_stack_whose_top_output_has_a_second_consumer():
             cross = [kl.FeatureCross(projection_dim=p, kernel_initializer=kl_base.GlorotUniform(seed=90 + i),
                                      bias_initializer=kl_base.RandomUniform(-0.1, 0.1, seed=95 + i),
                                      dtype="mixed_bfloat16") for i in range(2)]
-            mlp = kl.Dense(64, activation="relu", kernel_initializer=kl_base.GlorotUniform(seed=99), dtype="mixed_bfloat16")
+            mlp = kl.Dense(units, activation="relu", kernel_initializer=kl_base.GlorotUniform(seed=99), dtype="mixed_bfloat16")
             x = x0.clone().requires_grad_()
             xl = x
             for layer in cross:
@@ -1228,25 +1248,35 @@ def test_dense_above_a_cross_stack_whose_top_output_has_a_second_consumer():
         finally:
             A.FUSE_CROSS_BWD = old
 
-    a, b = run(True), run(False)
+    routes = _spy_cross_bwd_routes(monkeypatch)
+    a = run(True)
+    if units == 256:    # the Dense layer's launch (no dL/dx0: epilogue 8), then the top cross layer's (u_upper: 7)
+        assert routes[0] == ("pp64", 8), routes
+    else:
+        assert routes[0] == ("two_call", 0), routes
+    b = run(False)
     for (name, u), (_, v) in zip(a, b):
         scale = float(v.float().abs().max())
         torch.testing.assert_close(u.float(), v.float(), rtol=2.0 ** -6, atol=2.0 ** -7 * scale, msg=lambda m: f"{name}: {m}")
 
 
+@pytest.mark.parametrize("units", [(512, 512, 256, 1), (768, 768, 512, 1)])
 @pytest.mark.parametrize("policy,acts", [("mixed_bfloat16", ("relu", "relu", "relu", "sigmoid")), ("float32", ("tanh", "relu", None, "sigmoid"))])
-def test_stacked_dense_layers_run_the_lower_layers_activation_backward_in_the_upper_data_gradient(policy, acts):
-    """Round 6 (review item 5): the data-gradient product dx = dz K^T of a Dense layer on top of another Dense layer runs that
-    layer's dz = dL/dy * act'(y) and bias gradient in its epilogue (krs_gemm_cross_bwd, dense form: dL/dy is never written).
-    Every weight / bias / input gradient of a 4-layer stack (units that take the fused ring kernel in bf16 and the two-call
-    form in fp32 / for the 1-unit layer) against the same stack with the fusion switched off: dz and dx bit for bit -- the
-    derivative is applied to the same once-rounded product --, bias gradients to fp32 summation order."""
+def test_stacked_dense_layers_run_the_lower_layers_activation_backward_in_the_upper_data_gradient(policy, acts, units,
+                                                                                                 monkeypatch):
+    """Round 6 (review item 5): the data-gradient product G = dz K^T of a Dense layer on top of another Dense layer runs that
+    layer's dz = dL/dy * act'(y) and bias gradient in its epilogue (krs_gemm_cross_bwd, dense form; G, the true dL/dy, is
+    stored too and is what autograd receives).  Every weight / bias / input gradient of a 4-layer stack against the same
+    stack with the fusion switched off: dz and dx bit for bit -- the derivative is applied to the same once-rounded
+    product --, bias gradients to fp32 summation order.  Units (768, 768, 512, 1) at B = 16424: the products over the
+    768-wide layers have 195 tiles of 256 x 256 and take the fused ring kernel in bf16 (route asserted); (512, 512, 256, 1)
+    has at most 130 and runs the two-call form, as does fp32."""
     from keras_rs_amd import autograd as A
     from keras_rs_amd.layers import base as kl_base
 
     kl = _layers()
     g = torch.Generator(device=DEV).manual_seed(41)
-    B, d, units = 16384 + 40, 768, (512, 512, 256, 1)
+    B, d = 16384 + 40, 768
     dt = torch.bfloat16 if policy == "mixed_bfloat16" else torch.float32
     x0 = (torch.randn(B, d, device=DEV, generator=g) * 0.5).to(dt)
     gy = (torch.randn(B, 1, device=DEV, generator=g) * 0.1).to(dt)
@@ -1267,7 +1297,13 @@ def test_stacked_dense_layers_run_the_lower_layers_activation_backward_in_the_up
         finally:
             A.FUSE_DENSE_BWD = old
 
-    a, b = run(True), run(False)
+    routes = _spy_cross_bwd_routes(monkeypatch)
+    a = run(True)
+    # the products over layers 1 and 0 run last; the 1-unit layer's product (k = 1) runs the two-call form
+    fused = dt == torch.bfloat16 and units[0] == 768
+    assert len(routes) >= 2 and routes[-2:] == [("pp64", 10) if fused else ("two_call", 0)] * 2, routes
+    assert all(r == ("two_call", 0) for r in routes[:-2]), routes
+    b = run(False)
     for (name, u), (_, v) in zip(a, b):
         if name.endswith("bias"):
             torch.testing.assert_close(u, v, rtol=1e-4, atol=1e-4 * float(v.abs().max() + 1e-6), msg=lambda m: f"{name}: {m}")
@@ -1293,10 +1329,13 @@ def test_stacked_dense_layers_run_the_lower_layers_activation_backward_in_the_up
         assert float(close.double().mean()) > 0.999 and float((got - ref).abs().max()) < 1e-3
 
 
-def test_a_dense_output_with_a_second_consumer_or_a_watcher_still_gets_the_right_gradient():
-    """The upper Dense layer hands autograd the LOWER layer's dz instead of dL/dy.  With a second consumer of that output the
-    engine sums the other gradient into it: the lower backward notices (another tensor) and sends the difference through the
-    derivative.  With retain_grad() on the output nothing is fused and .grad is the real dL/dy."""
+@pytest.mark.parametrize("lo_units", [512, 768])
+def test_a_dense_output_with_a_second_consumer_or_a_watcher_still_gets_the_right_gradient(lo_units, monkeypatch):
+    """The upper Dense layer hands autograd G, the true dL/dy, and leaves the lower layer's dz on the relay.  With a second
+    consumer of that output the engine sums the other gradient into G: the lower backward notices (another tensor or a
+    moved version) and runs its own derivative on the sum.  With retain_grad() on the output nothing is fused and .grad is
+    the real dL/dy.  Lower width 768 at B = 16384: the upper product has 192 tiles and takes the fused ring kernel (route
+    asserted); width 512 (128 tiles) the two-call form."""
     from keras_rs_amd import autograd as A
     from keras_rs_amd.layers import base as kl_base
 
@@ -1304,11 +1343,12 @@ def test_a_dense_output_with_a_second_consumer_or_a_watcher_still_gets_the_right
     g = torch.Generator(device=DEV).manual_seed(43)
     B, d = 16384, 512
     x0 = (torch.randn(B, d, device=DEV, generator=g) * 0.5).to(torch.bfloat16)
+    routes = _spy_cross_bwd_routes(monkeypatch)
 
     def run(fuse, watch):
         old, A.FUSE_DENSE_BWD = A.FUSE_DENSE_BWD, fuse
         try:
-            lo = kl.Dense(512, activation="sigmoid", kernel_initializer=kl_base.GlorotUniform(seed=81), dtype="mixed_bfloat16")
+            lo = kl.Dense(lo_units, activation="sigmoid", kernel_initializer=kl_base.GlorotUniform(seed=81), dtype="mixed_bfloat16")
             hi = kl.Dense(256, activation="relu", kernel_initializer=kl_base.GlorotUniform(seed=82), dtype="mixed_bfloat16")
             x = x0.clone().requires_grad_()
             y = lo(x)
@@ -1323,7 +1363,10 @@ def test_a_dense_output_with_a_second_consumer_or_a_watcher_still_gets_the_right
             A.FUSE_DENSE_BWD = old
 
     for watch in (False, True):
-        a, b = run(True, watch), run(False, watch)
+        del routes[:]
+        a = run(True, watch)
+        assert routes == ([] if watch else [("pp64", 10) if lo_units == 768 else ("two_call", 0)]), routes
+        b = run(False, watch)
         for (name, u), (_, v) in zip(a, b):
             if watch:
                 assert torch.equal(u, v), name       # nothing was fused: the same launches

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- the hot path's headline benchmark (see BASELINE.json / SURVEY.md section 8d).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one synthetic batch, through the drop-in layers
@@ -14,20 +14,29 @@ A "step" is one pass of the hot path over one synthetic batch, through the drop-
 
 Workload C3 (DLRM-small): 26 tables x 1,000,000 rows x 128, batch 65,536 global, bf16 tables
 and activations with fp32 accumulation, fp32 master weights for the dense kernels.  SURVEY.md
-section 8d defines C3 with two bag-length lists; both are measured in one run: the primary one
-(`value`, `ms_per_step`, `roofline`) uses the ml_perf DLRM lengths (sum L = 214, i.e. a real
-gather+POOL; examples/ml_perf/configs/v6e_8.py), the L = 1 variant is reported under `also`
+section 8d defines C3 with two bag-length lists: the primary one (`value`, `ms_per_step`,
+`roofline`) uses the ml_perf DLRM lengths (sum L = 214, i.e. a real gather+POOL;
+examples/ml_perf/configs/v6e_8.py), the L = 1 variant is reported under `also` by --full runs
 (`--hotness 1` swaps them).
 With N > 1 the tables are MOD row-sharded over the ranks (C4), B_local = 65,536 / N.
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the
+K steps, writes --dump-outputs and prints the line.  `--full` adds, all of it BEHIND the timed
+steps: the sustained steps (`--sustained-steps`, default 500), the probe steps (`roofline_step`,
+`--probe-steps`, default 3), the isolated K1 launches (`roofline`), the other bag-length leg
+(`also`), the C2 leg in a process of its own (`also_c2`, skipped by --no-c2) and the host-CPU
+baseline (`cpu_baseline`, skipped by --no-cpu-baseline).  Sharded runs keep their self-check
+(`parity`) and graph-replayed leg either way: the check's step comes before the timed steps, whose
+tables it updates, and the replayed leg may become `value`.
 
 The K timed steps run with Python's cyclic garbage collector switched off (reference counting still frees every
 tensor): a full collection inside the region starves the GPU for a whole step on a fresh box.
 
 The LAST stdout line (rank 0) is ONE JSON object below 4 KB (`compact_line`: the driver keeps an ~8 KB tail of stdout + stderr)
-with `value` = whole-job embedding lookups/s, `ms_per_step` = the DCN fwd+bwd step time, a `roofline` object for K1 measured
-live with HIP events on the launch stream (priced at its in-step duration, the isolated launch beside it), `roofline_dominant`
-(the kernel family that costs the step the most time) and a `cpu_baseline` object (the reference's op composition on this
-box's host cores on a bounded sample of the same workload).  Everything else the run measured -- `roofline_step` per kernel
+with `value` = whole-job embedding lookups/s, `ms_per_step` = the DCN fwd+bwd step time and, from a --full run, a `roofline`
+object for K1 measured live with HIP events on the launch stream (priced at its in-step duration, the isolated launch beside
+it), `roofline_dominant` (the kernel family that costs the step the most time) and a `cpu_baseline` object (the reference's op
+composition on this box's host cores on a bounded sample of the same workload).  Everything else the run measured -- `roofline_step` per kernel
 family, the L = 1 and C2 legs, per-step times, the sharded run's `phases` / `graph_leg` / `parity` -- goes to the side file the
 line names under `detail` (`--detail`, default ./bench_detail.json).
 
@@ -62,7 +71,7 @@ MFMA_F32_PEAK = 157.3e12  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 (fp32 in
 DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: the sample of one step's results, all files together
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
@@ -82,7 +91,7 @@ def parse():
     ap.add_argument("--id-skew", type=float, default=0.0, metavar="E",
                     help="power-law ids: id = perm(floor(V * u^E)) with a fixed affine permutation of the rows "
                          "(E = 4: 1 %% of the rows draw 32 %% of the lookups); 0 = uniform ids")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` leg")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the MOD-sharded embedding path even at N = 1 (dry run of the multi-GPU code)")
     ap.add_argument("--cpu-sample-batch", type=int, default=2048)
@@ -95,15 +104,20 @@ def parse():
     ap.add_argument("--exchange", choices=["static", "exact"], default="static",
                     help="sharded runs: 'static' = fixed-capacity blocks, no host wait in the step (the reference's "
                          "max_ids_per_partition contract); 'exact' = data-dependent sizes through one host wait")
-    ap.add_argument("--probe-steps", type=int, default=3,
+    ap.add_argument("--full", action="store_true",
+                    help="run everything else the benchmark measures, behind the headline figure: the sustained steps, the "
+                         "probe steps, the isolated K1 launches (`roofline`), the other bag-length leg (`also`), the C2 leg "
+                         "and the host-CPU baseline.  Without it a run sets up, warms up, times the K steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--probe-steps", type=int, default=None,
                     help="extra steps after each timed region with event spans around the C-ABI calls (K2 apply, GEMMs): "
-                         "the `roofline_step` entries; 0 = off")
-    ap.add_argument("--sustained-steps", type=int, default=500,
+                         "the `roofline_step` entries; 0 = off (default: 3 with --full, 0 without)")
+    ap.add_argument("--sustained-steps", type=int, default=None,
                     help="back-to-back steps run BEHIND the K timed steps (HIP events at every step boundary): the "
-                         "power-capped steady state, reported under `sustained`; 0 = off")
+                         "power-capped steady state, reported under `sustained`; 0 = off (default: 500 with --full, 0 without)")
     ap.add_argument("--no-c2", action="store_true",
-                    help="skip the `also_c2` leg (BASELINE.json configs[1]: 8 tables x 100k x 64 fp32, 3 full-rank FeatureCross, "
-                         "batch 8192, fp32)")
+                    help="with --full: skip the `also_c2` leg (BASELINE.json configs[1]: 8 tables x 100k x 64 fp32, 3 full-rank "
+                         "FeatureCross, batch 8192, fp32)")
     ap.add_argument("--c2-leg", action="store_true",
                     help="(internal) run ONLY the C2 leg and print its object: the default run starts this in a process of its "
                          "own, so that the leg's graph capture cannot take the headline line with it")
@@ -154,7 +168,11 @@ def parse():
     ap.add_argument("--cpu-pools", default="16", metavar="LIST",
                     help="intra-op pool sizes of the torch-CPU leg of cpu_baseline, comma separated, each capped at the host's "
                          "thread count (BASELINE.md section 4 records the 256- and 64-thread pools as 130x / 2.4x SLOWER than 16)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.probe_steps is None:
+        a.probe_steps = 3 if a.full else 0
+    if a.sustained_steps is None:
+        a.sustained_steps = 500 if a.full else 0
     if a.criteo_vocab:
         if a.tables != len(CRITEO_VOCABS):
             ap.error("--criteo-vocab needs --tables 26")
@@ -221,6 +239,40 @@ def _free_port():
         return sk.getsockname()[1]
 
 
+class TableDraws:
+    """The tables' initial values drawn on the host a few tables AHEAD of the layer that asks for them, on a small thread
+    pool.  RandomUniform's host draw is a single-threaded torch.rand (about half a second per 1 M x 128 table: most of a
+    plain run's set-up when the layer draws the 26 tables one after the other).  Each draw is the table's own initializer
+    called as the layer would call it (same generator, seed and arithmetic), so the tables hold the same bits; about
+    `depth` fp32 host copies are held at a time.  `table(t)` is the initializer to give table t: a callable
+    (shape, dtype) -> fp32 host tensor, which the layer casts and moves as RandomUniform does."""
+
+    def __init__(self, inits, shapes, depth=4):
+        from concurrent.futures import ThreadPoolExecutor
+
+        self.inits, self.shapes, self.depth = inits, [tuple(s) for s in shapes], depth
+        self.pool = ThreadPoolExecutor(max_workers=depth)
+        self.draws, self.started = [None] * len(inits), 0
+        self._start_until(depth)
+
+    def _start_until(self, end):
+        while self.started < min(end, len(self.inits)):
+            self.draws[self.started] = self.pool.submit(self.inits[self.started], self.shapes[self.started])
+            self.started += 1
+
+    def take(self, t, shape):
+        self._start_until(t + 1 + self.depth)
+        draw, self.draws[t] = self.draws[t], None
+        if self.started == len(self.inits) and all(d is None for d in self.draws):
+            self.pool.shutdown(wait=False)      # (every draw is handed out: the threads exit as the last one ends)
+        if draw is None or tuple(shape) != self.shapes[t]:      # (not the call it was drawn for: draw it here)
+            return self.inits[t](tuple(shape))
+        return draw.result()
+
+    def table(self, t):
+        return lambda shape, dtype=None: self.take(t, shape)
+
+
 class Model(torch.nn.Module):
     """Embedding -> [DotInteraction] -> DCN cross stack, from the drop-in layers."""
 
@@ -235,11 +287,15 @@ class Model(torch.nn.Module):
         if a.rowwise_adagrad:   # opt-in variant, NOT the reference's optimizer (one accumulator per row)
             opt = kl.RowwiseAdagrad(learning_rate=0.0034, initial_accumulator_value=0.1)
         feats = {}
+        # the 40 M-row tables of C5 are drawn on the device, they never exist in host memory
+        inits = [base.RandomUniform(-0.05, 0.05, seed=1337 + t, device_rng=bool(a.criteo_vocab)) for t in range(a.tables)]
+        if world == 1 and not a.force_sharded and not a.criteo_vocab:
+            # (the unsharded layer draws every table whole, in order: host draws run ahead on a thread pool, same bits)
+            ahead = TableDraws(inits, [(v, a.dim) for v in a.vocabs])
+            inits = [ahead.table(t) for t in range(a.tables)]
         for t in range(a.tables):
-            # the 40 M-row tables of C5 are drawn on the device, they never exist in host memory
-            init = base.RandomUniform(-0.05, 0.05, seed=1337 + t, device_rng=bool(a.criteo_vocab))
             tc = kl.TableConfig(name=f"cat_{t}", vocabulary_size=a.vocabs[t], embedding_dim=a.dim,
-                                initializer=init, optimizer=opt,
+                                initializer=inits[t], optimizer=opt,
                                 combiner="sum", placement="sparsecore")
             feats[f"cat_{t:02d}_id"] = kl.FeatureConfig(f"cat_{t}", tc, (a.batch // world, hots[t]),
                                                        (a.batch // world, a.dim))
@@ -492,11 +548,11 @@ def cpu_baseline(a, hots):
 
 
 def measure(model, a, hots, world, rank, dev, b_local, steps, warmup, opt_box, loader=None, probe_steps=0,
-            sustained_steps=0, dump=None):
+            sustained_steps=0, dump=None, k1_probe=True):
     """Times `steps` steps of the hot path for one bag-length list.  Returns a dict: `elapsed` (wall seconds of the
-    timed region, max over ranks), `k1_s` (one K1 launch, events), `step_ms` (per-step GPU time of the timed steps,
-    from events recorded at the step boundaries) and, with `probe_steps`, `probe` (in-step kernel spans of that many
-    EXTRA steps run after the timed region; keras_rs_amd/probe.py).
+    timed region, max over ranks), `k1_s` (one K1 launch, events, behind the timed region; None without `k1_probe`),
+    `step_ms` (per-step GPU time of the timed steps, from events recorded at the step boundaries) and, with `probe_steps`,
+    `probe` (in-step kernel spans of that many EXTRA steps run after the timed region; keras_rs_amd/probe.py).
     With `loader`, every step takes its preprocessed ids from it (host-resident inputs).
     With `dump` (a dict), the last timed step keeps its outputs and `dump` receives dump_sample() of that step, taken
     behind the timed region and before anything else runs a step."""
@@ -656,15 +712,15 @@ def measure(model, a, hots, world, rank, dev, b_local, steps, warmup, opt_box, l
     # K1 launch duration, measured live with events on the launch stream, BEHIND the timed steps (one krs_embed_bag_fwd
     # launch per event pair).  It used to sit between the warm-up and the timed steps: its blocker copies left the first
     # timed steps 0.3-1.8 ms slow (11.99, 10.46, then 10.1-10.2 ms in `step_stats.each_ms`), i.e. the warm-up was undone.
-    k1_s = None
-    if sharded:
+    k1_s, call = None, None
+    if k1_probe and sharded:
         # sharded run: the embedding call contains the all-to-alls, so K1 is timed on its own in the form
         # the owner side runs it (row gather of this rank's share of the lookups from its shard)
         emb = model.embedding
         nloc = b_local * sum(hots)
         rows = torch.randint(0, emb.shard.shape[0], (nloc,), device=dev, dtype=torch.int32)
         call = lambda: emb.kernels.gather_rows(emb.shard.data, rows)   # noqa: E731
-    else:
+    elif k1_probe:
         # One K1 launch per event pair, through the thin op wrapper (krs_embed_bag_fwd on the layer's own
         # tables / descriptors, same slab shape as the layer call).  A blocker kernel is queued first, so
         # the event pairs and launches are all enqueued while the GPU is still busy: the interval between
@@ -676,19 +732,20 @@ def measure(model, a, hots, world, rank, dev, b_local, steps, warmup, opt_box, l
         slab = torch.empty((b_local, lead + n * a.dim), dtype=adt, device=dev)
         call = lambda: group.bags.forward(fi["ids"], b_local, hots=fi["hots"], offsets=fi["offsets"],   # noqa: E731
                                           out=slab[:, lead:])
-    for _ in range(3):
-        call()
-    torch.cuda.synchronize()
-    for _ in range(4):
-        gpu_block(dev, 3.0)  # launches are enqueued behind a busy GPU: events bracket the kernel alone
-        for _ in range(5):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+    if call is not None:
+        for _ in range(3):
             call()
-            e1.record()
-            k1_ev.append((e0, e1))
         torch.cuda.synchronize()
-    k1_s = float(np.median([e0.elapsed_time(e1) for e0, e1 in k1_ev])) * 1e-3
+        for _ in range(4):
+            gpu_block(dev, 3.0)  # launches are enqueued behind a busy GPU: events bracket the kernel alone
+            for _ in range(5):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                call()
+                e1.record()
+                k1_ev.append((e0, e1))
+            torch.cuda.synchronize()
+        k1_s = float(np.median([e0.elapsed_time(e1) for e0, e1 in k1_ev])) * 1e-3
     res = {"elapsed": elapsed, "k1_s": k1_s, "enqueue_s": enqueue_s, "step_ms": step_ms, "sustained": sustained}
     if probe_steps > 0:
         from keras_rs_amd import autograd as krs_autograd
@@ -1285,22 +1342,24 @@ def main():
     t_mark = time.perf_counter()
     dumped = {} if a.dump_outputs and rank == 0 else None
     r1 = measure(model, a, primary, world, rank, dev, b_local, a.steps, a.warmup, opt_box, probe_steps=a.probe_steps,
-                 sustained_steps=a.sustained_steps, dump=dumped)
+                 sustained_steps=a.sustained_steps, dump=dumped, k1_probe=a.full)
     wall["primary_leg"] = time.perf_counter() - t_mark
     if dumped is not None:
         write_dump(dumped, a.dump_outputs)
         dumped = None
-    t_mark = time.perf_counter()
-    # the other C3 bag-length list (SURVEY.md section 8d lists both), same tables and model, shorter run.  The
-    # shapes change (ids, plan workspace), so the leg gets its own warm-up of at least 5 steps: the caching
-    # allocator re-carves its blocks during the first steps after a shape change
-    sec_steps = max(3, a.steps // 2)
-    r2 = measure(model, a, secondary, world, rank, dev, b_local, sec_steps, max(5, a.warmup), opt_box,
-                 probe_steps=a.probe_steps)
-    wall["secondary_leg"] = time.perf_counter() - t_mark
-    elapsed, k1_s, elapsed2, k1_s2 = r1["elapsed"], r1["k1_s"], r2["elapsed"], r2["k1_s"]
-    c2 = None
-    want_c2 = not a.no_c2 and world == 1 and not a.force_sharded and not a.criteo_vocab and not a.graph
+    elapsed, k1_s = r1["elapsed"], r1["k1_s"]
+    r2 = None
+    if a.full:
+        t_mark = time.perf_counter()
+        # the other C3 bag-length list (SURVEY.md section 8d lists both), same tables and model, shorter run.  The
+        # shapes change (ids, plan workspace), so the leg gets its own warm-up of at least 5 steps: the caching
+        # allocator re-carves its blocks during the first steps after a shape change
+        sec_steps = max(3, a.steps // 2)
+        r2 = measure(model, a, secondary, world, rank, dev, b_local, sec_steps, max(5, a.warmup), opt_box,
+                     probe_steps=a.probe_steps)
+        wall["secondary_leg"] = time.perf_counter() - t_mark
+        elapsed2, k1_s2 = r2["elapsed"], r2["k1_s"]
+    want_c2 = a.full and not a.no_c2 and world == 1 and not a.force_sharded and not a.criteo_vocab and not a.graph
     host = None
     if a.host_inputs > 0 and world == 1 and not a.force_sharded:
         # ids start in host memory: a small pool of batches cycles through the loader threads, which
@@ -1316,7 +1375,8 @@ def main():
                 yield from pool
 
         loader = ThreadedDataLoader(model.embedding.preprocess, cycle(), num_workers=a.host_inputs, buffer_size=4)
-        el_h = measure(model, a, primary, world, rank, dev, b_local, a.steps, a.warmup, opt_box, loader=loader)["elapsed"]
+        el_h = measure(model, a, primary, world, rank, dev, b_local, a.steps, a.warmup, opt_box, loader=loader,
+                       k1_probe=False)["elapsed"]
         loader.stop()
         id_bytes = 4 * b_local * sum(primary)
         host = {"ms_per_step": el_h / a.steps * 1e3, "value": a.batch * sum(primary) / (el_h / a.steps),
@@ -1458,14 +1518,17 @@ def main():
                                         "note": "median GPU step minus the phases above: DotInteraction + cross stack forward / "
                                                 "backward, dense optimizer, launch gaps (the probe steps keep every span on one stream)"}
                 out["phases"] = ph
-            out["overflow_steps"] = int(r1.get("overflow_steps", 0)) + int(r2.get("overflow_steps", 0))
+            out["overflow_steps"] = sum(int(r.get("overflow_steps", 0)) for r in (r1, r2) if r is not None)
             if out["overflow_steps"]:
                 out["invalid"] = ("the static exchange dropped lookups in %d step(s) (capacity %s, largest per-owner need %s): "
                                   "`value` counts dropped lookups as work" % (out["overflow_steps"], ex.get("capacity"), ex.get("need")))
-        second = {"workload": "same tables / model, " + describe(secondary),
-                  "value": a.batch * sum(secondary) / (elapsed2 / sec_steps), "unit": "lookups/s",
-                  "ms_per_step": elapsed2 / sec_steps * 1e3, "steps": sec_steps, "warmup": max(5, a.warmup),
-                  "step_stats": step_stats(r2["step_ms"])}
+        legs = [(r1, out, primary)]
+        if r2 is not None:
+            second = {"workload": "same tables / model, " + describe(secondary),
+                      "value": a.batch * sum(secondary) / (elapsed2 / sec_steps), "unit": "lookups/s",
+                      "ms_per_step": elapsed2 / sec_steps * 1e3, "steps": sec_steps, "warmup": max(5, a.warmup),
+                      "step_stats": step_stats(r2["step_ms"])}
+            legs.append((r2, second, secondary))
         if k1_s is not None:
             n1 = "embed_gather_hot1 (K1 owner-side row gather of the sharded path, rank 0)" if sharded else k1_name(primary)
             n2 = n1 if sharded else k1_name(secondary)
@@ -1475,9 +1538,10 @@ def main():
                 return None if sharded or not e or not e["calls"] else e["ms_total"] / e["calls"] * 1e-3
 
             out["roofline"] = k1_roofline(a, primary, b_local, k1_s, n1, sharded, in_step(r1))
-            second["embed_fwd_lookups_per_s"] = vworld * b_local * sum(secondary) / k1_s2
-            second["roofline"] = k1_roofline(a, secondary, b_local, k1_s2, n2, sharded, in_step(r2))
-        for res, tgt, hots in ((r1, out, primary), (r2, second, secondary)):
+            if r2 is not None:
+                second["embed_fwd_lookups_per_s"] = vworld * b_local * sum(secondary) / k1_s2
+                second["roofline"] = k1_roofline(a, secondary, b_local, k1_s2, n2, sharded, in_step(r2))
+        for res, tgt, hots in legs:
             rs = roofline_step(a, hots, b_local, res)
             if rs:
                 tgt["roofline_step"] = rs
@@ -1485,7 +1549,8 @@ def main():
             dom = dominant_roofline(out.get("roofline_step"), single)
             if dom:
                 out[key] = dom
-        out["also"] = second
+        if r2 is not None:
+            out["also"] = second
         if host is not None:
             out["host_inputs"] = host
         if full is not None:
@@ -1525,7 +1590,7 @@ def main():
         info = {"attempted": True, "ok": False}
         try:
             a.graph, a._graph_used = True, False
-            rg = measure(model, a, primary, world, rank, dev, b_local, a.steps, max(a.warmup, 3), opt_box)
+            rg = measure(model, a, primary, world, rank, dev, b_local, a.steps, max(a.warmup, 3), opt_box, k1_probe=False)
             poll = getattr(model.embedding, "poll_exchange_stats", None)
             grew = bool(poll()) if poll is not None else False
             g_ms = rg["elapsed"] / a.steps * 1e3
@@ -1572,7 +1637,7 @@ def main():
             out["also_c2"] = {"error": "the C2 leg's process failed: " + repr(e)[:300]}
         out["wall_seconds"]["c2_leg_process"] = time.perf_counter() - t_mark
         t_mark = time.perf_counter()
-    if not a.no_cpu_baseline and world == 1 and not a.criteo_vocab:   # the host-CPU leg is timed on rank 0 of the single-GPU run only
+    if a.full and not a.no_cpu_baseline and world == 1 and not a.criteo_vocab:   # (rank 0 of the single-GPU run only)
         out["cpu_baseline"] = cpu_baseline(a, primary)
         out["wall_seconds"]["cpu_baseline"] = time.perf_counter() - t_mark
     out["wall_seconds"]["total_since_import"] = time.perf_counter() - T_START

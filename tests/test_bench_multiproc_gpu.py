@@ -27,7 +27,7 @@ def test_two_rank_bench_run_over_gloo():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--batch", "4096", "--vocab", "50000", "--sustained-steps", "4", "--detail", _detail_path()]
+           "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--batch", "4096", "--vocab", "50000", "--sustained-steps", "4", "--detail", _detail_path()]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -49,7 +49,7 @@ def test_the_self_check_of_the_sharded_line_has_teeth():
     and the line is marked invalid."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env["KRS_BENCH_PARITY_SABOTAGE"] = "1"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-sharded", "--steps", "2", "--warmup", "1",
            "--no-cpu-baseline", "--batch", "2048", "--vocab", "20000", "--sustained-steps", "0", "--probe-steps", "0", "--detail", _detail_path()]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -82,7 +82,7 @@ def test_bare_bench_command_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it (RANK unset) starts its two ranks itself; with more ranks
     than GPUs and the default backend it falls back to gloo and says so in the line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--no-cpu-baseline", "--batch", "4096", "--vocab", "50000", "--sustained-steps", "0", "--detail", _detail_path()]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -115,7 +115,7 @@ def test_sharded_step_through_a_one_rank_rccl_communicator():
     run takes, on the one GPU of the test box."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     for exchange in ("static", "exact"):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--rccl-self", "--exchange", exchange,
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-sharded", "--rccl-self", "--exchange", exchange,
                "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--batch", "8192", "--vocab", "100000",
                "--sustained-steps", "0", "--detail", _detail_path()]
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -140,7 +140,8 @@ def test_virtual_world_runs_rank_zero_of_an_n_way_job_with_n_way_shapes():
     owners, N blocks per exchange, loopback copies for the links -- the per-rank KERNEL time of an N-way job, a projection
     that the line labels as such (no parity: the other ranks' shards do not exist)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--virtual-world", "4", "--steps", "3", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-sharded", "--virtual-world", "4", "--steps", "3",
+           "--warmup", "2",
            "--no-cpu-baseline", "--batch", "8192", "--vocab", "100000", "--sustained-steps", "0", "--detail", _detail_path()]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -27,7 +27,7 @@ def _run(extra, timeout=900):
     detail = os.path.join(tempfile.mkdtemp(prefix="krs_c5_"), "bench_detail.json")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dist-backend", "gloo", "--criteo-vocab", "40000000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--dist-backend", "gloo", "--criteo-vocab", "40000000",
            "--id-skew", "4", "--steps", "1", "--warmup", "1", "--sustained-steps", "0", "--probe-steps", "0", "--no-cpu-baseline",
            "--detail", detail] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)

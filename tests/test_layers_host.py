@@ -477,6 +477,48 @@ def test_bench_last_line_stays_below_the_drivers_tail():
     assert "phases_ms" not in line
 
 
+def test_bench_plain_run_leaves_the_other_legs_to_full():
+    """bench.py without --full times the K steps and nothing else: no probe or sustained steps unless asked for, and the line of
+    such a record keeps the headline members; --full brings the old defaults back (3 probe steps, 500 sustained)."""
+    bench, root = _load_bench()
+    plain = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.probe_steps == 0 and plain.sustained_steps == 0
+    full = bench.parse(["--full"])
+    assert full.full and full.probe_steps == 3 and full.sustained_steps == 500
+    assert bench.parse(["--sustained-steps", "4"]).sustained_steps == 4
+    assert bench.parse(["--full", "--probe-steps", "0"]).probe_steps == 0
+    with open(os.path.join(root, "tests", "golden", "bench_lines", "default_n1.json")) as f:
+        rec = json.load(f)
+    for key in ("roofline", "roofline_step", "embed_fwd_lookups_per_s", "also", "also_c2", "sustained", "cpu_baseline"):
+        rec.pop(key)
+    line = bench.compact_line(rec, "bench_detail.json")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config", "detail"):
+        assert key in line, key
+    assert line["value"] == pytest.approx(rec["value"], rel=1e-5) and "roofline" not in line and "cpu_baseline" not in line
+
+
+def test_bench_table_draws_ahead_hold_the_same_bits():
+    """bench.py::TableDraws: the tables drawn ahead on a thread pool and handed to the layer as callables hold exactly what
+    RandomUniform draws for them one after the other -- in order, out of order, twice, and at a shape it was not drawn for."""
+    import torch
+
+    from keras_rs_amd.layers import base
+
+    bench, _ = _load_bench()
+    shapes = [(1000 + 37 * t, 16) for t in range(7)]
+
+    def inits():
+        return [base.RandomUniform(-0.05, 0.05, seed=1337 + t) for t in range(7)]
+
+    exp = [init(s, torch.bfloat16, "cpu") for init, s in zip(inits(), shapes)]
+    ahead = bench.TableDraws(inits(), shapes, depth=2)
+    got = {t: base.get_initializer(ahead.table(t))(shapes[t], torch.bfloat16, "cpu") for t in (0, 1, 4, 2, 3, 6, 5, 1)}
+    for t, g in got.items():
+        assert g.dtype == torch.bfloat16 and torch.equal(g, exp[t]), t
+    odd = base.get_initializer(ahead.table(3))((5, 16), torch.float32, "cpu")
+    assert torch.equal(odd, base.RandomUniform(-0.05, 0.05, seed=1340)((5, 16)))
+
+
 def test_bench_dominant_entry_is_priced_per_step():
     """bench.py::dominant_roofline: the entry with the largest per-step time among those with a roofline of their own; with
     `single` the aggregate over the GEMM families is left out (K2 apply at C3)."""

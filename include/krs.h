@@ -335,13 +335,7 @@ size_t krs_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k, int a_is_km);
  * rounding) -- without the second pass reading G, x0 and u back and with the streams written by the product's epilogue.
  * Row stride `ld` for x0, u, dz and dx0; workspace: krs_gemm_cross_bwd_workspace_bytes(m, n) when dbias is wanted.
  * bf16 tiles the 256x256 ring kernel covers run fused; every other shape / dtype runs the two calls (needs ldg == ld).
- *
- * DENSE form (round 6): x0 == NULL -- the layer below is a Dense layer (examples/ml_perf/model.py:214-262), u its saved
- * output y:  dz = G * act'(y),  dbias = column sums of dz;  R, dx0, u_upper, fold_direct must be absent.  g_out != NULL: G is
- * stored there by every route (it is the true dL/dy of the lower layer's output, what autograd must hand to anyone who
- * observes that output); g_out == NULL: G is not stored by the fused route, and the two-call route lands it in dz's buffer
- * and applies the derivative in place -- the launch then streams y in and dz out where krs_gemm + krs_dense_act_bwd write
- * G, read G and y and write dz.  G and dz are bit-identical to those two calls (one rounding of G, then the derivative). */
+ * x0, u, dz and g_out are required (krs_gemm_dense_bwd is the form for a Dense layer below). */
 size_t krs_gemm_cross_bwd_workspace_bytes(int64_t m, int64_t n);
 int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb,
                        const void* r, int64_t ldr, float beta,
@@ -349,11 +343,22 @@ int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb,
                        const void* x0, const void* u, void* dz, void* dx0, int64_t ld, int dx0_accumulate,
                        const void* u_upper, int fold_direct, float* dbias, int64_t m, int64_t n, int64_t k, int act, int dtype,
                        void* workspace, size_t workspace_bytes, void* stream);
-/* Diagnostic, host only: the route the CALLING THREAD's last krs_gemm_cross_bwd took -- KRS_CROSS_BWD_NONE (no call yet, a
- * refused call, or m == 0 / n == 0), KRS_CROSS_BWD_TWO_CALL (krs_gemm + the elementwise pass), KRS_CROSS_BWD_PP64 /
- * KRS_CROSS_BWD_PP256 (fused, on gemm_pp64_kernel / gemm_pp256_kernel).  *epilogue (if not NULL) receives the fused
- * epilogue number (3 .. 10: 9 = the dense form without G, 10 = with G), 0 for the other routes.  Lets tests prove which
- * path they exercised. */
+/* The same fusion when the layer below is a Dense layer (examples/ml_perf/model.py:214-262) with saved output y:
+ *      G   = A[M,K] @ Bt[N,K]^T,  dz = G * act'(y),  dbias[n] = sum_m dz[m,n]  (fp32, fixed order; NULL: not wanted)
+ * g_out != NULL: G is stored there by every route (it is the true dL/dy of the lower layer's output, what autograd must
+ * hand to anyone who observes that output); g_out == NULL: G is not stored by the fused route, and the two-call route
+ * lands it in dz's buffer and applies the derivative in place -- the launch then streams y in and dz out where krs_gemm +
+ * krs_dense_act_bwd write G, read G and y and write dz.  G and dz are bit-identical to those two calls (one rounding of
+ * G, then the derivative).  Row stride `ld` for y and dz; same routes, gate and workspace
+ * (krs_gemm_cross_bwd_workspace_bytes) as krs_gemm_cross_bwd. */
+int krs_gemm_dense_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb, void* g_out, int64_t ldg,
+                       const void* y, void* dz, int64_t ld, float* dbias, int64_t m, int64_t n, int64_t k, int act,
+                       int dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* Diagnostic, host only: the route the CALLING THREAD's last krs_gemm_cross_bwd / krs_gemm_dense_bwd took --
+ * KRS_CROSS_BWD_NONE (no call yet, a refused call, or m == 0 / n == 0), KRS_CROSS_BWD_TWO_CALL (krs_gemm + the elementwise
+ * pass), KRS_CROSS_BWD_PP64 / KRS_CROSS_BWD_PP256 (fused, on gemm_pp64_kernel / gemm_pp256_kernel).  *epilogue (if not
+ * NULL) receives the fused epilogue number (3 .. 10: 9 = the dense form without G, 10 = with G), 0 for the other routes.
+ * Lets tests prove which path they exercised. */
 enum { KRS_CROSS_BWD_NONE = 0, KRS_CROSS_BWD_TWO_CALL = 1, KRS_CROSS_BWD_PP64 = 2, KRS_CROSS_BWD_PP256 = 3 };
 int krs_gemm_cross_bwd_last_route(int* epilogue);
 

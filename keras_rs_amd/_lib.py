@@ -54,60 +54,68 @@ class GemmEpilogue(C.Structure):
     ]
 
 
-# Every symbol include/krs.h declares (checked by tests/test_capi_symbols.py).
-SYMBOLS = [
-    "krs_version",
-    "krs_last_error",
-    "krs_embed_bag_fwd",
-    "krs_embed_bag_bwd_workspace_bytes",
-    "krs_embed_bag_bwd_plan",
-    "krs_embed_bag_bwd_plan_tables",
-    "krs_embed_bag_bwd_dense",
-    "krs_embed_bag_bwd_fused_sgd",
-    "krs_embed_bag_bwd_fused_adagrad",
-    "krs_embed_bag_bwd_fused_adagrad_rowwise",
-    "krs_embed_bag_bwd_fused_adam",
-    "krs_embed_bag_bwd_fused_adam_dyn",
-    "krs_store_f32",
-    "krs_embed_bag_bwd_fused_ftrl",
-    "krs_embed_bag_bwd_sparse",
-    "krs_gemm",
-    "krs_gemm_workspace_bytes",
-    "krs_gemm_set_option",
-    "krs_embed_set_option",
-    "krs_cross_epilogue_fwd",
-    "krs_cross_epilogue_bwd",
-    "krs_gemm_cross_bwd",
-    "krs_gemm_cross_bwd_workspace_bytes",
-    "krs_gemm_cross_bwd_last_route",
-    "krs_colsum",
-    "krs_colsum_workspace_bytes",
-    "krs_cast_transpose",
-    "krs_cast_transpose_many",
-    "krs_dense_adagrad",
-    "krs_dense_act_bwd",
-    "krs_dot_interaction_fwd",
-    "krs_dot_interaction_bwd",
-    "krs_dot_interaction_bwd_accumulate",
-    "krs_mod_bucketize_workspace_bytes",
-    "krs_mod_bucketize",
-    "krs_shard_route_workspace_bytes",
-    "krs_shard_route",
-    "krs_shard_unpack_workspace_bytes",
-    "krs_shard_unpack",
-    "krs_shard_combine",
-    "krs_shard_static_block_words",
-    "krs_shard_route_static",
-    "krs_shard_unpack_static",
-    "krs_publish_i64",
-    "krs_bce_fwd_bwd",
-    "krs_topk_rows",
-    "krs_topk_rows_workspace_bytes",
-    "krs_retrieval_topk",
-    "krs_retrieval_topk_workspace_bytes",
-    "krs_pairwise_loss",
-    "krs_listmle_loss",
-]
+# Prototype of every entry point include/krs.h declares, in its order: name -> (restype, argtypes).  Any pointer is a
+# void* (pass L.ptr(t), an int or None; ctypes arrays and C.byref(struct) where the C side takes an array or a struct).
+# tests/test_capi_symbols.py parses the header and checks this table against it row by row.
+_P, _I, _I64, _U64, _SZ, _F = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_size_t, C.c_float
+_EMBED_BWD = [_P, _I, _P, _I, _P, _P, _P, _I, _I64, _I, _I, _I, _I64]   # tables .. nnz of the fused K2 optimizers
+PROTOTYPES = {
+    "krs_version": (_I, []),
+    "krs_last_error": (C.c_char_p, []),
+    "krs_embed_bag_fwd": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I64, _I, _I, _I, _P, _I, _I64, _P, _P, _P]),
+    "krs_embed_bag_bwd_workspace_bytes": (_SZ, [_I64]),
+    "krs_embed_bag_bwd_plan": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I64, _I64, _P, _SZ, _P, _P]),
+    "krs_embed_bag_bwd_plan_tables": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I64, _I64, _P, _SZ, _P, _P]),
+    "krs_embed_bag_bwd_dense": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I64, _I, _I, _I64, _P, _P]),
+    "krs_embed_bag_bwd_fused_sgd": (_I, _EMBED_BWD + [_P, _P]),
+    "krs_embed_bag_bwd_fused_adagrad": (_I, _EMBED_BWD + [_P, _P]),
+    "krs_embed_bag_bwd_fused_adagrad_rowwise": (_I, _EMBED_BWD + [_P, _P]),
+    "krs_embed_bag_bwd_fused_adam": (_I, _EMBED_BWD + [_F, _F, _F, _F, _P, _P]),
+    "krs_embed_bag_bwd_fused_ftrl": (_I, _EMBED_BWD + [_F, _F, _F, _F, _P, _P]),
+    "krs_embed_bag_bwd_fused_adam_dyn": (_I, _EMBED_BWD + [_F, _F, _F, _P, _P, _P]),
+    "krs_store_f32": (_I, [_P, _I64, _P, _I, _P]),
+    "krs_embed_bag_bwd_sparse": (_I, [_P, _I, _P, _P, _P, _I, _I64, _I, _I, _I64, _P, _P, _P, _P, _P]),
+    "krs_gemm": (_I, [_P, _I64, _I, _P, _I64, _I, _P, _I64, _I64, _I64, _I64, _I, _I, _P, _P, _SZ, _P]),
+    "krs_gemm_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
+    "krs_gemm_cross_bwd_workspace_bytes": (_SZ, [_I64, _I64]),
+    "krs_gemm_cross_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _F, _P, _I64, _P, _P, _P, _P, _I64, _I, _P, _I, _P,
+                                _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
+    "krs_gemm_dense_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
+    "krs_gemm_cross_bwd_last_route": (_I, [_P]),
+    "krs_gemm_set_option": (_I, [_I, _I]),
+    "krs_embed_set_option": (_I, [_I, _I]),
+    "krs_colsum_workspace_bytes": (_SZ, [_I64, _I64]),
+    "krs_cross_epilogue_fwd": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _F, _I, _P]),
+    "krs_cross_epilogue_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I64, _I64, _I64, _F, _I, _I, _P, _SZ, _P]),
+    "krs_cast_transpose": (_I, [_P, _I64, _I64, _I64, _I, _P, _I64, _P, _I64, _I, _P]),
+    "krs_cast_transpose_many": (_I, [_I, _P, _P, _P, _I, _P, _P, _I, _P]),
+    "krs_dense_act_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _P, _SZ, _P]),
+    "krs_dense_adagrad": (_I, [_P, _P, _P, _P, _I, _F, _F, _P]),
+    "krs_colsum": (_I, [_P, _I64, _I64, _I64, _I, _P, _P, _SZ, _P]),
+    "krs_dot_interaction_fwd": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P]),
+    "krs_dot_interaction_bwd": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
+    "krs_dot_interaction_bwd_accumulate": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _P, _U64, _P]),
+    "krs_mod_bucketize_workspace_bytes": (_SZ, [_I64, _I]),
+    "krs_mod_bucketize": (_I, [_P, _I, _I64, _I, _P, _P, _P, _P, _SZ, _P]),
+    "krs_bce_fwd_bwd": (_I, [_P, _I, _P, _I64, _F, _F, _P, _P, _P, _P]),
+    "krs_shard_route_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "krs_shard_route": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I64, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "krs_shard_unpack_workspace_bytes": (_SZ, [_I64]),
+    "krs_shard_unpack": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    "krs_shard_combine": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I64, _P]),
+    "krs_shard_static_block_words": (_I64, [_I64, _I64, _I]),
+    "krs_shard_route_static": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I64, _I, _I, _I, _I64, _I64, _P, _P, _P, _P, _P,
+                                    _P, _P, _SZ, _P]),
+    "krs_shard_unpack_static": (_I, [_P, _I, _I64, _I64, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "krs_publish_i64": (_I, [_P, _I, _P, _I64, _P]),
+    "krs_topk_rows_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "krs_topk_rows": (_I, [_P, _P, _F, _I64, _I, _I64, _I64, _I, _P, _P, _P, _SZ, _P]),
+    "krs_retrieval_topk_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I, _I]),
+    "krs_retrieval_topk": (_I, [_P, _I64, _P, _I64, _P, _I, _I64, _I64, _I64, _I, _P, _P, _P, _SZ, _P]),
+    "krs_pairwise_loss": (_I, [_I, _P, _I64, _I, _P, _P, _P, _F, _F, _I64, _I64, _P, _P, _P]),
+    "krs_listmle_loss": (_I, [_P, _I64, _I, _P, _P, _P, _F, _F, _I64, _I64, _P, _P, _P]),
+}
+SYMBOLS = list(PROTOTYPES)
 
 _lib = None
 
@@ -125,15 +133,12 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m keras_rs_amd.build` "
                 "(hipcc --offload-arch=gfx950).  keras_rs_amd has no CPU fallback."
             )
-        _lib = C.CDLL(LIB_PATH)
-        _lib.krs_last_error.restype = C.c_char_p
-        for name in ("krs_embed_bag_bwd_workspace_bytes", "krs_gemm_workspace_bytes",
-                     "krs_mod_bucketize_workspace_bytes", "krs_shard_route_workspace_bytes",
-                     "krs_shard_unpack_workspace_bytes", "krs_colsum_workspace_bytes",
-                     "krs_gemm_cross_bwd_workspace_bytes", "krs_topk_rows_workspace_bytes",
-                     "krs_retrieval_topk_workspace_bytes"):
-            getattr(_lib, name).restype = C.c_size_t
-        _lib.krs_shard_static_block_words.restype = C.c_int64
+        handle = C.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(handle, name, None)   # (an older build loaded through KRS_LIB may lack newer entries)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
+        _lib = handle
     return _lib
 
 
@@ -150,12 +155,12 @@ def require_device(t: torch.Tensor, what: str) -> None:
         )
 
 
-def ptr(t: torch.Tensor | None):
-    return None if t is None else C.c_void_p(t.data_ptr())
+def ptr(t: torch.Tensor | None) -> int | None:
+    return None if t is None else t.data_ptr()
 
 
-def stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def stream_ptr() -> int:
+    return torch.cuda.current_stream().cuda_stream
 
 
 def fdtype(t: torch.Tensor) -> int:

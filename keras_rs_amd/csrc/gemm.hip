@@ -753,7 +753,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_glds_kernel(const GemmParams p
 // the term of the layer ABOVE computed here from its dL/dy (= R, already loaded) and its saved u, so that the top layer of a
 // stack neither writes nor this launch reads a [M, N] matrix for it (that one sum is rounded once instead of twice);
 // 3: no dL/dx0 at all from this launch (the caller hands u to the NEXT launch as its u_upper: a Dense layer above a stack).
-// X0 = false: the DENSE form (krs_gemm_cross_bwd with x0 = NULL, round 6) -- the layer below is a Dense layer, dz = G act'(y)
+// X0 = false: the DENSE form (krs_gemm_dense_bwd, round 6) -- the layer below is a Dense layer, dz = G act'(y)
 // with y in the place of u, no x0 stream, no dL/dx0.  STORE_G: G is stored as well (the caller passed g_out: autograd hands
 // G, the true dL/dy, to whoever observes that output); without it two streams (y in, dz out) instead of krs_dense_act_bwd's
 // three behind a stored and re-read G.
@@ -1715,6 +1715,28 @@ bool mfma_eligible(const GemmParams& p, int es) {
   return p.m >= 1 && p.n >= 1 && p.k >= 1;
 }
 
+// Launches Kern with `lds` bytes of dynamic LDS.  The kernel's dynamic-LDS limit is raised on its first launch: a
+// function-local static, initialised once per kernel (and thread-safe).  `what` names the launch in error messages.
+template <auto Kern, class... Args>
+int launch_lds(const char* what, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (attr != hipSuccess) return fail(KRS_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(attr));
+  hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+  KRS_CHECK_LAUNCH(what);
+  return KRS_OK;
+}
+
+// f(std::integral_constant<int, E>()) for the epilogue number e, First <= e <= Last: a kernel's EPI template argument
+// picked at run time
+template <int First, int Last, class F>
+int with_epilogue(int e, F&& f) {
+  if constexpr (First < Last) {
+    if (e != First) return with_epilogue<First + 1, Last>(e, f);
+  }
+  return f(std::integral_constant<int, First>());
+}
+
 template <int ES>
 int launch_mfma(const GemmParams& p, hipStream_t st) {
   const int64_t mt = p.a_km ? ceil_div(p.m, BM) : ceil_div(ceil_div(p.m, BM), 8) * 8;
@@ -1725,23 +1747,6 @@ int launch_mfma(const GemmParams& p, hipStream_t st) {
   if (p.has_ep && p.ep_vec && p.splits == 1 && p.out_dtype == KRS_BF16 && p.n >= 8) {
     if (p.ep.x0 && !p.ep.r) epi = 1;
     else if (p.ep.r && !p.ep.x0 && !p.ep.bias && p.ep.act == KRS_ACT_NONE) epi = 2;
-  }
-#define KRS_GEMM_LAUNCH(AK, BK_, EP)                                                                \
-  {                                                                                                 \
-    auto kern = gemm_mfma_kernel<ES, AK, BK_, EP>;                                                  \
-    static bool attr_set = false;                                                                   \
-    if (!attr_set) {                                                                                \
-      KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                              \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
-      attr_set = true;                                                                              \
-    }                                                                                               \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);                                          \
-  }
-#define KRS_GEMM_CASE(AK, BK_)                                                                      \
-  {                                                                                                 \
-    if (epi == 1) KRS_GEMM_LAUNCH(AK, BK_, 1)                                                       \
-    else if (epi == 2) KRS_GEMM_LAUNCH(AK, BK_, 2)                                                  \
-    else KRS_GEMM_LAUNCH(AK, BK_, 0)                                                                \
   }
   if (p.a_km && p.b_nk) return fail(KRS_ERR_UNSUPPORTED, "krs_gemm: A^T . B^T layout is not used by the layer");
   // Long contractions: the LDS-DMA pipeline (no staging registers, no ds_write traffic).  Short ones
@@ -1768,66 +1773,22 @@ int launch_mfma(const GemmParams& p, hipStream_t st) {
       const int nt_ = (int)ceil_div(p.n, 256);
       // (the residual-add form with a short K -- dx = dh U^T + g -- was 4 % faster on a two-stage loop until its R
       // operands were fetched under the ring's tail: 340 -> 301 us)
-#define KRS_PP_LAUNCH(EP)                                                                            \
-  {                                                                                                  \
-    auto kern = gemm_pp256_kernel<false, 4, EP>;                                                     \
-    static bool attr_set = false;                                                                    \
-    if (!attr_set) {                                                                                 \
-      KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                               \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pp::STAGE));       \
-      attr_set = true;                                                                               \
-    }                                                                                                \
-    hipLaunchKernelGGL(kern, grid256, dim3(512), 4 * pp::STAGE, st, p, 0, nt_);                      \
-  }
       // whole 64-k blocks of both operands and of every split, at least three of them -> the 64-k ring (pipeline 5: never)
       const bool k64 = gemm_pipe() == 4 && p.k % 64 == 0 && p.k_per_split % 64 == 0 &&
                        p.k - (int64_t)(p.splits - 1) * p.k_per_split >= 192;
-#define KRS_PP64_LAUNCH(EP)                                                                          \
-  {                                                                                                  \
-    auto kern = gemm_pp64_kernel<EP>;                                                                \
-    static bool attr_set = false;                                                                    \
-    if (!attr_set) {                                                                                 \
-      KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                               \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, pp64::NSLOT * pp64::SLOT)); \
-      attr_set = true;                                                                               \
-    }                                                                                                \
-    hipLaunchKernelGGL(kern, grid256, dim3(512), pp64::NSLOT * pp64::SLOT, st, p, nt_);              \
-  }
-      if (k64) {
-        if (epi == 1) KRS_PP64_LAUNCH(1)
-        else if (epi == 2) KRS_PP64_LAUNCH(2)
-        else KRS_PP64_LAUNCH(0)
-        KRS_CHECK_LAUNCH("gemm_pp64_kernel");
-        return KRS_OK;
-      }
-#undef KRS_PP64_LAUNCH
-      if (epi == 1) KRS_PP_LAUNCH(1)
-      else if (epi == 2) KRS_PP_LAUNCH(2)
-      else KRS_PP_LAUNCH(0)
-#undef KRS_PP_LAUNCH
-      KRS_CHECK_LAUNCH("gemm_pp256_kernel");
-      return KRS_OK;
+      return with_epilogue<0, 2>(epi, [&](auto E) {
+        return k64 ? launch_lds<gemm_pp64_kernel<E>>("gemm_pp64_kernel", grid256, dim3(512), pp64::NSLOT * pp64::SLOT, st,
+                                                     p, nt_)
+                   : launch_lds<gemm_pp256_kernel<false, 4, E>>("gemm_pp256_kernel", grid256, dim3(512), 4 * pp::STAGE, st,
+                                                                p, 0, nt_);
+      });
     }
   }
   if (use_glds) {
     const size_t glds_lds = 4 * BM * ROW_BYTES;  // 2 stages x (A + B) x 16 KB
-#define KRS_GLDS_LAUNCH(EP)                                                                          \
-  {                                                                                                  \
-    auto kern = gemm_glds_kernel<ES, EP>;                                                            \
-    static bool attr_set = false;                                                                    \
-    if (!attr_set) {                                                                                 \
-      KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                               \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds_lds));       \
-      attr_set = true;                                                                               \
-    }                                                                                                \
-    hipLaunchKernelGGL(kern, grid, dim3(256), glds_lds, st, p);                                      \
-  }
-    if (epi == 1) KRS_GLDS_LAUNCH(1)
-    else if (epi == 2) KRS_GLDS_LAUNCH(2)
-    else KRS_GLDS_LAUNCH(0)
-#undef KRS_GLDS_LAUNCH
-    KRS_CHECK_LAUNCH("gemm_glds_kernel");
-    return KRS_OK;
+    return with_epilogue<0, 2>(epi, [&](auto E) {
+      return launch_lds<gemm_glds_kernel<ES, E>>("gemm_glds_kernel", grid, dim3(256), glds_lds, st, p);
+    });
   }
   // bf16 weight gradients: LDS-DMA + transposing reads (K extents in whole 64-row tiles, >= 8 columns)
   if (ES == 2 && p.a_km && !p.b_nk && p.k % 64 == 0 && p.k_per_split % 64 == 0 && p.m >= 8 && p.n >= 8 &&
@@ -1837,38 +1798,19 @@ int launch_mfma(const GemmParams& p, hipStream_t st) {
     if (p.m >= 256 && p.n >= 256 && !tn128 && gemm_pipe() != 0 && p.k_per_split >= 256) {
       const int mt_ = (int)ceil_div(p.m, 256), nt_ = (int)ceil_div(p.n, 256);
       const dim3 grid_tn((unsigned)(ceil_div((int64_t)p.splits * mt_ * nt_, 8) * 8));
-      auto kern = gemm_pp256_kernel<true, 4, 0>;
-      static bool attr_set = false;
-      if (!attr_set) {
-        KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    4 * pp::STAGE));
-        attr_set = true;
-      }
-      hipLaunchKernelGGL(kern, grid_tn, dim3(512), 4 * pp::STAGE, st, p, mt_, nt_);
-      KRS_CHECK_LAUNCH("gemm_pp256_kernel (K-strided operands)");
-      return KRS_OK;
+      return launch_lds<gemm_pp256_kernel<true, 4, 0>>("gemm_pp256_kernel (K-strided operands)", grid_tn, dim3(512),
+                                                       4 * pp::STAGE, st, p, mt_, nt_);
     }
     const int mt_ = (int)ceil_div(p.m, BM), nt_ = (int)ceil_div(p.n, BN);
     const dim3 grid_tn((unsigned)(ceil_div(p.splits, 8) * 8 * mt_ * nt_));
     const size_t lds_tn = 4 * 64 * 128 * 2;  // 2 stages x (A + B) x 16 KB
-    auto kern = gemm_tn_glds_kernel<0>;
-    static bool attr_set = false;
-    if (!attr_set) {
-      KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_tn));
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, grid_tn, dim3(256), lds_tn, st, p, mt_, nt_);
-    KRS_CHECK_LAUNCH("gemm_tn_glds_kernel");
-    return KRS_OK;
+    return launch_lds<gemm_tn_glds_kernel<0>>("gemm_tn_glds_kernel", grid_tn, dim3(256), lds_tn, st, p, mt_, nt_);
   }
-  if (p.a_km) KRS_GEMM_CASE(true, false)
-  else if (p.b_nk) KRS_GEMM_CASE(false, true)
-  else KRS_GEMM_CASE(false, false)
-#undef KRS_GEMM_LAUNCH
-#undef KRS_GEMM_CASE
-  KRS_CHECK_LAUNCH("gemm_mfma_kernel");
-  return KRS_OK;
+  return with_epilogue<0, 2>(epi, [&](auto E) {
+    if (p.a_km) return launch_lds<gemm_mfma_kernel<ES, true, false, E>>("gemm_mfma_kernel", grid, dim3(256), lds, st, p);
+    if (p.b_nk) return launch_lds<gemm_mfma_kernel<ES, false, true, E>>("gemm_mfma_kernel", grid, dim3(256), lds, st, p);
+    return launch_lds<gemm_mfma_kernel<ES, false, false, E>>("gemm_mfma_kernel", grid, dim3(256), lds, st, p);
+  });
 }
 
 }  // namespace
@@ -2016,7 +1958,7 @@ extern "C" size_t krs_gemm_cross_bwd_workspace_bytes(int64_t m, int64_t n) {
   return std::max(krs_colsum_workspace_bytes(m, n), (size_t)(2 * ceil_div(m, 256)) * (size_t)n * sizeof(float));
 }
 
-// which route the calling thread's last krs_gemm_cross_bwd took (krs_gemm_cross_bwd_last_route)
+// which route the calling thread's last krs_gemm_cross_bwd / krs_gemm_dense_bwd took (krs_gemm_cross_bwd_last_route)
 static thread_local int cb_route = KRS_CROSS_BWD_NONE, cb_epilogue = 0;
 
 extern "C" int krs_gemm_cross_bwd_last_route(int* epilogue) {
@@ -2024,30 +1966,22 @@ extern "C" int krs_gemm_cross_bwd_last_route(int* epilogue) {
   return cb_route;
 }
 
-extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb, const void* r, int64_t ldr,
-                                  float beta, void* g_out, int64_t ldg, const void* x0, const void* u, void* dz,
-                                  void* dx0, int64_t ld, int dx0_accumulate, const void* u_upper, int fold_direct,
-                                  float* dbias, int64_t m, int64_t n, int64_t k, int act, int dtype, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-  cb_route = KRS_CROSS_BWD_NONE; cb_epilogue = 0;
-  const bool dense_form = x0 == nullptr;    // the layer below is a Dense layer: dz = G act'(u) (u = its saved output), dbias
-  // (an empty product may come with NULL operands: a framework's empty tensors have no storage)
-  KRS_REQUIRE((a && bt && u && dz && (dense_form || g_out)) || m == 0 || n == 0, "krs_gemm_cross_bwd: null operand");
-  KRS_REQUIRE(!dense_form || (!r && !dx0 && !dx0_accumulate && !u_upper && !fold_direct),
-              "krs_gemm_cross_bwd: the dense form (x0 = NULL) takes no R, dx0, u_upper or fold_direct");
+// The body of krs_gemm_cross_bwd and of krs_gemm_dense_bwd (`dense`: the layer below is a Dense layer, u its saved output:
+// dz = G act'(u), dbias; x0, R, dx0, u_upper and fold_direct are absent).  The entries have checked their operands; `who`
+// names the entry in error messages.
+static int cross_bwd(const char* who, bool dense, const void* a, int64_t lda, const void* bt, int64_t ldb, const void* r,
+                     int64_t ldr, float beta, void* g_out, int64_t ldg, const void* x0, const void* u, void* dz, void* dx0,
+                     int64_t ld, int dx0_accumulate, const void* u_upper, int fold_direct, float* dbias, int64_t m,
+                     int64_t n, int64_t k, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
   // dense form: G is stored only where the caller asked for it (g_out != NULL), by either route; without g_out the fused
   // route writes dz alone and the two-call route lands G in dz's buffer and applies the derivative in place
   const bool store_g = g_out != nullptr;
-  if (dense_form && !g_out) { g_out = dz; ldg = ld; }
+  if (dense && !g_out) { g_out = dz; ldg = ld; }
   if (!r) { ldr = n; beta = 0.0f; }
-  KRS_REQUIRE(dx0 || (!r && !dx0_accumulate && !u_upper && !fold_direct),
-              "krs_gemm_cross_bwd: dx0 = NULL (the term is left to the next launch's u_upper) is the form without R");
-  KRS_REQUIRE(!u_upper || (r && !dx0_accumulate && beta == 1.0f),
-              "krs_gemm_cross_bwd: u_upper (dx0 = R * u_upper + ...) needs R with beta = 1 and no dx0 to accumulate into");
-  KRS_REQUIRE(dtype == KRS_BF16 || dtype == KRS_F32, "krs_gemm_cross_bwd: bad dtype");
-  KRS_REQUIRE(m >= 0 && n >= 0 && k > 0 && ld >= n && ldg >= n && ldr >= n, "krs_gemm_cross_bwd: bad sizes");
+  KRS_REQUIRE(dtype == KRS_BF16 || dtype == KRS_F32, "%s: bad dtype", who);
+  KRS_REQUIRE(m >= 0 && n >= 0 && k > 0 && ld >= n && ldg >= n && ldr >= n, "%s: bad sizes", who);
   if (dbias) KRS_REQUIRE(workspace_bytes >= krs_gemm_cross_bwd_workspace_bytes(m, n) && (workspace || m == 0 || n == 0),
-                         "krs_gemm_cross_bwd: workspace too small (krs_gemm_cross_bwd_workspace_bytes)");
+                         "%s: workspace too small (krs_gemm_cross_bwd_workspace_bytes)", who);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (m == 0 || n == 0) {   // (the column sums over no rows are zeros)
     if (dbias && n > 0) KRS_HIP(hipMemsetAsync(dbias, 0, (size_t)n * sizeof(float), st));
@@ -2068,11 +2002,11 @@ extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, in
     if (int rc = gemm_run(a, lda, 0, bt, ldb, 1, g_out, ldg, m, n, k, dtype, dtype, r ? &ep : nullptr, nullptr, 0, stream,
                           false))
       return rc;
-    KRS_REQUIRE(ldg == ld, "krs_gemm_cross_bwd: the two-call form needs one row stride for G, x0, u, dz and dx0");
-    if (dense_form)    // G lands in (or is) dz's buffer, the activation derivative is applied in place
+    KRS_REQUIRE(ldg == ld, "%s: the two-call form needs one row stride for G, x0, u, dz and dx0", who);
+    if (dense)    // G lands in (or is) dz's buffer, the activation derivative is applied in place
       return krs_dense_act_bwd(g_out, ldg, u, ld, dz, ld, dbias, m, n, act, dtype, workspace, workspace_bytes, stream);
     if (u_upper) {   // the upper layer's term first: dx0 = R * u_upper (its own rounding here), then accumulate
-      KRS_REQUIRE(ldr == ld, "krs_gemm_cross_bwd: the two-call form needs R on the common row stride");
+      KRS_REQUIRE(ldr == ld, "%s: the two-call form needs R on the common row stride", who);
       if (int rc = krs_cross_epilogue_bwd(r, u_upper, x0, x0, nullptr, dx0, 0, nullptr, nullptr, m, n, ld, 0.0f, KRS_ACT_NONE,
                                           dtype, nullptr, 0, stream)) return rc;
       dx0_accumulate = 1;
@@ -2092,63 +2026,49 @@ extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, in
   p.f_partial = dbias ? reinterpret_cast<float*>(workspace) : nullptr;
   const int nt_ = (int)ceil_div(n, 256);
   const dim3 grid256((unsigned)(ceil_div(ceil_div(m, 256), 8) * 8 * nt_));
-#define KRS_CB_LAUNCH(EP)                                                                              \
-  {                                                                                                    \
-    auto kern = gemm_pp256_kernel<false, 4, EP>;                                                       \
-    cb_route = KRS_CROSS_BWD_PP256; cb_epilogue = EP;                                                  \
-    static bool attr_set = false;                                                                      \
-    if (!attr_set) {                                                                                   \
-      KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                 \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pp::STAGE));         \
-      attr_set = true;                                                                                 \
-    }                                                                                                  \
-    hipLaunchKernelGGL(kern, grid256, dim3(512), 4 * pp::STAGE, st, p, 0, nt_);                        \
-  }
-  if (gemm_pipe() == 4 && k % 64 == 0 && k >= 192) {   // the 64-k ring, as krs_gemm's K-contiguous products (level with the 32-k
-                                                        // ring on this epilogue-bound form: 640-650 us either way)
-#define KRS_CB64_LAUNCH(EP)                                                                            \
-  {                                                                                                    \
-    auto kern = gemm_pp64_kernel<EP>;                                                                  \
-    cb_route = KRS_CROSS_BWD_PP64; cb_epilogue = EP;                                                   \
-    static bool attr_set = false;                                                                      \
-    if (!attr_set) {                                                                                   \
-      KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                 \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, pp64::NSLOT * pp64::SLOT)); \
-      attr_set = true;                                                                                 \
-    }                                                                                                  \
-    hipLaunchKernelGGL(kern, grid256, dim3(512), pp64::NSLOT * pp64::SLOT, st, p, nt_);                \
-  }
-    if (dense_form) {
-      if (store_g) KRS_CB64_LAUNCH(10)
-      else KRS_CB64_LAUNCH(9)
-    } else if (u_upper) KRS_CB64_LAUNCH(7)
-    else if (r) {
-      if (dx0_accumulate) KRS_CB64_LAUNCH(4)
-      else KRS_CB64_LAUNCH(3)
-    } else {
-      if (!dx0) KRS_CB64_LAUNCH(8)
-      else if (dx0_accumulate) KRS_CB64_LAUNCH(6)
-      else KRS_CB64_LAUNCH(5)
-    }
-#undef KRS_CB64_LAUNCH
-    KRS_CHECK_LAUNCH("gemm_pp64_kernel (fused cross backward)");
-    if (dbias) return finish_colsum(p.f_partial, 2 * ceil_div(m, 256), n, dbias, st);
-    return KRS_OK;
-  }
-  if (dense_form) {
-    if (store_g) KRS_CB_LAUNCH(10)
-    else KRS_CB_LAUNCH(9)
-  } else if (u_upper) KRS_CB_LAUNCH(7)
-  else if (r) {
-    if (dx0_accumulate) KRS_CB_LAUNCH(4)
-    else KRS_CB_LAUNCH(3)
-  } else {
-    if (!dx0) KRS_CB_LAUNCH(8)
-    else if (dx0_accumulate) KRS_CB_LAUNCH(6)
-    else KRS_CB_LAUNCH(5)
-  }
-#undef KRS_CB_LAUNCH
-  KRS_CHECK_LAUNCH("gemm_pp256_kernel (fused cross backward)");
-  if (dbias) return finish_colsum(p.f_partial, 2 * ceil_div(m, 256), n, dbias, st);
-  return KRS_OK;
+  // the fused epilogue of this form (EPI 3 .. 10 of both ring kernels)
+  int epi;
+  if (dense) epi = store_g ? 10 : 9;
+  else if (u_upper) epi = 7;
+  else if (r) epi = dx0_accumulate ? 4 : 3;
+  else epi = !dx0 ? 8 : (dx0_accumulate ? 6 : 5);
+  // the 64-k ring, as krs_gemm's K-contiguous products (level with the 32-k ring on this epilogue-bound form: 640-650 us
+  // either way)
+  const bool k64 = gemm_pipe() == 4 && k % 64 == 0 && k >= 192;
+  cb_route = k64 ? KRS_CROSS_BWD_PP64 : KRS_CROSS_BWD_PP256; cb_epilogue = epi;
+  const int rc = with_epilogue<3, 10>(epi, [&](auto E) {
+    return k64 ? launch_lds<gemm_pp64_kernel<E>>("gemm_pp64_kernel (fused cross backward)", grid256, dim3(512),
+                                                 pp64::NSLOT * pp64::SLOT, st, p, nt_)
+               : launch_lds<gemm_pp256_kernel<false, 4, E>>("gemm_pp256_kernel (fused cross backward)", grid256, dim3(512),
+                                                            4 * pp::STAGE, st, p, 0, nt_);
+  });
+  if (rc != KRS_OK) return rc;
+  return dbias ? finish_colsum(p.f_partial, 2 * ceil_div(m, 256), n, dbias, st) : KRS_OK;
+}
+
+extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb, const void* r, int64_t ldr,
+                                  float beta, void* g_out, int64_t ldg, const void* x0, const void* u, void* dz,
+                                  void* dx0, int64_t ld, int dx0_accumulate, const void* u_upper, int fold_direct,
+                                  float* dbias, int64_t m, int64_t n, int64_t k, int act, int dtype, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  cb_route = KRS_CROSS_BWD_NONE; cb_epilogue = 0;
+  // (an empty product may come with NULL operands: a framework's empty tensors have no storage)
+  // (x0 = NULL selected the dense form before it had an entry of its own: the message says where it went)
+  KRS_REQUIRE((a && bt && x0 && u && dz && g_out) || m == 0 || n == 0, "krs_gemm_cross_bwd: null operand%s",
+              x0 ? "" : " (x0 = NULL: the dense form is krs_gemm_dense_bwd)");
+  KRS_REQUIRE(dx0 || (!r && !dx0_accumulate && !u_upper && !fold_direct),
+              "krs_gemm_cross_bwd: dx0 = NULL (the term is left to the next launch's u_upper) is the form without R");
+  KRS_REQUIRE(!u_upper || (r && !dx0_accumulate && beta == 1.0f),
+              "krs_gemm_cross_bwd: u_upper (dx0 = R * u_upper + ...) needs R with beta = 1 and no dx0 to accumulate into");
+  return cross_bwd("krs_gemm_cross_bwd", false, a, lda, bt, ldb, r, ldr, beta, g_out, ldg, x0, u, dz, dx0, ld,
+                   dx0_accumulate, u_upper, fold_direct, dbias, m, n, k, act, dtype, workspace, workspace_bytes, stream);
+}
+
+extern "C" int krs_gemm_dense_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb, void* g_out, int64_t ldg,
+                                  const void* y, void* dz, int64_t ld, float* dbias, int64_t m, int64_t n, int64_t k,
+                                  int act, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  cb_route = KRS_CROSS_BWD_NONE; cb_epilogue = 0;
+  KRS_REQUIRE((a && bt && y && dz) || m == 0 || n == 0, "krs_gemm_dense_bwd: null operand");
+  return cross_bwd("krs_gemm_dense_bwd", true, a, lda, bt, ldb, nullptr, n, 0.0f, g_out, ldg, nullptr, y, dz, nullptr, ld,
+                   0, nullptr, 0, dbias, m, n, k, act, dtype, workspace, workspace_bytes, stream);
 }

@@ -74,7 +74,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, a_is_km: bool = False, b_is_nk: bo
             raise L.KrsError("gemm: R must have the output dtype")
         keep.append(r)
         ep.r, ep.ldr, ep.beta = r.data_ptr(), r.stride(0), float(beta)
-    wsb = L.lib().krs_gemm_workspace_bytes(C.c_int64(m), C.c_int64(n), C.c_int64(k), C.c_int(int(a_is_km)))
+    wsb = L.lib().krs_gemm_workspace_bytes(m, n, k, int(a_is_km))
     ws = torch.empty(int(wsb), dtype=torch.uint8, device=a.device) if wsb else None
     # (bench.py's per-product roofline: one span name per product FAMILY -- operand layout, epilogue form, dtype, shape)
     name = "gemm"
@@ -84,11 +84,11 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, a_is_km: bool = False, b_is_nk: bo
                                            "bf16" if a.dtype == torch.bfloat16 else "f32", m, n, k)
     with probe.span(name, 2.0 * m * n * k):
         rc = L.lib().krs_gemm(
-            L.ptr(a), C.c_int64(a.stride(0)), C.c_int(int(a_is_km)),
-            L.ptr(b), C.c_int64(b.stride(0)), C.c_int(int(b_is_nk)),
-            L.ptr(c), C.c_int64(c.stride(0)), C.c_int64(m), C.c_int64(n), C.c_int64(k),
-            C.c_int(L.fdtype(a)), C.c_int(L.fdtype(c)), C.byref(ep),
-            L.ptr(ws), C.c_size_t(int(wsb)), L.stream_ptr())
+            L.ptr(a), a.stride(0), int(a_is_km),
+            L.ptr(b), b.stride(0), int(b_is_nk),
+            L.ptr(c), c.stride(0), m, n, k,
+            L.fdtype(a), L.fdtype(c), C.byref(ep),
+            L.ptr(ws), int(wsb), L.stream_ptr())
     L.check(rc, "krs_gemm")
     return c, u
 
@@ -97,8 +97,8 @@ def cross_epilogue_fwd(u, x0, x, diag_scale=0.0):
     u, x0, x = (_rowmajor(t, "cross_epilogue_fwd").contiguous() for t in (u, x0, x))
     y = torch.empty_like(x)
     m, n = x.shape
-    rc = L.lib().krs_cross_epilogue_fwd(L.ptr(u), L.ptr(x0), L.ptr(x), L.ptr(y), C.c_int64(m), C.c_int64(n),
-                                        C.c_int64(n), C.c_float(diag_scale or 0.0), C.c_int(L.fdtype(x)),
+    rc = L.lib().krs_cross_epilogue_fwd(L.ptr(u), L.ptr(x0), L.ptr(x), L.ptr(y), m, n,
+                                        n, diag_scale or 0.0, L.fdtype(x),
                                         L.stream_ptr())
     L.check(rc, "krs_cross_epilogue_fwd")
     return y
@@ -107,9 +107,9 @@ def cross_epilogue_fwd(u, x0, x, diag_scale=0.0):
 def _colsum_ws(m: int, n: int, device):
     """(pointer, byte count) arguments of the two-stage column sums (run-to-run identical bias gradients) + the
     tensor that keeps the workspace alive until the call has been enqueued."""
-    nbytes = int(L.lib().krs_colsum_workspace_bytes(C.c_int64(m), C.c_int64(n)))
+    nbytes = int(L.lib().krs_colsum_workspace_bytes(m, n))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-    return ws, L.ptr(ws), C.c_size_t(nbytes)
+    return ws, L.ptr(ws), nbytes
 
 
 def cross_epilogue_bwd(g, u, x0, x, diag_scale=0.0, *, act: int = L.ACT_NONE,
@@ -132,11 +132,11 @@ def cross_epilogue_bwd(g, u, x0, x, diag_scale=0.0, *, act: int = L.ACT_NONE,
             raise L.KrsError("cross_epilogue_bwd: dx0 buffer must be contiguous")
     dxd = dx0 if fold_direct else (torch.empty_like(x) if want_dxd else None)
     dbias = torch.empty(n, dtype=torch.float32, device=x.device) if want_dbias else None
-    ws, ws_ptr, ws_bytes = _colsum_ws(m, n, x.device) if want_dbias else (None, None, C.c_size_t(0))
+    ws, ws_ptr, ws_bytes = _colsum_ws(m, n, x.device) if want_dbias else (None, None, 0)
     rc = L.lib().krs_cross_epilogue_bwd(
-        L.ptr(g), L.ptr(u), L.ptr(x0), L.ptr(x), L.ptr(du), L.ptr(dx0), C.c_int(int(dx0_into is not None)),
-        L.ptr(dxd), L.ptr(dbias), C.c_int64(m), C.c_int64(n), C.c_int64(n), C.c_float(diag_scale or 0.0),
-        C.c_int(act), C.c_int(L.fdtype(x)), ws_ptr, ws_bytes, L.stream_ptr())
+        L.ptr(g), L.ptr(u), L.ptr(x0), L.ptr(x), L.ptr(du), L.ptr(dx0), int(dx0_into is not None),
+        L.ptr(dxd), L.ptr(dbias), m, n, n, diag_scale or 0.0,
+        act, L.fdtype(x), ws_ptr, ws_bytes, L.stream_ptr())
     L.check(rc, "krs_cross_epilogue_bwd")
     return du, dx0, dxd, dbias
 
@@ -173,25 +173,21 @@ def gemm_cross_bwd(a: torch.Tensor, bt: torch.Tensor, r: torch.Tensor, x0: torch
         if dx0_into is not None or r is None or beta != 1.0 or u_upper.dtype != a.dtype or tuple(u_upper.shape) != (m, n):
             raise L.KrsError("gemm_cross_bwd: u_upper needs R (beta = 1), no dx0 to accumulate into, and the operands' shape / dtype")
     dbias = torch.empty(n, dtype=torch.float32, device=a.device) if want_dbias else None
-    nbytes = int(L.lib().krs_gemm_cross_bwd_workspace_bytes(C.c_int64(m), C.c_int64(n))) if want_dbias else 0
+    nbytes = int(L.lib().krs_gemm_cross_bwd_workspace_bytes(m, n)) if want_dbias else 0
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device) if want_dbias else None
     # (its own span: the launch is a product AND five to seven [M, N] streams of elementwise work)
     with probe.span("gemm_cross_bwd", 2.0 * m * n * k):
         rc = L.lib().krs_gemm_cross_bwd(
-            L.ptr(a), C.c_int64(a.stride(0)), L.ptr(bt), C.c_int64(bt.stride(0)), L.ptr(r),
-            C.c_int64(r.stride(0) if r is not None else n),
-            C.c_float(beta), L.ptr(g), C.c_int64(n), L.ptr(x0), L.ptr(u), L.ptr(dz), L.ptr(dx0), C.c_int64(n),
-            C.c_int(int(dx0_into is not None)), L.ptr(u_upper), C.c_int(int(fold_direct)), L.ptr(dbias), C.c_int64(m),
-            C.c_int64(n),
-            C.c_int64(k), C.c_int(act),
-            C.c_int(L.fdtype(a)), L.ptr(ws), C.c_size_t(nbytes), L.stream_ptr())
+            L.ptr(a), a.stride(0), L.ptr(bt), bt.stride(0), L.ptr(r), r.stride(0) if r is not None else n, beta,
+            L.ptr(g), n, L.ptr(x0), L.ptr(u), L.ptr(dz), L.ptr(dx0), n, int(dx0_into is not None), L.ptr(u_upper),
+            int(fold_direct), L.ptr(dbias), m, n, k, act, L.fdtype(a), L.ptr(ws), nbytes, L.stream_ptr())
     L.check(rc, "krs_gemm_cross_bwd")
     return g, dz, dx0, dbias
 
 
 def gemm_dense_bwd(a: torch.Tensor, bt: torch.Tensor, y: torch.Tensor, act: int, want_dbias: bool = True,
                    want_g: bool = False):
-    """The dense form of krs_gemm_cross_bwd: dz = (A @ Bt^T) * act'(y) and dbias = column sums of dz in ONE launch -- the
+    """krs_gemm_dense_bwd: dz = (A @ Bt^T) * act'(y) and dbias = column sums of dz in ONE launch -- the
     data-gradient product of a Dense layer running the activation backward of the Dense layer BELOW it (whose saved output
     is y) in its epilogue.  want_g: the product G = A @ Bt^T (rounded once; dz is computed from it as stored) is written
     too -- the true dL/dy of that output; otherwise it is never stored.  a: [M, K], bt: [N, K], y: [M, N].
@@ -205,15 +201,13 @@ def gemm_dense_bwd(a: torch.Tensor, bt: torch.Tensor, y: torch.Tensor, act: int,
     dz = torch.empty((m, n), dtype=a.dtype, device=a.device)
     g = torch.empty_like(dz) if want_g else None
     dbias = torch.empty(n, dtype=torch.float32, device=a.device) if want_dbias else None
-    nbytes = int(L.lib().krs_gemm_cross_bwd_workspace_bytes(C.c_int64(m), C.c_int64(n))) if want_dbias else 0
+    nbytes = int(L.lib().krs_gemm_cross_bwd_workspace_bytes(m, n)) if want_dbias else 0
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device) if want_dbias else None
     with probe.span("gemm_dense_bwd", 2.0 * m * n * k):
-        rc = L.lib().krs_gemm_cross_bwd(
-            L.ptr(a), C.c_int64(a.stride(0)), L.ptr(bt), C.c_int64(bt.stride(0)), None, C.c_int64(n), C.c_float(0.0),
-            L.ptr(g), C.c_int64(n), None, L.ptr(y), L.ptr(dz), None, C.c_int64(n), C.c_int(0), None, C.c_int(0), L.ptr(dbias),
-            C.c_int64(m), C.c_int64(n), C.c_int64(k), C.c_int(act), C.c_int(L.fdtype(a)), L.ptr(ws), C.c_size_t(nbytes),
-            L.stream_ptr())
-    L.check(rc, "krs_gemm_cross_bwd (dense form)")
+        rc = L.lib().krs_gemm_dense_bwd(L.ptr(a), a.stride(0), L.ptr(bt), bt.stride(0), L.ptr(g), n, L.ptr(y),
+                                        L.ptr(dz), n, L.ptr(dbias), m, n, k, act, L.fdtype(a), L.ptr(ws), nbytes,
+                                        L.stream_ptr())
+    L.check(rc, "krs_gemm_dense_bwd")
     return dz, dbias, g
 
 
@@ -221,9 +215,10 @@ CROSS_BWD_ROUTES = {0: None, 1: "two_call", 2: "pp64", 3: "pp256"}
 
 
 def last_cross_bwd_route():
-    """(route, epilogue) of the calling thread's last krs_gemm_cross_bwd (gemm_cross_bwd / gemm_dense_bwd): route is
-    "two_call", "pp64" or "pp256" (fused, on that ring kernel), None when no launch was made; epilogue is the fused
-    epilogue number (3 .. 10), 0 otherwise.  A diagnostic for tests: it reads a host-side record, no device sync."""
+    """(route, epilogue) of the calling thread's last krs_gemm_cross_bwd / krs_gemm_dense_bwd (gemm_cross_bwd /
+    gemm_dense_bwd): route is "two_call", "pp64" or "pp256" (fused, on that ring kernel), None when no launch was made;
+    epilogue is the fused epilogue number (3 .. 10), 0 otherwise.  A diagnostic for tests: it reads a host-side record,
+    no device sync."""
     ep = C.c_int(0)
     route = int(L.lib().krs_gemm_cross_bwd_last_route(C.byref(ep)))
     return CROSS_BWD_ROUTES[route], int(ep.value)
@@ -233,8 +228,8 @@ def colsum(a: torch.Tensor) -> torch.Tensor:
     a = _rowmajor(a, "colsum")
     out = torch.empty(a.shape[1], dtype=torch.float32, device=a.device)
     ws, ws_ptr, ws_bytes = _colsum_ws(a.shape[0], a.shape[1], a.device)
-    rc = L.lib().krs_colsum(L.ptr(a), C.c_int64(a.stride(0)), C.c_int64(a.shape[0]), C.c_int64(a.shape[1]),
-                            C.c_int(L.fdtype(a)), L.ptr(out), ws_ptr, ws_bytes, L.stream_ptr())
+    rc = L.lib().krs_colsum(L.ptr(a), a.stride(0), a.shape[0], a.shape[1],
+                            L.fdtype(a), L.ptr(out), ws_ptr, ws_bytes, L.stream_ptr())
     L.check(rc, "krs_colsum")
     return out
 
@@ -252,11 +247,11 @@ def dense_act_bwd(g: torch.Tensor, y: torch.Tensor | None, act: int, want_dbias:
     dz = torch.empty((m, n), dtype=g.dtype, device=g.device) if need_dz else None
     db = torch.empty(n, dtype=torch.float32, device=g.device) if want_dbias else None
     if need_dz or want_dbias:
-        ws, ws_ptr, ws_bytes = _colsum_ws(m, n, g.device) if want_dbias else (None, None, C.c_size_t(0))
-        rc = L.lib().krs_dense_act_bwd(L.ptr(g), C.c_int64(g.stride(0)), L.ptr(y if need_dz else None),
-                                       C.c_int64(y.stride(0) if (y is not None and need_dz) else n),
-                                       L.ptr(dz), C.c_int64(n), L.ptr(db), C.c_int64(m), C.c_int64(n), C.c_int(act),
-                                       C.c_int(L.fdtype(g)), ws_ptr, ws_bytes, L.stream_ptr())
+        ws, ws_ptr, ws_bytes = _colsum_ws(m, n, g.device) if want_dbias else (None, None, 0)
+        rc = L.lib().krs_dense_act_bwd(L.ptr(g), g.stride(0), L.ptr(y if need_dz else None),
+                                       y.stride(0) if (y is not None and need_dz) else n,
+                                       L.ptr(dz), n, L.ptr(db), m, n, act,
+                                       L.fdtype(g), ws_ptr, ws_bytes, L.stream_ptr())
         L.check(rc, "krs_dense_act_bwd")
     return (dz if need_dz else g), db
 
@@ -288,10 +283,10 @@ def cast_transpose(w: torch.Tensor, dtype: torch.dtype, want_plain: bool = True,
     wt = torch.empty((cols, rows), dtype=dtype, device=w.device) if want_t else None
     write_plain = plain is not None and plain is not w
     if write_plain or want_t:
-        rc = L.lib().krs_cast_transpose(L.ptr(w), C.c_int64(rows), C.c_int64(cols), C.c_int64(w.stride(0)),
-                                        C.c_int(L.fdtype(w)), L.ptr(plain) if write_plain else None,
-                                        C.c_int64(cols), L.ptr(wt), C.c_int64(rows),
-                                        C.c_int(L.fdtype(plain if plain is not None else wt)), L.stream_ptr())
+        rc = L.lib().krs_cast_transpose(L.ptr(w), rows, cols, w.stride(0),
+                                        L.fdtype(w), L.ptr(plain) if write_plain else None,
+                                        cols, L.ptr(wt), rows,
+                                        L.fdtype(plain if plain is not None else wt), L.stream_ptr())
         L.check(rc, "krs_cast_transpose")
     return plain, wt
 
@@ -320,8 +315,8 @@ def refresh_casts(params) -> int:
             trans.append(buf[1])
         ptrs = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
         rc = L.lib().krs_cast_transpose_many(
-            C.c_int(n), ptrs(ps), (C.c_int64 * n)(*[p.shape[0] for p in ps]), (C.c_int64 * n)(*[p.shape[1] for p in ps]),
-            C.c_int(L.fdtype(ps[0])), ptrs(plains), ptrs(trans), C.c_int(L.fdtype(plains[0])), L.stream_ptr())
+            n, ptrs(ps), (C.c_int64 * n)(*[p.shape[0] for p in ps]), (C.c_int64 * n)(*[p.shape[1] for p in ps]),
+            L.fdtype(ps[0]), ptrs(plains), ptrs(trans), L.fdtype(plains[0]), L.stream_ptr())
         L.check(rc, "krs_cast_transpose_many")
         for p, a, b in zip(ps, plains, trans):
             # the C ABI rewrote these buffers behind torch's back: bump their version counters (host-side bookkeeping,
@@ -350,9 +345,9 @@ def dot_interaction_fwd(feats: Sequence[torch.Tensor], self_interaction=False, s
     out = torch.empty((batch, dot_out_cols(len(feats), self_interaction, skip_gather)), dtype=feats[0].dtype,
                       device=feats[0].device)
     ptrs, lds = _ptr_table(feats)
-    rc = L.lib().krs_dot_interaction_fwd(ptrs, lds, C.c_int(len(feats)), C.c_int64(batch), C.c_int(dim),
-                                         C.c_int(L.fdtype(feats[0])), C.c_int(int(self_interaction)),
-                                         C.c_int(int(skip_gather)), L.ptr(out), C.c_int64(out.stride(0)),
+    rc = L.lib().krs_dot_interaction_fwd(ptrs, lds, len(feats), batch, dim,
+                                         L.fdtype(feats[0]), int(self_interaction),
+                                         int(skip_gather), L.ptr(out), out.stride(0),
                                          L.stream_ptr())
     L.check(rc, "krs_dot_interaction_fwd")
     return out
@@ -387,11 +382,11 @@ def dot_interaction_bwd(feats: Sequence[torch.Tensor], grad_out: torch.Tensor, s
         grads = [None if i not in slot else outs[i] for i in range(n)]
     ptrs, lds = _ptr_table(feats)
     gptrs, glds = _ptr_table(outs)
-    rc = L.lib().krs_dot_interaction_bwd_accumulate(ptrs, lds, C.c_int(n), C.c_int64(batch), C.c_int(dim),
-                                                    C.c_int(L.fdtype(feats[0])), C.c_int(int(self_interaction)),
-                                                    C.c_int(int(skip_gather)), L.ptr(grad_out),
-                                                    C.c_int64(grad_out.stride(0)), gptrs, glds,
-                                                    C.c_uint64(int(accumulate_mask)), L.stream_ptr())
+    rc = L.lib().krs_dot_interaction_bwd_accumulate(ptrs, lds, n, batch, dim,
+                                                    L.fdtype(feats[0]), int(self_interaction),
+                                                    int(skip_gather), L.ptr(grad_out),
+                                                    grad_out.stride(0), gptrs, glds,
+                                                    int(accumulate_mask), L.stream_ptr())
     L.check(rc, "krs_dot_interaction_bwd_accumulate")
     return grads
 
@@ -404,10 +399,10 @@ def mod_bucketize(ids: torch.Tensor, n_shards: int):
     local = torch.empty_like(ids)
     perm = torch.empty(nnz, dtype=torch.int32, device=ids.device)
     counts = torch.empty(n_shards, dtype=torch.int64, device=ids.device)
-    wsb = L.lib().krs_mod_bucketize_workspace_bytes(C.c_int64(nnz), C.c_int(n_shards))
+    wsb = L.lib().krs_mod_bucketize_workspace_bytes(nnz, n_shards)
     ws = torch.empty(max(int(wsb), 1), dtype=torch.uint8, device=ids.device)
-    rc = L.lib().krs_mod_bucketize(L.ptr(ids), C.c_int(L.itype(ids)), C.c_int64(nnz), C.c_int(n_shards),
-                                   L.ptr(local), L.ptr(perm), L.ptr(counts), L.ptr(ws), C.c_size_t(ws.numel()),
+    rc = L.lib().krs_mod_bucketize(L.ptr(ids), L.itype(ids), nnz, n_shards,
+                                   L.ptr(local), L.ptr(perm), L.ptr(counts), L.ptr(ws), ws.numel(),
                                    L.stream_ptr())
     L.check(rc, "krs_mod_bucketize")
     return local, perm, counts
@@ -429,7 +424,7 @@ def bce_fwd_bwd(pred: torch.Tensor, labels: torch.Tensor, epsilon: float = 1e-7,
     loss = torch.empty((), dtype=torch.float32, device=pred.device)
     dp = torch.empty_like(p) if want_grad else None
     scratch = torch.empty(64, dtype=torch.float32, device=pred.device)     # KRS_BCE_MAX_BLOCKS partial sums
-    rc = L.lib().krs_bce_fwd_bwd(L.ptr(p), C.c_int(L.fdtype(p)), L.ptr(y), C.c_int64(p.numel()), C.c_float(epsilon),
-                                 C.c_float(grad_scale), L.ptr(loss), L.ptr(dp), L.ptr(scratch), L.stream_ptr())
+    rc = L.lib().krs_bce_fwd_bwd(L.ptr(p), L.fdtype(p), L.ptr(y), p.numel(), epsilon,
+                                 grad_scale, L.ptr(loss), L.ptr(dp), L.ptr(scratch), L.stream_ptr())
     L.check(rc, "krs_bce_fwd_bwd")
     return loss, (None if dp is None else dp.reshape(pred.shape))

@@ -90,8 +90,8 @@ class FusedBags:
             return
         n = len(self.tables)
         vals = (C.c_float * n)(*lrs)
-        rc = L.lib().krs_store_f32(C.c_void_p(self._tab_dev.data_ptr() + L.TABLE_DT.fields["lr"][1]), C.c_int64(L.TABLE_DT.itemsize),
-                                   vals, C.c_int(n), L.stream_ptr())
+        rc = L.lib().krs_store_f32(self._tab_dev.data_ptr() + L.TABLE_DT.fields["lr"][1], L.TABLE_DT.itemsize,
+                                   vals, n, L.stream_ptr())
         L.check(rc, "krs_store_f32")
         self._tab_key = self._tab_key[:2 * n] + tuple(lrs) + self._tab_key[3 * n:]
         if self._tab_host is not None:
@@ -136,12 +136,12 @@ class FusedBags:
         tdesc, fdesc = self.table_desc(), self.feature_desc(batch, hots, dev)
         with probe.span("k1"):
             rc = L.lib().krs_embed_bag_fwd(
-                L.ptr(tdesc), L.ptr(fdesc), C.c_int(n_feats),
-                L.ptr(ids), C.c_int(L.itype(ids)),
-                L.ptr(offsets), C.c_int(L.itype(offsets) if offsets is not None else L.I32),
-                L.ptr(weights), C.c_int64(ids.numel()), C.c_int(batch), C.c_int(self.dim),
-                C.c_int(L.fdtype(self.tables[0])),
-                L.ptr(out), C.c_int(L.fdtype(out)), C.c_int64(out.stride(0)),
+                L.ptr(tdesc), L.ptr(fdesc), n_feats,
+                L.ptr(ids), L.itype(ids),
+                L.ptr(offsets), L.itype(offsets) if offsets is not None else L.I32,
+                L.ptr(weights), ids.numel(), batch, self.dim,
+                L.fdtype(self.tables[0]),
+                L.ptr(out), L.fdtype(out), out.stride(0),
                 L.ptr(scale), L.ptr(err_flag), L.stream_ptr())
         L.check(rc, "krs_embed_bag_fwd")
         return out, scale
@@ -158,7 +158,7 @@ class FusedBags:
         ask for this form); for such a plan krs_embed_bag_bwd_sparse reports n_unique = -1 and backward_sparse raises KrsError."""
         L.require_device(ids, "ids")
         nnz = ids.numel()
-        nbytes = L.lib().krs_embed_bag_bwd_workspace_bytes(C.c_int64(nnz))
+        nbytes = L.lib().krs_embed_bag_bwd_workspace_bytes(nnz)
         # ws: a workspace the caller keeps across steps (autograd.EmbedBagFusedFn: the plan runs on a side stream, and a
         # fresh tensor per step there is a fresh hipMalloc per step for as long as the host runs ahead of the device)
         if ws is None or ws.numel() < max(int(nbytes), 1) or ws.device != ids.device:
@@ -169,19 +169,19 @@ class FusedBags:
             fh = self._feat_host[(batch, tuple(hots), str(ids.device))]
             with probe.span("k2_plan"):
                 rc = L.lib().krs_embed_bag_bwd_plan_tables(
-                    L.ptr(tdesc), th.ctypes.data_as(C.c_void_p), C.c_int(len(th)),
-                    L.ptr(fdesc), fh.ctypes.data_as(C.c_void_p), C.c_int(len(self.features)),
-                    L.ptr(ids), C.c_int(L.itype(ids)), C.c_int(batch), C.c_int64(nnz), C.c_int64(self.total_rows),
-                    L.ptr(ws), C.c_size_t(ws.numel()), L.ptr(err_flag), L.stream_ptr())
+                    L.ptr(tdesc), th.ctypes.data_as(C.c_void_p), len(th),
+                    L.ptr(fdesc), fh.ctypes.data_as(C.c_void_p), len(self.features),
+                    L.ptr(ids), L.itype(ids), batch, nnz, self.total_rows,
+                    L.ptr(ws), ws.numel(), L.ptr(err_flag), L.stream_ptr())
             L.check(rc, "krs_embed_bag_bwd_plan_tables")
             return ws
         with probe.span("k2_plan"):
             rc = L.lib().krs_embed_bag_bwd_plan(
                 L.ptr(tdesc), L.ptr(fdesc),
-                C.c_int(len(self.features)), L.ptr(ids), C.c_int(L.itype(ids)),
-                L.ptr(offsets), C.c_int(L.itype(offsets) if offsets is not None else L.I32),
-                C.c_int(batch), C.c_int64(nnz), C.c_int64(self.total_rows),
-                L.ptr(ws), C.c_size_t(ws.numel()), L.ptr(err_flag), L.stream_ptr())
+                len(self.features), L.ptr(ids), L.itype(ids),
+                L.ptr(offsets), L.itype(offsets) if offsets is not None else L.I32,
+                batch, nnz, self.total_rows,
+                L.ptr(ws), ws.numel(), L.ptr(err_flag), L.stream_ptr())
         L.check(rc, "krs_embed_bag_bwd_plan")
         return ws
 
@@ -199,9 +199,9 @@ class FusedBags:
             out = [torch.zeros(t.shape, dtype=torch.float32, device=grad.device) for t in self.tables]
         gdesc = self.table_desc(weights=list(out), slots=[None] * len(out))
         rc = L.lib().krs_embed_bag_bwd_dense(
-            L.ptr(gdesc), C.c_int(len(out)), L.ptr(fdesc), C.c_int(len(self.features)),
-            L.ptr(weights), L.ptr(bag_scale), L.ptr(grad), C.c_int(L.fdtype(grad)),
-            C.c_int64(grad.stride(0)), C.c_int(batch), C.c_int(self.dim), C.c_int64(nnz),
+            L.ptr(gdesc), len(out), L.ptr(fdesc), len(self.features),
+            L.ptr(weights), L.ptr(bag_scale), L.ptr(grad), L.fdtype(grad),
+            grad.stride(0), batch, self.dim, nnz,
             L.ptr(ws), L.stream_ptr())
         L.check(rc, "krs_embed_bag_bwd_dense")
         return list(out)
@@ -213,10 +213,9 @@ class FusedBags:
         grad, fdesc = self._apply_common(grad, batch, hots)
         if kind != "sgd" and any(s is None for s in self.slots):
             raise L.KrsError(f"fused {kind} needs a slot buffer per table")
-        head = (L.ptr(self.table_desc()), C.c_int(len(self.tables)), L.ptr(fdesc),
-                C.c_int(len(self.features)), L.ptr(weights), L.ptr(bag_scale), L.ptr(grad),
-                C.c_int(L.fdtype(grad)), C.c_int64(grad.stride(0)), C.c_int(batch), C.c_int(self.dim),
-                C.c_int(L.fdtype(self.tables[0])), C.c_int64(nnz))
+        head = (L.ptr(self.table_desc()), len(self.tables), L.ptr(fdesc), len(self.features), L.ptr(weights),
+                L.ptr(bag_scale), L.ptr(grad), L.fdtype(grad), grad.stride(0), batch, self.dim,
+                L.fdtype(self.tables[0]), nnz)
         tail = (L.ptr(ws), L.stream_ptr())
         if kind in ("sgd", "adagrad", "adagrad_rowwise"):
             fn = {"sgd": L.lib().krs_embed_bag_bwd_fused_sgd, "adagrad": L.lib().krs_embed_bag_bwd_fused_adagrad,
@@ -230,13 +229,13 @@ class FusedBags:
                 # bias correction kept in device memory (StepConstants): the launch reads it when it RUNS
                 L.require_device(hyper[3], "Adam bias correction")
                 with probe.span("k2_apply"):
-                    rc = L.lib().krs_embed_bag_bwd_fused_adam_dyn(*head, *(C.c_float(float(h)) for h in hyper[:3]),
+                    rc = L.lib().krs_embed_bag_bwd_fused_adam_dyn(*head, *(float(h) for h in hyper[:3]),
                                                                   L.ptr(hyper[3]), *tail)
                 L.check(rc, "krs_embed_bag_bwd_fused_adam_dyn")
                 return
             fn = {"adam": L.lib().krs_embed_bag_bwd_fused_adam, "ftrl": L.lib().krs_embed_bag_bwd_fused_ftrl}[kind]
             with probe.span("k2_apply"):
-                rc = fn(*head, *(C.c_float(float(h)) for h in hyper), *tail)
+                rc = fn(*head, *(float(h) for h in hyper), *tail)
         else:
             raise L.KrsError(f"unknown fused optimizer {kind!r}")
         L.check(rc, f"krs_embed_bag_bwd_fused_{kind}")
@@ -249,9 +248,9 @@ class FusedBags:
         vals = torch.empty((max(nnz, 1), self.dim), dtype=torch.float32, device=dev)
         n_u = torch.zeros(1, dtype=torch.int64, device=dev)
         rc = L.lib().krs_embed_bag_bwd_sparse(
-            L.ptr(fdesc), C.c_int(len(self.features)), L.ptr(weights), L.ptr(bag_scale), L.ptr(grad),
-            C.c_int(L.fdtype(grad)), C.c_int64(grad.stride(0)), C.c_int(batch), C.c_int(self.dim),
-            C.c_int64(nnz), L.ptr(ws), L.ptr(rows), L.ptr(vals), L.ptr(n_u), L.stream_ptr())
+            L.ptr(fdesc), len(self.features), L.ptr(weights), L.ptr(bag_scale), L.ptr(grad),
+            L.fdtype(grad), grad.stride(0), batch, self.dim,
+            nnz, L.ptr(ws), L.ptr(rows), L.ptr(vals), L.ptr(n_u), L.stream_ptr())
         L.check(rc, "krs_embed_bag_bwd_sparse")
         u = int(n_u.item())
         if u < 0:
@@ -289,7 +288,7 @@ class StepConstants:
                 self.bias_correction = torch.ones(1, dtype=torch.float32, device=self.bags_of().tables[0].device)
             b1, b2 = self.adam_betas
             bc = math.sqrt(1.0 - b2 ** o.step) / (1.0 - b1 ** o.step)
-            rc = L.lib().krs_store_f32(L.ptr(self.bias_correction), C.c_int64(4), (C.c_float * 1)(bc), C.c_int(1), L.stream_ptr())
+            rc = L.lib().krs_store_f32(L.ptr(self.bias_correction), 4, (C.c_float * 1)(bc), 1, L.stream_ptr())
             L.check(rc, "krs_store_f32")
 
     def on_backward(self) -> None:

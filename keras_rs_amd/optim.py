@@ -54,8 +54,8 @@ class Adagrad(torch.optim.Optimizer):
                 continue
             arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
             sizes = (C.c_int64 * n)(*[t.numel() for t in ps])
-            rc = L.lib().krs_dense_adagrad(arr(ps), arr(gs), arr(accs), sizes, C.c_int(n), C.c_float(group["lr"]),
-                                           C.c_float(group["eps"]), L.stream_ptr())
+            rc = L.lib().krs_dense_adagrad(arr(ps), arr(gs), arr(accs), sizes, n, group["lr"], group["eps"],
+                                           L.stream_ptr())
             L.check(rc, "krs_dense_adagrad")
             # weights created with a constraint (Layer.add_weight(constraint=...)) are projected behind their update, as
             # a Keras optimizer does; the in-place copy moves the version counter, so their cached casts are rebuilt

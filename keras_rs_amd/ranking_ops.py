@@ -6,8 +6,6 @@ graph.  Each returns (unreduced loss or None, dL/dlogits or None).
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from keras_rs_amd import _lib as L
@@ -48,9 +46,8 @@ def pairwise_loss(kind: str, logits: torch.Tensor, labels: torch.Tensor, mask: t
     gw = _weights(g, (b, n), x.device)
     loss = torch.empty((b, n), dtype=torch.float32, device=x.device) if want_loss else None
     dx = torch.empty((b, n), dtype=x.dtype, device=x.device) if want_grad else None
-    rc = L.lib().krs_pairwise_loss(C.c_int(PAIRWISE_KINDS[kind]), L.ptr(x), C.c_int64(ld), C.c_int(L.fdtype(x)),
-                                   L.ptr(y), L.ptr(m), L.ptr(gw), C.c_float(g_scale), C.c_float(inv_temperature),
-                                   C.c_int64(b), C.c_int64(n), L.ptr(loss), L.ptr(dx), L.stream_ptr())
+    rc = L.lib().krs_pairwise_loss(PAIRWISE_KINDS[kind], L.ptr(x), ld, L.fdtype(x), L.ptr(y), L.ptr(m), L.ptr(gw),
+                                   g_scale, inv_temperature, b, n, L.ptr(loss), L.ptr(dx), L.stream_ptr())
     L.check(rc, "krs_pairwise_loss")
     return loss, dx
 
@@ -65,8 +62,8 @@ def listmle_loss(logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor 
     gw = _weights(g, (b,), x.device)
     loss = torch.empty((b,), dtype=torch.float32, device=x.device) if want_loss else None
     dx = torch.empty((b, n), dtype=x.dtype, device=x.device) if want_grad else None
-    rc = L.lib().krs_listmle_loss(L.ptr(x), C.c_int64(ld), C.c_int(L.fdtype(x)), L.ptr(y), L.ptr(m), L.ptr(gw),
-                                  C.c_float(g_scale), C.c_float(inv_temperature), C.c_int64(b), C.c_int64(n),
+    rc = L.lib().krs_listmle_loss(L.ptr(x), ld, L.fdtype(x), L.ptr(y), L.ptr(m), L.ptr(gw),
+                                  g_scale, inv_temperature, b, n,
                                   L.ptr(loss), L.ptr(dx), L.stream_ptr())
     L.check(rc, "krs_listmle_loss")
     return loss, dx

@@ -6,8 +6,6 @@ device, so a call can be captured into a HIP graph.
 
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from keras_rs_amd import _lib as L
@@ -26,13 +24,12 @@ def _rowmajor(t: torch.Tensor, what: str) -> torch.Tensor:
 
 
 def topk_rows_workspace_bytes(rows: int, cols: int, k: int) -> int:
-    return int(L.lib().krs_topk_rows_workspace_bytes(C.c_int64(rows), C.c_int64(cols), C.c_int(k)))
+    return int(L.lib().krs_topk_rows_workspace_bytes(rows, cols, k))
 
 
 def retrieval_topk_workspace_bytes(b: int, n: int, d: int, k: int, dtype: torch.dtype) -> int:
     dt = L.BF16 if dtype == torch.bfloat16 else L.F32
-    return int(L.lib().krs_retrieval_topk_workspace_bytes(C.c_int64(b), C.c_int64(n), C.c_int64(d), C.c_int(k),
-                                                          C.c_int(dt)))
+    return int(L.lib().krs_retrieval_topk_workspace_bytes(b, n, d, k, dt))
 
 
 def topk_rows(x: torch.Tensor, k: int, *, boost: torch.Tensor | None = None, boost_scale: float = 0.0,
@@ -52,9 +49,8 @@ def topk_rows(x: torch.Tensor, k: int, *, boost: torch.Tensor | None = None, boo
     idx = torch.empty((rows, k), dtype=torch.int32, device=x.device)
     keys = torch.empty((rows, k), dtype=torch.float32, device=x.device) if want_keys else None
     ws = torch.empty(max(1, topk_rows_workspace_bytes(rows, cols, k)), dtype=torch.uint8, device=x.device)
-    rc = L.lib().krs_topk_rows(L.ptr(x), L.ptr(boost), C.c_float(boost_scale), C.c_int64(x.stride(0) if rows else cols),
-                               C.c_int(L.fdtype(x)), C.c_int64(rows), C.c_int64(cols), C.c_int(k), L.ptr(idx),
-                               L.ptr(keys), L.ptr(ws), C.c_size_t(ws.numel()), L.stream_ptr())
+    rc = L.lib().krs_topk_rows(L.ptr(x), L.ptr(boost), boost_scale, x.stride(0) if rows else cols, L.fdtype(x), rows,
+                               cols, k, L.ptr(idx), L.ptr(keys), L.ptr(ws), ws.numel(), L.stream_ptr())
     L.check(rc, "krs_topk_rows")
     return (idx, keys) if want_keys else idx
 
@@ -78,9 +74,9 @@ def retrieval_topk(query: torch.Tensor, candidates: torch.Tensor, k: int, *, ids
     scores = torch.empty((b, k), dtype=q.dtype, device=q.device) if want_scores else None
     out_ids = torch.empty((b, k), dtype=torch.int32, device=q.device)
     ws = torch.empty(max(1, retrieval_topk_workspace_bytes(b, n, d, k, q.dtype)), dtype=torch.uint8, device=q.device)
-    rc = L.lib().krs_retrieval_topk(L.ptr(q), C.c_int64(q.stride(0) if b else d), L.ptr(c), C.c_int64(c.stride(0)),
-                                    L.ptr(ids), C.c_int(L.fdtype(q)), C.c_int64(b), C.c_int64(n), C.c_int64(d),
-                                    C.c_int(k), L.ptr(scores), L.ptr(out_ids), L.ptr(ws), C.c_size_t(ws.numel()),
+    rc = L.lib().krs_retrieval_topk(L.ptr(q), q.stride(0) if b else d, L.ptr(c), c.stride(0),
+                                    L.ptr(ids), L.fdtype(q), b, n, d,
+                                    k, L.ptr(scores), L.ptr(out_ids), L.ptr(ws), ws.numel(),
                                     L.stream_ptr())
     L.check(rc, "krs_retrieval_topk")
     return scores, out_ids

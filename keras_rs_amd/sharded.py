@@ -117,15 +117,15 @@ class HipShardKernels:
         seg_grow = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         bag_seg = torch.empty((max(n_bags, 1), n_shards), dtype=torch.int32, device=dev)
         counts = torch.empty((3, n_shards), dtype=torch.int64, device=dev)
-        wsb = int(L.lib().krs_shard_route_workspace_bytes(C.c_int64(nnz), C.c_int64(n_bags), C.c_int(n_shards)))
+        wsb = int(L.lib().krs_shard_route_workspace_bytes(nnz, n_bags, n_shards))
         ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
         if weights is not None and weights.dtype != torch.float32:
             weights = weights.float()
         rc = L.lib().krs_shard_route(
-            L.ptr(ddev), desc.ctypes.data_as(C.c_void_p), C.c_int(n_feats), L.ptr(ids), C.c_int(L.itype(ids)),
-            L.ptr(offsets), C.c_int(L.itype(offsets) if offsets is not None else L.I32), L.ptr(weights),
-            C.c_int64(nnz), C.c_int(batch), C.c_int(n_shards), C.c_int(int(emit_w)), L.ptr(packed), L.ptr(seg_bag),
-            L.ptr(seg_grow), L.ptr(bag_seg), L.ptr(counts), L.ptr(err_flag), L.ptr(ws), C.c_size_t(ws.numel()),
+            L.ptr(ddev), desc.ctypes.data_as(C.c_void_p), n_feats, L.ptr(ids), L.itype(ids),
+            L.ptr(offsets), L.itype(offsets) if offsets is not None else L.I32, L.ptr(weights),
+            nnz, batch, n_shards, int(emit_w), L.ptr(packed), L.ptr(seg_bag),
+            L.ptr(seg_grow), L.ptr(bag_seg), L.ptr(counts), L.ptr(err_flag), L.ptr(ws), ws.numel(),
             L.stream_ptr())
         L.check(rc, "krs_shard_route")
         return dict(packed=packed, seg_grow=seg_grow, bag_seg=bag_seg, counts=counts)
@@ -138,11 +138,11 @@ class HipShardKernels:
         rows = torch.empty(max(n_cnt, 1), dtype=torch.int32, device=dev)
         w = torch.empty(max(n_cnt, 1), dtype=torch.float32, device=dev) if weighted else None
         off = torch.empty(n_seg + 1, dtype=torch.int32, device=dev)
-        wsb = int(L.lib().krs_shard_unpack_workspace_bytes(C.c_int64(n_seg)))
+        wsb = int(L.lib().krs_shard_unpack_workspace_bytes(n_seg))
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         arr = lambda v: (C.c_int64 * n)(*[int(x) for x in v])  # noqa: E731
-        rc = L.lib().krs_shard_unpack(L.ptr(packed), C.c_int(n), arr(lookups), arr(segments), C.c_int(int(weighted)),
-                                      L.ptr(rows), L.ptr(w), L.ptr(off), L.ptr(ws), C.c_size_t(wsb), L.stream_ptr())
+        rc = L.lib().krs_shard_unpack(L.ptr(packed), n, arr(lookups), arr(segments), int(weighted),
+                                      L.ptr(rows), L.ptr(w), L.ptr(off), L.ptr(ws), wsb, L.stream_ptr())
         L.check(rc, "krs_shard_unpack")
         return rows[:n_cnt], (None if w is None else w[:n_cnt]), off
 
@@ -157,22 +157,22 @@ class HipShardKernels:
             ddev = self._desc_cache[key] = L.struct_to_device(desc, dev)
         nnz, n_feats = ids.numel(), len(desc)
         n_bags = batch * n_feats
-        words = int(L.lib().krs_shard_static_block_words(C.c_int64(cap_l), C.c_int64(cap_s), C.c_int(int(emit_w))))
+        words = int(L.lib().krs_shard_static_block_words(cap_l, cap_s, int(emit_w)))
         packed = torch.empty((n_shards, words), dtype=torch.int32, device=dev)
         seg_bag = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         seg_grow = torch.empty(n_shards * cap_s, dtype=torch.int32, device=dev)
         bag_seg = torch.empty((max(n_bags, 1), n_shards), dtype=torch.int32, device=dev)
         counts = torch.empty((3, n_shards), dtype=torch.int64, device=dev)
-        wsb = int(L.lib().krs_shard_route_workspace_bytes(C.c_int64(nnz), C.c_int64(n_bags), C.c_int(n_shards)))
+        wsb = int(L.lib().krs_shard_route_workspace_bytes(nnz, n_bags, n_shards))
         ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
         if weights is not None and weights.dtype != torch.float32:
             weights = weights.float()
         rc = L.lib().krs_shard_route_static(
-            L.ptr(ddev), desc.ctypes.data_as(C.c_void_p), C.c_int(n_feats), L.ptr(ids), C.c_int(L.itype(ids)),
-            L.ptr(offsets), C.c_int(L.itype(offsets) if offsets is not None else L.I32), L.ptr(weights),
-            C.c_int64(nnz), C.c_int(batch), C.c_int(n_shards), C.c_int(int(emit_w)), C.c_int64(cap_l), C.c_int64(cap_s),
+            L.ptr(ddev), desc.ctypes.data_as(C.c_void_p), n_feats, L.ptr(ids), L.itype(ids),
+            L.ptr(offsets), L.itype(offsets) if offsets is not None else L.I32, L.ptr(weights),
+            nnz, batch, n_shards, int(emit_w), cap_l, cap_s,
             L.ptr(packed), L.ptr(seg_bag), L.ptr(seg_grow), L.ptr(bag_seg), L.ptr(counts), L.ptr(err_flag), L.ptr(ws),
-            C.c_size_t(ws.numel()), L.stream_ptr())
+            ws.numel(), L.stream_ptr())
         L.check(rc, "krs_shard_route_static")
         return dict(packed=packed, seg_grow=seg_grow, bag_seg=bag_seg, counts=counts)
 
@@ -184,19 +184,19 @@ class HipShardKernels:
         w = torch.empty(n * cap_l, dtype=torch.float32, device=dev) if weighted else None
         off = torch.empty(n * cap_s + 1, dtype=torch.int32, device=dev)
         stats = torch.empty(4, dtype=torch.int64, device=dev)
-        wsb = int(L.lib().krs_shard_unpack_workspace_bytes(C.c_int64(n * cap_s)))
+        wsb = int(L.lib().krs_shard_unpack_workspace_bytes(n * cap_s))
         ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-        rc = L.lib().krs_shard_unpack_static(L.ptr(packed), C.c_int(n), C.c_int64(cap_l), C.c_int64(cap_s),
-                                             C.c_int(int(weighted)), L.ptr(rows), L.ptr(w), L.ptr(off), L.ptr(stats),
-                                             L.ptr(ws), C.c_size_t(wsb), L.stream_ptr())
+        rc = L.lib().krs_shard_unpack_static(L.ptr(packed), n, cap_l, cap_s,
+                                             int(weighted), L.ptr(rows), L.ptr(w), L.ptr(off), L.ptr(stats),
+                                             L.ptr(ws), wsb, L.stream_ptr())
         L.check(rc, "krs_shard_unpack_static")
         return rows, w, off, stats
 
     def combine(self, partials, bag_seg, batch: int, n_feats: int, dim: int, out):
         """krs_shard_combine into `out` (a [batch, n_feats*dim] row-major window of the slab)."""
-        rc = L.lib().krs_shard_combine(L.ptr(partials), L.ptr(bag_seg), C.c_int(batch), C.c_int(n_feats),
-                                       C.c_int(bag_seg.shape[1]), C.c_int(dim), C.c_int(L.fdtype(out)), L.ptr(out),
-                                       C.c_int64(out.stride(0)), L.stream_ptr())
+        rc = L.lib().krs_shard_combine(L.ptr(partials), L.ptr(bag_seg), batch, n_feats,
+                                       bag_seg.shape[1], dim, L.fdtype(out), L.ptr(out),
+                                       out.stride(0), L.stream_ptr())
         L.check(rc, "krs_shard_combine")
         return out
 
@@ -265,8 +265,7 @@ class _HostCounts:
     def read(self, dev_counts: torch.Tensor) -> list:
         n = dev_counts.numel()
         self.seq += 1
-        rc = L.lib().krs_publish_i64(L.ptr(dev_counts), C.c_int(n), C.c_void_p(self.buf.data_ptr()),
-                                     C.c_int64(self.seq), L.stream_ptr())
+        rc = L.lib().krs_publish_i64(L.ptr(dev_counts), n, self.buf.data_ptr(), self.seq, L.stream_ptr())
         L.check(rc, "krs_publish_i64")
         flag = self.buf[n:n + 1]
         t0 = time.monotonic()

@@ -66,14 +66,13 @@ if a.copyref:
     for _ in range(10): dst.copy_(src)
     e1.record(); torch.cuda.synchronize()
     print(json.dumps({"copy_GBps": 2 * 10 * (1 << 30) / (e0.elapsed_time(e1) * 1e-3) / 1e9}))
-import ctypes as _C
 from keras_rs_amd import _lib as _L
 _variants = [(b, h) for b in (a.bpgs.split(",") if a.bpgs else [""]) for h in (a.hotrows.split(",") if a.hotrows else [""])]
 for bpg, hr in _variants:
     if bpg:
         os.environ["KRS_BPG"] = bpg
     if hr != "":
-        _L.check(_L.lib().krs_embed_set_option(_C.c_int(3), _C.c_int(int(hr))), "set_option")
+        _L.check(_L.lib().krs_embed_set_option(3, int(hr)), "set_option")
     for _ in range(3):
         fb.forward(ids, a.batch, hots=hots, out=out)
     torch.cuda.synchronize()
@@ -91,7 +90,7 @@ for bpg, hr in _variants:
                       "min_us": float(ts.min() * 1e6), "lookups_per_s": nnz / float(np.median(ts)),
                       "GBps": bytes_ / float(np.median(ts)) / 1e9, "frac_of_8TBps": bytes_ / float(np.median(ts)) / 8e12}))
     
-_L.lib().krs_embed_set_option(_C.c_int(3), _C.c_int(0))
+_L.lib().krs_embed_set_option(3, 0)
 # ---- K2 timings (plan = sort; apply = fused Adagrad) ----
 def timeit(fn, iters=10):
     for _ in range(2):
@@ -110,9 +109,8 @@ if not a.fmajor_out:
     grad = (torch.rand(a.batch, a.tables * a.dim, device=dev) * 1e-3).to(dt)
     nnz = ids.numel()
     from keras_rs_amd import _lib as L
-    import ctypes as C
     for pv in (1, 0, 1, 0):          # KRS_EMBED_OPT_PLAN: 1 = global sort, 0 = table-segmented sort
-        L.check(L.lib().krs_embed_set_option(C.c_int(2), C.c_int(pv)), "set_option")
+        L.check(L.lib().krs_embed_set_option(2, pv), "set_option")
         print(json.dumps({"plan_variant": pv, "k2_plan_us": timeit(lambda: fb.plan_backward(ids, a.batch, hots=hots, global_order=False)) * 1e6}))
     t_plan = timeit(lambda: fb.plan_backward(ids, a.batch, hots=hots, global_order=False))
     ws = fb.plan_backward(ids, a.batch, hots=hots, global_order=False)

@@ -1,10 +1,9 @@
-"""The fused backward hand-offs (krs_gemm_cross_bwd): the dense form of the fused kernel against a float64 reference and
+"""The fused backward hand-offs (krs_gemm_cross_bwd, krs_gemm_dense_bwd): the dense form of the fused kernel against a float64 reference and
 against its own two-call form, at shapes on both sides of the fused gate; and every gradient a caller can observe around
 the three hand-offs that ride in it (Dense -> Dense, cross -> cross, Dense over a cross stack) and the DotInteraction ->
 slab join, against the same model with the fusions switched off."""
 
 import contextlib
-import ctypes as C
 
 import pytest
 import torch
@@ -23,17 +22,17 @@ def _lib():
 def _pipeline(v):
     """krs_gemm_set_option(KRS_GEMM_OPT_PIPELINE, v) for the block; back to the default ring (4) afterwards."""
     L = _lib()
-    L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(v)), "krs_gemm_set_option")
+    L.check(L.lib().krs_gemm_set_option(0, v), "krs_gemm_set_option")
     try:
         yield
     finally:
-        L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(4)), "krs_gemm_set_option")
+        L.check(L.lib().krs_gemm_set_option(0, 4), "krs_gemm_set_option")
 
 
-# ---- B. the dense form of krs_gemm_cross_bwd: dz = (A Bt^T) act'(y), dbias = column sums of dz ---------------------------
+# ---- B. the dense form, krs_gemm_dense_bwd: dz = (A Bt^T) act'(y), dbias = column sums of dz ----------------------------
 
 def _expected_route(m, n, k, pipe, aligned):
-    """The fused gate of krs_gemm_cross_bwd (bf16): >= 192 tiles of 256 x 256, k >= 256 and k % 64 == 0, every stride and
+    """The fused gate of krs_gemm_cross_bwd / krs_gemm_dense_bwd (bf16): >= 192 tiles of 256 x 256, k >= 256 and k % 64 == 0, every stride and
     pointer 8-element / 16-byte aligned; pipeline 4 takes the 64-k ring (gemm_pp64_kernel), 5 the 32-k one."""
     tiles = -(-m // 256) * -(-n // 256)
     if pipe == 0 or not aligned or m < 256 or n < 256 or k < 256 or k % 64 or tiles < 192:
@@ -157,8 +156,9 @@ def test_dense_form_against_float64_and_its_two_call_form(shape, pipe):
 
 
 def test_dense_form_empty_and_refused_calls():
-    """m = 0 / n = 0: nothing launched, the bias gradient of no rows is zeros; k = 0, mismatched shapes / dtypes and the
-    operands the dense form does not take are refused with KrsError."""
+    """m = 0 / n = 0: nothing launched, the bias gradient of no rows is zeros; k = 0 and mismatched shapes / dtypes are
+    refused with KrsError; krs_gemm_cross_bwd refuses the dense form's x0 = NULL (with R: operands the dense form does not
+    take) and names the dense form's own entry."""
     L = _lib()
     from keras_rs_amd import dense_ops as D
 
@@ -178,13 +178,15 @@ def test_dense_form_empty_and_refused_calls():
         D.gemm_dense_bwd(bf(300, 64), bf(300, 64), bf(300, 200), L.ACT_RELU)       # y not [m, n]
     with pytest.raises(L.KrsError):
         D.gemm_dense_bwd(bf(300, 64), bf(300, 64).float(), bf(300, 300), L.ACT_RELU)
-    # the dense form (x0 = NULL) takes no R / dx0
+    # the dense form (x0 = NULL) takes no R / dx0; krs_gemm_cross_bwd now refuses x0 = NULL as a null operand and names
+    # krs_gemm_dense_bwd
     a, bt, y, dz, r = bf(300, 64), bf(300, 64), bf(300, 300), bf(300, 300), bf(300, 300)
     rc = L.lib().krs_gemm_cross_bwd(
-        L.ptr(a), C.c_int64(64), L.ptr(bt), C.c_int64(64), L.ptr(r), C.c_int64(300), C.c_float(1.0), None, C.c_int64(300),
-        None, L.ptr(y), L.ptr(dz), None, C.c_int64(300), C.c_int(0), None, C.c_int(0), None, C.c_int64(300),
-        C.c_int64(300), C.c_int64(64), C.c_int(L.ACT_RELU), C.c_int(L.fdtype(a)), None, C.c_size_t(0), L.stream_ptr())
+        L.ptr(a), 64, L.ptr(bt), 64, L.ptr(r), 300, 1.0, None, 300,
+        None, L.ptr(y), L.ptr(dz), None, 300, 0, None, 0, None, 300,
+        300, 64, L.ACT_RELU, L.fdtype(a), None, 0, L.stream_ptr())
     assert rc != 0 and b"dense form" in L.lib().krs_last_error()
+    assert b"null operand" in L.lib().krs_last_error() and b"krs_gemm_dense_bwd" in L.lib().krs_last_error()
     assert D.last_cross_bwd_route() == (None, 0)
 
 

@@ -396,7 +396,6 @@ def test_bias_gradients_are_two_stage_sums_identical_from_run_to_run(dt, m, n):
     """krs_colsum_workspace_bytes: with the workspace the three column sums of the path (cross bias, Dense bias, colsum)
     are formed per row group and then over the groups IN ORDER -- the same bits on every run -- and agree with the
     workspace-free form of the C ABI (fp32 atomics over the same groups) to rounding; a short workspace is refused."""
-    import ctypes as C
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd import dense_ops as D
@@ -414,16 +413,14 @@ def test_bias_gradients_are_two_stage_sums_identical_from_run_to_run(dt, m, n):
     np.testing.assert_allclose(runs[0][2].cpu().numpy(), to_f32(to_np(g)).astype(np.float64).sum(0), rtol=0,
                                atol=2e-6 * scale * np.sqrt(m))
     # workspace-free form of the ABI (atomics): same groups, other order
-    nbytes = L.lib().krs_colsum_workspace_bytes(C.c_int64(m), C.c_int64(n))
+    nbytes = L.lib().krs_colsum_workspace_bytes(m, n)
     assert nbytes >= 4 * n
     out = torch.empty(n, dtype=torch.float32, device=DEV)
-    rc = L.lib().krs_colsum(L.ptr(g), C.c_int64(n), C.c_int64(m), C.c_int64(n), C.c_int(L.fdtype(g)), L.ptr(out), None,
-                            C.c_size_t(0), L.stream_ptr())
+    rc = L.lib().krs_colsum(L.ptr(g), n, m, n, L.fdtype(g), L.ptr(out), None, 0, L.stream_ptr())
     assert rc == 0
     np.testing.assert_allclose(out.cpu().numpy(), runs[0][2].cpu().numpy(), rtol=0, atol=1e-6 * scale * np.sqrt(m))
     ws = torch.empty(max(nbytes // 2, 4), dtype=torch.uint8, device=DEV)
-    rc = L.lib().krs_colsum(L.ptr(g), C.c_int64(n), C.c_int64(m), C.c_int64(n), C.c_int(L.fdtype(g)), L.ptr(out), L.ptr(ws),
-                            C.c_size_t(nbytes // 2), L.stream_ptr())
+    rc = L.lib().krs_colsum(L.ptr(g), n, m, n, L.fdtype(g), L.ptr(out), L.ptr(ws), nbytes // 2, L.stream_ptr())
     assert rc != 0 and b"workspace too small" in L.lib().krs_last_error()
 
 
@@ -494,7 +491,6 @@ def test_fused_cross_backward_every_epilogue_form_against_the_two_call_form_at_r
     (EPI 7) and dx0 = NULL (EPI 8), with and without an activation, on the ring kernel `pipe` selects (the route and
     epilogue each call took are asserted).  G, dz and dx0 bit for bit (EPI 7's dx0: the fused form rounds R*u_upper + G*u
     once, the two calls twice -- one ulp of the larger term); dbias to fp32 summation order."""
-    import ctypes as C
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd import dense_ops as D
@@ -512,7 +508,7 @@ def test_fused_cross_backward_every_epilogue_form_against_the_two_call_form_at_r
                                 u_upper=form.get("u_upper"), want_dx0=form.get("want_dx0", True))
 
     def set_pipe(v):
-        L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(v)), "krs_gemm_set_option")
+        L.check(L.lib().krs_gemm_set_option(0, v), "krs_gemm_set_option")
 
     def epilogue(form):
         if form.get("u_upper") is not None:
@@ -550,7 +546,6 @@ def test_ring_gemm_equals_the_two_stage_kernels_bit_for_bit():
     """krs_gemm's ring kernel (256 x 256 tiles, pipeline 4) against the 128 x 128 two-stage kernels (pipeline 0) on the
     three operand layouts of a cross layer at shapes with partial tiles: same fragment layout, same k order per
     accumulator -> identical bits (plain, cross-epilogue and residual forms; the weight gradient through split-K)."""
-    import ctypes as C
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd import dense_ops as D
@@ -570,14 +565,14 @@ def test_ring_gemm_equals_the_two_stage_kernels_bit_for_bit():
         return h, y, uo, dx, dk
 
     try:
-        L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(4)), "krs_gemm_set_option")
+        L.check(L.lib().krs_gemm_set_option(0, 4), "krs_gemm_set_option")
         ring = products()         # default: the 64-k ring (gemm_pp64_kernel) for the K-contiguous products, K = 1088 and 512
-        L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(5)), "krs_gemm_set_option")
+        L.check(L.lib().krs_gemm_set_option(0, 5), "krs_gemm_set_option")
         ring32 = products()       # the 32-k ring (gemm_pp256_kernel) for all of them
-        L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(0)), "krs_gemm_set_option")
+        L.check(L.lib().krs_gemm_set_option(0, 0), "krs_gemm_set_option")
         ref = products()
     finally:
-        L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(4))
+        L.lib().krs_gemm_set_option(0, 4)
     for got in (ring, ring32):
         for name, a, b in zip(("h", "y", "u", "dx", "dK"), got, ref):
             if name == "dK":     # split-K slabs: the split count is a function of the shape alone, but the tile kernels differ
@@ -594,7 +589,6 @@ def test_split_k_on_the_ring_kernel_for_outputs_too_small_to_fill_the_chip(m, n,
     workgroups per tile (fp32 slabs, fixed-order reduce with the vector epilogue) instead of one round of 128 x 128 tiles.
     Against float64: the bf16 output is the fp32 sum rounded once (<= 1 ulp of the exact value); partial tiles, a K whose last
     split is shorter, and the bias + ReLU epilogue of a Dense layer at that batch.  Run-to-run identical (no atomics)."""
-    import ctypes as C
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd import dense_ops as D
@@ -603,7 +597,7 @@ def test_split_k_on_the_ring_kernel_for_outputs_too_small_to_fill_the_chip(m, n,
     gen = torch.Generator(device=dev).manual_seed(31)
     a = ((torch.rand(m, k, device=dev, generator=gen) - 0.5)).to(torch.bfloat16)
     bt = ((torch.rand(n, k, device=dev, generator=gen) - 0.5) * 0.2).to(torch.bfloat16)
-    wsb = int(L.lib().krs_gemm_workspace_bytes(C.c_int64(m), C.c_int64(n), C.c_int64(k), C.c_int(0)))
+    wsb = int(L.lib().krs_gemm_workspace_bytes(m, n, k, 0))
     assert wsb >= 2 * m * n * 4, "the shape is expected to take split-K"
     bias = (torch.rand(n, device=dev, generator=gen) - 0.5) if ep else None
     got, _ = D.gemm(a, bt, b_is_nk=True, bias=bias, act=L.ACT_RELU if ep else L.ACT_NONE)
@@ -617,10 +611,10 @@ def test_split_k_on_the_ring_kernel_for_outputs_too_small_to_fill_the_chip(m, n,
     torch.testing.assert_close(got[rows].double(), ref, rtol=2.0 ** -8 * 1.01, atol=1e-4)
     # the reference schedule (pipeline 0: no ring) on the same split: same slabs order, other tile kernels -> same value to fp32 noise
     try:
-        L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(0)), "krs_gemm_set_option")
+        L.check(L.lib().krs_gemm_set_option(0, 0), "krs_gemm_set_option")
         ref0, _ = D.gemm(a, bt, b_is_nk=True, bias=bias, act=L.ACT_RELU if ep else L.ACT_NONE)
     finally:
-        L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(4))
+        L.lib().krs_gemm_set_option(0, 4)
     assert (got == ref0).float().mean() > 0.99
     torch.testing.assert_close(got.float(), ref0.float(), rtol=2.0 ** -7, atol=1e-4)
 
@@ -632,14 +626,13 @@ def test_cross_backward_with_a_long_k_on_a_small_batch_needs_no_split_k_workspac
     workspace for a shape pick_splits deals over several workgroups per tile (KRS_ERR_WORKSPACE).  The inner product now runs in
     one pass over K; G against float64, dz / dx0 from G as stored.  fp32 / row-major products of that shape no longer take the
     ring's split either: krs_gemm with a NULL workspace succeeds for them."""
-    import ctypes as C
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd import dense_ops as D
 
     dev = "cuda:0"
     m, n, k = 2048, 3456, 2048
-    assert int(L.lib().krs_gemm_workspace_bytes(C.c_int64(m), C.c_int64(n), C.c_int64(k), C.c_int(0))) > 0   # (a split shape)
+    assert int(L.lib().krs_gemm_workspace_bytes(m, n, k, 0)) > 0   # (a split shape)
     gen = torch.Generator(device=dev).manual_seed(37)
     rnd = lambda *sh: ((torch.rand(*sh, device=dev, generator=gen) - 0.5)).to(dt)  # noqa: E731
     A, Bt, R, x0, u = rnd(m, k), rnd(n, k) * 0.1, rnd(m, n), rnd(m, n), rnd(m, n)
@@ -654,9 +647,8 @@ def test_cross_backward_with_a_long_k_on_a_small_batch_needs_no_split_k_workspac
     if dt == torch.float32:
         # krs_gemm itself, fp32 operands, NULL workspace: one pass (the ring's split is for bf16 [N, K] operands only)
         out = torch.empty(m, n, device=dev, dtype=dt)
-        rc = L.lib().krs_gemm(C.c_void_p(A.data_ptr()), C.c_int64(k), C.c_int(0), C.c_void_p(Bt.data_ptr()), C.c_int64(k), C.c_int(1),
-                              C.c_void_p(out.data_ptr()), C.c_int64(n), C.c_int64(m), C.c_int64(n), C.c_int64(k), C.c_int(L.F32),
-                              C.c_int(L.F32), None, None, C.c_size_t(0), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = L.lib().krs_gemm(A.data_ptr(), k, 0, Bt.data_ptr(), k, 1, out.data_ptr(), n, m, n, k, L.F32, L.F32, None,
+                              None, 0, torch.cuda.current_stream().cuda_stream)
         L.check(rc, "krs_gemm")
         torch.testing.assert_close(out.double(), A.double() @ Bt.double().t(), rtol=1e-5, atol=1e-4)
 
@@ -668,7 +660,6 @@ def test_the_64k_ring_at_its_edges(m, n, k):
     is not a multiple of 8 (scalar epilogue stores, clamped DMA rows in the last N tile) and an M with a partial last tile --
     against float64 on sampled rows and bit for bit against the reference schedule (pipeline 0) and the 32-k ring (pipeline 5),
     plain and with the bias + ReLU epilogue; run-to-run identical."""
-    import ctypes as C
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd import dense_ops as D
@@ -693,11 +684,11 @@ def test_the_64k_ring_at_its_edges(m, n, k):
     torch.testing.assert_close(got[1][rows].double(), torch.relu(ref + bias.double()), rtol=2.0 ** -8 * 1.01, atol=1e-4)
     try:
         for pipe in (0, 5):
-            L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(pipe)), "krs_gemm_set_option")
+            L.check(L.lib().krs_gemm_set_option(0, pipe), "krs_gemm_set_option")
             other = both()
             assert torch.equal(got[0], other[0]) and torch.equal(got[1], other[1]), pipe
     finally:
-        L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(4))
+        L.lib().krs_gemm_set_option(0, 4)
 
 
 def test_the_64k_ring_is_race_free_over_many_launches():
@@ -705,7 +696,6 @@ def test_the_64k_ring_is_race_free_over_many_launches():
     and go with memory load (cdna_hip_programming.md, 8-phase template notes) -- so the C3 long-K product (54 blocks through the
     five slots, 512 workgroups in two rounds) and the K = 512 cross form run 150 times each, while a second stream keeps HBM busy,
     and every output must equal the first launch's bits (which equal the reference schedule's)."""
-    import ctypes as C
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd import dense_ops as D
@@ -718,11 +708,11 @@ def test_the_64k_ring_is_race_free_over_many_launches():
     ut = ((torch.rand(p, d, device=dev, generator=gen) - 0.5) * 0.1).to(torch.bfloat16)
     vt = ((torch.rand(d, p, device=dev, generator=gen) - 0.5) * 0.1).to(torch.bfloat16)
     try:
-        L.check(L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(0)), "krs_gemm_set_option")
+        L.check(L.lib().krs_gemm_set_option(0, 0), "krs_gemm_set_option")
         h_ref, _ = D.gemm(x, ut, b_is_nk=True)
         y_ref, u_ref = D.gemm(h_ref, vt, b_is_nk=True, x0=x0, x=x, want_u=True)
     finally:
-        L.lib().krs_gemm_set_option(C.c_int(0), C.c_int(4))
+        L.lib().krs_gemm_set_option(0, 4)
     noise_src = torch.empty(256 << 20, dtype=torch.uint8, device=dev)
     noise_dst = torch.empty_like(noise_src)
     side = torch.cuda.Stream()

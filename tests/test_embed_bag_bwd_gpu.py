@@ -408,7 +408,6 @@ def test_table_segmented_plan_equals_global_plan(vocabs, dim, with_bad):
     64-bit values) against the global sort (KRS_EMBED_OPT_PLAN = 1): the fused Adagrad update and the dense gradient
     they lead to must be bit-identical -- problems that end in partial tiles, two features on one table (neighbours),
     1 / 2 / 3 passes, out-of-range ids (which end their table's run instead of the array)."""
-    import ctypes as C
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd.embedding_ops import FusedBags
@@ -429,7 +428,7 @@ def test_table_segmented_plan_equals_global_plan(vocabs, dim, with_bad):
     res = []
     try:
         for variant in (0, 1):
-            L.check(L.lib().krs_embed_set_option(C.c_int(2), C.c_int(variant)), "krs_embed_set_option")
+            L.check(L.lib().krs_embed_set_option(2, variant), "krs_embed_set_option")
             g = np.random.default_rng(9)
             tables = [torch.from_numpy(g.uniform(-1, 1, (v, dim)).astype(np.float32)).to(dev) for v in vocabs]
             slots = [torch.full((v, dim), 0.1, device=dev) for v in vocabs]
@@ -443,7 +442,7 @@ def test_table_segmented_plan_equals_global_plan(vocabs, dim, with_bad):
             torch.cuda.synchronize()
             res.append((tables, slots, dense))
     finally:
-        L.lib().krs_embed_set_option(C.c_int(2), C.c_int(0))
+        L.lib().krs_embed_set_option(2, 0)
     for part in range(3):
         for a, b in zip(res[0][part], res[1][part]):
             assert torch.equal(a, b)

@@ -167,7 +167,6 @@ def test_hot_rows_staged_in_lds_give_identical_outputs(rows, hots):
     """KRS_EMBED_OPT_HOTROWS: lookups of rows 0 .. n-1 are served from an LDS copy through flat loads -- the pooled
     outputs must be bit-identical to the plain kernel's (same fp32 accumulation order), with ids concentrated on the
     staged rows, a table smaller than the staged window, and workgroups that straddle two features (no staging there)."""
-    import ctypes as C
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd.embedding_ops import FusedBags
@@ -182,11 +181,11 @@ def test_hot_rows_staged_in_lds_give_identical_outputs(rows, hots):
     ]).astype(np.int32)).to(dev)
     fb = FusedBags(tables, [(t, "sum", t * D) for t in range(3)])
     try:
-        L.check(L.lib().krs_embed_set_option(C.c_int(3), C.c_int(0)), "set_option")
+        L.check(L.lib().krs_embed_set_option(3, 0), "set_option")
         ref, _ = fb.forward(ids, B, hots=hots)
-        L.check(L.lib().krs_embed_set_option(C.c_int(3), C.c_int(rows)), "set_option")
+        L.check(L.lib().krs_embed_set_option(3, rows), "set_option")
         got, _ = fb.forward(ids, B, hots=hots)
         torch.cuda.synchronize()
     finally:
-        L.lib().krs_embed_set_option(C.c_int(3), C.c_int(0))
+        L.lib().krs_embed_set_option(3, 0)
     assert torch.equal(ref, got)

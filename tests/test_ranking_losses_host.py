@@ -2,7 +2,6 @@
 value of the reference's own tests, the reference's ValueErrors, config round trips, and the C ABI's symbols and its
 list-length limit -- none of it needs a GPU."""
 
-import ctypes as C
 import json
 import os
 
@@ -120,10 +119,9 @@ def test_list_longer_than_4096_is_refused_with_the_limit(entry):
 
     build()
     fn = getattr(L.lib(), entry)
-    args = [C.c_void_p(8), C.c_int64(4097), C.c_int(0), C.c_void_p(8), None, None, C.c_float(1.0), C.c_float(1.0),
-            C.c_int64(1), C.c_int64(4097), C.c_void_p(8), None, None]
+    args = [8, 4097, 0, 8, None, None, 1.0, 1.0, 1, 4097, 8, None, None]
     if entry == "krs_pairwise_loss":
-        args = [C.c_int(1)] + args
+        args = [1] + args
     rc = fn(*args)
     assert rc == -1
     msg = L.lib().krs_last_error().decode()

@@ -70,7 +70,8 @@ typedef struct krs_table {
   void* weights;    /* [vocab, dim] fp32 or bf16 (table dtype of the call) */
   float* slot;      /* optimizer slot: Adagrad accumulator [vocab, dim] fp32, or NULL */
   int64_t row_base; /* global row id of row 0: tables of one call get disjoint
-                       [row_base, row_base+vocab) ranges (sort keys of the backward) */
+                       [row_base, row_base+vocab) ranges (sort keys of the backward),
+                       in any order: row_base need not ascend with the table index */
   int32_t vocab;
   float lr;         /* learning rate of this table's fused optimizer */
 } krs_table;

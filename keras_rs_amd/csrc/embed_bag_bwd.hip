@@ -832,16 +832,6 @@ __device__ __forceinline__ void store_elems(TT* dst, const float (&f)[N], bool a
   }
 }
 
-// table index of a global row: tables are few and row_base ascending
-__device__ __forceinline__ int find_table(const krs_table* tables, int n_tables, int64_t row) {
-  int lo = 0, hi = n_tables - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tables[mid].row_base <= row) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 constexpr int kLongUnroll = 4;   // ... and per group in the hot-row kernel, whose chunks are long
 constexpr int kSegsPerGroup = 4;  // segments each group walks (amortises the descriptor prologue)
 // ... per mode: the slot-less modes (SGD, dense, compact) keep fewer rows in flight per lane and run better with TWO
@@ -1344,7 +1334,8 @@ __global__ __launch_bounds__(256) void bag_apply_generic(const ApplyParams p, in
   const int64_t e0 = u + 1 < n_seg ? (int64_t)p.seg_start[u + 1] : p.nnz;
   const uint32_t key = p.keys[s0];
   if (key == kInvalidKey) return;
-  const int t = MODE == kSparse ? 0 : find_table(p.tables, p.n_tables, (int64_t)key);
+  // the table of the segment's first lookup, as in finish_row (row bases are disjoint, in no particular order)
+  const int t = MODE == kSparse ? 0 : p.feats[(uint32_t)(p.vals[s0] >> 32) / (uint32_t)p.batch].table;
   auto column_grad = [&](int c) {
     float acc = 0.0f;
     for (int64_t j = s0; j < e0; ++j) {

@@ -267,7 +267,7 @@ def test_hot_rows_take_the_workgroup_path(tdt, gdt, dim, batch):
                                    rtol=2 ** -7 if tdt == "bf16" else 1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("kind", ["sgd", "adagrad", "adam", "adagrad_rowwise"])
+@pytest.mark.parametrize("kind", ["sgd", "adagrad", "adam", "ftrl", "adagrad_rowwise"])
 @pytest.mark.parametrize("tdt,gdt,dim", [("bf16", "bf16", 128), ("f32", "f32", 64), ("bf16", "f32", 32), ("f32", "bf16", 24)])
 def test_apply_kernel_gives_the_same_bits_on_misaligned_table_and_slot_bases(kind, tdt, gdt, dim):
     """bag_apply_fast_kernel has ONE access form -- under-aligned wide vector accesses, the memory pipeline runs in
@@ -296,15 +296,18 @@ def test_apply_kernel_gives_the_same_bits_on_misaligned_table_and_slot_bases(kin
         g = np.random.default_rng(5)
         tables = [alloc((v, dim), TORCH_DT[tdt], torch.from_numpy(g.uniform(-1, 1, (v, dim)).astype(np.float32)).to(dev),
                         misaligned) for v in vocabs]
-        planes = {"sgd": None, "adagrad": 1, "adam": 2, "adagrad_rowwise": 0}[kind]
+        planes = {"sgd": None, "adagrad": 1, "adam": 2, "ftrl": 2, "adagrad_rowwise": 0}[kind]
         if planes is None:
             slots = [None] * n_tables
         elif planes == 0:
             slots = [alloc((v,), torch.float32, torch.full((v,), 0.1, device=dev), misaligned) for v in vocabs]
         elif planes == 1:
             slots = [alloc((v, dim), torch.float32, torch.full((v, dim), 0.1, device=dev), misaligned) for v in vocabs]
-        else:
-            slots = [alloc((2, v, dim), torch.float32, torch.zeros((2, v, dim), device=dev), misaligned) for v in vocabs]
+        else:   # Adam (m, v) from zero; FTRL (accumulator, linear) from (0.1, 0)
+            init = torch.zeros((2, 1, 1), device=dev)
+            if kind == "ftrl":
+                init[0] = 0.1
+            slots = [alloc((2, v, dim), torch.float32, init.expand(2, v, dim), misaligned) for v in vocabs]
         fb = FusedBags(tables, [(tix[f], ["sum", "mean", "sqrtn", "sum"][f], 3 + f * dim) for f in range(4)],
                        slots=slots, lrs=[0.01, 0.02, 0.03])
         return tables, slots, fb
@@ -321,7 +324,7 @@ def test_apply_kernel_gives_the_same_bits_on_misaligned_table_and_slot_bases(kin
         out = torch.empty((batch, cols), dtype=TORCH_DT[tdt], device=dev)
         _, scale = fb.forward(ids, batch, hots=hots, weights=w, out=out, want_scale=True)
         ws = fb.plan_backward(ids, batch, hots=hots, global_order=False)
-        hyper = (0.9, 0.999, 1e-7, 0.3) if kind == "adam" else None
+        hyper = {"adam": (0.9, 0.999, 1e-7, 0.3), "ftrl": FTRL}.get(kind)
         fb.backward_fused(kind, ws, grad, batch, ids.numel(), hots=hots, weights=w, bag_scale=scale, hyper=hyper)
         torch.cuda.synchronize()
         assert any(not torch.equal(x, y) for x, y in zip(before, tables)), "the update did not run"

@@ -363,6 +363,37 @@ int krs_gemm_dense_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb, 
 enum { KRS_CROSS_BWD_NONE = 0, KRS_CROSS_BWD_TWO_CALL = 1, KRS_CROSS_BWD_PP64 = 2, KRS_CROSS_BWD_PP256 = 3 };
 int krs_gemm_cross_bwd_last_route(int* epilogue);
 
+/* Diagnostic, host only: where the CALLING THREAD's last krs_gemm ran.  Every field is 0 when there was no call yet, the
+ * call was refused (any return other than KRS_OK) or had nothing to do (m == 0 or n == 0).
+ *   kernel      KRS_GEMM_KERNEL_*: the kernel family that formed the products (gemm_generic_kernel, gemm_mfma_kernel,
+ *               gemm_glds_kernel, gemm_tn_glds_kernel, gemm_pp256_kernel on K-contiguous / on K-strided operands,
+ *               gemm_pp64_kernel, gemm_thin_kernel, gemm_rowdot_kernel, gemm_smallk_kernel)
+ *   splits      workgroups along K per output tile (1 = no split-K)
+ *   reduce      KRS_GEMM_REDUCE_*: the slab-reduce kernel that followed a split product (gemm_slab_reduce_kernel,
+ *               gemm_slab_reduce_vec4_kernel, gemm_slab_reduce_vec8_kernel)
+ *   epilogue    epilogue build of the tile kernel: 0 = general, 1 = cross, 2 = residual (bf16 output, unsplit)
+ *   ep_vec      1 when every epilogue operand allowed 8-wide vector access
+ *   thin_width  gemm_thin_kernel only: its width build (1, 4, 8, 16), else 0
+ *   thin_is_a   gemm_thin_kernel only: 1 when A was the thin operand (m <= n), 0 when B was
+ * The two-call form of krs_gemm_cross_bwd / krs_gemm_dense_bwd runs krs_gemm's body and therefore leaves a record too;
+ * their fused form does not touch it.  Returns `kernel`; `route` may be NULL.  Lets tests prove which kernel they ran. */
+enum {
+  KRS_GEMM_KERNEL_NONE = 0, KRS_GEMM_KERNEL_GENERIC = 1, KRS_GEMM_KERNEL_MFMA = 2, KRS_GEMM_KERNEL_GLDS = 3,
+  KRS_GEMM_KERNEL_TN_GLDS = 4, KRS_GEMM_KERNEL_PP256 = 5, KRS_GEMM_KERNEL_PP256_KSTRIDED = 6, KRS_GEMM_KERNEL_PP64 = 7,
+  KRS_GEMM_KERNEL_THIN = 8, KRS_GEMM_KERNEL_ROWDOT = 9, KRS_GEMM_KERNEL_SMALLK = 10
+};
+enum { KRS_GEMM_REDUCE_NONE = 0, KRS_GEMM_REDUCE_SCALAR = 1, KRS_GEMM_REDUCE_VEC4 = 2, KRS_GEMM_REDUCE_VEC8 = 3 };
+typedef struct krs_gemm_route {
+  int32_t kernel;
+  int32_t splits;
+  int32_t reduce;
+  int32_t epilogue;
+  int32_t ep_vec;
+  int32_t thin_width;
+  int32_t thin_is_a;
+} krs_gemm_route;
+int krs_gemm_last_route(krs_gemm_route* route);
+
 /* Tuning / diagnostic switches of krs_gemm (process-wide; results never depend on them).
  *   KRS_GEMM_OPT_PIPELINE: 4 = the big bf16 shapes run the four-stage ping-pong ring on 256x256 tiles (default, or
  *   the environment variable KRS_GEMM_PIPE at first use); 0 = every shape runs the two-stage 128x128 kernels and

@@ -54,6 +54,11 @@ class GemmEpilogue(C.Structure):
     ]
 
 
+class GemmRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in
+                ("kernel", "splits", "reduce", "epilogue", "ep_vec", "thin_width", "thin_is_a")]
+
+
 # Prototype of every entry point include/krs.h declares, in its order: name -> (restype, argtypes).  Any pointer is a
 # void* (pass L.ptr(t), an int or None; ctypes arrays and C.byref(struct) where the C side takes an array or a struct).
 # tests/test_capi_symbols.py parses the header and checks this table against it row by row.
@@ -82,6 +87,7 @@ PROTOTYPES = {
                                 _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
     "krs_gemm_dense_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
     "krs_gemm_cross_bwd_last_route": (_I, [_P]),
+    "krs_gemm_last_route": (_I, [_P]),
     "krs_gemm_set_option": (_I, [_I, _I]),
     "krs_embed_set_option": (_I, [_I, _I]),
     "krs_colsum_workspace_bytes": (_SZ, [_I64, _I64]),

@@ -1737,8 +1737,9 @@ int with_epilogue(int e, F&& f) {
   return f(std::integral_constant<int, First>());
 }
 
+// (`rt`: the route record of krs_gemm_last_route -- kernel family and epilogue build are noted here, host side only)
 template <int ES>
-int launch_mfma(const GemmParams& p, hipStream_t st) {
+int launch_mfma(const GemmParams& p, hipStream_t st, krs_gemm_route& rt) {
   const int64_t mt = p.a_km ? ceil_div(p.m, BM) : ceil_div(ceil_div(p.m, BM), 8) * 8;
   const dim3 grid((unsigned)(mt * ceil_div(p.n, BN)), 1, (unsigned)p.splits);
   const size_t lds = 2 * TILE_BYTES;
@@ -1771,11 +1772,13 @@ int launch_mfma(const GemmParams& p, hipStream_t st) {
         !force128) {
       const dim3 grid256((unsigned)(ceil_div(ceil_div(p.m, 256), 8) * 8 * ceil_div(p.n, 256) * p.splits));
       const int nt_ = (int)ceil_div(p.n, 256);
+      rt.epilogue = epi;
       // (the residual-add form with a short K -- dx = dh U^T + g -- was 4 % faster on a two-stage loop until its R
       // operands were fetched under the ring's tail: 340 -> 301 us)
       // whole 64-k blocks of both operands and of every split, at least three of them -> the 64-k ring (pipeline 5: never)
       const bool k64 = gemm_pipe() == 4 && p.k % 64 == 0 && p.k_per_split % 64 == 0 &&
                        p.k - (int64_t)(p.splits - 1) * p.k_per_split >= 192;
+      rt.kernel = k64 ? KRS_GEMM_KERNEL_PP64 : KRS_GEMM_KERNEL_PP256;
       return with_epilogue<0, 2>(epi, [&](auto E) {
         return k64 ? launch_lds<gemm_pp64_kernel<E>>("gemm_pp64_kernel", grid256, dim3(512), pp64::NSLOT * pp64::SLOT, st,
                                                      p, nt_)
@@ -1786,6 +1789,7 @@ int launch_mfma(const GemmParams& p, hipStream_t st) {
   }
   if (use_glds) {
     const size_t glds_lds = 4 * BM * ROW_BYTES;  // 2 stages x (A + B) x 16 KB
+    rt.kernel = KRS_GEMM_KERNEL_GLDS; rt.epilogue = epi;
     return with_epilogue<0, 2>(epi, [&](auto E) {
       return launch_lds<gemm_glds_kernel<ES, E>>("gemm_glds_kernel", grid, dim3(256), glds_lds, st, p);
     });
@@ -1798,14 +1802,17 @@ int launch_mfma(const GemmParams& p, hipStream_t st) {
     if (p.m >= 256 && p.n >= 256 && !tn128 && gemm_pipe() != 0 && p.k_per_split >= 256) {
       const int mt_ = (int)ceil_div(p.m, 256), nt_ = (int)ceil_div(p.n, 256);
       const dim3 grid_tn((unsigned)(ceil_div((int64_t)p.splits * mt_ * nt_, 8) * 8));
+      rt.kernel = KRS_GEMM_KERNEL_PP256_KSTRIDED;
       return launch_lds<gemm_pp256_kernel<true, 4, 0>>("gemm_pp256_kernel (K-strided operands)", grid_tn, dim3(512),
                                                        4 * pp::STAGE, st, p, mt_, nt_);
     }
     const int mt_ = (int)ceil_div(p.m, BM), nt_ = (int)ceil_div(p.n, BN);
     const dim3 grid_tn((unsigned)(ceil_div(p.splits, 8) * 8 * mt_ * nt_));
     const size_t lds_tn = 4 * 64 * 128 * 2;  // 2 stages x (A + B) x 16 KB
+    rt.kernel = KRS_GEMM_KERNEL_TN_GLDS;
     return launch_lds<gemm_tn_glds_kernel<0>>("gemm_tn_glds_kernel", grid_tn, dim3(256), lds_tn, st, p, mt_, nt_);
   }
+  rt.kernel = KRS_GEMM_KERNEL_MFMA; rt.epilogue = epi;
   return with_epilogue<0, 2>(epi, [&](auto E) {
     if (p.a_km) return launch_lds<gemm_mfma_kernel<ES, true, false, E>>("gemm_mfma_kernel", grid, dim3(256), lds, st, p);
     if (p.b_nk) return launch_lds<gemm_mfma_kernel<ES, false, true, E>>("gemm_mfma_kernel", grid, dim3(256), lds, st, p);
@@ -1835,12 +1842,18 @@ extern "C" size_t krs_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k, int 
 
 namespace krs {
 namespace {
+// where the calling thread's last krs_gemm ran (krs_gemm_last_route): cleared when gemm_run starts, written when it has
+// queued its last kernel, so a refused call and an empty product leave "none"
+thread_local krs_gemm_route g_route = {};
+
 // krs_gemm's body.  `allow_split` false = one pass over K whatever pick_splits would choose (the two-call form of
 // krs_gemm_cross_bwd, whose workspace is sized for the column sums only).
 int gemm_run(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb, int b_is_nk,
              void* c, int64_t ldc, int64_t m, int64_t n, int64_t k, int in_dtype, int out_dtype,
              const krs_gemm_epilogue* epilogue, void* workspace, size_t workspace_bytes,
              void* stream, bool allow_split) {
+  g_route = krs_gemm_route{};
+  krs_gemm_route rt = {};
   KRS_REQUIRE(a && b && c, "krs_gemm: null operand");
   KRS_REQUIRE(m >= 0 && n >= 0 && k >= 0, "krs_gemm: negative size");
   KRS_REQUIRE((in_dtype == KRS_F32 || in_dtype == KRS_BF16) && (out_dtype == KRS_F32 || out_dtype == KRS_BF16),
@@ -1865,6 +1878,7 @@ int gemm_run(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb
       if (epilogue->r) v = v && al16(epilogue->r) && epilogue->ldr % 8 == 0;
     }
     p.ep_vec = v;
+    rt.ep_vec = v;
   }
   const int es = in_dtype == KRS_BF16 ? 2 : 4;
   if (k > 0 && mfma_eligible(p, es) && !(p.a_km && p.b_nk)) {
@@ -1878,8 +1892,9 @@ int gemm_run(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb
       p.k_per_split = ceil_div(ceil_div(k, s), bk) * bk;
       p.slabs = reinterpret_cast<float*>(workspace);
     }
-    const int rc = es == 2 ? launch_mfma<2>(p, st) : launch_mfma<4>(p, st);
+    const int rc = es == 2 ? launch_mfma<2>(p, st, rt) : launch_mfma<4>(p, st, rt);
     if (rc != KRS_OK) return rc;
+    rt.splits = p.splits;
     if (p.splits > 1) {
       const bool vec4 = !p.has_ep && out_dtype == KRS_F32 && n % 4 == 0 && ldc % 4 == 0 &&
                         (reinterpret_cast<uintptr_t>(c) & 15) == 0;
@@ -1890,7 +1905,9 @@ int gemm_run(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb
       else
         hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)ceil_div(m * n, 256)), dim3(256), 0, st, p);
       KRS_CHECK_LAUNCH("gemm_slab_reduce_kernel");
+      rt.reduce = vec4 ? KRS_GEMM_REDUCE_VEC4 : (p.ep_vec && n % 8 == 0 ? KRS_GEMM_REDUCE_VEC8 : KRS_GEMM_REDUCE_SCALAR);
     }
+    g_route = rt;
     return KRS_OK;
   }
   if (p.a_km && !p.b_nk && k >= 1024 && std::min(m, n) <= kThinMax) {
@@ -1916,16 +1933,22 @@ int gemm_run(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb
 #undef KRS_THIN_NT
 #undef KRS_THIN
     KRS_CHECK_LAUNCH("gemm_thin_kernel");
+    rt.kernel = KRS_GEMM_KERNEL_THIN; rt.splits = p.splits; rt.thin_is_a = thin_is_a;
+    rt.thin_width = n_thin <= 1 ? 1 : (n_thin <= 4 ? 4 : (n_thin <= 8 ? 8 : 16));
     if (p.splits > 1) {
       hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)ceil_div(m * n, 256)), dim3(256), 0, st, p);
       KRS_CHECK_LAUNCH("gemm_slab_reduce_kernel");
+      rt.reduce = KRS_GEMM_REDUCE_SCALAR;
     }
+    g_route = rt;
     return KRS_OK;
   }
   if (!p.a_km && p.splits == 1 && n <= 8 && k >= 32 && m >= 1024) {
     if (in_dtype == KRS_BF16) hipLaunchKernelGGL(gemm_rowdot_kernel<2>, dim3((unsigned)ceil_div(m, 16)), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(gemm_rowdot_kernel<4>, dim3((unsigned)ceil_div(m, 16)), dim3(256), 0, st, p);
     KRS_CHECK_LAUNCH("gemm_rowdot_kernel");
+    rt.kernel = KRS_GEMM_KERNEL_ROWDOT; rt.splits = 1;
+    g_route = rt;
     return KRS_OK;
   }
   if (!p.a_km && p.splits == 1 && k <= 16 && n % 8 == 0 && n <= 1024 && m * n >= (1 << 16)) {
@@ -1935,10 +1958,14 @@ int gemm_run(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb
     if (in_dtype == KRS_BF16) hipLaunchKernelGGL(gemm_smallk_kernel<2>, dim3(blocks), dim3(256), lds, st, p, rows_per_wg);
     else hipLaunchKernelGGL(gemm_smallk_kernel<4>, dim3(blocks), dim3(256), lds, st, p, rows_per_wg);
     KRS_CHECK_LAUNCH("gemm_smallk_kernel");
+    rt.kernel = KRS_GEMM_KERNEL_SMALLK; rt.splits = 1;
+    g_route = rt;
     return KRS_OK;
   }
   hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned)ceil_div(m * n, 256)), dim3(256), 0, st, p, in_dtype);
   KRS_CHECK_LAUNCH("gemm_generic_kernel");
+  rt.kernel = KRS_GEMM_KERNEL_GENERIC; rt.splits = 1;
+  g_route = rt;
   return KRS_OK;
 }
 }  // namespace
@@ -1950,6 +1977,11 @@ extern "C" int krs_gemm(const void* a, int64_t lda, int a_is_km, const void* b, 
                         void* stream) {
   return gemm_run(a, lda, a_is_km, b, ldb, b_is_nk, c, ldc, m, n, k, in_dtype, out_dtype, epilogue, workspace,
                   workspace_bytes, stream, true);
+}
+
+extern "C" int krs_gemm_last_route(krs_gemm_route* route) {
+  if (route) *route = g_route;
+  return g_route.kernel;
 }
 
 // ---- krs_gemm_cross_bwd: data-gradient product + the elementwise backward of the layer below, one launch ---------------

@@ -224,6 +224,23 @@ def last_cross_bwd_route():
     return CROSS_BWD_ROUTES[route], int(ep.value)
 
 
+GEMM_KERNELS = {0: None, 1: "generic", 2: "mfma", 3: "glds", 4: "tn_glds", 5: "pp256", 6: "pp256_kstrided", 7: "pp64",
+                8: "thin", 9: "rowdot", 10: "smallk"}
+GEMM_REDUCES = {0: None, 1: "scalar", 2: "vec4", 3: "vec8"}
+
+
+def last_gemm_route() -> dict:
+    """Where the calling thread's last krs_gemm ran (krs_gemm_last_route): kernel (a GEMM_KERNELS name, None when no
+    launch was made), splits (1 = no split-K), reduce (a GEMM_REDUCES name), epilogue (the tile kernel's build: 0, 1, 2),
+    ep_vec, and for gemm_thin_kernel thin_width (1, 4, 8, 16) and thin_is_a.  A diagnostic for tests: it reads a host-side
+    record, no device sync."""
+    rt = L.GemmRoute()
+    L.lib().krs_gemm_last_route(C.byref(rt))
+    return dict(kernel=GEMM_KERNELS[rt.kernel], splits=int(rt.splits), reduce=GEMM_REDUCES[rt.reduce],
+                epilogue=int(rt.epilogue), ep_vec=bool(rt.ep_vec), thin_width=int(rt.thin_width),
+                thin_is_a=bool(rt.thin_is_a))
+
+
 def colsum(a: torch.Tensor) -> torch.Tensor:
     a = _rowmajor(a, "colsum")
     out = torch.empty(a.shape[1], dtype=torch.float32, device=a.device)

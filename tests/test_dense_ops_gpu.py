@@ -30,10 +30,21 @@ def _tol(dt, k):
 @pytest.mark.parametrize("m,n,k", [(1, 3, 3), (5, 7, 9), (128, 128, 64), (130, 200, 72), (256, 512, 512),
                                    (300, 136, 1000), (64, 3456, 512), (130, 200, 1088), (257, 512, 3456),
                                    (700, 300, 1024), (512, 768, 2048),  # the last three: 256x256-tile kernel
-                                   (13, 520, 4100), (264, 1, 4100), (16, 16, 9000),  # tn: thin weight-gradient kernel
-                                   (3, 700, 1030), (8, 300, 2048), (520, 5, 1500),      # ... its 4- / 8-wide builds
-                                   (2048, 1, 256), (1500, 3, 77), (1100, 8, 40),        # nn / nt: gemm_rowdot_kernel
-                                   (2048, 256, 1), (300, 512, 5), (5000, 16, 16)])      # nn / nt: gemm_smallk_kernel
+                                   # The small-shape kernels run only what mfma_eligible refuses (an axis that is not
+                                   # whole 16-byte vectors); krs_gemm_last_route settled which of these reach them, and
+                                   # tests/test_gemm_routes_gpu.py asserts the route of every such shape:
+                                   (13, 520, 4100), (264, 1, 4100),   # tn: gemm_thin_kernel (16- and 1-wide builds)
+                                   (16, 16, 9000),                    # tn: eligible -> gemm_mfma_kernel, 17 splits
+                                   (15, 16, 9000),                    # tn: gemm_thin_kernel, 16-wide
+                                   (3, 700, 1030), (520, 5, 1500),    # tn: gemm_thin_kernel, 4- / 8-wide
+                                   (8, 300, 2048),                    # tn: thin 8-wide in bf16; fp32: eligible -> mfma, split
+                                   (2048, 1, 256),                    # nn: gemm_rowdot_kernel; nt: eligible -> gemm_mfma_kernel
+                                   (1500, 3, 77),                     # nn / nt: gemm_rowdot_kernel
+                                   (1100, 8, 40),                     # nn / nt: eligible -> gemm_mfma_kernel; tn: generic
+                                   (2048, 1, 250), (1100, 8, 42),     # nn / nt: gemm_rowdot_kernel (K not in whole vectors)
+                                   (2048, 256, 1), (300, 512, 5),     # nn / nt: gemm_smallk_kernel
+                                   (5000, 16, 16),                    # nn / nt: eligible -> gemm_mfma_kernel
+                                   (5000, 16, 13)])                   # nn / nt: gemm_smallk_kernel
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("layout", ["nn", "nt", "tn"])
 def test_gemm_layouts(m, n, k, dt, layout):
@@ -52,7 +63,9 @@ def test_gemm_layouts(m, n, k, dt, layout):
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("act", [None, "relu", "sigmoid", "tanh"])
 def test_gemm_tiny_dimension_epilogues(dt, act):
-    # the last Dense of the DLRM top MLP (256 -> 1 unit): y = sigmoid(x k + b) on gemm_rowdot_kernel, and the data
+    # the last Dense of the DLRM top MLP (256 -> 1 unit): y = sigmoid(x k + b) -- given K-contiguous with K = 256 this product
+    # is MFMA-eligible and runs on gemm_mfma_kernel, not on gemm_rowdot_kernel (krs_gemm_last_route; the route is asserted in
+    # tests/test_gemm_routes_gpu.py, which also runs a 1-unit shape that does reach gemm_rowdot_kernel) -- and the data
     # gradient dz k^T (K = 1) on gemm_smallk_kernel
     from keras_rs_amd import dense_ops as D
 

@@ -714,6 +714,65 @@ int krs_listmle_loss(const void* logits, int64_t ld, int dtype, const float* lab
                      const float* g, float g_scale, float inv_temperature, int64_t batch, int64_t list,
                      float* list_loss, void* dlogits, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * K10  Ranking metrics (keras_rs.metrics): one sort of each list in LDS, up to KRS_METRIC_MAX_SPECS metrics from it
+ *
+ * scores [batch, list] fp32 / bf16 with row stride ld; labels, gain (NULL = 2^y - 1) [batch, list] fp32 and mask
+ * [batch, list] uint8 (NULL = all set), contiguous.  The weight of item i of list b is
+ * weights[b * weights_row_stride + i * weights_item_stride] (fp32; item stride 1 = a weight per item, 0 = one
+ * weight per list, no [batch, list] copy needed), or the scalar `weight` for every item when weights is NULL (pass
+ * 1 for an unweighted call).  An item is valid when label >= 0, its mask byte is non-zero and its weight is > 0; an invalid item counts with label 0 and weight 0 and ranks after every
+ * valid item.  Order within a list: valid first, score descending (the total order of K8 / K9: -0 == +0, NaN above
+ * +inf), then the tie key ascending in the index (shuffle_ties == 0) or descending in the 20-bit hash of (seed,
+ * *draw, row, index) and then ascending in the index.
+ *
+ * krs_ranking_metrics (stage A).  Spec j is (kinds[j], ks[j]) -- host arrays; ks[j] <= 0 means the whole list;
+ * k = min(ks[j], list) -- and gives values[j * batch + b], with rel = (label >= 1), r the 1-based rank:
+ *     KRS_METRIC_DCG        sum_{r <= k} w_r (gain_r discount_r)              (not yet divided by the list weight)
+ *     KRS_METRIC_NDCG       DCG / the same sum in the order w * gain descending, 0 when that is 0
+ *     KRS_METRIC_MAP        sum_{r <= k} (cumsum(rel)_r / r) (w_r rel_r) / sum_all w rel, 0 when that is 0
+ *     KRS_METRIC_MRR        max_{r <= k} rel_r / r
+ *     KRS_METRIC_PRECISION  sum_{r <= k} rel_r / min(k, number of valid items), 0 when that is 0
+ *     KRS_METRIC_RECALL     sum_{r <= k} rel_r / sum_all rel, 0 when that is 0
+ * discount (NULL = 1 / log2(1 + r)): discount_len fp32 values for r = 1 .. discount_len, discount_len >= every k of
+ * a DCG / NDCG spec.  sums [5, batch] fp32 receives per list: sum w gain, sum gain, sum w rel, sum rel, sum w.
+ * order (NULL = not wanted) [batch, list] int32 receives the item index at each rank.  draw is a device int64
+ * read by the launch (NULL = 0); it is not changed here.
+ *
+ * krs_ranking_metrics_accumulate (stage B).  Turns sums into the per-list weights of
+ * get_list_weights (ranking_metrics_utils.py:132-224): with relevance = gain for DCG / NDCG and rel otherwise,
+ *     0 when sum w == 0;  sum(w relevance) / sum(relevance) when sum relevance > 0;  otherwise the batch-wide
+ *     sum of those quotients / #{lists with sum w > 0 and sum relevance > 0}, or 1 when there is no such list.
+ * A DCG value is divided by its weight (0 when that is 0).  states[j] (host array of n_specs device pointers) is
+ * spec j's {total, count}: total += sum_b value weight, count += sum_b weight.  out_values / out_weights (NULL =
+ * not wanted) [n_specs, batch] receive the per-list values and weights.  draw (NULL = none) is advanced by one.
+ * Up to 1024 lists run in one workgroup and one launch.  A larger batch is spread over up to 256 workgroups in three
+ * launches (partial sums of the default weight; partial sums of the Mean update; the states) and needs
+ * krs_ranking_metrics_accumulate_workspace_bytes(batch) bytes of device workspace (0 up to 1024 lists), which need not
+ * be initialised; too little is KRS_ERR_WORKSPACE.
+ *
+ * Fixed summation orders and no float atomics: bit-identical from call to call.  No host synchronisation.
+ * 1 <= list <= KRS_RANK_MAX_LIST and 1 <= n_specs <= KRS_METRIC_MAX_SPECS, otherwise KRS_ERR_INVALID.
+ * ------------------------------------------------------------------------- */
+#define KRS_METRIC_MAX_SPECS 8
+typedef enum krs_metric_kind {
+  KRS_METRIC_DCG = 0,
+  KRS_METRIC_NDCG = 1,
+  KRS_METRIC_MAP = 2,
+  KRS_METRIC_MRR = 3,
+  KRS_METRIC_PRECISION = 4,
+  KRS_METRIC_RECALL = 5
+} krs_metric_kind;
+int krs_ranking_metrics(const void* scores, int64_t ld, int dtype, const float* labels, const uint8_t* mask,
+                        const float* weights, int64_t weights_row_stride, int64_t weights_item_stride, float weight,
+                        const float* gain, const float* discount, int64_t discount_len, int shuffle_ties,
+                        uint64_t seed, const int64_t* draw, const int* kinds, const int* ks, int n_specs,
+                        int64_t batch, int64_t list, float* values, float* sums, int32_t* order, void* stream);
+size_t krs_ranking_metrics_accumulate_workspace_bytes(int64_t batch);
+int krs_ranking_metrics_accumulate(const float* values, const float* sums, const int* kinds, int n_specs,
+                                   int64_t batch, float* const* states, float* out_values, float* out_weights,
+                                   int64_t* draw, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ There is no CPU fallback: computing without the HIP library or without a GPU rai
 
 from keras_rs_amd import layers  # noqa: F401
 from keras_rs_amd import losses  # noqa: F401
+from keras_rs_amd import metrics  # noqa: F401
 from keras_rs_amd._lib import KrsError  # noqa: F401
 
 __version__ = "0.1.0"

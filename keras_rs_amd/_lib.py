@@ -120,6 +120,10 @@ PROTOTYPES = {
     "krs_retrieval_topk": (_I, [_P, _I64, _P, _I64, _P, _I, _I64, _I64, _I64, _I, _P, _P, _P, _SZ, _P]),
     "krs_pairwise_loss": (_I, [_I, _P, _I64, _I, _P, _P, _P, _F, _F, _I64, _I64, _P, _P, _P]),
     "krs_listmle_loss": (_I, [_P, _I64, _I, _P, _P, _P, _F, _F, _I64, _I64, _P, _P, _P]),
+    "krs_ranking_metrics": (_I, [_P, _I64, _I, _P, _P, _P, _I64, _I64, _F, _P, _P, _I64, _I, _U64, _P, _P, _P, _I, _I64,
+                                 _I64, _P, _P, _P, _P]),
+    "krs_ranking_metrics_accumulate_workspace_bytes": (_SZ, [_I64]),
+    "krs_ranking_metrics_accumulate": (_I, [_P, _P, _P, _I, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -1,0 +1,102 @@
+"""Host side of K10: thin torch wrappers over krs_ranking_metrics and krs_ranking_metrics_accumulate (include/krs.h).
+
+Both run on the current stream and never wait for the device, so a metric update can be captured in a HIP graph.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from keras_rs_amd import _lib as L
+
+MAX_LIST = 4096   # KRS_RANK_MAX_LIST
+MAX_SPECS = 8     # KRS_METRIC_MAX_SPECS
+METRIC_KINDS = {"dcg": 0, "ndcg": 1, "map": 2, "mrr": 3, "precision": 4, "recall": 5}   # krs_metric_kind
+
+
+def _int_array(xs):
+    return (C.c_int * len(xs))(*xs)
+
+
+def _full(t, name, shape, device, dtype, what):
+    if t is None:
+        return None
+    t = t.to(device=device, dtype=dtype).contiguous()
+    if tuple(t.shape) != tuple(shape):
+        raise L.KrsError(f"{what}: {name} shape {tuple(t.shape)} where {tuple(shape)} is expected")
+    return t
+
+
+def ranking_metrics(specs, scores: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor | None = None,
+                    weights: torch.Tensor | float | None = None, *, gain: torch.Tensor | None = None,
+                    discount: torch.Tensor | None = None, shuffle_ties: bool = False, seed: int = 0,
+                    draw: torch.Tensor | None = None, want_order: bool = False):
+    """Stage A.  specs: up to 8 (kind, k) with kind a METRIC_KINDS key and k an int or None.  scores [B, L] fp32 /
+    bf16; labels, gain [B, L]; weights [B, L], [B] (one weight per list) or a Python number (every item's weight):
+    the last two reach the kernel as they are, no [B, L] copy is made; mask [B, L] bool; discount [>= every DCG /
+    NDCG k]; draw a device int64 tensor of one element (read, not advanced).  Returns (values [n, B], sums [5, B],
+    order [B, L] int32 or None): see include/krs.h for each."""
+    what = "ranking_metrics"
+    L.require_device(scores, what)
+    if scores.dim() != 2:
+        raise L.KrsError(f"{what}: expected [batch, list] scores, got shape {tuple(scores.shape)}")
+    b, n = scores.shape
+    if scores.stride(1) != 1 or (b > 1 and scores.stride(0) < n):
+        scores = scores.contiguous()
+    ld = scores.stride(0) if b > 1 else n
+    dev = scores.device
+    y = _full(labels, "labels", (b, n), dev, torch.float32, what)
+    m = _full(mask, "mask", (b, n), dev, torch.bool, what)
+    m = None if m is None else m.view(torch.uint8)
+    w, w_strides, w_scalar = None, (0, 0), 1.0
+    if isinstance(weights, (int, float)):
+        w_scalar = float(weights)
+    elif weights is not None and weights.dim() == 1:
+        w, w_strides = _full(weights, "weights", (b,), dev, torch.float32, what), (1, 0)
+    elif weights is not None:
+        w, w_strides = _full(weights, "weights", (b, n), dev, torch.float32, what), (n, 1)
+    g = _full(gain, "gain", (b, n), dev, torch.float32, what)
+    d = None if discount is None else discount.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    if draw is not None and (draw.dtype != torch.int64 or draw.device != dev or draw.numel() != 1):
+        raise L.KrsError(f"{what}: draw must be one int64 on {dev}")
+    kinds = _int_array([METRIC_KINDS[kind] for kind, _ in specs])
+    ks = _int_array([0 if k is None else int(k) for _, k in specs])
+    values = torch.empty((len(specs), b), dtype=torch.float32, device=dev)
+    sums = torch.empty((5, b), dtype=torch.float32, device=dev)
+    order = torch.empty((b, n), dtype=torch.int32, device=dev) if want_order else None
+    rc = L.lib().krs_ranking_metrics(L.ptr(scores), ld, L.fdtype(scores), L.ptr(y), L.ptr(m), L.ptr(w), w_strides[0],
+                                     w_strides[1], w_scalar, L.ptr(g), L.ptr(d), 0 if d is None else d.numel(),
+                                     int(bool(shuffle_ties)),
+                                     int(seed) & (2 ** 64 - 1), L.ptr(draw), kinds, ks, len(specs), b, n,
+                                     L.ptr(values), L.ptr(sums), L.ptr(order), L.stream_ptr())
+    L.check(rc, "krs_ranking_metrics")
+    return values, sums, order
+
+
+def ranking_metrics_accumulate(kinds, values: torch.Tensor, sums: torch.Tensor, states, *,
+                               draw: torch.Tensor | None = None, want_lists: bool = False):
+    """Stage B.  kinds: the METRIC_KINDS keys of the rows of `values`; states: one fp32 device tensor {total, count}
+    per row, updated in place; draw is advanced by one.  Returns (per-list values, per-list weights), both [n, B],
+    or (None, None)."""
+    what = "ranking_metrics_accumulate"
+    L.require_device(values, what)
+    n, b = values.shape
+    if len(kinds) != n or len(states) != n or tuple(sums.shape) != (5, b):
+        raise L.KrsError(f"{what}: {len(kinds)} kinds, {len(states)} states and sums {tuple(sums.shape)} for values "
+                         f"{tuple(values.shape)}")
+    for s in states:
+        if s.dtype != torch.float32 or s.numel() != 2 or s.device != values.device or not s.is_contiguous():
+            raise L.KrsError(f"{what}: a state must be two contiguous fp32 values on {values.device}")
+    out_v = torch.empty_like(values) if want_lists else None
+    out_w = torch.empty_like(values) if want_lists else None
+    ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in states])
+    ws_bytes = L.lib().krs_ranking_metrics_accumulate_workspace_bytes(b)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=values.device) if ws_bytes else None
+    rc = L.lib().krs_ranking_metrics_accumulate(L.ptr(values), L.ptr(sums),
+                                                _int_array([METRIC_KINDS[k] for k in kinds]), n, b, ptrs,
+                                                L.ptr(out_v), L.ptr(out_w), L.ptr(draw), L.ptr(ws), ws_bytes,
+                                                L.stream_ptr())
+    L.check(rc, "krs_ranking_metrics_accumulate")
+    return out_v, out_w

@@ -36,7 +36,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     objs = []
     for s in srcs:
         src = os.path.join(CSRC, s)
-        # (embed_bag_bwd.hip: ~590 kernel instantiations -- four objects compiled side by side, see KRS_BWD_PART there)
+        # (embed_bag_bwd.hip, the K2 apply kernels: ~590 instantiations -- four objects compiled side by side, see KRS_BWD_PART
+        #  there; their plan is embed_bag_plan.hip, one object like every other source)
         parts = [(f"_p{i}", [f"-DKRS_BWD_PART={i}"]) for i in range(4)] if s == "embed_bag_bwd.hip" else [("", [])]
         for suffix, defs in parts:
             obj = os.path.join(OBJ, s[:-4] + suffix + ".o")

@@ -1,17 +1,14 @@
-// K2 -- index-scatter gradient of the fused embedding bag (backward of K1).
+// K2 -- index-scatter gradient of the fused embedding bag (backward of K1): the APPLY kernels.
 //
 // Replaces the autodiff of ops.take/multiply/sum (the dense [V, D] scatter-add
 // restated by the reference at keras_rs/src/layers/embedding/jax/test_utils.py:395-417,
 // summed per table over the features that share it, :450-468) and, in the fused
 // forms, the per-table optimizer step of jax/test_utils.py:474-497.
 //
-// Plan (once per batch of ids, independent of the gradient values):
-//   keys[p] = tables[t(f)].row_base + ids[p]   (u32; invalid ids -> 0xffffffff)
-//   vals[p] = (bag(p) << 32) | p               (u64)
-//   stable LSD radix sort of (keys, vals) over ceil(log2(total_rows)) bits (namespace rs below: own kernels;
-//   dense bags whose tables form contiguous runs of positions are sorted per table, over the id bits alone).
-//   head flags -> exclusive scan -> segment list (first sorted position of every run of equal
-//   keys), and the work items of the segments longer than kLongSeg lookups.
+// Plan (embed_bag_plan.hip; once per batch of ids, independent of the gradient values): the lookups sorted by global
+//   table row, as (key, bag << 32 | position) pairs, equal keys in ascending position; the segment list (first sorted
+//   position of every run of equal keys); the work items of the segments longer than kLongSeg lookups.  This file
+//   reads them from the workspace laid out by krs_bag_plan.h and knows nothing else of the plan.
 // Apply: a group of LPR lanes (one 16-byte piece of the gradient row per lane, as in K1) per
 //   SEGMENT = per touched table row: it issues the loads of the row (and optimizer slots) it will
 //   update, gathers and sums the segment's gradient rows, and writes the finished row once:
@@ -22,16 +19,16 @@
 //   lookups; rows spanning several chunks are finished from fp32 partial rows in chunk order.
 //   Table / slot rows are read and written non-temporally (each is touched once per launch).
 // Algorithmic bytes: bags*D*s_g + nnz*(4+8) + U*(2*D*s_t [+ 2*D*4 per slot plane]).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
-#include "krs_common.h"
-#include "krs_scan.h"
+#include "krs_bag_plan.h"
 
 // The apply kernels are instantiated per (gradient type, table type, lanes per row, optimizer, weights, scale): 3 dtype
 // pairs x 4 widths x 7 kernels x 7 modes = ~590 kernels (round 4: ~1000 -- the round-1 per-segment kernel and the
 // fp32-gradient / bf16-table pair are gone).  keras_rs_amd/build.py compiles this file four times, in parallel:
-// KRS_BWD_PART 0 = the plan + the dense / sparse / SGD forms, 1 = Adagrad and row-wise Adagrad, 2 = Adam, 3 = FTRL
+// KRS_BWD_PART 0 = the dense / sparse / SGD forms, 1 = Adagrad and row-wise Adagrad, 2 = Adam, 3 = FTRL
 // (entry points outside a part are left out of it).  Undefined = the whole file in one object.
 #ifndef KRS_BWD_PART
 #define KRS_BWD_PART -1
@@ -39,626 +36,7 @@
 #define KRS_BWD_HAS(part) (KRS_BWD_PART < 0 || KRS_BWD_PART == (part))
 
 namespace krs {
-#if KRS_BWD_HAS(0)
-// krs_embed_set_option(KRS_EMBED_OPT_PLAN, v): 0 = table-segmented sort where the layout allows it (default), 1 = always the global sort
-int g_plan_variant = 0;
-#else
-extern int g_plan_variant;
-#endif
 namespace {
-
-constexpr uint32_t kInvalidKey = 0xffffffffu;
-constexpr int kLongSeg = 128;   // segments longer than this are summed by whole workgroups
-constexpr int kChunk = 2048;    // ... in chunks of this many lookups, one workgroup each
-constexpr int kPartialBytes = 2048;  // fp32 partial row of a chunk (row bytes <= 1024 on the vector path)
-
-// one workgroup's share of a long segment
-struct LongItem {
-  uint32_t seg;       // segment index
-  uint32_t chunk;     // which kChunk-sized piece of it
-  uint32_t partial;   // slot in the partial-row buffer, or ~0u when the segment is a single chunk
-};
-// a long segment that spans several chunks: its partial rows are summed in chunk order afterwards
-struct MultiSeg {
-  uint32_t seg, partial_base, n_chunks;
-};
-
-struct PlanLayout {
-  uint32_t* keys_in;      // dead after the sort -> reused as head flags
-  uint32_t* keys_sorted;
-  uint64_t* vals_in;      // dead after the sort -> its second half is reused as seg_start
-  uint64_t* vals_sorted;
-  uint32_t* seg_start;    // = vals_in, next n words: first sorted position of every segment
-  uint32_t* n_seg;        // number of segments (a trailing run of invalid keys counts as one)
-  uint32_t* n_long;       // number of LongItems (device scalar); [1] partial rows handed out; [2] MultiSegs
-  uint32_t* sort_mode;    // 0 = global sort (out-of-range lookups form ONE trailing run), != 0 = table-segmented sort
-  LongItem* long_list;    // work items of the segments longer than kLongSeg (any order)
-  MultiSeg* multi_list;   // segments longer than kChunk
-  float* partials;        // [<= 2 * nnz / kChunk + 2] fp32 partial rows, kPartialBytes apart
-  void* temp;
-  size_t temp_bytes;
-  size_t total_bytes;
-};
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// ---- plan: the sort (LSD radix sort of (row key, bag << 32 | position) pairs, written for this plan) -----------
-// Digits of up to 10 bits, ceil(bits / 10) passes over ceil(log2(total_rows + 1)) key bits (C3: 25 bits = 3 passes,
-// against 4 passes of 8 bits over the same bits in a general-purpose device sort).  One pass = per-tile digit
-// histogram -> exclusive scan of the [digit][tile] counts (krs_scan.h) -> stable scatter.  A tile is 4096 consecutive
-// lookups, one workgroup; wave w owns the w-th quarter, so the (wave, round, lane) order IS the input order and
-// the ranks below keep equal keys in input order (stability = ascending position inside a row's segment = a fixed
-// summation order in the apply kernels).  Dense bags: the first pass computes keys and values from the ids on the
-// fly (no key generation kernel, no round trip of 12 bytes per lookup through HBM).
-namespace rs {
-#ifndef KRS_SORT_TILE
-#define KRS_SORT_TILE 4096       // (development builds vary the tile / workgroup shape: scripts/exp/build_variants.sh)
-#endif
-#ifndef KRS_SORT_THREADS
-#define KRS_SORT_THREADS 512
-#endif
-constexpr int kTile = KRS_SORT_TILE, kMaxBits = 10, kMaxBins = 1 << kMaxBits;
-constexpr int kHistThreads = 256, kHistItems = kTile / kHistThreads;
-constexpr int kThreads = KRS_SORT_THREADS, kWaves = kThreads / 64, kItems = kTile / kThreads;   // scatter: 8 waves x 512 lookups
-constexpr int kGenFeats = 256;   // features whose descriptors the generating pass caches in LDS
-constexpr int kMaxProb = 128;    // tables (problems) of the table-segmented sort
-
-struct Gen {   // key generation for dense bags (first pass)
-  const krs_table* tables;
-  const krs_feature* feats;
-  int n_feats;
-  const void* ids;
-  int id64;
-  int batch;
-  int* err_flag;
-};
-
-struct Pass {
-  const uint32_t* keys_in;     // null in a generating pass
-  const uint64_t* vals_in;
-  uint32_t* keys_out;
-  uint64_t* vals_out;
-  int32_t* counts;             // [bins][tiles]: histogram, then exclusive offsets
-  int64_t nnz;
-  int n_tiles;
-  int shift, bits;
-  Gen gen;
-};
-
-// per-feature constants of the generating pass, in LDS
-struct GenLds {
-  uint32_t base[kGenFeats + 1];   // first lookup position of the feature (nnz < 2^31)
-  uint32_t hot[kGenFeats];
-  uint32_t row_base[kGenFeats];   // total_rows < 2^32 (checked by the plan)
-  uint32_t vocab[kGenFeats];
-};
-__device__ __forceinline__ void load_gen(const Pass& p, GenLds& g, int n_threads) {
-  for (int i = threadIdx.x; i <= p.gen.n_feats; i += n_threads) {
-    if (i < p.gen.n_feats) {
-      const krs_feature ft = p.gen.feats[i];
-      const krs_table tb = p.gen.tables[ft.table];
-      g.base[i] = (uint32_t)ft.ids_base;
-      g.hot[i] = (uint32_t)ft.hot;
-      g.row_base[i] = (uint32_t)tb.row_base;
-      g.vocab[i] = (uint32_t)tb.vocab;
-    } else {
-      g.base[i] = (uint32_t)p.nnz;
-    }
-  }
-}
-// (key, value) of lookup position q; dense bags, features laid out one after the other
-__device__ __forceinline__ void generate(const Pass& p, const GenLds& g, uint32_t q, uint32_t& key, uint64_t& val,
-                                         bool& bad) {
-  int lo = 0, hi = p.gen.n_feats;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (g.base[mid] <= q) lo = mid; else hi = mid;
-  }
-  const uint32_t bag = (uint32_t)lo * (uint32_t)p.gen.batch + (q - g.base[lo]) / g.hot[lo];
-  const int64_t id = ld_index(p.gen.ids, p.gen.id64, q);
-  key = kInvalidKey;
-  if (id >= 0 && id < (int64_t)g.vocab[lo]) key = g.row_base[lo] + (uint32_t)id;
-  else bad = true;
-  val = ((uint64_t)bag << 32) | (uint64_t)q;
-}
-
-template <bool GEN>
-__global__ __launch_bounds__(kHistThreads) void hist_kernel(const Pass p) {
-  __shared__ int h[kMaxBins];
-  __shared__ GenLds g;
-  const int bins = 1 << p.bits;
-  for (int i = threadIdx.x; i < bins; i += kHistThreads) h[i] = 0;
-  if constexpr (GEN) load_gen(p, g, kHistThreads);
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kTile;
-  bool bad = false;
-  for (int it = 0; it < kHistItems; ++it) {
-    const int64_t q = base + it * kHistThreads + threadIdx.x;
-    if (q < p.nnz) {
-      uint32_t key;
-      if constexpr (GEN) {
-        uint64_t v;
-        generate(p, g, (uint32_t)q, key, v, bad);
-      } else {
-        key = p.keys_in[q];
-      }
-      atomicAdd(&h[(key >> p.shift) & (bins - 1)], 1);
-    }
-  }
-  if constexpr (GEN)
-    if (bad && p.gen.err_flag) atomicOr(p.gen.err_flag, KRS_FLAG_ID_OUT_OF_RANGE);
-  __syncthreads();
-  for (int i = threadIdx.x; i < bins; i += kHistThreads) p.counts[(int64_t)i * p.n_tiles + blockIdx.x] = h[i];
-}
-
-template <bool GEN>
-__global__ __launch_bounds__(kThreads) void scatter_kernel(const Pass p) {
-  // 74 KB of LDS: two workgroups (16 waves) per CU
-  __shared__ uint16_t cnt[kWaves][kMaxBins];   // per wave: elements of each digit seen so far -> (wave, digit) start
-  __shared__ uint16_t tile_excl[kMaxBins];     // first slot of every digit in the tile's sorted image
-  __shared__ int gbase[kMaxBins];              // first output slot of the tile's elements of every digit
-  __shared__ uint32_t skey[kTile];             // the tile, sorted by digit (stable): consecutive threads then
-  __shared__ uint64_t sval[kTile];             // write consecutive output slots inside a digit's run
-  __shared__ int wtot[kWaves];
-  __shared__ GenLds g;
-  const int bins = 1 << p.bits;
-  for (int i = threadIdx.x; i < kWaves * kMaxBins; i += kThreads) (&cnt[0][0])[i] = 0;
-  if constexpr (GEN) load_gen(p, g, kThreads);
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t tile0 = (int64_t)blockIdx.x * kTile;
-  const int64_t base = tile0 + (int64_t)wave * (kTile / kWaves);
-  uint32_t key[kItems];
-  uint64_t val[kItems];
-  int rank[kItems];
-  bool bad = false;
-  volatile uint16_t* mine = cnt[wave];
-#pragma unroll
-  for (int it = 0; it < kItems; ++it) {
-    const int64_t q = base + it * 64 + lane;
-    const bool live = q < p.nnz;
-    key[it] = kInvalidKey;
-    val[it] = 0;
-    if (live) {
-      if constexpr (GEN) {
-        generate(p, g, (uint32_t)q, key[it], val[it], bad);
-      } else {
-        key[it] = p.keys_in[q];
-        val[it] = p.vals_in[q];
-      }
-    }
-    const int d = (int)((key[it] >> p.shift) & (bins - 1));
-    // lanes of this round with the same digit
-    unsigned long long peers = __ballot(live);
-    for (int b = 0; b < p.bits; ++b) {
-      const unsigned long long m = __ballot((d >> b) & 1);
-      peers &= ((d >> b) & 1) ? m : ~m;
-    }
-    int r = 0, c = 0;
-    if (live) {
-      r = __popcll(peers & ((1ULL << lane) - 1ULL));
-      const int leader = __ffsll((long long)peers) - 1;
-      if (lane == leader) {
-        c = mine[d];
-        mine[d] = (uint16_t)(c + __popcll(peers));
-      }
-      c = __shfl(c, leader, 64);
-    }
-    rank[it] = c + r;
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  // digit totals of the tile -> exclusive scan over the digits (bins <= 1024 = 2 per thread)
-  int tot[2], run = 0;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int i = threadIdx.x * 2 + k;
-    tot[k] = 0;
-    if (i < bins)
-      for (int w = 0; w < kWaves; ++w) tot[k] += cnt[w][i];
-    run += tot[k];
-  }
-  int x = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wtot[wave] = x;
-  __syncthreads();
-  int excl = x - run;
-  for (int w = 0; w < wave; ++w) excl += wtot[w];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int i = threadIdx.x * 2 + k;
-    if (i < bins) {
-      tile_excl[i] = (uint16_t)excl;
-      gbase[i] = p.counts[(int64_t)i * p.n_tiles + blockIdx.x];
-      int o = excl;
-      for (int w = 0; w < kWaves; ++w) {
-        const int t = cnt[w][i];
-        cnt[w][i] = (uint16_t)o;
-        o += t;
-      }
-      excl += tot[k];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < kItems; ++it) {
-    const int64_t q = base + it * 64 + lane;
-    if (q < p.nnz) {
-      const int d = (int)((key[it] >> p.shift) & (bins - 1));
-      const int lp = cnt[wave][d] + rank[it];
-      skey[lp] = key[it];
-      sval[lp] = val[it];
-    }
-  }
-  __syncthreads();
-  const int n_here = (int)min<int64_t>(kTile, p.nnz - tile0);
-#pragma unroll
-  for (int it = 0; it < kItems; ++it) {
-    const int i = it * kThreads + threadIdx.x;
-    if (i < n_here) {
-      const uint32_t k = skey[i];
-      const int d = (int)((k >> p.shift) & (bins - 1));
-      const int pos = gbase[d] + (i - (int)tile_excl[d]);
-      p.keys_out[pos] = k;
-      p.vals_out[pos] = sval[i];
-    }
-  }
-  (void)bad;   // the histogram pass of the same data reports out-of-range ids
-}
-
-// ---- the same sort, SEGMENTED BY TABLE (round 3) ------------------------------------------------------------
-// Dense bags arrive feature-major, so the lookups of one table already form ONE contiguous run of positions (when
-// the features of a table are neighbours and tables ascend with the features -- what DistributedEmbedding builds).
-// Sorting by the global row then needs no pass over the table bits: every table's run is an independent PROBLEM,
-// sorted in place by the id alone -- ceil(log2(max vocab + 1)) bits, 20 at C3 = TWO passes instead of three -- and
-// the problems' sorted runs, one after the other, are exactly the global order.  Tiles never straddle problems
-// (a problem's last tile may be partial); the count matrix is laid out [problem][digit][tile of the problem], so
-// ONE exclusive scan over it still yields every tile's output offsets (a problem's lookups stay inside its run).
-// Intermediate passes carry (local key, position) = 8 bytes per lookup instead of (key, bag << 32 | position) = 12;
-// the LAST pass writes what the apply kernels read: the global key (row_base + id; all ones for an invalid id) and
-// the 64-bit value, whose bag is recomputed from the position (feature constants in LDS, as the first pass does).
-// Per lookup 40 bytes move instead of 76.  Out-of-range ids sort to the END OF THEIR TABLE'S RUN (sentinel = all
-// ones in the key bits), not to the end of the array: the apply kernels skip invalid segments wherever they are;
-// the compact (sparse) form, whose output is indexed by segment, keeps the global sort.
-struct Seg {
-  int n;                                  // problems
-  uint32_t lookup_start[kMaxProb + 1];    // first lookup position of problem i; [n] = nnz
-  uint32_t tile_start[kMaxProb + 1];      // first tile of problem i; [n] = tiles in all
-  uint32_t row_base[kMaxProb];            // global row of the table's row 0
-};
-struct SegPass {
-  const uint32_t* keys_in;     // FIRST pass: null (keys come from the ids)
-  const uint32_t* pos_in;
-  uint32_t* keys_out;          // LAST pass: global keys
-  uint32_t* pos_out;           // intermediate passes
-  uint64_t* vals_out;          // LAST pass
-  int32_t* counts;
-  int64_t nnz;
-  int shift, bits, key_bits;
-  Gen gen;
-  Seg seg;
-};
-__device__ __forceinline__ int seg_problem(const Seg& sg, uint32_t tile) {
-  int lo = 0, hi = sg.n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (sg.tile_start[mid] <= tile) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ void load_gen_seg(const SegPass& p, GenLds& g, int n_threads) {
-  for (int i = threadIdx.x; i <= p.gen.n_feats; i += n_threads) {
-    if (i < p.gen.n_feats) {
-      const krs_feature ft = p.gen.feats[i];
-      const krs_table tb = p.gen.tables[ft.table];
-      g.base[i] = (uint32_t)ft.ids_base;
-      g.hot[i] = (uint32_t)ft.hot;
-      g.row_base[i] = (uint32_t)tb.row_base;
-      g.vocab[i] = (uint32_t)tb.vocab;
-    } else {
-      g.base[i] = (uint32_t)p.nnz;
-    }
-  }
-}
-__device__ __forceinline__ int gen_feature(const GenLds& g, int n_feats, uint32_t q) {
-  int lo = 0, hi = n_feats;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (g.base[mid] <= q) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-// local key of lookup position q: its id, or all ones in the key bits when the id is out of range
-__device__ __forceinline__ uint32_t seg_local_key(const SegPass& p, const GenLds& g, uint32_t q, bool& bad) {
-  const int f = gen_feature(g, p.gen.n_feats, q);
-  const int64_t id = ld_index(p.gen.ids, p.gen.id64, q);
-  if (id >= 0 && id < (int64_t)g.vocab[f]) return (uint32_t)id;
-  bad = true;
-  return (1u << p.key_bits) - 1u;
-}
-
-// (Round 5 measured one workgroup per EIGHT consecutive tiles here, so that a digit's counters leave as 32 contiguous bytes:
-//  the write counter of this kernel fell from 121 MB to 14 MB per launch -- one tile's 1024 counters are 1024 scattered
-//  4-byte stores into the [digit][tile] matrix -- and the plan got SLOWER, 558 -> 582 us with 1024-thread groups (1815 us
-//  with 256-thread ones): the partial-sector writes are absorbed by L2, the kernel wants its 3400 independent workgroups.)
-template <bool FIRST>
-__global__ __launch_bounds__(kHistThreads) void hist_seg_kernel(const SegPass p) {
-  __shared__ int h[kMaxBins];
-  __shared__ GenLds g;
-  const int bins = 1 << p.bits;
-  for (int i = threadIdx.x; i < bins; i += kHistThreads) h[i] = 0;
-  if constexpr (FIRST) load_gen_seg(p, g, kHistThreads);
-  __syncthreads();
-  const int pr = seg_problem(p.seg, blockIdx.x);
-  const uint32_t tl = blockIdx.x - p.seg.tile_start[pr], nt = p.seg.tile_start[pr + 1] - p.seg.tile_start[pr];
-  const int64_t base = (int64_t)p.seg.lookup_start[pr] + (int64_t)tl * kTile;
-  const int64_t end = min<int64_t>(base + kTile, p.seg.lookup_start[pr + 1]);
-  bool bad = false;
-  uint32_t key[kHistItems];
-  if constexpr (FIRST) {
-    int64_t idv[kHistItems];
-#pragma unroll
-    for (int it = 0; it < kHistItems; ++it)
-      idv[it] = ld_index(p.gen.ids, p.gen.id64, min<int64_t>(base + it * kHistThreads + threadIdx.x, end - 1));
-    // (a tile lies inside ONE feature almost always -- tiles never straddle tables, and a table's features are few: the
-    //  per-key search over the feature bases is then one search per tile; round 5)
-    const int f_lo = gen_feature(g, p.gen.n_feats, (uint32_t)base), f_hi = gen_feature(g, p.gen.n_feats, (uint32_t)(end - 1));
-#pragma unroll
-    for (int it = 0; it < kHistItems; ++it) {
-      const int64_t q = min<int64_t>(base + it * kHistThreads + threadIdx.x, end - 1);
-      const int f = f_lo == f_hi ? f_lo : gen_feature(g, p.gen.n_feats, (uint32_t)q);
-      const bool valid = idv[it] >= 0 && idv[it] < (int64_t)g.vocab[f];
-      key[it] = valid ? (uint32_t)idv[it] : (1u << p.key_bits) - 1u;
-      bad = bad || (!valid && base + it * kHistThreads + threadIdx.x < end);
-    }
-  } else {
-#pragma unroll
-    for (int it = 0; it < kHistItems; ++it)
-      key[it] = p.keys_in[min<int64_t>(base + it * kHistThreads + threadIdx.x, end - 1)];
-  }
-#pragma unroll
-  for (int it = 0; it < kHistItems; ++it)
-    if (base + it * kHistThreads + threadIdx.x < end) atomicAdd(&h[(key[it] >> p.shift) & (bins - 1)], 1);
-  if constexpr (FIRST)
-    if (bad && p.gen.err_flag) atomicOr(p.gen.err_flag, KRS_FLAG_ID_OUT_OF_RANGE);
-  __syncthreads();
-  int32_t* dst = p.counts + (int64_t)bins * p.seg.tile_start[pr];
-  for (int i = threadIdx.x; i < bins; i += kHistThreads) dst[(int64_t)i * nt + tl] = h[i];
-}
-
-template <bool FIRST, bool LAST>
-__global__ __launch_bounds__(kThreads) void scatter_seg_kernel(const SegPass p) {
-  __shared__ uint16_t cnt[kWaves][kMaxBins];
-  __shared__ uint16_t tile_excl[kMaxBins];
-  __shared__ int gbase[kMaxBins];
-  __shared__ uint32_t skey[kTile];
-  __shared__ uint32_t spos[kTile];
-  __shared__ int wtot[kWaves];
-  __shared__ GenLds g;
-  const int bins = 1 << p.bits;
-  for (int i = threadIdx.x; i < kWaves * kMaxBins; i += kThreads) (&cnt[0][0])[i] = 0;
-  if constexpr (FIRST || LAST) load_gen_seg(p, g, kThreads);
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int pr = seg_problem(p.seg, blockIdx.x);
-  const uint32_t tl = blockIdx.x - p.seg.tile_start[pr], nt = p.seg.tile_start[pr + 1] - p.seg.tile_start[pr];
-  const int64_t tile0 = (int64_t)p.seg.lookup_start[pr] + (int64_t)tl * kTile;
-  const int64_t tile_end = min<int64_t>(tile0 + kTile, p.seg.lookup_start[pr + 1]);
-  const int64_t base = tile0 + (int64_t)wave * (kTile / kWaves);
-  uint32_t key[kItems], pos[kItems];
-  int rank[kItems];
-  bool bad = false;
-  volatile uint16_t* mine = cnt[wave];
-  // all of the thread's keys are requested before the first is ranked (addresses clamped to the tile, dead slots
-  // masked afterwards): one exposed memory latency per tile instead of one per round of the ranking loop below,
-  // whose LDS counter updates form a dependent chain the loads could not be scheduled across
-  if constexpr (FIRST) {
-    int64_t idv[kItems];
-#pragma unroll
-    for (int it = 0; it < kItems; ++it) {
-      const int64_t q = min<int64_t>(base + it * 64 + lane, tile_end - 1);
-      idv[it] = ld_index(p.gen.ids, p.gen.id64, q);
-    }
-    const int f_lo = gen_feature(g, p.gen.n_feats, (uint32_t)tile0), f_hi = gen_feature(g, p.gen.n_feats, (uint32_t)(tile_end - 1));
-#pragma unroll
-    for (int it = 0; it < kItems; ++it) {
-      const int64_t q = min<int64_t>(base + it * 64 + lane, tile_end - 1);
-      const int f = f_lo == f_hi ? f_lo : gen_feature(g, p.gen.n_feats, (uint32_t)q);   // (one search per tile, see hist_seg_kernel)
-      const bool valid = idv[it] >= 0 && idv[it] < (int64_t)g.vocab[f];
-      key[it] = valid ? (uint32_t)idv[it] : (1u << p.key_bits) - 1u;
-      pos[it] = (uint32_t)q;
-    }
-  } else {
-#pragma unroll
-    for (int it = 0; it < kItems; ++it) {
-      const int64_t q = min<int64_t>(base + it * 64 + lane, tile_end - 1);
-      key[it] = p.keys_in[q];
-      pos[it] = p.pos_in[q];
-    }
-  }
-#pragma unroll
-  for (int it = 0; it < kItems; ++it) {
-    const int64_t q = base + it * 64 + lane;
-    const bool live = q < tile_end;
-    if (!live) { key[it] = 0xffffffffu; pos[it] = 0; }
-    const int d = (int)((key[it] >> p.shift) & (bins - 1));
-    unsigned long long peers = __ballot(live);
-    for (int b = 0; b < p.bits; ++b) {
-      const unsigned long long m = __ballot((d >> b) & 1);
-      peers &= ((d >> b) & 1) ? m : ~m;
-    }
-    int r = 0, c = 0;
-    if (live) {
-      r = __popcll(peers & ((1ULL << lane) - 1ULL));
-      const int leader = __ffsll((long long)peers) - 1;
-      if (lane == leader) {
-        c = mine[d];
-        mine[d] = (uint16_t)(c + __popcll(peers));
-      }
-      c = __shfl(c, leader, 64);
-    }
-    rank[it] = c + r;
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  int tot[2], run = 0;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int i = threadIdx.x * 2 + k;
-    tot[k] = 0;
-    if (i < bins)
-      for (int w = 0; w < kWaves; ++w) tot[k] += cnt[w][i];
-    run += tot[k];
-  }
-  int x = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wtot[wave] = x;
-  __syncthreads();
-  int excl = x - run;
-  for (int w = 0; w < wave; ++w) excl += wtot[w];
-  const int32_t* cbase = p.counts + (int64_t)bins * p.seg.tile_start[pr];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int i = threadIdx.x * 2 + k;
-    if (i < bins) {
-      tile_excl[i] = (uint16_t)excl;
-      gbase[i] = cbase[(int64_t)i * nt + tl];
-      int o = excl;
-      for (int w = 0; w < kWaves; ++w) {
-        const int t = cnt[w][i];
-        cnt[w][i] = (uint16_t)o;
-        o += t;
-      }
-      excl += tot[k];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < kItems; ++it) {
-    const int64_t q = base + it * 64 + lane;
-    if (q < tile_end) {
-      const int d = (int)((key[it] >> p.shift) & (bins - 1));
-      const int lp = cnt[wave][d] + rank[it];
-      skey[lp] = key[it];
-      spos[lp] = pos[it];
-    }
-  }
-  __syncthreads();
-  const int n_here = (int)(tile_end - tile0);
-  const uint32_t sentinel = (1u << p.key_bits) - 1u, rb = p.seg.row_base[pr];
-  // (last pass: a key's original position lies anywhere in its TABLE's run; a table looked up by one feature -- the usual
-  //  case -- needs one search per tile instead of one per key)
-  int pf_lo = 0, pf_hi = 1;
-  if constexpr (LAST) {
-    pf_lo = gen_feature(g, p.gen.n_feats, p.seg.lookup_start[pr]);
-    pf_hi = gen_feature(g, p.gen.n_feats, p.seg.lookup_start[pr + 1] - 1);
-  }
-#pragma unroll
-  for (int it = 0; it < kItems; ++it) {
-    const int i = it * kThreads + threadIdx.x;
-    if (i < n_here) {
-      const uint32_t k = skey[i], q = spos[i];
-      const int d = (int)((k >> p.shift) & (bins - 1));
-      const int o = gbase[d] + (i - (int)tile_excl[d]);
-      if constexpr (LAST) {
-        const int f = pf_lo == pf_hi ? pf_lo : gen_feature(g, p.gen.n_feats, q);
-        const uint32_t bag = (uint32_t)f * (uint32_t)p.gen.batch + (q - g.base[f]) / g.hot[f];
-        p.keys_out[o] = k == sentinel ? kInvalidKey : rb + k;
-        p.vals_out[o] = ((uint64_t)bag << 32) | (uint64_t)q;
-      } else {
-        p.keys_out[o] = k;
-        p.pos_out[o] = q;
-      }
-    }
-  }
-  (void)bad;
-}
-
-inline int n_passes(unsigned bits) { return (int)((bits + kMaxBits - 1) / kMaxBits); }
-inline size_t temp_bytes(int64_t nnz) {
-  const int64_t tiles = ceil_div(nnz > 0 ? nnz : 1, kTile) + kMaxProb;   // (every problem may end in a partial tile)
-  const size_t counts = (size_t)kMaxBins * tiles * sizeof(int32_t);
-  return align_up(counts, 256) + align_up(scan::workspace_bytes((int64_t)kMaxBins * tiles), 256) +
-         align_up(scan::workspace_bytes(nnz), 256);
-}
-}  // namespace rs
-
-PlanLayout plan_layout(void* ws, int64_t nnz, bool need_temp = false) {
-  PlanLayout l;
-  char* p = reinterpret_cast<char*>(ws);
-  size_t o = 0;
-  const size_t n = (size_t)(nnz > 0 ? nnz : 1);
-  l.keys_in = reinterpret_cast<uint32_t*>(p + o); o += align_up(n * 4, 256);
-  l.keys_sorted = reinterpret_cast<uint32_t*>(p + o); o += align_up(n * 4, 256);
-  l.vals_in = reinterpret_cast<uint64_t*>(p + o); o += align_up(n * 8 + 8, 256);
-  l.vals_sorted = reinterpret_cast<uint64_t*>(p + o); o += align_up(n * 8, 256);
-  l.n_seg = reinterpret_cast<uint32_t*>(p + o);
-  l.n_long = l.n_seg + 1;
-  l.sort_mode = l.n_seg + 8; o += 256;
-  // every long segment has <= len / kChunk + 1 items; there are <= n / kLongSeg long segments
-  l.long_list = reinterpret_cast<LongItem*>(p + o); o += align_up((n / kLongSeg + n / kChunk + 2) * sizeof(LongItem), 256);
-  l.multi_list = reinterpret_cast<MultiSeg*>(p + o); o += align_up((n / kChunk + 2) * sizeof(MultiSeg), 256);
-  l.partials = reinterpret_cast<float*>(p + o); o += align_up((2 * (n / kChunk) + 2) * (size_t)kPartialBytes, 256);
-  l.seg_start = reinterpret_cast<uint32_t*>(l.vals_in) + n;
-  l.temp = p + o;
-  l.temp_bytes = need_temp ? rs::temp_bytes(nnz) : 0;
-  l.total_bytes = o + l.temp_bytes;
-  return l;
-}
-
-// ---- plan: key generation ---------------------------------------------------
-struct KeyParams {
-  const krs_table* tables;
-  const krs_feature* feats;
-  int n_feats;
-  const void* ids;
-  int id64;
-  const void* offsets;
-  int off64;
-  int batch;
-  uint32_t* keys;
-  uint64_t* vals;
-  int* err_flag;
-};
-
-// 16 lanes per bag; lanes stride over the bag's positions (coalesced writes).
-__global__ __launch_bounds__(256) void bag_keys_kernel(const KeyParams p) {
-  const int64_t bag = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  const int sub = threadIdx.x & 15;
-  if (bag >= (int64_t)p.n_feats * p.batch) return;
-  const int f = (int)(bag / p.batch);
-  const int b = (int)(bag - (int64_t)f * p.batch);
-  const krs_feature ft = p.feats[f];
-  const krs_table tb = p.tables[ft.table];
-  int64_t s, e;
-  if (p.offsets) {
-    s = ld_index(p.offsets, p.off64, bag);
-    e = ld_index(p.offsets, p.off64, bag + 1);
-  } else {
-    s = ft.ids_base + (int64_t)b * ft.hot;
-    e = s + ft.hot;
-  }
-  int oob = 0;
-  for (int64_t q = s + sub; q < e; q += 16) {
-    const int64_t id = ld_index(p.ids, p.id64, q);
-    uint32_t key = kInvalidKey;
-    if (id >= 0 && id < tb.vocab)
-      key = (uint32_t)(tb.row_base + id);
-    else
-      oob = 1;
-    p.keys[q] = key;
-    p.vals[q] = ((uint64_t)bag << 32) | (uint64_t)(uint32_t)q;
-  }
-  if (oob && p.err_flag) atomicOr(p.err_flag, KRS_FLAG_ID_OUT_OF_RANGE);
-}
 
 // ---- apply ------------------------------------------------------------------
 enum ApplyMode { kDense = 0, kSgd = 1, kAdagrad = 2, kSparse = 3, kAdam = 4, kFtrl = 5, kAdagradRow = 6 };
@@ -1394,93 +772,6 @@ __global__ __launch_bounds__(256) void bag_apply_generic(const ApplyParams p, in
   }
 }
 
-// ---- plan: segment list ---------------------------------------------------------
-// (Measured and not kept: sorting each feature's lookups by row id alone when every feature has its own table -- the
-//  lookups arrive grouped by feature, so two 10-bit passes replace the three 9/8/8-bit ones at 26 x 1 M rows: 602 us
-//  either way; the scatter pass pays per key BIT (ballots), 20 against 25, and the per-feature tile bookkeeping and the
-//  wider count matrix took the difference back.)
-// Segment list (first sorted position of every run of equal keys) by block-wise compaction: heads are counted
-// per block of 4096 keys, the block counts are scanned by one workgroup, and a second pass over the keys writes
-// every head's position at (block offset + rank inside the block).  Two reads of the sorted keys and one
-// compact write -- the flag / index arrays of a flags -> device-wide scan -> scatter pipeline (five launches,
-// 0.5 GB of traffic at 14 M lookups) are not materialised.  A trailing run of invalid keys is a segment too.
-constexpr int kSegTile = 4096, kSegItems = 16;   // 256 threads x 16 consecutive keys
-__device__ __forceinline__ uint32_t seg_head_mask(const uint32_t* keys, int64_t nnz, int64_t t0) {
-  if (t0 >= nnz) return 0u;
-  uint32_t prev = t0 > 0 ? keys[t0 - 1] : ~keys[0];   // position 0 is a head
-  uint32_t mask = 0u;
-  if (t0 + kSegItems <= nnz) {
-    const uint4* v = reinterpret_cast<const uint4*>(keys + t0);   // t0 is a multiple of 16: 64-byte aligned
-#pragma unroll
-    for (int q = 0; q < kSegItems / 4; ++q) {
-      const uint4 k = v[q];
-      mask |= (uint32_t)(k.x != prev) << (4 * q);
-      mask |= (uint32_t)(k.y != k.x) << (4 * q + 1);
-      mask |= (uint32_t)(k.z != k.y) << (4 * q + 2);
-      mask |= (uint32_t)(k.w != k.z) << (4 * q + 3);
-      prev = k.w;
-    }
-  } else {
-    for (int k = 0; t0 + k < nnz; ++k) {
-      const uint32_t cur = keys[t0 + k];
-      mask |= (uint32_t)(cur != prev) << k;
-      prev = cur;
-    }
-  }
-  return mask;
-}
-__global__ __launch_bounds__(256) void seg_count_kernel(const uint32_t* keys, int64_t nnz, int32_t* block_heads) {
-  __shared__ int total;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
-  int c = __popc(seg_head_mask(keys, nnz, (int64_t)blockIdx.x * kSegTile + threadIdx.x * kSegItems));
-  for (int o = 32; o; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&total, c);   // integer: order does not matter
-  __syncthreads();
-  if (threadIdx.x == 0) block_heads[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(256) void seg_emit_kernel(const uint32_t* keys, int64_t nnz, const int32_t* block_off,
-                                                       uint32_t* seg_start, uint32_t* n_seg) {
-  __shared__ int wsum[4];
-  const int64_t t0 = (int64_t)blockIdx.x * kSegTile + threadIdx.x * kSegItems;
-  const uint32_t mask = seg_head_mask(keys, nnz, t0);
-  const int c = __popc(mask), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  uint32_t off = (uint32_t)block_off[blockIdx.x] + (uint32_t)(x - c);
-  for (int w = 0; w < wave; ++w) off += (uint32_t)wsum[w];
-  uint32_t m = mask;
-  while (m) {
-    const int k = __ffs(m) - 1;
-    m &= m - 1;
-    seg_start[off++] = (uint32_t)(t0 + k);
-  }
-  if (t0 < nnz && t0 + kSegItems >= nnz) *n_seg = off;   // the thread that holds the last key
-}
-__global__ void long_list_kernel(const uint32_t* seg_start, const uint32_t* n_seg, int64_t nnz, uint32_t* counters,
-                                 LongItem* items, MultiSeg* multi) {
-  // counters[0] = work items, [1] = partial rows handed out, [2] = multi-chunk segments
-  const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t ns = *n_seg;
-  if (u >= ns) return;
-  const int64_t e = u + 1 < ns ? (int64_t)seg_start[u + 1] : nnz;
-  const int64_t len = e - (int64_t)seg_start[u];
-  if (len <= kLongSeg) return;
-  const uint32_t nch = (uint32_t)((len + kChunk - 1) / kChunk);
-  const uint32_t base = atomicAdd(counters, nch);
-  uint32_t pb = 0xffffffffu;
-  if (nch > 1) {
-    pb = atomicAdd(counters + 1, nch);
-    multi[atomicAdd(counters + 2, 1u)] = MultiSeg{(uint32_t)u, pb, nch};
-  }
-  for (uint32_t c = 0; c < nch; ++c) items[base + c] = LongItem{(uint32_t)u, c, nch > 1 ? pb + c : 0xffffffffu};
-}
 __global__ void count_unique_kernel(const uint32_t* keys, const uint32_t* n_seg, const uint32_t* sort_mode, int64_t nnz,
                                     int64_t* n_unique) {
   // segments minus the trailing run of invalid keys, if any.  A table-segmented plan leaves the out-of-range lookups at
@@ -1588,231 +879,40 @@ ApplyParams make_apply(const krs_table* tables, int n_tables, const krs_feature*
   return p;
 }
 
+// What the entry points of the table forms do: check the arguments, point an ApplyParams at the plan in the workspace,
+// run MODE.  hyper_d_dev: Adam's bias-correction factor in device memory (ApplyParams::hyper_d_dev).
+template <int MODE>
+int apply_tables(const krs_table* tables, int n_tables, const krs_feature* feats, int n_feats, const float* weights,
+                 const float* bag_scale, const void* grad, int grad_dtype, int64_t grad_ld, int batch, int dim,
+                 int table_dtype, int64_t nnz, const void* workspace, void* stream,
+                 Hyper hyper = Hyper{0.0f, 0.0f, 0.0f, 0.0f}, const float* hyper_d_dev = nullptr) {
+  if (int rc = check_apply_args(tables, 1, feats, grad, grad_dtype, batch, dim, nnz, workspace)) return rc;
+  ApplyParams p = make_apply(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_ld, batch, dim, nnz, workspace);
+  p.hyper = hyper;
+  p.hyper_d_dev = hyper_d_dev;
+  return run_apply<MODE>(p, grad_dtype, table_dtype, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 }  // namespace krs
 
 using namespace krs;
 
 #if KRS_BWD_HAS(0)
-extern "C" size_t krs_embed_bag_bwd_workspace_bytes(int64_t nnz) {
-  if (nnz < 0) return 0;
-  return plan_layout(nullptr, nnz, true).total_bytes;
-}
-#endif
-
-// Which sort produced the plan is recorded IN the workspace (PlanLayout::sort_mode, written by the plan call on its
-// stream): krs_embed_bag_bwd_sparse reports n_unique = -1 for a table-segmented plan wherever the workspace has been
-// copied to.  (Round 3 also kept a host map keyed by the workspace address; an allocator hands freed addresses out
-// again, so a stale entry could refuse a good plan -- removed)
-
-// Table-segmented sort (rs::scatter_seg_kernel) when the host descriptors are given and the lookups are laid out for
-// it: dense bags, the features of a table neighbours, tables (and their row bases) ascending with the features.
-// Returns true when it has enqueued the sort; false = the caller runs the global sort.
-static bool plan_sort_by_table(const PlanLayout& l, const krs_table* tables, const krs_table* tables_host, int n_tables,
-                               const krs_feature* feats, const krs_feature* feats_host, int n_feats, const void* ids,
-                               int id_type, int batch, int64_t nnz, int* err_flag, hipStream_t st) {
-  if (!tables_host || !feats_host || n_feats > rs::kGenFeats || n_tables <= 0) return false;
-  rs::SegPass sp;
-  rs::Seg& sg = sp.seg;
-  sg.n = 0;
-  int64_t pos = 0, max_vocab = 0;
-  int prev_table = -1;
-  for (int f = 0; f < n_feats; ++f) {
-    const krs_feature& ft = feats_host[f];
-    if (ft.hot < 1 || ft.ids_base != pos || ft.table < prev_table || ft.table >= n_tables) return false;
-    if (ft.table != prev_table) {
-      if (sg.n == rs::kMaxProb) return false;
-      const krs_table& tb = tables_host[ft.table];
-      if (prev_table >= 0 && tb.row_base < tables_host[prev_table].row_base + tables_host[prev_table].vocab) return false;
-      sg.lookup_start[sg.n] = (uint32_t)pos;
-      sg.row_base[sg.n] = (uint32_t)tb.row_base;
-      max_vocab = std::max<int64_t>(max_vocab, tb.vocab);
-      ++sg.n;
-      prev_table = ft.table;
-    }
-    pos += (int64_t)batch * ft.hot;
-  }
-  if (pos != nnz || sg.n == 0) return false;
-  sg.lookup_start[sg.n] = (uint32_t)nnz;
-  uint32_t tiles = 0;
-  for (int i = 0; i < sg.n; ++i) {
-    sg.tile_start[i] = tiles;
-    tiles += (uint32_t)ceil_div((int64_t)sg.lookup_start[i + 1] - sg.lookup_start[i], rs::kTile);
-  }
-  sg.tile_start[sg.n] = tiles;
-  if (tiles == 0) return false;
-  // key = id, plus one pattern (all ones) for an out-of-range id
-  unsigned bits = 1;
-  while (bits < 32 && (1ULL << bits) <= (uint64_t)max_vocab) ++bits;
-  if (bits > 31) return false;
-  const int passes = rs::n_passes(bits);
-  char* tp = reinterpret_cast<char*>(l.temp);
-  int32_t* counts = reinterpret_cast<int32_t*>(tp);
-  tp += align_up((size_t)rs::kMaxBins * (ceil_div(nnz, rs::kTile) + rs::kMaxProb) * sizeof(int32_t), 256);
-  int32_t* sums = reinterpret_cast<int32_t*>(tp);
-  sp.counts = counts; sp.nnz = nnz; sp.key_bits = (int)bits;
-  sp.gen.tables = tables; sp.gen.feats = feats; sp.gen.n_feats = n_feats; sp.gen.ids = ids;
-  sp.gen.id64 = id_type == KRS_I64; sp.gen.batch = batch; sp.gen.err_flag = err_flag;
-  // intermediate (key, position) pairs ping-pong between I0 = (keys_in, vals_in as u32) and I1 = (keys_sorted,
-  // vals_sorted as u32); the LAST pass reads I0 and writes the final (keys_sorted, vals_sorted): the pass before it
-  // writes I0, the one before that I1, ...
-  uint32_t* k0 = l.keys_in; uint32_t* q0 = reinterpret_cast<uint32_t*>(l.vals_in);
-  uint32_t* k1 = l.keys_sorted; uint32_t* q1 = reinterpret_cast<uint32_t*>(l.vals_sorted);
-  unsigned done = 0;
-  for (int ps = 0; ps < passes; ++ps) {
-    const bool first = ps == 0, last = ps == passes - 1;
-    sp.bits = (int)((bits - done + (passes - ps) - 1) / (passes - ps));
-    sp.shift = (int)done;
-    const bool out_is_i0 = ((passes - 2 - ps) % 2) == 0;        // (meaningless for the last pass)
-    const bool in_is_i0 = ((passes - 1 - ps) % 2) == 0;         // the last pass reads I0
-    sp.keys_in = first ? nullptr : (in_is_i0 ? k0 : k1);
-    sp.pos_in = first ? nullptr : (in_is_i0 ? q0 : q1);
-    sp.keys_out = last ? l.keys_sorted : (out_is_i0 ? k0 : k1);
-    sp.pos_out = last ? nullptr : (out_is_i0 ? q0 : q1);
-    sp.vals_out = last ? l.vals_sorted : nullptr;
-    if (first) hipLaunchKernelGGL(rs::hist_seg_kernel<true>, dim3(tiles), dim3(rs::kHistThreads), 0, st, sp);
-    else hipLaunchKernelGGL(rs::hist_seg_kernel<false>, dim3(tiles), dim3(rs::kHistThreads), 0, st, sp);
-    scan::exclusive(counts, counts, (int64_t)(1 << sp.bits) * tiles, sums, nullptr, st);
-    if (first && last) hipLaunchKernelGGL((rs::scatter_seg_kernel<true, true>), dim3(tiles), dim3(rs::kThreads), 0, st, sp);
-    else if (first) hipLaunchKernelGGL((rs::scatter_seg_kernel<true, false>), dim3(tiles), dim3(rs::kThreads), 0, st, sp);
-    else if (last) hipLaunchKernelGGL((rs::scatter_seg_kernel<false, true>), dim3(tiles), dim3(rs::kThreads), 0, st, sp);
-    else hipLaunchKernelGGL((rs::scatter_seg_kernel<false, false>), dim3(tiles), dim3(rs::kThreads), 0, st, sp);
-    done += (unsigned)sp.bits;
-  }
-  return true;
-}
-
-static int plan_impl(const krs_table* tables, const krs_table* tables_host, int n_tables, const krs_feature* feats,
-                     const krs_feature* feats_host, int n_feats, const void* ids, int id_type, const void* offsets,
-                     int off_type, int batch, int64_t nnz, int64_t total_rows, void* workspace,
-                     size_t workspace_bytes, int* err_flag, void* stream) {
-  KRS_REQUIRE(tables && feats && (ids || nnz == 0), "embed_bag_bwd_plan: null argument");
-  KRS_REQUIRE(n_feats > 0 && batch > 0 && nnz >= 0, "embed_bag_bwd_plan: bad sizes");
-  KRS_REQUIRE(total_rows > 0 && total_rows < 0xffffffffLL, "embed_bag_bwd_plan: total_rows must fit 32-bit keys");
-  KRS_REQUIRE(nnz < 0x7fffffffLL && (int64_t)n_feats * batch < 0xffffffffLL,
-              "embed_bag_bwd_plan: nnz must stay below 2^31 and the bag count below 2^32");
-  if (nnz == 0) return KRS_OK;
-  KRS_REQUIRE(workspace, "embed_bag_bwd_plan: null workspace");
-  const PlanLayout l = plan_layout(workspace, nnz, true);
-  if (workspace_bytes < l.total_bytes)
-    return fail(KRS_ERR_WORKSPACE, "embed_bag_bwd_plan: workspace %zu < %zu bytes", workspace_bytes, l.total_bytes);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int n_tiles = (int)ceil_div(nnz, rs::kTile);
-  char* tp = reinterpret_cast<char*>(l.temp);
-  int32_t* counts = reinterpret_cast<int32_t*>(tp);
-  tp += align_up((size_t)rs::kMaxBins * (n_tiles + rs::kMaxProb) * sizeof(int32_t), 256);
-  int32_t* sums = reinterpret_cast<int32_t*>(tp);
-  tp += align_up(scan::workspace_bytes((int64_t)rs::kMaxBins * (n_tiles + rs::kMaxProb)), 256);
-  int32_t* sums2 = reinterpret_cast<int32_t*>(tp);
-  const bool by_table = offsets == nullptr && g_plan_variant == 0 &&
-                        plan_sort_by_table(l, tables, tables_host, n_tables, feats, feats_host, n_feats, ids, id_type,
-                                           batch, nnz, err_flag, st);
-  if (!by_table) {
-  KeyParams kp;
-  kp.tables = tables; kp.feats = feats; kp.n_feats = n_feats; kp.ids = ids; kp.id64 = id_type == KRS_I64;
-  kp.offsets = offsets; kp.off64 = off_type == KRS_I64; kp.batch = batch; kp.keys = l.keys_in; kp.vals = l.vals_in;
-  kp.err_flag = err_flag;
-  // Sort only the significant key bits.  2^bits - 1 > every valid row id, so the invalid key (all ones) still
-  // sorts last.
-  unsigned bits = 1;
-  while (bits < 32 && (1ULL << bits) <= (uint64_t)total_rows) ++bits;
-  const int passes = rs::n_passes(bits);
-  // ping-pong between (keys_in, vals_in) and (keys_sorted, vals_sorted); the LAST pass must write the sorted pair
-  // dense bags: keys are generated inside the first pass (feature constants cached in LDS)
-  const bool gen = offsets == nullptr && n_feats <= rs::kGenFeats;
-  bool to_sorted = (passes % 2) == 1;    // where the first pass writes
-  if (!gen) {
-    // CSR bags (or very many features): the key kernel walks the bags
-    kp.keys = to_sorted ? l.keys_in : l.keys_sorted;
-    kp.vals = to_sorted ? l.vals_in : l.vals_sorted;
-    const int64_t n_bags = (int64_t)n_feats * batch;
-    // lookup positions outside every bag (offsets[n_bags] < nnz: the padded tail of a static-capacity exchange)
-    // must not carry stale keys: all ones = the invalid key, which sorts behind every row and is skipped
-    KRS_HIP(hipMemsetAsync(kp.keys, 0xff, (size_t)nnz * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(bag_keys_kernel, dim3((unsigned)ceil_div(n_bags, 16)), dim3(256), 0, st, kp);
-    KRS_CHECK_LAUNCH("bag_keys_kernel");
-  }
-  unsigned done = 0;
-  for (int ps = 0; ps < passes; ++ps) {
-    rs::Pass p;
-    p.bits = (int)((bits - done + (passes - ps) - 1) / (passes - ps));
-    p.shift = (int)done;
-    p.nnz = nnz;
-    p.n_tiles = n_tiles;
-    p.counts = counts;
-    const bool generating = gen && ps == 0;
-    p.keys_in = generating ? nullptr : (to_sorted ? l.keys_in : l.keys_sorted);
-    p.vals_in = generating ? nullptr : (to_sorted ? l.vals_in : l.vals_sorted);
-    p.keys_out = to_sorted ? l.keys_sorted : l.keys_in;
-    p.vals_out = to_sorted ? l.vals_sorted : l.vals_in;
-    p.gen.tables = tables; p.gen.feats = feats; p.gen.n_feats = n_feats; p.gen.ids = ids;
-    p.gen.id64 = id_type == KRS_I64; p.gen.batch = batch; p.gen.err_flag = err_flag;
-    if (generating) hipLaunchKernelGGL(rs::hist_kernel<true>, dim3(n_tiles), dim3(rs::kHistThreads), 0, st, p);
-    else hipLaunchKernelGGL(rs::hist_kernel<false>, dim3(n_tiles), dim3(rs::kHistThreads), 0, st, p);
-    scan::exclusive(counts, counts, (int64_t)(1 << p.bits) * n_tiles, sums, nullptr, st);
-    if (generating) hipLaunchKernelGGL(rs::scatter_kernel<true>, dim3(n_tiles), dim3(rs::kThreads), 0, st, p);
-    else hipLaunchKernelGGL(rs::scatter_kernel<false>, dim3(n_tiles), dim3(rs::kThreads), 0, st, p);
-    done += (unsigned)p.bits;
-    to_sorted = !to_sorted;
-  }
-  }
-  KRS_CHECK_LAUNCH("embed_bag_bwd_plan: radix sort");
-  // segment list: heads per block -> one-workgroup scan of the block counts -> head positions
-  const unsigned nb = (unsigned)ceil_div(nnz, 256);
-  const unsigned nsb = (unsigned)ceil_div(nnz, kSegTile);
-  hipLaunchKernelGGL(seg_count_kernel, dim3(nsb), dim3(256), 0, st, l.keys_sorted, nnz, sums2);
-  hipLaunchKernelGGL(scan::block_kernel, dim3(1), dim3(1024), 0, st, sums2, (int64_t)nsb, (int64_t*)nullptr);
-  hipLaunchKernelGGL(seg_emit_kernel, dim3(nsb), dim3(256), 0, st, l.keys_sorted, nnz, sums2, l.seg_start, l.n_seg);
-  KRS_CHECK_LAUNCH("seg_emit_kernel");
-  // segments too long for one lane group (at most nnz / kLongSeg of them)
-  KRS_HIP(hipMemsetAsync(l.n_long, 0, 3 * sizeof(uint32_t), st));
-  KRS_HIP(hipMemsetAsync(l.sort_mode, by_table ? 1 : 0, sizeof(uint32_t), st));
-  hipLaunchKernelGGL(long_list_kernel, dim3(nb), dim3(256), 0, st, l.seg_start, l.n_seg, nnz, l.n_long, l.long_list,
-                     l.multi_list);
-  KRS_CHECK_LAUNCH("long_list_kernel");
-  return KRS_OK;
-}
-
-#if KRS_BWD_HAS(0)
-extern "C" int krs_embed_bag_bwd_plan(const krs_table* tables, const krs_feature* feats, int n_feats,
-                                      const void* ids, int id_type, const void* offsets, int off_type,
-                                      int batch, int64_t nnz, int64_t total_rows, void* workspace,
-                                      size_t workspace_bytes, int* err_flag, void* stream) {
-  return plan_impl(tables, nullptr, 0, feats, nullptr, n_feats, ids, id_type, offsets, off_type, batch, nnz, total_rows,
-                   workspace, workspace_bytes, err_flag, stream);
-}
-#endif
-
-#if KRS_BWD_HAS(0)
-extern "C" int krs_embed_bag_bwd_plan_tables(const krs_table* tables, const krs_table* tables_host, int n_tables,
-                                             const krs_feature* feats, const krs_feature* feats_host, int n_feats,
-                                             const void* ids, int id_type, int batch, int64_t nnz, int64_t total_rows,
-                                             void* workspace, size_t workspace_bytes, int* err_flag, void* stream) {
-  KRS_REQUIRE(tables_host && feats_host && n_tables > 0, "embed_bag_bwd_plan_tables: null host descriptors");
-  return plan_impl(tables, tables_host, n_tables, feats, feats_host, n_feats, ids, id_type, nullptr, KRS_I32, batch, nnz,
-                   total_rows, workspace, workspace_bytes, err_flag, stream);
-}
-#endif
-
-#if KRS_BWD_HAS(0)
 extern "C" int krs_embed_bag_bwd_dense(const krs_table* grad_tables, int n_tables, const krs_feature* feats,
                                        int n_feats, const float* weights, const float* bag_scale,
                                        const void* grad, int grad_dtype, int64_t grad_ld, int batch, int dim,
                                        int64_t nnz, const void* workspace, void* stream) {
-  if (int rc = check_apply_args(grad_tables, 1, feats, grad, grad_dtype, batch, dim, nnz, workspace)) return rc;
-  ApplyParams p = make_apply(grad_tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_ld, batch, dim, nnz, workspace);
-  return run_apply<kDense>(p, grad_dtype, KRS_F32, reinterpret_cast<hipStream_t>(stream));
+  return apply_tables<kDense>(grad_tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_dtype, grad_ld, batch,
+                              dim, KRS_F32, nnz, workspace, stream);
 }
-#endif
 
-#if KRS_BWD_HAS(0)
 extern "C" int krs_embed_bag_bwd_fused_sgd(const krs_table* tables, int n_tables, const krs_feature* feats,
                                            int n_feats, const float* weights, const float* bag_scale,
                                            const void* grad, int grad_dtype, int64_t grad_ld, int batch, int dim,
                                            int table_dtype, int64_t nnz, const void* workspace, void* stream) {
-  if (int rc = check_apply_args(tables, 1, feats, grad, grad_dtype, batch, dim, nnz, workspace)) return rc;
-  ApplyParams p = make_apply(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_ld, batch, dim, nnz, workspace);
-  return run_apply<kSgd>(p, grad_dtype, table_dtype, reinterpret_cast<hipStream_t>(stream));
+  return apply_tables<kSgd>(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_dtype, grad_ld, batch, dim,
+                            table_dtype, nnz, workspace, stream);
 }
 #endif
 
@@ -1822,21 +922,17 @@ extern "C" int krs_embed_bag_bwd_fused_adagrad(const krs_table* tables, int n_ta
                                                const void* grad, int grad_dtype, int64_t grad_ld, int batch,
                                                int dim, int table_dtype, int64_t nnz, const void* workspace,
                                                void* stream) {
-  if (int rc = check_apply_args(tables, 1, feats, grad, grad_dtype, batch, dim, nnz, workspace)) return rc;
-  ApplyParams p = make_apply(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_ld, batch, dim, nnz, workspace);
-  return run_apply<kAdagrad>(p, grad_dtype, table_dtype, reinterpret_cast<hipStream_t>(stream));
+  return apply_tables<kAdagrad>(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_dtype, grad_ld, batch,
+                                dim, table_dtype, nnz, workspace, stream);
 }
-#endif
 
-#if KRS_BWD_HAS(1)
 extern "C" int krs_embed_bag_bwd_fused_adagrad_rowwise(const krs_table* tables, int n_tables,
                                                        const krs_feature* feats, int n_feats, const float* weights,
                                                        const float* bag_scale, const void* grad, int grad_dtype,
                                                        int64_t grad_ld, int batch, int dim, int table_dtype,
                                                        int64_t nnz, const void* workspace, void* stream) {
-  if (int rc = check_apply_args(tables, 1, feats, grad, grad_dtype, batch, dim, nnz, workspace)) return rc;
-  ApplyParams p = make_apply(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_ld, batch, dim, nnz, workspace);
-  return run_apply<kAdagradRow>(p, grad_dtype, table_dtype, reinterpret_cast<hipStream_t>(stream));
+  return apply_tables<kAdagradRow>(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_dtype, grad_ld, batch,
+                                   dim, table_dtype, nnz, workspace, stream);
 }
 #endif
 
@@ -1847,26 +943,20 @@ extern "C" int krs_embed_bag_bwd_fused_adam(const krs_table* tables, int n_table
                                             int dim, int table_dtype, int64_t nnz, float beta_1, float beta_2,
                                             float epsilon, float bias_correction, const void* workspace,
                                             void* stream) {
-  if (int rc = check_apply_args(tables, 1, feats, grad, grad_dtype, batch, dim, nnz, workspace)) return rc;
-  ApplyParams p = make_apply(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_ld, batch, dim, nnz, workspace);
-  p.hyper = Hyper{beta_1, beta_2, epsilon, bias_correction};
-  return run_apply<kAdam>(p, grad_dtype, table_dtype, reinterpret_cast<hipStream_t>(stream));
+  return apply_tables<kAdam>(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_dtype, grad_ld, batch, dim,
+                             table_dtype, nnz, workspace, stream, Hyper{beta_1, beta_2, epsilon, bias_correction});
 }
-#endif
 
-#if KRS_BWD_HAS(2)
 extern "C" int krs_embed_bag_bwd_fused_adam_dyn(const krs_table* tables, int n_tables, const krs_feature* feats,
                                                 int n_feats, const float* weights, const float* bag_scale,
                                                 const void* grad, int grad_dtype, int64_t grad_ld, int batch,
                                                 int dim, int table_dtype, int64_t nnz, float beta_1, float beta_2,
                                                 float epsilon, const float* bias_correction_dev, const void* workspace,
                                                 void* stream) {
-  if (int rc = check_apply_args(tables, 1, feats, grad, grad_dtype, batch, dim, nnz, workspace)) return rc;
   KRS_REQUIRE(bias_correction_dev, "krs_embed_bag_bwd_fused_adam_dyn: null bias_correction_dev");
-  ApplyParams p = make_apply(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_ld, batch, dim, nnz, workspace);
-  p.hyper = Hyper{beta_1, beta_2, epsilon, 1.0f};
-  p.hyper_d_dev = bias_correction_dev;
-  return run_apply<kAdam>(p, grad_dtype, table_dtype, reinterpret_cast<hipStream_t>(stream));
+  return apply_tables<kAdam>(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_dtype, grad_ld, batch, dim,
+                             table_dtype, nnz, workspace, stream, Hyper{beta_1, beta_2, epsilon, 1.0f},
+                             bias_correction_dev);
 }
 #endif
 
@@ -1876,10 +966,8 @@ extern "C" int krs_embed_bag_bwd_fused_ftrl(const krs_table* tables, int n_table
                                             const void* grad, int grad_dtype, int64_t grad_ld, int batch,
                                             int dim, int table_dtype, int64_t nnz, float learning_rate_power,
                                             float l1, float l2, float beta, const void* workspace, void* stream) {
-  if (int rc = check_apply_args(tables, 1, feats, grad, grad_dtype, batch, dim, nnz, workspace)) return rc;
-  ApplyParams p = make_apply(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_ld, batch, dim, nnz, workspace);
-  p.hyper = Hyper{learning_rate_power, l1, l2, beta};
-  return run_apply<kFtrl>(p, grad_dtype, table_dtype, reinterpret_cast<hipStream_t>(stream));
+  return apply_tables<kFtrl>(tables, n_tables, feats, n_feats, weights, bag_scale, grad, grad_dtype, grad_ld, batch, dim,
+                             table_dtype, nnz, workspace, stream, Hyper{learning_rate_power, l1, l2, beta});
 }
 #endif
 

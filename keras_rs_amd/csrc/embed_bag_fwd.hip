@@ -638,7 +638,7 @@ int dispatch_lpr(const EmbedFwdParams& p, int row_pieces, bool one_hot, bool str
 }  // namespace
 }  // namespace krs
 
-namespace krs { extern int g_plan_variant; }   // embed_bag_bwd.hip
+namespace krs { extern int g_plan_variant; }   // embed_bag_plan.hip
 
 extern "C" int krs_embed_set_option(int key, int value) {
   if (key == KRS_EMBED_OPT_PLAN) {

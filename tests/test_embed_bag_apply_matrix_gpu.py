@@ -1,11 +1,11 @@
 """K2 apply stage, kernel by kernel and mode by mode, against float64.
 
-`run_apply` (keras_rs_amd/csrc/embed_bag_bwd.hip:1541-1563) sends a call to the vector kernels when the gradient
+`run_apply` (keras_rs_amd/csrc/embed_bag_bwd.hip:832-854) sends a call to the vector kernels when the gradient
 row is a whole number of 16-byte pieces of at most 1024 bytes, the dtype pair is not fp32 gradients into bf16
-tables in a fused mode, and there are at most 512 features and tables (:1548-1549); `launch_apply_lpr`
-(:1494-1538) then picks LPR = 8 / 16 / 32 / 64 lanes per row from the piece count (:1495) and HAS_W x HAS_SCALE
-from the call (:1501-1503), and adds bag_apply_long_kernel for segments longer than 128 lookups (:1512) and
-bag_apply_finish_kernel for segments longer than 2048 (:1527).  Everything else runs bag_apply_generic (:1555-1560).
+tables in a fused mode, and there are at most 512 features and tables (:839-840); `launch_apply_lpr`
+(:785-829) then picks LPR = 8 / 16 / 32 / 64 lanes per row from the piece count (:786) and HAS_W x HAS_SCALE
+from the call (:792-794), and adds bag_apply_long_kernel for segments longer than 128 lookups (:803) and
+bag_apply_finish_kernel for segments longer than 2048 (:818).  Everything else runs bag_apply_generic (:846-851).
 Every case below runs all seven modes: dense, compact, SGD, Adagrad, Adam, FTRL (three learning-rate powers),
 row-wise Adagrad.  `test_the_cases_cover_the_apply_matrix` checks the table against the dispatch rule.
 

@@ -410,7 +410,9 @@ def test_table_segmented_plan_equals_global_plan(vocabs, dim, with_bad):
     """krs_embed_bag_bwd_plan_tables (per-table sort on the id, 8-byte intermediate pairs, final pass rebuilds the
     64-bit values) against the global sort (KRS_EMBED_OPT_PLAN = 1): the fused Adagrad update and the dense gradient
     they lead to must be bit-identical -- problems that end in partial tiles, two features on one table (neighbours),
-    1 / 2 / 3 passes, out-of-range ids (which end their table's run instead of the array)."""
+    1 / 2 / 3 passes, out-of-range ids (which end their table's run instead of the array).  Third leg: the same bags
+    given as CSR offsets (krs_embed_bag_bwd_plan: keys written by the key kernel, no generating pass, the pairs
+    ping-pong between the two buffer pairs in both parities over 1 / 2 / 3 passes of 3 to 4 tiles) -- bit-identical too."""
 
     from keras_rs_amd import _lib as L
     from keras_rs_amd.embedding_ops import FusedBags
@@ -428,27 +430,37 @@ def test_table_segmented_plan_equals_global_plan(vocabs, dim, with_bad):
     cols = len(tix) * dim
     grad = torch.from_numpy(rng.uniform(-1, 1, (batch, cols)).astype(np.float32)).to(dev)
     w = torch.from_numpy(rng.uniform(0.1, 1, len(ids_np)).astype(np.float32)).to(dev)
+    # the same bags as CSR: offsets[bag] = first lookup of the bag, bags feature-major as the ids are
+    offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(np.repeat(hots, batch))]).astype(np.int32)).to(dev)
+    assert offsets.numel() == len(tix) * batch + 1 and int(offsets[-1]) == len(ids_np)
     res = []
     try:
-        for variant in (0, 1):
-            L.check(L.lib().krs_embed_set_option(2, variant), "krs_embed_set_option")
+        for leg in ("segmented", "global", "csr"):
+            L.check(L.lib().krs_embed_set_option(2, 1 if leg == "global" else 0), "krs_embed_set_option")
             g = np.random.default_rng(9)
             tables = [torch.from_numpy(g.uniform(-1, 1, (v, dim)).astype(np.float32)).to(dev) for v in vocabs]
             slots = [torch.full((v, dim), 0.1, device=dev) for v in vocabs]
             fb = FusedBags(tables, [(tix[f], "sum", f * dim) for f in range(len(tix))], slots=slots,
                            lrs=[0.01 * (t + 1) for t in range(len(vocabs))])
             err = torch.zeros(1, dtype=torch.int32, device=dev)
-            ws = fb.plan_backward(ids, batch, hots=hots, err_flag=err, global_order=False)
+            if leg == "csr":
+                # keys from bag_keys_kernel, every pass of the global sort reads (keys, values) from memory
+                ws = fb.plan_backward(ids, batch, offsets=offsets, err_flag=err)
+                form = {}
+            else:
+                ws = fb.plan_backward(ids, batch, hots=hots, err_flag=err, global_order=False)
+                form = {"hots": hots}
             assert bool(int(err.item()) & 1) == with_bad
-            dense = fb.backward_dense(ws, grad, batch, ids.numel(), hots=hots, weights=w)
-            fb.backward_fused("adagrad", ws, grad, batch, ids.numel(), hots=hots, weights=w)
+            dense = fb.backward_dense(ws, grad, batch, ids.numel(), weights=w, **form)
+            fb.backward_fused("adagrad", ws, grad, batch, ids.numel(), weights=w, **form)
             torch.cuda.synchronize()
             res.append((tables, slots, dense))
     finally:
         L.lib().krs_embed_set_option(2, 0)
-    for part in range(3):
-        for a, b in zip(res[0][part], res[1][part]):
-            assert torch.equal(a, b)
+    for other in res[1:]:
+        for part in range(3):
+            for a, b in zip(res[0][part], other[part]):
+                assert torch.equal(a, b)
     assert not torch.equal(res[0][0][0], torch.from_numpy(np.random.default_rng(9).uniform(-1, 1, (vocabs[0], dim)).astype(np.float32)).to(dev))
 
 

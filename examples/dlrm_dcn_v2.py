@@ -1,14 +1,14 @@
 """DLRM-DCN-v2 from the MI355X layers: the model of the reference's ml_perf example
 (examples/ml_perf/model.py:30-262, 296-345) with `keras_rs` / `keras.layers` swapped for
 `keras_rs_amd.layers` -- bottom MLP -> DistributedEmbedding -> concat -> FeatureCross stack -> top MLP
-(sigmoid) -> binary cross-entropy (examples/ml_perf/main.py:201-210).
+(sigmoid) -> binary cross-entropy, BinaryAccuracy and AUC (examples/ml_perf/main.py:201-210).
 
     python examples/dlrm_dcn_v2.py            # a few training steps on synthetic data (needs an MI355X)
 
 The only edits against the reference model code: `layers.concat_features` instead of
 `ops.concatenate` (the embeddings land directly in the interaction input, no copy) with
-`slab_lead_cols` reserving the bottom-MLP slot, `kl.binary_crossentropy` for keras.losses.BinaryCrossentropy() and
-`keras_rs_amd.optim.Adagrad` for the dense optimizer.
+`slab_lead_cols` reserving the bottom-MLP slot, `kl.binary_crossentropy` for keras.losses.BinaryCrossentropy(),
+`kl.BinaryAccuracy` / `kl.AUC` for the two keras.metrics and `keras_rs_amd.optim.Adagrad` for the dense optimizer.
 """
 
 from __future__ import annotations
@@ -119,10 +119,13 @@ def build_model(batch, vocab, hots, embedding_dim=128, projection=512, cross_lay
                      embedding_dtype=embedding_dtype, small_emb_features=small or None)
 
 
-def train_step(model, opt_box, inputs, labels):
-    """One step: forward, BCE, backward (table optimizers run inside it), dense optimizer step."""
+def train_step(model, opt_box, inputs, labels, metrics=None):
+    """One step: forward, BCE, backward (table optimizers run inside it), dense optimizer step.  `metrics` (a
+    kl.BinaryMetricGroup, or any object with keras' update_state) is updated with the step's predictions."""
     pred = model(inputs)
     loss = kl.binary_crossentropy(labels, pred)     # main.py:201-210, forward + backward in one pass (krs_bce_fwd_bwd)
+    if metrics is not None:
+        metrics.update_state(labels, pred.detach())  # main.py:201-210: one krs_binary_metrics call, no host wait
     loss.backward()
     if opt_box[0] is None:  # the first step has built the layers
         dense_params = [p for p in model.parameters() if p.requires_grad]
@@ -139,6 +142,8 @@ if __name__ == "__main__":
     hots = [3, 2, 1, 2, 6, 1, 1, 1, 1, 7, 3, 8, 1, 6, 9, 5, 1, 1, 1, 12, 100, 27, 10, 3, 1, 1]
     model = build_model(8192, 100_000, hots)
     box = [None]
+    metrics = kl.BinaryMetricGroup([kl.BinaryAccuracy(), kl.AUC()])
     for step in range(5):
         x, y = synthetic_batch(8192, 13, 100_000, hots, dev, seed=step)
-        print(f"step {step}: loss {float(train_step(model, box, x, y)):.4f}")
+        print(f"step {step}: loss {float(train_step(model, box, x, y, metrics)):.4f}")
+    print(", ".join(f"{name} {float(value):.4f}" for name, value in metrics.result().items()))

@@ -773,6 +773,46 @@ int krs_ranking_metrics_accumulate(const float* values, const float* sums, const
                                    int64_t batch, float* const* states, float* out_values, float* out_weights,
                                    int64_t* draw, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * K12  Binary metrics (keras.metrics.BinaryAccuracy and keras.metrics.AUC, the metrics the ml_perf step compiles):
+ *      one pass over the predictions, every requested state updated from it
+ *
+ * pred [n] fp32 / bf16 (computed on in fp32) and labels [n] fp32, contiguous.  Sample i weighs weights[i] (fp32), or
+ * the scalar `weight` when weights is NULL (pass 1 for an unweighted call).
+ *
+ * Accuracy (acc_state != NULL): acc_state is {total, count}, keras.metrics.Mean:
+ *     total += sum_i w_i (float(pred_i > acc_threshold) == label_i),   count += sum_i w_i
+ * (a label that is neither 0 nor 1 matches nothing).
+ *
+ * AUC spec j of n_aucs (host arrays of n_aucs entries each): auc_states[j] is [4, T] fp32 with T = auc_T[j], the
+ * rows true_positives, false_positives, true_negatives, false_negatives.  p = pred, or 1 / (1 + exp(-pred)) when
+ * auc_from_logits[j]; then p = min(max(p, 0), 1) with NaN -> 0.  A sample is positive iff label != 0:
+ * wpos = w positive, wneg = w (1 - positive).  Its bucket is
+ *     auc_thresholds[j] == NULL (T >= 3; the even set -1e-7, 1/(T-1), .., (T-2)/(T-1), 1+1e-7):
+ *         b = max((int)ceilf(p * (float)(T - 1)) - 1, 0)                              (fp32, exactly this)
+ *     auc_thresholds[j] = T ascending fp32 values on the device, end points included:
+ *         b = #{i : t_i < p} - 1                            (b < 0: the sample exceeds no threshold)
+ * and then  pos[b] += wpos, neg[b] += wneg;  tp[i] += sum_{b >= i} pos[b], fp[i] += sum_{b >= i} neg[b],
+ * fn[i] += sum pos - tp[i], tn[i] += sum neg - fp[i].
+ *
+ * Summation order (fixed; no float atomics; the same bits on any device, from call to call, and for a spec alone
+ * or beside others): samples are cut into chunks of KRS_BINARY_METRIC_CHUNK; within a chunk a bin adds its samples
+ * in index order.  Workgroup g of G = min(number of chunks, KRS_BINARY_METRIC_GROUPS) adds the chunks g, g + G,
+ * g + 2 G, .. in that order; the G partials are added in the order of g; the sums over b >= i are one scan of
+ * fixed shape.  workspace: krs_binary_metrics_workspace_bytes bytes on the device, which need not be initialised;
+ * too little is KRS_ERR_WORKSPACE.  n >= 0; 0 <= n_aucs <= KRS_BINARY_METRIC_MAX_AUCS and
+ * 2 <= T <= KRS_BINARY_METRIC_MAX_THRESHOLDS, otherwise KRS_ERR_INVALID.  No host synchronisation.
+ * ------------------------------------------------------------------------- */
+#define KRS_BINARY_METRIC_MAX_AUCS 4
+#define KRS_BINARY_METRIC_MAX_THRESHOLDS 2048
+#define KRS_BINARY_METRIC_CHUNK 1024
+#define KRS_BINARY_METRIC_GROUPS 256
+size_t krs_binary_metrics_workspace_bytes(int64_t n, int n_aucs, const int* auc_T);
+int krs_binary_metrics(const void* pred, int dtype, const float* labels, const float* weights, float weight,
+                       int64_t n, float acc_threshold, float* acc_state, int n_aucs,
+                       const float* const* auc_thresholds, const int* auc_T, const int* auc_from_logits,
+                       float* const* auc_states, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ from keras_rs_amd.layers.dot_interaction import DotInteraction
 from keras_rs_amd.layers.embed_reduce import EmbedReduce, Embedding, Ragged
 from keras_rs_amd.layers.feature_cross import FeatureCross
 from keras_rs_amd.layers.losses import BinaryCrossentropy, binary_crossentropy
+from keras_rs_amd.layers.metrics import AUC, BinaryAccuracy, BinaryMetricGroup, auc_from_confusion
 from keras_rs_amd.layers.retrieval import BruteForceRetrieval, HardNegativeMining, Retrieval
 
-__all__ = ["Adagrad", "Adam", "BinaryCrossentropy", "binary_crossentropy", "BruteForceRetrieval", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
+__all__ = ["AUC", "Adagrad", "Adam", "BinaryAccuracy", "BinaryCrossentropy", "BinaryMetricGroup", "auc_from_confusion", "binary_crossentropy", "BruteForceRetrieval", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
            "FeatureCross", "Ftrl", "HardNegativeMining", "Ragged", "Retrieval", "RowwiseAdagrad", "SGD", "TableConfig", "concat_features"]

@@ -1,6 +1,7 @@
-"""Host side of K10: thin torch wrappers over krs_ranking_metrics and krs_ranking_metrics_accumulate (include/krs.h).
+"""Host side of K10 and K12: thin torch wrappers over krs_ranking_metrics, krs_ranking_metrics_accumulate and
+krs_binary_metrics (include/krs.h).
 
-Both run on the current stream and never wait for the device, so a metric update can be captured in a HIP graph.
+All run on the current stream and never wait for the device, so a metric update can be captured in a HIP graph.
 """
 
 from __future__ import annotations
@@ -13,6 +14,9 @@ from keras_rs_amd import _lib as L
 
 MAX_LIST = 4096   # KRS_RANK_MAX_LIST
 MAX_SPECS = 8     # KRS_METRIC_MAX_SPECS
+MAX_AUCS = 4            # KRS_BINARY_METRIC_MAX_AUCS
+MAX_THRESHOLDS = 2048   # KRS_BINARY_METRIC_MAX_THRESHOLDS
+BINARY_CHUNK = 1024     # KRS_BINARY_METRIC_CHUNK
 METRIC_KINDS = {"dcg": 0, "ndcg": 1, "map": 2, "mrr": 3, "precision": 4, "recall": 5}   # krs_metric_kind
 
 
@@ -100,3 +104,48 @@ def ranking_metrics_accumulate(kinds, values: torch.Tensor, sums: torch.Tensor, 
                                                 L.stream_ptr())
     L.check(rc, "krs_ranking_metrics_accumulate")
     return out_v, out_w
+
+
+def binary_metrics(pred: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | float | None = None, *,
+                   accuracy=None, aucs=()) -> None:
+    """K12.  pred [n] fp32 / bf16 and labels [n] (any shapes of n elements); weights [n] or a Python number (every
+    sample's weight).  accuracy: None or (threshold, state) with state two fp32 device values {total, count}.  aucs:
+    up to 4 (thresholds, T, from_logits, state): thresholds None (the even set, T >= 3) or T ascending fp32 values
+    on the device, state [4, T] fp32 (tp, fp, tn, fn).  Every state is updated in place."""
+    what = "binary_metrics"
+    L.require_device(pred, what)
+    dev = pred.device
+    pred = pred.contiguous().reshape(-1)
+    n = pred.numel()
+    y = _full(labels.reshape(-1), "labels", (n,), dev, torch.float32, what)
+    w, w_scalar = None, 1.0
+    if isinstance(weights, (int, float)):
+        w_scalar = float(weights)
+    elif weights is not None:
+        w = _full(weights.reshape(-1), "weights", (n,), dev, torch.float32, what)
+    aucs = list(aucs)
+
+    def state_ok(s, numel):
+        return s.dtype == torch.float32 and s.numel() == numel and s.device == dev and s.is_contiguous()
+
+    acc_threshold, acc_state = 0.0, None
+    if accuracy is not None:
+        acc_threshold, acc_state = float(accuracy[0]), accuracy[1]
+        if not state_ok(acc_state, 2):
+            raise L.KrsError(f"{what}: the accuracy state must be two contiguous fp32 values on {dev}")
+    for th, t, _, state in aucs:
+        if not state_ok(state, 4 * int(t)):
+            raise L.KrsError(f"{what}: an AUC state must be [4, {t}] contiguous fp32 on {dev}")
+        if th is not None and (th.dtype != torch.float32 or th.numel() != int(t) or th.device != dev
+                               or not th.is_contiguous()):
+            raise L.KrsError(f"{what}: thresholds must be {t} contiguous fp32 values on {dev}")
+    ts = _int_array([int(t) for _, t, _, _ in aucs])
+    logits = _int_array([int(bool(fl)) for _, _, fl, _ in aucs])
+    th_ptrs = (C.c_void_p * len(aucs))(*[L.ptr(th) for th, _, _, _ in aucs])
+    st_ptrs = (C.c_void_p * len(aucs))(*[s.data_ptr() for _, _, _, s in aucs])
+    ws_bytes = L.lib().krs_binary_metrics_workspace_bytes(n, len(aucs), ts)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    rc = L.lib().krs_binary_metrics(L.ptr(pred), L.fdtype(pred), L.ptr(y), L.ptr(w), w_scalar, n, acc_threshold,
+                                    L.ptr(acc_state), len(aucs), th_ptrs, ts, logits, st_ptrs, L.ptr(ws), ws_bytes,
+                                    L.stream_ptr())
+    L.check(rc, "krs_binary_metrics")

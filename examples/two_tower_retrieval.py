@@ -1,0 +1,66 @@
+"""Two-tower retrieval from the MI355X layers: the in-batch softmax loss of the reference's retrieval examples
+(examples/sequential_retrieval.py:344-360, examples/multi_task.py: scores = q c^T, labels = eye(batch),
+CategoricalCrossentropy(from_logits=True)) with the three optional logit stages of a retrieval task in their usual
+order, then serving with BruteForceRetrieval.
+
+    python examples/two_tower_retrieval.py            # a few training steps on synthetic ids (needs an MI355X)
+
+Stages of `retrieval_task_loss`: scores -> SamplingProbabilityCorrection -> RemoveAccidentalHits ->
+HardNegativeMining -> CategoricalCrossentropy.  The scores are one GEMM; everything after it is K11 / K8 kernels.
+"""
+
+from __future__ import annotations
+
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import keras_rs_amd.layers as kl  # noqa: E402
+
+
+def retrieval_task_loss(query_emb: torch.Tensor, cand_emb: torch.Tensor, cand_ids: torch.Tensor | None = None,
+                        cand_prob: torch.Tensor | None = None, num_hard_negatives: int | None = None,
+                        loss=None) -> torch.Tensor:
+    """The in-batch softmax loss of query_emb [B, D] against cand_emb [N, D] (N >= B; candidate i is the positive of
+    query i).  cand_prob [N]: the candidates' sampling probabilities (logits -= log p).  cand_ids [N]: candidates with
+    the positive's id are accidental hits.  num_hard_negatives: keep that many highest-scoring negatives per query."""
+    loss = loss if loss is not None else kl.CategoricalCrossentropy(from_logits=True)
+    scores = torch.matmul(query_emb, cand_emb.transpose(0, 1))
+    labels = torch.eye(scores.shape[0], scores.shape[1], dtype=torch.float32, device=scores.device)
+    if cand_prob is not None:
+        scores = kl.SamplingProbabilityCorrection()(scores, cand_prob)
+    if cand_ids is not None:
+        scores = kl.RemoveAccidentalHits()(scores, labels, cand_ids)
+    if num_hard_negatives is not None:
+        scores, labels = kl.HardNegativeMining(num_hard_negatives)(scores, labels)
+    return loss(labels, scores)
+
+
+def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000, dim: int = 32) -> None:
+    dev = torch.device("cuda", torch.cuda.current_device())
+    query_tower = kl.Embedding(users, dim, device=dev)
+    cand_tower = kl.Embedding(items, dim, device=dev)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    user_ids = torch.randint(0, users, (batch,), device=dev, generator=gen, dtype=torch.int32)
+    item_ids = torch.randint(0, items, (batch,), device=dev, generator=gen, dtype=torch.int32)
+    item_prob = torch.full((batch,), 1.0 / items, device=dev)        # uniform in-batch sampling
+    query_tower(user_ids), cand_tower(item_ids)                       # (builds the tables)
+    opt = torch.optim.SGD(query_tower.weights + cand_tower.weights, lr=0.5)
+    for step in range(steps):
+        opt.zero_grad()
+        value = retrieval_task_loss(query_tower(user_ids), cand_tower(item_ids), cand_ids=item_ids,
+                                    cand_prob=item_prob, num_hard_negatives=32)
+        value.backward()
+        opt.step()
+        print(f"step {step}: loss {float(value):.4f}")
+    all_items = torch.arange(items, device=dev, dtype=torch.int32)
+    retrieval = kl.BruteForceRetrieval(cand_tower(all_items).detach(), all_items, k=5, device=dev)
+    scores, top = retrieval(query_tower(user_ids[:4]).detach())
+    print("top-5 items of the first queries:", top.tolist())
+
+
+if __name__ == "__main__":
+    main()

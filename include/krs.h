@@ -774,6 +774,42 @@ int krs_ranking_metrics_accumulate(const float* values, const float* sums, const
                                    int64_t* draw, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * K11  Retrieval training head: row softmax cross-entropy with its gradient, and the two logit corrections
+ *
+ * In all three, logits [rows, cols] is fp32 / bf16 with row stride ld (>= cols) and is computed on in fp32; outputs in
+ * the logits' dtype have their own row stride.  rows >= 0 (0 is a successful no-op), 1 <= cols <= 2^30, otherwise
+ * KRS_ERR_INVALID.  Fixed summation orders and no atomics: bit-identical from call to call.  No host synchronisation,
+ * no workspace.
+ *
+ * krs_softmax_xent (keras.losses.CategoricalCrossentropy / SparseCategoricalCrossentropy with from_logits=True).
+ * Labels are either dense, labels [rows, cols] fp32 with row stride ld_labels, or sparse, label_index [rows] int32
+ * (y = one-hot of the index): exactly one of the two is non-NULL.  With y' = y (1 - label_smoothing) +
+ * label_smoothing / cols (0 <= label_smoothing < 1), m = max_j x_j, Z = sum_j exp(x_j - m), S = sum_j y'_j:
+ *     row_loss[r]   = sum_j y'_j ((m - x_j) + log Z)                 (fp32; labels are not renormalised)
+ *     dlogits[r, j] = g_r (S exp(x_j - m) / Z - y'_j),  g_r = g_scale * g[r]  (g [rows] fp32, NULL = g_scale)
+ * Either output may be NULL, not both.  A label_index outside [0, cols) is never used as an address: it makes that
+ * row's loss and gradient NaN.  Logits must be finite.  Rows of up to 9216 columns are read from memory once; longer
+ * rows twice.
+ *
+ * krs_sampling_correction (sampling_probability_correction.py:56-58): out = logits - log(min(max(p, epsilon), 1)).
+ * probs [p_rows, cols] fp32, contiguous; logits row r reads probs row r mod p_rows (p_rows = 1 broadcasts one row).
+ *
+ * krs_remove_accidental_hits (remove_accidental_hits.py:84-97), in fp32 with every operation rounded on its own:
+ *     pos = the first index of the row's largest label (0 for an all-zero row; -0 == +0, NaN above +inf)
+ *     out[r, j] = logits[r, j] + ((ids[j] == ids[pos] ? 1 : 0) - labels[r, j]) * value
+ * labels [rows, cols] fp32 with row stride ld_labels; ids [id_rows, cols] int32 / int64 (id_dtype: krs_itype),
+ * contiguous, logits row r reads ids row r mod id_rows.
+ * ------------------------------------------------------------------------- */
+int krs_softmax_xent(const void* logits, int64_t ld, int dtype, const float* labels, int64_t ld_labels,
+                     const int32_t* label_index, float label_smoothing, const float* g, float g_scale,
+                     int64_t rows, int64_t cols, float* row_loss, void* dlogits, int64_t ld_dlogits, void* stream);
+int krs_sampling_correction(const void* logits, int64_t ld, int dtype, const float* probs, int64_t p_rows,
+                            float epsilon, int64_t rows, int64_t cols, void* out, int64_t ld_out, void* stream);
+int krs_remove_accidental_hits(const void* logits, int64_t ld, int dtype, const float* labels, int64_t ld_labels,
+                               const void* ids, int id_dtype, int64_t id_rows, float value, int64_t rows,
+                               int64_t cols, void* out, int64_t ld_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * K12  Binary metrics (keras.metrics.BinaryAccuracy and keras.metrics.AUC, the metrics the ml_perf step compiles):
  *      one pass over the predictions, every requested state updated from it
  *

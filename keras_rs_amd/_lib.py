@@ -124,6 +124,9 @@ PROTOTYPES = {
                                  _I64, _P, _P, _P, _P]),
     "krs_ranking_metrics_accumulate_workspace_bytes": (_SZ, [_I64]),
     "krs_ranking_metrics_accumulate": (_I, [_P, _P, _P, _I, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
+    "krs_softmax_xent": (_I, [_P, _I64, _I, _P, _I64, _P, _F, _P, _F, _I64, _I64, _P, _P, _I64, _P]),
+    "krs_sampling_correction": (_I, [_P, _I64, _I, _P, _I64, _F, _I64, _I64, _P, _I64, _P]),
+    "krs_remove_accidental_hits": (_I, [_P, _I64, _I, _P, _I64, _P, _I, _I64, _F, _I64, _I64, _P, _I64, _P]),
     "krs_binary_metrics_workspace_bytes": (_SZ, [_I64, _I, _P]),
     "krs_binary_metrics": (_I, [_P, _I, _P, _P, _F, _I64, _F, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
 }

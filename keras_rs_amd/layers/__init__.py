@@ -7,9 +7,12 @@ from keras_rs_amd.layers.distributed_embedding_config import FeatureConfig, Tabl
 from keras_rs_amd.layers.dot_interaction import DotInteraction
 from keras_rs_amd.layers.embed_reduce import EmbedReduce, Embedding, Ragged
 from keras_rs_amd.layers.feature_cross import FeatureCross
-from keras_rs_amd.layers.losses import BinaryCrossentropy, binary_crossentropy
+from keras_rs_amd.layers.losses import (BinaryCrossentropy, CategoricalCrossentropy, SparseCategoricalCrossentropy,
+                                        binary_crossentropy)
 from keras_rs_amd.layers.metrics import AUC, BinaryAccuracy, BinaryMetricGroup, auc_from_confusion
-from keras_rs_amd.layers.retrieval import BruteForceRetrieval, HardNegativeMining, Retrieval
+from keras_rs_amd.layers.retrieval import (BruteForceRetrieval, HardNegativeMining, RemoveAccidentalHits, Retrieval,
+                                           SamplingProbabilityCorrection)
 
-__all__ = ["AUC", "Adagrad", "Adam", "BinaryAccuracy", "BinaryCrossentropy", "BinaryMetricGroup", "auc_from_confusion", "binary_crossentropy", "BruteForceRetrieval", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
-           "FeatureCross", "Ftrl", "HardNegativeMining", "Ragged", "Retrieval", "RowwiseAdagrad", "SGD", "TableConfig", "concat_features"]
+__all__ = ["AUC", "Adagrad", "Adam", "BinaryAccuracy", "BinaryCrossentropy", "BinaryMetricGroup", "auc_from_confusion", "binary_crossentropy", "BruteForceRetrieval", "CategoricalCrossentropy", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
+           "FeatureCross", "Ftrl", "HardNegativeMining", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SamplingProbabilityCorrection",
+           "SparseCategoricalCrossentropy", "TableConfig", "concat_features"]

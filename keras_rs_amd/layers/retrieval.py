@@ -1,6 +1,9 @@
 """Retrieval layers on MI355X: drop-ins for keras_rs.layers.BruteForceRetrieval
 (keras_rs/src/layers/retrieval/brute_force_retrieval.py) and keras_rs.layers.HardNegativeMining
-(hard_negative_mining.py), both on K8's exact top-k (include/krs.h: krs_retrieval_topk, krs_topk_rows).
+(hard_negative_mining.py), both on K8's exact top-k (include/krs.h: krs_retrieval_topk, krs_topk_rows), and for the two
+logit corrections of the training head, keras_rs.layers.SamplingProbabilityCorrection
+(sampling_probability_correction.py) and keras_rs.layers.RemoveAccidentalHits (remove_accidental_hits.py), on K11
+(krs_sampling_correction, krs_remove_accidental_hits).
 
 Selection order: score descending, then candidate index ascending (-0.0 as +0.0, NaN above +inf); rows come back
 sorted.  Known divergence: for bf16 inputs keras.ops.matmul rounds the scores to bf16 before top_k, so among
@@ -188,3 +191,66 @@ class HardNegativeMining(base.Layer):
         config = super().get_config()
         config.update({"num_hard_negatives": self._num_hard_negatives})
         return config
+
+
+def _check_logits_rank(logits: torch.Tensor) -> None:
+    if logits.dim() not in (1, 2, 3):
+        raise ValueError(f"`logits` must have rank 1 to 3, received shape {tuple(logits.shape)}")
+
+
+class SamplingProbabilityCorrection(base.Layer):
+    """logits - log(clip(candidate_sampling_probability, epsilon, 1)) (sampling_probability_correction.py:56-58).  The
+    probabilities have the logits' shape or that of its last axes (`[num_candidates]` against `[batch,
+    num_candidates]`): they are broadcast inside the kernel.  The gradient reaches the logits unchanged; the
+    probabilities get none."""
+
+    def __init__(self, epsilon: float = 1e-6, **kwargs: Any):
+        super().__init__(**kwargs)
+        self.epsilon = epsilon
+        self.built = True
+
+    def call(self, logits: torch.Tensor, candidate_sampling_probability: torch.Tensor) -> torch.Tensor:
+        _check_logits_rank(logits)
+        p = _as_tensor(candidate_sampling_probability, logits.device)
+        if p.dim() == 0:
+            p = p.expand(logits.shape[-1:])
+        if p.dim() > logits.dim() or tuple(p.shape) != tuple(logits.shape[logits.dim() - p.dim():]):
+            raise ValueError("`candidate_sampling_probability` should have the same shape as the last dimensions of "
+                             f"`logits`. Received: `candidate_sampling_probability.shape` = {tuple(p.shape)}, "
+                             f"`logits.shape` = {tuple(logits.shape)}.")
+        L.require_device(logits, "SamplingProbabilityCorrection logits")
+        L.require_device(p, "SamplingProbabilityCorrection candidate_sampling_probability")
+        return retrieval_ops.corrected(retrieval_ops.sampling_correction, logits, p.detach(), self.epsilon)
+
+    def get_config(self) -> dict:
+        config = super().get_config()
+        config.update({"epsilon": self.epsilon})
+        return config
+
+
+class RemoveAccidentalHits(base.Layer):
+    """logits + ((candidate_ids == the positive's id) - labels) * SMALLEST_FLOAT (remove_accidental_hits.py:84-97), the
+    positive of a row being the first argmax of its labels.  SMALLEST_FLOAT is the reference's 1.1754944e-40, a
+    positive subnormal: as in the reference, a logit changes only where it is itself of about that magnitude, and for
+    ordinary logits the layer is the identity.  The gradient reaches the logits unchanged."""
+
+    def __init__(self, **kwargs: Any):
+        super().__init__(**kwargs)
+        self.built = True
+
+    def call(self, logits: torch.Tensor, labels: torch.Tensor, candidate_ids: torch.Tensor) -> torch.Tensor:
+        labels = _as_tensor(labels, logits.device)
+        candidate_ids = _as_tensor(candidate_ids, logits.device)
+        labels_shape, logits_shape, ids_shape = tuple(labels.shape), tuple(logits.shape), tuple(candidate_ids.shape)
+        if labels_shape != logits_shape:
+            raise ValueError("`labels` and `logits` should have the same shape. Received: "
+                             f"`labels.shape` = {labels_shape}, `logits.shape` = {logits_shape}.")
+        if len(ids_shape) == 0 or labels_shape[-len(ids_shape):] != ids_shape:
+            raise ValueError("`candidate_ids` should have the same shape as the last dimensions of `labels`. "
+                             f"Received: `candidate_ids.shape` = {ids_shape}, `labels.shape` = {labels_shape}.")
+        _check_logits_rank(logits)
+        L.require_device(logits, "RemoveAccidentalHits logits")
+        L.require_device(labels, "RemoveAccidentalHits labels")
+        L.require_device(candidate_ids, "RemoveAccidentalHits candidate_ids")
+        return retrieval_ops.corrected(retrieval_ops.remove_accidental_hits, logits, labels.detach(),
+                                       candidate_ids.detach(), retrieval_ops.SMALLEST_FLOAT)

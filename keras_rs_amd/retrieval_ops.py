@@ -1,17 +1,23 @@
-"""Host side of K8: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (include/krs.h).
+"""Host side of K8 and K11: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and mining), and
+over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head), all of
+include/krs.h.
 
-Both run on the current stream, allocate their workspace from torch's caching allocator and never wait for the
-device, so a call can be captured into a HIP graph.
+All run on the current stream, allocate from torch's caching allocator and never wait for the device, so a call can
+be captured into a HIP graph.
 """
 
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from keras_rs_amd import _lib as L
 
 # HardNegativeMining's boost (hard_negative_mining.py: MAX_FLOAT = finfo(float32).max / 100)
 MAX_FLOAT = float(torch.finfo(torch.float32).max) / 100.0
+# RemoveAccidentalHits' constant (remove_accidental_hits.py: finfo(float32).smallest_normal / 100): 1.1754944e-40, a
+# positive fp32 subnormal
+SMALLEST_FLOAT = float(np.float32(np.finfo(np.float32).tiny) / np.float32(100.0))
 
 
 def _rowmajor(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -80,3 +86,157 @@ def retrieval_topk(query: torch.Tensor, candidates: torch.Tensor, k: int, *, ids
                                     L.stream_ptr())
     L.check(rc, "krs_retrieval_topk")
     return scores, out_ids
+
+
+# ---- K11: the training head ---------------------------------------------------------------------------------------
+def _rows2d(t: torch.Tensor, what: str):
+    """(a [rows, cols] view of t over its last axis whose rows are `ld` elements apart, ld): no copy where the last
+    axis is contiguous and the rows are evenly spaced, a contiguous copy otherwise."""
+    L.require_device(t, what)
+    if t.dim() == 0:
+        raise L.KrsError(f"{what}: expected at least one axis, got a scalar")
+    cols = t.shape[-1]
+    if t.dim() <= 2 and (cols == 1 or t.stride(-1) == 1) and (t.dim() == 1 or t.shape[0] <= 1 or t.stride(0) >= cols):
+        t2 = t.reshape(1, cols) if t.dim() == 1 else t
+        return t2, (t2.stride(0) if t2.shape[0] > 1 else cols)
+    return t.contiguous().view(-1, cols), cols
+
+
+def _float_logits(logits: torch.Tensor) -> torch.Tensor:
+    return logits if logits.dtype in (torch.float32, torch.bfloat16) else logits.to(torch.float32)
+
+
+def sampling_correction(logits: torch.Tensor, probs: torch.Tensor, epsilon: float = 1e-6) -> torch.Tensor:
+    """logits - log(clip(probs, epsilon, 1)) in the logits' dtype (fp32 / bf16, computed in fp32).  probs' shape is
+    the last probs.dim() axes of logits': it is broadcast over the leading ones inside the kernel."""
+    L.require_device(probs, "sampling_correction probs")
+    x, ld = _rows2d(_float_logits(logits), "sampling_correction logits")
+    rows, cols = x.shape
+    if probs.dim() > logits.dim() or tuple(probs.shape) != tuple(logits.shape[logits.dim() - probs.dim():]) \
+            or probs.dim() == 0:
+        raise L.KrsError(f"sampling_correction: probs shape {tuple(probs.shape)} is not the last axes of logits "
+                         f"{tuple(logits.shape)}")
+    p = probs.to(torch.float32).contiguous().view(-1, cols)
+    out = torch.empty((rows, cols), dtype=x.dtype, device=x.device)
+    rc = L.lib().krs_sampling_correction(L.ptr(x), ld, L.fdtype(x), L.ptr(p), max(1, p.shape[0]), float(epsilon),
+                                         rows, cols, L.ptr(out), cols, L.stream_ptr())
+    L.check(rc, "krs_sampling_correction")
+    return out.view(logits.shape)
+
+
+def remove_accidental_hits(logits: torch.Tensor, labels: torch.Tensor, ids: torch.Tensor,
+                           value: float = SMALLEST_FLOAT) -> torch.Tensor:
+    """logits + ((ids == ids[argmax(labels)]) - labels) * value, row by row in fp32 with each operation rounded on its
+    own, in the logits' dtype.  labels has logits' shape; ids' shape (int32 / int64) is its last ids.dim() axes."""
+    L.require_device(labels, "remove_accidental_hits labels")
+    L.require_device(ids, "remove_accidental_hits ids")
+    if tuple(labels.shape) != tuple(logits.shape):
+        raise L.KrsError(f"remove_accidental_hits: labels shape {tuple(labels.shape)} differs from logits "
+                         f"{tuple(logits.shape)}")
+    if ids.dim() == 0 or ids.dim() > logits.dim() or tuple(ids.shape) != tuple(logits.shape[logits.dim() - ids.dim():]):
+        raise L.KrsError(f"remove_accidental_hits: ids shape {tuple(ids.shape)} is not the last axes of logits "
+                         f"{tuple(logits.shape)}")
+    x, ld = _rows2d(_float_logits(logits), "remove_accidental_hits logits")
+    y, ldy = _rows2d(labels.to(torch.float32), "remove_accidental_hits labels")
+    rows, cols = x.shape
+    if ids.dtype not in (torch.int32, torch.int64):
+        ids = ids.to(torch.int64)
+    i2 = ids.contiguous().view(-1, cols)
+    out = torch.empty((rows, cols), dtype=x.dtype, device=x.device)
+    rc = L.lib().krs_remove_accidental_hits(L.ptr(x), ld, L.fdtype(x), L.ptr(y), ldy, L.ptr(i2), L.itype(i2),
+                                            max(1, i2.shape[0]), float(value), rows, cols, L.ptr(out), cols,
+                                            L.stream_ptr())
+    L.check(rc, "krs_remove_accidental_hits")
+    return out.view(logits.shape)
+
+
+def softmax_xent(logits: torch.Tensor, labels: torch.Tensor | None = None, label_index: torch.Tensor | None = None, *,
+                 label_smoothing: float = 0.0, g: torch.Tensor | None = None, g_scale: float = 1.0,
+                 want_loss: bool = True, want_grad: bool = True):
+    """Row softmax cross-entropy of logits [R, C] (fp32 / bf16) against dense labels [R, C] or label_index [R]
+    (exactly one of them): (fp32 loss [R] or None, d(sum_r g_r loss_r)/dlogits [R, C] in logits' dtype or None) with
+    g_r = g_scale * g[r] (g broadcast to [R]; None = g_scale)."""
+    if logits.dim() != 2:
+        raise L.KrsError(f"softmax_xent: expected [rows, cols] logits, got shape {tuple(logits.shape)}")
+    if (labels is None) == (label_index is None):
+        raise L.KrsError("softmax_xent: give exactly one of labels and label_index")
+    x, ld = _rows2d(logits, "softmax_xent logits")
+    rows, cols = x.shape
+    y, ldy, idx = None, 0, None
+    if labels is not None:
+        if tuple(labels.shape) != (rows, cols):
+            raise L.KrsError(f"softmax_xent: labels shape {tuple(labels.shape)} differs from logits {(rows, cols)}")
+        y, ldy = _rows2d(labels.to(torch.float32), "softmax_xent labels")
+    else:
+        L.require_device(label_index, "softmax_xent label_index")
+        if tuple(label_index.shape) != (rows,):
+            raise L.KrsError(f"softmax_xent: label_index shape {tuple(label_index.shape)} is not ({rows},)")
+        # (an index beyond int32 stays out of range after the clamp: it marks its row NaN like any other)
+        idx = label_index if label_index.dtype == torch.int32 else label_index.clamp(-1, 2**31 - 1).to(torch.int32)
+        idx = idx.contiguous()
+    gw = None if g is None else g.to(device=x.device, dtype=torch.float32).expand((rows,)).contiguous()
+    loss = torch.empty((rows,), dtype=torch.float32, device=x.device) if want_loss else None
+    dx = torch.empty((rows, cols), dtype=x.dtype, device=x.device) if want_grad else None
+    rc = L.lib().krs_softmax_xent(L.ptr(x), ld, L.fdtype(x), L.ptr(y), ldy, L.ptr(idx), float(label_smoothing),
+                                  L.ptr(gw), float(g_scale), rows, cols, L.ptr(loss), L.ptr(dx), cols, L.stream_ptr())
+    L.check(rc, "krs_softmax_xent")
+    return loss, dx
+
+
+class SoftmaxCrossentropyFn(torch.autograd.Function):
+    """Softmax cross-entropy of logits [R, C] with its Keras reduction, in ranking_ops.RankingLossFn's scheme: a scalar
+    reduction knows every row's share g = weight / divisor of the result before the launch and takes loss and gradient
+    from ONE launch, the backward only scales that gradient by the incoming scalar; reduction "none" computes the
+    losses alone and its backward runs a second launch with g = upstream * weight.  `weight` is None, a scalar tensor
+    or [R]; exactly one of `labels` [R, C] and `index` [R] is a tensor."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, index, weight, label_smoothing, reduction):
+        ctx.meta = (label_smoothing, reduction)
+        if reduction == "none":
+            v, _ = softmax_xent(logits, labels, index, label_smoothing=label_smoothing, want_grad=False)
+            ctx.save_for_backward(logits, labels, index, weight)
+            return v if weight is None else v * weight
+        rows = logits.shape[0]
+        g, scale = weight, 1.0
+        if reduction == "mean_with_sample_weight" and weight is not None:
+            div = weight.expand((rows,)).sum()
+            g = torch.where(div != 0, weight / div, torch.zeros_like(weight))   # divide_no_nan
+        elif reduction != "sum":
+            scale = 1.0 / rows if rows else 0.0
+        v, dx = softmax_xent(logits, labels, index, label_smoothing=label_smoothing, g=g, g_scale=scale,
+                             want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(dx)
+        return (v.sum() if g is None else (v * g).sum()) * scale
+
+    @staticmethod
+    def backward(ctx, up):
+        label_smoothing, reduction = ctx.meta
+        if reduction != "none":
+            (dx,) = ctx.saved_tensors
+            return (dx.float() * up).to(dx.dtype), None, None, None, None, None
+        logits, labels, index, weight = ctx.saved_tensors
+        g = up.to(torch.float32)
+        if weight is not None:
+            g = g * weight
+        _, dx = softmax_xent(logits, labels, index, label_smoothing=label_smoothing, g=g, want_loss=False)
+        return dx, None, None, None, None, None
+
+
+class _LogitCorrectionFn(torch.autograd.Function):
+    """A K11 logit correction: out = logits + (a term that does not depend on the logits), so the backward hands the
+    upstream gradient to the logits unchanged and nothing to the other operands."""
+
+    @staticmethod
+    def forward(ctx, logits, op, *operands):
+        ctx.in_dtype, ctx.n_operands = logits.dtype, len(operands)
+        return op(logits, *operands)
+
+    @staticmethod
+    def backward(ctx, up):
+        return (up.to(ctx.in_dtype), None) + (None,) * ctx.n_operands
+
+
+def corrected(op, logits: torch.Tensor, *operands):
+    """op(logits, *operands) (sampling_correction or remove_accidental_hits) with the identity gradient to logits."""
+    return _LogitCorrectionFn.apply(logits, op, *operands)

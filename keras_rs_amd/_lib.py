@@ -24,6 +24,7 @@ ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3
 FLAG_ID_OUT_OF_RANGE = 1
 FLAG_BAD_OFFSETS = 2
 FLAG_CAPACITY_OVERFLOW = 4
+MAX_LIST = 4096   # KRS_RANK_MAX_LIST
 
 # struct layouts of include/krs.h
 TABLE_DT = np.dtype(
@@ -168,6 +169,18 @@ def require_device(t: torch.Tensor, what: str) -> None:
             f"{what}: tensor is on {t.device}; keras_rs_amd runs on MI355X HIP kernels only "
             "(no CPU fallback)"
         )
+
+
+def rowmajor(t: torch.Tensor, what: str, expected: str = "a matrix") -> torch.Tensor:
+    """t itself when a kernel can walk it as rows with a leading dimension (read ld = t.stride(0), or the width when
+    there is one row at most), else a contiguous copy."""
+    require_device(t, what)
+    if t.dim() != 2:
+        raise KrsError(f"{what}: expected {expected}, got shape {tuple(t.shape)}")
+    # a row-broadcast view (strides (0, 1), e.g. the gradient of y.sum(0)) has no leading dimension a kernel can walk
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        return t.contiguous()
+    return t
 
 
 def ptr(t: torch.Tensor | None) -> int | None:

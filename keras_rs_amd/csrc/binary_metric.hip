@@ -87,9 +87,7 @@ __global__ __launch_bounds__(1024) void binary_hist_kernel(const P* __restrict__
       int bin = -1;
       float wp = 0.0f, wn = 0.0f, am = 0.0f, aw = 0.0f;
       if (i < m) {
-        float x;
-        if constexpr (sizeof(P) == 2) x = bf16_to_f32(pred[base + i]);
-        else x = pred[base + i];
+        const float x = load1(&pred[base + i]);
         const float y = labels[base + i];
         const float w = weights ? weights[base + i] : weight;
         if (T) {

@@ -56,6 +56,19 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
 }
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) { return (uint16_t)(pack_bf16x2(f, f) & 0xffffu); }
 
+// compile-time-dtype element access: T = float, or uint16_t for bf16
+template <typename T>
+__device__ __forceinline__ float load1(const T* p) {
+  if constexpr (sizeof(T) == 2) return bf16_to_f32(*p);
+  else return *p;
+}
+template <typename T>
+__device__ __forceinline__ void store1(T* p, float v) {
+  if constexpr (sizeof(T) == 2) *p = f32_to_bf16(v);
+  else *p = v;
+}
+__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7fc00000u); }
+
 // runtime-dtype element access (generic / fallback kernels only)
 __device__ __forceinline__ float ld_elem(const void* p, int dtype, int64_t i) {
   return dtype == KRS_BF16 ? bf16_to_f32(((const uint16_t*)p)[i]) : ((const float*)p)[i];
@@ -80,6 +93,13 @@ __device__ __forceinline__ uint32_t order_key(float f) {
 }
 
 __host__ __device__ __forceinline__ int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// the smallest power of two >= v (1 for v <= 1)
+template <typename I>
+__host__ __device__ __forceinline__ I pow2_at_least(I v) {
+  I p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
 
 }  // namespace krs
 #endif

@@ -13,28 +13,21 @@
 //                       Mean squared error (symmetric weight valid_k valid_j, k != j, no temperature):
 //                         l_k = sum_j w_kj d_kj^2,  d_kj = (y_k - y_j) - (s_k - s_j)
 //                         dl/ds_k = -2 sum_j w_kj d_kj (g_k + g_j)
-//   * listmle_kernel    sorts each list in LDS on the K8 pair key (label descending, index ascending; invalid items
+//   * listmle_kernel    sorts each list in LDS on pair_key (label descending, index ascending; invalid items
 //                       carry the label -1e9 as in the reference), then one reverse scan for the normalisers
 //                       E_r = sum_{q >= r} exp(z_q - m) and one forward scan for the closed-form gradient.
 //
-// Lists of up to kThreads items are packed several per workgroup (all lists of a launch share L, so every
-// workgroup runs one uniform schedule); longer lists take a workgroup each.  No atomics and fixed summation orders:
-// repeated calls are bit-identical.  No host synchronisation: a call can be captured into a HIP graph.
-#include "krs_common.h"
+// Packing, sort, reductions and scans are krs_list.h's.  No atomics and fixed summation orders: repeated calls are
+// bit-identical.  No host synchronisation: a call can be captured into a HIP graph.
+#include "krs_list.h"
 
 namespace krs {
 namespace {
 
-constexpr int kThreads = 1024;
+constexpr int kThreads = kListThreads;
 constexpr int kMaxList = KRS_RANK_MAX_LIST;
 constexpr float kListMleEps = 1e-10f;   // list_mle_loss.py: self._epsilon
 constexpr float kListMleMasked = -1e9f; // list_mle_loss.py: the label / logit of an invalid item
-
-__device__ __forceinline__ int pow2_at_least(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
 
 // ---- pairwise --------------------------------------------------------------------------------------------------------
 // phi and phi' of one weighted ordered pair, as autodiff differentiates the reference's expression (relu'(0) = 0,
@@ -67,6 +60,8 @@ __global__ __launch_bounds__(kThreads) void pairwise_kernel(const T* __restrict_
                                                             int64_t batch, int L, float* __restrict__ item_loss,
                                                             T* __restrict__ dlogits) {
   __shared__ float4 sm[kMaxList];   // {s, y' (NaN = invalid), g, unused}
+  // ListPack's tpl and lpb (the host launches by it), written out: taken from the struct, the same pair loop measured
+  // 1-2 % slower at (256, 2048).  Items are packed L, not P, apart: nothing is sorted here.
   const int tpl = L >= kThreads ? kThreads : pow2_at_least(L);   // threads per list
   const int lpb = kThreads / tpl;                                  // lists per workgroup
   const int64_t row0 = (int64_t)blockIdx.x * lpb;
@@ -76,13 +71,11 @@ __global__ __launch_bounds__(kThreads) void pairwise_kernel(const T* __restrict_
     const int64_t row = row0 + q;
     if (row >= batch) break;
     const int64_t o = row * L + k;
-    float s;
-    if constexpr (sizeof(T) == 2) s = bf16_to_f32(logits[row * ld + k]);
-    else s = logits[row * ld + k];
+    const float s = load1(&logits[row * ld + k]);
     const float y = labels[o];
     const bool valid = y >= 0.0f && (!mask || mask[o]);
     const float gv = valid ? (g ? g_scale * g[o] : g_scale) : 0.0f;
-    sm[i] = make_float4(s, valid ? y : __uint_as_float(0x7fc00000u), gv, 0.0f);
+    sm[i] = make_float4(s, valid ? y : quiet_nan(), gv, 0.0f);
   }
   __syncthreads();
   const int q = threadIdx.x / tpl, u = threadIdx.x - q * tpl;
@@ -122,33 +115,11 @@ __global__ __launch_bounds__(kThreads) void pairwise_kernel(const T* __restrict_
     }
     const int64_t o = row * L + k;
     if (item_loss) item_loss[o] = loss;
-    if (dlogits) {
-      if constexpr (sizeof(T) == 2) dlogits[o] = f32_to_bf16(grad);
-      else dlogits[o] = grad;
-    }
+    if (dlogits) store1(&dlogits[o], grad);
   }
 }
 
 // ---- ListMLE -----------------------------------------------------------------------------------------------------------
-// inclusive scan (reverse: suffix) of v over the tpl threads of each list; every thread of the workgroup calls it
-template <bool REVERSE, bool MAX>
-__device__ __forceinline__ float seg_scan(float* buf, float v, int u, int tpl) {
-  __syncthreads();   // (the previous scan's results have been read)
-  buf[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 1; o < tpl; o <<= 1) {
-    const bool has = REVERSE ? u + o < tpl : u >= o;
-    if (has) {
-      const float w = buf[REVERSE ? threadIdx.x + o : threadIdx.x - o];
-      v = MAX ? fmaxf(v, w) : v + w;
-    }
-    __syncthreads();
-    buf[threadIdx.x] = v;
-    __syncthreads();
-  }
-  return v;
-}
-
 constexpr int kEpt = kMaxList / kThreads;   // sorted positions per thread, at most
 
 template <typename T>
@@ -160,46 +131,28 @@ __global__ __launch_bounds__(kThreads) void listmle_kernel(const T* __restrict__
                                                            T* __restrict__ dlogits) {
   __shared__ uint64_t keys[kMaxList];
   __shared__ float z[kMaxList];     // s / T in item order
-  __shared__ float buf[kThreads];
-  const int P = pow2_at_least(L);
-  const int tpl = P >= kThreads ? kThreads : P;
-  const int ept = P / tpl;
-  const int lpb = kThreads / tpl;
-  const int64_t row0 = (int64_t)blockIdx.x * lpb;
-  const int n_slots = lpb * P;
+  __shared__ float buf[kThreads / kListWaves][kListWaves];   // scans use all of it, reductions its first rows
+  const ListPack lp(L);
+  const int P = lp.P, tpl = lp.tpl, ept = lp.ept;
+  const int64_t row0 = lp.row0();
+  const int n_slots = lp.n_slots();
   for (int i = threadIdx.x; i < n_slots; i += kThreads) {
     const int q = i / P, k = i - q * P;
     const int64_t row = row0 + q;
     uint64_t key = 0;                          // padding: below every real pair
     if (k < L && row < batch) {
       const int64_t o = row * L + k;
-      float s;
-      if constexpr (sizeof(T) == 2) s = bf16_to_f32(logits[row * ld + k]);
-      else s = logits[row * ld + k];
       const float y = labels[o];
       const bool valid = y >= 0.0f && (!mask || mask[o]);
-      key = ((uint64_t)order_key(valid ? y : kListMleMasked) << 32) | (uint32_t)~(uint32_t)k;
-      z[q * L + k] = s * inv_t;
+      key = pair_key(order_key(valid ? y : kListMleMasked), (uint32_t)k);
+      z[q * L + k] = load1(&logits[row * ld + k]) * inv_t;
     }
     keys[i] = key;
   }
   __syncthreads();
-  // bitonic sort of each P-long segment, descending
-  for (int kk = 2; kk <= P; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int p = threadIdx.x; p < n_slots / 2; p += kThreads) {
-        const int e = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-        const uint64_t a = keys[e], b = keys[e + j];
-        const bool desc = ((e & (P - 1)) & kk) == 0;
-        if (desc ? a < b : a > b) {
-          keys[e] = b;
-          keys[e + j] = a;
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort(keys, n_slots, P, 0);
 
-  const int q = threadIdx.x / tpl, u = threadIdx.x - q * tpl;
+  const int q = lp.q(), u = lp.u();
   const int64_t row = row0 + q;
   const bool live = row < batch;
   const uint64_t* lk = keys + q * P + u * ept;   // this thread's sorted positions u*ept .. u*ept + ept - 1
@@ -207,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void listmle_kernel(const T* __restrict__
   // valid: a label >= 0 has the top bit of its order key set; -1e9 (invalid) and padding do not
   bool valid[kEpt];
   float zr[kEpt];
-  float zmax = -__builtin_inff(), nvalid = 0.0f;
+  float top2[2] = {-__builtin_inff(), 0.0f};   // {max z, number of valid items}
 #pragma unroll
   for (int c = 0; c < kEpt; ++c) {
     valid[c] = false;
@@ -216,56 +169,53 @@ __global__ __launch_bounds__(kThreads) void listmle_kernel(const T* __restrict__
       const uint64_t key = lk[c];
       valid[c] = (key >> 63) != 0;
       if (valid[c]) {
-        zr[c] = lz[~(uint32_t)key];
-        zmax = fmaxf(zmax, zr[c]);
-        nvalid += 1.0f;
+        zr[c] = lz[pair_index(key)];
+        top2[0] = fmaxf(top2[0], zr[c]);
+        top2[1] += 1.0f;
       }
     }
   }
-  const int last = threadIdx.x - u + tpl - 1;    // the thread holding a list's inclusive total
-  seg_scan<false, true>(buf, zmax, u, tpl);
-  const float m_raw = buf[last];
-  seg_scan<false, false>(buf, nvalid, u, tpl);
-  const bool any_valid = buf[last] > 0.0f;
+  seg_all_reduce<2>(buf, top2, 1u, tpl);
+  const float m_raw = top2[0];
+  const bool any_valid = top2[1] > 0.0f;
   const float m = any_valid ? m_raw : 0.0f;
   // ties of the maximum share its gradient (autodiff of max)
-  float ties = 0.0f, ez[kEpt];
+  float ties[1] = {0.0f}, ez[kEpt];
   bool top[kEpt];
 #pragma unroll
   for (int c = 0; c < kEpt; ++c) {
     top[c] = valid[c] && zr[c] == m_raw;
-    ties += top[c] ? 1.0f : 0.0f;
+    ties[0] += top[c] ? 1.0f : 0.0f;
     zr[c] = zr[c] - m;                          // sorted_logits - raw_max
     ez[c] = valid[c] ? expf(zr[c]) : 0.0f;
   }
-  seg_scan<false, false>(buf, ties, u, tpl);
-  const float n_ties = buf[last];
+  seg_all_reduce<1>(buf, ties, 0u, tpl);
+  const float n_ties = ties[0];
   // E_r: suffix sums of exp, fixed order (within a thread from its last position down, then across threads)
   float tsum = 0.0f;
 #pragma unroll
   for (int c = kEpt - 1; c >= 0; --c) tsum += ez[c];
-  seg_scan<true, false>(buf, tsum, u, tpl);
-  float acc = u + 1 < tpl ? buf[threadIdx.x + 1] : 0.0f;
-  float inv[kEpt], lsum = 0.0f, esum = 0.0f, isum = 0.0f;
+  float* sbuf = &buf[0][0];
+  seg_scan<true, false>(sbuf, tsum, u, tpl);
+  float acc = u + 1 < tpl ? sbuf[threadIdx.x + 1] : 0.0f;
+  float inv[kEpt], tot[2] = {0.0f, 0.0f}, isum = 0.0f;   // tot: {loss, dl/dm = sum_r eps / (E_r + eps)}
 #pragma unroll
   for (int c = kEpt - 1; c >= 0; --c) {
     acc += ez[c];
     const float den = acc + kListMleEps;
     inv[c] = valid[c] ? 1.0f / den : 0.0f;
     if (valid[c]) {
-      lsum += logf(den) - zr[c];
-      esum += kListMleEps * inv[c];
+      tot[0] += logf(den) - zr[c];
+      tot[1] += kListMleEps * inv[c];
     }
   }
   // prefix sums of 1 / (E_r + eps)
 #pragma unroll
   for (int c = 0; c < kEpt; ++c) isum += inv[c];
-  seg_scan<false, false>(buf, isum, u, tpl);
-  float pre = u > 0 ? buf[threadIdx.x - 1] : 0.0f;
-  seg_scan<false, false>(buf, lsum, u, tpl);
-  const float loss = buf[last];
-  seg_scan<false, false>(buf, esum, u, tpl);
-  const float dmax = buf[last];   // dl/dm = sum_r eps / (E_r + eps)
+  seg_scan<false, false>(sbuf, isum, u, tpl);
+  float pre = u > 0 ? sbuf[threadIdx.x - 1] : 0.0f;
+  seg_all_reduce<2>(buf, tot, 0u, tpl);   // (its leading barrier follows the read of sbuf)
+  const float loss = tot[0], dmax = tot[1];
   if (!live) return;
   const float gl = any_valid ? (g ? g_scale * g[row] : g_scale) * inv_t : 0.0f;
   if (u == 0 && list_loss) list_loss[row] = any_valid ? loss : 0.0f;
@@ -281,9 +231,7 @@ __global__ __launch_bounds__(kThreads) void listmle_kernel(const T* __restrict__
       d = ez[c] * pre - 1.0f;
       if (top[c]) d += dmax / n_ties;
     }
-    const int64_t o = row * L + ~(uint32_t)key;
-    if constexpr (sizeof(T) == 2) dlogits[o] = f32_to_bf16(gl * d);
-    else dlogits[o] = gl * d;
+    store1(&dlogits[row * L + pair_index(key)], gl * d);
   }
 }
 
@@ -307,11 +255,8 @@ void launch_pairwise(int kind, dim3 grid, hipStream_t st, const void* logits, in
 
 int check_common(const char* what, const void* logits, int64_t ld, int dtype, const float* labels, float inv_t,
                  int64_t batch, int64_t list, const void* loss, const void* dlogits) {
-  KRS_REQUIRE(list >= 1 && list <= kMaxList, "%s: list length %lld outside the supported 1..%d (KRS_RANK_MAX_LIST)",
-              what, (long long)list, kMaxList);
-  KRS_REQUIRE(batch >= 0, "%s: negative batch", what);
-  KRS_REQUIRE(ld >= list, "%s: ld %lld below the list length %lld", what, (long long)ld, (long long)list);
-  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "%s: bad dtype", what);
+  const int rc = check_lists(what, ld, dtype, batch, list);
+  if (rc != KRS_OK) return rc;
   KRS_REQUIRE(inv_t > 0.0f, "%s: inverse temperature must be positive", what);
   KRS_REQUIRE(loss || dlogits, "%s: neither the loss nor the gradient is wanted", what);
   KRS_REQUIRE(batch == 0 || (logits && labels), "%s: null argument", what);
@@ -331,10 +276,7 @@ extern "C" int krs_pairwise_loss(int kind, const void* logits, int64_t ld, int d
   KRS_REQUIRE(kind >= KRS_RANK_HINGE && kind <= KRS_RANK_MSE, "krs_pairwise_loss: bad loss kind %d", kind);
   if (batch == 0) return KRS_OK;
   const int L = (int)list;
-  int tpl = 1;
-  while (tpl < L && tpl < kThreads) tpl <<= 1;
-  const int lpb = kThreads / tpl;
-  const dim3 grid((unsigned)ceil_div(batch, lpb));
+  const dim3 grid = ListPack(L).grid(batch);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (dtype == KRS_BF16)
     launch_pairwise<uint16_t>(kind, grid, st, logits, ld, labels, mask, g, g_scale, inv_temperature, batch, L,
@@ -355,10 +297,7 @@ extern "C" int krs_listmle_loss(const void* logits, int64_t ld, int dtype, const
   if (rc != KRS_OK) return rc;
   if (batch == 0) return KRS_OK;
   const int L = (int)list;
-  int P = 1;
-  while (P < L) P <<= 1;
-  const int lpb = P >= kThreads ? 1 : kThreads / P;
-  const dim3 grid((unsigned)ceil_div(batch, lpb));
+  const dim3 grid = ListPack(L).grid(batch);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (dtype == KRS_BF16)
     hipLaunchKernelGGL(listmle_kernel<uint16_t>, grid, dim3(kThreads), 0, st,

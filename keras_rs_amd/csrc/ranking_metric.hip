@@ -19,19 +19,18 @@
 //                                over several workgroups in three launches (metric_*_partials_kernel,
 //                                metric_state_update_kernel).
 //
-// Lists of up to kThreads items are packed several per workgroup as in K9.  Sums run in a fixed order (a thread's
-// items in rank order, a butterfly over the lanes of a wave, then a butterfly over the waves of a list): no atomics,
-// bit-identical from call to call.  Nothing waits for the host.
-#include "krs_common.h"
+// Packing, sort, reductions and the scan are krs_list.h's.  Sums run in a fixed order (a thread's items in rank
+// order, then seg_all_reduce's butterflies): no atomics, bit-identical from call to call.  Nothing waits for the host.
+#include "krs_list.h"
 
 namespace krs {
 namespace {
 
-constexpr int kThreads = 1024;
+constexpr int kThreads = kListThreads;
 constexpr int kMaxList = KRS_RANK_MAX_LIST;
 constexpr int kMaxSpecs = KRS_METRIC_MAX_SPECS;
 constexpr int kEpt = kMaxList / kThreads;   // sorted positions per thread, at most
-constexpr int kWaves = kThreads / 64;
+constexpr int kWaves = kListWaves;
 // reduction slots of stage A: one per spec, then sum w gain, sum gain, sum w rel, sum rel, sum w, number of valid items
 constexpr int kSumWG = kMaxSpecs, kSumG = kMaxSpecs + 1, kSumWR = kMaxSpecs + 2, kSumR = kMaxSpecs + 3,
               kSumW = kMaxSpecs + 4, kNValid = kMaxSpecs + 5, kSlots = kMaxSpecs + 6;
@@ -63,84 +62,6 @@ __device__ __forceinline__ uint32_t tie_r20(uint64_t salt, int64_t row, int inde
   return (uint32_t)(mix64(salt + (((uint64_t)row << 12) | (uint64_t)index)) >> 44);
 }
 
-__device__ __forceinline__ int pow2_at_least(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
-// descending bitonic sort of each P-long segment of keys[0 .. n_slots)
-__device__ __forceinline__ void sort_segments(uint64_t* keys, int n_slots, int P) {
-  for (int kk = 2; kk <= P; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int p = threadIdx.x; p < n_slots / 2; p += kThreads) {
-        const int e = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-        const uint64_t a = keys[e], b = keys[e + j];
-        const bool desc = ((e & (P - 1)) & kk) == 0;
-        if (desc ? a < b : a > b) {
-          keys[e] = b;
-          keys[e + j] = a;
-        }
-      }
-      __syncthreads();
-    }
-}
-
-// all-reduce of NV values over the tpl threads of each list (tpl a power of two); slot j is a maximum when bit j of
-// max_mask is set, a sum otherwise.  Every thread of the workgroup calls it and ends with its list's totals.
-template <int NV>
-__device__ __forceinline__ void seg_reduce(float (*red)[kWaves], float (&v)[NV], unsigned max_mask, int tpl) {
-  const int w = tpl < 64 ? tpl : 64;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const bool mx = (max_mask >> j) & 1u;
-    for (int o = 1; o < w; o <<= 1) {
-      const float t = __shfl_xor(v[j], o);
-      v[j] = mx ? fmaxf(v[j], t) : v[j] + t;
-    }
-  }
-  if (tpl > 64) {
-    const int wave = threadIdx.x >> 6, nw = tpl >> 6, w0 = (wave / nw) * nw;
-    __syncthreads();   // (the previous call's partials have been read)
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int j = 0; j < NV; ++j) red[j][wave] = v[j];
-    }
-    __syncthreads();
-    const int mine = w0 + (threadIdx.x & (nw - 1));   // (nw is a power of two: a butterfly over the list's waves)
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const bool mx = (max_mask >> j) & 1u;
-      float a = red[j][mine];
-      for (int o = 1; o < nw; o <<= 1) {
-        const float t = __shfl_xor(a, o);
-        a = mx ? fmaxf(a, t) : a + t;
-      }
-      v[j] = a;
-    }
-  }
-}
-
-// exclusive prefix sum of cnt over the tpl threads of each list
-__device__ __forceinline__ int seg_exclusive_scan(int* ibuf, int cnt, int tpl) {
-  const int w = tpl < 64 ? tpl : 64;
-  const int lane = threadIdx.x & (w - 1);
-  int inc = cnt;
-  for (int o = 1; o < w; o <<= 1) {
-    const int t = __shfl_up(inc, o, w);
-    if (lane >= o) inc += t;
-  }
-  int pre = inc - cnt;
-  if (tpl > 64) {
-    const int wave = threadIdx.x >> 6, nw = tpl >> 6, w0 = (wave / nw) * nw;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 63) ibuf[wave] = inc;
-    __syncthreads();
-    for (int i = w0; i < wave; ++i) pre += ibuf[i];
-  }
-  return pre;
-}
-
 __device__ __forceinline__ float rank_discount(const float* __restrict__ discount, int discount_len, int r1) {
   if (discount) return r1 <= discount_len ? discount[r1 - 1] : 0.0f;
   return 1.0f / log2f(1.0f + (float)r1);
@@ -158,13 +79,11 @@ __global__ __launch_bounds__(kThreads, 8) void ranking_metric_kernel(
   __shared__ float ws[kMaxList];      // weight in item order, 0 for an invalid item
   __shared__ float red[kSlots][kWaves];
   __shared__ int ibuf[kWaves];
-  const int P = pow2_at_least(L);
+  const ListPack lp(L);
+  const int P = lp.P, tpl = lp.tpl, ept = lp.ept;
   const int lgP = __ffs(P) - 1;
-  const int tpl = P >= kThreads ? kThreads : P;   // threads per list
-  const int ept = P / tpl;
-  const int lpb = kThreads / tpl;                 // lists per workgroup
-  const int64_t row0 = (int64_t)blockIdx.x * lpb;
-  const int n_slots = lpb * P;
+  const int64_t row0 = lp.row0();
+  const int n_slots = lp.n_slots();
   const uint64_t salt = shuffle ? tie_salt(seed, draw ? (uint64_t)*draw : 0ull) : 0ull;
 
   bool need_map = false, need_dcg = false, need_ndcg = false;
@@ -185,9 +104,7 @@ __global__ __launch_bounds__(kThreads, 8) void ranking_metric_kernel(
     float y = 0.0f, w = 0.0f;
     if (k < L && row < batch) {
       const int64_t o = row * L + k;
-      float s;
-      if constexpr (sizeof(T) == 2) s = bf16_to_f32(scores[row * ld + k]);
-      else s = scores[row * ld + k];
+      const float s = load1(&scores[row * ld + k]);
       const float yy = labels[o];
       const float ww = weights ? weights[row * w_row_stride + k * w_item_stride] : weight;
       const bool valid = yy >= 0.0f && (!mask || mask[o]) && ww > 0.0f;
@@ -202,9 +119,9 @@ __global__ __launch_bounds__(kThreads, 8) void ranking_metric_kernel(
     ws[i] = w;
   }
   __syncthreads();
-  sort_segments(keys, n_slots, P);
+  bitonic_sort(keys, n_slots, P, 0);
 
-  const int q = threadIdx.x / tpl, u = threadIdx.x - q * tpl;
+  const int q = lp.q(), u = lp.u();
   const int64_t row = row0 + q;
   const bool live = row < batch;
   const uint64_t* lk = keys + q * P + u * ept;   // this thread's ranks u*ept + 1 .. u*ept + ept
@@ -259,7 +176,7 @@ __global__ __launch_bounds__(kThreads, 8) void ranking_metric_kernel(
       }
     }
   }
-  seg_reduce<kSlots>(red, acc, max_mask, tpl);
+  seg_all_reduce<kSlots>(red, acc, max_mask, tpl);
 
   float vals[kMaxSpecs];
 #pragma unroll
@@ -286,7 +203,7 @@ __global__ __launch_bounds__(kThreads, 8) void ranking_metric_kernel(
       keys[i] = key;
     }
     __syncthreads();
-    sort_segments(keys, n_slots, P);
+    bitonic_sort(keys, n_slots, P, 0);
     float ideal[kMaxSpecs];
 #pragma unroll
     for (int j = 0; j < kMaxSpecs; ++j) ideal[j] = 0.0f;
@@ -304,7 +221,7 @@ __global__ __launch_bounds__(kThreads, 8) void ranking_metric_kernel(
       for (int j = 0; j < kMaxSpecs; ++j)
         if (j < sp.n && sp.kind[j] == KRS_METRIC_NDCG && r1 <= sp.k[j]) ideal[j] += w * (g * d);
     }
-    seg_reduce<kMaxSpecs>(red, ideal, 0u, tpl);
+    seg_all_reduce<kMaxSpecs>(red, ideal, 0u, tpl);
 #pragma unroll
     for (int j = 0; j < kMaxSpecs; ++j)
       if (j < sp.n && sp.kind[j] == KRS_METRIC_NDCG) vals[j] = divide_no_nan(vals[j], ideal[j]);
@@ -319,26 +236,6 @@ __global__ __launch_bounds__(kThreads, 8) void ranking_metric_kernel(
   sums[2 * batch + row] = acc[kSumWR];
   sums[3 * batch + row] = acc[kSumR];
   sums[4 * batch + row] = acc[kSumW];
-}
-
-// all-reduce (sums) of NV values over the workgroup, in a fixed order
-template <int NV>
-__device__ __forceinline__ void block_reduce(float (*red)[kWaves], float (&v)[NV]) {
-#pragma unroll
-  for (int j = 0; j < NV; ++j)
-    for (int o = 1; o < 64; o <<= 1) v[j] += __shfl_xor(v[j], o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int j = 0; j < NV; ++j) red[j][threadIdx.x >> 6] = v[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    float a = red[j][threadIdx.x & (kWaves - 1)];   // a butterfly over the 16 wave partials
-    for (int o = 1; o < kWaves; o <<= 1) a += __shfl_xor(a, o);
-    v[j] = a;
-  }
 }
 
 // get_list_weights for one list: 0 without weight, sum(w relevance) / sum(relevance) with relevance, else the default
@@ -407,12 +304,12 @@ __global__ __launch_bounds__(kThreads) void metric_accumulate_kernel(const float
   __shared__ float red[2 * kMaxSpecs][kWaves];
   float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   default_weight_sums(sums, batch, threadIdx.x, kThreads, s);
-  block_reduce<4>(red, s);
+  seg_all_reduce<4>(red, s, 0u, kThreads);
   float t[2 * kMaxSpecs];
 #pragma unroll
   for (int j = 0; j < 2 * kMaxSpecs; ++j) t[j] = 0.0f;
   mean_update_sums(values, sums, sp, batch, threadIdx.x, kThreads, s, out_values, out_weights, t);
-  block_reduce<2 * kMaxSpecs>(red, t);
+  seg_all_reduce<2 * kMaxSpecs>(red, t, 0u, kThreads);
   if (threadIdx.x != 0) return;
 #pragma unroll
   for (int j = 0; j < kMaxSpecs; ++j)
@@ -439,7 +336,7 @@ __global__ __launch_bounds__(kThreads) void metric_weight_partials_kernel(const 
   __shared__ float red[4][kWaves];
   float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   default_weight_sums(sums, batch, (int64_t)blockIdx.x * kThreads + threadIdx.x, (int64_t)gridDim.x * kThreads, s);
-  block_reduce<4>(red, s);
+  seg_all_reduce<4>(red, s, 0u, kThreads);
   if (threadIdx.x != 0) return;
 #pragma unroll
   for (int c = 0; c < 4; ++c) ws[blockIdx.x * kAccPartials + c] = s[c];
@@ -461,7 +358,7 @@ __global__ __launch_bounds__(kThreads) void metric_mean_partials_kernel(const fl
   for (int j = 0; j < 2 * kMaxSpecs; ++j) t[j] = 0.0f;
   mean_update_sums(values, sums, sp, batch, (int64_t)blockIdx.x * kThreads + threadIdx.x,
                    (int64_t)gridDim.x * kThreads, s, out_values, out_weights, t);
-  block_reduce<2 * kMaxSpecs>(red, t);
+  seg_all_reduce<2 * kMaxSpecs>(red, t, 0u, kThreads);
   if (threadIdx.x != 0) return;
 #pragma unroll
   for (int j = 0; j < 2 * kMaxSpecs; ++j) ws[blockIdx.x * kAccPartials + 4 + j] = t[j];
@@ -513,15 +410,12 @@ extern "C" int krs_ranking_metrics(const void* scores, int64_t ld, int dtype, co
                                    float* values, float* sums, int32_t* order, void* stream) {
   using namespace krs;
   const char* what = "krs_ranking_metrics";
-  KRS_REQUIRE(list >= 1 && list <= kMaxList, "%s: list length %lld outside the supported 1..%d (KRS_RANK_MAX_LIST)",
-              what, (long long)list, kMaxList);
+  int rc = check_lists(what, ld, dtype, batch, list);
+  if (rc != KRS_OK) return rc;
   const int L = (int)list;
   Specs sp;
-  const int rc = fill_specs(what, kinds, ks, n_specs, L, &sp);
+  rc = fill_specs(what, kinds, ks, n_specs, L, &sp);
   if (rc != KRS_OK) return rc;
-  KRS_REQUIRE(batch >= 0, "%s: negative batch", what);
-  KRS_REQUIRE(ld >= list, "%s: ld %lld below the list length %lld", what, (long long)ld, (long long)list);
-  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "%s: bad dtype", what);
   KRS_REQUIRE(!weights || (weights_row_stride >= 0 && (weights_item_stride == 0 || weights_item_stride == 1) &&
                            weights_row_stride >= weights_item_stride * list),
               "%s: weights strides (%lld, %lld) are neither [batch, list] nor one weight per list", what,
@@ -532,10 +426,7 @@ extern "C" int krs_ranking_metrics(const void* scores, int64_t ld, int dtype, co
                   "%s: %lld discounts for k = %d", what, (long long)discount_len, sp.k[j]);
   KRS_REQUIRE(batch == 0 || (scores && labels && values && sums), "%s: null argument", what);
   if (batch == 0) return KRS_OK;
-  int P = 1;
-  while (P < L) P <<= 1;
-  const int lpb = P >= kThreads ? 1 : kThreads / P;
-  const dim3 grid((unsigned)ceil_div(batch, lpb));
+  const dim3 grid = ListPack(L).grid(batch);
   const int dlen = discount ? (int)(discount_len < kMaxList ? discount_len : kMaxList) : 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (dtype == KRS_BF16)

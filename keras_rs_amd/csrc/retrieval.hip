@@ -7,8 +7,9 @@
 //
 // One total order everywhere: the fp32 score descending, then the index ascending; -0.0 counts as +0.0 and NaN
 // ranks above +inf (torch.topk).  A score becomes an order-preserving uint32 (order_key), and a (score, index) pair
-// the unique uint64 (key << 32) | ~index, so "descending uint64" IS the total order and a selection never meets a tie.
-// The value 0 is below every real pair (-inf maps to 0x007fffff) and pads partial lists.
+// the unique uint64 pair_key of krs_list.h, so "descending uint64" IS the total order and a selection never meets a
+// tie.  The value 0 is below every real pair (-inf maps to 0x007fffff) and pads partial lists.  The LDS sorts are
+// krs_list.h's bitonic_sort / bitonic_step, so every launch that sorts in LDS has kListThreads threads.
 //
 //   * krs_topk_rows           rows of a [R, C] matrix: C <= 2048 -> load the row into LDS, bitonic sort, emit
 //                             (topk_small_kernel); longer rows -> MSD radix select on the uint64 pairs, one workgroup per
@@ -22,7 +23,7 @@
 //                             query-chunked fp32 slab, then the krs_topk_rows selection.
 #include <algorithm>
 
-#include "krs_common.h"
+#include "krs_list.h"
 
 namespace krs {
 namespace {
@@ -45,13 +46,6 @@ __device__ __forceinline__ float key_value(uint32_t k) {
   if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
-__device__ __forceinline__ uint64_t make_pair(uint32_t key, uint32_t idx) { return ((uint64_t)key << 32) | (uint32_t)~idx; }
-
-inline int64_t pow2_ceil(int64_t v) {
-  int64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // ---- sources of pairs ------------------------------------------------------------------------------------------------
@@ -67,7 +61,7 @@ struct MatSrc {
     const int64_t o = (row0 + r) * ld + i;
     float v = ld_elem(x, dtype, o);
     if (boost) v = __fadd_rn(v, __fmul_rn(scale, ld_elem(boost, dtype, o)));
-    return make_pair(order_key(v), (uint32_t)i);
+    return pair_key(order_key(v), (uint32_t)i);
   }
 };
 // the per-slice lists stage 1 wrote: [rows, len] pairs
@@ -87,35 +81,16 @@ struct Out {
   int64_t row0;
   int64_t n;   // columns / candidates: a padding pair (never selected while n >= k) maps to -1
   __device__ __forceinline__ void emit(int64_t r, int j, uint64_t e) const {
-    const uint32_t i = ~(uint32_t)e;
+    const uint32_t i = pair_index(e);
     const int64_t o = (row0 + r) * k + j;
     idx[o] = (int64_t)i >= n ? -1 : ids ? ids[i] : (int32_t)i;
     if (val) st_elem(val, val_dtype, o, key_value((uint32_t)(e >> 32)));
   }
 };
 
-// ---- bitonic sort, descending ----------------------------------------------------------------------------------------
-// One compare-exchange step (kk, j) over `n` LDS pairs whose first element has the list index `base`.
-__device__ __forceinline__ void lds_step(uint64_t* s, int n, int64_t base, int64_t kk, int j) {
-  for (int p = threadIdx.x; p < n / 2; p += blockDim.x) {
-    const int e = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-    const uint64_t a = s[e], b = s[e + j];
-    const bool desc = ((base + e) & kk) == 0;
-    if (desc ? a < b : a > b) {
-      s[e] = b;
-      s[e + j] = a;
-    }
-  }
-  __syncthreads();
-}
-// full sort of a power-of-two LDS list (descending when base & n == 0)
-__device__ void lds_sort(uint64_t* s, int n, int64_t base) {
-  for (int kk = 2; kk <= n; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) lds_step(s, n, base, kk, j);
-}
-
+// ---- bitonic sort, descending: the steps that leave LDS --------------------------------------------------------------
 // sort blocks of a row list: kk == 0 -> full sort of each block, else the steps j < block of merge stage kk
-__global__ __launch_bounds__(1024) void sort_block_kernel(uint64_t* a, int64_t P, int64_t kk) {
+__global__ __launch_bounds__(kListThreads) void sort_block_kernel(uint64_t* a, int64_t P, int64_t kk) {
   __shared__ uint64_t s[kSortMax];
   const int n = (int)std::min<int64_t>(P, kSortMax);
   const int64_t blocks = P / n;
@@ -123,9 +98,9 @@ __global__ __launch_bounds__(1024) void sort_block_kernel(uint64_t* a, int64_t P
   uint64_t* g = a + row * P + base;
   for (int i = threadIdx.x; i < n; i += blockDim.x) s[i] = g[i];
   __syncthreads();
-  if (kk == 0) lds_sort(s, n, base);
+  if (kk == 0) bitonic_sort(s, n, n, base);
   else
-    for (int j = n >> 1; j > 0; j >>= 1) lds_step(s, n, base, kk, j);
+    for (int j = n >> 1; j > 0; j >>= 1) bitonic_step(s, n, n, base, kk, j);
   for (int i = threadIdx.x; i < n; i += blockDim.x) g[i] = s[i];
 }
 // one global step (kk, j >= kSortMax) of each row list
@@ -153,12 +128,12 @@ __global__ __launch_bounds__(256) void emit_kernel(const uint64_t* a, int64_t ro
 // ---- selection -------------------------------------------------------------------------------------------------------
 // rows of at most kSortMax pairs: the whole row in LDS, sorted, first k emitted
 template <class Src>
-__global__ __launch_bounds__(1024) void topk_small_kernel(Src src, int64_t len, int n, Out out) {
+__global__ __launch_bounds__(kListThreads) void topk_small_kernel(Src src, int64_t len, int n, Out out) {
   __shared__ uint64_t s[kSortMax];
   const int64_t row = blockIdx.x;
   for (int i = threadIdx.x; i < n; i += blockDim.x) s[i] = i < len ? src.pair(row, i) : 0;
   __syncthreads();
-  lds_sort(s, n, 0);
+  bitonic_sort(s, n, n, 0);
   for (int j = threadIdx.x; j < out.k; j += blockDim.x) out.emit(row, j, s[j]);
 }
 
@@ -223,7 +198,7 @@ __global__ __launch_bounds__(1024) void radix_select_kernel(Src src, int64_t len
 
 inline size_t select_list_bytes(int64_t rows, int64_t len, int k) {
   if (len <= kSortMax) return 0;
-  return (size_t)rows * (size_t)pow2_ceil(k) * sizeof(uint64_t);
+  return (size_t)rows * (size_t)pow2_at_least<int64_t>(k) * sizeof(uint64_t);
 }
 
 // top-k of `rows` rows of `len` pairs each -> out; `list` = select_list_bytes of workspace
@@ -231,17 +206,17 @@ template <class Src>
 int select_rows(const Src& src, int64_t rows, int64_t len, int k, const Out& out, uint64_t* list, hipStream_t st) {
   if (rows <= 0) return KRS_OK;
   if (len <= kSortMax) {
-    hipLaunchKernelGGL(topk_small_kernel<Src>, dim3((unsigned)rows), dim3(1024), 0, st, src, len,
-                       (int)pow2_ceil(len), out);
+    hipLaunchKernelGGL(topk_small_kernel<Src>, dim3((unsigned)rows), dim3(kListThreads), 0, st, src, len,
+                       (int)pow2_at_least(len), out);
     KRS_CHECK_LAUNCH("topk_small_kernel");
     return KRS_OK;
   }
-  const int64_t P = pow2_ceil(k);
+  const int64_t P = pow2_at_least<int64_t>(k);
   hipLaunchKernelGGL(radix_select_kernel<Src>, dim3((unsigned)rows), dim3(1024), 0, st, src, len, k, list, P);
   KRS_CHECK_LAUNCH("radix_select_kernel");
   const int64_t n = std::min<int64_t>(P, kSortMax);
   const unsigned sblocks = (unsigned)(rows * (P / n));
-  hipLaunchKernelGGL(sort_block_kernel, dim3(sblocks), dim3(1024), 0, st, list, P, (int64_t)0);
+  hipLaunchKernelGGL(sort_block_kernel, dim3(sblocks), dim3(kListThreads), 0, st, list, P, (int64_t)0);
   KRS_CHECK_LAUNCH("sort_block_kernel");
   for (int64_t kk = 2 * n; kk <= P; kk <<= 1) {
     for (int64_t j = kk >> 1; j >= n; j >>= 1) {
@@ -249,7 +224,7 @@ int select_rows(const Src& src, int64_t rows, int64_t len, int k, const Out& out
                          P, kk, j);
       KRS_CHECK_LAUNCH("sort_step_kernel");
     }
-    hipLaunchKernelGGL(sort_block_kernel, dim3(sblocks), dim3(1024), 0, st, list, P, kk);
+    hipLaunchKernelGGL(sort_block_kernel, dim3(sblocks), dim3(kListThreads), 0, st, list, P, kk);
     KRS_CHECK_LAUNCH("sort_block_kernel");
   }
   hipLaunchKernelGGL(emit_kernel, dim3((unsigned)ceil_div(rows * k, 256)), dim3(256), 0, st, list, rows, P, out);
@@ -425,7 +400,7 @@ __global__ __launch_bounds__(256) void retr_stage1_kernel(const Stage1 p) {
       const uint32_t key = order_key(acc[r]);
       if (cvalid && q0 + row < p.b && key > t_reg[r]) {
         const int s = atomicAdd(&cnt[row], 1);
-        queue[row * p.cap + s] = make_pair(key, (uint32_t)cand);
+        queue[row * p.cap + s] = pair_key(key, (uint32_t)cand);
       }
     }
     __syncthreads();
@@ -481,7 +456,7 @@ inline size_t fused_bytes(int64_t b, int64_t n, int k) {
 }
 // rows of one chunk of the two-step path
 inline int64_t chunk_rows(int64_t b, int64_t n, int k) {
-  const size_t per_row = (size_t)n * sizeof(float) + (n > kSortMax ? (size_t)pow2_ceil(k) * sizeof(uint64_t) : 0);
+  const size_t per_row = (size_t)n * sizeof(float) + select_list_bytes(1, n, k);
   return std::max<int64_t>(1, std::min<int64_t>(b, (int64_t)(kSlabBudget / per_row)));
 }
 

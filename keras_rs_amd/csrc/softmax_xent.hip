@@ -17,8 +17,8 @@
 //   * remove_accidental_hits_kernel   pos = first argmax of the row's labels, dup_j = (ids_j == ids_pos),
 //                                     out_j = x_j + (dup_j - y_j) * value with every operation rounded on its own
 //
-// Layout (K9's): workgroups of kThreads = 1024.  Rows of up to 1024 columns are packed 1024 / pow2ceil(cols) per
-// workgroup, one element per thread, the row held in registers.  Longer rows take a workgroup each:
+// Layout: rows of up to kThreads columns are packed as krs_list.h's ListPack packs lists, one element per thread, the
+// row held in registers.  Longer rows take a workgroup each:
 //   - cols <= kStageCols = 9216: the row's logits and smoothed labels are staged in LDS as fp32 while the statistics
 //     are taken (2 x 36 KiB + 192 B of partials = 73,920 B per workgroup; two workgroups, 147,840 B, fit the CU's
 //     160 KiB, and 1024 threads at <= 64 VGPRs leave both resident), so HBM sees logits and labels once;
@@ -28,28 +28,16 @@
 // Reductions: lane butterflies within a wave, then the wave partials of a row added through LDS in wave order.  No
 // atomics, a fixed summation order: repeated calls are bit-identical.  No host synchronisation and no allocation: a
 // call can be captured into a HIP graph.
-#include "krs_common.h"
+#include "krs_list.h"
 
 namespace krs {
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / 64;
+constexpr int kThreads = kListThreads;
+constexpr int kWaves = kListWaves;
 constexpr int kStageCols = 9216;
 constexpr float kNegInf = -__builtin_inff();
 
-__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7fc00000u); }
-
-template <typename T>
-__device__ __forceinline__ float load1(const T* p) {
-  if constexpr (sizeof(T) == 2) return bf16_to_f32(*p);
-  else return *p;
-}
-template <typename T>
-__device__ __forceinline__ void store1(T* p, float v) {
-  if constexpr (sizeof(T) == 2) *p = f32_to_bf16(v);
-  else *p = v;
-}
 // 16 bytes of T (kVec<T> elements) at p, which is 16-byte aligned
 template <typename T>
 constexpr int kVec = 16 / (int)sizeof(T);
@@ -93,7 +81,8 @@ __device__ __forceinline__ void store_f32(float* p, const float (&v)[N]) {
 
 // All-reduce of K values over the `tpr` threads of a row (tpr a power of two, rows aligned to it; tpr and the call
 // are uniform over the workgroup).  Lane butterflies up to the wave; beyond it the row's wave partials go through
-// `red` [K][kWaves] and every thread adds them in wave order.
+// `red` [K][kWaves] and every thread adds them in wave order, ((a + b) + c) + d: seg_all_reduce's butterfly over the
+// partials would change low bits of the loss and the gradient for rows of four waves or more.
 template <bool MAX, int K>
 __device__ __forceinline__ void row_all_reduce(float (&v)[K], float* red, int tpr) {
   const int width = tpr < 64 ? tpr : 64;
@@ -155,11 +144,10 @@ __global__ __launch_bounds__(kThreads) void softmax_xent_kernel(const T* __restr
   __shared__ float red[3 * kWaves];
   const float keep = 1.0f - ls, spread = ls / (float)cols;
   const bool packed = cols <= kThreads;
+  // ListPack's tpl and lpb (the host launches by it), written out: with tpr a constant on the staged and streamed
+  // paths the kernel measured 1-2 % faster at (8192, 8192) than with the struct's.
   int tpr = kThreads;
-  if (packed) {
-    tpr = 1;
-    while (tpr < cols) tpr <<= 1;
-  }
+  if (packed) tpr = pow2_at_least(cols);
   const int rpb = kThreads / tpr;
   const int q = threadIdx.x / tpr, u = threadIdx.x - q * tpr;
   const int64_t row = (int64_t)blockIdx.x * rpb + q;
@@ -307,21 +295,17 @@ __global__ __launch_bounds__(kThreads) void remove_accidental_hits_kernel(const 
                                                                           int64_t id_rows, float value, int64_t rows,
                                                                           int cols, T* __restrict__ out, int64_t ldo) {
   __shared__ unsigned long long red[kWaves];
-  int tpr = kThreads;
-  if (cols <= kThreads) {
-    tpr = 1;
-    while (tpr < cols) tpr <<= 1;
-  }
-  const int rpb = kThreads / tpr;
-  const int q = threadIdx.x / tpr, u = threadIdx.x - q * tpr;
-  const int64_t row = (int64_t)blockIdx.x * rpb + q;
+  const ListPack lp(cols);
+  const int tpr = lp.tpl;
+  const int u = lp.u();
+  const int64_t row = lp.row0() + lp.q();
   const bool live = row < rows;
   const float* y = labels + (live ? row : 0) * ldl;
   // first index of the largest label: the largest (order key, ~index) pair; 0 (no element) is below every pair
   unsigned long long best = 0;
   if (live)
     for (int j = u; j < cols; j += tpr) {
-      const unsigned long long key = ((unsigned long long)order_key(y[j]) << 32) | (uint32_t)~(uint32_t)j;
+      const unsigned long long key = pair_key(order_key(y[j]), (uint32_t)j);
       best = key > best ? key : best;
     }
   const int width = tpr < 64 ? tpr : 64;
@@ -337,7 +321,7 @@ __global__ __launch_bounds__(kThreads) void remove_accidental_hits_kernel(const 
     for (int i = 1; i < wpr; ++i) best = red[w0 + i] > best ? red[w0 + i] : best;
   }
   if (!live) return;
-  const int pos = (int)~(uint32_t)best;          // < cols: every live row has cols >= 1 elements
+  const int pos = (int)pair_index(best);         // < cols: every live row has cols >= 1 elements
   const I* idr = ids + (row % id_rows) * cols;
   const I id_pos = idr[pos];
   const T* x = logits + row * ldx;
@@ -350,11 +334,7 @@ __global__ __launch_bounds__(kThreads) void remove_accidental_hits_kernel(const 
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-inline int rows_per_block(int64_t cols) {
-  int tpr = 1;
-  while (tpr < cols && tpr < kThreads) tpr <<= 1;
-  return kThreads / tpr;
-}
+inline int rows_per_block(int64_t cols) { return ListPack((int)cols).lpb; }   // (cols <= 2^30)
 
 int check_matrix(const char* what, const void* logits, int64_t ld, int dtype, int64_t rows, int64_t cols) {
   KRS_REQUIRE(rows >= 0, "%s: negative row count", what);

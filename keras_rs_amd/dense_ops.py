@@ -19,16 +19,6 @@ ACTS = {None: L.ACT_NONE, "linear": L.ACT_NONE, "relu": L.ACT_RELU, "sigmoid": L
         "tanh": L.ACT_TANH}
 
 
-def _rowmajor(t: torch.Tensor, what: str) -> torch.Tensor:
-    L.require_device(t, what)
-    if t.dim() != 2:
-        raise L.KrsError(f"{what}: expected a matrix, got shape {tuple(t.shape)}")
-    # a row-broadcast view (strides (0, 1), e.g. the gradient of y.sum(0)) has no leading dimension a kernel can walk
-    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        return t.contiguous()
-    return t
-
-
 def gemm(a: torch.Tensor, b: torch.Tensor, *, a_is_km: bool = False, b_is_nk: bool = False,
          out_dtype: torch.dtype | None = None, bias: torch.Tensor | None = None, act: int = L.ACT_NONE,
          diag_scale: float = 0.0, x0: torch.Tensor | None = None, x: torch.Tensor | None = None,
@@ -37,8 +27,8 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, a_is_km: bool = False, b_is_nk: bo
     """C = epilogue(A @ B) (include/krs.h: krs_gemm).  Returns (C, u_or_None).
 
     a: [M,K] (or [K,M] when a_is_km);  b: [K,N] (or [N,K] when b_is_nk)."""
-    a = _rowmajor(a, "gemm A")
-    b = _rowmajor(b, "gemm B")
+    a = L.rowmajor(a, "gemm A")
+    b = L.rowmajor(b, "gemm B")
     if a.dtype != b.dtype:
         raise L.KrsError("gemm: A and B must share a dtype")
     m, k = (a.shape[1], a.shape[0]) if a_is_km else (a.shape[0], a.shape[1])
@@ -56,8 +46,8 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, a_is_km: bool = False, b_is_nk: bo
     ep.act = act
     ep.diag_scale = float(diag_scale or 0.0)
     if x0 is not None:
-        x0 = _rowmajor(x0, "gemm x0")
-        x = _rowmajor(x, "gemm x")
+        x0 = L.rowmajor(x0, "gemm x0")
+        x = L.rowmajor(x, "gemm x")
         if x0.stride(0) != x.stride(0):
             x0, x = x0.contiguous(), x.contiguous()
         if x0.dtype != odt or x.dtype != odt:
@@ -69,7 +59,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, a_is_km: bool = False, b_is_nk: bo
         u = torch.empty((m, n), dtype=odt, device=a.device)
         ep.u_out, ep.ldu = u.data_ptr(), u.stride(0)
     if r is not None:
-        r = _rowmajor(r, "gemm R")
+        r = L.rowmajor(r, "gemm R")
         if r.dtype != odt:
             raise L.KrsError("gemm: R must have the output dtype")
         keep.append(r)
@@ -94,7 +84,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, a_is_km: bool = False, b_is_nk: bo
 
 
 def cross_epilogue_fwd(u, x0, x, diag_scale=0.0):
-    u, x0, x = (_rowmajor(t, "cross_epilogue_fwd").contiguous() for t in (u, x0, x))
+    u, x0, x = (L.rowmajor(t, "cross_epilogue_fwd").contiguous() for t in (u, x0, x))
     y = torch.empty_like(x)
     m, n = x.shape
     rc = L.lib().krs_cross_epilogue_fwd(L.ptr(u), L.ptr(x0), L.ptr(x), L.ptr(y), m, n,
@@ -118,9 +108,9 @@ def cross_epilogue_bwd(g, u, x0, x, diag_scale=0.0, *, act: int = L.ACT_NONE,
     """Returns (du, dx0, dxd, dbias); dx0 accumulates into `dx0_into` when given.
     fold_direct (the case x is x0): the direct term g + diag*g*x0 is added into dx0 instead of
     being written to its own buffer (the C ABI's `dxd == dx0` aliasing rule); dxd is then dx0."""
-    g, x0, x = (_rowmajor(t, "cross_epilogue_bwd").contiguous() for t in (g, x0, x))
+    g, x0, x = (L.rowmajor(t, "cross_epilogue_bwd").contiguous() for t in (g, x0, x))
     # (u None: allowed when neither dL/dx0 nor an activation derivative is wanted -- dz = g * x0 needs no third stream)
-    u = None if u is None else _rowmajor(u, "cross_epilogue_bwd").contiguous()
+    u = None if u is None else L.rowmajor(u, "cross_epilogue_bwd").contiguous()
     if u is None and (want_dx0 or act != L.ACT_NONE):
         raise L.KrsError("cross_epilogue_bwd: u is needed for dL/dx0 and for an activation's derivative")
     m, n = x.shape
@@ -152,9 +142,9 @@ def gemm_cross_bwd(a: torch.Tensor, bt: torch.Tensor, r: torch.Tensor, x0: torch
     of in a matrix that layer would have written; want_dx0=False, without R only: no dL/dx0 from this launch -- `u` is
     handed to the next one as ITS u_upper).  Returns (G, dz, dx0, dbias).  a: [M, K], bt: [N, K] (K-contiguous
     weight), r / x0 / u: [M, N] row-major of a's dtype."""
-    a, bt = _rowmajor(a, "gemm_cross_bwd A"), _rowmajor(bt, "gemm_cross_bwd Bt")
-    x0, u = (_rowmajor(t, "gemm_cross_bwd operand").contiguous() for t in (x0, u))
-    r = None if r is None else _rowmajor(r, "gemm_cross_bwd R").contiguous()      # (None: no residual term)
+    a, bt = L.rowmajor(a, "gemm_cross_bwd A"), L.rowmajor(bt, "gemm_cross_bwd Bt")
+    x0, u = (L.rowmajor(t, "gemm_cross_bwd operand").contiguous() for t in (x0, u))
+    r = None if r is None else L.rowmajor(r, "gemm_cross_bwd R").contiguous()      # (None: no residual term)
     m, k = a.shape
     n = bt.shape[0]
     if bt.shape[1] != k or (r is not None and tuple(r.shape) != (m, n)) or tuple(x0.shape) != (m, n) or tuple(u.shape) != (m, n):
@@ -169,7 +159,7 @@ def gemm_cross_bwd(a: torch.Tensor, bt: torch.Tensor, r: torch.Tensor, x0: torch
     if dx0 is not None and (not dx0.is_contiguous() or dx0.dtype != a.dtype or tuple(dx0.shape) != (m, n)):
         raise L.KrsError("gemm_cross_bwd: dx0 buffer must be a contiguous [M, N] matrix of the operands' dtype")
     if u_upper is not None:
-        u_upper = _rowmajor(u_upper, "gemm_cross_bwd u_upper").contiguous()
+        u_upper = L.rowmajor(u_upper, "gemm_cross_bwd u_upper").contiguous()
         if dx0_into is not None or r is None or beta != 1.0 or u_upper.dtype != a.dtype or tuple(u_upper.shape) != (m, n):
             raise L.KrsError("gemm_cross_bwd: u_upper needs R (beta = 1), no dx0 to accumulate into, and the operands' shape / dtype")
     dbias = torch.empty(n, dtype=torch.float32, device=a.device) if want_dbias else None
@@ -192,8 +182,8 @@ def gemm_dense_bwd(a: torch.Tensor, bt: torch.Tensor, y: torch.Tensor, act: int,
     is y) in its epilogue.  want_g: the product G = A @ Bt^T (rounded once; dz is computed from it as stored) is written
     too -- the true dL/dy of that output; otherwise it is never stored.  a: [M, K], bt: [N, K], y: [M, N].
     Returns (dz, dbias, G or None)."""
-    a, bt = _rowmajor(a, "gemm_dense_bwd A"), _rowmajor(bt, "gemm_dense_bwd Bt")
-    y = _rowmajor(y, "gemm_dense_bwd y").contiguous()
+    a, bt = L.rowmajor(a, "gemm_dense_bwd A"), L.rowmajor(bt, "gemm_dense_bwd Bt")
+    y = L.rowmajor(y, "gemm_dense_bwd y").contiguous()
     m, k = a.shape
     n = bt.shape[0]
     if bt.shape[1] != k or tuple(y.shape) != (m, n) or not (a.dtype == bt.dtype == y.dtype):
@@ -242,7 +232,7 @@ def last_gemm_route() -> dict:
 
 
 def colsum(a: torch.Tensor) -> torch.Tensor:
-    a = _rowmajor(a, "colsum")
+    a = L.rowmajor(a, "colsum")
     out = torch.empty(a.shape[1], dtype=torch.float32, device=a.device)
     ws, ws_ptr, ws_bytes = _colsum_ws(a.shape[0], a.shape[1], a.device)
     rc = L.lib().krs_colsum(L.ptr(a), a.stride(0), a.shape[0], a.shape[1],
@@ -254,10 +244,10 @@ def colsum(a: torch.Tensor) -> torch.Tensor:
 def dense_act_bwd(g: torch.Tensor, y: torch.Tensor | None, act: int, want_dbias: bool = True):
     """(dz, dbias) of a Dense layer's bias + activation epilogue: dz = g * act'(y) from the saved output y
     (None without an activation), dbias = fp32 column sums of dz (None if not wanted); krs_dense_act_bwd."""
-    g = _rowmajor(g, "dense_act_bwd g")
+    g = L.rowmajor(g, "dense_act_bwd g")
     m, n = g.shape
     if y is not None:
-        y = _rowmajor(y, "dense_act_bwd y")
+        y = L.rowmajor(y, "dense_act_bwd y")
         if y.dtype != g.dtype or tuple(y.shape) != (m, n):
             raise L.KrsError("dense_act_bwd: y must have the shape and dtype of g")
     need_dz = act != L.ACT_NONE
@@ -285,7 +275,7 @@ def cast_transpose(w: torch.Tensor, dtype: torch.dtype, want_plain: bool = True,
     keras_rs_amd.optim.Adagrad(prepare_casts=True) right behind its update -- then prepares the copies of ALL such
     weights for the next step in one launch and leaves them on the parameter (`_krs_cast`), where this function finds
     them ONCE (keyed by storage address, torch version, shape and dtypes)."""
-    w = _rowmajor(w, "cast_transpose")
+    w = L.rowmajor(w, "cast_transpose")
     if isinstance(w, torch.nn.Parameter) and w.dtype != dtype and want_plain and want_t and w.is_contiguous():
         hit = getattr(w, "_krs_cast", None)
         if hit is not None:
@@ -357,7 +347,7 @@ def dot_out_cols(n_feats: int, self_interaction: bool, skip_gather: bool) -> int
 
 
 def dot_interaction_fwd(feats: Sequence[torch.Tensor], self_interaction=False, skip_gather=False):
-    feats = [_rowmajor(f, "dot_interaction feature") for f in feats]
+    feats = [L.rowmajor(f, "dot_interaction feature") for f in feats]
     batch, dim = feats[0].shape
     out = torch.empty((batch, dot_out_cols(len(feats), self_interaction, skip_gather)), dtype=feats[0].dtype,
                       device=feats[0].device)
@@ -377,8 +367,8 @@ def dot_interaction_bwd(feats: Sequence[torch.Tensor], grad_out: torch.Tensor, s
     into / accumulate_mask (krs_dot_interaction_bwd_accumulate): `into` is a [B, F*dim] row-major matrix that
     already holds gradients of the features; feature f with bit f of the mask set is ADDED there (its returned
     gradient is None: the caller hands `into` on), the others are written to a fresh buffer as usual."""
-    feats = [_rowmajor(f, "dot_interaction feature") for f in feats]
-    grad_out = _rowmajor(grad_out, "dot_interaction grad")
+    feats = [L.rowmajor(f, "dot_interaction feature") for f in feats]
+    grad_out = L.rowmajor(grad_out, "dot_interaction grad")
     batch, dim = feats[0].shape
     n = len(feats)
     # one buffer, per-feature column views: a consumer that wants the gradients side by side

@@ -12,7 +12,7 @@ import torch
 
 from keras_rs_amd import _lib as L
 
-MAX_LIST = 4096   # KRS_RANK_MAX_LIST
+MAX_LIST = L.MAX_LIST
 MAX_SPECS = 8     # KRS_METRIC_MAX_SPECS
 MAX_AUCS = 4            # KRS_BINARY_METRIC_MAX_AUCS
 MAX_THRESHOLDS = 2048   # KRS_BINARY_METRIC_MAX_THRESHOLDS
@@ -43,12 +43,8 @@ def ranking_metrics(specs, scores: torch.Tensor, labels: torch.Tensor, mask: tor
     NDCG k]; draw a device int64 tensor of one element (read, not advanced).  Returns (values [n, B], sums [5, B],
     order [B, L] int32 or None): see include/krs.h for each."""
     what = "ranking_metrics"
-    L.require_device(scores, what)
-    if scores.dim() != 2:
-        raise L.KrsError(f"{what}: expected [batch, list] scores, got shape {tuple(scores.shape)}")
+    scores = L.rowmajor(scores, what, "[batch, list] scores")
     b, n = scores.shape
-    if scores.stride(1) != 1 or (b > 1 and scores.stride(0) < n):
-        scores = scores.contiguous()
     ld = scores.stride(0) if b > 1 else n
     dev = scores.device
     y = _full(labels, "labels", (b, n), dev, torch.float32, what)

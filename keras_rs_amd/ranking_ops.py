@@ -10,17 +10,13 @@ import torch
 
 from keras_rs_amd import _lib as L
 
-MAX_LIST = 4096   # KRS_RANK_MAX_LIST
+MAX_LIST = L.MAX_LIST
 PAIRWISE_KINDS = {"hinge": 0, "logistic": 1, "soft_zero_one": 2, "mse": 3}   # krs_rank_loss
 
 
 def _operands(logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor | None, what: str):
-    L.require_device(logits, what)
-    if logits.dim() != 2:
-        raise L.KrsError(f"{what}: expected [batch, list] logits, got shape {tuple(logits.shape)}")
+    logits = L.rowmajor(logits, what, "[batch, list] logits")
     b, n = logits.shape
-    if logits.stride(1) != 1 or (b > 1 and logits.stride(0) < n):
-        logits = logits.contiguous()
     ld = logits.stride(0) if b > 1 else n
     y = labels.to(device=logits.device, dtype=torch.float32).contiguous()
     m = None if mask is None else mask.to(device=logits.device, dtype=torch.bool).contiguous().view(torch.uint8)

@@ -20,15 +20,6 @@ MAX_FLOAT = float(torch.finfo(torch.float32).max) / 100.0
 SMALLEST_FLOAT = float(np.float32(np.finfo(np.float32).tiny) / np.float32(100.0))
 
 
-def _rowmajor(t: torch.Tensor, what: str) -> torch.Tensor:
-    L.require_device(t, what)
-    if t.dim() != 2:
-        raise L.KrsError(f"{what}: expected a matrix, got shape {tuple(t.shape)}")
-    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        return t.contiguous()
-    return t
-
-
 def topk_rows_workspace_bytes(rows: int, cols: int, k: int) -> int:
     return int(L.lib().krs_topk_rows_workspace_bytes(rows, cols, k))
 
@@ -42,9 +33,9 @@ def topk_rows(x: torch.Tensor, k: int, *, boost: torch.Tensor | None = None, boo
               want_keys: bool = False):
     """Top-k column indices of each row of x [R, C] (fp32 / bf16) on the key x + boost_scale * boost (fp32), in the
     order key descending, index ascending.  Returns int32 indices [R, k], or (indices, fp32 keys) with want_keys."""
-    x = _rowmajor(x, "topk_rows x")
+    x = L.rowmajor(x, "topk_rows x")
     if boost is not None:
-        boost = _rowmajor(boost, "topk_rows boost")
+        boost = L.rowmajor(boost, "topk_rows boost")
         if boost.dtype != x.dtype:
             boost = boost.to(x.dtype)
         if tuple(boost.shape) != tuple(x.shape):
@@ -65,8 +56,8 @@ def retrieval_topk(query: torch.Tensor, candidates: torch.Tensor, k: int, *, ids
                    want_scores: bool = True):
     """Top-k of query [B, D] . candidates [N, D]^T per query row (one dtype, fp32 / bf16).  Returns
     (scores [B, k] in the input dtype or None, int32 ids [B, k]); ids = ids[index] when ids (int32 [N]) is given."""
-    q = _rowmajor(query, "retrieval_topk query")
-    c = _rowmajor(candidates, "retrieval_topk candidates")
+    q = L.rowmajor(query, "retrieval_topk query")
+    c = L.rowmajor(candidates, "retrieval_topk candidates")
     if q.dtype != c.dtype:
         raise L.KrsError("retrieval_topk: query and candidates must share a dtype")
     b, d = q.shape

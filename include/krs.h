@@ -408,13 +408,17 @@ int krs_gemm_set_option(int key, int value);
 /* Tuning switches of krs_embed_bag_fwd / krs_embed_bag_bwd_* (process-wide; results never depend on them).
  *   KRS_EMBED_OPT_PLAN: krs_embed_bag_bwd_plan_tables -- 0 = table-segmented sort where the layout allows it
  *   (default), 1 = always the global sort (A/B).
+ *   KRS_EMBED_OPT_RANK: how the plan's scatter passes rank the keys of a round of 64 -- 0 = from the wave's LDS digit
+ *   counters (a no-return add between two reads), one ballot per collided group, and one ballot per digit bit only
+ *   for a round with more possible groups than bits (default); 1 = always one ballot per digit bit (A/B); 2 = always
+ *   from the counters.  The three give the same plan, bit for bit.
  *   KRS_EMBED_OPT_HOTROWS: LDS staging of hot embedding rows in the pooled gather -- 0 = off (default), 64 / 128 =
  *   rows 0 .. n-1 of a workgroup's table are copied to LDS and lookups of them are served from there (one flat
  *   16-byte load per lookup, routed to LDS or memory by its address); pays only when ids are relabelled
  *   hot-first and those rows are NOT already cache hits (profiles/r3_k1_hot_rows_lds.txt: they are).
  *   (Keys 0 and 1 -- the one-hot gather variants and the round-1 per-segment backward kernel -- were retired in
  *   round 5 with the kernels they selected; they are refused.) */
-enum { KRS_EMBED_OPT_PLAN = 2, KRS_EMBED_OPT_HOTROWS = 3 };
+enum { KRS_EMBED_OPT_PLAN = 2, KRS_EMBED_OPT_HOTROWS = 3, KRS_EMBED_OPT_RANK = 4 };
 int krs_embed_set_option(int key, int value);
 
 /* Elementwise halves of FeatureCross for the host-composed path (arbitrary

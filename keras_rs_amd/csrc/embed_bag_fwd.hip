@@ -638,12 +638,17 @@ int dispatch_lpr(const EmbedFwdParams& p, int row_pieces, bool one_hot, bool str
 }  // namespace
 }  // namespace krs
 
-namespace krs { extern int g_plan_variant; }   // embed_bag_plan.hip
+namespace krs { extern int g_plan_variant, g_rank_mode; }   // embed_bag_plan.hip
 
 extern "C" int krs_embed_set_option(int key, int value) {
   if (key == KRS_EMBED_OPT_PLAN) {
     KRS_REQUIRE(value == 0 || value == 1, "krs_embed_set_option: plan variant must be 0 or 1");
     krs::g_plan_variant = value;
+    return KRS_OK;
+  }
+  if (key == KRS_EMBED_OPT_RANK) {
+    KRS_REQUIRE(value >= 0 && value <= 2, "krs_embed_set_option: rank mode must be 0, 1 or 2");
+    krs::g_rank_mode = value;
     return KRS_OK;
   }
   if (key == KRS_EMBED_OPT_HOTROWS) {

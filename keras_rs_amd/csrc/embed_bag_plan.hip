@@ -17,6 +17,9 @@
 namespace krs {
 // krs_embed_set_option(KRS_EMBED_OPT_PLAN, v): 0 = table-segmented sort where the layout allows it (default), 1 = always the global sort
 int g_plan_variant = 0;
+// krs_embed_set_option(KRS_EMBED_OPT_RANK, v): how a scatter pass ranks the keys of a round (rs::count_rank below) -- 0 = by the
+// LDS counts, ballots only for rounds with many collisions (default), 1 = always ballots (A/B), 2 = always by the counts
+int g_rank_mode = 0;
 namespace {
 
 // ---- plan: the sort (LSD radix sort of (row key, bag << 32 | position) pairs, written for this plan) -----------
@@ -91,6 +94,15 @@ __device__ __forceinline__ bool generate(const Gen& gen, const GenLds& g, uint32
 
 __device__ __forceinline__ int digit_of(uint32_t key, int shift, int bins) { return (int)((key >> shift) & (bins - 1)); }
 
+// Which tile workgroup b takes.  Workgroups are dealt round-robin to the chip's eight XCDs (each with an L2 of its own), so b
+// and b + 8 share one; they take CONSECUTIVE tiles: a digit's pieces of neighbouring tiles -- runs of about four keys = 16
+// bytes with 1024 digits -- and the neighbouring 4-byte counters of the [digit][tile] matrix then meet in one L2 and
+// leave it as whole lines.  The grid is tile_grid(tiles) = 8 * ceil(tiles / 8) workgroups; those whose tile lies past the
+// end exit.  A bijection on the tiles whatever the placement: where a workgroup runs changes the speed only.
+// (Multi-hot C3 plan, table-segmented: 533 -> 411 us; docs/measurement_log.md, K2 plan ranking.)
+__device__ __forceinline__ uint32_t tile_of_block(uint32_t b, uint32_t tiles) { return (b & 7) * ((tiles + 7) / 8) + (b >> 3); }
+inline unsigned tile_grid(unsigned tiles) { return (tiles + 7) / 8 * 8; }
+
 // ---- histogram pass: the tile's digit counts, in LDS, to the tile's column of the [digit][tile] count matrix ----
 __device__ __forceinline__ void hist_zero(int (&h)[kMaxBins], int bins) {
   for (int i = threadIdx.x; i < bins; i += kHistThreads) h[i] = 0;
@@ -122,17 +134,22 @@ template <typename V>
 __device__ __forceinline__ void zero_counts(TileLds<V>& s) {
   for (int i = threadIdx.x; i < kWaves * kMaxBins; i += kThreads) (&s.cnt[0][0])[i] = 0;
 }
-// One round of ballot ranking: the rank of this lane's key among the keys of the same digit that its wave has seen so
-// far (`mine` = the wave's row of cnt; dead lanes take no part and get 0).
-__device__ __forceinline__ int ballot_rank(uint32_t key, bool live, int shift, int bits, volatile uint16_t* mine,
-                                           int lane) {
-  const int d = digit_of(key, shift, 1 << bits);
-  // lanes of this round with the same digit
+// Lanes of this round whose key has this lane's digit: one ballot per digit bit (gfx950 has no match_any).
+__device__ __forceinline__ unsigned long long digit_peers(int d, bool live, int bits) {
   unsigned long long peers = __ballot(live);
   for (int b = 0; b < bits; ++b) {
     const unsigned long long m = __ballot((d >> b) & 1);
     peers &= ((d >> b) & 1) ? m : ~m;
   }
+  return peers;
+}
+// One round of ballot ranking: the rank of this lane's key among the keys of the same digit that its wave has seen so
+// far (`mine` = the wave's row of cnt; dead lanes take no part and get 0).  `bits` ballots per round, and the rounds of a
+// wave are a serial chain through the leader's read-modify-write of the counter.
+__device__ __forceinline__ int ballot_rank(uint32_t key, bool live, int shift, int bits, volatile uint16_t* mine,
+                                           int lane) {
+  const int d = digit_of(key, shift, 1 << bits);
+  const unsigned long long peers = digit_peers(d, live, bits);
   int r = 0, c = 0;
   if (live) {
     r = __popcll(peers & ((1ULL << lane) - 1ULL));
@@ -145,6 +162,68 @@ __device__ __forceinline__ int ballot_rank(uint32_t key, bool live, int shift, i
   }
   __builtin_amdgcn_wave_barrier();
   return c + r;
+}
+// Count-and-fix ranking of all the thread's rounds: the same ranks and the same final counters as kItems calls of
+// ballot_rank, found from the counters themselves.  The wave's row of cnt is read as 32-bit words (digit d = half d & 1
+// of word d >> 1; a wave sees at most 512 keys of a tile, so a half never carries into the other).  A round reads its
+// lanes' words, adds one to the digit's half with an LDS add that returns nothing, and reads the words again: the adds
+// of one instruction commute, so what the second read sees does not depend on the order in which the hardware serves
+// the lanes.  The first read holds c, the digit's count before the round; the difference n, the live lanes of the
+// round with that digit.  n == 1 (nearly every key when the digit is wide): rank = c, no ballot.  n > 1: one ballot
+// per collided group of the round, lanes ranked in ascending order = input order (stable).  A wave's LDS instructions
+// execute in order, so all rounds' instructions are issued back to back (a later round's first read sees the earlier
+// rounds' adds) and waited for once.  `fallback`: a round in which more groups may have collided than its digit has
+// bits is ranked by digit_peers instead (narrow digits, tiny vocabularies, hot rows); never both forms in one round.
+typedef uint32_t __attribute__((may_alias)) cnt_word;
+__device__ __forceinline__ void count_rank(const uint32_t (&key)[kItems], int64_t first, int64_t end, int shift, int bits,
+                                           bool fallback, uint16_t* mine, int lane, int (&rank)[kItems]) {
+  cnt_word* word = reinterpret_cast<cnt_word*>(mine);
+  uint32_t before[kItems], after[kItems];
+#pragma unroll
+  for (int it = 0; it < kItems; ++it) {
+    const int d = digit_of(key[it], shift, 1 << bits);
+    const bool live = first + it * 64 < end;
+    cnt_word* w = word + (d >> 1);
+    before[it] = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __builtin_amdgcn_wave_barrier();
+    // (dead lanes add 0: no change of the execution mask between the LDS instructions)
+    __hip_atomic_fetch_add(w, live ? 1u << (16 * (d & 1)) : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __builtin_amdgcn_wave_barrier();
+    after[it] = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __builtin_amdgcn_wave_barrier();
+  }
+  const unsigned long long below = (1ULL << lane) - 1ULL;
+#pragma unroll
+  for (int it = 0; it < kItems; ++it) {
+    const int d = digit_of(key[it], shift, 1 << bits);
+    const bool live = first + it * 64 < end;
+    const int c = (int)((before[it] >> (16 * (d & 1))) & 0xffffu);
+    const int n = (int)((after[it] >> (16 * (d & 1))) & 0xffffu) - c;
+    int r = c;
+    unsigned long long pend = __ballot(live && n > 1);   // lanes of collided groups
+    if (fallback && __popcll(pend) / 2 > bits) {
+      r = c + __popcll(digit_peers(d, live, bits) & below);
+    } else {
+      while (pend) {
+        const int leader = __ffsll((long long)pend) - 1;
+        const int dl = __builtin_amdgcn_readlane(d, leader);
+        const unsigned long long peers = __ballot(live && d == dl);
+        if (d == dl) r = c + __popcll(peers & below);
+        pend &= ~peers;
+      }
+    }
+    rank[it] = live ? r : 0;
+  }
+}
+// The ranks of the thread's keys (positions first + it * 64, live below end) by the form that `mode` (g_rank_mode) asks for.
+__device__ __forceinline__ void rank_keys(const uint32_t (&key)[kItems], int64_t first, int64_t end, int shift, int bits,
+                                          int mode, uint16_t* mine, int lane, int (&rank)[kItems]) {
+  if (mode == 1) {
+#pragma unroll
+    for (int it = 0; it < kItems; ++it) rank[it] = ballot_rank(key[it], first + it * 64 < end, shift, bits, mine, lane);
+  } else {
+    count_rank(key, first, end, shift, bits, mode == 0, mine, lane, rank);
+  }
 }
 // Once every wave has ranked its keys: digit totals of the tile -> exclusive scan over the digits (bins <= 1024 = 2 per
 // thread) -> tile_excl, the (wave, digit) starts (in place of the counts) and gbase from the tile's column (col /
@@ -220,6 +299,7 @@ struct Pass {
   int64_t nnz;
   int n_tiles;
   int shift, bits;
+  int rank;                    // g_rank_mode
   Gen gen;
 };
 
@@ -227,11 +307,13 @@ template <bool GEN>
 __global__ __launch_bounds__(kHistThreads) void hist_kernel(const Pass p) {
   __shared__ int h[kMaxBins];
   __shared__ GenLds g;
+  const uint32_t tile = tile_of_block(blockIdx.x, p.n_tiles);
+  if (tile >= (uint32_t)p.n_tiles) return;
   const int bins = 1 << p.bits;
   hist_zero(h, bins);
   if constexpr (GEN) load_gen(p.gen, p.nnz, g, kHistThreads);
   __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kTile;
+  const int64_t base = (int64_t)tile * kTile;
   bool bad = false;
   for (int it = 0; it < kHistItems; ++it) {
     const int64_t q = base + it * kHistThreads + threadIdx.x;
@@ -246,19 +328,21 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const Pass p) {
       hist_add(h, key, p.shift, bins);
     }
   }
-  hist_finish(h, bins, p.counts + blockIdx.x, p.n_tiles, bad, p.gen.err_flag);
+  hist_finish(h, bins, p.counts + tile, p.n_tiles, bad, p.gen.err_flag);
 }
 
 template <bool GEN>
 __global__ __launch_bounds__(kThreads) void scatter_kernel(const Pass p) {
   __shared__ TileLds<uint64_t> s;
   __shared__ GenLds g;
+  const uint32_t tile = tile_of_block(blockIdx.x, p.n_tiles);
+  if (tile >= (uint32_t)p.n_tiles) return;
   const int bins = 1 << p.bits;
   zero_counts(s);
   if constexpr (GEN) load_gen(p.gen, p.nnz, g, kThreads);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t tile0 = (int64_t)blockIdx.x * kTile;
+  const int64_t tile0 = (int64_t)tile * kTile;
   const int64_t first = tile0 + (int64_t)wave * (kTile / kWaves) + lane;
   uint32_t key[kItems];
   uint64_t val[kItems];
@@ -277,9 +361,9 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const Pass p) {
         val[it] = p.vals_in[q];
       }
     }
-    rank[it] = ballot_rank(key[it], live, p.shift, p.bits, s.cnt[wave], lane);
   }
-  digit_bases(s, bins, p.counts + blockIdx.x, p.n_tiles);
+  rank_keys(key, first, p.nnz, p.shift, p.bits, p.rank, s.cnt[wave], lane, rank);
+  digit_bases(s, bins, p.counts + tile, p.n_tiles);
   stage_tile(s, key, val, rank, first, p.nnz, p.shift, bins);
   const int n_here = (int)min<int64_t>(kTile, p.nnz - tile0);
 #pragma unroll
@@ -327,6 +411,7 @@ struct SegPass {
   int32_t* counts;
   int64_t nnz;
   int shift, bits, key_bits;
+  int rank;                    // g_rank_mode
   Gen gen;
   Seg seg;
 };
@@ -381,16 +466,19 @@ __device__ __forceinline__ bool seg_first_keys(const SegPass& p, const GenLds& g
 // (Round 5 measured one workgroup per EIGHT consecutive tiles here, so that a digit's counters leave as 32 contiguous bytes:
 //  the write counter of this kernel fell from 121 MB to 14 MB per launch -- one tile's 1024 counters are 1024 scattered
 //  4-byte stores into the [digit][tile] matrix -- and the plan got SLOWER, 558 -> 582 us with 1024-thread groups (1815 us
-//  with 256-thread ones): the partial-sector writes are absorbed by L2, the kernel wants its 3400 independent workgroups.)
+//  with 256-thread ones): the kernel wants its 3400 independent workgroups.  tile_of_block keeps them and puts the eight
+//  neighbouring columns into one L2 instead: 40 -> 26 us in the second pass.)
 template <bool FIRST>
 __global__ __launch_bounds__(kHistThreads) void hist_seg_kernel(const SegPass p) {
   __shared__ int h[kMaxBins];
   __shared__ GenLds g;
+  const uint32_t tile = tile_of_block(blockIdx.x, p.seg.tile_start[p.seg.n]);
+  if (tile >= p.seg.tile_start[p.seg.n]) return;
   const int bins = 1 << p.bits;
   hist_zero(h, bins);
   if constexpr (FIRST) load_gen(p.gen, p.nnz, g, kHistThreads);
   __syncthreads();
-  const SegTile t = seg_tile(p, blockIdx.x);
+  const SegTile t = seg_tile(p, tile);
   const int64_t first = t.t0 + threadIdx.x;
   bool bad = false;
   uint32_t key[kHistItems];
@@ -411,12 +499,14 @@ template <bool FIRST, bool LAST>
 __global__ __launch_bounds__(kThreads) void scatter_seg_kernel(const SegPass p) {
   __shared__ TileLds<uint32_t> s;   // the payload is the lookup's position
   __shared__ GenLds g;
+  const uint32_t tile = tile_of_block(blockIdx.x, p.seg.tile_start[p.seg.n]);
+  if (tile >= p.seg.tile_start[p.seg.n]) return;
   const int bins = 1 << p.bits;
   zero_counts(s);
   if constexpr (FIRST || LAST) load_gen(p.gen, p.nnz, g, kThreads);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const SegTile t = seg_tile(p, blockIdx.x);
+  const SegTile t = seg_tile(p, tile);
   const int64_t first = t.t0 + (int64_t)wave * (kTile / kWaves) + lane;
   uint32_t key[kItems], pos[kItems];
   int rank[kItems];
@@ -437,8 +527,8 @@ __global__ __launch_bounds__(kThreads) void scatter_seg_kernel(const SegPass p) 
   for (int it = 0; it < kItems; ++it) {
     const bool live = first + it * 64 < t.end;
     if (!live) { key[it] = 0xffffffffu; pos[it] = 0; }
-    rank[it] = ballot_rank(key[it], live, p.shift, p.bits, s.cnt[wave], lane);
   }
+  rank_keys(key, first, t.end, p.shift, p.bits, p.rank, s.cnt[wave], lane, rank);
   digit_bases(s, bins, t.col, t.stride);
   stage_tile(s, key, pos, rank, first, t.end, p.shift, bins);
   const int n_here = (int)(t.end - t.t0);
@@ -669,7 +759,7 @@ bool plan_sort_by_table(const PlanLayout& l, const rs::Temp& tmp, const rs::Gen&
   const unsigned bits = rs::key_bits(max_vocab);
   if (bits > 31) return false;
   const rs::Schedule sch = rs::pass_schedule(bits);
-  sp.counts = tmp.counts; sp.nnz = nnz; sp.key_bits = (int)bits;
+  sp.counts = tmp.counts; sp.nnz = nnz; sp.key_bits = (int)bits; sp.rank = g_rank_mode;
   sp.gen = gen;
   // intermediate (key, position) pairs ping-pong between I0 = (keys_in, vals_in as u32) and I1 = (keys_sorted,
   // vals_sorted as u32); the LAST pass reads I0 and writes the final (keys_sorted, vals_sorted): the pass before it
@@ -687,13 +777,13 @@ bool plan_sort_by_table(const PlanLayout& l, const rs::Temp& tmp, const rs::Gen&
     sp.keys_out = last ? l.keys_sorted : (out_is_i0 ? k0 : k1);
     sp.pos_out = last ? nullptr : (out_is_i0 ? q0 : q1);
     sp.vals_out = last ? l.vals_sorted : nullptr;
-    if (first) hipLaunchKernelGGL(rs::hist_seg_kernel<true>, dim3(tiles), dim3(rs::kHistThreads), 0, st, sp);
-    else hipLaunchKernelGGL(rs::hist_seg_kernel<false>, dim3(tiles), dim3(rs::kHistThreads), 0, st, sp);
+    if (first) hipLaunchKernelGGL(rs::hist_seg_kernel<true>, dim3(rs::tile_grid(tiles)), dim3(rs::kHistThreads), 0, st, sp);
+    else hipLaunchKernelGGL(rs::hist_seg_kernel<false>, dim3(rs::tile_grid(tiles)), dim3(rs::kHistThreads), 0, st, sp);
     scan::exclusive(tmp.counts, tmp.counts, (int64_t)(1 << sp.bits) * tiles, tmp.sums, nullptr, st);
-    if (first && last) hipLaunchKernelGGL((rs::scatter_seg_kernel<true, true>), dim3(tiles), dim3(rs::kThreads), 0, st, sp);
-    else if (first) hipLaunchKernelGGL((rs::scatter_seg_kernel<true, false>), dim3(tiles), dim3(rs::kThreads), 0, st, sp);
-    else if (last) hipLaunchKernelGGL((rs::scatter_seg_kernel<false, true>), dim3(tiles), dim3(rs::kThreads), 0, st, sp);
-    else hipLaunchKernelGGL((rs::scatter_seg_kernel<false, false>), dim3(tiles), dim3(rs::kThreads), 0, st, sp);
+    if (first && last) hipLaunchKernelGGL((rs::scatter_seg_kernel<true, true>), dim3(rs::tile_grid(tiles)), dim3(rs::kThreads), 0, st, sp);
+    else if (first) hipLaunchKernelGGL((rs::scatter_seg_kernel<true, false>), dim3(rs::tile_grid(tiles)), dim3(rs::kThreads), 0, st, sp);
+    else if (last) hipLaunchKernelGGL((rs::scatter_seg_kernel<false, true>), dim3(rs::tile_grid(tiles)), dim3(rs::kThreads), 0, st, sp);
+    else hipLaunchKernelGGL((rs::scatter_seg_kernel<false, false>), dim3(rs::tile_grid(tiles)), dim3(rs::kThreads), 0, st, sp);
   }
   return true;
 }
@@ -724,6 +814,7 @@ int plan_sort_global(const PlanLayout& l, const rs::Temp& tmp, const rs::Gen& ge
   p.nnz = nnz;
   p.n_tiles = (int)ceil_div(nnz, rs::kTile);
   p.counts = tmp.counts;
+  p.rank = g_rank_mode;
   p.gen = gen;
   for (int ps = 0; ps < sch.passes; ++ps) {
     p.bits = sch.bits[ps];
@@ -733,11 +824,11 @@ int plan_sort_global(const PlanLayout& l, const rs::Temp& tmp, const rs::Gen& ge
     p.vals_in = generating ? nullptr : (to_sorted ? l.vals_in : l.vals_sorted);
     p.keys_out = to_sorted ? l.keys_sorted : l.keys_in;
     p.vals_out = to_sorted ? l.vals_sorted : l.vals_in;
-    if (generating) hipLaunchKernelGGL(rs::hist_kernel<true>, dim3(p.n_tiles), dim3(rs::kHistThreads), 0, st, p);
-    else hipLaunchKernelGGL(rs::hist_kernel<false>, dim3(p.n_tiles), dim3(rs::kHistThreads), 0, st, p);
+    if (generating) hipLaunchKernelGGL(rs::hist_kernel<true>, dim3(rs::tile_grid((unsigned)p.n_tiles)), dim3(rs::kHistThreads), 0, st, p);
+    else hipLaunchKernelGGL(rs::hist_kernel<false>, dim3(rs::tile_grid((unsigned)p.n_tiles)), dim3(rs::kHistThreads), 0, st, p);
     scan::exclusive(tmp.counts, tmp.counts, (int64_t)(1 << p.bits) * p.n_tiles, tmp.sums, nullptr, st);
-    if (generating) hipLaunchKernelGGL(rs::scatter_kernel<true>, dim3(p.n_tiles), dim3(rs::kThreads), 0, st, p);
-    else hipLaunchKernelGGL(rs::scatter_kernel<false>, dim3(p.n_tiles), dim3(rs::kThreads), 0, st, p);
+    if (generating) hipLaunchKernelGGL(rs::scatter_kernel<true>, dim3(rs::tile_grid((unsigned)p.n_tiles)), dim3(rs::kThreads), 0, st, p);
+    else hipLaunchKernelGGL(rs::scatter_kernel<false>, dim3(rs::tile_grid((unsigned)p.n_tiles)), dim3(rs::kThreads), 0, st, p);
     to_sorted = !to_sorted;
   }
   return KRS_OK;

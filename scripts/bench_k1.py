@@ -109,9 +109,19 @@ if not a.fmajor_out:
     grad = (torch.rand(a.batch, a.tables * a.dim, device=dev) * 1e-3).to(dt)
     nnz = ids.numel()
     from keras_rs_amd import _lib as L
+    # the same bags as CSR offsets (krs_embed_bag_bwd_plan: key kernel + global sort, every pass reads its pairs from memory)
+    offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(np.repeat(hots, a.batch))]).astype(np.int32)).to(dev)
     for pv in (1, 0, 1, 0):          # KRS_EMBED_OPT_PLAN: 1 = global sort, 0 = table-segmented sort
         L.check(L.lib().krs_embed_set_option(2, pv), "set_option")
-        print(json.dumps({"plan_variant": pv, "k2_plan_us": timeit(lambda: fb.plan_backward(ids, a.batch, hots=hots, global_order=False)) * 1e6}))
+        for rk in (1, 0):            # KRS_EMBED_OPT_RANK: 1 = ballots per digit bit, 0 = LDS counts (ballots per collided round)
+            if L.lib().krs_embed_set_option(4, rk) != 0:    # (an older library loaded through KRS_LIB: ballots only)
+                if rk == 0:
+                    continue
+                rk = None
+            print(json.dumps({"plan_variant": pv, "rank": rk, "k2_plan_us": timeit(lambda: fb.plan_backward(ids, a.batch, hots=hots, global_order=False)) * 1e6}))
+            if pv == 1:
+                print(json.dumps({"plan_variant": "csr", "rank": rk, "k2_plan_us": timeit(lambda: fb.plan_backward(ids, a.batch, offsets=offsets)) * 1e6}))
+    L.lib().krs_embed_set_option(4, 0)
     t_plan = timeit(lambda: fb.plan_backward(ids, a.batch, hots=hots, global_order=False))
     ws = fb.plan_backward(ids, a.batch, hots=hots, global_order=False)
     for _ in range(2):

@@ -312,8 +312,9 @@ int krs_gemm(const void* a, int64_t lda, int a_is_km,
 /* Bytes of `workspace` a krs_gemm call of this shape needs (0 = none): split-K products keep one fp32 [M, N] slab per
  * split and reduce them in a fixed order (deterministic, no atomics) -- the weight-gradient contractions over the batch
  * (a_is_km), and since round 5 K-contiguous products whose output is too small for 256 x 256 tiles to fill the chip but
- * whose K is long (M = 8192 against N = 512, K = 3456: the per-rank products of a strongly-scaled job).  A call with less
- * workspace than this returns KRS_ERR_WORKSPACE. */
+ * whose K is long (M = 8192 against N = 512, K = 3456: the per-rank products of a strongly-scaled job).  The figure is the
+ * largest need over the input dtypes and B layouts (which the query does not see): enough for every call of this shape.  A
+ * split call with less workspace than ITS need returns KRS_ERR_WORKSPACE. */
 size_t krs_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k, int a_is_km);
 
 /* Data-gradient product of a cross layer FUSED with the elementwise backward of the cross layer below it in a stack
@@ -362,6 +363,15 @@ int krs_gemm_dense_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb, 
  * Lets tests prove which path they exercised. */
 enum { KRS_CROSS_BWD_NONE = 0, KRS_CROSS_BWD_TWO_CALL = 1, KRS_CROSS_BWD_PP64 = 2, KRS_CROSS_BWD_PP256 = 3 };
 int krs_gemm_cross_bwd_last_route(int* epilogue);
+/* Diagnostic, host only, no GPU needed: the route krs_gemm_cross_bwd WOULD take for these arguments (those of
+ * krs_gemm_cross_bwd up to `dtype`, without fold_direct, dbias and act, which no route depends on) under the pipeline option
+ * in force; x0 == NULL asks for the dense form, krs_gemm_dense_bwd with y = u.  Pointer values are read for their alignment
+ * only; nothing is dereferenced or launched and the last-route record is untouched.  Returns KRS_CROSS_BWD_* (or a negative
+ * krs_status for arguments the entry refuses); *epilogue (if not NULL) receives the fused epilogue number, else 0. */
+int krs_gemm_cross_bwd_plan_route(const void* a, int64_t lda, const void* bt, int64_t ldb, const void* r, int64_t ldr,
+                                  float beta, void* g_out, int64_t ldg, const void* x0, const void* u, void* dz, void* dx0,
+                                  int64_t ld, int dx0_accumulate, const void* u_upper, int64_t m, int64_t n, int64_t k,
+                                  int dtype, int* epilogue);
 
 /* Diagnostic, host only: where the CALLING THREAD's last krs_gemm ran.  Every field is 0 when there was no call yet, the
  * call was refused (any return other than KRS_OK) or had nothing to do (m == 0 or n == 0).
@@ -393,6 +403,15 @@ typedef struct krs_gemm_route {
   int32_t thin_is_a;
 } krs_gemm_route;
 int krs_gemm_last_route(krs_gemm_route* route);
+/* Diagnostic, host only, no GPU needed: where a krs_gemm with these arguments (krs_gemm's, without the workspace pointer
+ * and the stream) WOULD run under the pipeline option in force.  The decision is a pure function of sizes, strides, dtypes,
+ * the 16-byte alignment of the pointer VALUES and the epilogue struct (read from host memory); no operand is dereferenced,
+ * no HIP call is made and the last-route record is untouched.  Fills *route (all zero when nothing would be launched) and
+ * returns what krs_gemm returns before its first launch: KRS_OK, KRS_ERR_INVALID, KRS_ERR_WORKSPACE (a split product with
+ * fewer than its slab bytes) or KRS_ERR_UNSUPPORTED (a grid beyond the launch limits). */
+int krs_gemm_plan_route(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb, int b_is_nk, const void* c,
+                        int64_t ldc, int64_t m, int64_t n, int64_t k, int in_dtype, int out_dtype,
+                        const krs_gemm_epilogue* epilogue, size_t workspace_bytes, krs_gemm_route* route);
 
 /* Tuning / diagnostic switches of krs_gemm (process-wide; results never depend on them).
  *   KRS_GEMM_OPT_PIPELINE: 4 = the big bf16 shapes run the four-stage ping-pong ring on 256x256 tiles (default, or

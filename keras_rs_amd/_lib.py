@@ -88,7 +88,10 @@ PROTOTYPES = {
                                 _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
     "krs_gemm_dense_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
     "krs_gemm_cross_bwd_last_route": (_I, [_P]),
+    "krs_gemm_cross_bwd_plan_route": (_I, [_P, _I64, _P, _I64, _P, _I64, _F, _P, _I64, _P, _P, _P, _P, _I64, _I, _P, _I64,
+                                           _I64, _I64, _I, _P]),
     "krs_gemm_last_route": (_I, [_P]),
+    "krs_gemm_plan_route": (_I, [_P, _I64, _I, _P, _I64, _I, _P, _I64, _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
     "krs_gemm_set_option": (_I, [_I, _I]),
     "krs_embed_set_option": (_I, [_I, _I]),
     "krs_colsum_workspace_bytes": (_SZ, [_I64, _I64]),

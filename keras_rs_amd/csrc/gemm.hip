@@ -10,40 +10,34 @@
 // the layer needs (forward, data gradient, weight gradient).  MFMA throughout:
 // v_mfma_f32_32x32x16_bf16 (bf16) / v_mfma_f32_32x32x2_f32 (fp32, exact fmaf chain), fp32
 // accumulators in registers, a lane's operand = 16 bytes of LDS.  Kernels, by shape:
-//   * gemm_pp64_kernel      (round 6) the big K-contiguous bf16 products -- h = x U, dh = dz K^T, the cross / residual /
-//                           fused-backward forms -- whenever K is whole 64-k blocks: gemm_pp256_kernel's tile and ping-pong
-//                           on 64-k pieces whose rows are whole 128-byte lines, five 32 KB slots, the LDS-DMA instructions
-//                           issued among the MFMAs (h 204 -> 189 us, dh 214 -> 193, cross product 455 -> 430; bit-identical);
+//   * gemm_pp64_kernel      the big K-contiguous bf16 products -- h = x U, dh = dz K^T, the cross / residual / fused-backward
+//                           forms -- whenever K is whole 64-k blocks: gemm_pp256_kernel's tile and ping-pong on 64-k pieces
+//                           whose rows are whole 128-byte lines, five 32 KB slots, LDS-DMA issued among the MFMAs;
 //   * gemm_pp256_kernel     the weight gradients (K-strided operands) and the K-contiguous shapes gemm_pp64_kernel does not
-//                           take: the 256x256 tile (8 waves as
-//                           2(M) x 4(N), 128x64 per wave) on a four-stage LDS-DMA ring (global_load_lds, XOR swizzle on
-//                           the source side), ping-pong wave groups, counted vmcnt, epilogue operands fetched under the
-//                           tail of the main loop; bit-identical to the 128x128 two-stage kernels below, which every
-//                           shape takes under pipeline 0 of krs_gemm_set_option.  (The 256x256 two-stage kernels of
-//                           round 1, gemm_glds256_kernel / gemm_tn_glds256_kernel, were deleted in round 5: 222-230 ->
-//                           204 us and 276 -> 208-220 us against the ring, profiles/archive/r2_gemm_ab.txt.)
+//                           take: the 256x256 tile (8 waves as 2(M) x 4(N), 128x64 per wave) on a four-stage LDS-DMA ring
+//                           (global_load_lds, XOR swizzle on the source side), ping-pong wave groups, counted vmcnt, epilogue
+//                           operands fetched under the tail of the main loop; bit-identical to the 128x128 two-stage kernels
+//                           below, which every shape takes under pipeline 0 of krs_gemm_set_option;
 //   * gemm_glds_kernel      two 32 KB stages filled by LDS-DMA on a 128x128 tile for smaller M / N (K >= 1024);
-//   * gemm_tn_glds_kernel
-//                           bf16 weight gradients (both operands K-strided): tiles DMA'd as they
-//                           lie in memory, fragments by the transposing ds_read_b64_tr_b16,
-//                           split along K into fp32 slabs (one split per XCD at a time) that are
-//                           reduced in a fixed order (deterministic, no atomics);
-//   * gemm_mfma_kernel      every other aligned shape: global -> register -> LDS staging
-//                           (K-strided operands transposed in registers), one 36 KB buffer,
-//                           three workgroups per CU;
+//   * gemm_tn_glds_kernel   bf16 weight gradients (both operands K-strided): tiles DMA'd as they lie in memory, fragments by
+//                           the transposing ds_read_b64_tr_b16, split along K into fp32 slabs (one split per XCD at a time)
+//                           that are reduced in a fixed order (deterministic, no atomics);
+//   * gemm_mfma_kernel      every other aligned shape: global -> register -> LDS staging (K-strided operands transposed in
+//                           registers), one 36 KB buffer, three workgroups per CU;
 //   * gemm_thin_kernel      weight gradients with min(M, N) <= 16 (13 dense inputs, 1 unit);
 //   * gemm_rowdot_kernel / gemm_smallk_kernel   N <= 8 / K <= 16 with a row-major A (the 1-unit and 13-input Dense layers);
 //   * gemm_generic_kernel   anything else (the reference's toy shapes, d = 3).
-// Epilogue on the accumulator, staged through LDS so that a lane owns 8 consecutive columns:
-// + bias, activation, cross (x0*(v+diag*x)+x), + beta*R, one rounding to the output dtype; the
-// cross / residual forms stream x0 / x / R / u / y with non-temporal accesses.
-// What bounds these products on MI355X is the L2 -> LDS operand path, not MFMA issue (DESIGN.md
+// Epilogue on the accumulator, staged through LDS so that a lane owns 8 consecutive columns: + bias, activation, cross
+// (x0*(v+diag*x)+x), + beta*R, one rounding to the output dtype; the cross / residual forms stream x0 / x / R / u / y with
+// non-temporal accesses.  What bounds these products on MI355X is the L2 -> LDS operand path, not MFMA issue (DESIGN.md
 // section 3, scripts/exp/gemm_probe.hip): hence the large tiles.
+// Which kernel a call gets is decided in gemm_plan.h, a pure host function of the call (every threshold is named there,
+// once); the host code at the end of this file validates, plans and launches what the plan names.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 
+#include "gemm_plan.h"
 #include "krs_dense_common.h"
 
 namespace krs {
@@ -53,10 +47,10 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BM = 128, BN = 128;
-constexpr int ROW_BYTES = 128;          // K extent of a tile row in bytes (64 bf16 / 32 fp32)
-constexpr int LDS_STRIDE = ROW_BYTES + 16;
-constexpr int TILE_BYTES = BM * LDS_STRIDE;  // one operand tile (BM == BN)
+constexpr int BM = gplan::kTile, BN = gplan::kTile;
+constexpr int ROW_BYTES = gplan::kRowBytes;  // K extent of a tile row in bytes (64 bf16 / 32 fp32)
+constexpr int LDS_STRIDE = gplan::kLdsStride;
+constexpr int TILE_BYTES = gplan::kTileBytes;  // one operand tile (BM == BN)
 
 struct GemmParams {
   const char* a; int64_t lda; int a_km;
@@ -1416,7 +1410,6 @@ __global__ __launch_bounds__(512) void gemm_pp64_kernel(const GemmParams p, int 
 // MFMA tiles do not apply and one thread per output would walk K = batch alone; here a thread owns
 // one column of the WIDE operand (coalesced across the workgroup), the THIN operand's rows are
 // staged in LDS and broadcast, K is split over blockIdx.y into fp32 slabs (fixed-order reduce).
-constexpr int kThinMax = 16;
 // ES: operand element size (2 = bf16, 4 = fp32); NT: thin extent rounded up to 1 / 4 / 8 / 16 (the LDS rows are
 // read as float4).  Eight rows of the wide operand are requested before they are consumed (the first version
 // walked its 1024 rows one dependent load at a time behind a run-time dtype switch: 394 us for the 13 x 512 gradient).
@@ -1651,70 +1644,6 @@ int gemm_pipe() {
   return g_pipe;
 }
 
-// Split-K factor.  Weight-gradient shapes that take the 256x256 tiles (a_is_km, M, N >= 256, long K): the
-// factor that minimises  rounds over the 256 CUs x (K per split + per-workgroup overhead) + slab traffic
-// -- 2 x 14 tiles of the C3 weight gradients: 9 splits = 252 workgroups in ONE round (16 splits were 448
-// workgroups = 1.75 rounds, and 113 MB of slabs instead of 64).
-// `ring_ok`: the product can take the ring kernel's split-K form (bf16, B as [N, K]) -- the third branch hands
-// out splits for that kernel only; the workspace query leaves it true (an upper bound for every dtype / layout).
-int pick_splits(int64_t m, int64_t n, int64_t k, int a_is_km, bool ring_ok = true) {
-  if (a_is_km && k >= 1024 && std::min(m, n) <= 16) {   // gemm_thin_kernel: >= 512 rows of K per split, <= 128 splits
-    const int64_t s = k / 512;                            // (256 splits made the slab reduction the longer kernel,
-    return (int)(s > 128 ? 128 : s);                      //  64 left half of the CUs without a workgroup)
-  }
-  if (a_is_km && m >= 256 && n >= 256 && k % 64 == 0 && k >= 4096) {
-    const int64_t t256 = ceil_div(m, 256) * ceil_div(n, 256);
-    const double slab = (double)m * (double)n * 6.45e-5;   // slab write + read of one split, in units of one k step of a tile
-    double best = 0;
-    int best_s = 1;
-    for (int s = 1; s <= 64 && k / s >= 512; ++s) {
-      const int64_t kps = ceil_div(ceil_div(k, s), 64) * 64;
-      if ((int64_t)(s - 1) * kps >= k) continue;          // the last split would be empty
-      const double cost = (double)ceil_div(t256 * s, 256) * (double)(kps + 256) + (s > 1 ? slab * s : 0.0);
-      if (s == 1 || cost < best) { best = cost; best_s = s; }
-    }
-    return best_s;
-  }
-  // K-contiguous products whose output is too small for 256x256 tiles to fill the chip (M = 8192 against N = 512: 64 tiles)
-  // but whose K is long: the ring kernel with the K range dealt to s workgroups per tile -- half the operand bytes per flop
-  // of the 128x128 kernel that ran these shapes until round 5, at the price of s fp32 slabs (h = x U at M = 8192: 59 -> 4x us,
-  // DESIGN.md section 4).  s * tiles ~ 256 workgroups, >= 512 of K per split, whole 32-k blocks.
-  if (ring_ok && !a_is_km && m >= 256 && n >= 256 && k >= 2048 && k % 32 == 0) {
-    const int64_t t256 = ceil_div(m, 256) * ceil_div(n, 256);
-    if (t256 < 192) {
-      // (krs_gemm rounds the K per split up to whole 64-k tiles: the last split takes what is left, and must still hold
-      //  a ring's depth of 32-k blocks)
-      int64_t s = 256 / t256;
-      auto fits = [&](int64_t q) {
-        const int64_t kps = ceil_div(ceil_div(k, q), 64) * 64, last = k - (q - 1) * kps;
-        return k / q >= 512 && last >= 128 && last % 32 == 0;
-      };
-      while (s > 1 && !fits(s)) --s;
-      if (s > 1) return (int)s;
-    }
-  }
-  const int64_t tiles = ceil_div(m, BM) * ceil_div(n, BN);
-  if (tiles >= 256 || k < 4096) return 1;
-  int64_t s = ceil_div(1024, tiles);       // aim at ~4 workgroups per CU
-  const int64_t max_s = k / 1024;          // keep >= 1024 of K per split
-  if (s > max_s) s = max_s;
-  if (s > 64) s = 64;
-  if (s > 8) s = (s + 7) / 8 * 8;          // whole rounds over the 8 XCDs (gemm_tn_glds_kernel deals splits to XCDs)
-  if (s > max_s) s = max_s / 8 * 8;
-  return s < 1 ? 1 : (int)s;
-}
-
-bool mfma_eligible(const GemmParams& p, int es) {
-  const int64_t va = 16 / es;  // elements per 16-byte vector
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al(p.a) || !al(p.b)) return false;
-  if (p.lda % va || p.ldb % va) return false;
-  // the vector-loaded axis must be a multiple of the vector length
-  if (p.a_km ? (p.m % va) : (p.k % va)) return false;
-  if (p.b_nk ? (p.k % va) : (p.n % va)) return false;
-  return p.m >= 1 && p.n >= 1 && p.k >= 1;
-}
-
 // Launches Kern with `lds` bytes of dynamic LDS.  The kernel's dynamic-LDS limit is raised on its first launch: a
 // function-local static, initialised once per kernel (and thread-safe).  `what` names the launch in error messages.
 template <auto Kern, class... Args>
@@ -1737,89 +1666,6 @@ int with_epilogue(int e, F&& f) {
   return f(std::integral_constant<int, First>());
 }
 
-// (`rt`: the route record of krs_gemm_last_route -- kernel family and epilogue build are noted here, host side only)
-template <int ES>
-int launch_mfma(const GemmParams& p, hipStream_t st, krs_gemm_route& rt) {
-  const int64_t mt = p.a_km ? ceil_div(p.m, BM) : ceil_div(ceil_div(p.m, BM), 8) * 8;
-  const dim3 grid((unsigned)(mt * ceil_div(p.n, BN)), 1, (unsigned)p.splits);
-  const size_t lds = 2 * TILE_BYTES;
-  // specialised epilogues: bf16 output, vector access everywhere, no split-K
-  int epi = 0;
-  if (p.has_ep && p.ep_vec && p.splits == 1 && p.out_dtype == KRS_BF16 && p.n >= 8) {
-    if (p.ep.x0 && !p.ep.r) epi = 1;
-    else if (p.ep.r && !p.ep.x0 && !p.ep.bias && p.ep.act == KRS_ACT_NONE) epi = 2;
-  }
-  if (p.a_km && p.b_nk) return fail(KRS_ERR_UNSUPPORTED, "krs_gemm: A^T . B^T layout is not used by the layer");
-  // Long contractions: the LDS-DMA pipeline (no staging registers, no ds_write traffic).  Short ones
-  // (K = 512: eight tiles, then a heavy epilogue) run better on the register-staged kernel, whose
-  // 36 KB of LDS lets three workgroups share a CU and hide each other's epilogues.
-  const bool dma_ok = !p.a_km && p.b_nk && p.splits == 1 && p.k % (ROW_BYTES / ES) == 0;
-  // split-K on the ring kernel (round 5): K-contiguous bf16 operands, every split a whole number of 32-k blocks and at
-  // least a ring's depth of them (pick_splits' nt branch hands out exactly such splits)
-  const bool ring_split = ES == 2 && !p.a_km && p.b_nk && p.splits > 1 && p.k % 32 == 0 && p.k_per_split % 32 == 0 &&
-                          p.k - (int64_t)(p.splits - 1) * p.k_per_split >= 128 && gemm_pipe() != 0;
-  // development switch: 128 x 128 tiles at two workgroups per CU for every LDS-DMA shape (y = cross(h V): 474 us against 429)
-  static const bool force128 = getenv("KRS_GEMM_FORCE128") != nullptr;
-  const bool use_glds = dma_ok && (p.k >= 1024 || force128);
-  // ... provided its 4x larger tiles still cover most of the 256 CUs (a per-rank batch of 8192 rows against
-  // N = 512 is 64 such tiles: the 128x128 kernels below launch 256 workgroups instead)
-  const bool fills256 = ceil_div(p.m, 256) * ceil_div(p.n, 256) >= 192;
-  if constexpr (ES == 2) {
-    // the ring kernel (gemm_pp256_kernel); krs_gemm_set_option(KRS_GEMM_OPT_PIPELINE, 0) sends these shapes to the 128x128
-    // two-stage kernels below instead (same fragment layout, same k order per accumulator: bit-identical results -- the
-    // reference schedule of tests/test_dense_ops_gpu.py and scripts/exp/gemm_bench)
-    if (((dma_ok && fills256) || ring_split) && gemm_pipe() != 0 && p.k >= 256 && p.k % 32 == 0 && p.m >= 256 && p.n >= 256 &&
-        !force128) {
-      const dim3 grid256((unsigned)(ceil_div(ceil_div(p.m, 256), 8) * 8 * ceil_div(p.n, 256) * p.splits));
-      const int nt_ = (int)ceil_div(p.n, 256);
-      rt.epilogue = epi;
-      // (the residual-add form with a short K -- dx = dh U^T + g -- was 4 % faster on a two-stage loop until its R
-      // operands were fetched under the ring's tail: 340 -> 301 us)
-      // whole 64-k blocks of both operands and of every split, at least three of them -> the 64-k ring (pipeline 5: never)
-      const bool k64 = gemm_pipe() == 4 && p.k % 64 == 0 && p.k_per_split % 64 == 0 &&
-                       p.k - (int64_t)(p.splits - 1) * p.k_per_split >= 192;
-      rt.kernel = k64 ? KRS_GEMM_KERNEL_PP64 : KRS_GEMM_KERNEL_PP256;
-      return with_epilogue<0, 2>(epi, [&](auto E) {
-        return k64 ? launch_lds<gemm_pp64_kernel<E>>("gemm_pp64_kernel", grid256, dim3(512), pp64::NSLOT * pp64::SLOT, st,
-                                                     p, nt_)
-                   : launch_lds<gemm_pp256_kernel<false, 4, E>>("gemm_pp256_kernel", grid256, dim3(512), 4 * pp::STAGE, st,
-                                                                p, 0, nt_);
-      });
-    }
-  }
-  if (use_glds) {
-    const size_t glds_lds = 4 * BM * ROW_BYTES;  // 2 stages x (A + B) x 16 KB
-    rt.kernel = KRS_GEMM_KERNEL_GLDS; rt.epilogue = epi;
-    return with_epilogue<0, 2>(epi, [&](auto E) {
-      return launch_lds<gemm_glds_kernel<ES, E>>("gemm_glds_kernel", grid, dim3(256), glds_lds, st, p);
-    });
-  }
-  // bf16 weight gradients: LDS-DMA + transposing reads (K extents in whole 64-row tiles, >= 8 columns)
-  if (ES == 2 && p.a_km && !p.b_nk && p.k % 64 == 0 && p.k_per_split % 64 == 0 && p.m >= 8 && p.n >= 8 &&
-      p.m % 8 == 0 && p.n % 8 == 0) {
-    // development switch: the 128 x 128 twin (4 waves, <= 128 VGPRs, 64 KB of LDS: half a CU) for every shape
-    static const bool tn128 = getenv("KRS_GEMM_TN128") != nullptr;
-    if (p.m >= 256 && p.n >= 256 && !tn128 && gemm_pipe() != 0 && p.k_per_split >= 256) {
-      const int mt_ = (int)ceil_div(p.m, 256), nt_ = (int)ceil_div(p.n, 256);
-      const dim3 grid_tn((unsigned)(ceil_div((int64_t)p.splits * mt_ * nt_, 8) * 8));
-      rt.kernel = KRS_GEMM_KERNEL_PP256_KSTRIDED;
-      return launch_lds<gemm_pp256_kernel<true, 4, 0>>("gemm_pp256_kernel (K-strided operands)", grid_tn, dim3(512),
-                                                       4 * pp::STAGE, st, p, mt_, nt_);
-    }
-    const int mt_ = (int)ceil_div(p.m, BM), nt_ = (int)ceil_div(p.n, BN);
-    const dim3 grid_tn((unsigned)(ceil_div(p.splits, 8) * 8 * mt_ * nt_));
-    const size_t lds_tn = 4 * 64 * 128 * 2;  // 2 stages x (A + B) x 16 KB
-    rt.kernel = KRS_GEMM_KERNEL_TN_GLDS;
-    return launch_lds<gemm_tn_glds_kernel<0>>("gemm_tn_glds_kernel", grid_tn, dim3(256), lds_tn, st, p, mt_, nt_);
-  }
-  rt.kernel = KRS_GEMM_KERNEL_MFMA; rt.epilogue = epi;
-  return with_epilogue<0, 2>(epi, [&](auto E) {
-    if (p.a_km) return launch_lds<gemm_mfma_kernel<ES, true, false, E>>("gemm_mfma_kernel", grid, dim3(256), lds, st, p);
-    if (p.b_nk) return launch_lds<gemm_mfma_kernel<ES, false, true, E>>("gemm_mfma_kernel", grid, dim3(256), lds, st, p);
-    return launch_lds<gemm_mfma_kernel<ES, false, false, E>>("gemm_mfma_kernel", grid, dim3(256), lds, st, p);
-  });
-}
-
 }  // namespace
 }  // namespace krs
 
@@ -1835,136 +1681,130 @@ extern "C" int krs_gemm_set_option(int key, int value) {
 }
 
 extern "C" size_t krs_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k, int a_is_km) {
-  if (m <= 0 || n <= 0 || k <= 0) return 0;
-  const int s = pick_splits(m, n, k, a_is_km);
-  return s > 1 ? (size_t)s * (size_t)m * (size_t)n * sizeof(float) : 0;
+  return gplan::plan_workspace_bytes(m, n, k, a_is_km != 0);
 }
 
 namespace krs {
 namespace {
+static_assert(gplan::kRingLds == 4 * pp::STAGE && gplan::kRing64Lds == pp64::NSLOT * pp64::SLOT, "the planner's LDS bytes");
+
 // where the calling thread's last krs_gemm ran (krs_gemm_last_route): cleared when gemm_run starts, written when it has
 // queued its last kernel, so a refused call and an empty product leave "none"
 thread_local krs_gemm_route g_route = {};
 
-// krs_gemm's body.  `allow_split` false = one pass over K whatever pick_splits would choose (the two-call form of
-// krs_gemm_cross_bwd, whose workspace is sized for the column sums only).
+bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+// krs_gemm's argument checks, then the call's plan (gemm_plan.h); a refused plan leaves its message.  Host memory only:
+// pointer VALUES are read for their alignment, the epilogue struct is read, no operand is dereferenced.
+int gemm_plan(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb, int b_is_nk, const void* c, int64_t ldc,
+              int64_t m, int64_t n, int64_t k, int in_dtype, int out_dtype, const krs_gemm_epilogue* ep,
+              size_t workspace_bytes, bool allow_split, gplan::GemmCall& call, gplan::GemmPlan& pl) {
+  KRS_REQUIRE(a && b && c, "krs_gemm: null operand");
+  KRS_REQUIRE(m >= 0 && n >= 0 && k >= 0, "krs_gemm: negative size");
+  KRS_REQUIRE((in_dtype == KRS_F32 || in_dtype == KRS_BF16) && (out_dtype == KRS_F32 || out_dtype == KRS_BF16),
+              "krs_gemm: bad dtype");
+  if (ep && ep->x0) KRS_REQUIRE(ep->x, "krs_gemm: cross epilogue needs x with x0");
+  static const bool tn128 = getenv("KRS_GEMM_TN128") != nullptr;
+  call = gplan::GemmCall();
+  call.m = m; call.n = n; call.k = k; call.a_km = a_is_km != 0; call.b_nk = b_is_nk != 0;
+  call.es = in_dtype == KRS_BF16 ? 2 : 4; call.out_dtype = out_dtype;
+  call.lda = lda; call.ldb = ldb; call.ldc = ldc; call.al_a = al16(a); call.al_b = al16(b); call.al_c = al16(c);
+  if (ep) {
+    call.has_ep = true; call.act = ep->act; call.bias = ep->bias != nullptr; call.al_bias = al16(ep->bias);
+    call.x0 = ep->x0 != nullptr; call.al_x0 = al16(ep->x0); call.al_x = al16(ep->x); call.ldx = ep->ldx;
+    call.u_out = ep->u_out != nullptr; call.al_u = al16(ep->u_out); call.ldu = ep->ldu;
+    call.r = ep->r != nullptr; call.al_r = al16(ep->r); call.ldr = ep->ldr;
+  }
+  call.workspace_bytes = workspace_bytes; call.allow_split = allow_split; call.pipe = gemm_pipe(); call.tn128 = tn128;
+  pl = gplan::plan_gemm(call);
+  if (pl.status == KRS_ERR_WORKSPACE)
+    return fail(pl.status, "krs_gemm: split-K needs %zu workspace bytes, got %zu", pl.need, workspace_bytes);
+  if (pl.status != KRS_OK) return fail(pl.status, "krs_gemm: the shape needs a grid beyond the launch limits");
+  return KRS_OK;
+}
+
+// launches the kernel the plan names; ES = bytes per input element
+template <int ES>
+int gemm_launch(const GemmParams& p, const gplan::GemmPlan& pl, int in_dtype, hipStream_t st) {
+  const krs_gemm_route& rt = pl.route;
+  const dim3 grid((unsigned)pl.grid[0], (unsigned)pl.grid[1], (unsigned)pl.grid[2]), block((unsigned)pl.block);
+  switch (rt.kernel) {
+    case KRS_GEMM_KERNEL_PP64:
+      return with_epilogue<0, 2>(rt.epilogue, [&](auto E) {
+        return launch_lds<gemm_pp64_kernel<E>>("gemm_pp64_kernel", grid, block, pl.lds, st, p, pl.nt);
+      });
+    case KRS_GEMM_KERNEL_PP256:
+      return with_epilogue<0, 2>(rt.epilogue, [&](auto E) {
+        return launch_lds<gemm_pp256_kernel<false, 4, E>>("gemm_pp256_kernel", grid, block, pl.lds, st, p, 0, pl.nt);
+      });
+    case KRS_GEMM_KERNEL_PP256_KSTRIDED:
+      return launch_lds<gemm_pp256_kernel<true, 4, 0>>("gemm_pp256_kernel (K-strided operands)", grid, block, pl.lds, st, p,
+                                                       pl.mt, pl.nt);
+    case KRS_GEMM_KERNEL_TN_GLDS:
+      return launch_lds<gemm_tn_glds_kernel<0>>("gemm_tn_glds_kernel", grid, block, pl.lds, st, p, pl.mt, pl.nt);
+    case KRS_GEMM_KERNEL_GLDS:
+      return with_epilogue<0, 2>(rt.epilogue, [&](auto E) {
+        return launch_lds<gemm_glds_kernel<ES, E>>("gemm_glds_kernel", grid, block, pl.lds, st, p);
+      });
+    case KRS_GEMM_KERNEL_MFMA:
+      return with_epilogue<0, 2>(rt.epilogue, [&](auto E) {
+        if (p.a_km) return launch_lds<gemm_mfma_kernel<ES, true, false, E>>("gemm_mfma_kernel", grid, block, pl.lds, st, p);
+        if (p.b_nk) return launch_lds<gemm_mfma_kernel<ES, false, true, E>>("gemm_mfma_kernel", grid, block, pl.lds, st, p);
+        return launch_lds<gemm_mfma_kernel<ES, false, false, E>>("gemm_mfma_kernel", grid, block, pl.lds, st, p);
+      });
+    case KRS_GEMM_KERNEL_THIN:
+      if (rt.thin_width == 1) hipLaunchKernelGGL((gemm_thin_kernel<ES, 1>), grid, block, 0, st, p, rt.thin_is_a);
+      else if (rt.thin_width == 4) hipLaunchKernelGGL((gemm_thin_kernel<ES, 4>), grid, block, 0, st, p, rt.thin_is_a);
+      else if (rt.thin_width == 8) hipLaunchKernelGGL((gemm_thin_kernel<ES, 8>), grid, block, 0, st, p, rt.thin_is_a);
+      else hipLaunchKernelGGL((gemm_thin_kernel<ES, 16>), grid, block, 0, st, p, rt.thin_is_a);
+      KRS_CHECK_LAUNCH("gemm_thin_kernel");
+      return KRS_OK;
+    case KRS_GEMM_KERNEL_ROWDOT:
+      hipLaunchKernelGGL(gemm_rowdot_kernel<ES>, grid, block, 0, st, p);
+      KRS_CHECK_LAUNCH("gemm_rowdot_kernel");
+      return KRS_OK;
+    case KRS_GEMM_KERNEL_SMALLK:
+      hipLaunchKernelGGL(gemm_smallk_kernel<ES>, grid, block, pl.lds, st, p, gplan::kSmallkRows);
+      KRS_CHECK_LAUNCH("gemm_smallk_kernel");
+      return KRS_OK;
+    default:
+      hipLaunchKernelGGL(gemm_generic_kernel, grid, block, 0, st, p, in_dtype);
+      KRS_CHECK_LAUNCH("gemm_generic_kernel");
+      return KRS_OK;
+  }
+}
+
+// krs_gemm's body: validate and plan -> launch what the plan names.  `allow_split` false = one pass over K (the two-call
+// form of krs_gemm_cross_bwd, whose workspace is sized for the column sums only).
 int gemm_run(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb, int b_is_nk,
              void* c, int64_t ldc, int64_t m, int64_t n, int64_t k, int in_dtype, int out_dtype,
              const krs_gemm_epilogue* epilogue, void* workspace, size_t workspace_bytes,
              void* stream, bool allow_split) {
   g_route = krs_gemm_route{};
-  krs_gemm_route rt = {};
-  KRS_REQUIRE(a && b && c, "krs_gemm: null operand");
-  KRS_REQUIRE(m >= 0 && n >= 0 && k >= 0, "krs_gemm: negative size");
-  KRS_REQUIRE((in_dtype == KRS_F32 || in_dtype == KRS_BF16) && (out_dtype == KRS_F32 || out_dtype == KRS_BF16),
-              "krs_gemm: bad dtype");
-  if (epilogue && epilogue->x0) KRS_REQUIRE(epilogue->x, "krs_gemm: cross epilogue needs x with x0");
-  if (m == 0 || n == 0) return KRS_OK;
+  gplan::GemmCall call;
+  gplan::GemmPlan pl;
+  if (int rc = gemm_plan(a, lda, a_is_km, b, ldb, b_is_nk, c, ldc, m, n, k, in_dtype, out_dtype, epilogue,
+                         workspace ? workspace_bytes : 0, allow_split, call, pl))
+    return rc;
+  const krs_gemm_route& rt = pl.route;
+  if (rt.kernel == KRS_GEMM_KERNEL_NONE) return KRS_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   GemmParams p{};
-  p.a = reinterpret_cast<const char*>(a); p.lda = lda; p.a_km = a_is_km != 0;
-  p.b = reinterpret_cast<const char*>(b); p.ldb = ldb; p.b_nk = b_is_nk != 0;
+  p.a = reinterpret_cast<const char*>(a); p.lda = lda; p.a_km = call.a_km;
+  p.b = reinterpret_cast<const char*>(b); p.ldb = ldb; p.b_nk = call.b_nk;
   p.c = reinterpret_cast<char*>(c); p.ldc = ldc; p.m = m; p.n = n; p.k = k; p.out_dtype = out_dtype;
   p.has_ep = epilogue != nullptr;
   if (epilogue) p.ep = *epilogue; else memset(&p.ep, 0, sizeof(p.ep));
-  p.splits = 1; p.k_per_split = k; p.slabs = nullptr;
-  {
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    bool v = n % 8 == 0 && ldc % 8 == 0 && al16(c);
-    if (epilogue) {
-      if (epilogue->bias) v = v && al16(epilogue->bias);
-      if (epilogue->x0) v = v && al16(epilogue->x0) && al16(epilogue->x) && epilogue->ldx % 8 == 0;
-      if (epilogue->u_out) v = v && al16(epilogue->u_out) && epilogue->ldu % 8 == 0;
-      if (epilogue->r) v = v && al16(epilogue->r) && epilogue->ldr % 8 == 0;
-    }
-    p.ep_vec = v;
-    rt.ep_vec = v;
+  p.splits = rt.splits; p.k_per_split = pl.k_per_split; p.ep_vec = rt.ep_vec;
+  p.slabs = rt.splits > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
+  if (int rc = call.es == 2 ? gemm_launch<2>(p, pl, in_dtype, st) : gemm_launch<4>(p, pl, in_dtype, st)) return rc;
+  if (rt.reduce) {
+    const dim3 rgrid((unsigned)pl.reduce_grid);
+    if (rt.reduce == KRS_GEMM_REDUCE_VEC4) hipLaunchKernelGGL(gemm_slab_reduce_vec4_kernel, rgrid, dim3(256), 0, st, p);
+    else if (rt.reduce == KRS_GEMM_REDUCE_VEC8) hipLaunchKernelGGL(gemm_slab_reduce_vec8_kernel, rgrid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(gemm_slab_reduce_kernel, rgrid, dim3(256), 0, st, p);
+    KRS_CHECK_LAUNCH("gemm_slab_reduce_kernel");
   }
-  const int es = in_dtype == KRS_BF16 ? 2 : 4;
-  if (k > 0 && mfma_eligible(p, es) && !(p.a_km && p.b_nk)) {
-    const int s = allow_split ? pick_splits(m, n, k, a_is_km, es == 2 && b_is_nk) : 1;
-    if (s > 1) {
-      const size_t need = (size_t)s * m * n * sizeof(float);
-      if (!workspace || workspace_bytes < need)
-        return fail(KRS_ERR_WORKSPACE, "krs_gemm: split-K needs %zu workspace bytes, got %zu", need, workspace_bytes);
-      const int64_t bk = ROW_BYTES / es;
-      p.splits = s;
-      p.k_per_split = ceil_div(ceil_div(k, s), bk) * bk;
-      p.slabs = reinterpret_cast<float*>(workspace);
-    }
-    const int rc = es == 2 ? launch_mfma<2>(p, st, rt) : launch_mfma<4>(p, st, rt);
-    if (rc != KRS_OK) return rc;
-    rt.splits = p.splits;
-    if (p.splits > 1) {
-      const bool vec4 = !p.has_ep && out_dtype == KRS_F32 && n % 4 == 0 && ldc % 4 == 0 &&
-                        (reinterpret_cast<uintptr_t>(c) & 15) == 0;
-      if (vec4)
-        hipLaunchKernelGGL(gemm_slab_reduce_vec4_kernel, dim3((unsigned)ceil_div(m * (n / 4), 256)), dim3(256), 0, st, p);
-      else if (p.ep_vec && n % 8 == 0)
-        hipLaunchKernelGGL(gemm_slab_reduce_vec8_kernel, dim3((unsigned)ceil_div(m * (n / 8), 256)), dim3(256), 0, st, p);
-      else
-        hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)ceil_div(m * n, 256)), dim3(256), 0, st, p);
-      KRS_CHECK_LAUNCH("gemm_slab_reduce_kernel");
-      rt.reduce = vec4 ? KRS_GEMM_REDUCE_VEC4 : (p.ep_vec && n % 8 == 0 ? KRS_GEMM_REDUCE_VEC8 : KRS_GEMM_REDUCE_SCALAR);
-    }
-    g_route = rt;
-    return KRS_OK;
-  }
-  if (p.a_km && !p.b_nk && k >= 1024 && std::min(m, n) <= kThinMax) {
-    const int s = pick_splits(m, n, k, a_is_km);
-    if (s > 1 && workspace && workspace_bytes >= (size_t)s * m * n * sizeof(float)) {
-      p.splits = s;
-      p.k_per_split = ceil_div(k, s);
-      p.slabs = reinterpret_cast<float*>(workspace);
-    }
-    const int thin_is_a = m <= n;
-    const int64_t n_wide = thin_is_a ? n : m;
-    const int64_t n_thin = thin_is_a ? m : n;
-    const dim3 tgrid((unsigned)ceil_div(n_wide, 256), (unsigned)p.splits);
-#define KRS_THIN(ES_, NT_) hipLaunchKernelGGL((gemm_thin_kernel<ES_, NT_>), tgrid, dim3(256), 0, st, p, thin_is_a)
-#define KRS_THIN_NT(ES_)                                          \
-  {                                                               \
-    if (n_thin <= 1) KRS_THIN(ES_, 1);                            \
-    else if (n_thin <= 4) KRS_THIN(ES_, 4);                       \
-    else if (n_thin <= 8) KRS_THIN(ES_, 8);                       \
-    else KRS_THIN(ES_, 16);                                       \
-  }
-    if (in_dtype == KRS_BF16) KRS_THIN_NT(2) else KRS_THIN_NT(4)
-#undef KRS_THIN_NT
-#undef KRS_THIN
-    KRS_CHECK_LAUNCH("gemm_thin_kernel");
-    rt.kernel = KRS_GEMM_KERNEL_THIN; rt.splits = p.splits; rt.thin_is_a = thin_is_a;
-    rt.thin_width = n_thin <= 1 ? 1 : (n_thin <= 4 ? 4 : (n_thin <= 8 ? 8 : 16));
-    if (p.splits > 1) {
-      hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)ceil_div(m * n, 256)), dim3(256), 0, st, p);
-      KRS_CHECK_LAUNCH("gemm_slab_reduce_kernel");
-      rt.reduce = KRS_GEMM_REDUCE_SCALAR;
-    }
-    g_route = rt;
-    return KRS_OK;
-  }
-  if (!p.a_km && p.splits == 1 && n <= 8 && k >= 32 && m >= 1024) {
-    if (in_dtype == KRS_BF16) hipLaunchKernelGGL(gemm_rowdot_kernel<2>, dim3((unsigned)ceil_div(m, 16)), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(gemm_rowdot_kernel<4>, dim3((unsigned)ceil_div(m, 16)), dim3(256), 0, st, p);
-    KRS_CHECK_LAUNCH("gemm_rowdot_kernel");
-    rt.kernel = KRS_GEMM_KERNEL_ROWDOT; rt.splits = 1;
-    g_route = rt;
-    return KRS_OK;
-  }
-  if (!p.a_km && p.splits == 1 && k <= 16 && n % 8 == 0 && n <= 1024 && m * n >= (1 << 16)) {
-    const int rows_per_wg = 64;
-    const unsigned blocks = (unsigned)ceil_div(m, rows_per_wg);
-    const size_t lds = (size_t)k * n * sizeof(float);   // <= 64 KB
-    if (in_dtype == KRS_BF16) hipLaunchKernelGGL(gemm_smallk_kernel<2>, dim3(blocks), dim3(256), lds, st, p, rows_per_wg);
-    else hipLaunchKernelGGL(gemm_smallk_kernel<4>, dim3(blocks), dim3(256), lds, st, p, rows_per_wg);
-    KRS_CHECK_LAUNCH("gemm_smallk_kernel");
-    rt.kernel = KRS_GEMM_KERNEL_SMALLK; rt.splits = 1;
-    g_route = rt;
-    return KRS_OK;
-  }
-  hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned)ceil_div(m * n, 256)), dim3(256), 0, st, p, in_dtype);
-  KRS_CHECK_LAUNCH("gemm_generic_kernel");
-  rt.kernel = KRS_GEMM_KERNEL_GENERIC; rt.splits = 1;
   g_route = rt;
   return KRS_OK;
 }
@@ -1977,6 +1817,18 @@ extern "C" int krs_gemm(const void* a, int64_t lda, int a_is_km, const void* b, 
                         void* stream) {
   return gemm_run(a, lda, a_is_km, b, ldb, b_is_nk, c, ldc, m, n, k, in_dtype, out_dtype, epilogue, workspace,
                   workspace_bytes, stream, true);
+}
+
+extern "C" int krs_gemm_plan_route(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb, int b_is_nk,
+                                   const void* c, int64_t ldc, int64_t m, int64_t n, int64_t k, int in_dtype,
+                                   int out_dtype, const krs_gemm_epilogue* epilogue, size_t workspace_bytes,
+                                   krs_gemm_route* route) {
+  gplan::GemmCall call;
+  gplan::GemmPlan pl;
+  const int rc = gemm_plan(a, lda, a_is_km, b, ldb, b_is_nk, c, ldc, m, n, k, in_dtype, out_dtype, epilogue,
+                           workspace_bytes, true, call, pl);
+  if (route) *route = pl.route;
+  return rc;
 }
 
 extern "C" int krs_gemm_last_route(krs_gemm_route* route) {
@@ -2000,11 +1852,12 @@ extern "C" int krs_gemm_cross_bwd_last_route(int* epilogue) {
 
 // The body of krs_gemm_cross_bwd and of krs_gemm_dense_bwd (`dense`: the layer below is a Dense layer, u its saved output:
 // dz = G act'(u), dbias; x0, R, dx0, u_upper and fold_direct are absent).  The entries have checked their operands; `who`
-// names the entry in error messages.
+// names the entry in error messages.  `plan_only` (krs_gemm_cross_bwd_plan_route): the plan is handed back, nothing runs.
 static int cross_bwd(const char* who, bool dense, const void* a, int64_t lda, const void* bt, int64_t ldb, const void* r,
                      int64_t ldr, float beta, void* g_out, int64_t ldg, const void* x0, const void* u, void* dz, void* dx0,
                      int64_t ld, int dx0_accumulate, const void* u_upper, int fold_direct, float* dbias, int64_t m,
-                     int64_t n, int64_t k, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+                     int64_t n, int64_t k, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream,
+                     gplan::CrossBwdPlan* plan_only = nullptr) {
   // dense form: G is stored only where the caller asked for it (g_out != NULL), by either route; without g_out the fused
   // route writes dz alone and the two-call route lands G in dz's buffer and applies the derivative in place
   const bool store_g = g_out != nullptr;
@@ -2012,6 +1865,20 @@ static int cross_bwd(const char* who, bool dense, const void* a, int64_t lda, co
   if (!r) { ldr = n; beta = 0.0f; }
   KRS_REQUIRE(dtype == KRS_BF16 || dtype == KRS_F32, "%s: bad dtype", who);
   KRS_REQUIRE(m >= 0 && n >= 0 && k > 0 && ld >= n && ldg >= n && ldr >= n, "%s: bad sizes", who);
+  // the product as the two-call form hands it to krs_gemm (one pass over K: this entry's workspace holds the column sums,
+  // not split-K slabs), and the plan of the whole call
+  krs_gemm_epilogue ep;
+  memset(&ep, 0, sizeof(ep));
+  ep.r = r; ep.ldr = ldr; ep.beta = beta;
+  gplan::CrossBwdPlan cb;
+  if (m > 0 && n > 0) {
+    gplan::GemmCall call;
+    if (int rc = gemm_plan(a, lda, 0, bt, ldb, 1, g_out, ldg, m, n, k, dtype, dtype, r ? &ep : nullptr, 0, false, call, cb.product))
+      return rc;
+    gplan::plan_cross_bwd(cb, r != nullptr, ld, al16(x0) && al16(u) && al16(dz) && al16(dx0) && al16(u_upper), dense, store_g,
+                          dx0 != nullptr, dx0_accumulate != 0, u_upper != nullptr);
+  }
+  if (plan_only) { *plan_only = cb; return KRS_OK; }
   if (dbias) KRS_REQUIRE(workspace_bytes >= krs_gemm_cross_bwd_workspace_bytes(m, n) && (workspace || m == 0 || n == 0),
                          "%s: workspace too small (krs_gemm_cross_bwd_workspace_bytes)", who);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -2019,18 +1886,9 @@ static int cross_bwd(const char* who, bool dense, const void* a, int64_t lda, co
     if (dbias && n > 0) KRS_HIP(hipMemsetAsync(dbias, 0, (size_t)n * sizeof(float), st));
     return KRS_OK;
   }
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const bool fused = dtype == KRS_BF16 && gemm_pipe() != 0 && m >= 256 && n >= 256 && k >= 256 && k % 64 == 0 &&
-                     ceil_div(m, 256) * ceil_div(n, 256) >= 192 && n % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 &&
-                     ldr % 8 == 0 && ldg % 8 == 0 && ld % 8 == 0 && al16(a) && al16(bt) && (!r || al16(r)) && al16(g_out) &&
-                     (!x0 || al16(x0)) && al16(u) && al16(dz) && (!dx0 || al16(dx0)) && (!u_upper || al16(u_upper));
-  if (!fused) {
+  if (cb.route == KRS_CROSS_BWD_TWO_CALL) {
     // any other shape / dtype: the two calls this entry stands for
-    cb_route = KRS_CROSS_BWD_TWO_CALL;
-    krs_gemm_epilogue ep;
-    memset(&ep, 0, sizeof(ep));
-    ep.r = r; ep.ldr = ldr; ep.beta = beta;
-    // (one pass over K: this entry's workspace holds the column sums, not split-K slabs)
+    cb_route = cb.route;
     if (int rc = gemm_run(a, lda, 0, bt, ldb, 1, g_out, ldg, m, n, k, dtype, dtype, r ? &ep : nullptr, nullptr, 0, stream,
                           false))
       return rc;
@@ -2051,31 +1909,34 @@ static int cross_bwd(const char* who, bool dense, const void* a, int64_t lda, co
   p.b = reinterpret_cast<const char*>(bt); p.ldb = ldb; p.b_nk = 1;
   p.c = reinterpret_cast<char*>(g_out); p.ldc = ldg; p.m = m; p.n = n; p.k = k; p.out_dtype = KRS_BF16;
   p.has_ep = 1;
-  memset(&p.ep, 0, sizeof(p.ep));
-  p.ep.r = r; p.ep.ldr = ldr; p.ep.beta = beta;
+  p.ep = ep;
   p.splits = 1; p.k_per_split = k; p.slabs = nullptr; p.ep_vec = 1;
   p.f_x0 = x0; p.f_u = u; p.f_uup = u_upper; p.f_dz = dz; p.f_dx0 = dx0; p.f_ld = ld; p.f_act = act; p.f_fold = fold_direct != 0;
   p.f_partial = dbias ? reinterpret_cast<float*>(workspace) : nullptr;
-  const int nt_ = (int)ceil_div(n, 256);
-  const dim3 grid256((unsigned)(ceil_div(ceil_div(m, 256), 8) * 8 * nt_));
-  // the fused epilogue of this form (EPI 3 .. 10 of both ring kernels)
-  int epi;
-  if (dense) epi = store_g ? 10 : 9;
-  else if (u_upper) epi = 7;
-  else if (r) epi = dx0_accumulate ? 4 : 3;
-  else epi = !dx0 ? 8 : (dx0_accumulate ? 6 : 5);
-  // the 64-k ring, as krs_gemm's K-contiguous products (level with the 32-k ring on this epilogue-bound form: 640-650 us
-  // either way)
-  const bool k64 = gemm_pipe() == 4 && k % 64 == 0 && k >= 192;
-  cb_route = k64 ? KRS_CROSS_BWD_PP64 : KRS_CROSS_BWD_PP256; cb_epilogue = epi;
-  const int rc = with_epilogue<3, 10>(epi, [&](auto E) {
-    return k64 ? launch_lds<gemm_pp64_kernel<E>>("gemm_pp64_kernel (fused cross backward)", grid256, dim3(512),
-                                                 pp64::NSLOT * pp64::SLOT, st, p, nt_)
-               : launch_lds<gemm_pp256_kernel<false, 4, E>>("gemm_pp256_kernel (fused cross backward)", grid256, dim3(512),
-                                                            4 * pp::STAGE, st, p, 0, nt_);
+  // the fused epilogue of this form (EPI 3 .. 10 of both ring kernels) on the ring the planner gives the product (the 64-k
+  // ring is level with the 32-k one on this epilogue-bound form: 640-650 us either way)
+  const gplan::GemmPlan& pl = cb.product;
+  const dim3 grid256((unsigned)pl.grid[0]), block((unsigned)pl.block);
+  cb_route = cb.route; cb_epilogue = cb.epilogue;
+  const int rc = with_epilogue<3, 10>(cb.epilogue, [&](auto E) {
+    return cb.route == KRS_CROSS_BWD_PP64
+               ? launch_lds<gemm_pp64_kernel<E>>("gemm_pp64_kernel (fused cross backward)", grid256, block, pl.lds, st, p, pl.nt)
+               : launch_lds<gemm_pp256_kernel<false, 4, E>>("gemm_pp256_kernel (fused cross backward)", grid256, block, pl.lds,
+                                                            st, p, 0, pl.nt);
   });
   if (rc != KRS_OK) return rc;
   return dbias ? finish_colsum(p.f_partial, 2 * ceil_div(m, 256), n, dbias, st) : KRS_OK;
+}
+
+extern "C" int krs_gemm_cross_bwd_plan_route(const void* a, int64_t lda, const void* bt, int64_t ldb, const void* r,
+                                             int64_t ldr, float beta, void* g_out, int64_t ldg, const void* x0, const void* u,
+                                             void* dz, void* dx0, int64_t ld, int dx0_accumulate, const void* u_upper,
+                                             int64_t m, int64_t n, int64_t k, int dtype, int* epilogue) {
+  gplan::CrossBwdPlan cb;
+  const int rc = cross_bwd("krs_gemm_cross_bwd_plan_route", x0 == nullptr, a, lda, bt, ldb, r, ldr, beta, g_out, ldg, x0, u, dz,
+                           dx0, ld, dx0_accumulate, u_upper, 0, nullptr, m, n, k, KRS_ACT_NONE, dtype, nullptr, 0, nullptr, &cb);
+  if (epilogue) *epilogue = cb.epilogue;
+  return rc ? rc : cb.route;
 }
 
 extern "C" int krs_gemm_cross_bwd(const void* a, int64_t lda, const void* bt, int64_t ldb, const void* r, int64_t ldr,

@@ -219,6 +219,12 @@ GEMM_KERNELS = {0: None, 1: "generic", 2: "mfma", 3: "glds", 4: "tn_glds", 5: "p
 GEMM_REDUCES = {0: None, 1: "scalar", 2: "vec4", 3: "vec8"}
 
 
+def _route_dict(rt) -> dict:
+    return dict(kernel=GEMM_KERNELS[rt.kernel], splits=int(rt.splits), reduce=GEMM_REDUCES[rt.reduce],
+                epilogue=int(rt.epilogue), ep_vec=bool(rt.ep_vec), thin_width=int(rt.thin_width),
+                thin_is_a=bool(rt.thin_is_a))
+
+
 def last_gemm_route() -> dict:
     """Where the calling thread's last krs_gemm ran (krs_gemm_last_route): kernel (a GEMM_KERNELS name, None when no
     launch was made), splits (1 = no split-K), reduce (a GEMM_REDUCES name), epilogue (the tile kernel's build: 0, 1, 2),
@@ -226,9 +232,18 @@ def last_gemm_route() -> dict:
     record, no device sync."""
     rt = L.GemmRoute()
     L.lib().krs_gemm_last_route(C.byref(rt))
-    return dict(kernel=GEMM_KERNELS[rt.kernel], splits=int(rt.splits), reduce=GEMM_REDUCES[rt.reduce],
-                epilogue=int(rt.epilogue), ep_vec=bool(rt.ep_vec), thin_width=int(rt.thin_width),
-                thin_is_a=bool(rt.thin_is_a))
+    return _route_dict(rt)
+
+
+def plan_gemm_route(a, lda, a_is_km, b, ldb, b_is_nk, c, ldc, m, n, k, in_dtype, out_dtype, epilogue=None,
+                    workspace_bytes=0):
+    """(status, route) a krs_gemm with these arguments would have (krs_gemm_plan_route; needs no GPU): a, b, c are
+    addresses (ints: only their alignment is read), epilogue a GemmEpilogue or None; status is what krs_gemm returns
+    before its first launch, route the dict of last_gemm_route()."""
+    rt = L.GemmRoute()
+    rc = L.lib().krs_gemm_plan_route(a, lda, int(a_is_km), b, ldb, int(b_is_nk), c, ldc, m, n, k, in_dtype, out_dtype,
+                                     C.byref(epilogue) if epilogue is not None else None, int(workspace_bytes), C.byref(rt))
+    return int(rc), _route_dict(rt)
 
 
 def colsum(a: torch.Tensor) -> torch.Tensor:

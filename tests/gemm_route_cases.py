@@ -3,9 +3,9 @@ tests/test_gemm_routes_host.py.  No torch, no GPU: plain data.
 
 A case fixes one krs_gemm call: operand layout, dtypes, sizes, the padding of every leading dimension, an element
 offset of every base pointer, the epilogue form, the pipeline option, whether a workspace is passed -- and the route
-record krs_gemm_last_route must report for it.  The expected routes were read from gemm_run / launch_mfma / pick_splits
-(keras_rs_amd/csrc/gemm.hip); the GPU test asserts each one, so a dispatch change shows up as a failing case, not as
-lost coverage.
+record krs_gemm_last_route must report for it.  The expected routes are asserted on the host against the planner
+(keras_rs_amd/csrc/gemm_plan.h, tests/test_gemm_routes_host.py) and on the device against what ran, so a dispatch change
+shows up as a failing case, not as lost coverage.
 """
 
 from collections import namedtuple
@@ -95,6 +95,9 @@ CASES = [
     case("mfma-nt-f32-split-scalar", "nt", "f32", "f32", 130, 203, 4100, "bias_res", R("mfma", splits=4,
          reduce="scalar"), pad=dict(a=4, b=4, c=1, r=3)),
     case("mfma-nt-f32-null", "nt", "f32", "f32", 100, 52, 36, "null", R("mfma")),
+    # the general split rule asks for 6 slabs where the ring rule (bf16 only) would ask for 5: the query sizes the larger
+    case("mfma-nt-f32-split6-query-ws", "nt", "f32", "f32", 2056, 1032, 6144, "null", R("mfma", splits=6,
+         reduce="vec4", vec=True)),
     case("mfma-nn-f32-4x4x4", "nn", "f32", "f32", 4, 4, 4, "bias", R("mfma")),
     case("mfma-nt-bf16-8x8x8", "nt", "bf16", "bf16", 8, 8, 8, "bias", R("mfma", vec=True)),
     case("mfma-nt-bf16-8x8x8-f32out", "nt", "bf16", "f32", 8, 8, 8, "bias", R("mfma", vec=True)),
@@ -205,6 +208,9 @@ CASES = [
     case("pp256k-split-scalar-f32out", "tn", "bf16", "f32", 264, 520, 4352, "cross_u", R("pp256_kstrided", splits=8,
          reduce="scalar"), pad=dict(c=3, x=5, u=2)),
     case("pp256k-pipe0-tn-glds", "tn", "bf16", "bf16", 264, 520, 512, "bias", R("tn_glds", vec=True), pipe=0),
+    # 9 splits of 576 would leave the last one 64 k, half a ring: the planner skips that count (8 x 640, the last 192)
+    case("pp256k-split-short-last", "tn", "bf16", "bf16", 256, 256, 4672, "bias", R("pp256_kstrided", splits=8,
+         reduce="vec8", vec=True)),
     # gemm_thin_kernel: widths 1 / 4 / 8 / 16, either operand thin, split and (no workspace passed) unsplit
     case("thin-w1-a-split-bf16", "tn", "bf16", "bf16", 1, 520, 4100, "bias", R("thin", splits=8, reduce="scalar",
          width=1, thin_is_a=True), pad=P3),
@@ -246,7 +252,7 @@ CASES = [
          reduce="scalar", vec=True, width=16, thin_is_a=True), off=dict(a=1)),
     case("thin-w8-b-off-f32", "tn", "f32", "f32", 300, 8, 1500, "res", R("thin", splits=2, reduce="scalar", vec=True,
          width=8, thin_is_a=False), off=dict(b=1), beta=0.5),
-    # gemm_rowdot_kernel (N <= 8) and gemm_smallk_kernel (K <= 16): shapes mfma_eligible refuses
+    # gemm_rowdot_kernel (N <= 8) and gemm_smallk_kernel (K <= 16): shapes the planner's tile_eligible refuses
     case("rowdot-nn-bf16-n1", "nn", "bf16", "bf16", 2048, 1, 256, "bias", R("rowdot"), pad=P3),
     case("rowdot-nn-bf16-n1-f32out", "nn", "bf16", "f32", 2048, 1, 256, "bias", R("rowdot"), pad=P3),
     case("rowdot-nt-bf16-k77", "nt", "bf16", "bf16", 1500, 3, 77, "cross_u", R("rowdot"), pad=P3),
@@ -271,7 +277,7 @@ CASES = [
          beta=1.0),
     case("smallk-k0-bias", "nn", "f32", "f32", 1024, 64, 0, "bias", R("smallk", vec=True)),
     # the small shapes tests/test_dense_ops_gpu.py once labelled gemm_rowdot_kernel / gemm_smallk_kernel / gemm_thin_kernel:
-    # mfma_eligible takes them first wherever the contiguous axes are whole vectors (the 256 -> 1 unit forward included)
+    # tile_eligible takes them first wherever the contiguous axes are whole vectors (the 256 -> 1 unit forward included)
     case("dense1-fwd-nt-bf16-3000x1x256", "nt", "bf16", "bf16", 3000, 1, 256, "bias", R("mfma")),
     case("dense1-fwd-nt-bf16-3000x1x256-f32out", "nt", "bf16", "f32", 3000, 1, 256, "bias", R("mfma")),
     case("dense1-fwd-nt-f32-3000x1x256", "nt", "f32", "f32", 3000, 1, 256, "bias", R("mfma")),

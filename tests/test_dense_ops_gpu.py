@@ -30,7 +30,7 @@ def _tol(dt, k):
 @pytest.mark.parametrize("m,n,k", [(1, 3, 3), (5, 7, 9), (128, 128, 64), (130, 200, 72), (256, 512, 512),
                                    (300, 136, 1000), (64, 3456, 512), (130, 200, 1088), (257, 512, 3456),
                                    (700, 300, 1024), (512, 768, 2048),  # the last three: 256x256-tile kernel
-                                   # The small-shape kernels run only what mfma_eligible refuses (an axis that is not
+                                   # The small-shape kernels run only what tile_eligible (gemm_plan.h) refuses (an axis that is not
                                    # whole 16-byte vectors); krs_gemm_last_route settled which of these reach them, and
                                    # tests/test_gemm_routes_gpu.py asserts the route of every such shape:
                                    (13, 520, 4100), (264, 1, 4100),   # tn: gemm_thin_kernel (16- and 1-wide builds)

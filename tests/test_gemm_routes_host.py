@@ -1,8 +1,19 @@
-"""Coverage of the krs_gemm route table (tests/gemm_route_cases.py), checked without a GPU: the expected route records,
-which tests/test_gemm_routes_gpu.py asserts case by case on the device, name every kernel family, build, width, reduce
-kernel and pipeline of keras_rs_amd/csrc/gemm.hip.  A case dropped from the table fails here, not silently."""
+"""The krs_gemm route table (tests/gemm_route_cases.py), checked without a GPU.  Every expected route record is asserted
+against the planner (keras_rs_amd/csrc/gemm_plan.h through krs_gemm_plan_route, which launches nothing); the planner's
+invariants are walked by a stand-alone program built with the sanitizers (tests/host/gemm_plan_check.cpp); and the table
+names every kernel family, build, width, reduce kernel and pipeline of keras_rs_amd/csrc/gemm.hip, so a case dropped
+from it fails here, not silently.  tests/test_gemm_routes_gpu.py asserts the same records against what ran."""
 
-from tests.gemm_route_cases import ACT_FORMS, CASES, FORMS, leading_dims, split_geometry
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from tests.gemm_route_cases import ACT_FORMS, CASES, FORMS, R, leading_dims, split_geometry
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TILE_KERNELS = ("mfma", "glds", "pp256", "pp64")
 
@@ -106,3 +117,115 @@ def test_the_argument_classes_the_layers_use_are_present():
         assert [c for c in CASES if c.diag == v and "x0" in FORMS[c.ep]], ("diag_scale", v)
         assert [c for c in CASES if c.beta == v and "r" in FORMS[c.ep]], ("beta", v)
     assert set(ACT_FORMS) <= set(FORMS)
+
+
+# ---- the table against the planner -------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def lib():
+    from keras_rs_amd import _lib as L
+    from keras_rs_amd.build import build
+
+    build()
+    yield L
+    L.lib().krs_gemm_set_option(0, 4)
+
+
+def _planned(L, c, ws=None):
+    """(status, route) of the call tests/test_gemm_routes_gpu.py makes for case c: its leading dimensions, a fake base
+    address 0x100000 + offset per operand (only alignment is read), its epilogue struct, the workspace of the query."""
+    from keras_rs_amd import dense_ops as D
+
+    es_in, es_out = (2 if c.idt == "bf16" else 4), (2 if c.odt == "bf16" else 4)
+    lda, ldb, ldc, ldx, ldu, ldr = leading_dims(c)
+
+    def addr(key, es):
+        return 0x100000 + c.off.get(key, 0) * es
+
+    form, ep = FORMS[c.ep], None
+    if c.ep != "null":
+        ep = L.GemmEpilogue()
+        ep.act, ep.diag_scale, ep.beta = 0, c.diag, c.beta
+        if "bias" in form:
+            ep.bias = addr("bias", 4)
+        if "x0" in form:
+            ep.x0, ep.x, ep.ldx = addr("x0", es_out), addr("x", es_out), ldx
+        if "u" in form:
+            ep.u_out, ep.ldu = addr("u", es_out), ldu
+        if "r" in form:
+            ep.r, ep.ldr = addr("r", es_out), ldr
+    a_km, b_nk = c.layout == "tn", c.layout == "nt"
+    if ws is None:
+        ws = int(L.lib().krs_gemm_workspace_bytes(c.m, c.n, c.k, int(a_km))) if c.ws else 0
+    L.check(L.lib().krs_gemm_set_option(0, c.pipe), "krs_gemm_set_option")
+    try:
+        return D.plan_gemm_route(addr("a", es_in), lda, a_km, addr("b", es_in), ldb, b_nk, addr("c", es_out), ldc, c.m, c.n,
+                                 c.k, L.F32 if c.idt == "f32" else L.BF16, L.F32 if c.odt == "f32" else L.BF16, ep, ws)
+    finally:
+        L.lib().krs_gemm_set_option(0, 4)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
+def test_the_planner_gives_every_case_its_expected_route(lib, case):
+    assert _planned(lib, case) == (0, case.route)
+
+
+def test_the_planner_refuses_a_split_product_without_its_workspace_and_leaves_no_record(lib):
+    from keras_rs_amd import dense_ops as D
+
+    case = next(c for c in CASES if c.name == "ring-split-64k-vec8")
+    assert (case.layout, case.idt, case.m, case.n, case.k) == ("nt", "bf16", 1032, 520, 2112)
+    before = D.last_gemm_route()
+    status, route = _planned(lib, case, ws=0)
+    assert status != 0 and route == R(None)
+    assert b"workspace" in lib.lib().krs_last_error()
+    assert D.last_gemm_route() == before          # (the query does not touch the record of the last call)
+    # the two findings of the planner's first reading, at their shapes: the short last split and the undersized query
+    assert _planned(lib, next(c for c in CASES if c.name == "pp256k-split-short-last"))[1]["splits"] == 8
+    assert lib.lib().krs_gemm_workspace_bytes(2056, 1032, 6144, 0) == 6 * 2056 * 1032 * 4
+
+
+def _cross_bwd_planned(L, m, n, k, pipe, lda_pad=0, ldb_pad=0, misalign=False, dense=True, store_g=True):
+    """(route, epilogue) krs_gemm_cross_bwd_plan_route gives the bf16 call tests/test_dense_bwd_fusion_gpu.py makes"""
+    from keras_rs_amd import dense_ops as D
+
+    base, ep = 0x100000, C.c_int(-1)
+    L.check(L.lib().krs_gemm_set_option(0, pipe), "krs_gemm_set_option")
+    try:
+        route = L.lib().krs_gemm_cross_bwd_plan_route(
+            base + (2 if misalign else 0), k + lda_pad, base, k + ldb_pad, None if dense else base, n, 1.0,
+            base if store_g else None, n, None if dense else base, base, base, None if dense else base, n, 0, None, m, n, k,
+            L.BF16, C.byref(ep))
+    finally:
+        L.lib().krs_gemm_set_option(0, 4)
+    return D.CROSS_BWD_ROUTES[route], ep.value
+
+
+def test_the_cross_backward_planner_fuses_exactly_the_shapes_the_gpu_test_expects(lib):
+    from tests.test_dense_bwd_fusion_gpu import SHAPES, _aligned, _expected_route
+
+    for name, (m, n, k, lda_pad, ldb_pad, mis) in SHAPES.items():
+        for pipe in (0, 4, 5):
+            want = _expected_route(m, n, k, pipe, _aligned(m, n, k, lda_pad, ldb_pad, mis))
+            for store_g in (True, False):
+                got = _cross_bwd_planned(lib, m, n, k, pipe, lda_pad, ldb_pad, mis, store_g=store_g)
+                assert got == (want, (10 if store_g else 9) if want != "two_call" else 0), (name, pipe, store_g)
+    # the cross form (x0, R): epilogue 3 on the C3 shape, two-call below 192 tiles
+    assert _cross_bwd_planned(lib, 16384, 768, 256, 4, dense=False) == ("pp64", 3)
+    assert _cross_bwd_planned(lib, 16384, 768, 256, 5, dense=False) == ("pp256", 3)
+    assert _cross_bwd_planned(lib, 191 * 256, 256, 256, 4, dense=False) == ("two_call", 0)
+    assert _cross_bwd_planned(lib, 0, 256, 256, 4) == (None, 0)
+
+
+# ---- the planner's invariants, walked by a stand-alone program under the sanitizers ------------------------------------
+
+def test_the_planner_keeps_its_invariants_over_the_lattice_under_the_sanitizers(tmp_path):
+    cxx = shutil.which(os.environ.get("CXX", "g++")) or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "gemm_plan_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "host", "gemm_plan_check.cpp"), "-o", exe],
+                   check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-4000:]
+    assert "0 failed checks" in run.stdout

@@ -7,6 +7,11 @@ order, then serving with BruteForceRetrieval.
 
 Stages of `retrieval_task_loss`: scores -> SamplingProbabilityCorrection -> RemoveAccidentalHits ->
 HardNegativeMining -> CategoricalCrossentropy.  The scores are one GEMM; everything after it is K11 / K8 kernels.
+
+    python examples/two_tower_retrieval.py --fused    # the same run on InBatchSoftmaxLoss (K13)
+
+`fused_retrieval_task_loss` is the same loss without hard-negative mining, computed from the embeddings by the fused
+kernels: the [B, N] scores are never stored, so it also runs at batch sizes where the score matrix does not fit.
 """
 
 from __future__ import annotations
@@ -39,7 +44,15 @@ def retrieval_task_loss(query_emb: torch.Tensor, cand_emb: torch.Tensor, cand_id
     return loss(labels, scores)
 
 
-def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000, dim: int = 32) -> None:
+def fused_retrieval_task_loss(query_emb: torch.Tensor, cand_emb: torch.Tensor, cand_ids: torch.Tensor | None = None,
+                              cand_prob: torch.Tensor | None = None) -> torch.Tensor:
+    """retrieval_task_loss without hard-negative mining, on InBatchSoftmaxLoss: memory O((B + N) D)."""
+    return kl.InBatchSoftmaxLoss()(query_emb, cand_emb, candidate_ids=cand_ids,
+                                   candidate_sampling_probability=cand_prob)
+
+
+def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000, dim: int = 32,
+         fused: bool = False) -> None:
     dev = torch.device("cuda", torch.cuda.current_device())
     query_tower = kl.Embedding(users, dim, device=dev)
     cand_tower = kl.Embedding(items, dim, device=dev)
@@ -51,8 +64,12 @@ def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000,
     opt = torch.optim.SGD(query_tower.weights + cand_tower.weights, lr=0.5)
     for step in range(steps):
         opt.zero_grad()
-        value = retrieval_task_loss(query_tower(user_ids), cand_tower(item_ids), cand_ids=item_ids,
-                                    cand_prob=item_prob, num_hard_negatives=32)
+        if fused:
+            value = fused_retrieval_task_loss(query_tower(user_ids), cand_tower(item_ids), cand_ids=item_ids,
+                                              cand_prob=item_prob)
+        else:
+            value = retrieval_task_loss(query_tower(user_ids), cand_tower(item_ids), cand_ids=item_ids,
+                                        cand_prob=item_prob, num_hard_negatives=32)
         value.backward()
         opt.step()
         print(f"step {step}: loss {float(value):.4f}")
@@ -63,4 +80,4 @@ def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000,
 
 
 if __name__ == "__main__":
-    main()
+    main(fused="--fused" in sys.argv[1:])

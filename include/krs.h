@@ -872,6 +872,49 @@ int krs_binary_metrics(const void* pred, int dtype, const float* labels, const f
                        const float* const* auc_thresholds, const int* auc_T, const int* auc_from_logits,
                        float* const* auc_states, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * K13  Fused in-batch softmax retrieval loss: the scores are formed tile by tile on the matrix cores and never stored
+ *
+ * q [b, d] and c [n, d] are bf16 with row strides ldq, ldc (>= d; a column slice of a wider matrix needs no copy).
+ * Per query row i and candidate j, in fp32:
+ *     s_ij   = sum_k q_ik c_jk  (fp32 accumulate)  + bias_j  + hit_value * [ids_j == ids_{pos_i} and j != pos_i]
+ *     y'_ij  = (1 - ls) [j == pos_i] + ls / n
+ *     m_i = max_j s_ij,  Z_i = sum_j exp(s_ij - m_i),  lse_i = m_i + log Z_i
+ *     loss_i = sum_j y'_ij ((m_i - s_ij) + log Z_i)     (K11's accumulation: non-negative terms, no lse - s
+ *                                                         cancellation)
+ *     P_ij   = g_i (exp(s_ij - lse_i) - y'_ij),   g_i = g_scale * g[i]  (g [b] fp32, NULL = g_scale)
+ *     dq_i   = sum_j P_ij c_j,    dc_j = sum_i P_ij q_i   (P rounded to bf16, nearest even, for these two products;
+ *                                                         fp32 accumulate; stored in bf16 with row strides lddq, lddc)
+ * pos: int32 [b], or NULL for pos_i = i (labels = eye(b, n)).  cand_bias: fp32 [n] or NULL (the sampling correction
+ * -log(clip(p, eps, 1)) of SamplingProbabilityCorrection).  cand_ids: int32 / int64 [n] (id_dtype: krs_itype) or
+ * NULL; hit_value is added to the accidental hits of RemoveAccidentalHits (the reference's constant 1.1754944e-40
+ * changes no ordinary logit; a large negative finite value removes them).  ls = label_smoothing, 0 <= ls < 1.
+ * A pos_i outside [0, n) is never used as an address: that row's loss is NaN and its g_i counts as NaN, so its dq
+ * row and every dc entry are NaN, as in the stored-matrix head.  Scores must be finite.
+ *
+ * Known divergence from the stored-matrix head: for bf16 inputs that head rounds the scores to bf16 before the
+ * corrections and the softmax; here they stay in fp32 (as K8 ranks fp32 scores).
+ *
+ * krs_retrieval_xent_fwd writes row_loss [b] and row_lse [b] (fp32); krs_retrieval_xent_bwd recomputes the scores
+ * from q, c and row_lse and writes dq [b, d] and / or dc [n, d] (either may be NULL, not both).  Memory is
+ * O((b + n) d): when the owner side of a sweep gives too few workgroups the other side is cut into slices whose
+ * partials live in `workspace` (krs_retrieval_xent_workspace_bytes, at most about 16 (b + n) d floats, possibly 0;
+ * it need not be initialised) and are combined in slice order.  No float atomics: bit-identical from call to call.
+ * No host synchronisation.  b == 0 is a successful no-op.  n < 1, d < 1, d > 256, a dtype other than KRS_BF16 and
+ * more than 2^31 - 1 rows are KRS_ERR_INVALID (the Python wrapper routes such shapes to a slab path built from
+ * krs_gemm and K11); too little workspace is KRS_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------- */
+size_t krs_retrieval_xent_workspace_bytes(int64_t b, int64_t n, int64_t d, int dtype);
+int krs_retrieval_xent_fwd(const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b, int64_t n,
+                           int64_t d, const int32_t* pos, const float* cand_bias, const void* cand_ids, int id_dtype,
+                           float hit_value, float label_smoothing, float* row_loss, float* row_lse, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int krs_retrieval_xent_bwd(const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b, int64_t n,
+                           int64_t d, const int32_t* pos, const float* cand_bias, const void* cand_ids, int id_dtype,
+                           float hit_value, float label_smoothing, const float* row_lse, const float* g, float g_scale,
+                           void* dq, int64_t lddq, void* dc, int64_t lddc, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

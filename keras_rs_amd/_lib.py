@@ -133,6 +133,11 @@ PROTOTYPES = {
     "krs_remove_accidental_hits": (_I, [_P, _I64, _I, _P, _I64, _P, _I, _I64, _F, _I64, _I64, _P, _I64, _P]),
     "krs_binary_metrics_workspace_bytes": (_SZ, [_I64, _I, _P]),
     "krs_binary_metrics": (_I, [_P, _I, _P, _P, _F, _I64, _F, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "krs_retrieval_xent_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
+    "krs_retrieval_xent_fwd": (_I, [_P, _I64, _P, _I64, _I, _I64, _I64, _I64, _P, _P, _P, _I, _F, _F, _P, _P, _P, _SZ,
+                                    _P]),
+    "krs_retrieval_xent_bwd": (_I, [_P, _I64, _P, _I64, _I, _I64, _I64, _I64, _P, _P, _P, _I, _F, _F, _P, _P, _F, _P,
+                                    _I64, _P, _I64, _P, _SZ, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

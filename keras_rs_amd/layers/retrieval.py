@@ -3,7 +3,8 @@
 (hard_negative_mining.py), both on K8's exact top-k (include/krs.h: krs_retrieval_topk, krs_topk_rows), and for the two
 logit corrections of the training head, keras_rs.layers.SamplingProbabilityCorrection
 (sampling_probability_correction.py) and keras_rs.layers.RemoveAccidentalHits (remove_accidental_hits.py), on K11
-(krs_sampling_correction, krs_remove_accidental_hits).
+(krs_sampling_correction, krs_remove_accidental_hits); and InBatchSoftmaxLoss, the whole in-batch softmax head computed
+from the two embedding matrices without storing the scores (K13: krs_retrieval_xent_fwd / krs_retrieval_xent_bwd).
 
 Selection order: score descending, then candidate index ascending (-0.0 as +0.0, NaN above +inf); rows come back
 sorted.  Known divergence: for bf16 inputs keras.ops.matmul rounds the scores to bf16 before top_k, so among
@@ -19,6 +20,7 @@ import numpy as np
 import torch
 
 from keras_rs_amd import _lib as L
+from keras_rs_amd import losses as _reductions
 from keras_rs_amd import retrieval_ops
 from keras_rs_amd.layers import base
 
@@ -254,3 +256,83 @@ class RemoveAccidentalHits(base.Layer):
         L.require_device(candidate_ids, "RemoveAccidentalHits candidate_ids")
         return retrieval_ops.corrected(retrieval_ops.remove_accidental_hits, logits, labels.detach(),
                                        candidate_ids.detach(), retrieval_ops.SMALLEST_FLOAT)
+
+
+class InBatchSoftmaxLoss:
+    """The in-batch softmax loss of a two-tower retrieval model, from the embeddings: scores = query . candidates^T,
+    SamplingProbabilityCorrection, RemoveAccidentalHits and CategoricalCrossentropy(from_logits=True) against the
+    positives, with the [batch, candidates] scores, labels and logit gradient never stored (include/krs.h, K13;
+    memory O((B + N) D)).
+
+        loss(query_embeddings [B, D], candidate_embeddings [N, D], positive_index=None, candidate_ids=None,
+             candidate_sampling_probability=None, sample_weight=None)
+
+    positive_index [B]: the candidate that is each query's positive (None: candidate i for query i, the eye(B, N)
+    labels of the reference's examples); an index outside [0, N) makes that row's loss and gradients NaN.
+    candidate_sampling_probability [N]: logits -= log(clip(p, epsilon, 1)).  candidate_ids [N]: candidates with the
+    positive's id, other than the positive itself, have accidental_hit_value added to their logit; the default is the
+    reference's constant, which changes no ordinary logit, a large negative finite value
+    removes them.  bf16 embeddings of up to 256 columns run on the fused kernels, with fp32 scores (the stored-matrix
+    head rounds them to bf16 first); other inputs run krs_gemm + K11 slab by slab in fp32.
+
+    Hard-negative mining is not part of this loss: it needs a per-row top-k of the corrected scores.  Use the
+    stored-matrix head for it (examples/two_tower_retrieval.py: retrieval_task_loss with num_hard_negatives)."""
+
+    def __init__(self, label_smoothing: float = 0.0, reduction: str | None = "sum_over_batch_size",
+                 epsilon: float = 1e-6, accidental_hit_value: float = retrieval_ops.SMALLEST_FLOAT,
+                 name: str | None = None):
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"`label_smoothing` should be in [0, 1). Received: label_smoothing={label_smoothing}")
+        if reduction not in _reductions.REDUCTIONS:
+            raise ValueError(f"Invalid value for argument `reduction`. Expected one of {_reductions.REDUCTIONS}. "
+                             f"Received: reduction={reduction}")
+        if not np.isfinite(accidental_hit_value):
+            raise ValueError(f"`accidental_hit_value` should be finite. Received: {accidental_hit_value}")
+        self.label_smoothing, self.reduction = float(label_smoothing), reduction
+        self.epsilon, self.accidental_hit_value = float(epsilon), float(accidental_hit_value)
+        self.name = name or "in_batch_softmax_loss"
+
+    def __call__(self, query_embeddings, candidate_embeddings, positive_index=None, candidate_ids=None,
+                 candidate_sampling_probability=None, sample_weight=None) -> torch.Tensor:
+        q = _as_tensor(query_embeddings)
+        c = _as_tensor(candidate_embeddings, q.device)
+        shapes = f"`query_embeddings.shape` = {tuple(q.shape)}, `candidate_embeddings.shape` = {tuple(c.shape)}"
+        if q.dim() != 2 or c.dim() != 2 or q.shape[1] != c.shape[1] or c.shape[0] < 1 or c.shape[1] < 1:
+            raise ValueError("`query_embeddings` [batch, dim] and `candidate_embeddings` [candidates, dim] should be "
+                             f"matrices of one width with at least one candidate. Received: {shapes}.")
+        if q.dtype != c.dtype or q.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("`query_embeddings` and `candidate_embeddings` should share a dtype, float32 or bfloat16. "
+                             f"Received: {q.dtype} and {c.dtype} ({shapes}).")
+        b, n = q.shape[0], c.shape[0]
+        pos = ids = bias = None
+        if positive_index is not None:
+            pos = _as_tensor(positive_index, q.device)
+            if tuple(pos.shape) != (b,) or pos.dtype.is_floating_point or pos.dtype == torch.bool:
+                raise ValueError(f"`positive_index` should be {b} integers, one per query. Received: "
+                                 f"`positive_index.shape` = {tuple(pos.shape)}, dtype {pos.dtype} ({shapes}).")
+        if candidate_ids is not None:
+            ids = _as_tensor(candidate_ids, q.device)
+            if tuple(ids.shape) != (n,) or ids.dtype.is_floating_point or ids.dtype == torch.bool:
+                raise ValueError(f"`candidate_ids` should be {n} integers, one per candidate. Received: "
+                                 f"`candidate_ids.shape` = {tuple(ids.shape)}, dtype {ids.dtype} ({shapes}).")
+        if candidate_sampling_probability is not None:
+            prob = _as_tensor(candidate_sampling_probability, q.device)
+            if tuple(prob.shape) != (n,):
+                raise ValueError(f"`candidate_sampling_probability` should have one entry per candidate. Received: "
+                                 f"`candidate_sampling_probability.shape` = {tuple(prob.shape)} ({shapes}).")
+            bias = -torch.log(torch.clamp(prob.detach().to(torch.float32), self.epsilon, 1.0))
+        w = _reductions._sample_weight(sample_weight, (b,), q.device)
+        L.require_device(q, "InBatchSoftmaxLoss query_embeddings")
+        L.require_device(c, "InBatchSoftmaxLoss candidate_embeddings")
+        return retrieval_ops.retrieval_xent(q, c, positive_index=None if pos is None else pos.detach(), cand_bias=bias,
+                                            cand_ids=None if ids is None else ids.detach(),
+                                            hit_value=self.accidental_hit_value, label_smoothing=self.label_smoothing,
+                                            sample_weight=w, reduction=self.reduction)
+
+    def get_config(self) -> dict:
+        return {"name": self.name, "label_smoothing": self.label_smoothing, "reduction": self.reduction,
+                "epsilon": self.epsilon, "accidental_hit_value": self.accidental_hit_value}
+
+    @classmethod
+    def from_config(cls, config: dict):
+        return cls(**config)

@@ -1,5 +1,6 @@
-"""Host side of K8 and K11: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and mining), and
-over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head), all of
+"""Host side of K8, K11 and K13: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and mining),
+over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored scores), and
+over krs_retrieval_xent_fwd / krs_retrieval_xent_bwd (the in-batch softmax loss that never stores the scores), all of
 include/krs.h.
 
 All run on the current stream, allocate from torch's caching allocator and never wait for the device, so a call can
@@ -231,3 +232,219 @@ class _LogitCorrectionFn(torch.autograd.Function):
 def corrected(op, logits: torch.Tensor, *operands):
     """op(logits, *operands) (sampling_correction or remove_accidental_hits) with the identity gradient to logits."""
     return _LogitCorrectionFn.apply(logits, op, *operands)
+
+
+# ---- K13: the in-batch softmax loss from the embeddings, scores never stored -----------------------------------------
+SLAB_BYTES = 256 << 20     # default budget of the slab path's fp32 score slab
+XENT_MAX_D = 256           # widest embedding of the fused kernels (bf16 only)
+
+
+def retrieval_xent_workspace_bytes(b: int, n: int, d: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    dt = L.BF16 if dtype == torch.bfloat16 else L.F32
+    return int(L.lib().krs_retrieval_xent_workspace_bytes(b, n, d, dt))
+
+
+def _xent_operands(query, candidates, positive_index, cand_bias, cand_ids):
+    """The operands of K13 checked and in the form the C ABI takes: (q, c, pos int32 [B] or None, bias fp32 [N] or
+    None, ids int32 / int64 [N] or None)."""
+    q = L.rowmajor(query, "retrieval_xent query")
+    c = L.rowmajor(candidates, "retrieval_xent candidates")
+    if q.dtype != c.dtype or q.dtype not in (torch.float32, torch.bfloat16):
+        raise L.KrsError(f"retrieval_xent: query ({q.dtype}) and candidates ({c.dtype}) must share a dtype, float32 or "
+                         "bfloat16")
+    b, d = q.shape
+    n = c.shape[0]
+    if c.shape[1] != d or n < 1 or d < 1:
+        raise L.KrsError(f"retrieval_xent: query {tuple(q.shape)} against candidates {tuple(c.shape)}: the widths must "
+                         "agree and there must be at least one candidate and one column")
+    pos = bias = ids = None
+    if positive_index is not None:
+        L.require_device(positive_index, "retrieval_xent positive_index")
+        if tuple(positive_index.shape) != (b,) or positive_index.dtype.is_floating_point:
+            raise L.KrsError(f"retrieval_xent: positive_index must be {b} integers, got {tuple(positive_index.shape)} "
+                             f"{positive_index.dtype}")
+        # (an index beyond int32 stays out of range after the clamp: it marks its row NaN like any other)
+        pos = positive_index if positive_index.dtype == torch.int32 else \
+            positive_index.clamp(-1, 2**31 - 1).to(torch.int32)
+        pos = pos.contiguous()
+    if cand_bias is not None:
+        L.require_device(cand_bias, "retrieval_xent cand_bias")
+        if tuple(cand_bias.shape) != (n,):
+            raise L.KrsError(f"retrieval_xent: cand_bias must have shape ({n},), got {tuple(cand_bias.shape)}")
+        bias = cand_bias.detach().to(torch.float32).contiguous()
+    if cand_ids is not None:
+        L.require_device(cand_ids, "retrieval_xent cand_ids")
+        if tuple(cand_ids.shape) != (n,) or cand_ids.dtype.is_floating_point:
+            raise L.KrsError(f"retrieval_xent: cand_ids must be {n} integers, got {tuple(cand_ids.shape)} "
+                             f"{cand_ids.dtype}")
+        ids = cand_ids if cand_ids.dtype in (torch.int32, torch.int64) else cand_ids.to(torch.int64)
+        ids = ids.contiguous()
+    return q, c, pos, bias, ids
+
+
+def _xent_workspace(b, n, d, device):
+    size = retrieval_xent_workspace_bytes(b, n, d)
+    return torch.empty(max(1, size), dtype=torch.uint8, device=device), size
+
+
+def retrieval_xent_fwd(q, c, pos, bias, ids, hit_value: float, label_smoothing: float):
+    """krs_retrieval_xent_fwd on checked operands: (fp32 loss [B], fp32 log-sum-exp [B])."""
+    b, d = q.shape
+    n = c.shape[0]
+    loss = torch.empty((b,), dtype=torch.float32, device=q.device)
+    lse = torch.empty((b,), dtype=torch.float32, device=q.device)
+    ws, size = _xent_workspace(b, n, d, q.device)
+    rc = L.lib().krs_retrieval_xent_fwd(L.ptr(q), q.stride(0) if b > 1 else d, L.ptr(c), c.stride(0) if n > 1 else d,
+                                        L.fdtype(q), b, n, d, L.ptr(pos), L.ptr(bias), L.ptr(ids),
+                                        L.itype(ids) if ids is not None else L.I32, float(hit_value),
+                                        float(label_smoothing), L.ptr(loss), L.ptr(lse), L.ptr(ws), size,
+                                        L.stream_ptr())
+    L.check(rc, "krs_retrieval_xent_fwd")
+    return loss, lse
+
+
+def retrieval_xent_bwd(q, c, pos, bias, ids, hit_value: float, label_smoothing: float, lse, g, *, want_dq: bool = True,
+                       want_dc: bool = True):
+    """krs_retrieval_xent_bwd on checked operands with the per-row factor g (fp32 [B]): (dq, dc) in the inputs'
+    dtype, None where not wanted."""
+    b, d = q.shape
+    n = c.shape[0]
+    dq = torch.empty((b, d), dtype=q.dtype, device=q.device) if want_dq else None
+    dc = torch.empty((n, d), dtype=c.dtype, device=c.device) if want_dc else None
+    if b == 0:
+        return dq, (None if dc is None else dc.zero_())
+    ws, size = _xent_workspace(b, n, d, q.device)
+    rc = L.lib().krs_retrieval_xent_bwd(L.ptr(q), q.stride(0) if b > 1 else d, L.ptr(c), c.stride(0) if n > 1 else d,
+                                        L.fdtype(q), b, n, d, L.ptr(pos), L.ptr(bias), L.ptr(ids),
+                                        L.itype(ids) if ids is not None else L.I32, float(hit_value),
+                                        float(label_smoothing), L.ptr(lse), L.ptr(g), 1.0, L.ptr(dq), d, L.ptr(dc), d,
+                                        L.ptr(ws), size, L.stream_ptr())
+    L.check(rc, "krs_retrieval_xent_bwd")
+    return dq, dc
+
+
+# The slab path: the same loss from existing entry points only (krs_gemm with its bias epilogue for the sampling
+# correction, krs_remove_accidental_hits, krs_softmax_xent), a slab of query rows at a time, everything in fp32.
+def _slabs(b: int, n: int, slab_bytes: int):
+    rows = max(1, min(b, int(slab_bytes) // (4 * n)))
+    return [(r0, min(b, r0 + rows)) for r0 in range(0, b, rows)]
+
+
+def _slab_scores(q32, c32, r0, r1, pos, bias, ids, hit_value):
+    """(corrected fp32 scores [r1 - r0, N], int32 positives of the slab)"""
+    from keras_rs_amd import dense_ops
+
+    n = c32.shape[0]
+    scores, _ = dense_ops.gemm(q32[r0:r1], c32, b_is_nk=True, out_dtype=torch.float32, bias=bias)
+    idx = pos[r0:r1] if pos is not None else torch.arange(r0, r1, dtype=torch.int32, device=q32.device)
+    if ids is not None:
+        ok = (idx >= 0) & (idx < n)
+        labels = torch.zeros((r1 - r0, n), dtype=torch.float32, device=q32.device)
+        labels.scatter_(1, idx.clamp(0, n - 1).to(torch.int64)[:, None], ok.to(torch.float32)[:, None])
+        scores = remove_accidental_hits(scores, labels, ids, hit_value)
+    return scores, idx
+
+
+def retrieval_xent_slab_fwd(q, c, pos, bias, ids, hit_value: float, label_smoothing: float,
+                            slab_bytes: int = SLAB_BYTES) -> torch.Tensor:
+    """The fp32 row losses [B] by the slab path."""
+    b, n = q.shape[0], c.shape[0]
+    q32, c32 = q.to(torch.float32), c.to(torch.float32)
+    loss = torch.empty((b,), dtype=torch.float32, device=q.device)
+    for r0, r1 in _slabs(b, n, slab_bytes):
+        scores, idx = _slab_scores(q32, c32, r0, r1, pos, bias, ids, hit_value)
+        loss[r0:r1], _ = softmax_xent(scores, label_index=idx, label_smoothing=label_smoothing, want_grad=False)
+    return loss
+
+
+def retrieval_xent_slab_bwd(q, c, pos, bias, ids, hit_value: float, label_smoothing: float, g,
+                            slab_bytes: int = SLAB_BYTES):
+    """(dq [B, D], dc [N, D]) in fp32 by the slab path: each slab's scores are recomputed, its logit gradient feeds
+    two more krs_gemm calls, and dc is accumulated across slabs in fp32."""
+    from keras_rs_amd import dense_ops
+
+    b, d = q.shape
+    n = c.shape[0]
+    q32, c32 = q.to(torch.float32), c.to(torch.float32)
+    dq = torch.empty((b, d), dtype=torch.float32, device=q.device)
+    dc = None
+    for r0, r1 in _slabs(b, n, slab_bytes):
+        scores, idx = _slab_scores(q32, c32, r0, r1, pos, bias, ids, hit_value)
+        _, dx = softmax_xent(scores, label_index=idx, label_smoothing=label_smoothing, g=g[r0:r1], want_loss=False)
+        dense_ops.gemm(dx, c32, out=dq[r0:r1])
+        dc, _ = dense_ops.gemm(dx, q32[r0:r1], a_is_km=True, r=dc)
+    if dc is None:
+        dc = torch.zeros((n, d), dtype=torch.float32, device=q.device)
+    return dq, dc
+
+
+class RetrievalXentFn(torch.autograd.Function):
+    """The in-batch softmax loss of query [B, D] against candidates [N, D] with its Keras reduction.  The forward keeps
+    q, c, the log-sum-exp per row (fused path) and the small operands; the backward recomputes the scores with the
+    per-row factor g = upstream * weight / divisor.  `weight` is None, a scalar tensor or [B]."""
+
+    @staticmethod
+    def forward(ctx, q, c, pos, bias, ids, weight, hit_value, label_smoothing, reduction, fused, slab_bytes):
+        if fused:
+            v, lse = retrieval_xent_fwd(q, c, pos, bias, ids, hit_value, label_smoothing)
+        else:
+            v, lse = retrieval_xent_slab_fwd(q, c, pos, bias, ids, hit_value, label_smoothing, slab_bytes), None
+        rows = q.shape[0]
+        g, scale = weight, 1.0
+        if reduction == "mean_with_sample_weight" and weight is not None:
+            div = weight.expand((rows,)).sum()
+            g = torch.where(div != 0, weight / div, torch.zeros_like(weight))   # divide_no_nan
+        elif reduction not in ("none", "sum"):
+            scale = 1.0 / rows if rows else 0.0
+        ctx.meta = (hit_value, label_smoothing, reduction, fused, slab_bytes, scale)
+        ctx.save_for_backward(q, c, lse, pos, bias, ids, g)
+        if reduction == "none":
+            return v if weight is None else v * weight
+        return (v.sum() if g is None else (v * g).sum()) * scale
+
+    @staticmethod
+    def backward(ctx, up):
+        hit_value, label_smoothing, reduction, fused, slab_bytes, scale = ctx.meta
+        q, c, lse, pos, bias, ids, g = ctx.saved_tensors
+        rows = q.shape[0]
+        gv = up.to(torch.float32) if scale == 1.0 else up.to(torch.float32) * scale
+        if g is not None:
+            gv = gv * g
+        gv = gv.expand((rows,)).contiguous()
+        want_dq, want_dc = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if fused:
+            dq, dc = retrieval_xent_bwd(q, c, pos, bias, ids, hit_value, label_smoothing, lse, gv, want_dq=want_dq,
+                                        want_dc=want_dc)
+        else:
+            dq, dc = retrieval_xent_slab_bwd(q, c, pos, bias, ids, hit_value, label_smoothing, gv, slab_bytes)
+            dq, dc = (dq.to(q.dtype) if want_dq else None), (dc.to(c.dtype) if want_dc else None)
+        return (dq, dc) + (None,) * 9
+
+
+def retrieval_xent(query: torch.Tensor, candidates: torch.Tensor, *, positive_index: torch.Tensor | None = None,
+                   cand_bias: torch.Tensor | None = None, cand_ids: torch.Tensor | None = None,
+                   hit_value: float = SMALLEST_FLOAT, label_smoothing: float = 0.0, path: str = "auto",
+                   sample_weight: torch.Tensor | None = None, reduction: str | None = "none",
+                   slab_bytes: int = SLAB_BYTES) -> torch.Tensor:
+    """Softmax cross-entropy of the scores query [B, D] . candidates [N, D]^T + cand_bias (+ hit_value on the
+    accidental hits given by cand_ids) against the positives positive_index (None: candidate i for query i), with
+    gradients to both embeddings (include/krs.h, K13).  The [B, N] scores are never stored.
+
+    path: "fused" -- the K13 kernels (bf16, D <= 256); "slab" -- krs_gemm + K11 on slabs of query rows whose fp32
+    scores stay under slab_bytes, in fp32; "auto" -- fused wherever it is eligible, whatever the shape: its contract
+    is memory, not speed.  reduction / sample_weight follow SoftmaxCrossentropyFn: "none" / None returns the fp32
+    losses [B] (times the weight), the others a scalar."""
+    if path not in ("auto", "fused", "slab"):
+        raise L.KrsError(f"retrieval_xent: path must be 'auto', 'fused' or 'slab', got {path!r}")
+    if not 0.0 <= label_smoothing < 1.0:
+        raise L.KrsError(f"retrieval_xent: label_smoothing {label_smoothing} outside [0, 1)")
+    q, c, pos, bias, ids = _xent_operands(query, candidates, positive_index, cand_bias, cand_ids)
+    fused = path == "fused" or (path == "auto" and q.dtype == torch.bfloat16 and q.shape[1] <= XENT_MAX_D)
+    w = None
+    if sample_weight is not None:
+        w = sample_weight.detach().to(device=q.device, dtype=torch.float32)
+        if w.dim() > 0:
+            w = w.expand((q.shape[0],)).contiguous()
+    reduction = "none" if reduction is None else reduction
+    return RetrievalXentFn.apply(q, c, pos, bias, ids, w, float(hit_value), float(label_smoothing), reduction, fused,
+                                 int(slab_bytes))

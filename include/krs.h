@@ -435,9 +435,15 @@ int krs_gemm_set_option(int key, int value);
  *   rows 0 .. n-1 of a workgroup's table are copied to LDS and lookups of them are served from there (one flat
  *   16-byte load per lookup, routed to LDS or memory by its address); pays only when ids are relabelled
  *   hot-first and those rows are NOT already cache hits (profiles/r3_k1_hot_rows_lds.txt: they are).
+ *   KRS_EMBED_OPT_APPLY_DEPTH: how krs_embed_bag_bwd_* fetch the rest of a table row's segment beyond its first two
+ *   lookups -- 0 = four gradient rows per trip, each trip a load of the lookups' values and then the gathers (A/B, and
+ *   the reference of the bit-for-bit test); 4 (default) / 8 / 16 = the deep front: sixteen values in one coalesced
+ *   load requested with the row, that many gradient rows requested together, the next values requested before these
+ *   rows are summed.  Same bytes, same order of additions: the four give the same bits; 4 is the fastest at the
+ *   benchmark's shape (profiles/k2_apply_depth_ab.txt).
  *   (Keys 0 and 1 -- the one-hot gather variants and the round-1 per-segment backward kernel -- were retired in
  *   round 5 with the kernels they selected; they are refused.) */
-enum { KRS_EMBED_OPT_PLAN = 2, KRS_EMBED_OPT_HOTROWS = 3, KRS_EMBED_OPT_RANK = 4 };
+enum { KRS_EMBED_OPT_PLAN = 2, KRS_EMBED_OPT_HOTROWS = 3, KRS_EMBED_OPT_RANK = 4, KRS_EMBED_OPT_APPLY_DEPTH = 5 };
 int krs_embed_set_option(int key, int value);
 
 /* Elementwise halves of FeatureCross for the host-composed path (arbitrary

@@ -22,12 +22,13 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "krs_bag_plan.h"
 
 // The apply kernels are instantiated per (gradient type, table type, lanes per row, optimizer, weights, scale): 3 dtype
 // pairs x 4 widths x 7 kernels x 7 modes = ~590 kernels (round 4: ~1000 -- the round-1 per-segment kernel and the
-// fp32-gradient / bf16-table pair are gone).  keras_rs_amd/build.py compiles this file four times, in parallel:
+// fp32-gradient / bf16-table pair are gone), the fast kernel (four of the seven) once per KRS_EMBED_OPT_APPLY_DEPTH value.  keras_rs_amd/build.py compiles this file four times, in parallel:
 // KRS_BWD_PART 0 = the dense / sparse / SGD forms, 1 = Adagrad and row-wise Adagrad, 2 = Adam, 3 = FTRL
 // (entry points outside a part are left out of it).  Undefined = the whole file in one object.
 #ifndef KRS_BWD_PART
@@ -36,6 +37,7 @@
 #define KRS_BWD_HAS(part) (KRS_BWD_PART < 0 || KRS_BWD_PART == (part))
 
 namespace krs {
+extern int g_apply_depth;   // embed_bag_fwd.hip: krs_embed_set_option(KRS_EMBED_OPT_APPLY_DEPTH, v)
 namespace {
 
 // ---- apply ------------------------------------------------------------------
@@ -242,7 +244,7 @@ typedef const __attribute__((address_space(1))) u32x4* gvec_ptr;
 //     the first two values), and the segments are software-pipelined: the table row, accumulator row and the
 //     first two gradient rows of segment i+1 are requested before segment i is consumed.
 // Per group that is 2 + 1 trips for four segments instead of ~8 each.  Segments longer than two lookups finish
-// in a loop of four gradient rows per trip.  Results are bit-identical to the round-1 kernel (same fmaf chain in
+// in a loop of four gradient rows per trip (DEPTH 0) or from sixteen values fetched in one load (DEPTH > 0, below).  Results are bit-identical to the round-1 kernel (same fmaf chain in
 // ascending position, same row_update).  Descriptor counts beyond the LDS cache (> 512 features or tables) and the
 // one dtype pair no Keras policy produces (fp32 gradients into bf16 tables) take bag_apply_generic.
 typedef u32x4 u32x4_ua __attribute__((aligned(2)));
@@ -312,11 +314,39 @@ __device__ __forceinline__ RawRow<N * (int)sizeof(TT) / 4> f32_to_raw(const floa
 }
 
 constexpr int kFastFirst = 2;   // gradient rows requested with the row itself
-constexpr int kFastMore = 4;    // ... and per trip of the remainder loop
+constexpr int kFastMore = 4;    // ... and per trip of the remainder loop (DEPTH 0)
+constexpr int kValsBlock = 16;  // values of a longer segment a group fetches in one trip (DEPTH > 0)
 
-template <typename GT, typename TT, int LPR, int MODE, bool HAS_W, bool HAS_SCALE>
+// DEPTH (krs_embed_set_option(KRS_EMBED_OPT_APPLY_DEPTH, v)): how the rest of a segment longer than kFastFirst is fetched.
+//   0 = the remainder loop: per trip of kFastMore rows a `vals` load, then the gathers whose addresses it gives -- two
+//       dependent round trips per four lookups, and a row of 6.6 lookups (the 100-per-bag table of C3) goes through
+//       five of them where a one-lookup row goes through two.  The A/B switch and the reference of the bit-for-bit test.
+//   4 (default) / 8 / 16 = the deep front.  The group's lanes fetch the segment's next kValsBlock values in ONE coalesced
+//       load (lane k of sixteen takes position s0 + kFastFirst + k, clamped to the segment), requested together with
+//       the row, its slots and its first two gradient rows; the lanes hand each other the values by a 16-wide shuffle,
+//       DEPTH gradient rows (and their coefficients) are requested together, and the following block of values is
+//       requested BEFORE this block's rows are consumed.  A segment of <= kFastFirst + DEPTH lookups costs ONE round
+//       trip beyond the row's own.  Same bytes, same fmaf chain in ascending position, same masking of clamped slots:
+//       bit-identical to DEPTH 0 in every mode (tests/test_embed_bag_bwd_depth_gpu.py).
+//   Every wave runs the deep body: the one load it adds to a row of one or two lookups (a clamped, coalesced 8 bytes per
+//   lane out of the line its first values came from) is not measurable on the one-hot tables.  What was measured and
+//   dropped: a second instantiation without any remainder code for the waves whose segments are all short (93 VGPRs,
+//   5 waves per SIMD) beside a deep-only one, each leaving the other's waves alone -- the waves that leave still cost
+//   40 - 50 us per launch (descriptor fill, barrier, two trips), more than the split returns; and both bodies behind a
+//   wave-uniform branch in one kernel, which hipcc allocates at 152 VGPRs (3 waves per SIMD) for DEPTH 4.
+//   Registers / waves per SIMD (-Rpass-analysis=kernel-resource-usage, fused Adagrad, 16 lanes per row, no weights or
+//   scales; no instance uses scratch):   DEPTH      0        4        8        16
+//                                bf16 rows, bf16 gradients   118 / 4  128 / 4  150 / 3  168 / 3
+//                                fp32 rows, fp32 gradients   108 / 4  124 / 4  128 / 4  211 / 2
+//   Measured at C3 (profiles/k2_apply_depth_ab.txt): DEPTH 4 keeps the four waves of DEPTH 0 and takes the 100-per-bag
+//   table from 572 to 480 us, the 2 ... 27-per-bag tables from 1544 to 1464, all 26 from 2255 to 2139, the one-hot
+//   tables stay at 227; 8 and 16 pay for their rows in flight with a wave per SIMD and lose part of that again.
+template <typename GT, typename TT, int LPR, int MODE, bool HAS_W, bool HAS_SCALE, int DEPTH>
 __global__ __launch_bounds__(256) void bag_apply_fast_kernel(const ApplyParams p) {
   constexpr int N = Piece<GT>::N;
+  constexpr int VW = LPR < kValsBlock ? LPR : kValsBlock;   // values per block: one per lane of a 16-lane (or narrower) group
+  constexpr int DT = DEPTH < VW ? (DEPTH > 0 ? DEPTH : 1) : VW;   // gradient rows per trip of the deep front
+  enum Rest { kRestLoop, kRestDeep };                             // how the body finishes segments longer than kFastFirst
   constexpr int S = segs_per_group(MODE);
   constexpr int WT = N * (int)sizeof(TT) / 4;   // dwords of a lane's table piece
   constexpr int WS = N;                         // ... of its fp32 slot piece
@@ -386,7 +416,9 @@ __global__ __launch_bounds__(256) void bag_apply_fast_kernel(const ApplyParams p
     float a_row;
     u32x4 g[kFastFirst];
     float c[kFastFirst];
+    uint64_t vx;   // kRestDeep: this lane's value of the segment's first block
   };
+  const int subv = threadIdx.x % VW;
   auto grad_src = [&](uint32_t bag) {
     const uint32_t f = bag / batch;
     const uint32_t b = bag - f * batch;
@@ -400,7 +432,8 @@ __global__ __launch_bounds__(256) void bag_apply_fast_kernel(const ApplyParams p
     if constexpr (HAS_SCALE) c *= p.bag_scale[(uint32_t)(v >> 32)];
     return c;
   };
-  auto issue = [&](int i, InFlight& x) {
+  auto issue = [&](auto rest_c, int i, InFlight& x) {
+    constexpr int REST = decltype(rest_c)::value;
     x.tb = krs_table{};
     x.off = 0;
     x.row = 0;
@@ -420,8 +453,10 @@ __global__ __launch_bounds__(256) void bag_apply_fast_kernel(const ApplyParams p
       x.g[q] = *(const KRS_AS1 u32x4_ua*)grad_src((uint32_t)(va[i][q] >> 32));
       x.c[q] = coef_of(va[i][q]);
     }
+    if constexpr (REST == kRestDeep) x.vx = p.vals[min(s0[i] + kFastFirst + subv, e0[i] - 1)];
   };
-  auto consume = [&](int i, const InFlight& x) {
+  auto consume = [&](auto rest_c, int i, const InFlight& x) {
+    constexpr int REST = decltype(rest_c)::value;
     const int64_t u = u_base + (int64_t)i * GPB + threadIdx.x / LPR;
     float acc[N];
 #pragma unroll
@@ -436,7 +471,7 @@ __global__ __launch_bounds__(256) void bag_apply_fast_kernel(const ApplyParams p
       }
     }
     // the rest of a longer segment, four gradient rows per trip (positions clamped, contributions masked)
-    if (ok[i]) {
+    if constexpr (REST == kRestLoop) if (ok[i]) {
       for (int64_t j0 = s0[i] + kFastFirst; j0 < e0[i]; j0 += kFastMore) {
         uint64_t vv[kFastMore];
 #pragma unroll
@@ -457,6 +492,40 @@ __global__ __launch_bounds__(256) void bag_apply_fast_kernel(const ApplyParams p
             for (int k = 0; k < N; ++k) acc[k] = fmaf(cf[q], gv[k], acc[k]);
           }
         }
+      }
+    }
+    // ... or the deep front: blocks of VW values, DT gradient rows per trip (the lanes of a group walk the same segment,
+    // so every lane a shuffle reads from is active with it)
+    if constexpr (REST == kRestDeep) if (ok[i]) {
+      // (a segment of invalid keys is not ok: none of its values becomes an address; zeros stand in all the same)
+      uint64_t mv = key[i] == kInvalidKey ? 0 : x.vx;
+      for (int64_t jb = s0[i] + kFastFirst; jb < e0[i]; jb += VW) {
+        const uint64_t mvn = p.vals[min(jb + VW + subv, e0[i] - 1)];   // the next block, before this one is consumed
+#pragma unroll
+        for (int t = 0; t < VW; t += DT) {
+          if (jb + t < e0[i]) {
+            u32x4 raw[DT];
+            float cf[DT];
+#pragma unroll
+            for (int q = 0; q < DT; ++q) {
+              const uint32_t bag = (uint32_t)__shfl((int)(uint32_t)(mv >> 32), t + q, VW);
+              uint32_t pos = 0;
+              if constexpr (HAS_W) pos = (uint32_t)__shfl((int)(uint32_t)mv, t + q, VW);
+              raw[q] = *(const KRS_AS1 u32x4_ua*)grad_src(bag);
+              cf[q] = coef_of(((uint64_t)bag << 32) | pos);
+            }
+#pragma unroll
+            for (int q = 0; q < DT; ++q) {
+              if (jb + t + q < e0[i]) {
+                float gv[N];
+                Piece<GT>::unpack(make_uint4(raw[q].x, raw[q].y, raw[q].z, raw[q].w), gv);
+#pragma unroll
+                for (int k = 0; k < N; ++k) acc[k] = fmaf(cf[q], gv[k], acc[k]);
+              }
+            }
+          }
+        }
+        mv = mvn;
       }
     }
     if constexpr (MODE == kAdagradRow) {
@@ -501,13 +570,17 @@ __global__ __launch_bounds__(256) void bag_apply_fast_kernel(const ApplyParams p
     }
   };
 
-  InFlight fl[2];
-  issue(0, fl[0]);
+  auto run = [&](auto rest_c) {
+    InFlight fl[2];
+    issue(rest_c, 0, fl[0]);
 #pragma unroll
-  for (int i = 0; i < S; ++i) {
-    if (i + 1 < S) issue(i + 1, fl[(i + 1) & 1]);
-    consume(i, fl[i & 1]);
-  }
+    for (int i = 0; i < S; ++i) {
+      if (i + 1 < S) issue(rest_c, i + 1, fl[(i + 1) & 1]);
+      consume(rest_c, i, fl[i & 1]);
+    }
+  };
+  if constexpr (DEPTH == 0) run(std::integral_constant<int, kRestLoop>{});
+  else run(std::integral_constant<int, kRestDeep>{});
 }
 
 // Writes one finished row (summed gradient `tot` of segment u, this lane's N columns): dense
@@ -787,8 +860,17 @@ int launch_apply_lpr(const ApplyParams& p, int pieces, hipStream_t st) {
   const int64_t groups = p.nnz;  // upper bound of the segment count (device-side n_seg trims it)
   const int64_t blocks = ceil_div(groups, (256 / lpr) * segs_per_group(MODE));
   if (blocks > 0x7fffffffLL) return fail(KRS_ERR_UNSUPPORTED, "embed_bag_bwd: grid too large");
-#define KRS_LAUNCH_FAST(L, W, SC) \
-  hipLaunchKernelGGL((bag_apply_fast_kernel<GT, TT, L, MODE, W, SC>), dim3((unsigned)blocks), dim3(256), 0, st, p)
+#define KRS_LAUNCH_FAST_D(L, W, SC, DP) \
+  hipLaunchKernelGGL((bag_apply_fast_kernel<GT, TT, L, MODE, W, SC, DP>), dim3((unsigned)blocks), dim3(256), 0, st, p)
+#define KRS_LAUNCH_FAST(L, W, SC)                                   \
+  do {                                                              \
+    switch (g_apply_depth) {                                        \
+      case 0: KRS_LAUNCH_FAST_D(L, W, SC, 0); break;                \
+      case 8: KRS_LAUNCH_FAST_D(L, W, SC, 8); break;                \
+      case 16: KRS_LAUNCH_FAST_D(L, W, SC, 16); break;              \
+      default: KRS_LAUNCH_FAST_D(L, W, SC, 4); break;               \
+    }                                                               \
+  } while (0)
 #define KRS_LAUNCH_APPLY(L)                                                                             \
   if (p.weights) { if (p.bag_scale) KRS_LAUNCH_FAST(L, true, true); else KRS_LAUNCH_FAST(L, true, false); }   \
   else { if (p.bag_scale) KRS_LAUNCH_FAST(L, false, true); else KRS_LAUNCH_FAST(L, false, false); }
@@ -798,6 +880,7 @@ int launch_apply_lpr(const ApplyParams& p, int pieces, hipStream_t st) {
   else { KRS_LAUNCH_APPLY(64) }
 #undef KRS_LAUNCH_APPLY
 #undef KRS_LAUNCH_FAST
+#undef KRS_LAUNCH_FAST_D
   KRS_CHECK_LAUNCH("bag_apply_fast_kernel");
   // hot rows: upper bound of the item count is nnz / kLongSeg + nnz / kChunk; surplus workgroups leave at once
   const int64_t max_long = p.nnz / kLongSeg;

@@ -639,6 +639,9 @@ int dispatch_lpr(const EmbedFwdParams& p, int row_pieces, bool one_hot, bool str
 }  // namespace krs
 
 namespace krs { extern int g_plan_variant, g_rank_mode; }   // embed_bag_plan.hip
+// krs_embed_set_option(KRS_EMBED_OPT_APPLY_DEPTH, v): gradient rows per trip of the K2 apply kernel's deep front
+// (embed_bag_bwd.hip, whose four objects read it): 0 = the remainder loop of four rows per trip, 4 (default) / 8 / 16
+namespace krs { int g_apply_depth = 4; }
 
 extern "C" int krs_embed_set_option(int key, int value) {
   if (key == KRS_EMBED_OPT_PLAN) {
@@ -654,6 +657,12 @@ extern "C" int krs_embed_set_option(int key, int value) {
   if (key == KRS_EMBED_OPT_HOTROWS) {
     KRS_REQUIRE(value == 0 || value == 64 || value == 128, "krs_embed_set_option: hot rows must be 0, 64 or 128");
     krs::g_hot_rows = value;
+    return KRS_OK;
+  }
+  if (key == KRS_EMBED_OPT_APPLY_DEPTH) {
+    KRS_REQUIRE(value == 0 || value == 4 || value == 8 || value == 16,
+                "krs_embed_set_option: apply depth must be 0, 4, 8 or 16");
+    krs::g_apply_depth = value;
     return KRS_OK;
   }
   return krs::fail(KRS_ERR_INVALID, "krs_embed_set_option: unknown key %d", key);

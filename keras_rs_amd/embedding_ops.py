@@ -24,6 +24,17 @@ from keras_rs_amd import _lib as L
 from keras_rs_amd import probe
 
 
+KRS_EMBED_OPT_APPLY_DEPTH = 5
+APPLY_DEPTH_DEFAULT = 4
+
+
+def set_apply_depth(depth: int) -> None:
+    """krs_embed_set_option(KRS_EMBED_OPT_APPLY_DEPTH, depth), process-wide: how the K2 apply kernel fetches the rest of a
+    row's segment beyond its first two lookups -- 0 = four gradient rows per trip behind a load of their values, 4 (default)
+    / 8 / 16 = that many rows requested together from sixteen values fetched in one load.  Same bits either way."""
+    L.check(L.lib().krs_embed_set_option(KRS_EMBED_OPT_APPLY_DEPTH, int(depth)), "krs_embed_set_option")
+
+
 class FusedBags:
     """Descriptors for `tables` (list of [V, D] tensors of one dtype and width) and
     `features` = [(table_index, combiner, out_col)], bags numbered feature-major."""

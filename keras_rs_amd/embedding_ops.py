@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Sequence
+from typing import NamedTuple, Sequence
 
 import numpy as np
 import torch
@@ -33,6 +33,16 @@ def set_apply_depth(depth: int) -> None:
     row's segment beyond its first two lookups -- 0 = four gradient rows per trip behind a load of their values, 4 (default)
     / 8 / 16 = that many rows requested together from sixteen values fetched in one load.  Same bits either way."""
     L.check(L.lib().krs_embed_set_option(KRS_EMBED_OPT_APPLY_DEPTH, int(depth)), "krs_embed_set_option")
+
+
+class _TableKey(NamedTuple):
+    """Cache key of FusedBags.table_desc(): everything a krs_table descriptor carries, per table."""
+
+    tables: tuple      # storage pointers
+    slots: tuple       # slot storage pointers (0: none)
+    lrs: tuple
+    rows: tuple
+    row_bases: tuple
 
 
 class FusedBags:
@@ -62,6 +72,10 @@ class FusedBags:
         self._tab_host = None
 
     # ---- descriptors ------------------------------------------------------
+    def _table_key(self, weights, slots) -> _TableKey:
+        return _TableKey(tuple(w.data_ptr() for w in weights), tuple(0 if s is None else s.data_ptr() for s in slots),
+                         tuple(self.lrs), tuple(int(w.shape[0]) for w in weights), tuple(int(b) for b in self.row_bases))
+
     def table_desc(self, weights=None, slots=None) -> torch.Tensor:
         """krs_table array on the device (rebuilt when a storage pointer moved)."""
         weights = self.tables if weights is None else weights
@@ -69,8 +83,7 @@ class FusedBags:
         # everything a descriptor carries is in the key: a caller may re-point `self.tables` at a tensor that the
         # caching allocator placed at the previous step's address with a different row count (the sharded layer's
         # transient tables do: their height is the data-dependent number of segments)
-        key = tuple(w.data_ptr() for w in weights) + tuple(0 if s is None else s.data_ptr() for s in slots) \
-            + tuple(self.lrs) + tuple(int(w.shape[0]) for w in weights) + tuple(int(b) for b in self.row_bases)
+        key = self._table_key(weights, slots)
         cacheable = weights is self.tables
         if cacheable and key == self._tab_key:
             return self._tab_dev
@@ -104,7 +117,7 @@ class FusedBags:
         rc = L.lib().krs_store_f32(self._tab_dev.data_ptr() + L.TABLE_DT.fields["lr"][1], L.TABLE_DT.itemsize,
                                    vals, n, L.stream_ptr())
         L.check(rc, "krs_store_f32")
-        self._tab_key = self._tab_key[:2 * n] + tuple(lrs) + self._tab_key[3 * n:]
+        self._tab_key = self._tab_key._replace(lrs=tuple(lrs))
         if self._tab_host is not None:
             self._tab_host["lr"] = lrs
 

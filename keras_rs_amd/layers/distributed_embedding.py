@@ -33,12 +33,12 @@ from typing import Any, Sequence
 import numpy as np
 import torch
 
-from keras_rs_amd import _lib as L
 from keras_rs_amd.autograd import EmbedBagFn, EmbedBagFusedFn
 from keras_rs_amd.embedding_ops import FusedBags
 from keras_rs_amd.layers import base
 from keras_rs_amd.layers.distributed_embedding_config import FeatureConfig
 from keras_rs_amd.layers.embed_reduce import Ragged, check_shapes_compatible
+from keras_rs_amd.layers.embedding_host import IdRangeCheck, fuse_group_inputs, next_fused_hyper
 
 SUPPORTED_PLACEMENTS = ("auto", "default_device", "sparsecore")
 
@@ -244,28 +244,8 @@ class _Group:
     _constants: Any = None                # embedding_ops.StepConstants when a constant of the update depends on `step`
 
     def next_hyper(self):
-        """Called once per fused update, from the backward pass: counts the update, refreshes the constants that depend on
-        the count -- scheduled learning rates (in the kernel descriptors) and Adam's bias correction, both kept in DEVICE
-        memory (embedding_ops.StepConstants) -- and returns the Adam / FTRL constants (None for SGD / Adagrad).  While a
-        stream is capturing nothing is counted or written: GraphedStep does that before every replay."""
-        scheduled = bool(self.table_opts) and any(callable(o.lr) for o in self.table_opts)
-        adam = self.fused.kind == "adam"
-        if not scheduled and not adam:
-            from keras_rs_amd import graphs
-
-            graphs.count_update(self)      # (per replay under GraphedStep)
-            return self.fused.hyper(self.step)
-        if self._constants is None:
-            from keras_rs_amd.embedding_ops import StepConstants
-
-            self._constants = StepConstants(
-                self, lambda: self.bags, (lambda step: [o.lr_at(step) for o in self.table_opts]) if scheduled else None,
-                self.fused.consts[:2] if adam else None)
-        self._constants.on_backward()
-        if adam:
-            b1, b2, eps = self.fused.consts
-            return (b1, b2, eps, self._constants.bias_correction)
-        return self.fused.hyper(self.step)
+        """Called once per fused update, from the backward pass (embedding_host.next_fused_hyper)."""
+        return next_fused_hyper(self, self.fused, self.table_opts, lambda: self.bags)
 
 
 class DistributedEmbedding(base.Layer):
@@ -287,9 +267,8 @@ class DistributedEmbedding(base.Layer):
         self.update_stats = update_stats
         self._lock = threading.Lock()
         self._anchor = None
-        self._err_dev = None      # device int32[1]: the lookup kernels OR their KRS_FLAG_* bits into it
-        self._err_host = None     # its page-locked mirror, refreshed asynchronously after every call
-        self._err_event = None
+        self._id_check = IdRangeCheck("DistributedEmbedding: an embedding id was out of range for its table "
+                                      "(ids are never clamped; the lookup contributed nothing)")
         self._init_feature_configs_structures(feature_configs)
         self._groups: dict[str, list[_Group]] = {}
         self._table_params: dict[int, torch.nn.Parameter] = {}
@@ -502,62 +481,10 @@ class DistributedEmbedding(base.Layer):
         fcs = self._placement_to_path_to_feature_config[placement]
         out_inputs, out_weights = {}, {}
         for gi, g in enumerate(self._groups[placement]):
-            dev = g.bags.tables[0].device
-            id_parts, w_parts, hots, lens = [], [], [], []
-            ragged = False
-            batch = None
-            use_w = weights is not None
-            for path in g.paths:
-                x = inputs[path]
-                w = None if weights is None else weights[path]
-                x, w = _ragged_numpy_to_csr(x, w)
-                if isinstance(x, Ragged):
-                    ragged = True
-                    vals = _to_tensor(x.values)
-                    offs = np.asarray(_to_numpy(x.row_offsets), dtype=np.int64)
-                    b = len(offs) - 1
-                    id_parts.append(vals.reshape(-1))
-                    lens.append(np.diff(offs))
-                    hots.append(None)
-                    if w is not None:
-                        w_parts.append(_to_tensor(w.values if isinstance(w, Ragged) else w).reshape(-1))
-                else:
-                    t = _to_tensor(x)
-                    if t.dim() == 1:
-                        # rank-1: no reduction; weights only survive for "sum" (embed_reduce.py:224)
-                        if fcs[path].table.combiner != "sum":
-                            w = None if w is None else torch.ones(t.shape)
-                        t = t.reshape(-1, 1)
-                    elif t.dim() != 2:
-                        raise ValueError(f"Feature '{path}': inputs must be rank 1 or 2, got {tuple(t.shape)}")
-                    b = t.shape[0]
-                    id_parts.append(t.reshape(-1))
-                    hots.append(int(t.shape[1]))
-                    lens.append(np.full(b, t.shape[1], dtype=np.int64))
-                    if w is not None:
-                        wt = _to_tensor(w).float()
-                        if wt.numel() != t.numel():
-                            raise ValueError(f"Feature '{path}': weights shape {tuple(wt.shape)} does not match "
-                                             f"inputs shape {tuple(t.shape)}")
-                        w_parts.append(wt.reshape(-1))
-                if batch is None:
-                    batch = b
-                elif batch != b:
-                    raise ValueError("All features of a DistributedEmbedding call must share the batch size")
-            ids = _cat_index(id_parts).to(dev, non_blocking=True)
-            offsets = None
-            if ragged:
-                offsets = torch.from_numpy(
-                    np.concatenate([[0], np.cumsum(np.concatenate(lens))]).astype(np.int32)).to(dev, non_blocking=True)
-                hots_t = None
-            else:
-                hots_t = tuple(hots)
-            key = f"group{gi}"
-            out_inputs[key] = {"ids": ids, "offsets": offsets, "hots": hots_t, "batch": batch}
-            if use_w:
-                if len(w_parts) != len(g.paths):
-                    raise ValueError("weights must be given for every feature or for none")
-                out_weights[key] = torch.cat([p.reshape(-1) for p in w_parts]).float().to(dev, non_blocking=True)
+            fi = fuse_group_inputs(g.paths, lambda path: fcs[path].table.combiner, inputs, weights,
+                                   g.bags.tables[0].device, np.int32)
+            out_weights[f"group{gi}"] = fi.pop("weights")
+            out_inputs[f"group{gi}"] = fi
         res = {"inputs": out_inputs}
         if weights is not None:
             res["weights"] = out_weights
@@ -585,7 +512,7 @@ class DistributedEmbedding(base.Layer):
                     g.bags.slots = [self._table_slots[id(tc)] for tc in g.table_configs]
                     g.bags.tables = [self._table_params[id(tc)] for tc in g.table_configs]
                     g.bags._tab_key = None
-        self._err_dev = self._err_host = self._err_event = None
+        self._id_check.reset()
         return out
 
     def get_extra_state(self):
@@ -602,48 +529,12 @@ class DistributedEmbedding(base.Layer):
                     g.step = int(its[f"{pl}/{gi}"])
 
     # ---- out-of-range ids: flagged by the kernels, raised lazily (no per-step host sync) ---------------
-    def _err_flag(self, device) -> torch.Tensor | None:
-        if device.type != "cuda":
-            return None
-        if self._err_dev is None:
-            self._err_dev = torch.zeros(1, dtype=torch.int32, device=device)
-            self._err_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        return self._err_dev
-
-    def _err_snapshot(self) -> None:
-        """Queues a copy of the error word into page-locked memory behind the lookups just launched."""
-        if self._err_dev is not None:
-            self._err_host.copy_(self._err_dev, non_blocking=True)
-            if base.stream_capturing():
-                # inside a graph the copy is a node of every replay; there is no event to poll: check_ids(wait=True)
-                # between replays waits for the device instead
-                self._err_event, self._err_in_graph = None, True
-                return
-            self._err_event = torch.cuda.Event()
-            self._err_event.record()
-
     def check_ids(self, wait: bool = False) -> None:
         """Raises IndexError if a lookup launched by an earlier call met an id outside [0, vocabulary_size)
         (such ids contribute nothing; they are never clamped).  Called at the start of every `call` without
         waiting for the GPU (only snapshots that have already arrived are looked at), with wait=True from
         get_embedding_tables() and by callers that want the verdict on the last step now."""
-        if base.stream_capturing():
-            return
-        ev = self._err_event
-        if ev is None:
-            if not (wait and getattr(self, "_err_in_graph", False)):
-                return
-            torch.cuda.current_stream(self._err_dev.device).synchronize()   # replays of a captured step
-        elif wait:
-            ev.synchronize()
-        elif not ev.query():
-            return
-        self._err_event = None
-        if int(self._err_host.item()) & L.FLAG_ID_OUT_OF_RANGE:
-            self._err_dev.zero_()
-            self._err_host.zero_()
-            raise IndexError("DistributedEmbedding: an embedding id was out of range for its table "
-                             "(ids are never clamped; the lookup contributed nothing)")
+        self._id_check.check(wait)
 
     def _call_groups(self, placement: str, inputs: dict, weights: dict | None):
         outputs = {}
@@ -652,7 +543,7 @@ class DistributedEmbedding(base.Layer):
             fi = inputs[key]
             w = None if weights is None else weights[key]
             out_dtype = self.compute_dtype
-            err = self._err_flag(fi["ids"].device)
+            err = self._id_check.flag(fi["ids"].device)
             if placement == "sparsecore":
                 lead = self.slab_lead_cols if len(self._groups[placement]) == 1 else 0
                 slab, *out = EmbedBagFusedFn.apply(g.bags, fi["ids"], fi["batch"], fi["hots"], fi["offsets"], w,
@@ -749,7 +640,7 @@ class DistributedEmbedding(base.Layer):
             outs["sparsecore"] = self._sparsecore_call(**pre["sparsecore"], training=training)
         if "default_device" in pre:
             outs["default_device"] = self._default_device_call(**pre["default_device"], training=training)
-        self._err_snapshot()
+        self._id_check.snapshot()
         return base.map_structure_up_to(
             self._feature_deeply_nested_placement_and_paths, lambda pp: outs[pp.placement][pp.path],
             self._feature_deeply_nested_placement_and_paths, is_leaf=_is_placement_leaf)
@@ -924,46 +815,9 @@ def concat_features(tensors: Sequence[torch.Tensor]) -> torch.Tensor:
     return torch.cat(tensors, dim=-1)
 
 
-def _to_numpy(x):
-    if isinstance(x, torch.Tensor):
-        return x.detach().cpu().numpy()
-    return np.asarray(x)
-
-
-def _to_tensor(x) -> torch.Tensor:
-    if isinstance(x, torch.Tensor):
-        return x
-    if hasattr(x, "numpy") and callable(x.numpy):
-        x = x.numpy()
-    return torch.from_numpy(np.ascontiguousarray(x))
-
-
-def _cat_index(parts: Sequence[torch.Tensor]) -> torch.Tensor:
-    dt = torch.int64 if any(p.dtype == torch.int64 for p in parts) else torch.int32
-    parts = [p.to(dt) for p in parts]
-    if all(p.device.type == "cpu" for p in parts) and torch.cuda.is_available():
-        # host ids: concatenate straight into page-locked memory, so that the upload that follows is a
-        # true asynchronous DMA (the loader threads of data.ThreadedDataLoader overlap it with compute)
-        buf = torch.empty(sum(p.numel() for p in parts), dtype=dt, pin_memory=True)
-        return torch.cat(parts, out=buf) if len(parts) > 1 else buf.copy_(parts[0].reshape(-1))
-    return torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()
-
-
 def _shape_of(x):
     if isinstance(x, Ragged):
         return (len(x.row_offsets) - 1, None)
     if isinstance(x, np.ndarray) and x.dtype == object:
         return (len(x), None)
     return tuple(x.shape) if hasattr(x, "shape") else None
-
-
-def _ragged_numpy_to_csr(x, w):
-    """numpy object arrays of rows (the ragged form of base:31-92) -> Ragged CSR.
-    Results equal the reference's pad-to-dense form (padding carries weight 0)."""
-    if isinstance(x, np.ndarray) and x.dtype == object and len(x) > 0:
-        rx = Ragged.from_rows(list(x), dtype=np.asarray(x[0]).dtype if np.asarray(x[0]).dtype.kind == "i" else np.int32)
-        rw = None
-        if w is not None:
-            rw = Ragged(Ragged.from_rows(list(w), dtype=np.float32).values, rx.row_offsets)
-        return rx, rw
-    return x, w

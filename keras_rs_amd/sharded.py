@@ -66,6 +66,7 @@ from keras_rs_amd.layers import base
 from keras_rs_amd.layers.distributed_embedding import (DistributedEmbedding, FusedOptimizer,
                                                        resolve_fused_optimizer)
 from keras_rs_amd.layers.distributed_embedding_config import FeatureConfig, TableConfig
+from keras_rs_amd.layers.embedding_host import IdRangeCheck, fuse_group_inputs, next_fused_hyper
 
 
 class HipShardKernels:
@@ -102,25 +103,31 @@ class HipShardKernels:
         return fb
 
     # ---- K6 -------------------------------------------------------------------------------------
-    def route(self, desc: np.ndarray, ids, offsets, weights, batch: int, n_shards: int, emit_w: bool, err_flag=None):
-        """krs_shard_route.  desc: SHARD_FEATURE_DT array.  Returns dict(packed, seg_grow, bag_seg, counts):
-        device tensors, counts = int64 [3, n_shards] (lookups, segments, packed words per owner)."""
+    def _route_buffers(self, desc: np.ndarray, ids, weights, batch: int, n_shards: int):
+        """What both route forms need: the device copy of `desc` (cached), the outputs whose size does not depend on the
+        form, the workspace and fp32 weights."""
         dev = ids.device
         key = (desc.tobytes(), str(dev))
         ddev = self._desc_cache.get(key)
         if ddev is None:
             ddev = self._desc_cache[key] = L.struct_to_device(desc, dev)
-        nnz, n_feats = ids.numel(), len(desc)
-        n_bags = batch * n_feats
-        packed = torch.empty(max(nnz * (2 + int(emit_w)), 1), dtype=torch.int32, device=dev)
+        nnz, n_bags = ids.numel(), batch * len(desc)
         seg_bag = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
-        seg_grow = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         bag_seg = torch.empty((max(n_bags, 1), n_shards), dtype=torch.int32, device=dev)
         counts = torch.empty((3, n_shards), dtype=torch.int64, device=dev)
         wsb = int(L.lib().krs_shard_route_workspace_bytes(nnz, n_bags, n_shards))
         ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
         if weights is not None and weights.dtype != torch.float32:
             weights = weights.float()
+        return ddev, seg_bag, bag_seg, counts, ws, weights
+
+    def route(self, desc: np.ndarray, ids, offsets, weights, batch: int, n_shards: int, emit_w: bool, err_flag=None):
+        """krs_shard_route.  desc: SHARD_FEATURE_DT array.  Returns dict(packed, seg_grow, bag_seg, counts):
+        device tensors, counts = int64 [3, n_shards] (lookups, segments, packed words per owner)."""
+        ddev, seg_bag, bag_seg, counts, ws, weights = self._route_buffers(desc, ids, weights, batch, n_shards)
+        dev, nnz, n_feats = ids.device, ids.numel(), len(desc)
+        packed = torch.empty(max(nnz * (2 + int(emit_w)), 1), dtype=torch.int32, device=dev)
+        seg_grow = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         rc = L.lib().krs_shard_route(
             L.ptr(ddev), desc.ctypes.data_as(C.c_void_p), n_feats, L.ptr(ids), L.itype(ids),
             L.ptr(offsets), L.itype(offsets) if offsets is not None else L.I32, L.ptr(weights),
@@ -150,23 +157,11 @@ class HipShardKernels:
                      cap_l: int, cap_s: int, err_flag=None):
         """krs_shard_route_static: fixed-size blocks.  Returns dict(packed [n_shards, W] int32, seg_grow
         [n_shards*cap_s], bag_seg (segment SLOTS), counts [3, n_shards] on the device)."""
-        dev = ids.device
-        key = (desc.tobytes(), str(dev))
-        ddev = self._desc_cache.get(key)
-        if ddev is None:
-            ddev = self._desc_cache[key] = L.struct_to_device(desc, dev)
-        nnz, n_feats = ids.numel(), len(desc)
-        n_bags = batch * n_feats
+        ddev, seg_bag, bag_seg, counts, ws, weights = self._route_buffers(desc, ids, weights, batch, n_shards)
+        dev, nnz, n_feats = ids.device, ids.numel(), len(desc)
         words = int(L.lib().krs_shard_static_block_words(cap_l, cap_s, int(emit_w)))
         packed = torch.empty((n_shards, words), dtype=torch.int32, device=dev)
-        seg_bag = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         seg_grow = torch.empty(n_shards * cap_s, dtype=torch.int32, device=dev)
-        bag_seg = torch.empty((max(n_bags, 1), n_shards), dtype=torch.int32, device=dev)
-        counts = torch.empty((3, n_shards), dtype=torch.int64, device=dev)
-        wsb = int(L.lib().krs_shard_route_workspace_bytes(nnz, n_bags, n_shards))
-        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-        if weights is not None and weights.dtype != torch.float32:
-            weights = weights.float()
         rc = L.lib().krs_shard_route_static(
             L.ptr(ddev), desc.ctypes.data_as(C.c_void_p), n_feats, L.ptr(ids), L.itype(ids),
             L.ptr(offsets), L.itype(offsets) if offsets is not None else L.I32, L.ptr(weights),
@@ -289,6 +284,7 @@ class _ShardGroup:
     step: int = 0
     pname: str = ""
     sname: str = ""
+    _constants: Any = None     # embedding_ops.StepConstants when a constant of the update depends on `step`
 
 
 def _release_plan_of(layer_ref, gi, owns) -> None:
@@ -489,9 +485,9 @@ class ShardedDistributedEmbedding(base.Layer):
         self._grow_luts: dict = {}        # (batch, features, lead slots, device) -> row of (sample, feature) in the slab gradient
         self._host_counts = None
         self._collectives_at_world1 = False   # bench --rccl-self: run the collectives through a one-rank communicator
-        self._err_dev = self._err_host = self._err_event = None
+        self._id_check = IdRangeCheck("ShardedDistributedEmbedding: an embedding id was out of range for its table "
+                                      "(ids are never clamped; the lookup was dropped)")
         self.last_exchange: dict = {}    # host-side counts of the last lookup (tests / load-balance diagnostics)
-        self._step_constants: dict = {}  # group -> embedding_ops.StepConstants (scheduled rates / Adam bias correction)
 
     # single-group conveniences (the common case: one width, one optimizer) -- kept for callers / tests
     @property
@@ -587,91 +583,24 @@ class ShardedDistributedEmbedding(base.Layer):
             self._replicated.set_embedding_tables(tables)
 
     # ---------------------------------------------------------------- out-of-range ids (as DistributedEmbedding)
-    def _err_flag(self, device):
-        if device.type != "cuda":
-            return None
-        if self._err_dev is None:
-            self._err_dev = torch.zeros(1, dtype=torch.int32, device=device)
-            self._err_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        return self._err_dev
-
     def check_ids(self, wait: bool = False) -> None:
         """IndexError if an earlier lookup met an id outside [0, vocabulary_size) of its table (such lookups are
         dropped before the exchange: they reach no row of any table on any rank)."""
         if self._replicated is not None:
             self._replicated.check_ids(wait)
-        if base.stream_capturing():
-            return
-        ev = self._err_event
-        if ev is None:
-            if not (wait and getattr(self, "_err_in_graph", False)):
-                return
-            torch.cuda.current_stream(self._err_dev.device).synchronize()   # replays of a captured step
-        elif wait:
-            ev.synchronize()
-        elif not ev.query():
-            return
-        self._err_event = None
-        if int(self._err_host.item()) & L.FLAG_ID_OUT_OF_RANGE:
-            self._err_dev.zero_()
-            self._err_host.zero_()
-            raise IndexError("ShardedDistributedEmbedding: an embedding id was out of range for its table "
-                             "(ids are never clamped; the lookup was dropped)")
+        self._id_check.check(wait)
 
     # ---------------------------------------------------------------- inputs
     def preprocess(self, inputs: dict, weights: dict | None = None, training: bool = False):
         """{feature: ids} -> per group one feature-major id buffer (+ CSR offsets when any feature is ragged)."""
-        from keras_rs_amd.layers.distributed_embedding import _ragged_numpy_to_csr
-        from keras_rs_amd.layers.embed_reduce import Ragged
-
         if not self.built:
             self.build()
-        pre: dict = {"groups": []}
-        for g in self._sgroups:
-            dev = getattr(self, g.pname).device
-            parts, wparts, hots, lens, batch = [], [], [], [], None
-            ragged = False
-            for p in g.paths:
-                x = inputs[p]
-                w = None if weights is None else weights[p]
-                x, w = _ragged_numpy_to_csr(x, w)
-                if isinstance(x, Ragged):
-                    ragged = True
-                    vals = x.values if isinstance(x.values, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x.values))
-                    offs = np.asarray(x.row_offsets.cpu() if isinstance(x.row_offsets, torch.Tensor) else x.row_offsets,
-                                      dtype=np.int64)
-                    b = len(offs) - 1
-                    t = vals.reshape(-1)
-                    hots.append(None)
-                    lens.append(np.diff(offs))
-                    if w is not None:
-                        w = w.values if isinstance(w, Ragged) else w
-                else:
-                    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-                    if t.dim() == 1:
-                        t = t.reshape(-1, 1)
-                    b = t.shape[0]
-                    hots.append(int(t.shape[1]))
-                    lens.append(np.full(b, t.shape[1], dtype=np.int64))
-                batch = b if batch is None else batch
-                if b != batch:
-                    raise ValueError("all features must share the batch size")
-                parts.append(t.reshape(-1).to(torch.int64 if t.dtype == torch.int64 else torch.int32))
-                if weights is not None:
-                    w = w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w))
-                    wparts.append(w.reshape(-1).float())
-            dt = torch.int64 if any(q.dtype == torch.int64 for q in parts) else torch.int32
-            ids = torch.cat([q.to(dt) for q in parts]).to(dev, non_blocking=True)
-            w = torch.cat(wparts).to(dev, non_blocking=True) if weights is not None else None
-            offsets = None
-            if ragged:
-                offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(np.concatenate(lens))]).astype(np.int64)).to(dev)
-            pre["groups"].append({"ids": ids, "hots": None if ragged else tuple(hots), "batch": batch,
-                                  "offsets": offsets, "weights": w})
+        pre: dict = {"groups": [fuse_group_inputs(g.paths, lambda p: self._feature_configs[p].table.combiner, inputs, weights,
+                                                  getattr(self, g.pname).device, np.int64) for g in self._sgroups]}
         if self._replicated is not None:
             rp = [p for p in self._paths if self._where[p][0] == "rep"]
             pre["replicated"] = self._replicated.preprocess({p: inputs[p] for p in rp},
-                                                            None if weights is None else {p: weights[p] for p in rp})
+                                                            None if weights is None else {p: weights.get(p) for p in rp})
         return {"preprocessed_inputs_per_placement": {"sparsecore": pre}}
 
     # ---------------------------------------------------------------- step
@@ -691,13 +620,7 @@ class ShardedDistributedEmbedding(base.Layer):
             out.update(zip(g.paths, outs))
         if self._replicated is not None:
             out.update(self._replicated(pre["replicated"]))
-        if self._err_dev is not None:
-            self._err_host.copy_(self._err_dev, non_blocking=True)
-            if base.stream_capturing():
-                self._err_event, self._err_in_graph = None, True
-            else:
-                self._err_event = torch.cuda.Event()
-                self._err_event.record()
+        self._id_check.snapshot()
         return {p: out[p] for p in self._paths}
 
     def _a2a(self, send: torch.Tensor, send_counts: list | None = None, recv_counts: list | None = None) -> torch.Tensor:
@@ -882,7 +805,7 @@ class ShardedDistributedEmbedding(base.Layer):
         # (probe.span: per-phase event pairs when bench.py is probing -- `phases` of its line; otherwise one global read)
         with probe.span("route"):
             r = k.route_static(self._route_desc(g, batch, hots), ids, offsets, weights, batch, n, emit_w, cap_l, cap_s,
-                               self._err_flag(ids.device))
+                               self._id_check.flag(ids.device))
         with probe.span("a2a_ids", off_rank * 4 * n * r["packed"].shape[1]):
             recv_packed = self._a2a(r["packed"])                                # [n, W]: equal splits, no counts
         with probe.span("unpack"):
@@ -914,7 +837,7 @@ class ShardedDistributedEmbedding(base.Layer):
                 xs = self._xstream
                 if xs is None:
                     xs = self._xstream = torch.cuda.Stream(device=ids.device)
-                self._err_flag(ids.device)      # (allocated on the main stream, before the fork)
+                self._id_check.flag(ids.device)      # (allocated on the main stream, before the fork)
                 xs.wait_stream(main)            # the ids (and the previous call's use of the descriptors) are ordered first
                 with torch.cuda.stream(xs):
                     r, rows, w, off, stats = self._route_exchange(g, cap_l, cap_s, ids, batch, hots, fi["offsets"],
@@ -1030,7 +953,7 @@ class ShardedDistributedEmbedding(base.Layer):
             if cap is not None:
                 return self._forward_static(gi, g, cap, key, ids, batch, hots, offsets, weights, lead, emit_w)
         with probe.span("route"):
-            r = k.route(self._route_desc(g, batch, hots), ids, offsets, weights, batch, n, emit_w, self._err_flag(dev))
+            r = k.route(self._route_desc(g, batch, hots), ids, offsets, weights, batch, n, emit_w, self._id_check.flag(dev))
         with probe.span("counts_host_wait"):
             mine, theirs = self._exchange_sizes(r["counts"])
         send_cnt, send_segs, send_words = mine
@@ -1093,29 +1016,16 @@ class ShardedDistributedEmbedding(base.Layer):
         off_rank = (self.world - 1) / self.world if self.world > 1 else 1.0
         with probe.span("a2a_grads", off_rank * dpart.numel() * dpart.element_size()):
             dseg = self._a2a(dpart, s["send_segs"], s["recv_segs"])               # to the owners
-        if (callable(g.fused.lr) or g.fused.kind == "adam") and getattr(k, "device_step_constants", False):
-            # constants that depend on the update count live in device memory (embedding_ops.StepConstants): written here by an
-            # eager step, before every replay by GraphedStep when this backward is being captured
-            sc = self._step_constants.get(gi)
-            if sc is None:
-                from keras_rs_amd.embedding_ops import StepConstants
-
-                sc = self._step_constants[gi] = StepConstants(
-                    g, lambda g=g: k._bags_for(getattr(self, g.pname).data, self._slot(g), 0.0),
-                    (lambda step, g=g: [g.fused.lr_at(step)]) if callable(g.fused.lr) else None,
-                    g.fused.consts[:2] if g.fused.kind == "adam" else None)
-            sc.on_backward()
-            lr = None if callable(g.fused.lr) else g.fused.lr_at(g.step)
-            hyper = g.fused.consts + (sc.bias_correction,) if g.fused.kind == "adam" else g.fused.hyper(g.step)
+        stepwise = callable(g.fused.lr) or g.fused.kind == "adam"     # a constant of the update depends on its count
+        if not stepwise or getattr(k, "device_step_constants", False):
+            hyper = next_fused_hyper(g, g.fused, [g.fused],
+                                     lambda: k._bags_for(getattr(self, g.pname).data, self._slot(g), 0.0))
+            lr = None if callable(g.fused.lr) else g.fused.lr_at(g.step)   # (None: StepConstants wrote it into the descriptor)
         else:
-            from keras_rs_amd import graphs
-
+            # eager by-value fallback for kernels without device-resident constants (the oracle-backed test kernels)
             lr = g.fused.lr_at(g.step)
-            if callable(g.fused.lr) or g.fused.kind == "adam":
-                g.step += 1               # (test kernels without device-resident constants: by-value arguments, eager only)
-            else:
-                graphs.count_update(g)    # (per replay under GraphedStep)
-            hyper = g.fused.hyper(max(g.step, 1))
+            g.step += 1
+            hyper = g.fused.hyper(g.step)
         plan = s.get("plan")
         ws = None
         if plan is not None:

@@ -1538,3 +1538,54 @@ def test_scheduled_learning_rates_of_many_tables_reach_the_kernels_through_devic
         for t in (0, 1, 31, 32, 39):
             np.testing.assert_allclose(got[f"t{t}"].cpu().numpy(), exp[f"t{t}"], rtol=2e-5, atol=2e-6, err_msg=f"step {step} table {t}")
     assert emb._groups["sparsecore"][0].step == 3
+
+
+def test_sharded_embedding_reports_out_of_range_ids_lazily():
+    # test_distributed_embedding_reports_out_of_range_ids_lazily for the sharded layer (world 1, HIP kernels): the route
+    # kernel drops the bad lookup and raises the flag; the layer reports it on request or at a later call
+    kl = _layers()
+    from keras_rs_amd.sharded import ShardedDistributedEmbedding
+
+    tcs = [kl.TableConfig(f"t{i}", 10, 8, placement="sparsecore", optimizer="sgd", combiner="sum") for i in range(2)]
+    layer = ShardedDistributedEmbedding({k: kl.FeatureConfig(k, tc, (4, 2), (4, 8)) for k, tc in zip("ab", tcs)})
+    good = {"a": np.array([[1, 2], [3, 4], [5, 6], [7, 8]], np.int32), "b": np.array([[0, 9], [8, 1], [2, 7], [6, 3]], np.int32)}
+    bad = {"a": good["a"], "b": good["b"].copy()}
+    bad["b"][2, 1] = 10
+    with torch.no_grad():
+        out = layer(good)
+        layer.check_ids(wait=True)                                     # nothing to report
+        tab = layer.get_embedding_tables()["t1"].clone()
+        out_bad = layer(bad)
+        # the bad lookup contributed nothing (not row 0, not the last row)
+        torch.testing.assert_close(out_bad["b"][2].float(), tab[2].float())
+        torch.testing.assert_close(out_bad["b"][0].float(), out["b"][0].float())
+        torch.testing.assert_close(out_bad["a"].float(), out["a"].float())
+        with pytest.raises(IndexError):
+            layer.check_ids(wait=True)
+        layer.check_ids(wait=True)                                     # the flag was consumed
+        layer(bad)
+        torch.cuda.synchronize()
+        with pytest.raises(IndexError):                                # ... or it surfaces at the next call
+            layer(good)
+        layer(good)
+        layer.check_ids(wait=True)
+
+
+# (DistributedEmbedding with a scheduled SGD is left out: three eager updates of it are counted by
+#  test_scheduled_learning_rates_of_many_tables_reach_the_kernels_through_device_memory)
+@pytest.mark.parametrize("sharded,kind", [(False, "adagrad"), (False, "adam"),
+                                          (True, "adagrad"), (True, "adam"), (True, "scheduled_sgd")])
+def test_three_eager_training_steps_count_three_updates(sharded, kind):
+    # one case per branch of embedding_host.next_fused_hyper: constants that ignore the count, Adam, a schedule
+    kl = _layers()
+    from keras_rs_amd.sharded import ShardedDistributedEmbedding
+
+    opt = {"adagrad": kl.Adagrad(0.1, 0.1), "adam": kl.Adam(0.05), "scheduled_sgd": kl.SGD(lambda step: 0.5 / (1.0 + step))}[kind]
+    t = kl.TableConfig("t", 16, 8, placement="sparsecore", optimizer=opt, combiner="sum")
+    layer = (ShardedDistributedEmbedding if sharded else kl.DistributedEmbedding)({"a": kl.FeatureConfig("a", t, (4, 2), (4, 8))})
+    rng = np.random.default_rng(3)
+    for _ in range(3):
+        out = layer({"a": rng.integers(0, 16, (4, 2)).astype(np.int32)})["a"]
+        (out * torch.from_numpy(rng.uniform(-1, 1, (4, 8)).astype(np.float32)).to(DEV)).sum().backward()
+    its = layer.get_extra_state()["iterations"]
+    assert (list(its) if sharded else list(its.values())) == [3]

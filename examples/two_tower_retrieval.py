@@ -8,10 +8,11 @@ order, then serving with BruteForceRetrieval.
 Stages of `retrieval_task_loss`: scores -> SamplingProbabilityCorrection -> RemoveAccidentalHits ->
 HardNegativeMining -> CategoricalCrossentropy.  The scores are one GEMM; everything after it is K11 / K8 kernels.
 
-    python examples/two_tower_retrieval.py --fused    # the same run on InBatchSoftmaxLoss (K13)
+    python examples/two_tower_retrieval.py --fused    # the same run on InBatchSoftmaxLoss (K13 / K14)
 
-`fused_retrieval_task_loss` is the same loss without hard-negative mining, computed from the embeddings by the fused
-kernels: the [B, N] scores are never stored, so it also runs at batch sizes where the score matrix does not fit.
+`fused_retrieval_task_loss` is the same loss, hard-negative mining included, computed from the embeddings by the fused
+kernels: the [B, N] scores are never stored, so it also runs at batch sizes where the score matrix does not fit.  Both
+runs train one objective (the fused one keeps its scores in fp32 and sends ties to the lowest index).
 """
 
 from __future__ import annotations
@@ -45,10 +46,11 @@ def retrieval_task_loss(query_emb: torch.Tensor, cand_emb: torch.Tensor, cand_id
 
 
 def fused_retrieval_task_loss(query_emb: torch.Tensor, cand_emb: torch.Tensor, cand_ids: torch.Tensor | None = None,
-                              cand_prob: torch.Tensor | None = None) -> torch.Tensor:
-    """retrieval_task_loss without hard-negative mining, on InBatchSoftmaxLoss: memory O((B + N) D)."""
-    return kl.InBatchSoftmaxLoss()(query_emb, cand_emb, candidate_ids=cand_ids,
-                                   candidate_sampling_probability=cand_prob)
+                              cand_prob: torch.Tensor | None = None,
+                              num_hard_negatives: int | None = None) -> torch.Tensor:
+    """retrieval_task_loss on InBatchSoftmaxLoss: the [B, N] scores are never stored."""
+    return kl.InBatchSoftmaxLoss(num_hard_negatives=num_hard_negatives)(
+        query_emb, cand_emb, candidate_ids=cand_ids, candidate_sampling_probability=cand_prob)
 
 
 def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000, dim: int = 32,
@@ -66,7 +68,7 @@ def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000,
         opt.zero_grad()
         if fused:
             value = fused_retrieval_task_loss(query_tower(user_ids), cand_tower(item_ids), cand_ids=item_ids,
-                                              cand_prob=item_prob)
+                                              cand_prob=item_prob, num_hard_negatives=32)
         else:
             value = retrieval_task_loss(query_tower(user_ids), cand_tower(item_ids), cand_ids=item_ids,
                                         cand_prob=item_prob, num_hard_negatives=32)

@@ -921,6 +921,50 @@ int krs_retrieval_xent_bwd(const void* q, int64_t ldq, const void* c, int64_t ld
                            void* dq, int64_t lddq, void* dc, int64_t lddc, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * K14  Hard-negative mining for the in-batch softmax loss: the fused stage 1 of K8 on K13's corrected score
+ *
+ * Replaces keras_rs.layers.HardNegativeMining (hard_negative_mining.py:43-94) in front of
+ * CategoricalCrossentropy(from_logits=True, label_smoothing=ls) without ever storing the [b, n] scores.  For query row
+ * i, with k = min(num_hard_negatives, n - 1) chosen by the caller:
+ *     s_ij   = sum_d q_id c_jd (fp32 accumulate) + bias_j + hit_value * [ids_j == ids_{pos_i} and j != pos_i]
+ *              (K13's score; the two corrections are added in this order, each rounded to fp32)
+ *     M_i    = the k candidates j != pos_i that come first in K8's total order: the fp32 key s_ij descending, then
+ *              the index ascending; -0.0 ranks as +0.0
+ *     loss_i = softmax cross-entropy over the k + 1 logits (s_{i,pos_i}, s_{i,M_i}) against
+ *              y' = (1 - ls) [slot 0] + ls / (k + 1)
+ * The reference's top_k(logits + labels * MAX_FLOAT, k + 1, sorted=False) leaves the choice among equal scores at
+ * the k-th place open; the loss does not depend on it, the gradient does.  Here the tie goes to the LOWEST index.
+ * Scores stay in fp32 (K13's known divergence from the stored-matrix head, which rounds bf16 scores first) and must
+ * be finite.
+ *
+ * krs_retrieval_mine writes, per row, out_idx [b, k] int32 (M_i, sorted in the total order), out_scores [b, k] fp32
+ * (the corrected s_ij of those candidates, -0.0 as +0.0) and pos_score [b] fp32 (s_{i,pos_i}).  The softmax over the
+ * k + 1 logits is K11 (krs_softmax_xent); its gradient P [b, k+1] gives dq_i = sum_m P_im c[idx_im] (K1 with
+ * weights = P) and dc_j = sum_{(i,m): idx_im = j} P_im q_i (K2's plan + dense form with grad = q), which is what
+ * keras_rs_amd.retrieval_ops.retrieval_xent(num_hard_negatives=...) runs.
+ *
+ * pos: int32 [b], or NULL for pos_i = i.  A pos_i outside [0, n) is never used as an address: the row then has no
+ * positive and no accidental hits, its k candidates are mined among all n, and pos_score[i] is NaN.  The host op
+ * makes that row's loss and its P row NaN: its dq row is NaN, and in dc exactly the rows of the k candidates mined
+ * for it are NaN (K13, which touches every candidate for every row, makes all of dc NaN; here the other rows stay
+ * finite).
+ *
+ * q [b, d], c [n, d]: fp32 or bf16 (one dtype), row strides ldq, ldc >= d in elements.  cand_bias fp32 [n] or NULL;
+ * cand_ids int32 / int64 [n] (id_dtype: krs_itype) or NULL.  1 <= k <= min(n - 1, 128) and d <= 512; anything else,
+ * null q / c / outputs, a bad dtype and n > 2^31 - 1 are KRS_ERR_INVALID (the Python wrapper routes larger k or d
+ * to a slab path built from krs_gemm, krs_topk_rows and K11).  b == 0 is a successful no-op.  Workspace:
+ * krs_retrieval_mine_workspace_bytes = the slice lists, b * S * k pairs of 8 bytes with S = the number of candidate
+ * slices of stage 1 (a multiple of 8, about max(8, min(2048 / ceil(b / 32), n / 8192))), plus b * pow2(k) pairs when
+ * S * k > 2048; it need not be initialised; too little is KRS_ERR_WORKSPACE.  No float atomics, no host
+ * synchronisation, bit-identical from call to call.
+ * ------------------------------------------------------------------------- */
+size_t krs_retrieval_mine_workspace_bytes(int64_t b, int64_t n, int64_t d, int k, int dtype);
+int krs_retrieval_mine(const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b, int64_t n,
+                       int64_t d, int k, const int32_t* pos, const float* cand_bias, const void* cand_ids, int id_dtype,
+                       float hit_value, int32_t* out_idx, float* out_scores, float* pos_score, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

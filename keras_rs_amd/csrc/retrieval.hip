@@ -21,6 +21,9 @@
 //                             queue in LDS, and writes the slice's k best pairs per row; the same selection code as
 //                             krs_topk_rows then merges the S slices of each row.  Other (k, D): krs_gemm into a
 //                             query-chunked fp32 slab, then the krs_topk_rows selection.
+//   * krs_retrieval_mine      the same two stages for the hard negatives of the in-batch softmax loss: stage 1 ranks
+//                             K13's corrected score (bias, accidental hits) and leaves each row's positive out of the
+//                             queue, storing its score instead.
 #include <algorithm>
 
 #include "krs_list.h"
@@ -245,6 +248,15 @@ struct Stage1 {
   int row_bytes;       // K extent of the LDS query tile in bytes (d * ES rounded up to 32 bytes)
   uint64_t* out;       // [b, S, k]
 };
+// what the mining variant of stage 1 adds: the corrections of K13's score and the positive of each query row
+struct Mine {
+  const int32_t* pos;   // [b] or null (pos_i = i)
+  const float* bias;    // [n] or null
+  const void* ids;      // [n] int32 / int64 or null
+  int id64;
+  float hit;
+  float* pos_score;     // [b]
+};
 
 // one wave sorts a row queue of m <= 256 pairs (4 per lane, descending), keeps the first k and returns the new
 // threshold key (0 while fewer than k pairs were seen); `q` is rewritten with the kept pairs
@@ -304,14 +316,20 @@ __device__ uint32_t wave_compact(uint64_t* q, int m, int k, int lane) {
 // grid: S * qtiles workgroups of 256 threads.  The query tiles of one slice run back to back on one XCD (workgroup
 // ids are dealt round-robin to the 8 XCDs), so a slice is read from HBM about once and from that XCD's L2 after.
 // VEC: every candidate row is whole 16-byte chunks on a 16-byte boundary (else element loads, K tail zeroed).
-template <int ES, bool VEC>
-__global__ __launch_bounds__(256) void retr_stage1_kernel(const Stage1 p) {
+// MINE (krs_retrieval_mine): the score is corrected as K13's before it is ranked -- + bias[cand], + hit where the
+// candidate carries the id of the row's positive and is not the positive -- and the pair (row, its positive) is not
+// queued: its score goes to pos_score[row].  A row whose positive is outside [0, n) has no positive, so no accidental
+// hits either; slice 0 writes NaN to its pos_score.
+template <int ES, bool VEC, bool MINE>
+__device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lstride = p.row_bytes + 16;
   char* qt = smem;                                                           // [kQM][lstride]
   uint64_t* queue = reinterpret_cast<uint64_t*>(smem + kQM * lstride);       // [kQM][cap]
   int* cnt = reinterpret_cast<int*>(queue + kQM * p.cap);                    // [kQM]
   uint32_t* thr = reinterpret_cast<uint32_t*>(cnt + kQM);                    // [kQM]
+  int64_t* pid = reinterpret_cast<int64_t*>(thr + kQM);                      // [kQM]  MINE: id of the row's positive
+  int* posr = reinterpret_cast<int*>(pid + kQM);                             // [kQM]  MINE: the row's positive, or -1
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int frow = lane & 31, fhalf = lane >> 5;
@@ -338,6 +356,23 @@ __global__ __launch_bounds__(256) void retr_stage1_kernel(const Stage1 p) {
   if (threadIdx.x < kQM) {
     cnt[threadIdx.x] = 0;
     thr[threadIdx.x] = 0;
+    if constexpr (MINE) {
+      const int64_t qr = q0 + threadIdx.x;
+      int64_t pr = -1;
+      if (qr < p.b) {
+        pr = mn.pos ? (int64_t)mn.pos[qr] : qr;
+        if (pr < 0 || pr >= p.n) {
+          pr = -1;
+          if (slice == 0) mn.pos_score[qr] = __uint_as_float(0x7fc00000u);
+        }
+      }
+      posr[threadIdx.x] = (int)pr;
+      int64_t id = 0;
+      if (mn.ids && pr >= 0)
+        id = mn.id64 ? reinterpret_cast<const int64_t*>(mn.ids)[pr]
+                     : (int64_t) reinterpret_cast<const int32_t*>(mn.ids)[pr];
+      pid[threadIdx.x] = id;
+    }
   }
   __syncthreads();
 
@@ -345,6 +380,11 @@ __global__ __launch_bounds__(256) void retr_stage1_kernel(const Stage1 p) {
   uint32_t t_reg[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) t_reg[r] = 0;
+  int pos_reg[16];
+  if constexpr (MINE) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) pos_reg[r] = posr[(r & 3) + 8 * (r >> 2) + 4 * fhalf];
+  }
 
   for (int64_t blk = s0; blk < s1; blk += kCB) {
     const int64_t cand = blk + wave * 32 + frow;  // this lane's candidate row (B fragment)
@@ -394,13 +434,44 @@ __global__ __launch_bounds__(256) void retr_stage1_kernel(const Stage1 p) {
       }
     }
     // acc[r] = score of query row (r & 3) + 8 (r >> 2) + 4 fhalf against candidate `cand`
+    if constexpr (MINE) {
+      float bias = 0.0f;
+      int64_t cid = 0;
+      if (cvalid) {
+        if (mn.bias) bias = mn.bias[cand];
+        if (mn.ids)
+          cid = mn.id64 ? reinterpret_cast<const int64_t*>(mn.ids)[cand]
+                        : (int64_t) reinterpret_cast<const int32_t*>(mn.ids)[cand];
+      }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * fhalf;
-      const uint32_t key = order_key(acc[r]);
-      if (cvalid && q0 + row < p.b && key > t_reg[r]) {
-        const int s = atomicAdd(&cnt[row], 1);
-        queue[row * p.cap + s] = pair_key(key, (uint32_t)cand);
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * fhalf;
+        const int pr = pos_reg[r];
+        const bool is_pos = cand == (int64_t)pr;
+        float s = acc[r];
+        if (mn.bias) s = __fadd_rn(s, bias);
+        if (mn.ids && pr >= 0 && !is_pos && cid == pid[row]) s = __fadd_rn(s, mn.hit);
+        if (cvalid && q0 + row < p.b) {
+          if (is_pos) {
+            mn.pos_score[q0 + row] = s;
+          } else {
+            const uint32_t key = order_key(s);
+            if (key > t_reg[r]) {
+              const int e = atomicAdd(&cnt[row], 1);
+              queue[row * p.cap + e] = pair_key(key, (uint32_t)cand);
+            }
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * fhalf;
+        const uint32_t key = order_key(acc[r]);
+        if (cvalid && q0 + row < p.b && key > t_reg[r]) {
+          const int s = atomicAdd(&cnt[row], 1);
+          queue[row * p.cap + s] = pair_key(key, (uint32_t)cand);
+        }
       }
     }
     __syncthreads();
@@ -430,6 +501,15 @@ __global__ __launch_bounds__(256) void retr_stage1_kernel(const Stage1 p) {
     uint64_t* o = p.out + ((q0 + row) * p.S + slice) * p.k;
     for (int j = lane; j < p.k; j += 64) o[j] = j < m ? queue[row * p.cap + j] : 0;
   }
+}
+
+template <int ES, bool VEC>
+__global__ __launch_bounds__(256) void retr_stage1_kernel(const Stage1 p) {
+  stage1_body<ES, VEC, false>(p, Mine{});
+}
+template <int ES, bool VEC>
+__global__ __launch_bounds__(256) void retr_mine_stage1_kernel(const Stage1 p, const Mine mn) {
+  stage1_body<ES, VEC, true>(p, mn);
 }
 
 // stage-1 geometry of a fused call
@@ -574,4 +654,70 @@ extern "C" int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int
     if (rc2 != KRS_OK) return rc2;
   }
   return KRS_OK;
+}
+
+// ---- hard-negative mining of the in-batch softmax loss (K14) ---------------------------------------------------------
+extern "C" size_t krs_retrieval_mine_workspace_bytes(int64_t b, int64_t n, int64_t d, int k, int dtype) {
+  using namespace krs;
+  (void)dtype;
+  if (b <= 0 || n <= 1 || d <= 0 || k < 1 || !fused_path(d, k)) return 0;
+  return fused_bytes(b, n, k);
+}
+
+extern "C" int krs_retrieval_mine(const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b, int64_t n,
+                                  int64_t d, int k, const int32_t* pos, const float* cand_bias, const void* cand_ids,
+                                  int id_dtype, float hit_value, int32_t* out_idx, float* out_scores, float* pos_score,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace krs;
+  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1, "krs_retrieval_mine: bad shape b=%lld n=%lld d=%lld", (long long)b,
+              (long long)n, (long long)d);
+  KRS_REQUIRE(n <= INT32_MAX, "krs_retrieval_mine: more than 2^31 - 1 candidates");
+  KRS_REQUIRE(k >= 1 && k <= n - 1, "krs_retrieval_mine: k = %d outside [1, n - 1 = %lld]", k, (long long)(n - 1));
+  KRS_REQUIRE(fused_path(d, k), "krs_retrieval_mine: k = %d above %d or d = %lld above %d", k, kFusedMaxK, (long long)d,
+              kFusedMaxD);
+  KRS_REQUIRE(ldq >= d && ldc >= d, "krs_retrieval_mine: row stride below d");
+  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "krs_retrieval_mine: bad dtype");
+  KRS_REQUIRE(id_dtype == KRS_I32 || id_dtype == KRS_I64, "krs_retrieval_mine: bad id dtype");
+  if (b == 0) return KRS_OK;
+  KRS_REQUIRE(q && c && out_idx && out_scores && pos_score, "krs_retrieval_mine: null operand");
+  const size_t need = krs_retrieval_mine_workspace_bytes(b, n, d, k, dtype);
+  if (!workspace || workspace_bytes < need)
+    return fail(KRS_ERR_WORKSPACE, "krs_retrieval_mine: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int es = dtype == KRS_BF16 ? 2 : 4;
+  char* ws = reinterpret_cast<char*>(workspace);
+
+  const Plan pl = fused_plan(b, n);
+  Stage1 p;
+  p.q = reinterpret_cast<const char*>(q); p.ldq = ldq;
+  p.c = reinterpret_cast<const char*>(c); p.ldc = ldc;
+  p.b = b; p.n = n; p.d = d; p.k = k; p.cap = kQueue;
+  p.slice = pl.slice; p.S = pl.S; p.qtiles = pl.qtiles;
+  p.row_bytes = (int)(ceil_div(d * es, 32) * 32);
+  p.out = reinterpret_cast<uint64_t*>(ws);
+  const Mine mn{pos, cand_bias, cand_ids, id_dtype == KRS_I64, hit_value, pos_score};
+  // the query tile, the row queues, cnt and thr as in krs_retrieval_topk, then the positives' ids and the positives
+  const size_t lds = (size_t)kQM * (p.row_bytes + 16) + (size_t)kQM * p.cap * sizeof(uint64_t) + 2 * kQM * sizeof(int) +
+                     kQM * sizeof(int64_t) + kQM * sizeof(int);
+  const bool vec = (d * es) % 16 == 0 && (ldc * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(c) & 15) == 0;
+  const dim3 grid((unsigned)((int64_t)pl.S * pl.qtiles));
+#define KRS_MINE1(ES_, VEC_)                                                                                       \
+  {                                                                                                                \
+    auto kern = retr_mine_stage1_kernel<ES_, VEC_>;                                                                \
+    KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                (int)lds));                                                                        \
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, mn);                                                     \
+  }
+  if (es == 2) {
+    if (vec) KRS_MINE1(2, true) else KRS_MINE1(2, false)
+  } else {
+    if (vec) KRS_MINE1(4, true) else KRS_MINE1(4, false)
+  }
+#undef KRS_MINE1
+  KRS_CHECK_LAUNCH("retr_mine_stage1_kernel");
+  // the slice merge: every row has n - 1 >= k queued candidates in all, so no padding pair is selected
+  const int64_t len = (int64_t)pl.S * k;
+  uint64_t* list = reinterpret_cast<uint64_t*>(ws + align256((size_t)b * len * sizeof(uint64_t)));
+  const Out out{out_idx, out_scores, KRS_F32, nullptr, k, 0, n};
+  return select_rows(PairSrc{p.out, len}, b, len, k, out, list, st);
 }

@@ -262,7 +262,7 @@ class InBatchSoftmaxLoss:
     """The in-batch softmax loss of a two-tower retrieval model, from the embeddings: scores = query . candidates^T,
     SamplingProbabilityCorrection, RemoveAccidentalHits and CategoricalCrossentropy(from_logits=True) against the
     positives, with the [batch, candidates] scores, labels and logit gradient never stored (include/krs.h, K13;
-    memory O((B + N) D)).
+    memory O((B + N) D)).  With num_hard_negatives, HardNegativeMining sits in front of the cross-entropy (K14).
 
         loss(query_embeddings [B, D], candidate_embeddings [N, D], positive_index=None, candidate_ids=None,
              candidate_sampling_probability=None, sample_weight=None)
@@ -275,12 +275,17 @@ class InBatchSoftmaxLoss:
     removes them.  bf16 embeddings of up to 256 columns run on the fused kernels, with fp32 scores (the stored-matrix
     head rounds them to bf16 first); other inputs run krs_gemm + K11 slab by slab in fp32.
 
-    Hard-negative mining is not part of this loss: it needs a per-row top-k of the corrected scores.  Use the
-    stored-matrix head for it (examples/two_tower_retrieval.py: retrieval_task_loss with num_hard_negatives)."""
+    num_hard_negatives (an integer >= 1, default None: every candidate counts): the cross-entropy runs over each
+    query's positive and its k = min(num_hard_negatives, N - 1) highest corrected scores among the other candidates,
+    as keras_rs.layers.HardNegativeMining(k) in front of the loss does, and label_smoothing spreads over those k + 1
+    logits.  Equal scores at the k-th place go to the lowest candidate index (the reference leaves that choice open;
+    the loss does not depend on it).  The selection runs inside the fused scoring kernel for fp32 and bf16 embeddings
+    with k <= 128 and D <= 512 (include/krs.h, K14): memory is the inputs plus B * S * k (score, index) pairs, S
+    the number of candidate slices; larger k or D mine slab by slab on stored fp32 scores."""
 
     def __init__(self, label_smoothing: float = 0.0, reduction: str | None = "sum_over_batch_size",
                  epsilon: float = 1e-6, accidental_hit_value: float = retrieval_ops.SMALLEST_FLOAT,
-                 name: str | None = None):
+                 name: str | None = None, num_hard_negatives: int | None = None):
         if not 0.0 <= label_smoothing < 1.0:
             raise ValueError(f"`label_smoothing` should be in [0, 1). Received: label_smoothing={label_smoothing}")
         if reduction not in _reductions.REDUCTIONS:
@@ -290,6 +295,12 @@ class InBatchSoftmaxLoss:
             raise ValueError(f"`accidental_hit_value` should be finite. Received: {accidental_hit_value}")
         self.label_smoothing, self.reduction = float(label_smoothing), reduction
         self.epsilon, self.accidental_hit_value = float(epsilon), float(accidental_hit_value)
+        if num_hard_negatives is not None and (isinstance(num_hard_negatives, bool)
+                                               or not isinstance(num_hard_negatives, (int, np.integer))
+                                               or num_hard_negatives < 1):
+            raise ValueError("`num_hard_negatives` should be an integer >= 1 or None. Received: "
+                             f"num_hard_negatives={num_hard_negatives!r}")
+        self.num_hard_negatives = None if num_hard_negatives is None else int(num_hard_negatives)
         self.name = name or "in_batch_softmax_loss"
 
     def __call__(self, query_embeddings, candidate_embeddings, positive_index=None, candidate_ids=None,
@@ -327,11 +338,15 @@ class InBatchSoftmaxLoss:
         return retrieval_ops.retrieval_xent(q, c, positive_index=None if pos is None else pos.detach(), cand_bias=bias,
                                             cand_ids=None if ids is None else ids.detach(),
                                             hit_value=self.accidental_hit_value, label_smoothing=self.label_smoothing,
-                                            sample_weight=w, reduction=self.reduction)
+                                            sample_weight=w, reduction=self.reduction,
+                                            num_hard_negatives=self.num_hard_negatives)
 
     def get_config(self) -> dict:
-        return {"name": self.name, "label_smoothing": self.label_smoothing, "reduction": self.reduction,
-                "epsilon": self.epsilon, "accidental_hit_value": self.accidental_hit_value}
+        config = {"name": self.name, "label_smoothing": self.label_smoothing, "reduction": self.reduction,
+                  "epsilon": self.epsilon, "accidental_hit_value": self.accidental_hit_value}
+        if self.num_hard_negatives is not None:      # (an unset layer keeps the config it always had)
+            config["num_hard_negatives"] = self.num_hard_negatives
+        return config
 
     @classmethod
     def from_config(cls, config: dict):

@@ -1,7 +1,7 @@
-"""Host side of K8, K11 and K13: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and mining),
-over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored scores), and
-over krs_retrieval_xent_fwd / krs_retrieval_xent_bwd (the in-batch softmax loss that never stores the scores), all of
-include/krs.h.
+"""Host side of K8, K11, K13 and K14: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and mining),
+over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored scores),
+over krs_retrieval_xent_fwd / krs_retrieval_xent_bwd (the in-batch softmax loss that never stores the scores) and over
+krs_retrieval_mine (the same loss on each row's hardest negatives), all of include/krs.h.
 
 All run on the current stream, allocate from torch's caching allocator and never wait for the device, so a call can
 be captured into a HIP graph.
@@ -421,11 +421,180 @@ class RetrievalXentFn(torch.autograd.Function):
         return (dq, dc) + (None,) * 9
 
 
+# ---- K14: the in-batch softmax loss on each row's positive and its k hardest negatives ----------------------------------
+MINE_MAX_K = 128           # most negatives per row of the fused mining kernel
+MINE_MAX_D = 512           # its widest embedding
+
+
+def retrieval_mine_workspace_bytes(b: int, n: int, d: int, k: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    dt = L.BF16 if dtype == torch.bfloat16 else L.F32
+    return int(L.lib().krs_retrieval_mine_workspace_bytes(b, n, d, k, dt))
+
+
+def retrieval_mine(q, c, k: int, pos, bias, ids, hit_value: float):
+    """krs_retrieval_mine on checked operands: (int32 indices [B, k] of the k hardest negatives of each row in the
+    total order, their corrected fp32 scores [B, k], the positive's fp32 score [B], NaN for a positive outside
+    [0, N))."""
+    b, d = q.shape
+    n = c.shape[0]
+    idx = torch.empty((b, k), dtype=torch.int32, device=q.device)
+    val = torch.empty((b, k), dtype=torch.float32, device=q.device)
+    pos_score = torch.empty((b,), dtype=torch.float32, device=q.device)
+    size = retrieval_mine_workspace_bytes(b, n, d, k, q.dtype)
+    ws = torch.empty(max(1, size), dtype=torch.uint8, device=q.device)
+    rc = L.lib().krs_retrieval_mine(L.ptr(q), q.stride(0) if b > 1 else d, L.ptr(c), c.stride(0) if n > 1 else d,
+                                    L.fdtype(q), b, n, d, k, L.ptr(pos), L.ptr(bias), L.ptr(ids),
+                                    L.itype(ids) if ids is not None else L.I32, float(hit_value), L.ptr(idx), L.ptr(val),
+                                    L.ptr(pos_score), L.ptr(ws), ws.numel(), L.stream_ptr())
+    L.check(rc, "krs_retrieval_mine")
+    return idx, val, pos_score
+
+
+def retrieval_mine_slab(q, c, k: int, pos, bias, ids, hit_value: float, slab_bytes: int = SLAB_BYTES):
+    """What retrieval_mine returns, from existing entry points only: per slab of query rows the corrected fp32 scores
+    (krs_gemm, krs_remove_accidental_hits), then HardNegativeMining's selection top_k(scores + labels * MAX_FLOAT,
+    k + 1) by krs_topk_rows, whose first column is the positive."""
+    b, n = q.shape[0], c.shape[0]
+    q32, c32 = q.to(torch.float32), c.to(torch.float32)
+    idx = torch.empty((b, k), dtype=torch.int32, device=q.device)
+    val = torch.empty((b, k), dtype=torch.float32, device=q.device)
+    pos_score = torch.empty((b,), dtype=torch.float32, device=q.device)
+    for r0, r1 in _slabs(b, n, slab_bytes):
+        scores, p = _slab_scores(q32, c32, r0, r1, pos, bias, ids, hit_value)
+        ok = (p >= 0) & (p < n)
+        p64 = p.clamp(0, n - 1).to(torch.int64)[:, None]
+        labels = torch.zeros_like(scores).scatter_(1, p64, ok.to(torch.float32)[:, None])
+        sel = topk_rows(scores, k + 1, boost=labels, boost_scale=MAX_FLOAT)
+        # (a row without a positive has no boosted column: its k hardest candidates are the first k columns)
+        neg = torch.where(ok[:, None], sel[:, 1:], sel[:, :k])
+        idx[r0:r1] = neg
+        val[r0:r1] = scores.gather(1, neg.to(torch.int64))
+        pos_score[r0:r1] = torch.where(ok, scores.gather(1, p64)[:, 0], torch.full_like(scores[:, 0], float("nan")))
+    return idx, val, pos_score
+
+
+def _mined_bags(c):
+    """The candidate matrix as the one table of a K1 / K2 call: one dense feature, combiner sum."""
+    from keras_rs_amd import embedding_ops
+
+    return embedding_ops.FusedBags([c.contiguous()], [(0, "sum", 0)])
+
+
+class MinedRetrievalXentFn(torch.autograd.Function):
+    """The in-batch softmax loss on the positive and the k hardest negatives of each row (include/krs.h, K14), with
+    RetrievalXentFn's reduction scheme.  The forward keeps q, c, the index list [B, k + 1] (positive first) and the
+    logits [B, k + 1]; the backward takes P = d(sum_i g_i loss_i)/dlogits from K11 (fp32, never rounded to bf16) and
+    forms dq = sum_m P_im c[idx_im] with K1 and dc_j = sum_{idx_im = j} P_im q_i with K2's sort plan and dense form, or,
+    on the slab path, scatters P into a zeroed slab of query rows and runs the slab path's two krs_gemm calls."""
+
+    @staticmethod
+    def forward(ctx, q, c, pos, bias, ids, weight, k, hit_value, label_smoothing, reduction, fused, slab_bytes):
+        rows, n = q.shape[0], c.shape[0]
+        if fused:
+            idx, val, pos_score = retrieval_mine(q, c, k, pos, bias, ids, hit_value)
+        else:
+            idx, val, pos_score = retrieval_mine_slab(q, c, k, pos, bias, ids, hit_value, slab_bytes)
+        logits = torch.cat((pos_score[:, None], val), dim=1)
+        zeros = torch.zeros((rows,), dtype=torch.int32, device=q.device)
+        v, _ = softmax_xent(logits, label_index=zeros, label_smoothing=label_smoothing, want_grad=False)
+        bad = torch.isnan(pos_score)                      # (scores are finite: only a positive outside [0, N))
+        v = torch.where(bad, pos_score, v)
+        first = pos.clamp(0, n - 1) if pos is not None else \
+            torch.arange(rows, dtype=torch.int32, device=q.device).clamp(max=n - 1)
+        index = torch.cat((first[:, None], idx), dim=1)
+        g, scale = weight, 1.0
+        if reduction == "mean_with_sample_weight" and weight is not None:
+            div = weight.expand((rows,)).sum()
+            g = torch.where(div != 0, weight / div, torch.zeros_like(weight))   # divide_no_nan
+        elif reduction not in ("none", "sum"):
+            scale = 1.0 / rows if rows else 0.0
+        ctx.meta = (label_smoothing, fused, slab_bytes, scale)
+        ctx.save_for_backward(q, c, index, logits, g)
+        if reduction == "none":
+            return v if weight is None else v * weight
+        return (v.sum() if g is None else (v * g).sum()) * scale
+
+    @staticmethod
+    def backward(ctx, up):
+        from keras_rs_amd import dense_ops
+
+        label_smoothing, fused, slab_bytes, scale = ctx.meta
+        q, c, index, logits, g = ctx.saved_tensors
+        rows, d = q.shape
+        n, k1 = c.shape[0], index.shape[1]
+        want_dq, want_dc = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dq = torch.empty((rows, d), dtype=q.dtype, device=q.device) if want_dq else None
+        dc = torch.zeros((n, d), dtype=torch.float32, device=q.device) if want_dc else None
+        if rows == 0:
+            return (dq, None if dc is None else dc.to(c.dtype)) + (None,) * 10
+        gv = up.to(torch.float32) if scale == 1.0 else up.to(torch.float32) * scale
+        if g is not None:
+            gv = gv * g
+        gv = gv.expand((rows,)).contiguous()
+        zeros = torch.zeros((rows,), dtype=torch.int32, device=q.device)
+        _, P = softmax_xent(logits, label_index=zeros, label_smoothing=label_smoothing, g=gv, want_loss=False)
+        # a row without a positive: NaN on its k mined candidates, and nothing on slot 0, whose index is a stand-in
+        bad = torch.isnan(logits[:, :1])
+        slot0 = torch.arange(k1, device=q.device)[None, :] == 0
+        P = torch.where(bad, torch.where(slot0, torch.zeros_like(P), torch.full_like(P, float("nan"))), P)
+        if fused:
+            bags = _mined_bags(c)
+            flat, w = index.reshape(-1), P.reshape(-1)
+            if want_dq:
+                bags.forward(flat, rows, hots=[k1], weights=w, out=dq)
+            if want_dc:
+                plan = bags.plan_backward(flat, rows, hots=[k1])
+                bags.backward_dense(plan, q, rows, flat.numel(), hots=[k1], weights=w, out=[dc])
+        else:
+            q32, c32 = q.to(torch.float32), c.to(torch.float32)
+            dq32 = torch.empty((rows, d), dtype=torch.float32, device=q.device)
+            acc = None
+            for r0, r1 in _slabs(rows, n, slab_bytes):
+                dx = torch.zeros((r1 - r0, n), dtype=torch.float32, device=q.device)
+                dx.scatter_add_(1, index[r0:r1].to(torch.int64), P[r0:r1])
+                if want_dq:
+                    dense_ops.gemm(dx, c32, out=dq32[r0:r1])
+                if want_dc:
+                    acc, _ = dense_ops.gemm(dx, q32[r0:r1], a_is_km=True, r=acc)
+            dq = dq32.to(q.dtype) if want_dq else None
+            dc = acc if want_dc else None
+        return (dq, None if dc is None else dc.to(c.dtype)) + (None,) * 10
+
+
+def _retrieval_xent_mined(query, candidates, positive_index, cand_bias, cand_ids, hit_value, label_smoothing, path,
+                          sample_weight, reduction, slab_bytes, num_hard_negatives):
+    if isinstance(num_hard_negatives, bool) or not isinstance(num_hard_negatives, (int, np.integer)) \
+            or num_hard_negatives < 1:
+        raise L.KrsError(f"retrieval_xent: num_hard_negatives must be an integer >= 1 or None, got "
+                         f"{num_hard_negatives!r}")
+    if path not in ("auto", "fused", "slab"):
+        raise L.KrsError(f"retrieval_xent: path must be 'auto', 'fused' or 'slab', got {path!r}")
+    if not 0.0 <= label_smoothing < 1.0:
+        raise L.KrsError(f"retrieval_xent: label_smoothing {label_smoothing} outside [0, 1)")
+    q, c, pos, bias, ids = _xent_operands(query, candidates, positive_index, cand_bias, cand_ids)
+    n, d = c.shape
+    k = min(int(num_hard_negatives), n - 1)
+    if k == 0:     # one candidate: nothing to mine, the loss over (positive) alone is the unmined loss
+        return retrieval_xent(query, candidates, positive_index=positive_index, cand_bias=cand_bias, cand_ids=cand_ids,
+                              hit_value=hit_value, label_smoothing=label_smoothing, path=path,
+                              sample_weight=sample_weight, reduction=reduction, slab_bytes=slab_bytes)
+    fused = path == "fused" or (path == "auto" and k <= MINE_MAX_K and d <= MINE_MAX_D)
+    w = None
+    if sample_weight is not None:
+        w = sample_weight.detach().to(device=q.device, dtype=torch.float32)
+        if w.dim() > 0:
+            w = w.expand((q.shape[0],)).contiguous()
+    reduction = "none" if reduction is None else reduction
+    return MinedRetrievalXentFn.apply(q, c, pos, bias, ids, w, k, float(hit_value), float(label_smoothing), reduction,
+                                      fused, int(slab_bytes))
+
+
+
 def retrieval_xent(query: torch.Tensor, candidates: torch.Tensor, *, positive_index: torch.Tensor | None = None,
                    cand_bias: torch.Tensor | None = None, cand_ids: torch.Tensor | None = None,
                    hit_value: float = SMALLEST_FLOAT, label_smoothing: float = 0.0, path: str = "auto",
                    sample_weight: torch.Tensor | None = None, reduction: str | None = "none",
-                   slab_bytes: int = SLAB_BYTES) -> torch.Tensor:
+                   slab_bytes: int = SLAB_BYTES, num_hard_negatives: int | None = None) -> torch.Tensor:
     """Softmax cross-entropy of the scores query [B, D] . candidates [N, D]^T + cand_bias (+ hit_value on the
     accidental hits given by cand_ids) against the positives positive_index (None: candidate i for query i), with
     gradients to both embeddings (include/krs.h, K13).  The [B, N] scores are never stored.
@@ -433,7 +602,16 @@ def retrieval_xent(query: torch.Tensor, candidates: torch.Tensor, *, positive_in
     path: "fused" -- the K13 kernels (bf16, D <= 256); "slab" -- krs_gemm + K11 on slabs of query rows whose fp32
     scores stay under slab_bytes, in fp32; "auto" -- fused wherever it is eligible, whatever the shape: its contract
     is memory, not speed.  reduction / sample_weight follow SoftmaxCrossentropyFn: "none" / None returns the fp32
-    losses [B] (times the weight), the others a scalar."""
+    losses [B] (times the weight), the others a scalar.
+
+    num_hard_negatives (an integer >= 1): the softmax runs over each row's positive and its k = min(num_hard_negatives,
+    N - 1) highest-scoring other candidates only (include/krs.h, K14: HardNegativeMining in front of the loss, ties
+    to the lowest index), and label_smoothing spreads over those k + 1 logits.  Then path "fused" is krs_retrieval_mine
+    (fp32 or bf16, k <= 128, D <= 512), K11 on the [B, k + 1] logits, and K1 / K2 for the gradients; "slab" mines on
+    slabs of stored fp32 scores with krs_topk_rows; "auto" is fused wherever it is eligible."""
+    if num_hard_negatives is not None:
+        return _retrieval_xent_mined(query, candidates, positive_index, cand_bias, cand_ids, hit_value, label_smoothing,
+                                     path, sample_weight, reduction, slab_bytes, num_hard_negatives)
     if path not in ("auto", "fused", "slab"):
         raise L.KrsError(f"retrieval_xent: path must be 'auto', 'fused' or 'slab', got {path!r}")
     if not 0.0 <= label_smoothing < 1.0:

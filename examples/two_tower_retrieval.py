@@ -13,6 +13,11 @@ HardNegativeMining -> CategoricalCrossentropy.  The scores are one GEMM; everyth
 `fused_retrieval_task_loss` is the same loss, hard-negative mining included, computed from the embeddings by the fused
 kernels: the [B, N] scores are never stored, so it also runs at batch sizes where the score matrix does not fit.  Both
 runs train one objective (the fused one keeps its scores in fp32 and sends ties to the lowest index).
+
+    python examples/two_tower_retrieval.py --eval     # then: top-k accuracies and MRR over all items (K15)
+
+`evaluate` scores every query against the whole item table with FactorizedTopK: one sweep gives the positive's rank,
+hence every top-k accuracy and the mean reciprocal rank, again without storing the scores.
 """
 
 from __future__ import annotations
@@ -53,8 +58,17 @@ def fused_retrieval_task_loss(query_emb: torch.Tensor, cand_emb: torch.Tensor, c
         query_emb, cand_emb, candidate_ids=cand_ids, candidate_sampling_probability=cand_prob)
 
 
+def evaluate(query_emb: torch.Tensor, item_emb: torch.Tensor, positive_item: torch.Tensor,
+             ks=(1, 5, 10, 50, 100)) -> dict:
+    """Top-k categorical accuracies and the mean reciprocal rank of query_emb [B, D] against the whole item table
+    item_emb [items, D], positive_item [B] being the row of each query's item: floats by metric name."""
+    metric = kl.FactorizedTopK(item_emb.detach(), ks=ks)
+    metric.update_state(query_emb.detach(), positive_item)
+    return {name: float(value) for name, value in metric.result().items()}
+
+
 def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000, dim: int = 32,
-         fused: bool = False) -> None:
+         fused: bool = False, evaluate_after: bool = False) -> None:
     dev = torch.device("cuda", torch.cuda.current_device())
     query_tower = kl.Embedding(users, dim, device=dev)
     cand_tower = kl.Embedding(items, dim, device=dev)
@@ -79,7 +93,10 @@ def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000,
     retrieval = kl.BruteForceRetrieval(cand_tower(all_items).detach(), all_items, k=5, device=dev)
     scores, top = retrieval(query_tower(user_ids[:4]).detach())
     print("top-5 items of the first queries:", top.tolist())
+    if evaluate_after:
+        for name, value in evaluate(query_tower(user_ids), cand_tower(all_items), item_ids).items():
+            print(f"{name}: {value:.4f}")
 
 
 if __name__ == "__main__":
-    main(fused="--fused" in sys.argv[1:])
+    main(fused="--fused" in sys.argv[1:], evaluate_after="--eval" in sys.argv[1:])

@@ -965,6 +965,40 @@ int krs_retrieval_mine(const void* q, int64_t ldq, const void* c, int64_t ldc, i
                        float hit_value, int32_t* out_idx, float* out_scores, float* pos_score, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * K15  The positive's rank among all candidates, from the embeddings: the scores are formed tile by tile on the
+ *      matrix cores (K13's sweep) and never stored
+ *
+ * The evaluation counterpart of K13 (the idea of tfrs.metrics.FactorizedTopK): one sweep answers "how many
+ * candidates beat the positive?" for every query, which gives every top-k accuracy and the reciprocal rank at once.
+ * q [b, d] and c [n, d] are bf16 with row strides ldq, ldc (>= d), 1 <= d <= 256, n >= 1, b >= 0.  Per query row i:
+ *     s_ij    = sum_k q_ik c_jk   (fp32 accumulate; no bias, no smoothing)
+ *     rank_i  = #{ j != pos_i : j precedes pos_i in K8's total order and not (ids_j == ids_{pos_i}) }
+ * K8's order: the fp32 key s_ij descending, then the index ascending; -0.0 == +0.0, NaN above +inf (all NaN equal).
+ * Without ids, rank_i is the column at which krs_retrieval_topk with k = n returns the positive.
+ * pos: int32 [b], or NULL for pos_i = i.  cand_ids: int32 / int64 [n] (id_dtype: krs_itype) or NULL; with ids, a
+ * candidate other than the positive that carries the positive's id is not counted (K13's accidental hits, removed).
+ * A pos_i outside [0, n) is never used as an address: that row gets rank -1 and pos_score NaN.
+ *
+ * out_rank [b] int32; out_pos_score [b] fp32 (s_{i,pos_i}) may be NULL.  s_{i,pos_i} leaves the same MFMA chain as
+ * the streamed scores (a short first launch streams each workgroup's own positives, gathered through pos, and
+ * keeps the diagonal), so a candidate row byte-identical to the positive's ties with it exactly and the index decides.
+ *
+ * Memory is O((b + n) d).  The candidate side is cut into K13's slices (from (b, n) alone); the slices' int32 counts
+ * live in `workspace` and are added by a second small launch.  krs_retrieval_rank_workspace_bytes is the positives'
+ * scores, 4 b bytes, plus 4 S b bytes when S > 1 slices are used, each rounded up to 256:
+ *     at most 4 b + 32 (b + n) + 512 bytes                                     (S b <= 8 (b + n)).
+ * It need not be initialised.  Integer counts only: exact, order-independent, bit-identical from call to call.  No
+ * host synchronisation, no allocation, no scratch; graph-capturable.  b == 0 is a successful no-op.
+ * A dtype other than KRS_BF16 and d > 256 are KRS_ERR_UNSUPPORTED (the Python wrapper routes them to a slab path built
+ * from krs_gemm); null q, c or out_rank, d < 1, n < 1, more than 2^31 - 1 rows, a row stride below d and a bad id
+ * dtype are KRS_ERR_INVALID; too little workspace is KRS_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------- */
+size_t krs_retrieval_rank_workspace_bytes(int64_t b, int64_t n, int64_t d, int dtype);
+int krs_retrieval_rank(const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b, int64_t n,
+                       int64_t d, const int32_t* pos, const void* cand_ids, int id_dtype, int32_t* out_rank,
+                       float* out_pos_score, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,17 @@
 // or fp32 [S, rows, d] gradients -- to the caller's workspace and a second small launch combines them in slice
 // order.  Every output element has one owner and no float atomics are used: results are bit-identical from call to
 // call.  No host synchronisation, no allocation, no scratch.
+//
+// K15 (krs_retrieval_rank) -- the positive's rank in K8's order, on the same body (owner = queries; staging, tile
+// image, score chain and id test are MODE_FWD's):
+//   * MODE_POS, a short first launch without slices: the streamed rows of a workgroup are its own 128 owners'
+//     positives, gathered through pos, four tiles; wave w keeps, from tile w, the diagonal element of each lane's
+//     owner.  s_pos therefore leaves the very MFMA chain that produces the streamed scores, so a candidate row
+//     byte-identical to the positive's ties with it exactly (and the positive's own streamed score equals it);
+//   * MODE_RANK: per-lane state is one int32, the number of the lane's tile rows whose order_key beats s_pos's, or
+//     equals it at a lower index; the positive and its accidental hits are left out.  The two lanes of a query are
+//     added at the end; the slices' counts go to the workspace and are added by combine_rank_kernel.  Integers only:
+//     exact in any order.
 #include <algorithm>
 
 #include "krs_common.h"
@@ -47,7 +58,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kThreads = 256;
 constexpr float kNegInf = -__builtin_inff();
-enum { MODE_FWD = 0, MODE_DQ = 1, MODE_DC = 2 };
+enum { MODE_FWD = 0, MODE_DQ = 1, MODE_DC = 2, MODE_POS = 3, MODE_RANK = 4 };
 
 struct Params {
   const uint16_t* q;
@@ -72,6 +83,9 @@ struct Params {
   uint16_t* dout;     // dq or dc
   int64_t ldd;
   float* dpart;       // [S][rows][d]
+  float* pos_score;   // K15: s_{i,pos_i}, written by MODE_POS and read by MODE_RANK
+  int32_t* rank;      // K15
+  int32_t* rank_part; // K15: [S][b] counts
 };
 
 // the constants of a row: a query's {lse, g, pos, id of its positive} or a candidate's {bias, -, index, id}
@@ -154,6 +168,7 @@ struct RowStats {
 template <int DPAD, int MODE, bool VEC>
 __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
   constexpr bool SWAP = MODE == MODE_DC;        // owner = candidates
+  constexpr bool XENT = MODE == MODE_FWD || MODE == MODE_DQ || MODE == MODE_DC, GRAD = XENT && MODE != MODE_FWD;
   constexpr int NKS = DPAD / 16, DT = DPAD / 32, CH = DPAD / 8;
   constexpr int TILE_BYTES = kTile * DPAD * 2;
   constexpr int U = (kTile * CH + kThreads - 1) / kThreads;   // chunks a thread stages per tile
@@ -171,7 +186,10 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
   const uint16_t* T = SWAP ? p.q : p.c;
   const int64_t ldo = SWAP ? p.ldc : p.ldq, ldt = SWAP ? p.ldq : p.ldc;
   const int64_t RO = SWAP ? p.n : p.b, RT = SWAP ? p.b : p.n;
-  const int64_t t_begin = std::min<int64_t>(slice * p.slice, RT), t_end = std::min<int64_t>(t_begin + p.slice, RT);
+  // (MODE_POS streams the positives of the workgroup's own owners: "row t" is then owner oblock * kOwnRows + t)
+  const int64_t t_begin = MODE == MODE_POS ? 0 : std::min<int64_t>(slice * p.slice, RT);
+  const int64_t t_end = MODE == MODE_POS ? std::min<int64_t>(kOwnRows, RO - oblock * kOwnRows)
+                                         : std::min<int64_t>(t_begin + p.slice, RT);
   const bool has_ids = p.ids != nullptr;
 
   // the owner rows of this lane: fragments of the score product's B operand, and the row's constants
@@ -185,6 +203,10 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
       ofrag[ks] = load_chunk<VEC>(src + (2 * ks + fhalf) * 8, (2 * ks + fhalf) * 8, p.d, ovalid);
   }
   const RowC mine = load_rowc<!SWAP>(p, orow, ovalid);
+  uint32_t pos_key = 0;        // MODE_RANK: the positive's place in K8's order
+  int32_t ahead = 0;           //            candidates of this lane's 16 rows per tile that precede it
+  float diag = 0.0f;           // MODE_POS: the owner's score against its own positive
+  if constexpr (MODE == MODE_RANK) pos_key = order_key(ovalid ? p.pos_score[orow] : 0.0f);
 
   // staging of one streamed tile: registers first, LDS after the current tile has been consumed
   u32x4 sreg[U];
@@ -205,16 +227,29 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int ch = (tid + u * kThreads) % CH;
-      sreg[u] = load_chunk<VEC>(sptr[u] + step, ch * 8, p.d, srow_of[u] < left);
+      if constexpr (MODE == MODE_POS) {
+        // gathered through pos; a positive outside [0, n) is never an address: its row is staged as zeros
+        int64_t at = -1;
+        if (srow_of[u] < left) {
+          const int64_t own = oblock * kOwnRows + t0 + srow_of[u];
+          at = p.pos ? (int64_t)p.pos[own] : own;
+        }
+        const bool ok = at >= 0 && at < p.n;
+        sreg[u] = load_chunk<VEC>(T + (ok ? at : 0) * ldt + ch * 8, ch * 8, p.d, ok);
+      } else {
+        sreg[u] = load_chunk<VEC>(sptr[u] + step, ch * 8, p.d, srow_of[u] < left);
+      }
     }
-    if (tid < kTile) srow = load_rowc<SWAP>(p, t0 + tid, t0 + tid < t_end);
+    if constexpr (MODE != MODE_POS) {
+      if (tid < kTile) srow = load_rowc<SWAP>(p, t0 + tid, t0 + tid < t_end);
+    }
   };
   auto stage_store = [&](int buf) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (tid + u * kThreads < kTile * CH) *reinterpret_cast<u32x4*>(&tile[buf][sdst[u]]) = sreg[u];
     }
-    if (tid < kTile) {
+    if (MODE != MODE_POS && tid < kTile) {
       side_a[buf][tid] = srow.a;
       side_b[buf][tid] = srow.b;
       side_idx[buf][tid] = srow.idx;
@@ -224,8 +259,8 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
   };
 
   RowStats st;
-  f32x16 dacc[MODE == MODE_FWD ? 1 : DT];
-  if constexpr (MODE != MODE_FWD) {
+  f32x16 dacc[GRAD ? DT : 1];
+  if constexpr (GRAD) {
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -255,59 +290,93 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
                                                     acc, 0, 0, 0);
     }
 
-    // ---- corrected score, smoothed label and what MODE makes of them; register r is tile row
-    //      (r & 3) + 8 (r >> 2) + 4 fhalf ----
     const int live = (int)std::min<int64_t>(t_end - t0, kTile);   // rows of the tile that exist
-    float sv[16], yv[16];
+    if constexpr (MODE == MODE_POS) {
+      // the diagonal of tile `wave`: tile row frow of owner frow sits in half (frow >> 2) & 1, register
+      // (frow & 3) + 4 (frow >> 3)
+      if (it == wave) {
 #pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-      const int tb = 8 * gq + 4 * fhalf;
-      float ta[4], tbv[4];
-      int32_t tidx[4];
-      uint32_t tlo[4] = {0, 0, 0, 0}, thi[4] = {0, 0, 0, 0};
-      {
-        const float4 va = *reinterpret_cast<const float4*>(&side_a[buf][tb]);
-        ta[0] = va.x, ta[1] = va.y, ta[2] = va.z, ta[3] = va.w;
-        if constexpr (SWAP) {
-          const float4 vb = *reinterpret_cast<const float4*>(&side_b[buf][tb]);
-          tbv[0] = vb.x, tbv[1] = vb.y, tbv[2] = vb.z, tbv[3] = vb.w;
-          const int4 vi = *reinterpret_cast<const int4*>(&side_idx[buf][tb]);
-          tidx[0] = vi.x, tidx[1] = vi.y, tidx[2] = vi.z, tidx[3] = vi.w;
-        } else {
+        for (int r = 0; r < 16; ++r) diag = r == (frow & 3) + 4 * (frow >> 3) ? acc[r] : diag;
+      }
+    }
+    if constexpr (MODE == MODE_RANK) {
+      // ---- K15: count the tile's candidates that precede the positive: key descending, then index ascending; the
+      //      positive itself and, with ids, its accidental hits are left out ----
 #pragma unroll
-          for (int x = 0; x < 4; ++x) {
-            tbv[x] = 0.0f;
-            tidx[x] = (int32_t)(t0 + tb + x);
-          }
-        }
+      for (int gq = 0; gq < 4; ++gq) {
+        const int tb = 8 * gq + 4 * fhalf;
+        uint32_t tlo[4] = {0, 0, 0, 0}, thi[4] = {0, 0, 0, 0};
         if (has_ids) {
           const uint4 vl = *reinterpret_cast<const uint4*>(&side_lo[buf][tb]);
           const uint4 vh = *reinterpret_cast<const uint4*>(&side_hi[buf][tb]);
           tlo[0] = vl.x, tlo[1] = vl.y, tlo[2] = vl.z, tlo[3] = vl.w;
           thi[0] = vh.x, thi[1] = vh.y, thi[2] = vh.z, thi[3] = vh.w;
         }
-      }
 #pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int r = 4 * gq + x;
-        const bool valid = tb + x < live;
-        // the query's and the candidate's constants, whichever side owns the lane
-        const float bias = SWAP ? mine.a : ta[x];
-        const float lse = SWAP ? ta[x] : mine.a;
-        const float g = SWAP ? tbv[x] : mine.b;
-        const int32_t q_pos = SWAP ? tidx[x] : mine.idx;
-        const int32_t c_idx = SWAP ? mine.idx : tidx[x];
-        float s = acc[r] + bias;
-        if (has_ids) {
-          const bool hit = tlo[x] == mine.idlo && thi[x] == mine.idhi && c_idx != q_pos;
-          s = hit ? s + p.hit_value : s;
+        for (int x = 0; x < 4; ++x) {
+          const int32_t c_idx = (int32_t)(t0 + tb + x);
+          const uint32_t key = order_key(acc[4 * gq + x]);
+          // (bitwise on purpose: sixteen short-circuit tests per tile would be sixteen branches)
+          const bool before = (key > pos_key) | ((key == pos_key) & (c_idx < mine.idx));
+          const bool same_id = has_ids & (tlo[x] == mine.idlo) & (thi[x] == mine.idhi);
+          ahead += ((tb + x < live) & (c_idx != mine.idx) & before & !same_id) ? 1 : 0;
         }
-        const float yp = c_idx == q_pos ? p.keep + p.spread : p.spread;
-        if constexpr (MODE == MODE_FWD) {
-          sv[r] = valid ? s : kNegInf;
-          yv[r] = valid ? yp : 0.0f;
-        } else {
-          sv[r] = valid ? g * (__expf(s - lse) - yp) : 0.0f;
+      }
+    }
+    // ---- corrected score, smoothed label and what MODE makes of them; register r is tile row
+    //      (r & 3) + 8 (r >> 2) + 4 fhalf ----
+    float sv[16], yv[16];
+    if constexpr (XENT) {
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        const int tb = 8 * gq + 4 * fhalf;
+        float ta[4], tbv[4];
+        int32_t tidx[4];
+        uint32_t tlo[4] = {0, 0, 0, 0}, thi[4] = {0, 0, 0, 0};
+        {
+          const float4 va = *reinterpret_cast<const float4*>(&side_a[buf][tb]);
+          ta[0] = va.x, ta[1] = va.y, ta[2] = va.z, ta[3] = va.w;
+          if constexpr (SWAP) {
+            const float4 vb = *reinterpret_cast<const float4*>(&side_b[buf][tb]);
+            tbv[0] = vb.x, tbv[1] = vb.y, tbv[2] = vb.z, tbv[3] = vb.w;
+            const int4 vi = *reinterpret_cast<const int4*>(&side_idx[buf][tb]);
+            tidx[0] = vi.x, tidx[1] = vi.y, tidx[2] = vi.z, tidx[3] = vi.w;
+          } else {
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+              tbv[x] = 0.0f;
+              tidx[x] = (int32_t)(t0 + tb + x);
+            }
+          }
+          if (has_ids) {
+            const uint4 vl = *reinterpret_cast<const uint4*>(&side_lo[buf][tb]);
+            const uint4 vh = *reinterpret_cast<const uint4*>(&side_hi[buf][tb]);
+            tlo[0] = vl.x, tlo[1] = vl.y, tlo[2] = vl.z, tlo[3] = vl.w;
+            thi[0] = vh.x, thi[1] = vh.y, thi[2] = vh.z, thi[3] = vh.w;
+          }
+        }
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+          const int r = 4 * gq + x;
+          const bool valid = tb + x < live;
+          // the query's and the candidate's constants, whichever side owns the lane
+          const float bias = SWAP ? mine.a : ta[x];
+          const float lse = SWAP ? ta[x] : mine.a;
+          const float g = SWAP ? tbv[x] : mine.b;
+          const int32_t q_pos = SWAP ? tidx[x] : mine.idx;
+          const int32_t c_idx = SWAP ? mine.idx : tidx[x];
+          float s = acc[r] + bias;
+          if (has_ids) {
+            const bool hit = tlo[x] == mine.idlo && thi[x] == mine.idhi && c_idx != q_pos;
+            s = hit ? s + p.hit_value : s;
+          }
+          const float yp = c_idx == q_pos ? p.keep + p.spread : p.spread;
+          if constexpr (MODE == MODE_FWD) {
+            sv[r] = valid ? s : kNegInf;
+            yv[r] = valid ? yp : 0.0f;
+          } else {
+            sv[r] = valid ? g * (__expf(s - lse) - yp) : 0.0f;
+          }
         }
       }
     }
@@ -324,7 +393,7 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
         st.s += yv[r];
         st.a += valid ? yv[r] * (st.m - sv[r]) : 0.0f;
       }
-    } else {
+    } else if constexpr (GRAD) {
       // ---- Z[o][d] += sum_t P[t][o] T[t][d]: P's registers 8s .. 8s+7 are k-step s of the A operand, element j of
       //      lane half h being tile row 16 s + 8 (j >> 2) + 4 h + (j & 3); the B operand takes the same rows of
       //      column 32 dt + (lane & 31) with two transposed reads of 4 rows each ----
@@ -377,6 +446,14 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
         p.row_lse[orow] = st.m + lz;
       }
     }
+  } else if constexpr (MODE == MODE_POS) {
+    if (fhalf == ((frow >> 2) & 1) && ovalid) p.pos_score[orow] = mine.idx < 0 ? quiet_nan() : diag;
+  } else if constexpr (MODE == MODE_RANK) {
+    ahead += __shfl_xor(ahead, 32, 64);   // (rows 0-3, 8-11, .. of each tile, and rows 4-7, 12-15, ..)
+    if (fhalf == 0 && ovalid) {
+      if (p.S > 1) p.rank_part[slice * p.b + orow] = ahead;
+      else p.rank[orow] = mine.idx < 0 ? -1 : ahead;
+    }
   } else {
     // Z tile dt: column 32 dt + (lane & 31), owner row (r & 3) + 8 (r >> 2) + 4 fhalf of the wave's 32
     const int64_t obase = oblock * kOwnRows + wave * 32;
@@ -423,6 +500,16 @@ __global__ __launch_bounds__(256) void combine_grad_kernel(const float* __restri
   float v = part[i];
   for (int s = 1; s < S; ++s) v += part[(int64_t)s * rows * d + i];
   out[row * ldo + col] = f32_to_bf16(v);
+}
+
+__global__ __launch_bounds__(256) void combine_rank_kernel(const int32_t* __restrict__ part, int S, int64_t b, int64_t n,
+                                                           const int32_t* __restrict__ pos, int32_t* __restrict__ rank) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= b) return;
+  int32_t v = 0;
+  for (int s = 0; s < S; ++s) v += part[(int64_t)s * b + i];
+  const int64_t ps = pos ? (int64_t)pos[i] : i;
+  rank[i] = (ps < 0 || ps >= n) ? -1 : v;
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -551,6 +638,58 @@ extern "C" int krs_retrieval_xent_bwd(const void* q, int64_t ldq, const void* c,
                          (int)d, p.dout, lddc);
       KRS_CHECK_LAUNCH("combine_grad_kernel (dc)");
     }
+  }
+  return KRS_OK;
+}
+
+extern "C" size_t krs_retrieval_rank_workspace_bytes(int64_t b, int64_t n, int64_t d, int dtype) {
+  (void)dtype;
+  if (b <= 0 || n <= 0 || d <= 0) return 0;
+  return krs::xent::rank_bytes(b, n);
+}
+
+extern "C" int krs_retrieval_rank(const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b, int64_t n,
+                                  int64_t d, const int32_t* pos, const void* cand_ids, int id_dtype, int32_t* out_rank,
+                                  float* out_pos_score, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace krs;
+  const char* what = "krs_retrieval_rank";
+  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1, "%s: bad shape b=%lld n=%lld d=%lld", what, (long long)b, (long long)n,
+              (long long)d);
+  if (dtype != KRS_BF16)
+    return fail(KRS_ERR_UNSUPPORTED, "%s: bf16 inputs only (dtype %d): other inputs take the slab path of the wrapper",
+                what, dtype);
+  if (d > xent::kMaxD)
+    return fail(KRS_ERR_UNSUPPORTED, "%s: d = %lld above %d: wider inputs take the slab path of the wrapper", what,
+                (long long)d, xent::kMaxD);
+  KRS_REQUIRE(b <= INT32_MAX && n <= INT32_MAX, "%s: more than 2^31 - 1 rows", what);
+  KRS_REQUIRE(ldq >= d && ldc >= d, "%s: row stride below d", what);
+  KRS_REQUIRE(!cand_ids || id_dtype == KRS_I32 || id_dtype == KRS_I64, "%s: bad id dtype %d", what, id_dtype);
+  if (b == 0) return KRS_OK;
+  KRS_REQUIRE(q && c, "%s: null operand", what);
+  KRS_REQUIRE(out_rank, "%s: null output", what);
+  const xent::Sweep sw = xent::plan_sweep(b, n, b, n);
+  const size_t need = xent::rank_bytes(b, n);
+  if (!workspace || workspace_bytes < need)
+    return fail(KRS_ERR_WORKSPACE, "%s: needs %zu workspace bytes, got %zu", what, need, workspace_bytes);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  Params p{};
+  p.q = reinterpret_cast<const uint16_t*>(q), p.ldq = ldq;
+  p.c = reinterpret_cast<const uint16_t*>(c), p.ldc = ldc;
+  p.b = b, p.n = n, p.d = (int)d;
+  p.pos = pos, p.ids = cand_ids, p.id64 = id_dtype == KRS_I64;
+  char* ws = reinterpret_cast<char*>(workspace);
+  p.pos_score = out_pos_score ? out_pos_score : reinterpret_cast<float*>(ws);
+  p.rank = out_rank, p.rank_part = reinterpret_cast<int32_t*>(ws + xent::rank_pos_bytes(b));
+  p.S = 1, p.slice = xent::kOwnRows, p.oblocks = sw.oblocks;
+  launch_sweep<MODE_POS>(p, (unsigned)sw.oblocks, st);
+  KRS_CHECK_LAUNCH("xent_kernel (positive scores)");
+  p.S = sw.S, p.slice = sw.slice;
+  launch_sweep<MODE_RANK>(p, (unsigned)(sw.oblocks * sw.S), st);
+  KRS_CHECK_LAUNCH("xent_kernel (rank)");
+  if (sw.S > 1) {
+    hipLaunchKernelGGL(combine_rank_kernel, dim3((unsigned)ceil_div(b, 256)), dim3(256), 0, st, p.rank_part, sw.S, b, n,
+                       pos, out_rank);
+    KRS_CHECK_LAUNCH("combine_rank_kernel");
   }
   return KRS_OK;
 }

@@ -55,6 +55,13 @@ inline size_t dc_bytes(int64_t b, int64_t n, int64_t d) {
   const Sweep c = plan_sweep(n, b, b, n);
   return c.S > 1 ? align256((size_t)c.S * (size_t)n * (size_t)d * sizeof(float)) : 0;
 }
+// K15 (krs_retrieval_rank): the positives' scores [b] fp32, then the slices' counts [S, b] int32 when the sweep is
+// cut.  S b <= 8 (b + n), so this is at most 4 b + 32 (b + n) + 512 bytes.
+inline size_t rank_pos_bytes(int64_t b) { return align256((size_t)b * sizeof(float)); }
+inline size_t rank_bytes(int64_t b, int64_t n) {
+  const Sweep q = plan_sweep(b, n, b, n);
+  return rank_pos_bytes(b) + (q.S > 1 ? align256((size_t)q.S * (size_t)b * sizeof(int32_t)) : 0);
+}
 inline size_t workspace_bytes(int64_t b, int64_t n, int64_t d) {
   const size_t f = fwd_bytes(b, n), g = dq_bytes(b, n, d) + dc_bytes(b, n, d);
   return f > g ? f : g;

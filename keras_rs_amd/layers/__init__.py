@@ -9,10 +9,11 @@ from keras_rs_amd.layers.embed_reduce import EmbedReduce, Embedding, Ragged
 from keras_rs_amd.layers.feature_cross import FeatureCross
 from keras_rs_amd.layers.losses import (BinaryCrossentropy, CategoricalCrossentropy, SparseCategoricalCrossentropy,
                                         binary_crossentropy)
-from keras_rs_amd.layers.metrics import AUC, BinaryAccuracy, BinaryMetricGroup, auc_from_confusion
-from keras_rs_amd.layers.retrieval import (BruteForceRetrieval, HardNegativeMining, InBatchSoftmaxLoss,
+from keras_rs_amd.layers.metrics import (AUC, BinaryAccuracy, BinaryMetricGroup, SparseTopKCategoricalAccuracy,
+                                         auc_from_confusion)
+from keras_rs_amd.layers.retrieval import (BruteForceRetrieval, FactorizedTopK, HardNegativeMining, InBatchSoftmaxLoss,
                                            RemoveAccidentalHits, Retrieval, SamplingProbabilityCorrection)
 
 __all__ = ["AUC", "Adagrad", "Adam", "BinaryAccuracy", "BinaryCrossentropy", "BinaryMetricGroup", "auc_from_confusion", "binary_crossentropy", "BruteForceRetrieval", "CategoricalCrossentropy", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
-           "FeatureCross", "Ftrl", "HardNegativeMining", "InBatchSoftmaxLoss", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SamplingProbabilityCorrection",
-           "SparseCategoricalCrossentropy", "TableConfig", "concat_features"]
+           "FactorizedTopK", "FeatureCross", "Ftrl", "HardNegativeMining", "InBatchSoftmaxLoss", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SamplingProbabilityCorrection",
+           "SparseCategoricalCrossentropy", "SparseTopKCategoricalAccuracy", "TableConfig", "concat_features"]

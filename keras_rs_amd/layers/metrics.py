@@ -9,6 +9,10 @@ can be captured in a HIP graph.  y_true and y_pred may have any shapes with the 
 
 BinaryMetricGroup updates one BinaryAccuracy and up to four AUCs from one krs_binary_metrics call; a member's state
 after a group update is bit-identical to its state after updating it alone.
+
+SparseTopKCategoricalAccuracy(k, from_sorted_ids=True) is the metric the reference's retrieval examples compile behind
+BruteForceRetrieval: torch ops on the retrieved ids, no kernel of its own (FactorizedTopK, layers/retrieval.py, is the
+metric that needs no retrieved ids).
 """
 
 from __future__ import annotations
@@ -237,6 +241,71 @@ class AUC(_BinaryMetric):
         if self._init_from_thresholds:
             config["thresholds"] = self.thresholds[1:-1]   # (the end points are added again)
         return config
+
+
+class SparseTopKCategoricalAccuracy:
+    """keras.metrics.SparseTopKCategoricalAccuracy(k, from_sorted_ids=True) as the reference's retrieval examples
+    compile it behind BruteForceRetrieval(return_scores=False): y_pred [B, k'] holds each row's retrieved ids, best
+    first, and a row is a hit when y_true [B] (or [B, 1]) is among its first k columns.  The state is
+    keras.metrics.Mean's {total, count} as a device tensor; update_state is a handful of torch ops on y_pred's device
+    and waits for nothing.  from_sorted_ids=False (y_pred = stored logits) is not implemented: FactorizedTopK gives
+    the top-k accuracies of a two-tower model from the embeddings, without the logits."""
+    _state = None
+
+    def __init__(self, k: int = 5, from_sorted_ids: bool = False, name: str = "sparse_top_k_categorical_accuracy",
+                 dtype: Any = None):
+        _check_dtype(self, dtype)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"`k` should be an integer >= 1. Received: k={k!r}")
+        if not from_sorted_ids:
+            raise NotImplementedError("SparseTopKCategoricalAccuracy: only from_sorted_ids=True (y_pred = the ids "
+                                      "BruteForceRetrieval returns) is implemented; for the top-k accuracy of a "
+                                      "two-tower model from its embeddings use keras_rs_amd.layers.FactorizedTopK")
+        self.k, self.from_sorted_ids, self.name = int(k), True, name
+
+    def update_state(self, y_true, y_pred, sample_weight=None) -> None:
+        y_pred = y_pred if isinstance(y_pred, torch.Tensor) else torch.as_tensor(np.asarray(y_pred))
+        dev = y_pred.device
+        y_true = y_true.to(dev) if isinstance(y_true, torch.Tensor) else torch.as_tensor(np.asarray(y_true), device=dev)
+        if y_pred.dim() != 2 or y_true.numel() != y_pred.shape[0] or y_true.dim() > 2:
+            raise ValueError("`y_pred` should be [batch, ids] and `y_true` one id per row. Received: `y_true.shape` = "
+                             f"{tuple(y_true.shape)}, `y_pred.shape` = {tuple(y_pred.shape)}.")
+        if y_pred.dtype.is_floating_point or y_true.dtype.is_floating_point:
+            raise ValueError(f"`y_true` ({y_true.dtype}) and `y_pred` ({y_pred.dtype}) should be integer ids")
+        b = y_pred.shape[0]
+        w = None
+        if sample_weight is not None:
+            w = sample_weight if isinstance(sample_weight, torch.Tensor) else \
+                torch.as_tensor(sample_weight, dtype=torch.float32)
+            if w.dim() != 0 and w.numel() != b:
+                raise ValueError(f"`sample_weight` of shape {tuple(w.shape)} cannot be broadcast to {b} rows: give a "
+                                 "scalar or one weight per row.")
+            w = w.to(device=dev, dtype=torch.float32).reshape(-1 if w.dim() else ())
+        hit = (y_pred[:, :self.k].to(torch.int64) == y_true.reshape(b, 1).to(torch.int64)).any(dim=1)
+        w = torch.ones((b,), dtype=torch.float32, device=dev) if w is None else w.expand((b,))
+        if self._state is None or self._state.device != dev:
+            self._state = torch.zeros((2,), dtype=torch.float32, device=dev)
+        self._state.add_(torch.stack(((w * hit.to(torch.float32)).sum(), w.sum())))
+
+    def result(self) -> torch.Tensor:
+        if self._state is None:
+            return torch.zeros((), dtype=torch.float32)
+        return _divide_no_nan(self._state[0], self._state[1])
+
+    def reset_state(self) -> None:
+        if self._state is not None:
+            self._state.zero_()
+
+    def __call__(self, y_true, y_pred, sample_weight=None) -> torch.Tensor:
+        self.update_state(y_true, y_pred, sample_weight)
+        return self.result()
+
+    def get_config(self) -> dict:
+        return {"name": self.name, "dtype": "float32", "k": self.k, "from_sorted_ids": self.from_sorted_ids}
+
+    @classmethod
+    def from_config(cls, config: dict):
+        return cls(**config)
 
 
 class BinaryMetricGroup:

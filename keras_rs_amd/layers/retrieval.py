@@ -4,7 +4,9 @@
 logit corrections of the training head, keras_rs.layers.SamplingProbabilityCorrection
 (sampling_probability_correction.py) and keras_rs.layers.RemoveAccidentalHits (remove_accidental_hits.py), on K11
 (krs_sampling_correction, krs_remove_accidental_hits); and InBatchSoftmaxLoss, the whole in-batch softmax head computed
-from the two embedding matrices without storing the scores (K13: krs_retrieval_xent_fwd / krs_retrieval_xent_bwd).
+from the two embedding matrices without storing the scores (K13: krs_retrieval_xent_fwd / krs_retrieval_xent_bwd), and
+FactorizedTopK, the evaluation metric that goes with it: every top-k accuracy and the mean reciprocal rank from the
+positive's rank among all candidates, again without the scores (K15: krs_retrieval_rank).
 
 Selection order: score descending, then candidate index ascending (-0.0 as +0.0, NaN above +inf); rows come back
 sorted.  Known divergence: for bf16 inputs keras.ops.matmul rounds the scores to bf16 before top_k, so among
@@ -347,6 +349,172 @@ class InBatchSoftmaxLoss:
         if self.num_hard_negatives is not None:      # (an unset layer keeps the config it always had)
             config["num_hard_negatives"] = self.num_hard_negatives
         return config
+
+    @classmethod
+    def from_config(cls, config: dict):
+        return cls(**config)
+
+
+def rank_totals(rank: torch.Tensor, weight: torch.Tensor | None, ks: torch.Tensor) -> torch.Tensor:
+    """What one batch adds to FactorizedTopK's state, with torch ops in a fixed order on any device: fp32
+    [len(ks) + 2] = (sum_i w_i [0 <= rank_i < k] for each k, sum_i w_i / (rank_i + 1), sum_i w_i).  rank int [B]
+    (-1: no positive; the row counts in the last total only), weight None, a scalar or [B], ks int [K]."""
+    b = rank.shape[0]
+    w = torch.ones((b,), dtype=torch.float32, device=rank.device) if weight is None else \
+        weight.to(torch.float32).expand((b,))
+    found = rank >= 0
+    hit = found[:, None] & (rank[:, None] < ks[None, :])
+    top = (w[:, None] * hit.to(torch.float32)).sum(dim=0)
+    rr = torch.where(found, 1.0 / (rank.clamp(min=0).to(torch.float32) + 1.0), torch.zeros_like(w))
+    return torch.cat((top, (w * rr).sum()[None], w.sum()[None]))
+
+
+class FactorizedTopK:
+    """Top-k categorical accuracies and the mean reciprocal rank of a two-tower model, from the embeddings -- the idea of
+    tfrs.metrics.FactorizedTopK: score every query against all candidates and ask where its positive lands.  Here one
+    sweep (include/krs.h, K15: krs_retrieval_rank) counts the candidates that beat the positive, so every k and the
+    reciprocal rank come from one pass and the [B, N] scores are never stored (memory O((B + N) D)).
+
+        metric = FactorizedTopK(candidate_embeddings [N, D], candidate_ids=None, ks=(1, 5, 10, 50, 100))
+        metric.update_state(query_embeddings [B, D], positive_index [B], sample_weight=None)
+        metric.result() -> {"top_1_categorical_accuracy": ..., ..., "mean_reciprocal_rank": ...}
+
+    rank_i is the number of candidates other than the positive that precede it in BruteForceRetrieval's order (score
+    descending, then candidate index ascending), so `rank_i < k` is "the positive is among BruteForceRetrieval(k)'s
+    ids".  With candidate_ids, other candidates that carry the positive's id are not counted (accidental hits are
+    removed).  A positive_index outside [0, N) counts as a miss for every k and adds 0 to the reciprocal rank.
+    Values: top-k = sum w_i [rank_i < k] / sum w_i, MRR = sum w_i / (rank_i + 1) / sum w_i, 0 when sum w = 0.
+
+    Candidates given to update_state override the stored ones for that call (the in-batch use: candidates = the batch's
+    item embeddings, positive_index=None for candidate i of query i).  `update_candidates` with the same shape copies
+    in place, so a graph captured around update_state keeps reading the current candidates.  The totals are a device
+    tensor; nothing waits for the device.  bf16 embeddings of up to 256 columns run on the fused kernel, other inputs
+    on a slab path of krs_gemm."""
+
+    def __init__(self, candidate_embeddings=None, candidate_ids=None, ks=(1, 5, 10, 50, 100),
+                 name: str = "factorized_top_k"):
+        ks = tuple(ks)
+        if not ks or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 for k in ks):
+            raise ValueError(f"`ks` should be a non-empty sequence of integers >= 1. Received: ks={ks!r}")
+        self.ks = tuple(int(k) for k in ks)
+        self.name = name
+        self.candidate_embeddings = None
+        self.candidate_ids = None
+        self._state = None
+        self._ks_on: dict = {}
+        if candidate_embeddings is None:
+            if candidate_ids is not None:
+                raise ValueError("You cannot provide `candidate_ids` without providing `candidate_embeddings`")
+        else:
+            self.update_candidates(candidate_embeddings, candidate_ids)
+
+    @staticmethod
+    def _check_candidates(c, ids, what="candidate_embeddings"):
+        if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] < 1:
+            raise ValueError(f"`{what}` must be a tensor of rank 2 (num_candidates, embedding_size) with at least one "
+                             f"candidate, received shape {tuple(c.shape)}")
+        if c.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"`{what}` should be float32 or bfloat16. Received: {c.dtype}.")
+        if ids is not None and (tuple(ids.shape) != (c.shape[0],) or ids.dtype.is_floating_point
+                                or ids.dtype == torch.bool):
+            raise ValueError(f"`candidate_ids` should be {c.shape[0]} integers, one per candidate. Received: "
+                             f"`candidate_ids.shape` = {tuple(ids.shape)}, dtype {ids.dtype}.")
+
+    def update_candidates(self, candidate_embeddings, candidate_ids=None) -> None:
+        if candidate_embeddings is None:
+            raise ValueError("`candidate_embeddings` is required.")
+        emb = _as_tensor(candidate_embeddings).detach()
+        ids = None if candidate_ids is None else _as_tensor(candidate_ids, emb.device).detach()
+        self._check_candidates(emb, ids)
+        if ids is not None and ids.dtype not in (torch.int32, torch.int64):
+            ids = ids.to(torch.int64)
+        if self.candidate_embeddings is None:
+            self.candidate_embeddings = emb.clone()
+            self.candidate_ids = None if ids is None else ids.clone()
+            return
+        # assign: the stored tensors keep their shape and storage, which a captured graph reads
+        if tuple(emb.shape) != tuple(self.candidate_embeddings.shape):
+            raise ValueError(f"Cannot assign candidate_embeddings of shape {tuple(emb.shape)} to a variable of shape "
+                             f"{tuple(self.candidate_embeddings.shape)}")
+        if self.candidate_ids is None and ids is not None:
+            raise ValueError("New `candidate_ids` cannot be provided as previous candidates did not have candidate IDs")
+        self.candidate_embeddings.copy_(emb)
+        if ids is not None:
+            self.candidate_ids.copy_(ids)
+
+    def _device_state(self, device) -> torch.Tensor:
+        if self._state is None or self._state.device != device:
+            self._state = torch.zeros((len(self.ks) + 2,), dtype=torch.float32, device=device)
+        return self._state
+
+    def _device_ks(self, device) -> torch.Tensor:
+        ks = self._ks_on.get(device)
+        if ks is None:
+            ks = self._ks_on[device] = torch.tensor(self.ks, dtype=torch.int32, device=device)
+        return ks
+
+    def accumulate(self, rank: torch.Tensor, sample_weight=None) -> None:
+        """Adds the ranks of one batch (int [B], -1 for a row without a positive) to the totals, on rank's device."""
+        w = _reductions._sample_weight(sample_weight, (rank.shape[0],), rank.device)
+        self._device_state(rank.device).add_(rank_totals(rank, w, self._device_ks(rank.device)))
+
+    def update_state(self, query_embeddings, positive_index=None, sample_weight=None, candidate_embeddings=None,
+                     candidate_ids=None) -> None:
+        q = _as_tensor(query_embeddings)
+        if candidate_embeddings is not None:
+            c = _as_tensor(candidate_embeddings, q.device)
+            ids = None if candidate_ids is None else _as_tensor(candidate_ids, q.device)
+        elif candidate_ids is not None:
+            raise ValueError("You cannot provide `candidate_ids` without providing `candidate_embeddings`")
+        elif self.candidate_embeddings is None:
+            raise ValueError("No candidates: give `candidate_embeddings` or call `update_candidates` first.")
+        else:
+            c, ids = self.candidate_embeddings, self.candidate_ids
+        shapes = f"`query_embeddings.shape` = {tuple(q.shape)}, `candidate_embeddings.shape` = {tuple(c.shape)}"
+        if q.dim() != 2 or c.dim() != 2 or q.shape[1] != c.shape[1] or c.shape[0] < 1 or c.shape[1] < 1:
+            raise ValueError("`query_embeddings` [batch, dim] and `candidate_embeddings` [candidates, dim] should be "
+                             f"matrices of one width with at least one candidate. Received: {shapes}.")
+        if q.dtype != c.dtype or q.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("`query_embeddings` and `candidate_embeddings` should share a dtype, float32 or bfloat16. "
+                             f"Received: {q.dtype} and {c.dtype} ({shapes}).")
+        b, n = q.shape[0], c.shape[0]
+        pos = None
+        if positive_index is not None:
+            pos = _as_tensor(positive_index, q.device)
+            if tuple(pos.shape) != (b,) or pos.dtype.is_floating_point or pos.dtype == torch.bool:
+                raise ValueError(f"`positive_index` should be {b} integers, one per query. Received: "
+                                 f"`positive_index.shape` = {tuple(pos.shape)}, dtype {pos.dtype} ({shapes}).")
+        if ids is not None and (tuple(ids.shape) != (n,) or ids.dtype.is_floating_point or ids.dtype == torch.bool):
+            raise ValueError(f"`candidate_ids` should be {n} integers, one per candidate. Received: "
+                             f"`candidate_ids.shape` = {tuple(ids.shape)}, dtype {ids.dtype} ({shapes}).")
+        w = _reductions._sample_weight(sample_weight, (b,), q.device)
+        L.require_device(q, "FactorizedTopK query_embeddings")
+        L.require_device(c, "FactorizedTopK candidate_embeddings")
+        rank, _ = retrieval_ops.retrieval_rank(q.detach(), c.detach(), None if pos is None else pos.detach(),
+                                               None if ids is None else ids.detach())
+        self.accumulate(rank, w)
+
+    def result(self) -> dict:
+        state = torch.zeros((len(self.ks) + 2,), dtype=torch.float32) if self._state is None else self._state
+        total = state[-1]
+        nz = total != 0
+        values = torch.where(nz, state[:-1] / torch.where(nz, total, torch.ones_like(total)),
+                             torch.zeros_like(state[:-1]))
+        out = {f"top_{k}_categorical_accuracy": values[i] for i, k in enumerate(self.ks)}
+        out["mean_reciprocal_rank"] = values[len(self.ks)]
+        return out
+
+    def reset_state(self) -> None:
+        if self._state is not None:
+            self._state.zero_()
+
+    def __call__(self, query_embeddings, positive_index=None, sample_weight=None, candidate_embeddings=None,
+                 candidate_ids=None) -> dict:
+        self.update_state(query_embeddings, positive_index, sample_weight, candidate_embeddings, candidate_ids)
+        return self.result()
+
+    def get_config(self) -> dict:
+        return {"name": self.name, "ks": list(self.ks)}
 
     @classmethod
     def from_config(cls, config: dict):

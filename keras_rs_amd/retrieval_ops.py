@@ -1,7 +1,8 @@
-"""Host side of K8, K11, K13 and K14: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and mining),
-over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored scores),
-over krs_retrieval_xent_fwd / krs_retrieval_xent_bwd (the in-batch softmax loss that never stores the scores) and over
-krs_retrieval_mine (the same loss on each row's hardest negatives), all of include/krs.h.
+"""Host side of K8, K11, K13, K14 and K15: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and
+mining), over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored
+scores), over krs_retrieval_xent_fwd / krs_retrieval_xent_bwd (the in-batch softmax loss that never stores the scores),
+over krs_retrieval_mine (the same loss on each row's hardest negatives) and over krs_retrieval_rank (the positive's
+rank among all candidates, for evaluation), all of include/krs.h.
 
 All run on the current stream, allocate from torch's caching allocator and never wait for the device, so a call can
 be captured into a HIP graph.
@@ -626,3 +627,81 @@ def retrieval_xent(query: torch.Tensor, candidates: torch.Tensor, *, positive_in
     reduction = "none" if reduction is None else reduction
     return RetrievalXentFn.apply(q, c, pos, bias, ids, w, float(hit_value), float(label_smoothing), reduction, fused,
                                  int(slab_bytes))
+
+
+# ---- K15: the positive's rank among all candidates, scores never stored -----------------------------------------------
+def retrieval_rank_workspace_bytes(b: int, n: int, d: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    dt = L.BF16 if dtype == torch.bfloat16 else L.F32
+    return int(L.lib().krs_retrieval_rank_workspace_bytes(b, n, d, dt))
+
+
+def retrieval_rank_fused(q, c, pos, ids):
+    """krs_retrieval_rank on checked operands: (int32 rank [B], fp32 score of the positive [B])."""
+    b, d = q.shape
+    n = c.shape[0]
+    rank = torch.empty((b,), dtype=torch.int32, device=q.device)
+    pos_score = torch.empty((b,), dtype=torch.float32, device=q.device)
+    size = retrieval_rank_workspace_bytes(b, n, d, q.dtype)
+    ws = torch.empty(max(1, size), dtype=torch.uint8, device=q.device)
+    rc = L.lib().krs_retrieval_rank(L.ptr(q), q.stride(0) if b > 1 else d, L.ptr(c), c.stride(0) if n > 1 else d,
+                                    L.fdtype(q), b, n, d, L.ptr(pos), L.ptr(ids),
+                                    L.itype(ids) if ids is not None else L.I32, L.ptr(rank), L.ptr(pos_score),
+                                    L.ptr(ws), size, L.stream_ptr())
+    L.check(rc, "krs_retrieval_rank")
+    return rank, pos_score
+
+
+def rank_in_scores(scores: torch.Tensor, pos: torch.Tensor, ids: torch.Tensor | None = None):
+    """(int32 rank [R], fp32 score of the positive [R]) from stored fp32 scores [R, N] with plain torch ops (any
+    device): the number of candidates other than pos that precede it in K8's total order -- score descending, then
+    index ascending, -0.0 as +0.0, NaN above +inf -- leaving out those that carry the positive's id.  A pos outside
+    [0, N) gives -1 and NaN."""
+    n = scores.shape[1]
+    ok = (pos >= 0) & (pos < n)
+    p64 = pos.clamp(0, n - 1).to(torch.int64)[:, None]
+    sp = scores.gather(1, p64)
+    nan_s, nan_p = torch.isnan(scores), torch.isnan(sp)
+    above = (scores > sp) | (nan_s & ~nan_p)
+    level = (scores == sp) | (nan_s & nan_p)
+    col = torch.arange(n, device=scores.device)[None, :]
+    counts = (above | (level & (col < p64))) & (col != p64)
+    if ids is not None:
+        ids64 = ids.to(torch.int64)
+        counts &= ids64[None, :] != ids64[p64[:, 0]][:, None]
+    rank = torch.where(ok, counts.sum(dim=1), torch.full_like(p64[:, 0], -1)).to(torch.int32)
+    return rank, torch.where(ok, sp[:, 0], torch.full_like(sp[:, 0], float("nan")))
+
+
+def retrieval_rank_slab(q, c, pos, ids, slab_bytes: int = SLAB_BYTES):
+    """What retrieval_rank_fused returns, from krs_gemm into an fp32 slab of query rows and rank_in_scores on it."""
+    from keras_rs_amd import dense_ops
+
+    b, n = q.shape[0], c.shape[0]
+    q32, c32 = q.to(torch.float32), c.to(torch.float32)
+    rank = torch.empty((b,), dtype=torch.int32, device=q.device)
+    pos_score = torch.empty((b,), dtype=torch.float32, device=q.device)
+    for r0, r1 in _slabs(b, n, slab_bytes):
+        scores, _ = dense_ops.gemm(q32[r0:r1], c32, b_is_nk=True, out_dtype=torch.float32)
+        idx = pos[r0:r1] if pos is not None else torch.arange(r0, r1, dtype=torch.int32, device=q.device)
+        rank[r0:r1], pos_score[r0:r1] = rank_in_scores(scores, idx, ids)
+    return rank, pos_score
+
+
+def retrieval_rank(query: torch.Tensor, candidates: torch.Tensor, positive_index: torch.Tensor | None = None,
+                   cand_ids: torch.Tensor | None = None, path: str = "auto", *, slab_bytes: int = SLAB_BYTES):
+    """The rank of each query's positive among all candidates by the score query [B, D] . candidates [N, D]^T
+    (include/krs.h, K15): (int32 rank [B], fp32 score of the positive [B]).  rank is the number of candidates other
+    than the positive that precede it in K8's order (score descending, then index ascending), i.e. the column at which
+    BruteForceRetrieval(k = N) returns it; with cand_ids, candidates that carry the positive's id are not counted.
+    positive_index None: candidate i for query i; an index outside [0, N) gives rank -1 and score NaN.  No autograd.
+
+    path: "fused" -- krs_retrieval_rank (bf16, D <= 256), the [B, N] scores never stored; "slab" -- krs_gemm into fp32
+    slabs of query rows under slab_bytes and the count with torch ops; "auto" -- fused wherever it is eligible,
+    whatever the shape: its contract is memory, not speed."""
+    if path not in ("auto", "fused", "slab"):
+        raise L.KrsError(f"retrieval_rank: path must be 'auto', 'fused' or 'slab', got {path!r}")
+    q, c, pos, _, ids = _xent_operands(query.detach(), candidates.detach(), positive_index, None, cand_ids)
+    fused = path == "fused" or (path == "auto" and q.dtype == torch.bfloat16 and q.shape[1] <= XENT_MAX_D)
+    if fused:
+        return retrieval_rank_fused(q, c, pos, ids)
+    return retrieval_rank_slab(q, c, pos, ids, int(slab_bytes))

@@ -122,6 +122,35 @@ int krs_embed_bag_fwd(const krs_table* tables, const krs_feature* feats, int n_f
                       void* out, int out_dtype, int64_t out_ld,
                       float* bag_scale, int* err_flag, void* stream);
 
+/* Diagnostic, host only: where the CALLING THREAD's last krs_embed_bag_fwd ran.  Every field is 0 when there was no call
+ * yet, the call was refused (any return other than KRS_OK) or had nothing to do (n_feats == 0 or batch == 0).
+ *   kernel       KRS_EMBED_FWD_*: embed_bag_fwd_vec (pooled), embed_gather_hot1 (pure gather, feature-major),
+ *                embed_gather_hot1_rows (pure gather, sample-major), embed_bag_fwd_generic
+ *   lpr          lanes per row: 8 / 16 / 32 / 64 on the vector kernels, 1 .. 64 on the generic one
+ *   has_w        per-id weights are read (pooled: the HAS_W build; generic: weights != NULL); 0 on the gather kernels
+ *   stream       pooled kernel only: the STREAM build (nnz < 2 * bags)
+ *   hot_rows     pooled kernel only: rows staged in LDS (the HR build: 0, 64 or 128; KRS_EMBED_OPT_HOTROWS)
+ *   bpg          pooled kernel only: bags per group, 1 .. 16
+ *   table_dtype, out_dtype  the krs_dtype pair of the instantiation
+ *   blocks       workgroups launched
+ * Returns `kernel`; `route` may be NULL.  Lets tests prove which kernel they ran. */
+enum { KRS_EMBED_FWD_NONE = 0, KRS_EMBED_FWD_VEC, KRS_EMBED_FWD_HOT1, KRS_EMBED_FWD_HOT1_ROWS, KRS_EMBED_FWD_GENERIC };
+typedef struct krs_embed_fwd_route {
+  int32_t kernel, lpr, has_w, stream, hot_rows, bpg, table_dtype, out_dtype;
+  int64_t blocks;
+} krs_embed_fwd_route;
+int krs_embed_bag_fwd_last_route(krs_embed_fwd_route* route);
+/* Diagnostic, host only, no GPU needed: where a krs_embed_bag_fwd with these arguments WOULD run under the
+ * KRS_EMBED_OPT_HOTROWS value in force (csrc/embed_fwd_plan.h, the planner the entry itself runs).  offsets, weights and
+ * out are read as pointer VALUES only (nullness; the 16-byte alignment of out); nothing is dereferenced, no HIP call is
+ * made and the last-route record is untouched.  Fills *route (all zero when nothing would be launched) and returns what
+ * the entry returns before its first launch: KRS_OK, KRS_ERR_INVALID (null out, a negative size, dim <= 0, a bad dtype)
+ * or KRS_ERR_UNSUPPORTED (batch > INT_MAX - 128, whose bag arithmetic the kernels do in int; a grid beyond 2^31 - 1
+ * workgroups). */
+int krs_embed_bag_fwd_plan_route(int n_feats, const void* offsets, const float* weights, int64_t nnz, int batch, int dim,
+                                 int table_dtype, const void* out, int out_dtype, int64_t out_ld,
+                                 krs_embed_fwd_route* route);
+
 /* ------------------------------------------------------------------------- *
  * K2  index-scatter gradient of K1
  *

@@ -60,6 +60,11 @@ class GemmRoute(C.Structure):
                 ("kernel", "splits", "reduce", "epilogue", "ep_vec", "thin_width", "thin_is_a")]
 
 
+class EmbedFwdRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in
+                ("kernel", "lpr", "has_w", "stream", "hot_rows", "bpg", "table_dtype", "out_dtype")] + [("blocks", C.c_int64)]
+
+
 # Prototype of every entry point include/krs.h declares, in its order: name -> (restype, argtypes).  Any pointer is a
 # void* (pass L.ptr(t), an int or None; ctypes arrays and C.byref(struct) where the C side takes an array or a struct).
 # tests/test_capi_symbols.py parses the header and checks this table against it row by row.
@@ -69,6 +74,8 @@ PROTOTYPES = {
     "krs_version": (_I, []),
     "krs_last_error": (C.c_char_p, []),
     "krs_embed_bag_fwd": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I64, _I, _I, _I, _P, _I, _I64, _P, _P, _P]),
+    "krs_embed_bag_fwd_last_route": (_I, [_P]),
+    "krs_embed_bag_fwd_plan_route": (_I, [_I, _P, _P, _I64, _I, _I, _I, _P, _I, _I64, _P]),
     "krs_embed_bag_bwd_workspace_bytes": (_SZ, [_I64]),
     "krs_embed_bag_bwd_plan": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I64, _I64, _P, _SZ, _P, _P]),
     "krs_embed_bag_bwd_plan_tables": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I64, _I64, _P, _SZ, _P, _P]),

@@ -20,6 +20,7 @@
 // Algorithmic bytes per lookup: D*s_t + 4 (+4 with weights); per bag D*s_o + 4.
 #include <cstdlib>
 
+#include "embed_fwd_plan.h"
 #include "krs_common.h"
 
 namespace krs {
@@ -426,7 +427,7 @@ __global__ __launch_bounds__(256) void embed_gather_hot1(const EmbedFwdParams p)
 // 64 pieces one slab row apart.  Reads are random either way.  Per-feature constants sit in LDS; a lane fetches
 // the id of its own unit (the ids of one feature are consecutive in memory, so the 64 strided 4-byte reads hit
 // lines that the neighbouring waves use too) and the groups take (id, feature, sample) by ds_bpermute.
-constexpr int kRowsMaxFeats = 128;
+constexpr int kRowsMaxFeats = eplan::kRowsMaxFeats;
 template <typename TT, int LPR, int UREQ>
 __global__ __launch_bounds__(256) void embed_gather_hot1_rows(const EmbedFwdParams p) {
   constexpr int G = 64 / LPR;
@@ -579,60 +580,73 @@ __global__ __launch_bounds__(256) void embed_bag_fwd_generic(const EmbedFwdParam
 // 164.8 / 159.3 us at the C3 L = 1 launch, profiles/archive/r2_k1_hot1_variants_and_lds_hotrows.txt); round 5 keeps the winner only.
 int g_hot_rows = 0;   // krs_embed_set_option(KRS_EMBED_OPT_HOTROWS, rows): 0 = no LDS staging (default), 64, 128
 
+// where the calling thread's last krs_embed_bag_fwd ran (krs_embed_bag_fwd_last_route): cleared when the entry starts,
+// written when it has queued its kernel, so a refused call and an empty one leave "none"
+thread_local krs_embed_fwd_route g_route = {};
+static_assert(eplan::kMaxBpg == 16, "embed_bag_fwd_vec stages MAXB = 16 bag ends per group");
+
+// the argument checks the decision needs, then the call's plan (embed_fwd_plan.h); a refused plan leaves its message.
+// Pointer VALUES are read for nullness and alignment, nothing is dereferenced, no HIP call is made.
+int embed_fwd_plan(int n_feats, const void* offsets, const float* weights, int64_t nnz, int batch, int dim,
+                   int table_dtype, const void* out, int out_dtype, int64_t out_ld, eplan::EmbedFwdPlan& pl) {
+  eplan::EmbedFwdCall call;
+  call.n_feats = n_feats; call.batch = batch; call.dim = dim; call.nnz = nnz; call.out_ld = out_ld;
+  call.table_dtype = table_dtype; call.out_dtype = out_dtype;
+  call.has_offsets = offsets != nullptr; call.has_weights = weights != nullptr;
+  call.out_addr = reinterpret_cast<uintptr_t>(out); call.hot_rows_opt = g_hot_rows;
+  pl = eplan::plan_embed_fwd(call);
+  if (pl.status != KRS_OK) return fail(pl.status, "embed_bag_fwd: %s", pl.why);
+  return KRS_OK;
+}
+
+// launches the kernel the route names, on the grid it names
 template <typename TT, typename OT, int LPR>
-int launch_vec(const EmbedFwdParams& p, bool one_hot, bool stream, hipStream_t st) {
-  constexpr int G = 64 / LPR;
-  if (one_hot) {
+int launch_lpr(const EmbedFwdParams& p, const krs_embed_fwd_route& rt, hipStream_t st) {
+  const dim3 grid((unsigned)rt.blocks), block(256);
+  if (rt.kernel == KRS_EMBED_FWD_HOT1_ROWS) {
     if constexpr (sizeof(TT) == sizeof(OT)) {
-      const bool rows_ok = p.n_feats <= kRowsMaxFeats &&
-                           ((reinterpret_cast<uintptr_t>(p.out) | (uintptr_t)(p.out_ld * sizeof(OT))) & 15) == 0;
-      if (rows_ok) {
-        const int64_t blocks = ceil_div(ceil_div((int64_t)p.batch * p.n_feats, 64), 4);
-        if (blocks > 0x7fffffffLL) return fail(KRS_ERR_UNSUPPORTED, "embed_bag_fwd: grid too large");
-        hipLaunchKernelGGL((embed_gather_hot1_rows<TT, LPR, 16>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-        KRS_CHECK_LAUNCH("embed_gather_hot1_rows");
-        return KRS_OK;
-      }
+      hipLaunchKernelGGL((embed_gather_hot1_rows<TT, LPR, 16>), grid, block, 0, st, p);
+      KRS_CHECK_LAUNCH("embed_gather_hot1_rows");
+      return KRS_OK;
+    } else {
+      return fail(KRS_ERR_UNSUPPORTED, "embed_bag_fwd: embed_gather_hot1_rows needs equal table and output types");
     }
-    const int64_t blocks = ceil_div(ceil_div(p.batch, 64) * p.n_feats, 4);
-    if (blocks > 0x7fffffffLL) return fail(KRS_ERR_UNSUPPORTED, "embed_bag_fwd: grid too large");
-    hipLaunchKernelGGL((embed_gather_hot1<TT, OT, LPR, 16>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+  }
+  if (rt.kernel == KRS_EMBED_FWD_HOT1) {
+    hipLaunchKernelGGL((embed_gather_hot1<TT, OT, LPR, 16>), grid, block, 0, st, p);
     KRS_CHECK_LAUNCH("embed_gather_hot1");
     return KRS_OK;
   }
-  const int64_t waves_per_feat = ceil_div(p.batch, (int64_t)G * p.bpg);
-  const int64_t blocks = ceil_div(waves_per_feat * p.n_feats, 4);
-  if (blocks == 0) return KRS_OK;
-  if (blocks > 0x7fffffffLL) return fail(KRS_ERR_UNSUPPORTED, "embed_bag_fwd: grid too large");
-#define KRS_K1_LAUNCH(W, S) \
-  hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, W, S>), dim3((unsigned)blocks), dim3(256), 0, st, p)
-  if constexpr (sizeof(TT) == 2 && sizeof(OT) == 2 && LPR == 16) {
+  if (rt.hot_rows) {
     // LDS staging of hot rows (opt-in: krs_embed_set_option(KRS_EMBED_OPT_HOTROWS, 64 | 128)): bf16 rows of 256 bytes
-    if (g_hot_rows > 0 && !p.weights && (int64_t)p.dim * 2 == LPR * 16) {
-      if (g_hot_rows >= 128) {
-        if (stream) hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, false, true, 128>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, false, false, 128>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+    if constexpr (sizeof(TT) == 2 && sizeof(OT) == 2 && LPR == 16) {
+      if (rt.hot_rows == 128) {
+        if (rt.stream) hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, false, true, 128>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, false, false, 128>), grid, block, 0, st, p);
       } else {
-        if (stream) hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, false, true, 64>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, false, false, 64>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+        if (rt.stream) hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, false, true, 64>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, false, false, 64>), grid, block, 0, st, p);
       }
       KRS_CHECK_LAUNCH("embed_bag_fwd_vec (hot rows in LDS)");
       return KRS_OK;
+    } else {
+      return fail(KRS_ERR_UNSUPPORTED, "embed_bag_fwd: hot rows are staged for bf16 rows of 256 bytes only");
     }
   }
-  if (p.weights) { if (stream) KRS_K1_LAUNCH(true, true); else KRS_K1_LAUNCH(true, false); }
-  else { if (stream) KRS_K1_LAUNCH(false, true); else KRS_K1_LAUNCH(false, false); }
+#define KRS_K1_LAUNCH(W, S) hipLaunchKernelGGL((embed_bag_fwd_vec<TT, OT, LPR, W, S>), grid, block, 0, st, p)
+  if (rt.has_w) { if (rt.stream) KRS_K1_LAUNCH(true, true); else KRS_K1_LAUNCH(true, false); }
+  else { if (rt.stream) KRS_K1_LAUNCH(false, true); else KRS_K1_LAUNCH(false, false); }
 #undef KRS_K1_LAUNCH
   KRS_CHECK_LAUNCH("embed_bag_fwd_vec");
   return KRS_OK;
 }
 
 template <typename TT, typename OT>
-int dispatch_lpr(const EmbedFwdParams& p, int row_pieces, bool one_hot, bool stream_mode, hipStream_t stream) {
-  if (row_pieces <= 8) return launch_vec<TT, OT, 8>(p, one_hot, stream_mode, stream);
-  if (row_pieces <= 16) return launch_vec<TT, OT, 16>(p, one_hot, stream_mode, stream);
-  if (row_pieces <= 32) return launch_vec<TT, OT, 32>(p, one_hot, stream_mode, stream);
-  return launch_vec<TT, OT, 64>(p, one_hot, stream_mode, stream);
+int launch_vec(const EmbedFwdParams& p, const krs_embed_fwd_route& rt, hipStream_t st) {
+  if (rt.lpr == 8) return launch_lpr<TT, OT, 8>(p, rt, st);
+  if (rt.lpr == 16) return launch_lpr<TT, OT, 16>(p, rt, st);
+  if (rt.lpr == 32) return launch_lpr<TT, OT, 32>(p, rt, st);
+  return launch_lpr<TT, OT, 64>(p, rt, st);
 }
 
 }  // namespace
@@ -674,15 +688,15 @@ extern "C" int krs_embed_bag_fwd(const krs_table* tables, const krs_feature* fea
                                  int table_dtype, void* out, int out_dtype, int64_t out_ld,
                                  float* bag_scale, int* err_flag, void* stream) {
   using namespace krs;
+  g_route = krs_embed_fwd_route{};
   KRS_REQUIRE(tables && feats && out, "embed_bag_fwd: null tables/feats/out");
   KRS_REQUIRE(ids || nnz == 0, "embed_bag_fwd: null ids");
-  KRS_REQUIRE(n_feats >= 0 && batch >= 0 && dim > 0 && nnz >= 0, "embed_bag_fwd: negative size");
-  KRS_REQUIRE((table_dtype == KRS_F32 || table_dtype == KRS_BF16) &&
-                  (out_dtype == KRS_F32 || out_dtype == KRS_BF16),
-              "embed_bag_fwd: bad dtype");
+  eplan::EmbedFwdPlan pl;
+  if (int rc = embed_fwd_plan(n_feats, offsets, weights, nnz, batch, dim, table_dtype, out, out_dtype, out_ld, pl)) return rc;
   KRS_REQUIRE((id_type == KRS_I32 || id_type == KRS_I64) && (off_type == KRS_I32 || off_type == KRS_I64),
               "embed_bag_fwd: bad index type");
-  if (n_feats == 0 || batch == 0) return KRS_OK;
+  const krs_embed_fwd_route& rt = pl.route;
+  if (rt.kernel == KRS_EMBED_FWD_NONE) return KRS_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
   EmbedFwdParams p;
@@ -691,32 +705,32 @@ extern "C" int krs_embed_bag_fwd(const krs_table* tables, const krs_feature* fea
   p.offsets = offsets; p.off64 = off_type == KRS_I64;
   p.weights = weights; p.batch = batch; p.dim = dim;
   p.out = out; p.out_ld = out_ld; p.bag_scale = bag_scale; p.err_flag = err_flag;
-  // ~16-32 lookups per group: enough row loads in flight per wave without
-  // making one group's stream long (nnz / bags = mean bag length).
-  const int64_t n_bags = (int64_t)n_feats * batch;
-  const int64_t mean_hot = nnz / n_bags > 0 ? nnz / n_bags : 1;
-  int bpg = (int)(32 / mean_hot);
-  p.bpg = bpg < 1 ? 1 : (bpg > 16 ? 16 : bpg);
-  p.bpg = p.bpg < 1 ? 1 : (p.bpg > 16 ? 16 : p.bpg);          // the kernel stages at most 16 bag ends per group
+  p.bpg = rt.bpg;   // bags per group of embed_bag_fwd_vec (the other kernels do not read it)
 
-  const int64_t row_bytes = (int64_t)dim * (table_dtype == KRS_BF16 ? 2 : 4);
-  if (row_bytes % 16 == 0 && row_bytes <= 1024) {
-    const int pieces = (int)(row_bytes / 16);
-    // every bag has exactly one lookup (dense, unweighted): the pure-gather kernel
-    const bool one_hot = offsets == nullptr && weights == nullptr && nnz == n_bags;
-    const bool stream_mode = nnz < 2 * n_bags;
-    if (table_dtype == KRS_F32)
-      return out_dtype == KRS_F32 ? dispatch_lpr<float, float>(p, pieces, one_hot, stream_mode, st)
-                                  : dispatch_lpr<float, uint16_t>(p, pieces, one_hot, stream_mode, st);
-    return out_dtype == KRS_F32 ? dispatch_lpr<uint16_t, float>(p, pieces, one_hot, stream_mode, st)
-                                : dispatch_lpr<uint16_t, uint16_t>(p, pieces, one_hot, stream_mode, st);
+  int rc;
+  if (rt.kernel == KRS_EMBED_FWD_GENERIC) {
+    hipLaunchKernelGGL(embed_bag_fwd_generic, dim3((unsigned)rt.blocks), dim3(256), 0, st, p, table_dtype, out_dtype, rt.lpr);
+    KRS_CHECK_LAUNCH("embed_bag_fwd_generic");
+    rc = KRS_OK;
+  } else if (table_dtype == KRS_F32) {
+    rc = out_dtype == KRS_F32 ? launch_vec<float, float>(p, rt, st) : launch_vec<float, uint16_t>(p, rt, st);
+  } else {
+    rc = out_dtype == KRS_F32 ? launch_vec<uint16_t, float>(p, rt, st) : launch_vec<uint16_t, uint16_t>(p, rt, st);
   }
-  int lpr = 1;
-  while (lpr < dim && lpr < 64) lpr <<= 1;
-  const int64_t blocks = ceil_div(n_bags, 256 / lpr);
-  if (blocks > 0x7fffffffLL) return fail(KRS_ERR_UNSUPPORTED, "embed_bag_fwd: grid too large");
-  hipLaunchKernelGGL(embed_bag_fwd_generic, dim3((unsigned)blocks), dim3(256), 0, st, p, table_dtype,
-                     out_dtype, lpr);
-  KRS_CHECK_LAUNCH("embed_bag_fwd_generic");
-  return KRS_OK;
+  if (rc == KRS_OK) g_route = rt;
+  return rc;
+}
+
+extern "C" int krs_embed_bag_fwd_plan_route(int n_feats, const void* offsets, const float* weights, int64_t nnz, int batch,
+                                            int dim, int table_dtype, const void* out, int out_dtype, int64_t out_ld,
+                                            krs_embed_fwd_route* route) {
+  krs::eplan::EmbedFwdPlan pl;
+  const int rc = krs::embed_fwd_plan(n_feats, offsets, weights, nnz, batch, dim, table_dtype, out, out_dtype, out_ld, pl);
+  if (route) *route = pl.route;
+  return rc;
+}
+
+extern "C" int krs_embed_bag_fwd_last_route(krs_embed_fwd_route* route) {
+  if (route) *route = krs::g_route;
+  return krs::g_route.kernel;
 }

@@ -35,6 +35,38 @@ def set_apply_depth(depth: int) -> None:
     L.check(L.lib().krs_embed_set_option(KRS_EMBED_OPT_APPLY_DEPTH, int(depth)), "krs_embed_set_option")
 
 
+EMBED_FWD_KERNELS = {0: None, 1: "vec", 2: "hot1", 3: "hot1_rows", 4: "generic"}
+_DTYPE_NAMES = {L.F32: "f32", L.BF16: "bf16"}
+
+
+def _fwd_route_dict(rt) -> dict:
+    if rt.kernel == 0:
+        return dict(kernel=None, lpr=0, has_w=False, stream=False, hot_rows=0, bpg=0, table_dtype=None, out_dtype=None,
+                    blocks=0)
+    return dict(kernel=EMBED_FWD_KERNELS[rt.kernel], lpr=int(rt.lpr), has_w=bool(rt.has_w), stream=bool(rt.stream),
+                hot_rows=int(rt.hot_rows), bpg=int(rt.bpg), table_dtype=_DTYPE_NAMES[rt.table_dtype],
+                out_dtype=_DTYPE_NAMES[rt.out_dtype], blocks=int(rt.blocks))
+
+
+def embed_fwd_last_route() -> dict:
+    """Where the calling thread's last krs_embed_bag_fwd ran (krs_embed_bag_fwd_last_route): kernel (an EMBED_FWD_KERNELS
+    name, None when no launch was made), lpr, and for the pooled kernel has_w, stream, hot_rows and bpg; the dtype pair as
+    "f32" / "bf16"; blocks.  A diagnostic for tests: it reads a host-side record, no device sync."""
+    rt = L.EmbedFwdRoute()
+    L.lib().krs_embed_bag_fwd_last_route(C.byref(rt))
+    return _fwd_route_dict(rt)
+
+
+def embed_fwd_plan_route(n_feats, offsets, weights, nnz, batch, dim, table_dtype, out, out_dtype, out_ld) -> dict:
+    """What a krs_embed_bag_fwd with these arguments would do (krs_embed_bag_fwd_plan_route; needs no GPU): offsets,
+    weights and out are addresses (ints or None: only nullness and the alignment of out are read), the dtypes L.F32 /
+    L.BF16.  The dict of embed_fwd_last_route() plus status, what the entry returns before its first launch."""
+    rt = L.EmbedFwdRoute()
+    rc = L.lib().krs_embed_bag_fwd_plan_route(int(n_feats), offsets, weights, int(nnz), int(batch), int(dim),
+                                              int(table_dtype), out, int(out_dtype), int(out_ld), C.byref(rt))
+    return dict(_fwd_route_dict(rt), status=int(rc))
+
+
 class _TableKey(NamedTuple):
     """Cache key of FusedBags.table_desc(): everything a krs_table descriptor carries, per table."""
 

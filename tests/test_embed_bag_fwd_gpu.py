@@ -81,14 +81,17 @@ def test_long_bags_and_batch_not_multiple_of_wave():
 
 def test_gather_is_bit_exact_for_hot1_sum():
     """hot=1 / sum / no weights is a pure row gather: output rows == table rows, bit for bit."""
-    from keras_rs_amd.embedding_ops import FusedBags
+    from keras_rs_amd.embedding_ops import FusedBags, embed_fwd_last_route
 
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(5)
-    for dt in (torch.float32, torch.bfloat16):
+    for dt, name, lpr in ((torch.float32, "f32", 32), (torch.bfloat16, "bf16", 16)):
         tab = torch.randn(1000, 128, generator=g).to(dt).to(dev)
         ids = torch.randint(0, 1000, (4096,), generator=g, dtype=torch.int32).to(dev)
         out, _ = FusedBags([tab], [(0, "sum", 0)]).forward(ids, 4096, hots=[1])
+        route = embed_fwd_last_route()          # the sample-major gather: 4096 units in waves of 64, four per workgroup
+        assert (route["kernel"], route["table_dtype"], route["out_dtype"], route["lpr"], route["blocks"]) == (
+            "hot1_rows", name, name, lpr, 16)
         assert torch.equal(out, tab[ids.long()])
 
 
@@ -169,7 +172,7 @@ def test_hot_rows_staged_in_lds_give_identical_outputs(rows, hots):
     staged rows, a table smaller than the staged window, and workgroups that straddle two features (no staging there)."""
 
     from keras_rs_amd import _lib as L
-    from keras_rs_amd.embedding_ops import FusedBags
+    from keras_rs_amd.embedding_ops import FusedBags, embed_fwd_last_route
 
     rng = np.random.default_rng(rows)
     dev = torch.device("cuda:0")
@@ -183,9 +186,14 @@ def test_hot_rows_staged_in_lds_give_identical_outputs(rows, hots):
     try:
         L.check(L.lib().krs_embed_set_option(3, 0), "set_option")
         ref, _ = fb.forward(ids, B, hots=hots)
+        ref_route = embed_fwd_last_route()
         L.check(L.lib().krs_embed_set_option(3, rows), "set_option")
         got, _ = fb.forward(ids, B, hots=hots)
+        got_route = embed_fwd_last_route()
         torch.cuda.synchronize()
     finally:
         L.lib().krs_embed_set_option(3, 0)
+    # the pooled kernel both times, the second with `rows` rows of a workgroup's table in LDS
+    assert (ref_route["kernel"], ref_route["lpr"], ref_route["hot_rows"]) == ("vec", 16, 0)
+    assert got_route == dict(ref_route, hot_rows=rows)
     assert torch.equal(ref, got)

@@ -4,6 +4,7 @@
 (sigmoid) -> binary cross-entropy, BinaryAccuracy and AUC (examples/ml_perf/main.py:201-210).
 
     python examples/dlrm_dcn_v2.py            # a few training steps on synthetic data (needs an MI355X)
+    python examples/dlrm_dcn_v2.py --quantize # ... then serve: int8 embedding tables, one batch predicted both ways
 
 The only edits against the reference model code: `layers.concat_features` instead of
 `ops.concatenate` (the embeddings land directly in the interaction input, no copy) with
@@ -137,7 +138,28 @@ def train_step(model, opt_box, inputs, labels, metrics=None):
     return loss.detach()
 
 
+def quantize_and_compare(model, inputs):
+    """Serving: predicts one batch with the float tables, quantizes the embedding layer to int8 rows
+    (DistributedEmbedding.quantize("int8")) and predicts it again.  Returns (largest absolute difference of the
+    predictions, table bytes before, table bytes after)."""
+    layer = model.embedding_layer
+    with torch.no_grad():
+        before = model(inputs).float()
+        table_bytes = sum(t.numel() * t.element_size() for t in layer.get_embedding_tables().values())
+        layer.quantize("int8")
+        after = model(inputs).float()
+    layer.check_ids(wait=True)
+    q_bytes = sum(q.numel() + step.numel() * 4 for q, step in layer.get_quantized_tables().values())
+    return float((before - after).abs().max()), table_bytes, q_bytes
+
+
 if __name__ == "__main__":
+    import argparse
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--quantize", action="store_true",
+                    help="after the training steps, quantize the embedding tables to int8 and predict one batch both ways")
+    args = ap.parse_args()
     dev = torch.device("cuda", 0)
     hots = [3, 2, 1, 2, 6, 1, 1, 1, 1, 7, 3, 8, 1, 6, 9, 5, 1, 1, 1, 12, 100, 27, 10, 3, 1, 1]
     model = build_model(8192, 100_000, hots)
@@ -147,3 +169,8 @@ if __name__ == "__main__":
         x, y = synthetic_batch(8192, 13, 100_000, hots, dev, seed=step)
         print(f"step {step}: loss {float(train_step(model, box, x, y, metrics)):.4f}")
     print(", ".join(f"{name} {float(value):.4f}" for name, value in metrics.result().items()))
+    if args.quantize:
+        x, _ = synthetic_batch(8192, 13, 100_000, hots, dev, seed=99)
+        diff, nbytes, qbytes = quantize_and_compare(model, x)
+        print(f"int8 tables: largest |prediction difference| {diff:.3e}; table bytes {nbytes} -> {qbytes} "
+              f"({qbytes / nbytes:.3f}x)")

@@ -41,7 +41,9 @@ typedef enum krs_status {
   KRS_ERR_WORKSPACE = -4    /* workspace too small */
 } krs_status;
 
-typedef enum krs_dtype { KRS_F32 = 0, KRS_BF16 = 1 } krs_dtype;
+/* KRS_I8: int8 rows with one fp32 step per row (krs_quantize_rows_q8, krs_embed_bag_fwd_q8); every other entry takes
+ * KRS_F32 / KRS_BF16 only and refuses it. */
+typedef enum krs_dtype { KRS_F32 = 0, KRS_BF16 = 1, KRS_I8 = 2 } krs_dtype;
 typedef enum krs_itype { KRS_I32 = 0, KRS_I64 = 1 } krs_itype;
 
 /* EmbedReduce combiners, embed_reduce.py:10 (SUPPORTED_COMBINERS). */
@@ -62,13 +64,15 @@ typedef enum krs_activation {
 #define KRS_FLAG_ID_OUT_OF_RANGE 1
 #define KRS_FLAG_BAD_OFFSETS 2
 #define KRS_FLAG_CAPACITY_OVERFLOW 4   /* krs_shard_route_static: lookups beyond the static capacity were dropped */
+#define KRS_FLAG_NONFINITE_ROW 8       /* krs_quantize_rows_q8: a row held a NaN or an infinity (stored as q = 0, step = 0) */
 
 /* One embedding table ([vocab, dim] row-major).  Lives in DEVICE memory as an
  * array indexed by krs_feature.table.  Replaces the `embeddings` variable of
  * one EmbedReduce sublayer (base_distributed_embedding.py:836-852). */
 typedef struct krs_table {
-  void* weights;    /* [vocab, dim] fp32 or bf16 (table dtype of the call) */
-  float* slot;      /* optimizer slot: Adagrad accumulator [vocab, dim] fp32, or NULL */
+  void* weights;    /* [vocab, dim] fp32 or bf16 (table dtype of the call); krs_embed_bag_fwd_q8: [vocab, dim] int8 rows */
+  float* slot;      /* optimizer slot: Adagrad accumulator [vocab, dim] fp32, or NULL;
+                       krs_embed_bag_fwd_q8 (a quantized table has no optimizer): the [vocab] fp32 step of every row */
   int64_t row_base; /* global row id of row 0: tables of one call get disjoint
                        [row_base, row_base+vocab) ranges (sort keys of the backward),
                        in any order: row_base need not ascend with the table index */
@@ -150,6 +154,47 @@ int krs_embed_bag_fwd_last_route(krs_embed_fwd_route* route);
 int krs_embed_bag_fwd_plan_route(int n_feats, const void* offsets, const float* weights, int64_t nnz, int batch, int dim,
                                  int table_dtype, const void* out, int out_dtype, int64_t out_ld,
                                  krs_embed_fwd_route* route);
+
+/* ------------------------------------------------------------------------- *
+ * K16  int8 row-quantized tables for inference: the quantizer and the lookup
+ *
+ * The stored form of keras.layers.Embedding.quantize("int8") -- int8 rows plus one fp32 scale per row, abs-max --
+ * except that the stored scale is the DEQUANTIZATION step (Keras stores its reciprocal), so that a gather is one
+ * correctly rounded multiply.  For a row x[0..dim) (bf16 widened exactly), all in fp32 with IEEE operations:
+ *   a    = max_c |x[c]|
+ *   inv  = 127.0f / (a + 1e-7f)                      (correctly rounded division)
+ *   q[c] = clip(rint(x[c] * inv), -127, 127)         (rint = round half to even)
+ *   step = (a + 1e-7f) / 127.0f                      (correctly rounded division)
+ * A row holding a NaN or an infinity gets q = 0, step = 0 and raises KRS_FLAG_NONFINITE_ROW in err_flag.
+ *
+ * table [vocab, dim] fp32 / bf16 (table_dtype), q [vocab, dim] int8, step [vocab] fp32; any dim >= 1, vocab up to
+ * INT32_MAX.  One pass: a row of up to 1024 elements is read once and kept in registers between the abs-max and the
+ * rounding, a longer one is read twice.  No allocation, no host wait.
+ * ------------------------------------------------------------------------- */
+int krs_quantize_rows_q8(const void* table, int table_dtype, int64_t vocab, int dim, int8_t* q, float* step,
+                         int* err_flag, void* stream);
+
+/* The K1 lookup on quantized tables: krs_table.weights = the int8 rows, krs_table.slot = the [vocab] steps.
+ *   out[b*out_ld + feats[f].out_col + c] = scale(f,b) * sum_{p in bag(f,b)} w[p] * step[ids[p]] * q[ids[p], c]
+ * Combiners, divide_no_nan and the out-of-range rule are krs_embed_bag_fwd's (an out-of-range id contributes nothing,
+ * raises KRS_FLAG_ID_OUT_OF_RANGE and still counts in the denominator).  Accumulation is fp32: the factor w * step is
+ * formed once per lookup, every element is then one fused multiply-add, in ascending p.  Every int8 value is
+ * dequantized, -128 included.  Every table needs vocab >= 1: row 0 and step[0] are read (and masked) as the stand-in of
+ * an invalid or padding slot, as krs_embed_bag_fwd reads row 0.  Arguments as krs_embed_bag_fwd without table_dtype and bag_scale (forward only).  No
+ * allocation and no host wait: a lookup can be captured in a HIP graph. */
+int krs_embed_bag_fwd_q8(const krs_table* tables, const krs_feature* feats, int n_feats,
+                         const void* ids, int id_type,
+                         const void* offsets, int off_type,
+                         const float* weights, int64_t nnz,
+                         int batch, int dim,
+                         void* out, int out_dtype, int64_t out_ld,
+                         int* err_flag, void* stream);
+/* As krs_embed_bag_fwd_last_route / _plan_route, for krs_embed_bag_fwd_q8 (csrc/embed_fwd_q8_plan.h).  The record has
+ * table_dtype = KRS_I8; kernel is KRS_EMBED_FWD_VEC (dim a multiple of 16, at most 1024: one 16-byte piece of 16
+ * elements per lane, lpr 8 / 16 / 32 / 64) or KRS_EMBED_FWD_GENERIC; stream and hot_rows stay 0.  Refusals as K1's. */
+int krs_embed_bag_fwd_q8_last_route(krs_embed_fwd_route* route);
+int krs_embed_bag_fwd_q8_plan_route(int n_feats, const void* offsets, const float* weights, int64_t nnz, int batch, int dim,
+                                    const void* out, int out_dtype, int64_t out_ld, krs_embed_fwd_route* route);
 
 /* ------------------------------------------------------------------------- *
  * K2  index-scatter gradient of K1

@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KRS_LIB", os.path.join(_HERE, "libkrs_hip.so"))
 
-F32, BF16 = 0, 1
+F32, BF16, I8 = 0, 1, 2
 I32, I64 = 0, 1
 SUM, MEAN, SQRTN = 0, 1, 2
 COMBINERS = {"sum": SUM, "mean": MEAN, "sqrtn": SQRTN}
@@ -24,6 +24,7 @@ ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3
 FLAG_ID_OUT_OF_RANGE = 1
 FLAG_BAD_OFFSETS = 2
 FLAG_CAPACITY_OVERFLOW = 4
+FLAG_NONFINITE_ROW = 8
 MAX_LIST = 4096   # KRS_RANK_MAX_LIST
 
 # struct layouts of include/krs.h
@@ -76,6 +77,10 @@ PROTOTYPES = {
     "krs_embed_bag_fwd": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I64, _I, _I, _I, _P, _I, _I64, _P, _P, _P]),
     "krs_embed_bag_fwd_last_route": (_I, [_P]),
     "krs_embed_bag_fwd_plan_route": (_I, [_I, _P, _P, _I64, _I, _I, _I, _P, _I, _I64, _P]),
+    "krs_quantize_rows_q8": (_I, [_P, _I, _I64, _I, _P, _P, _P, _P]),
+    "krs_embed_bag_fwd_q8": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I64, _I, _I, _P, _I, _I64, _P, _P]),
+    "krs_embed_bag_fwd_q8_last_route": (_I, [_P]),
+    "krs_embed_bag_fwd_q8_plan_route": (_I, [_I, _P, _P, _I64, _I, _I, _P, _I, _I64, _P]),
     "krs_embed_bag_bwd_workspace_bytes": (_SZ, [_I64]),
     "krs_embed_bag_bwd_plan": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I64, _I64, _P, _SZ, _P, _P]),
     "krs_embed_bag_bwd_plan_tables": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I64, _I64, _P, _SZ, _P, _P]),

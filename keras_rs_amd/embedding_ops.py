@@ -315,6 +315,95 @@ class FusedBags:
         return rows[:u], vals[:u]
 
 
+# ---- K16: int8 row-quantized tables for inference ---------------------------------------------------------------------
+_DTYPE_NAMES[L.I8] = "i8"
+
+
+def embed_fwd_q8_last_route() -> dict:
+    """Where the calling thread's last krs_embed_bag_fwd_q8 ran, in the form of embed_fwd_last_route(): kernel "vec" or
+    "generic", table_dtype "i8"; stream and hot_rows stay False / 0."""
+    rt = L.EmbedFwdRoute()
+    L.lib().krs_embed_bag_fwd_q8_last_route(C.byref(rt))
+    return _fwd_route_dict(rt)
+
+
+def embed_fwd_q8_plan_route(n_feats, offsets, weights, nnz, batch, dim, out, out_dtype, out_ld) -> dict:
+    """What a krs_embed_bag_fwd_q8 with these arguments would do (krs_embed_bag_fwd_q8_plan_route; needs no GPU), as
+    embed_fwd_plan_route()."""
+    rt = L.EmbedFwdRoute()
+    rc = L.lib().krs_embed_bag_fwd_q8_plan_route(int(n_feats), offsets, weights, int(nnz), int(batch), int(dim), out,
+                                                 int(out_dtype), int(out_ld), C.byref(rt))
+    return dict(_fwd_route_dict(rt), status=int(rc))
+
+
+def quantize_rows(table: torch.Tensor, err_flag: torch.Tensor | None = None):
+    """(q [V, D] int8, step [V] fp32) of a [V, D] fp32 / bf16 table (krs_quantize_rows_q8): per row, abs-max int8 with the
+    dequantization step (a + 1e-7) / 127.  A row holding a NaN or an infinity gets q = 0 and step = 0 and raises
+    L.FLAG_NONFINITE_ROW in `err_flag` (device int32[1], optional).  No host wait."""
+    L.require_device(table, "quantize_rows: table")
+    if table.dim() != 2 or table.shape[1] < 1:
+        raise L.KrsError(f"quantize_rows: expected a [V, D] table, got shape {tuple(table.shape)}")
+    if not table.is_contiguous():
+        raise L.KrsError("quantize_rows: the table must be contiguous")
+    q = torch.empty(table.shape, dtype=torch.int8, device=table.device)
+    step = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
+    rc = L.lib().krs_quantize_rows_q8(L.ptr(table), L.fdtype(table), table.shape[0], table.shape[1], L.ptr(q), L.ptr(step),
+                                      L.ptr(err_flag), L.stream_ptr())
+    L.check(rc, "krs_quantize_rows_q8")
+    return q, step
+
+
+class QuantizedBags(FusedBags):
+    """FusedBags for int8 row-quantized tables, forward only: `q_tables` [V, D] int8 and `steps` [V] fp32 per table,
+    `features` = [(table_index, combiner, out_col)].  The descriptors are FusedBags' (cached the same way); a table's step
+    array travels in the slot field of its krs_table."""
+
+    def __init__(self, q_tables: Sequence[torch.Tensor], steps: Sequence[torch.Tensor], features: Sequence[tuple]):
+        if len(q_tables) != len(steps):
+            raise L.KrsError("QuantizedBags: one step array per table")
+        for q, s in zip(q_tables, steps):
+            if q.dtype != torch.int8 or s.dtype != torch.float32 or s.dim() != 1 or q.dim() != 2 or \
+                    s.shape[0] != q.shape[0] or not s.is_contiguous():
+                raise L.KrsError("QuantizedBags: tables are [V, D] int8 with one contiguous [V] float32 step array each")
+            if q.shape[0] == 0:      # (invalid and padding slots read row 0 and step[0] as a stand-in)
+                raise L.KrsError("QuantizedBags: a table needs at least one row")
+            L.require_device(s, "quantized table steps")
+        super().__init__(q_tables, features, slots=steps)
+
+    def forward(self, ids: torch.Tensor, batch: int, hots: Sequence[int] | None = None,
+                offsets: torch.Tensor | None = None, weights: torch.Tensor | None = None,
+                out: torch.Tensor | None = None, out_dtype: torch.dtype | None = None,
+                err_flag: torch.Tensor | None = None) -> torch.Tensor:
+        """As FusedBags.forward without the bag scale; returns out [batch, ld] (float32 unless out / out_dtype say bf16)."""
+        L.require_device(ids, "ids")
+        n_feats = len(self.features)
+        if (hots is None) == (offsets is None):
+            raise L.KrsError("QuantizedBags.forward: give exactly one of hots (dense) / offsets (CSR)")
+        if out is None:
+            ld = max(col for _, _, col in self.features) + self.dim
+            out = torch.empty((batch, ld), dtype=out_dtype or torch.float32, device=ids.device)
+        if out.stride(-1) != 1:
+            raise L.KrsError("out must be row-major")
+        if weights is not None and weights.dtype != torch.float32:
+            weights = weights.float()
+        tdesc, fdesc = self.table_desc(), self.feature_desc(batch, hots, ids.device)
+        with probe.span("k1_q8"):
+            rc = L.lib().krs_embed_bag_fwd_q8(
+                L.ptr(tdesc), L.ptr(fdesc), n_feats,
+                L.ptr(ids), L.itype(ids),
+                L.ptr(offsets), L.itype(offsets) if offsets is not None else L.I32,
+                L.ptr(weights), ids.numel(), batch, self.dim,
+                L.ptr(out), L.fdtype(out), out.stride(0),
+                L.ptr(err_flag), L.stream_ptr())
+        L.check(rc, "krs_embed_bag_fwd_q8")
+        return out
+
+    def _training_only(self, *_, **__):
+        raise L.KrsError("QuantizedBags is forward only: an int8 table has no gradient and no optimizer")
+
+    plan_backward = backward_dense = backward_fused = backward_sparse = store_lrs = _training_only
+
+
 class StepConstants:
     """The optimizer constants of a fused group that change from step to step -- scheduled learning rates and Adam's
     bias-correction factor sqrt(1 - beta_2^t) / (1 - beta_1^t) -- evaluated on the HOST once per update (the reference does

@@ -183,9 +183,13 @@ def make_layers(keras) -> types.SimpleNamespace:
         def build(self, input_shapes=None):
             self._impl.build(input_shapes)
             track = getattr(self, "_track_variable", None)
+            # (kept beside Keras' own tracking, not through it: quantize() has to find and drop exactly these)
+            object.__setattr__(self, "_table_variables", [])
             if track is not None:       # Keras 3: torch Parameters wrapped as keras Variables
                 for name, p in self._impl.named_parameters():
-                    track(keras.Variable(p, trainable=bool(p.requires_grad), name=name))
+                    v = keras.Variable(p, trainable=bool(p.requires_grad), name=name)
+                    track(v)
+                    self._table_variables.append(v)
             self.built = True
 
         # Keras checkpoints (.keras / .weights.h5, model.save_weights) call these two per layer.  The tables are
@@ -254,6 +258,27 @@ def make_layers(keras) -> types.SimpleNamespace:
 
         def set_embedding_tables(self, tables):
             self._impl.set_embedding_tables(tables)
+
+        def quantize(self, mode, **kwargs: Any):
+            """keras.layers.Layer.quantize for the embedding tables: "int8" rows with one fp32 step per row, inference
+            only (keras_rs_amd.layers.DistributedEmbedding.quantize)."""
+            del kwargs                  # (Keras passes type_check / config; the wrapped layer has one int8 form)
+            self._impl.quantize(mode)
+            # The Variables tracked at build() wrap the float tables and stacks the inner layer has just dropped: untrack
+            # them, or they keep that storage alive and `weights` goes on listing tables that no lookup reads.
+            untrack = getattr(self, "_untrack_variable", None)
+            for v in self._table_variables:
+                if untrack is not None:
+                    untrack(v)
+                else:       # a Layer without Keras 3's tracker: its plain variable lists
+                    for attr in ("_variables", "_trainable_variables", "_non_trainable_variables"):
+                        held = getattr(self, attr, None)
+                        if isinstance(held, list):
+                            held[:] = [x for x in held if x is not v]
+            self._table_variables.clear()
+
+        def get_quantized_tables(self):
+            return self._impl.get_quantized_tables()
 
         def compute_output_shape(self, input_shapes):
             return self._impl.compute_output_shape(input_shapes)

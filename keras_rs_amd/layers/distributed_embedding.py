@@ -33,11 +33,13 @@ from typing import Any, Sequence
 import numpy as np
 import torch
 
+from keras_rs_amd import _lib as L
 from keras_rs_amd.autograd import EmbedBagFn, EmbedBagFusedFn
-from keras_rs_amd.embedding_ops import FusedBags
+from keras_rs_amd.embedding_ops import FusedBags, QuantizedBags, quantize_rows
 from keras_rs_amd.layers import base
 from keras_rs_amd.layers.distributed_embedding_config import FeatureConfig
-from keras_rs_amd.layers.embed_reduce import Ragged, check_shapes_compatible
+from keras_rs_amd.layers.embed_reduce import (Ragged, check_quantize_request, check_shapes_compatible, keep_fp32_steps,
+                                               restore_fp32_steps)
 from keras_rs_amd.layers.embedding_host import IdRangeCheck, fuse_group_inputs, next_fused_hyper
 
 SUPPORTED_PLACEMENTS = ("auto", "default_device", "sparsecore")
@@ -276,6 +278,7 @@ class DistributedEmbedding(base.Layer):
         self._slot_buffer_names: dict[int, str] = {}
         self._stacks: list = []
         self._stack_of: dict[int, tuple] = {}      # table -> (stacked parameter, first row) for named stacks
+        self.quantization_mode = None              # "int8" after quantize(): tables are int8 rows + fp32 steps (buffers)
         if "sparsecore" in self._placement_to_path_to_feature_config:
             self._sparsecore_init(self._placement_to_path_to_feature_config["sparsecore"], table_stacking)
         if "default_device" in self._placement_to_path_to_feature_config:
@@ -501,11 +504,15 @@ class DistributedEmbedding(base.Layer):
     # ---- module state: optimizer slots are buffers, update counts travel as extra state ---------------
     def _apply(self, fn, recurse=True):
         """.to() / .cuda() / .float(): torch replaces buffer tensors; re-point the kernel descriptors at them."""
+        keep = keep_fp32_steps(self)          # (a quantized layer's steps stay fp32 under .half() / .bfloat16())
         out = super()._apply(fn, recurse)
+        restore_fp32_steps(self, keep)
         for key, bname in getattr(self, "_slot_buffer_names", {}).items():
             self._table_slots[key] = self._buffers[bname]
         for key, (stack, r0) in getattr(self, "_stack_of", {}).items():
             self._table_params[key] = stack.data[r0:r0 + self._table_params[key].shape[0]]
+        for key, bname in getattr(self, "_q_buffer_names", {}).items():
+            self._table_params[key] = self._buffers[bname]
         for groups in getattr(self, "_groups", {}).values():
             for g in groups:
                 if g.bags is not None:
@@ -536,7 +543,79 @@ class DistributedEmbedding(base.Layer):
         get_embedding_tables() and by callers that want the verdict on the last step now."""
         self._id_check.check(wait)
 
+    # ---- int8 rows for inference -------------------------------------------------------------------------------------
+    def quantize(self, mode: str = "int8") -> None:
+        """Replaces every table of both placements by int8 rows and one fp32 step per row (krs_quantize_rows_q8; the
+        tables of a named stack row by row, like any table) and frees the float tables, the stacks and the optimizer
+        slots.  From then on the layer serves lookups only: `call(..., training=True)` and `set_embedding_tables` raise,
+        `get_embedding_tables()` returns the dequantized fp32 tables q * step, `get_quantized_tables()` the stored pairs,
+        and state_dict() holds `<placement>_<table>_q` / `_step` and no float table.  Lookups, slab_lead_cols /
+        concat_features and check_ids work as before.  A table with a NaN or an infinity raises ValueError and leaves
+        the layer as it was."""
+        check_quantize_request(self, mode)
+        done = []
+        err = None
+        for placement, groups in self._groups.items():
+            for g in groups:
+                for tc in g.table_configs:
+                    table = self._table_params[id(tc)].detach()
+                    if err is None:
+                        err = torch.zeros(1, dtype=torch.int32, device=table.device)
+                    done.append((placement, tc, quantize_rows(table.contiguous(), err)))
+        if err is not None and int(err.item()) & L.FLAG_NONFINITE_ROW:     # one host read; nothing has been replaced yet
+            raise ValueError(f"DistributedEmbedding '{self.name}': a table row holds a NaN or an infinity; the layer "
+                             "cannot be quantized.")
+        for name in [n for n, p in self._parameters.items() if p is not None]:
+            del self._parameters[name]                      # every parameter of this layer is a table or a stack
+        self._weight_order.clear()
+        self._regularized.clear()
+        for bname in self._slot_buffer_names.values():
+            del self._buffers[bname]
+        self._slot_buffer_names.clear()
+        self._stack_of.clear()
+        self._q_buffer_names: dict[int, str] = {}
+        for placement, tc, (q, step) in done:
+            stem = f"{placement}_{tc.name}".replace(".", "_")
+            self.register_buffer(stem + "_q", q, persistent=True)
+            self.register_buffer(stem + "_step", step, persistent=True)
+            # the table / slot maps keep their roles for _apply (.to() re-points the descriptors through them): rows, steps
+            self._table_params[id(tc)], self._table_slots[id(tc)] = q, step
+            self._q_buffer_names[id(tc)], self._slot_buffer_names[id(tc)] = stem + "_q", stem + "_step"
+        for groups in self._groups.values():
+            for g in groups:
+                g.bags = QuantizedBags([self._table_params[id(tc)] for tc in g.table_configs],
+                                       [self._table_slots[id(tc)] for tc in g.table_configs], g.bags.features)
+                g.fused = g.table_opts = g._constants = None
+        self.quantization_mode = mode
+
+    def get_quantized_tables(self) -> dict:
+        """{TableConfig.name: (q [vocabulary_size, embedding_dim] int8, step [vocabulary_size] fp32)} of a quantized layer."""
+        if not self.quantization_mode:
+            raise RuntimeError(f"DistributedEmbedding '{self.name}' is not quantized: call quantize('int8') first.")
+        return {tc.name: (self._table_params[id(tc)], self._table_slots[id(tc)])
+                for groups in self._groups.values() for g in groups for tc in g.table_configs}
+
+    def _call_groups_quantized(self, placement: str, inputs: dict, weights: dict | None):
+        outputs = {}
+        groups = self._groups[placement]
+        for gi, g in enumerate(groups):
+            fi = inputs[f"group{gi}"]
+            w = None if weights is None else weights[f"group{gi}"]
+            n = len(g.paths)
+            lead = self.slab_lead_cols if placement == "sparsecore" and len(groups) == 1 else 0
+            slab = torch.empty((fi["batch"], lead + n * g.dim), dtype=self.compute_dtype, device=fi["ids"].device)
+            g.bags.forward(fi["ids"], fi["batch"], hots=fi["hots"], offsets=fi["offsets"], weights=w, out=slab[:, lead:],
+                           err_flag=self._id_check.flag(fi["ids"].device))
+            for i, path in enumerate(g.paths):
+                o = slab[:, lead + i * g.dim:lead + (i + 1) * g.dim]
+                if placement == "sparsecore":       # lets layers.concat_features find the slab (zero-copy concat)
+                    o._krs_slab = (slab, lead + i * g.dim, n, lead)
+                outputs[path] = o
+        return outputs
+
     def _call_groups(self, placement: str, inputs: dict, weights: dict | None):
+        if self.quantization_mode:
+            return self._call_groups_quantized(placement, inputs, weights)
         outputs = {}
         for gi, g in enumerate(self._groups[placement]):
             key = f"group{gi}"
@@ -569,7 +648,8 @@ class DistributedEmbedding(base.Layer):
         tables = {}
         for g in self._groups.get(placement, []):
             for tc in g.table_configs:
-                tables[tc.name] = self._table_params[id(tc)].detach()
+                p = self._table_params[id(tc)].detach()
+                tables[tc.name] = p.float() * self._table_slots[id(tc)][:, None] if self.quantization_mode else p
         return tables
 
     def _sparsecore_get_embedding_tables(self):
@@ -632,6 +712,9 @@ class DistributedEmbedding(base.Layer):
         return isinstance(inputs, dict) and "preprocessed_inputs_per_placement" in inputs
 
     def call(self, inputs, weights=None, training: bool = False):
+        if training and self.quantization_mode:
+            raise RuntimeError(f"DistributedEmbedding '{self.name}' is int8-quantized: it serves lookups only "
+                               "(training=True needs the float tables, which quantize() freed).")
         self.check_ids()   # verdict on earlier steps, if it has arrived (no wait)
         pre = inputs if self._is_preprocessed(inputs) else self.preprocess(inputs, weights, training)
         pre = pre["preprocessed_inputs_per_placement"]
@@ -646,7 +729,8 @@ class DistributedEmbedding(base.Layer):
             self._feature_deeply_nested_placement_and_paths, is_leaf=_is_placement_leaf)
 
     def get_embedding_tables(self) -> dict[str, torch.Tensor]:
-        """{TableConfig.name: [vocabulary_size, embedding_dim]} (base:810-825)."""
+        """{TableConfig.name: [vocabulary_size, embedding_dim]} (base:810-825); of a quantized layer, the dequantized
+        fp32 tables q * step."""
         if not self.built:
             self.build(None)
         self.check_ids(wait=True)
@@ -659,6 +743,9 @@ class DistributedEmbedding(base.Layer):
 
     def set_embedding_tables(self, tables: dict) -> None:
         """Overwrites tables by name (jax/distributed_embedding.py:746-756)."""
+        if self.quantization_mode:
+            raise RuntimeError(f"DistributedEmbedding '{self.name}' is int8-quantized: its tables cannot be set (build a "
+                               "float layer, set its tables and quantize that).")
         if not self.built:
             self.build(None)
         with torch.no_grad():

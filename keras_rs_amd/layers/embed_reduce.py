@@ -11,7 +11,8 @@ import numpy as np
 import torch
 
 from keras_rs_amd.autograd import EmbedBagFn
-from keras_rs_amd.embedding_ops import FusedBags
+from keras_rs_amd import _lib as L
+from keras_rs_amd.embedding_ops import FusedBags, QuantizedBags, quantize_rows
 from keras_rs_amd.layers import base
 
 SUPPORTED_COMBINERS = ("mean", "sum", "sqrtn")
@@ -62,6 +63,43 @@ def check_shapes_compatible(a, b) -> bool:
     return all(x is None or y is None or x == y for x, y in zip(a, b))
 
 
+def check_quantize_request(layer, mode) -> None:
+    """What every quantize() refuses before it touches the device: a mode other than "int8", an unbuilt layer, a layer
+    that is quantized already."""
+    if mode != "int8":
+        raise ValueError(f"Invalid quantization mode {mode!r}: the embedding layers support 'int8' only.")
+    if not layer.built:
+        raise RuntimeError(f"{type(layer).__name__} '{layer.name}' is not built: build it (or call it once) before "
+                           "quantize(): there is no table to quantize yet.")
+    if getattr(layer, "quantization_mode", None):
+        raise RuntimeError(f"{type(layer).__name__} '{layer.name}' is already quantized ({layer.quantization_mode}).")
+
+
+def quantize_rows_checked(table: torch.Tensor, what: str):
+    """embedding_ops.quantize_rows, then ONE host read of its error word: a row with a NaN or an infinity raises."""
+    err = torch.zeros(1, dtype=torch.int32, device=table.device)
+    q, step = quantize_rows(table.contiguous(), err)
+    if int(err.item()) & L.FLAG_NONFINITE_ROW:
+        raise ValueError(f"{what}: a table row holds a NaN or an infinity; it cannot be quantized.")
+    return q, step
+
+
+def keep_fp32_steps(layer) -> dict:
+    """The fp32 step buffers (`*_step`) of a quantized layer, by buffer name, taken before a Module._apply."""
+    if not getattr(layer, "quantization_mode", None):
+        return {}
+    return {n: b for n, b in layer._buffers.items() if n.endswith("_step") and b is not None}
+
+
+def restore_fp32_steps(layer, keep: dict) -> None:
+    """After a Module._apply: a step buffer that the call cast to another dtype gets its fp32 values back, on the
+    device the call moved it to."""
+    for name, before in keep.items():
+        now = layer._buffers[name]
+        if now.dtype != torch.float32:
+            layer._buffers[name] = before.to(now.device)
+
+
 class EmbedReduce(base.Layer):
     """Args (embed_reduce.py:133-160): input_dim, output_dim, embeddings_initializer,
     embeddings_regularizer, embeddings_constraint, mask_zero, weights (initial table),
@@ -86,6 +124,7 @@ class EmbedReduce(base.Layer):
         self._initial_weights = weights
         self.register_parameter("embeddings", None)
         self._bags: dict = {}
+        self.quantization_mode = None      # "int8" after quantize(): the table is two buffers, embeddings_q / embeddings_step
 
     def build(self, *_) -> None:
         if self.embeddings is None:
@@ -100,15 +139,58 @@ class EmbedReduce(base.Layer):
     def _input_shapes(self, args):
         return (getattr(args[0], "shape", None),)
 
+    # ---- int8 rows for inference (keras.layers.Embedding.quantize("int8")) ------------------------------------------
+    def quantize(self, mode: str = "int8") -> None:
+        """Replaces the float table by int8 rows and one fp32 step per row (krs_quantize_rows_q8: abs-max per row, step =
+        (max |x| + 1e-7) / 127) and frees it: `weights` becomes empty, state_dict() holds `embeddings_q` / `embeddings_step`,
+        and `call` runs the int8 gather + pool kernel.  Inference only: the outputs do not require grad.  A table with a
+        NaN or an infinity raises ValueError and leaves the layer as it was."""
+        check_quantize_request(self, mode)
+        q, step = quantize_rows_checked(self.embeddings.detach(), f"{type(self).__name__} '{self.name}'")
+        self.register_buffer("embeddings_q", q, persistent=True)
+        self.register_buffer("embeddings_step", step, persistent=True)
+        self.embeddings = None
+        self._weight_order.clear()
+        self._regularized.clear()
+        self._bags.clear()
+        self.quantization_mode = mode
+
+    def _table(self) -> torch.Tensor:
+        return self.embeddings_q if self.quantization_mode else self.embeddings
+
+    def _apply(self, fn, recurse=True):
+        """.to() / .cuda() / .half() / .bfloat16(): the steps of a quantized table move with the module and stay fp32 (the
+        kernel reads them as fp32; a cast would also round them)."""
+        keep = keep_fp32_steps(self)
+        out = super()._apply(fn, recurse)
+        restore_fp32_steps(self, keep)
+        return out
+
     def _fused(self, combiner: str) -> FusedBags:
         fb = self._bags.get(combiner)
+        if self.quantization_mode:
+            if fb is None or fb.tables[0] is not self.embeddings_q or fb.slots[0] is not self.embeddings_step:
+                fb = self._bags[combiner] = QuantizedBags([self.embeddings_q], [self.embeddings_step], [(0, combiner, 0)])
+            return fb
         if fb is None or fb.tables[0] is not self.embeddings:
             fb = FusedBags([self.embeddings], [(0, combiner, 0)])
             self._bags[combiner] = fb
         return fb
 
+    def _lookup(self, combiner, ids, batch, hots, offsets, w, out_dtype) -> torch.Tensor:
+        """One fused gather + pool of this layer's table: [batch, output_dim]."""
+        if not self.quantization_mode:
+            return EmbedBagFn.apply(self._fused(combiner), ids, batch, hots, offsets, w, out_dtype, True, self.embeddings)[0]
+        capturing = base.stream_capturing()       # (a captured lookup cannot read its error word: no id check there)
+        err = None if capturing else torch.zeros(1, dtype=torch.int32, device=ids.device)
+        out = self._fused(combiner).forward(ids, batch, hots=hots, offsets=offsets, weights=w, out_dtype=out_dtype,
+                                            err_flag=err)
+        if err is not None and int(err.item()) & L.FLAG_ID_OUT_OF_RANGE:
+            raise IndexError("embedding id out of range for its table (ids are never clamped)")
+        return out
+
     def call(self, inputs, weights=None) -> torch.Tensor:
-        dev = self.embeddings.device
+        dev = self._table().device
         if isinstance(inputs, Ragged):
             ids = as_index_tensor(inputs.values, dev).reshape(-1)
             offsets = torch.as_tensor(np.asarray(inputs.row_offsets) if not isinstance(inputs.row_offsets, torch.Tensor)
@@ -122,9 +204,8 @@ class EmbedReduce(base.Layer):
                     raise ValueError(f"The shape of `weights`: {tuple(w.shape)} is not compatible with the ragged "
                                      f"`inputs` ({ids.numel()} values).")
             out_dtype = self._out_dtype(w)
-            return EmbedBagFn.apply(self._fused(self.combiner), ids, batch, None, offsets,
-                                    None if w is None else w.float().reshape(-1), out_dtype, True,
-                                    self.embeddings)[0]
+            return self._lookup(self.combiner, ids, batch, None, offsets, None if w is None else w.float().reshape(-1),
+                                out_dtype)
 
         ids = as_index_tensor(inputs, dev)
         if ids.dim() not in (1, 2):
@@ -158,8 +239,7 @@ class EmbedReduce(base.Layer):
             w, combiner = wb.expand(ids.shape), "sum"
         if w is not None:
             w = w.float().contiguous().reshape(-1)
-        return EmbedBagFn.apply(self._fused(combiner), ids.contiguous().reshape(-1), batch, (hot,), None, w,
-                                out_dtype, True, self.embeddings)[0]
+        return self._lookup(combiner, ids.contiguous().reshape(-1), batch, (hot,), None, w, out_dtype)
 
     def _call_per_dimension_weights(self, ids, w, combiner, out_dtype):
         """Weights of the rank of the embedded inputs ([B, D] with 1-D ids, [B, L, D] with 2-D ids: one weight
@@ -167,8 +247,7 @@ class EmbedReduce(base.Layer):
         lookup, so this rare form gathers the rows with it (L = 1 bags) and applies embed_reduce.py:253-274 as
         device tensor ops on the gathered block."""
         n = ids.numel()
-        rows = EmbedBagFn.apply(self._fused("sum"), ids.contiguous().reshape(-1), n, (1,), None, None,
-                                torch.float32, True, self.embeddings)[0]
+        rows = self._lookup("sum", ids.contiguous().reshape(-1), n, (1,), None, None, torch.float32)
         x = rows.reshape(tuple(ids.shape) + (self.output_dim,))
         wf = w.float().expand(x.shape)
         if ids.dim() == 1:                       # no reduction; weights only survive for "sum"
@@ -222,7 +301,7 @@ class Embedding(EmbedReduce):
     def call(self, inputs, weights=None) -> torch.Tensor:
         if weights is not None:
             raise ValueError("Embedding takes no weights; use EmbedReduce")
-        ids = as_index_tensor(inputs, self.embeddings.device)
+        ids = as_index_tensor(inputs, self._table().device)
         flat = super().call(ids.reshape(-1))
         return flat.reshape(*ids.shape, self.output_dim)
 

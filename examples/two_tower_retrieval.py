@@ -18,6 +18,11 @@ runs train one objective (the fused one keeps its scores in fp32 and sends ties 
 
 `evaluate` scores every query against the whole item table with FactorizedTopK: one sweep gives the positive's rank,
 hence every top-k accuracy and the mean reciprocal rank, again without storing the scores.
+
+    python examples/two_tower_retrieval.py --quantize # then: serve the same queries from an int8 index (K17)
+
+`serve_quantized` builds the exact index and its `quantize("int8")` form from the same item embeddings, serves the same
+queries through both and reports how many of the exact top-k the int8 index returns, and the bytes of both.
 """
 
 from __future__ import annotations
@@ -67,8 +72,23 @@ def evaluate(query_emb: torch.Tensor, item_emb: torch.Tensor, positive_item: tor
     return {name: float(value) for name, value in metric.result().items()}
 
 
+def serve_quantized(query_emb: torch.Tensor, item_emb: torch.Tensor, item_ids: torch.Tensor, k: int = 5) -> dict:
+    """The same queries served from the exact index and from its int8 form: {"overlap": the mean share of the exact
+    top-k ids that the int8 index also returns (its recall against the exact one), "index_bytes": of the float index,
+    "quantized_index_bytes": int8 rows plus fp32 steps, "ids": the int8 index's ids}."""
+    exact = kl.BruteForceRetrieval(item_emb.detach(), item_ids, k=k, return_scores=False, device=item_emb.device)
+    quantized = kl.BruteForceRetrieval(item_emb.detach(), item_ids, k=k, return_scores=False, device=item_emb.device)
+    index_bytes = exact.candidate_embeddings.numel() * exact.candidate_embeddings.element_size()
+    quantized.quantize("int8")
+    q_bytes = quantized.candidate_embeddings_q.numel() + 4 * quantized.candidate_embeddings_step.numel()
+    want, got = exact(query_emb.detach()), quantized(query_emb.detach())
+    hits = (want[:, :, None] == got[:, None, :]).any(dim=2).float().sum(dim=1)       # ids are unique per item
+    return {"overlap": float((hits / k).mean()), "index_bytes": index_bytes, "quantized_index_bytes": q_bytes,
+            "ids": got}
+
+
 def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000, dim: int = 32,
-         fused: bool = False, evaluate_after: bool = False) -> None:
+         fused: bool = False, evaluate_after: bool = False, quantize: bool = False):
     dev = torch.device("cuda", torch.cuda.current_device())
     query_tower = kl.Embedding(users, dim, device=dev)
     cand_tower = kl.Embedding(items, dim, device=dev)
@@ -96,7 +116,14 @@ def main(steps: int = 5, batch: int = 256, users: int = 1000, items: int = 2000,
     if evaluate_after:
         for name, value in evaluate(query_tower(user_ids), cand_tower(all_items), item_ids).items():
             print(f"{name}: {value:.4f}")
+    if quantize:
+        served = serve_quantized(query_tower(user_ids), cand_tower(all_items), all_items, k=5)
+        print(f"int8 index: mean overlap with the exact top-5 {served['overlap']:.4f}; index bytes "
+              f"{served['index_bytes']} -> {served['quantized_index_bytes']}")
+        print("top-5 items of the first queries from the int8 index:", served["ids"][:4].tolist())
+        return served
+    return None
 
 
 if __name__ == "__main__":
-    main(fused="--fused" in sys.argv[1:], evaluate_after="--eval" in sys.argv[1:])
+    main(fused="--fused" in sys.argv[1:], evaluate_after="--eval" in sys.argv[1:], quantize="--quantize" in sys.argv[1:])

@@ -64,7 +64,7 @@ typedef enum krs_activation {
 #define KRS_FLAG_ID_OUT_OF_RANGE 1
 #define KRS_FLAG_BAD_OFFSETS 2
 #define KRS_FLAG_CAPACITY_OVERFLOW 4   /* krs_shard_route_static: lookups beyond the static capacity were dropped */
-#define KRS_FLAG_NONFINITE_ROW 8       /* krs_quantize_rows_q8: a row held a NaN or an infinity (stored as q = 0, step = 0) */
+#define KRS_FLAG_NONFINITE_ROW 8       /* krs_quantize_rows_q8, krs_retrieval_topk_q8 (a query row): a row held a NaN or an infinity (stored as q = 0, step = 0) */
 
 /* One embedding table ([vocab, dim] row-major).  Lives in DEVICE memory as an
  * array indexed by krs_feature.table.  Replaces the `embeddings` variable of
@@ -1072,6 +1072,42 @@ size_t krs_retrieval_rank_workspace_bytes(int64_t b, int64_t n, int64_t d, int d
 int krs_retrieval_rank(const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b, int64_t n,
                        int64_t d, const int32_t* pos, const void* cand_ids, int id_dtype, int32_t* out_rank,
                        float* out_pos_score, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * K17  BruteForceRetrieval over an int8 candidate index: K8's fused score + top-k on v_mfma_i32_32x32x32_i8
+ *
+ * The serving form of a two-tower model: the candidate index is stored as K16 stores a table, and the queries are
+ * quantized on the way in (Keras' dynamic activation quantization).  The arithmetic, all of it pinned:
+ *   Candidates  cq [n, d] int8 with row stride ldc (elements) and cstep [n] fp32: what krs_quantize_rows_q8 writes.
+ *               Every int8 value counts, -128 included (the quantizer never emits it; a caller may).
+ *   Queries     q [b, d] fp32 / bf16 (q_dtype) with row stride ldq.  Each row is quantized into the workspace by the
+ *               rule of krs_quantize_rows_q8, bit for bit: qq [b, d] int8 and qstep [b] fp32.
+ *   Non-finite  A query row holding a NaN or an infinity gets qq = 0, qstep = 0 and raises KRS_FLAG_NONFINITE_ROW in
+ *               err_flag (which may be NULL): every score of that row is +0.0 and it returns candidates 0 .. k-1.
+ *               Other rows are unaffected.
+ *   Score       s_ij = fmul_rn(fmul_rn((float) idot_ij, cstep_j), qstep_i),  idot_ij = sum_e qq[i,e] * cq[j,e] in int32:
+ *               two separately rounded fp32 multiplies in that order, nothing contracted.  |idot| <= 512 * 128 * 127
+ *               < 2^24, so the conversion is exact; steps are 0 or >= 7.8e-10, so no score is subnormal.
+ *   Order       K8's total order on s: fp32 descending, index ascending, -0.0 as +0.0.  Rows come back sorted.
+ *               out_scores [b, k] is s rounded once to out_dtype (KRS_F32 / KRS_BF16), or NULL; out_ids [b, k] int32 is
+ *               ids[index], or the index when ids is NULL.
+ *   Shapes      1 <= k <= min(n, 128), 1 <= d <= 512, n <= INT32_MAX, b >= 0, ldq >= d, ldc >= d.  k > 128 (with
+ *               k <= n) and d > 512 are KRS_ERR_UNSUPPORTED with a message naming the limit: there is no slab path.
+ *               Other bad shapes, a bad dtype and a null q, cq, cstep or out_ids (b > 0) are KRS_ERR_INVALID, the shape
+ *               checks first; too little workspace is KRS_ERR_WORKSPACE; b == 0 is a successful no-op.
+ *   Execution   Three stages on `stream`: the query quantizer, K8's stage 1 (a 32-query tile against a candidate slice,
+ *               one MFMA per 32 bytes of K, the scaling in the epilogue, then K8's threshold test and row queues) and
+ *               K8's slice merge.  16-byte candidate loads when d % 16 == 0, ldc % 16 == 0 and cq is 16-byte aligned,
+ *               byte loads otherwise.  Integer dot products are exact, so ids, order and score bits are a function of
+ *               the inputs alone: bit-identical from call to call.  No allocation, no host wait; graph-capturable.
+ * krs_retrieval_topk_q8_workspace_bytes: K8's slice lists plus the quantized queries (b rows of d rounded up to 32
+ * bytes, and 4 b bytes), each rounded up to 256; > 0 for b > 0 on a supported shape, 0 otherwise.  It need not be
+ * initialised.
+ * ------------------------------------------------------------------------- */
+size_t krs_retrieval_topk_q8_workspace_bytes(int64_t b, int64_t n, int64_t d, int k);
+int krs_retrieval_topk_q8(const void* q, int64_t ldq, int q_dtype, const int8_t* cq, int64_t ldc, const float* cstep,
+                          const int32_t* ids, int64_t b, int64_t n, int64_t d, int k, void* out_scores, int out_dtype,
+                          int32_t* out_ids, int* err_flag, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

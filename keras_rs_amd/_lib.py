@@ -155,6 +155,8 @@ PROTOTYPES = {
                                 _P]),
     "krs_retrieval_rank_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
     "krs_retrieval_rank": (_I, [_P, _I64, _P, _I64, _I, _I64, _I64, _I64, _P, _P, _I, _P, _P, _P, _SZ, _P]),
+    "krs_retrieval_topk_q8_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
+    "krs_retrieval_topk_q8": (_I, [_P, _I64, _I, _P, _I64, _P, _P, _I64, _I64, _I64, _I, _P, _I, _P, _P, _P, _SZ, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

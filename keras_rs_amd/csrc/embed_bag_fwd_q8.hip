@@ -14,6 +14,7 @@
 
 #include "embed_fwd_q8_plan.h"
 #include "krs_common.h"
+#include "krs_q8.h"
 
 namespace krs {
 namespace {
@@ -299,19 +300,7 @@ __global__ __launch_bounds__(256) void embed_bag_fwd_q8_generic(const Q8FwdParam
   if (oob && p.err_flag && sub == 0) atomicOr(p.err_flag, KRS_FLAG_ID_OUT_OF_RANGE);
 }
 
-// ---- the quantizer -------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
-// the arithmetic of include/krs.h (K16): correctly rounded divisions, round half to even, clip to +-127
-__device__ __forceinline__ void row_scales(float a, float& inv, float& step) {
-  const float d = a + 1e-7f;
-  inv = __fdiv_rn(127.0f, d);
-  step = __fdiv_rn(d, 127.0f);
-}
-__device__ __forceinline__ int quantize1(float x, float inv) {
-  return (int)fminf(fmaxf(rintf(__fmul_rn(x, inv)), -127.0f), 127.0f);
-}
+// ---- the quantizer (its arithmetic: nonfinite, row_scales, quantize1 of krs_q8.h) ------------------------------------------
 
 // Rows of up to 16 * lanes elements, held in registers: a group of `lanes` lanes (a power of two, 1 .. 64) per row, 16
 // elements per lane.  VEC: the lane's elements are [16 sub, 16 sub + 16), moved by 16-byte loads and one 16-byte store

@@ -21,18 +21,25 @@
 //                             queue in LDS, and writes the slice's k best pairs per row; the same selection code as
 //                             krs_topk_rows then merges the S slices of each row.  Other (k, D): krs_gemm into a
 //                             query-chunked fp32 slab, then the krs_topk_rows selection.
+//   * krs_retrieval_topk_q8   the fused path over an int8 candidate index (int8 rows + one fp32 step per row, K16's stored
+//                             form): the query rows are quantized into the workspace by K16's rule, stage 1 runs on
+//                             v_mfma_i32_32x32x32_i8 and scales each exact int32 dot product by the two steps before the
+//                             threshold test, stage 2 is the same merge.  No slab path.
 //   * krs_retrieval_mine      the same two stages for the hard negatives of the in-batch softmax loss: stage 1 ranks
 //                             K13's corrected score (bias, accidental hits) and leaves each row's positive out of the
 //                             queue, storing its score instead.
 #include <algorithm>
 
 #include "krs_list.h"
+#include "krs_q8.h"
 
 namespace krs {
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSortMax = 2048;    // longest list sorted in LDS (16 KB of pairs)
@@ -257,6 +264,11 @@ struct Mine {
   float hit;
   float* pos_score;     // [b]
 };
+// what the int8 variant of stage 1 adds (krs_retrieval_topk_q8): the dequantization steps of both operands
+struct Q8Scale {
+  const float* cstep;   // [n]
+  const float* qstep;   // [b]
+};
 
 // one wave sorts a row queue of m <= 256 pairs (4 per lane, descending), keeps the first k and returns the new
 // threshold key (0 while fewer than k pairs were seen); `q` is rewritten with the kept pairs
@@ -320,8 +332,12 @@ __device__ uint32_t wave_compact(uint64_t* q, int m, int k, int lane) {
 // candidate carries the id of the row's positive and is not the positive -- and the pair (row, its positive) is not
 // queued: its score goes to pos_score[row].  A row whose positive is outside [0, n) has no positive, so no accidental
 // hits either; slice 0 writes NaN to its pos_score.
+// ES == 1 (krs_retrieval_topk_q8): q and c are int8 rows, the query rows already quantized into the workspace with a
+// row stride of row_bytes and a zeroed K tail; a 32-byte K step is one v_mfma_i32_32x32x32_i8 (both operands take their
+// 16 bytes from the same chunk, so how the instruction deals k to lanes does not matter), and the exact int32 dot
+// product becomes the fp32 score fmul(fmul((float)idot, cstep[cand]), qstep[row]) before it is ranked.
 template <int ES, bool VEC, bool MINE>
-__device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
+__device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, const Q8Scale& q8 = Q8Scale{}) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lstride = p.row_bytes + 16;
   char* qt = smem;                                                           // [kQM][lstride]
@@ -330,6 +346,7 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
   uint32_t* thr = reinterpret_cast<uint32_t*>(cnt + kQM);                    // [kQM]
   int64_t* pid = reinterpret_cast<int64_t*>(thr + kQM);                      // [kQM]  MINE: id of the row's positive
   int* posr = reinterpret_cast<int*>(pid + kQM);                             // [kQM]  MINE: the row's positive, or -1
+  float* qstep = reinterpret_cast<float*>(thr + kQM);                        // [kQM]  ES == 1 (never with MINE)
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int frow = lane & 31, fhalf = lane >> 5;
@@ -341,11 +358,15 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
   const int64_t s0 = std::min<int64_t>(slice * p.slice, p.n), s1 = std::min<int64_t>(s0 + p.slice, p.n);
 
   // query tile -> LDS, zero beyond b rows and d columns
-  const int row_elems = p.row_bytes / ES;
+  const int row_elems = p.row_bytes / (ES == 1 ? 4 : ES);
   for (int i = threadIdx.x; i < kQM * row_elems; i += blockDim.x) {
     const int r = i / row_elems, e = i % row_elems;
     const bool ok = q0 + r < p.b && e < p.d;
-    if constexpr (ES == 2) {
+    if constexpr (ES == 1) {
+      // e counts 4-byte words: a workspace row is row_bytes long on a 256-byte boundary and zero beyond d
+      const uint32_t v = q0 + r < p.b ? *reinterpret_cast<const uint32_t*>(p.q + (q0 + r) * p.ldq + e * 4) : 0u;
+      *reinterpret_cast<uint32_t*>(qt + r * lstride + e * 4) = v;
+    } else if constexpr (ES == 2) {
       const uint16_t v = ok ? reinterpret_cast<const uint16_t*>(p.q)[(q0 + r) * p.ldq + e] : 0;
       *reinterpret_cast<uint16_t*>(qt + r * lstride + e * 2) = v;
     } else {
@@ -356,6 +377,7 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
   if (threadIdx.x < kQM) {
     cnt[threadIdx.x] = 0;
     thr[threadIdx.x] = 0;
+    if constexpr (ES == 1) qstep[threadIdx.x] = q0 + threadIdx.x < p.b ? q8.qstep[q0 + threadIdx.x] : 0.0f;
     if constexpr (MINE) {
       const int64_t qr = q0 + threadIdx.x;
       int64_t pr = -1;
@@ -385,6 +407,11 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) pos_reg[r] = posr[(r & 3) + 8 * (r >> 2) + 4 * fhalf];
   }
+  float qs_reg[16];
+  if constexpr (ES == 1) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) qs_reg[r] = qstep[(r & 3) + 8 * (r >> 2) + 4 * fhalf];
+  }
 
   for (int64_t blk = s0; blk < s1; blk += kCB) {
     const int64_t cand = blk + wave * 32 + frow;  // this lane's candidate row (B fragment)
@@ -393,6 +420,13 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    i32x16 iacc;
+    float cstep = 0.0f;
+    if constexpr (ES == 1) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) iacc[r] = 0;
+      if (cvalid) cstep = q8.cstep[cand];     // consecutive lanes, consecutive candidates: one coalesced load
+    }
     for (int ks0 = 0; ks0 < nks; ks0 += 8) {
       u32x4 fb[8];
 #pragma unroll
@@ -404,7 +438,12 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
           if constexpr (VEC) {
             if (e0 < p.d) v = *reinterpret_cast<const u32x4*>(crow + ch * 16);
           } else {
-            if constexpr (ES == 2) {
+            if constexpr (ES == 1) {
+              const uint8_t* cr = reinterpret_cast<const uint8_t*>(crow);
+#pragma unroll
+              for (int x = 0; x < 16; ++x)
+                v[x >> 2] |= (e0 + x < p.d ? (uint32_t)cr[e0 + x] : 0u) << (8 * (x & 3));
+            } else if constexpr (ES == 2) {
               const uint16_t* cr = reinterpret_cast<const uint16_t*>(crow);
               uint32_t h[8];
 #pragma unroll
@@ -423,7 +462,10 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
       for (int u = 0; u < 8; ++u) {
         if (ks0 + u >= nks) break;
         const u32x4 fa = *reinterpret_cast<const u32x4*>(qt + frow * lstride + ((ks0 + u) * 2 + fhalf) * 16);
-        if constexpr (ES == 2) {
+        if constexpr (ES == 1) {
+          iacc = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, fa), __builtin_bit_cast(i32x4, fb[u]),
+                                                       iacc, 0, 0, 0);
+        } else if constexpr (ES == 2) {
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fb[u]),
                                                         acc, 0, 0, 0);
         } else {
@@ -432,6 +474,11 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(fa[x]), __uint_as_float(fb[u][x]), acc, 0, 0, 0);
         }
       }
+    }
+    if constexpr (ES == 1) {
+      // |idot| <= 512 * 128 * 128 = 2^23: the conversion is exact; two separately rounded multiplies, nothing contracted
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = __fmul_rn(__fmul_rn((float)iacc[r], cstep), qs_reg[r]);
     }
     // acc[r] = score of query row (r & 3) + 8 (r >> 2) + 4 fhalf against candidate `cand`
     if constexpr (MINE) {
@@ -506,6 +553,45 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn) {
 template <int ES, bool VEC>
 __global__ __launch_bounds__(256) void retr_stage1_kernel(const Stage1 p) {
   stage1_body<ES, VEC, false>(p, Mine{});
+}
+// The query rows of krs_retrieval_topk_q8 -> int8 by the rule of krs_quantize_rows_q8 (krs_q8.h), bit for bit: a wave per
+// row, the row (d <= 512: 8 elements per lane) kept in registers between the abs-max and the rounding.  qq rows are
+// row_bytes long, zero beyond d.
+__global__ __launch_bounds__(256) void quantize_queries_q8_kernel(const void* q, int64_t ldq, int dtype, int64_t b, int d,
+                                                                  int row_bytes, int8_t* qq, float* qstep, int* err_flag) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= b) return;      // wave-uniform
+  float x[kFusedMaxD / 64];
+  float a = 0.0f;
+  int bad = 0;
+#pragma unroll
+  for (int i = 0; i < kFusedMaxD / 64; ++i) {
+    const int c = lane + 64 * i;
+    x[i] = c < d ? ld_elem(q, dtype, row * ldq + c) : 0.0f;
+    a = fmaxf(a, fabsf(x[i]));
+    bad |= nonfinite(x[i]);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    a = fmaxf(a, __shfl_xor(a, off, 64));
+    bad |= __shfl_xor(bad, off, 64);
+  }
+  float inv, st;
+  row_scales(a, inv, st);
+#pragma unroll
+  for (int i = 0; i < kFusedMaxD / 64; ++i) {
+    const int c = lane + 64 * i;
+    if (c < row_bytes) qq[row * row_bytes + c] = c < d && !bad ? (int8_t)quantize1(x[i], inv) : (int8_t)0;
+  }
+  if (lane == 0) {
+    qstep[row] = bad ? 0.0f : st;
+    if (bad && err_flag) atomicOr(err_flag, KRS_FLAG_NONFINITE_ROW);
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void retr_stage1_q8_kernel(const Stage1 p, const Q8Scale q8) {
+  stage1_body<1, VEC, false>(p, Mine{}, q8);
 }
 template <int ES, bool VEC>
 __global__ __launch_bounds__(256) void retr_mine_stage1_kernel(const Stage1 p, const Mine mn) {
@@ -654,6 +740,95 @@ extern "C" int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int
     if (rc2 != KRS_OK) return rc2;
   }
   return KRS_OK;
+}
+
+// ---- the int8 candidate index (K17) ------------------------------------------------------------------------------------
+namespace krs {
+namespace {
+// workspace of a krs_retrieval_topk_q8 call: the slice lists and the merge list of the fused path, then the quantized
+// query rows (row_bytes each) and their steps
+struct Q8Workspace {
+  int row_bytes;
+  size_t lists, qq, qstep, total;
+};
+inline Q8Workspace q8_workspace(int64_t b, int64_t n, int64_t d, int k) {
+  Q8Workspace w;
+  w.row_bytes = (int)(ceil_div(d, 32) * 32);
+  w.lists = fused_bytes(b, n, k);
+  w.qq = w.lists;
+  w.qstep = w.qq + align256((size_t)b * w.row_bytes);
+  w.total = w.qstep + align256((size_t)b * sizeof(float));
+  return w;
+}
+}  // namespace
+}  // namespace krs
+
+extern "C" size_t krs_retrieval_topk_q8_workspace_bytes(int64_t b, int64_t n, int64_t d, int k) {
+  using namespace krs;
+  if (b <= 0 || n <= 0 || d <= 0 || k < 1 || !fused_path(d, k)) return 0;
+  return q8_workspace(b, n, d, k).total;
+}
+
+extern "C" int krs_retrieval_topk_q8(const void* q, int64_t ldq, int q_dtype, const int8_t* cq, int64_t ldc,
+                                     const float* cstep, const int32_t* ids, int64_t b, int64_t n, int64_t d, int k,
+                                     void* out_scores, int out_dtype, int32_t* out_ids, int* err_flag, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  using namespace krs;
+  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1, "krs_retrieval_topk_q8: bad shape b=%lld n=%lld d=%lld", (long long)b,
+              (long long)n, (long long)d);
+  KRS_REQUIRE(n <= INT32_MAX, "krs_retrieval_topk_q8: more than 2^31 - 1 candidates");
+  KRS_REQUIRE(k >= 1 && k <= n, "krs_retrieval_topk_q8: k = %d outside [1, %lld]", k, (long long)n);
+  KRS_REQUIRE(ldq >= d && ldc >= d, "krs_retrieval_topk_q8: row stride below d");
+  KRS_REQUIRE(q_dtype == KRS_F32 || q_dtype == KRS_BF16, "krs_retrieval_topk_q8: bad query dtype");
+  KRS_REQUIRE(out_dtype == KRS_F32 || out_dtype == KRS_BF16, "krs_retrieval_topk_q8: bad output dtype");
+  if (k > kFusedMaxK)
+    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_topk_q8: k = %d above the limit of %d (there is no slab path)", k,
+                kFusedMaxK);
+  if (d > kFusedMaxD)
+    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_topk_q8: d = %lld above the limit of %d (there is no slab path)",
+                (long long)d, kFusedMaxD);
+  if (b == 0) return KRS_OK;
+  KRS_REQUIRE(q && cq && cstep && out_ids, "krs_retrieval_topk_q8: null operand");
+  const Q8Workspace w = q8_workspace(b, n, d, k);
+  if (!workspace || workspace_bytes < w.total)
+    return fail(KRS_ERR_WORKSPACE, "krs_retrieval_topk_q8: needs %zu workspace bytes, got %zu", w.total, workspace_bytes);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* ws = reinterpret_cast<char*>(workspace);
+  int8_t* qq = reinterpret_cast<int8_t*>(ws + w.qq);
+  float* qstep = reinterpret_cast<float*>(ws + w.qstep);
+
+  hipLaunchKernelGGL(quantize_queries_q8_kernel, dim3((unsigned)ceil_div(b, 4)), dim3(256), 0, st, q, ldq, q_dtype, b,
+                     (int)d, w.row_bytes, qq, qstep, err_flag);
+  KRS_CHECK_LAUNCH("quantize_queries_q8_kernel");
+
+  const Plan pl = fused_plan(b, n);
+  Stage1 p;
+  p.q = reinterpret_cast<const char*>(qq); p.ldq = w.row_bytes;
+  p.c = reinterpret_cast<const char*>(cq); p.ldc = ldc;
+  p.b = b; p.n = n; p.d = d; p.k = k; p.cap = kQueue;
+  p.slice = pl.slice; p.S = pl.S; p.qtiles = pl.qtiles;
+  p.row_bytes = w.row_bytes;
+  p.out = reinterpret_cast<uint64_t*>(ws);
+  const Q8Scale q8{cstep, qstep};
+  // the query tile, the row queues, cnt and thr as in krs_retrieval_topk, then the query steps
+  const size_t lds = (size_t)kQM * (p.row_bytes + 16) + (size_t)kQM * p.cap * sizeof(uint64_t) + 2 * kQM * sizeof(int) +
+                     kQM * sizeof(float);
+  const bool vec = d % 16 == 0 && ldc % 16 == 0 && (reinterpret_cast<uintptr_t>(cq) & 15) == 0;
+  const dim3 grid((unsigned)((int64_t)pl.S * pl.qtiles));
+#define KRS_STAGE1_Q8(VEC_)                                                                                        \
+  {                                                                                                                \
+    auto kern = retr_stage1_q8_kernel<VEC_>;                                                                       \
+    KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                (int)lds));                                                                        \
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, q8);                                                     \
+  }
+  if (vec) KRS_STAGE1_Q8(true) else KRS_STAGE1_Q8(false)
+#undef KRS_STAGE1_Q8
+  KRS_CHECK_LAUNCH("retr_stage1_q8_kernel");
+  const int64_t len = (int64_t)pl.S * k;
+  uint64_t* list = reinterpret_cast<uint64_t*>(ws + align256((size_t)b * len * sizeof(uint64_t)));
+  const Out out{out_ids, out_scores, out_dtype, ids, k, 0, n};
+  return select_rows(PairSrc{p.out, len}, b, len, k, out, list, st);
 }
 
 // ---- hard-negative mining of the in-batch softmax loss (K14) ---------------------------------------------------------

@@ -6,7 +6,8 @@ logit corrections of the training head, keras_rs.layers.SamplingProbabilityCorre
 (krs_sampling_correction, krs_remove_accidental_hits); and InBatchSoftmaxLoss, the whole in-batch softmax head computed
 from the two embedding matrices without storing the scores (K13: krs_retrieval_xent_fwd / krs_retrieval_xent_bwd), and
 FactorizedTopK, the evaluation metric that goes with it: every top-k accuracy and the mean reciprocal rank from the
-positive's rank among all candidates, again without the scores (K15: krs_retrieval_rank).
+positive's rank among all candidates, again without the scores (K15: krs_retrieval_rank).  BruteForceRetrieval also has a
+serving form, `quantize("int8")`: an int8 candidate index scored on the int8 matrix cores (K17: krs_retrieval_topk_q8).
 
 Selection order: score descending, then candidate index ascending (-0.0 as +0.0, NaN above +inf); rows come back
 sorted.  Known divergence: for bf16 inputs keras.ops.matmul rounds the scores to bf16 before top_k, so among
@@ -25,6 +26,7 @@ from keras_rs_amd import _lib as L
 from keras_rs_amd import losses as _reductions
 from keras_rs_amd import retrieval_ops
 from keras_rs_amd.layers import base
+from keras_rs_amd.layers.embed_reduce import keep_fp32_steps, quantize_rows_checked, restore_fp32_steps
 
 
 def _as_tensor(x, device=None) -> torch.Tensor:
@@ -77,6 +79,9 @@ class BruteForceRetrieval(Retrieval):
     Candidates and ids are non-trainable weights; `update_candidates` with the same shape copies in place, so a graph
     captured around `call` keeps reading the current candidates.  `call(query)` returns (top scores, top ids), or the
     ids alone when `return_scores=False`; ids are the candidate indices when the layer has no candidate ids.
+
+    `quantize("int8")` turns the index into its serving form (include/krs.h, K17): int8 rows and one fp32 step per row,
+    scored on the int8 matrix cores against queries quantized on the way in.
     """
 
     def __init__(self, candidate_embeddings=None, candidate_ids=None, k: int = 10, return_scores: bool = True,
@@ -85,6 +90,7 @@ class BruteForceRetrieval(Retrieval):
         self.register_parameter("candidate_embeddings", None)    # (weights once candidates arrive: add_weight)
         self.register_parameter("candidate_ids", None)
         self._converted: dict[torch.dtype, torch.Tensor] = {}   # candidates in another query dtype
+        self.quantization_mode = None      # "int8" after quantize(): candidate_embeddings_q / candidate_embeddings_step
         if candidate_embeddings is None:
             if candidate_ids is not None:
                 raise ValueError("You cannot provide `candidate_ids` without providing `candidate_embeddings`")
@@ -104,6 +110,8 @@ class BruteForceRetrieval(Retrieval):
                 if ids.dtype.is_floating_point or (ids.numel() and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31)):
                     raise ValueError("`candidate_ids` must be integers that fit int32")
                 ids = ids.to(torch.int32)
+        if self.quantization_mode:
+            return self._update_quantized(emb, ids)
         with torch.no_grad():
             if self.candidate_embeddings is not None:
                 # assign: the variable keeps its shape (and its storage, which a captured graph reads)
@@ -129,6 +137,75 @@ class BruteForceRetrieval(Retrieval):
                     self.candidate_ids.copy_(ids)
         self.built = True
 
+    # ---- the int8 index (keras' quantize("int8") on the one large serving-time state of a two-tower model) -------------
+    def quantize(self, mode: str = "int8") -> None:
+        """Replaces the float index by int8 rows and one fp32 step per row (krs_quantize_rows_q8) and frees it and every
+        converted copy: `weights` then holds candidate_ids only, state_dict() holds `candidate_embeddings_q` /
+        `candidate_embeddings_step`, and `call` runs krs_retrieval_topk_q8 on fp32 or bf16 queries.  k <= 128 and
+        D <= 512 only: the int8 index has no slab path.  A candidate row with a NaN or an infinity raises ValueError and
+        leaves the layer as it was."""
+        if mode != "int8":
+            raise ValueError(f"Invalid quantization mode {mode!r}: BruteForceRetrieval supports 'int8' only.")
+        if self.quantization_mode:
+            raise ValueError(f"{type(self).__name__} '{self.name}' is already quantized ({self.quantization_mode}).")
+        if self.candidate_embeddings is None:
+            raise ValueError(f"{type(self).__name__} '{self.name}' has no candidates: call `update_candidates` before "
+                             "quantize().")
+        if self.k > retrieval_ops.Q8_MAX_K:
+            raise ValueError(f"The int8 index retrieves at most k = {retrieval_ops.Q8_MAX_K} candidates per query, this "
+                             f"layer has k = {self.k}.")
+        if self.candidate_embeddings.shape[1] > retrieval_ops.Q8_MAX_D:
+            raise ValueError(f"The int8 index takes embeddings of at most D = {retrieval_ops.Q8_MAX_D} columns, the "
+                             f"candidates have D = {self.candidate_embeddings.shape[1]}.")
+        q, step = quantize_rows_checked(self.candidate_embeddings.detach(), f"{type(self).__name__} '{self.name}'")
+        self.register_buffer("candidate_embeddings_q", q, persistent=True)
+        self.register_buffer("candidate_embeddings_step", step, persistent=True)
+        self._weight_order[:] = [w for w in self._weight_order if w is not self.candidate_embeddings]
+        self.candidate_embeddings = None
+        self._converted.clear()
+        self.quantization_mode = mode
+
+    def _update_quantized(self, emb: torch.Tensor, ids) -> None:
+        """update_candidates on the int8 index: the new float rows are quantized into temporaries, checked with one host
+        read, and only then copied into the buffers a captured graph reads."""
+        if tuple(emb.shape) != tuple(self.candidate_embeddings_q.shape):
+            raise ValueError(f"Cannot assign candidate_embeddings of shape {tuple(emb.shape)} to a variable of shape "
+                             f"{tuple(self.candidate_embeddings_q.shape)}")
+        if self.candidate_ids is None and ids is not None:
+            raise ValueError("New `candidate_ids` cannot be provided as previous candidates did not have candidate IDs")
+        emb = emb.detach().to(self.candidate_embeddings_q.device)
+        q, step = quantize_rows_checked(emb, f"{type(self).__name__} '{self.name}'")
+        with torch.no_grad():
+            self.candidate_embeddings_q.copy_(q)
+            self.candidate_embeddings_step.copy_(step)
+            if ids is not None:
+                self.candidate_ids.copy_(ids)
+
+    def _apply(self, fn, recurse=True):
+        """.to() / .cuda() / .bfloat16(): the steps of the int8 index move with the module and stay fp32."""
+        keep = keep_fp32_steps(self)
+        out = super()._apply(fn, recurse)
+        restore_fp32_steps(self, keep)
+        return out
+
+    def _call_quantized(self, inputs):
+        q = _as_tensor(inputs)
+        d = self.candidate_embeddings_q.shape[1]
+        if q.dim() != 2 or q.shape[1] != d:
+            raise ValueError(f"The query must have shape (batch, {d}), received {tuple(q.shape)}")
+        L.require_device(q, "BruteForceRetrieval query")
+        L.require_device(self.candidate_embeddings_q, "BruteForceRetrieval candidates")
+        if q.dtype not in (torch.float32, torch.bfloat16):
+            raise L.KrsError(f"BruteForceRetrieval: unsupported query dtype {q.dtype} (float32 / bfloat16)")
+        ids = None if self.candidate_ids is None else self.candidate_ids.detach()
+        # (no error word: a call reads nothing back, so it stays capturable; a non-finite query row scores 0 everywhere)
+        scores, top_ids = retrieval_ops.retrieval_topk_q8(q.detach(), self.candidate_embeddings_q,
+                                                          self.candidate_embeddings_step, self.k, ids=ids,
+                                                          want_scores=self.return_scores)
+        if self.return_scores:
+            return scores, top_ids
+        return top_ids
+
     def _candidates_as(self, dtype: torch.dtype) -> torch.Tensor:
         cand = self.candidate_embeddings
         if cand.dtype == dtype:
@@ -140,6 +217,8 @@ class BruteForceRetrieval(Retrieval):
         return conv
 
     def call(self, inputs):
+        if self.quantization_mode:
+            return self._call_quantized(inputs)
         if self.candidate_embeddings is None:
             raise ValueError("No candidates: call `update_candidates` before using the layer.")
         q = _as_tensor(inputs)

@@ -1,5 +1,5 @@
-"""Host side of K8, K11, K13, K14 and K15: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and
-mining), over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored
+"""Host side of K8, K11, K13, K14, K15 and K17: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and
+mining), over krs_retrieval_topk_q8 (serving from an int8 index), over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored
 scores), over krs_retrieval_xent_fwd / krs_retrieval_xent_bwd (the in-batch softmax loss that never stores the scores),
 over krs_retrieval_mine (the same loss on each row's hardest negatives) and over krs_retrieval_rank (the positive's
 rank among all candidates, for evaluation), all of include/krs.h.
@@ -78,6 +78,53 @@ def retrieval_topk(query: torch.Tensor, candidates: torch.Tensor, k: int, *, ids
                                     k, L.ptr(scores), L.ptr(out_ids), L.ptr(ws), ws.numel(),
                                     L.stream_ptr())
     L.check(rc, "krs_retrieval_topk")
+    return scores, out_ids
+
+
+# ---- K17: the same over an int8 candidate index ------------------------------------------------------------------------
+Q8_MAX_K = 128             # most results per query of krs_retrieval_topk_q8 (there is no slab path)
+Q8_MAX_D = 512             # its widest embedding
+
+
+def retrieval_topk_q8_workspace_bytes(b: int, n: int, d: int, k: int) -> int:
+    return int(L.lib().krs_retrieval_topk_q8_workspace_bytes(b, n, d, k))
+
+
+def retrieval_topk_q8(query: torch.Tensor, cand_q: torch.Tensor, cand_step: torch.Tensor, k: int, *,
+                      ids: torch.Tensor | None = None, want_scores: bool = True,
+                      err_flag: torch.Tensor | None = None):
+    """Top-k of query [B, D] (fp32 / bf16) against the int8 index cand_q [N, D], cand_step [N] fp32 (the output of
+    embedding_ops.quantize_rows): the query rows are quantized on the way in and the scores are
+    (qq . cq) * cand_step * query_step (include/krs.h, K17).  Returns (scores [B, k] in the query's dtype or None, int32
+    ids [B, k]); ids = ids[index] when ids (int32 [N]) is given.  err_flag (int32 [1], optional) gets
+    FLAG_NONFINITE_ROW or-ed in when a query row holds a NaN or an infinity; such a row scores +0.0 everywhere."""
+    q = L.rowmajor(query, "retrieval_topk_q8 query")
+    c = L.rowmajor(cand_q, "retrieval_topk_q8 cand_q")
+    L.require_device(cand_step, "retrieval_topk_q8 cand_step")
+    if q.dtype not in (torch.float32, torch.bfloat16):
+        raise L.KrsError(f"retrieval_topk_q8: unsupported query dtype {q.dtype} (float32 / bfloat16)")
+    b, d = q.shape
+    n = c.shape[0]
+    if c.dtype != torch.int8 or c.shape[1] != d:
+        raise L.KrsError(f"retrieval_topk_q8: cand_q must be int8 [N, {d}], got {c.dtype} {tuple(c.shape)}")
+    if cand_step.dtype != torch.float32 or tuple(cand_step.shape) != (n,) or not cand_step.is_contiguous():
+        raise L.KrsError("retrieval_topk_q8: cand_step must be a contiguous float32 vector of one step per candidate")
+    if ids is not None:
+        L.require_device(ids, "retrieval_topk_q8 ids")
+        if ids.dtype != torch.int32 or ids.dim() != 1 or ids.shape[0] != n or not ids.is_contiguous():
+            raise L.KrsError("retrieval_topk_q8: ids must be a contiguous int32 vector of one id per candidate")
+    if err_flag is not None:
+        L.require_device(err_flag, "retrieval_topk_q8 err_flag")
+        if err_flag.dtype != torch.int32 or err_flag.numel() < 1:
+            raise L.KrsError("retrieval_topk_q8: err_flag must be an int32 tensor of at least one element")
+    scores = torch.empty((b, k), dtype=q.dtype, device=q.device) if want_scores else None
+    out_ids = torch.empty((b, k), dtype=torch.int32, device=q.device)
+    ws = torch.empty(max(1, retrieval_topk_q8_workspace_bytes(b, n, d, k)), dtype=torch.uint8, device=q.device)
+    rc = L.lib().krs_retrieval_topk_q8(L.ptr(q), q.stride(0) if b > 1 else d, L.fdtype(q), L.ptr(c),
+                                       c.stride(0) if n > 1 else d, L.ptr(cand_step), L.ptr(ids), b, n, d, k,
+                                       L.ptr(scores), L.fdtype(q), L.ptr(out_ids), L.ptr(err_flag), L.ptr(ws),
+                                       ws.numel(), L.stream_ptr())
+    L.check(rc, "krs_retrieval_topk_q8")
     return scores, out_ids
 
 

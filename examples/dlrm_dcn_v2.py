@@ -4,7 +4,8 @@
 (sigmoid) -> binary cross-entropy, BinaryAccuracy and AUC (examples/ml_perf/main.py:201-210).
 
     python examples/dlrm_dcn_v2.py            # a few training steps on synthetic data (needs an MI355X)
-    python examples/dlrm_dcn_v2.py --quantize # ... then serve: int8 embedding tables, one batch predicted both ways
+    python examples/dlrm_dcn_v2.py --quantize # ... then serve: int8 embedding tables, then int8 Dense / FeatureCross as well;
+                                              # one batch predicted each way against the float model
 
 The only edits against the reference model code: `layers.concat_features` instead of
 `ops.concatenate` (the embeddings land directly in the interaction input, no copy) with
@@ -138,10 +139,13 @@ def train_step(model, opt_box, inputs, labels, metrics=None):
     return loss.detach()
 
 
-def quantize_and_compare(model, inputs):
+def quantize_and_compare(model, inputs, dense=False):
     """Serving: predicts one batch with the float tables, quantizes the embedding layer to int8 rows
     (DistributedEmbedding.quantize("int8")) and predicts it again.  Returns (largest absolute difference of the
-    predictions, table bytes before, table bytes after)."""
+    predictions, table bytes before, table bytes after).  With dense=True every Dense and FeatureCross of the model is
+    quantized as well afterwards (their products then run on the int8 matrix cores, include/krs.h K18) and the batch is
+    predicted a third time: the tuple gains a fourth entry, the largest absolute difference of THOSE predictions against
+    the float model."""
     layer = model.embedding_layer
     with torch.no_grad():
         before = model(inputs).float()
@@ -150,7 +154,15 @@ def quantize_and_compare(model, inputs):
         after = model(inputs).float()
     layer.check_ids(wait=True)
     q_bytes = sum(q.numel() + step.numel() * 4 for q, step in layer.get_quantized_tables().values())
-    return float((before - after).abs().max()), table_bytes, q_bytes
+    result = (float((before - after).abs().max()), table_bytes, q_bytes)
+    if dense:
+        for m in model.modules():
+            if isinstance(m, (kl.Dense, kl.FeatureCross)):
+                m.quantize("int8")
+        with torch.no_grad():
+            served = model(inputs).float()
+        result += (float((before - served).abs().max()),)
+    return result
 
 
 if __name__ == "__main__":
@@ -158,7 +170,8 @@ if __name__ == "__main__":
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--quantize", action="store_true",
-                    help="after the training steps, quantize the embedding tables to int8 and predict one batch both ways")
+                    help="after the training steps, quantize the embedding tables to int8, then every Dense and FeatureCross, "
+                         "and predict one batch each way")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     hots = [3, 2, 1, 2, 6, 1, 1, 1, 1, 7, 3, 8, 1, 6, 9, 5, 1, 1, 1, 12, 100, 27, 10, 3, 1, 1]
@@ -171,6 +184,7 @@ if __name__ == "__main__":
     print(", ".join(f"{name} {float(value):.4f}" for name, value in metrics.result().items()))
     if args.quantize:
         x, _ = synthetic_batch(8192, 13, 100_000, hots, dev, seed=99)
-        diff, nbytes, qbytes = quantize_and_compare(model, x)
+        diff, nbytes, qbytes, diff_all = quantize_and_compare(model, x, dense=True)
         print(f"int8 tables: largest |prediction difference| {diff:.3e}; table bytes {nbytes} -> {qbytes} "
               f"({qbytes / nbytes:.3f}x)")
+        print(f"int8 tables + int8 Dense / FeatureCross: largest |prediction difference| {diff_all:.3e}")

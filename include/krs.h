@@ -1109,6 +1109,62 @@ int krs_retrieval_topk_q8(const void* q, int64_t ldq, int q_dtype, const int8_t*
                           const int32_t* ids, int64_t b, int64_t n, int64_t d, int k, void* out_scores, int out_dtype,
                           int32_t* out_ids, int* err_flag, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * K18  Dense and FeatureCross in int8: C = epilogue(scale(Aq . Wq^T)) on v_mfma_i32_32x32x32_i8
+ *
+ * The serving form of keras.layers.Dense.quantize("int8"): int8 weights with one step per output channel, activations
+ * quantized per row on the way in, an exact int32 product, two fp32 scalings, then krs_gemm's epilogue.  All pinned:
+ *   Weights      A Keras kernel W [K, N] is stored TRANSPOSED: wq [N, K] int8, K-contiguous with row stride ldw
+ *                (elements), plus wstep [N] fp32 -- exactly what krs_quantize_rows_q8 writes for the rows of W^T (Keras'
+ *                abs_max_quantize(kernel, axis=0), with the stored dequantization step).
+ *   Activations  aq [M, K] int8 with row stride lda and astep [M] fp32: what krs_quantize_rows_q8 writes for the rows of
+ *                A [M, K] fp32 / bf16 (Keras' dynamic per-row input quantization, as K17 does for queries).  Operands are
+ *                pre-quantized at this level; the Python op runs the quantizer in front.
+ *   Product      idot_ij = sum_e aq[i,e] * wq[j,e] in int32: exact, every int8 value counts, -128 included.
+ *                k <= 131072, so the sum cannot overflow; a larger k is KRS_ERR_UNSUPPORTED.
+ *                z_ij = fmul_rn(fmul_rn((float) idot_ij, wstep_j), astep_i): the conversion rounds to nearest even
+ *                (|idot| may exceed 2^24 here, unlike K17), then two separately rounded multiplies in that order, nothing
+ *                contracted.  idot is exact, so z is a function of the inputs alone -- not of tile shape or route.
+ *   Epilogue     krs_gemm's on v = z, the same krs_gemm_epilogue and operand rules (x0, x, u_out, r in the dtype of C):
+ *                + bias, act, x0 * (v + diag_scale * x) + x, + beta * R, one rounding to out_dtype (KRS_F32 / KRS_BF16).
+ *   Non-finite   The quantizer gives a row with a NaN or an infinity q = 0, step = 0 (KRS_FLAG_NONFINITE_ROW); a finite
+ *                row has step >= 1e-7 / 127.  Where astep_i == 0 every element of row i of C (and of u_out) is the
+ *                canonical quiet NaN (0x7fc00000, rounded to out_dtype), whatever the epilogue: a poisoned input stays
+ *                visible without a host read.  Other rows are unaffected.
+ *   Shapes       m, n, k >= 0; m == 0 or n == 0 is a successful no-op; k == 0 gives z = 0.  Null aq, astep, wq, wstep, c,
+ *                a negative size, a bad out_dtype, x0 without x: KRS_ERR_INVALID, the shape checks first.  k > 131072,
+ *                m or n > 2^31 - 1, a grid beyond the launch limits: KRS_ERR_UNSUPPORTED with a message naming the limit.
+ *   Execution    One launch, no workspace, no split-K, no allocation, no host wait: graph-capturable.  Kernels
+ *                (csrc/gemm_q8_plan.h decides, a pure host function): KRS_GEMM_Q8_KERNEL_RING -- 256 x 256 tiles, 128-k
+ *                pieces by LDS-DMA on gemm_pp64_kernel's five-slot ping-pong ring -- where aq and wq are on 16 bytes, lda
+ *                and ldw are multiples of 16, k is whole 128-k pieces and at least three, m, n >= 256 and the 256-tiles
+ *                number at least 192; KRS_GEMM_Q8_KERNEL_TILE128 -- 128 x 128 tiles, a K tail zero-filled in LDS -- for
+ *                every other shape with k % 16 == 0 and operands aligned like that (m = 1 and n = 1 included);
+ *                KRS_GEMM_Q8_KERNEL_GENERIC -- byte loads, one output per thread -- for the rest (k = 13, any k that is
+ *                not a multiple of 16, unaligned strides or bases).
+ * krs_gemm_q8_last_route / krs_gemm_q8_plan_route: as krs_gemm_last_route / krs_gemm_plan_route.  The record: kernel
+ * (KRS_GEMM_Q8_KERNEL_*), ep_vec (1 when every epilogue operand allowed 8-wide vector access), k_tail (TILE128 only: 1
+ * when k is not whole 128-byte tile rows and the tail is zero-filled), epilogue (RING only: 1 = the cross build -- bf16
+ * output, x0 without R, ep_vec -- whose x0 / x loads are issued ahead, as krs_gemm's build 1; else 0, the general
+ * epilogue).  All zero after a refused call or a no-op.
+ * ------------------------------------------------------------------------- */
+enum {
+  KRS_GEMM_Q8_KERNEL_NONE = 0, KRS_GEMM_Q8_KERNEL_GENERIC = 1, KRS_GEMM_Q8_KERNEL_TILE128 = 2, KRS_GEMM_Q8_KERNEL_RING = 3
+};
+typedef struct krs_gemm_q8_route {
+  int32_t kernel;
+  int32_t ep_vec;
+  int32_t k_tail;
+  int32_t epilogue;
+} krs_gemm_q8_route;
+int krs_gemm_q8(const int8_t* aq, int64_t lda, const float* astep, const int8_t* wq, int64_t ldw, const float* wstep,
+                void* c, int64_t ldc, int64_t m, int64_t n, int64_t k, int out_dtype, const krs_gemm_epilogue* epilogue,
+                void* stream);
+int krs_gemm_q8_last_route(krs_gemm_q8_route* route);
+int krs_gemm_q8_plan_route(const int8_t* aq, int64_t lda, const float* astep, const int8_t* wq, int64_t ldw,
+                           const float* wstep, const void* c, int64_t ldc, int64_t m, int64_t n, int64_t k, int out_dtype,
+                           const krs_gemm_epilogue* epilogue, krs_gemm_q8_route* route);
+
 #ifdef __cplusplus
 }
 #endif

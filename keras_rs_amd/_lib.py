@@ -61,6 +61,10 @@ class GemmRoute(C.Structure):
                 ("kernel", "splits", "reduce", "epilogue", "ep_vec", "thin_width", "thin_is_a")]
 
 
+class GemmQ8Route(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("kernel", "ep_vec", "k_tail", "epilogue")]
+
+
 class EmbedFwdRoute(C.Structure):
     _fields_ = [(name, C.c_int32) for name in
                 ("kernel", "lpr", "has_w", "stream", "hot_rows", "bpg", "table_dtype", "out_dtype")] + [("blocks", C.c_int64)]
@@ -157,6 +161,9 @@ PROTOTYPES = {
     "krs_retrieval_rank": (_I, [_P, _I64, _P, _I64, _I, _I64, _I64, _I64, _P, _P, _I, _P, _P, _P, _SZ, _P]),
     "krs_retrieval_topk_q8_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
     "krs_retrieval_topk_q8": (_I, [_P, _I64, _I, _P, _I64, _P, _P, _I64, _I64, _I64, _I, _P, _I, _P, _P, _P, _SZ, _P]),
+    "krs_gemm_q8": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _P]),
+    "krs_gemm_q8_last_route": (_I, [_P]),
+    "krs_gemm_q8_plan_route": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

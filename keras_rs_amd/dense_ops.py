@@ -246,6 +246,102 @@ def plan_gemm_route(a, lda, a_is_km, b, ldb, b_is_nk, c, ldc, m, n, k, in_dtype,
     return int(rc), _route_dict(rt)
 
 
+# ---- K18: Dense / FeatureCross products in int8 -----------------------------------------------------------------------
+GEMM_Q8_KERNELS = {0: None, 1: "generic", 2: "tile128", 3: "ring"}
+
+
+def _q8_route_dict(rt) -> dict:
+    return dict(kernel=GEMM_Q8_KERNELS[rt.kernel], ep_vec=bool(rt.ep_vec), k_tail=bool(rt.k_tail), epilogue=int(rt.epilogue))
+
+
+def last_gemm_q8_route() -> dict:
+    """Where the calling thread's last krs_gemm_q8 ran (krs_gemm_q8_last_route): kernel (a GEMM_Q8_KERNELS name, None when
+    no launch was made), ep_vec, k_tail, epilogue (the ring's build: 0 general, 1 cross).  Reads a host-side record, no
+    device sync."""
+    rt = L.GemmQ8Route()
+    L.lib().krs_gemm_q8_last_route(C.byref(rt))
+    return _q8_route_dict(rt)
+
+
+def plan_gemm_q8_route(aq, lda, astep, wq, ldw, wstep, c, ldc, m, n, k, out_dtype, epilogue=None):
+    """(status, route) a krs_gemm_q8 with these arguments would have (krs_gemm_q8_plan_route; needs no GPU): the operands
+    are addresses (ints: only their alignment and nullness are read), epilogue a GemmEpilogue or None."""
+    rt = L.GemmQ8Route()
+    rc = L.lib().krs_gemm_q8_plan_route(aq, lda, astep, wq, ldw, wstep, c, ldc, m, n, k, out_dtype,
+                                        C.byref(epilogue) if epilogue is not None else None, C.byref(rt))
+    return int(rc), _q8_route_dict(rt)
+
+
+def gemm_q8_prequantized(aq: torch.Tensor, astep: torch.Tensor, wq: torch.Tensor, wstep: torch.Tensor, *,
+                         bias: torch.Tensor | None = None, act: int = L.ACT_NONE, x0: torch.Tensor | None = None,
+                         x_res: torch.Tensor | None = None, diag_scale: float = 0.0,
+                         out_dtype: torch.dtype = torch.float32, u_out: bool = False, r: torch.Tensor | None = None,
+                         beta: float = 1.0, out: torch.Tensor | None = None):
+    """krs_gemm_q8 on operands that are int8 already: aq [M, K] with astep [M], wq [N, K] with wstep [N] (row strides
+    taken from the tensors).  Returns (C, u_or_None)."""
+    aq, wq = L.rowmajor(aq, "gemm_q8 aq"), L.rowmajor(wq, "gemm_q8 wq")
+    if aq.dtype != torch.int8 or wq.dtype != torch.int8:
+        raise L.KrsError("gemm_q8: aq and wq must be int8")
+    (m, k), (n, kw) = aq.shape, wq.shape
+    if k != kw or tuple(astep.shape) != (m,) or tuple(wstep.shape) != (n,):
+        raise L.KrsError(f"gemm_q8: shapes do not fit (aq {tuple(aq.shape)}, astep {tuple(astep.shape)}, "
+                         f"wq {tuple(wq.shape)}, wstep {tuple(wstep.shape)})")
+    if astep.dtype != torch.float32 or wstep.dtype != torch.float32 or not astep.is_contiguous() or not wstep.is_contiguous():
+        raise L.KrsError("gemm_q8: steps are contiguous float32 vectors")
+    c = out if out is not None else torch.empty((m, n), dtype=out_dtype, device=aq.device)
+    odt = c.dtype
+    ep = L.GemmEpilogue()
+    keep = []
+    if bias is not None:
+        bias = bias.float().contiguous()
+        keep.append(bias)
+        ep.bias = bias.data_ptr()
+    ep.act = act
+    ep.diag_scale = float(diag_scale or 0.0)
+    if x0 is not None:
+        x0, x_res = L.rowmajor(x0, "gemm_q8 x0"), L.rowmajor(x_res, "gemm_q8 x_res")
+        if x0.stride(0) != x_res.stride(0):
+            x0, x_res = x0.contiguous(), x_res.contiguous()
+        if x0.dtype != odt or x_res.dtype != odt or tuple(x0.shape) != (m, n) or tuple(x_res.shape) != (m, n):
+            raise L.KrsError("gemm_q8: x0 / x_res must have the output's shape and dtype")
+        keep += [x0, x_res]
+        ep.x0, ep.x, ep.ldx = x0.data_ptr(), x_res.data_ptr(), x0.stride(0) if m > 1 else n
+    u = None
+    if u_out:
+        u = torch.empty((m, n), dtype=odt, device=aq.device)
+        ep.u_out, ep.ldu = u.data_ptr(), n
+    if r is not None:
+        r = L.rowmajor(r, "gemm_q8 R")
+        if r.dtype != odt or tuple(r.shape) != (m, n):
+            raise L.KrsError("gemm_q8: R must have the output's shape and dtype")
+        keep.append(r)
+        ep.r, ep.ldr, ep.beta = r.data_ptr(), r.stride(0) if m > 1 else n, float(beta)
+    name = "gemm_q8 %dx%dx%d" % (m, n, k) if probe.ACTIVE is not None else "gemm_q8"
+    with probe.span(name, 2.0 * m * n * k):
+        rc = L.lib().krs_gemm_q8(L.ptr(aq), aq.stride(0) if m > 1 else k, L.ptr(astep), L.ptr(wq),
+                                 wq.stride(0) if n > 1 else k, L.ptr(wstep), L.ptr(c), c.stride(0) if m > 1 else n, m, n, k,
+                                 L.fdtype(c), C.byref(ep), L.stream_ptr())
+    L.check(rc, "krs_gemm_q8")
+    return c, u
+
+
+def gemm_q8(x: torch.Tensor, wq: torch.Tensor, wstep: torch.Tensor, *, bias: torch.Tensor | None = None,
+            act: int = L.ACT_NONE, x0: torch.Tensor | None = None, x_res: torch.Tensor | None = None,
+            diag_scale: float = 0.0, out_dtype: torch.dtype | None = None, u_out: bool = False):
+    """C = epilogue(scale(quantize(x) . wq^T)) (include/krs.h, K18): x [M, K] fp32 / bf16 is quantized per row
+    (embedding_ops.quantize_rows: Keras' dynamic input quantization), then ONE krs_gemm_q8 against the stored weight
+    wq [N, K] int8 / wstep [N] with the fused bias, activation and cross form.  Two launches, no error word read, no host
+    wait.  A row of x with a NaN or an infinity comes back as a row of NaNs.  Returns (C, u_or_None)."""
+    from keras_rs_amd.embedding_ops import quantize_rows
+
+    L.require_device(x, "gemm_q8 x")
+    if x.dim() != 2:
+        raise L.KrsError(f"gemm_q8: expected a matrix, got shape {tuple(x.shape)}")
+    aq, astep = quantize_rows(x.contiguous())
+    return gemm_q8_prequantized(aq, astep, wq, wstep, bias=bias, act=act, x0=x0, x_res=x_res, diag_scale=diag_scale,
+                                out_dtype=out_dtype or x.dtype, u_out=u_out)
+
+
 def colsum(a: torch.Tensor) -> torch.Tensor:
     a = L.rowmajor(a, "colsum")
     out = torch.empty(a.shape[1], dtype=torch.float32, device=a.device)

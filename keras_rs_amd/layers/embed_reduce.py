@@ -67,7 +67,7 @@ def check_quantize_request(layer, mode) -> None:
     """What every quantize() refuses before it touches the device: a mode other than "int8", an unbuilt layer, a layer
     that is quantized already."""
     if mode != "int8":
-        raise ValueError(f"Invalid quantization mode {mode!r}: the embedding layers support 'int8' only.")
+        raise ValueError(f"Invalid quantization mode {mode!r}: {type(layer).__name__} supports 'int8' only.")
     if not layer.built:
         raise RuntimeError(f"{type(layer).__name__} '{layer.name}' is not built: build it (or call it once) before "
                            "quantize(): there is no table to quantize yet.")

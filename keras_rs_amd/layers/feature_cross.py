@@ -14,6 +14,8 @@ import torch
 from keras_rs_amd import _lib as L
 from keras_rs_amd.autograd import CrossEpilogueFn, CrossLayerFn, Dx0Relay
 from keras_rs_amd.layers import base
+from keras_rs_amd.layers.dense import quantize_kernel, refuse_grad_input
+from keras_rs_amd.layers.embed_reduce import check_quantize_request, keep_fp32_steps, restore_fp32_steps
 
 _FUSED_ACTS = {None: L.ACT_NONE, base.linear: L.ACT_NONE, base.relu: L.ACT_RELU,
                base.sigmoid: L.ACT_SIGMOID, base.tanh: L.ACT_TANH}
@@ -25,6 +27,8 @@ class FeatureCross(base.Layer):
     Args mirror the reference (feature_cross.py:93-108): projection_dim, diag_scale,
     use_bias, pre_activation, kernel_initializer, bias_initializer,
     kernel_regularizer, bias_regularizer, plus base kwargs (dtype, name).
+    `quantize("int8")` turns the layer into its serving form (include/krs.h, K18): both kernels become int8 buffers
+    (down_kernel_q / down_kernel_step, kernel_q / kernel_step) and a call runs its products on the int8 matrix cores.
     """
 
     def __init__(self, projection_dim: int | None = None, diag_scale: float | None = 0.0,
@@ -46,6 +50,7 @@ class FeatureCross(base.Layer):
             raise ValueError(f"`diag_scale` should be non-negative. Received: `diag_scale={self.diag_scale}`")
         for w in ("down_kernel", "kernel", "bias"):
             self.register_parameter(w, None)
+        self.quantization_mode = None      # "int8" after quantize(): the kernels are buffers, *_q / *_step
 
     def build(self, input_shape, *_) -> None:
         d = int(input_shape[-1])
@@ -70,6 +75,8 @@ class FeatureCross(base.Layer):
             raise ValueError("`x0` and `x` should have the same shape. Received: "
                              f"`x.shape` = {tuple(x.shape)}, `x0.shape` = {tuple(x0.shape)}")
         L.require_device(x0, "FeatureCross input")
+        if self.quantization_mode:
+            return self._call_quantized(x0, x)
         lead, d = x0.shape[:-1], x0.shape[-1]
         same = x is x0
         x02 = x0.reshape(-1, d)
@@ -93,6 +100,56 @@ class FeatureCross(base.Layer):
             z = _Linear.apply(h, self.kernel, self.bias, cd)
             u = act(z).to(cd)
             y = CrossEpilogueFn.apply(u, x02.to(cd), x2.to(cd), diag)
+        return y.reshape(*lead, d)
+
+    # ---- int8 for inference (what keras' quantize("int8") does to the layer's two Dense sublayers) -----------------------
+    def quantize(self, mode: str = "int8") -> None:
+        """Replaces down_kernel (if present) and kernel by int8 rows of their transposes and one fp32 step per output
+        channel and frees them: `weights` holds the bias only, state_dict() holds the int8 form, get_config() is unchanged.
+        Inference only.  A kernel with a NaN or an infinity raises ValueError and leaves the layer as it was."""
+        check_quantize_request(self, mode)
+        what = f"{type(self).__name__} '{self.name}'"
+        done = {name: quantize_kernel(getattr(self, name), what) for name in ("down_kernel", "kernel")
+                if getattr(self, name) is not None}
+        for name, (q, step) in done.items():       # (nothing is touched before every kernel has passed its check)
+            self.register_buffer(name + "_q", q, persistent=True)
+            self.register_buffer(name + "_step", step, persistent=True)
+            setattr(self, name, None)
+        self._weight_order[:] = [w for w in self._weight_order if w is self.bias]
+        self._regularized[:] = [(w, reg) for w, reg in self._regularized if w is self.bias]
+        self.quantization_mode = mode
+
+    def _apply(self, fn, recurse=True):
+        """.to() / .bfloat16() / ...: the steps of the quantized kernels move with the module and stay fp32."""
+        keep = keep_fp32_steps(self)
+        out = super()._apply(fn, recurse)
+        restore_fp32_steps(self, keep)
+        return out
+
+    def _call_quantized(self, x0: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """quantize x -> h = x U on int8 (low rank only) -> quantize h -> int8 product with bias, pre-activation and the
+        cross form fused; a callable pre_activation runs between the product and krs_cross_epilogue_fwd."""
+        from keras_rs_amd import dense_ops as D
+
+        refuse_grad_input(self, x0, x)
+        lead, d = x0.shape[:-1], x0.shape[-1]
+        if d != self.kernel_q.shape[0]:
+            raise ValueError(f"FeatureCross: input feature size {d} does not match the kernel's {self.kernel_q.shape[0]}")
+        cd = self.compute_dtype
+        diag = float(self.diag_scale) if self.diag_scale else 0.0
+        act = self.pre_activation
+        with torch.no_grad():
+            x0c = x0.reshape(-1, d).to(cd)
+            xc = x0c if x is x0 else x.reshape(-1, d).to(cd)
+            h = xc
+            if getattr(self, "down_kernel_q", None) is not None:
+                h, _ = D.gemm_q8(h, self.down_kernel_q, self.down_kernel_step, out_dtype=cd)
+            if act in _FUSED_ACTS:
+                y, _ = D.gemm_q8(h, self.kernel_q, self.kernel_step, bias=self.bias, act=_FUSED_ACTS[act], x0=x0c, x_res=xc,
+                                 diag_scale=diag, out_dtype=cd)
+            else:
+                z, _ = D.gemm_q8(h, self.kernel_q, self.kernel_step, bias=self.bias, out_dtype=cd)
+                y = D.cross_epilogue_fwd(act(z).to(cd), x0c, xc, diag)
         return y.reshape(*lead, d)
 
     def get_config(self) -> dict:

@@ -40,54 +40,16 @@
 
 #include "gemm_device.h"
 #include "gemm_plan.h"
+#include "gemm_ring64.h"
 
 namespace krs {
 namespace {
 
 constexpr int BM = gplan::kTile, BN = gplan::kTile;
 constexpr int ROW_BYTES = gplan::kRowBytes;  // K extent of a tile row in bytes (64 bf16 / 32 fp32)
-constexpr int LDS_STRIDE = gplan::kLdsStride;
 constexpr int TILE_BYTES = gplan::kTileBytes;  // one operand tile (BM == BN)
 
-// ---- staging: HBM -> registers -> LDS ([row][k] with 144-byte rows) ---------
-// ES = element size (2 | 4).  `row0` tile origin along the operand's row axis
-// (m for A, n for B), `k0` along K.  rows/kk are the operand extents.
-
-// operand stored K-contiguous: elem(row, k) at base + (row*ld + k)*ES
-template <int ES>
-__device__ __forceinline__ void load_kcontig(const char* base, int64_t ld, int64_t row0, int64_t k0,
-                                             int64_t rows, int64_t kk, u32x4 (&r)[4]) {
-  const int t = threadIdx.x;
-  const int c = t & 7;
-  const int64_t kel = k0 + c * (16 / ES);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t row = row0 + (t >> 3) + 32 * i;
-    u32x4 v = {0, 0, 0, 0};
-    if (row < rows && kel < kk) v = *reinterpret_cast<const u32x4*>(base + (row * ld + kel) * ES);
-    r[i] = v;
-  }
-}
-// LDS address of 16-byte chunk `c` (0..7) of tile row `row`.
-//   K-contiguous staged operands: 144-byte rows, no swizzle: fragment reads (ds_read_b128) and
-//     the row-wise ds_write_b128 stores are both conflict-free;
-//   transposed-staged operands: 128-byte rows, chunk XOR (row >> 3): the column-wise
-//     ds_write_b64 / b128 stores drop from 16-way to the 2-way minimum of that access shape
-//     and fragment reads cost 2 cycles per lane group (scripts/lds_conflicts.py).
-template <bool KS>
-__device__ __forceinline__ int lds_chunk_off(int row, int c) {
-  if constexpr (KS) return row * ROW_BYTES + ((c ^ ((row >> 3) & 7)) << 4);
-  else return row * LDS_STRIDE + (c << 4);
-}
-
-__device__ __forceinline__ void store_kcontig(char* tile, const u32x4 (&r)[4]) {
-  const int t = threadIdx.x;
-  const int c = t & 7;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    *reinterpret_cast<u32x4*>(tile + lds_chunk_off<false>((t >> 3) + 32 * i, c)) = r[i];
-}
-
+// ---- staging: HBM -> registers -> LDS (load_kcontig / store_kcontig / lds_chunk_off: gemm_device.h) ---------
 // operand stored K-strided: elem(row, k) at base + (k*ld + row)*ES.  A thread
 // takes a 4(k) x (16/ES)(row) block: four 16-byte loads along `row`.
 template <int ES>
@@ -680,6 +642,23 @@ __device__ __forceinline__ void pp_lgkm_wait(u32x4 (&fa)[4], u32x4 (&fb)[2]) {
                : "n"(N));
 }
 
+// ---- what the two ring kernels (gemm_pp256_kernel, gemm_pp64_kernel) share besides the tile ---------------------------------
+// A wave's 128 x 64 block of C is acc[upper / lower 64 rows][m fragment][n fragment].  One MFMA of a main loop: 32-row chunk
+// i (0..3) of the wave's rows, 32-column half j, a lane's 16 bytes = 8 k of each operand.
+struct RingMmaBf16 {
+  f32x16 (&acc)[2][2][2];
+  __device__ __forceinline__ void operator()(int i, int j, const u32x4& fa, const u32x4& fb) const {
+    f32x16& d = acc[i >> 1][i & 1][j];
+    d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fb), d, 0, 0, 0);
+  }
+};
+// epilogue operands fetched under the tail of the main loop: 32-row chunks (residual form: all four of R; cross form: x0 and x
+// of the first two), and how many load instructions that is
+template <int EPI> constexpr int kRingEpiChunks = EPI == 2 ? 4 : EPI == 1 ? 2 : 0;
+template <int EPI> constexpr int kRingEpiLoads = kRingEpiChunks<EPI> * (EPI == 1 ? 8 : 4);
+// (The accumulator zeroing and the epilogue dispatch stay written out in both kernels: as shared functions, forced inline or
+//  not, they made hipcc reschedule every build of gemm_pp256_kernel -- docs/measurement_log.md, "One ring main loop".)
+
 // (Round 4 also built the 128x128 tile on a deep ring -- gemm_ring128_kernel, KRS_GEMM_OPT_PIPELINE = 7 -- for the per-rank
 //  shapes of a strongly-scaled job; it measured equal or slower than gemm_glds_kernel (47.2 against 44.9 us at M = 8192,
 //  profiles/archive/r4_gemm_ring128_b8192.txt: one 128x128 tile per CU already draws the ~40 GB/s per CU of the L2 -> LDS path) and
@@ -824,7 +803,7 @@ __global__ __launch_bounds__(512) void gemm_pp256_kernel(const GemmParams p, int
     }
   };
 
-  f32x16 acc[2][2][2];  // [upper / lower 64 rows][m fragment][n fragment]
+  f32x16 acc[2][2][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -833,20 +812,15 @@ __global__ __launch_bounds__(512) void gemm_pp256_kernel(const GemmParams p, int
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[h][i][j][r] = 0.0f;
-  // epilogue operands fetched under the tail of the main loop (ping-pong schedule): chunks, load instructions
-  constexpr int NPFC = EPI == 2 ? 4 : EPI == 1 ? 2 : 0;
-  constexpr int NPF = NPFC * (EPI == 1 ? 8 : 4);
+  const RingMmaBf16 mma{acc};
+  constexpr int NPFC = kRingEpiChunks<EPI>, NPF = kRingEpiLoads<EPI>;
   EpiOperands opf[4];
   auto mfma8 = [&](const u32x4(&fa)[4], const u32x4(&fb)[2]) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        f32x16& d = acc[i >> 1][i & 1][j];
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i]), __builtin_bit_cast(bf16x8, fb[j]), d, 0,
-                                                   0, 0);
-      }
+      for (int j = 0; j < 2; ++j) mma(i, j, fa[i], fb[j]);
     __builtin_amdgcn_s_setprio(0);
   };
   auto mfma8_dma = [&](const u32x4(&fa)[4], const u32x4(&fb)[2], bool is_a, int stage) {
@@ -855,9 +829,7 @@ __global__ __launch_bounds__(512) void gemm_pp256_kernel(const GemmParams p, int
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        f32x16& d = acc[i >> 1][i & 1][j];
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i]), __builtin_bit_cast(bf16x8, fb[j]), d, 0,
-                                                   0, 0);
+        mma(i, j, fa[i], fb[j]);
         if (i * 2 + j == 1) { __builtin_amdgcn_sched_barrier(0); issue_one(is_a, stage, 0); __builtin_amdgcn_sched_barrier(0); }
         if (i * 2 + j == 4) { __builtin_amdgcn_sched_barrier(0); issue_one(is_a, stage, 1); __builtin_amdgcn_sched_barrier(0); }
       }
@@ -951,39 +923,16 @@ __global__ __launch_bounds__(512) void gemm_pp256_kernel(const GemmParams p, int
 }
 
 // ---- gemm_pp64_kernel: the ring on 64-k blocks with WHOLE 128-byte lines per LDS-DMA row (round 6) --------------------------
-// (gemm_q8.hip's gemm_q8_ring_kernel is this schedule with int32 accumulators: a change to the prologue, the phase order, the
-//  counted waits or the slot arithmetic below belongs there too.)
-// Same tile (256 x 256, eight waves as 2 x 4, 128 x 64 per wave, v_mfma_f32_32x32x16_bf16), same ping-pong of the two wave
-// groups, same k order per accumulator (bit-identical to gemm_pp256_kernel) -- what changes is the operand stream: a piece is
-// 256 rows x 64 k = 32 KB and every row of it is one whole 128-byte line (gemm_pp256_kernel's 32-k pieces fetch each line of
-// A / B in two 64-byte halves, one K block apart: twice the requests on the per-CU L2 -> LDS path, which is what bounds the long-K
-// products -- 1920 cycles per 32-k block against 1024 of MFMA; scripts/exp/gemm_probe3 measured the stream alone at 137 us with
-// whole lines against 174).
-//   LDS: FIVE 32 KB slots (160 KB, the whole CU), piece i (A of block kb = 2 kb, B = 2 kb + 1) in slot i % 5: while block kb
-//   is read from two slots, pieces 2kb+2 .. 2kb+4 are landed / in flight in the other three.  Block kb issues piece 2kb+3 in its
-//   phases 0, 1 and piece 2kb+4 in its phases 2, 3 (two instructions per wave per phase, as the 32-k ring); the slot of 2kb+3 held
-//   A(kb-1), read last in phase 3 of block kb-1 -- that phase waits for its fragment reads before its first barrier, so the
-//   restage is ordered behind them by a barrier whichever wave group issues it.  One counted wait per block (phase 3: vmcnt(4) =
-//   piece 2kb+4 may stay in flight), the reads of block kb+1 come a phase later.
-//   Row image: 128-byte pitch, 16-byte chunk c of row r at physical chunk c ^ ((r >> 1) & 7): the four 16-lane groups of a
-//   ds_read_b128 (rows {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, +32) then cover the sixteen slots of the 256-byte bank row once.
-//   The DMA writes lanes linearly (8 lanes = one row), so the swizzle is applied to the SOURCE chunk: the eight lanes of a row
-//   still fetch one whole line.
-namespace pp64 {
-constexpr int SLOT = 32768;
-constexpr int NSLOT = 5;
-}  // namespace pp64
-
+// gemm_pp256_kernel's tile, accumulators and epilogues on the main loop of gemm_ring64.h (the schedule and its derivation are
+// there; gemm_q8.hip's gemm_q8_ring_kernel runs the same loop): a piece is 256 rows x 64 k, the epilogue's operands are
+// requested at the loop's tail point.
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_pp64_kernel(const GemmParams p, int nt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TM = 256, TN_ = 256;
-  typedef const __attribute__((address_space(1))) void* gptr;
-  typedef __attribute__((address_space(3))) void* lptr;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int grp = wave >> 2;
-  const int wm = grp, wn = wave & 3;
+  const int wm = wave >> 2, wn = wave & 3;
   const int64_t xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
   // (work-item order of gemm_pp256_kernel's K-contiguous form: the N tiles of an M panel, and the K splits of a tile, are
   //  neighbours on one XCD)
@@ -995,39 +944,6 @@ __global__ __launch_bounds__(512) void gemm_pp64_kernel(const GemmParams p, int 
   const int64_t kbeg = (int64_t)split * p.k_per_split;
   const int64_t nb = (min(p.k, kbeg + p.k_per_split) - kbeg) / 64;     // 64-k blocks (the host guarantees >= 3, whole)
 
-  // DMA sources: instruction q = wave*4 + i fills rows q*8 .. q*8+7 of a piece, lane = row*8 + physical chunk
-  const char* ap[4];
-  const char* bp[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = (wave * 4 + i) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    ap[i] = p.a + (min(m0 + r, p.m - 1) * p.lda + kbeg) * 2 + c * 16;
-    bp[i] = p.b + (min(n0 + r, p.n - 1) * p.ldb + kbeg) * 2 + c * 16;
-  }
-  const int dma_off = wave * 4096;      // + i*1024
-  auto issue_one = [&](const char* (&src)[4], int slot, int i) {
-    __builtin_amdgcn_global_load_lds((gptr)src[i], (lptr)(smem + slot * pp64::SLOT + dma_off + i * 1024), 16, 0, 0);
-    src[i] += 128;
-  };
-  auto issue_half = [&](const char* (&src)[4], int slot, int half) {
-    issue_one(src, slot, half * 2);
-    issue_one(src, slot, half * 2 + 1);
-  };
-  // fragment addresses inside a slot (sub-phase hk: ^ hk*32)
-  const int frow = lane & 31, fhalf = lane >> 5, key = (frow >> 1) & 7;
-  const int a_lane = (wm * 128 + frow) * 128 + ((fhalf ^ key) << 4);
-  const int b_lane = (wn * 64 + frow) * 128 + ((fhalf ^ key) << 4);
-  auto load_frags = [&](int sa, int sb, int hk, u32x4(&fa)[4], u32x4(&fb)[2]) {
-    const char* pa = smem + sa * pp64::SLOT;
-    const char* pb = smem + sb * pp64::SLOT;
-    const int x = hk * 32;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const u32x4*>(pb + (b_lane ^ x) + j * 4096);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const u32x4*>(pa + (a_lane ^ x) + i * 4096);
-  };
-
   f32x16 acc[2][2][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
@@ -1037,104 +953,12 @@ __global__ __launch_bounds__(512) void gemm_pp64_kernel(const GemmParams p, int 
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[h][i][j][r] = 0.0f;
-  constexpr int NPFC = EPI == 2 ? 4 : EPI == 1 ? 2 : 0;
-  constexpr int NPF = NPFC * (EPI == 1 ? 8 : 4);
+  constexpr int NPFC = kRingEpiChunks<EPI>;
   EpiOperands opf[4];
-  auto mfma8 = [&](const u32x4(&fa)[4], const u32x4(&fb)[2]) {
-    __builtin_amdgcn_s_setprio(1);
+  ring64_main_loop<2, kRingEpiLoads<EPI>>(smem, p, m0, n0, kbeg, nb, lane, wave, RingMmaBf16{acc}, [&]() {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        f32x16& d = acc[i >> 1][i & 1][j];
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i]), __builtin_bit_cast(bf16x8, fb[j]), d, 0,
-                                                   0, 0);
-      }
-    __builtin_amdgcn_s_setprio(0);
-  };
-  // the compute segment with the two LDS-DMA instructions of this phase's half piece (`src` / `slot`) behind its 2nd and 5th
-  // MFMA: in the load segment they (60-185 cycles each) made it the longer of the two segments -- h = x U 195 -> 189 us, the
-  // cross product 440 -> 430; where among the MFMAs they sit does not matter (profiles/r6_gemm_k64_dma_in_compute_ab.txt)
-  auto mfma8_dma = [&](const u32x4(&fa)[4], const u32x4(&fb)[2], const char* (&src)[4], int slot, int half) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        f32x16& d = acc[i >> 1][i & 1][j];
-        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i]), __builtin_bit_cast(bf16x8, fb[j]), d, 0,
-                                                   0, 0);
-        if (i * 2 + j == 1) { __builtin_amdgcn_sched_barrier(0); issue_one(src, slot, half * 2); __builtin_amdgcn_sched_barrier(0); }
-        if (i * 2 + j == 4) { __builtin_amdgcn_sched_barrier(0); issue_one(src, slot, half * 2 + 1); __builtin_amdgcn_sched_barrier(0); }
-      }
-    __builtin_amdgcn_s_setprio(0);
-  };
-  // one phase of a block that issues half a piece
-  auto phase = [&](int sa, int sb, int hk, const char* (&src)[4], int slot, int half, bool last_of_block) {
-    u32x4 fa[4], fb[2];
-    load_frags(sa, sb, hk, fa, fb);
-    if (last_of_block) {
-      // pieces 2kb+2, 2kb+3 have landed (read from the next phase on); the first half of piece 2kb+4 may stay in flight (its
-      // second half is issued behind this wait)
-      pp_vmcnt<2>();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this block's last reads are done before the barrier: its A slot is restaged next
-    }
-    pp_barrier();
-    mfma8_dma(fa, fb, src, slot, half);
-    pp_barrier();
-  };
-  auto step5 = [](int v, int by) { v += by; return v >= pp64::NSLOT ? v - pp64::NSLOT : v; };
-
-  {
-    // prologue: pieces 0 (A0), 1 (B0), 2 (A1) whole; blocks 0's operands must have landed, piece 2 may fly on
-    issue_half(ap, 0, 0); issue_half(ap, 0, 1);
-    issue_half(bp, 1, 0); issue_half(bp, 1, 1);
-    issue_half(ap, 2, 0); issue_half(ap, 2, 1);
-    pp_vmcnt<4>();
-    pp_barrier();
-    if (grp == 1) pp_barrier();  // rows 128..255 run one segment behind rows 0..127
-    int sa = 0, sb = 1, s3 = 3, s4 = 4;   // slots of pieces 2kb, 2kb+1, 2kb+3, 2kb+4
-    int64_t kb = 0;
-    for (; kb + 2 < nb; ++kb) {   // steady state: pieces 2kb+3 (B of kb+1) and 2kb+4 (A of kb+2) are issued
-      phase(sa, sb, 0, bp, s3, 0, false);
-      phase(sa, sb, 1, bp, s3, 1, false);
-      phase(sa, sb, 2, ap, s4, 0, false);
-      phase(sa, sb, 3, ap, s4, 1, true);
-      sa = step5(sa, 2); sb = step5(sb, 2); s3 = step5(s3, 2); s4 = step5(s4, 2);
-    }
-    // block nb-2: only B(nb-1) = piece 2kb+3 is left to issue; the epilogue's operands are requested behind it
-    {
-      phase(sa, sb, 0, bp, s3, 0, false);
-      phase(sa, sb, 1, bp, s3, 1, false);
-      u32x4 fa[4], fb[2];
-      load_frags(sa, sb, 2, fa, fb);
-      if constexpr (NPFC > 0) {
-#pragma unroll
-        for (int c = 0; c < NPFC; ++c) epi_prefetch<EPI>(p, opf[c], m0 + wm * 128 + c * 32, n0 + wn * 64);
-      }
-      pp_barrier();
-      mfma8(fa, fb);
-      pp_barrier();
-      load_frags(sa, sb, 3, fa, fb);
-      pp_vmcnt<NPF>();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      pp_barrier();
-      mfma8(fa, fb);
-      pp_barrier();
-      sa = step5(sa, 2); sb = step5(sb, 2);
-    }
-    // block nb-1: nothing in flight but the epilogue's operands
-#pragma unroll
-    for (int hk = 0; hk < 4; ++hk) {
-      u32x4 fa[4], fb[2];
-      load_frags(sa, sb, hk, fa, fb);
-      pp_barrier();
-      mfma8(fa, fb);
-      pp_barrier();
-    }
-    if (grp == 0) pp_barrier();
-  }
-  lds_dma_retired<NPF>();
+    for (int c = 0; c < NPFC; ++c) epi_prefetch<EPI>(p, opf[c], m0 + wm * 128 + c * 32, n0 + wn * 64);
+  });
   float* stage_f = reinterpret_cast<float*>(smem) + wave * (32 * 68);
   if constexpr (EPI >= 3) {
     gemm_epilogue_wave128_crossbwd<(EPI == 4 || EPI == 6) ? 1 : (EPI == 7 ? 2 : (EPI >= 8 ? 3 : 0)),
@@ -1417,13 +1241,11 @@ extern "C" size_t krs_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k, int 
 
 namespace krs {
 namespace {
-static_assert(gplan::kRingLds == 4 * pp::STAGE && gplan::kRing64Lds == pp64::NSLOT * pp64::SLOT, "the planner's LDS bytes");
+static_assert(gplan::kRingLds == 4 * pp::STAGE && gplan::kRing64Lds == ring64::NSLOT * ring64::SLOT, "the planner's LDS bytes");
 
 // where the calling thread's last krs_gemm ran (krs_gemm_last_route): cleared when gemm_run starts, written when it has
 // queued its last kernel, so a refused call and an empty product leave "none"
 thread_local krs_gemm_route g_route = {};
-
-bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // krs_gemm's argument checks, then the call's plan (gemm_plan.h); a refused plan leaves its message.  Host memory only:
 // pointer VALUES are read for their alignment, the epilogue struct is read, no operand is dereferenced.
@@ -1440,12 +1262,7 @@ int gemm_plan(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ld
   call.m = m; call.n = n; call.k = k; call.a_km = a_is_km != 0; call.b_nk = b_is_nk != 0;
   call.es = in_dtype == KRS_BF16 ? 2 : 4; call.out_dtype = out_dtype;
   call.lda = lda; call.ldb = ldb; call.ldc = ldc; call.al_a = al16(a); call.al_b = al16(b); call.al_c = al16(c);
-  if (ep) {
-    call.has_ep = true; call.act = ep->act; call.bias = ep->bias != nullptr; call.al_bias = al16(ep->bias);
-    call.x0 = ep->x0 != nullptr; call.al_x0 = al16(ep->x0); call.al_x = al16(ep->x); call.ldx = ep->ldx;
-    call.u_out = ep->u_out != nullptr; call.al_u = al16(ep->u_out); call.ldu = ep->ldu;
-    call.r = ep->r != nullptr; call.al_r = al16(ep->r); call.ldr = ep->ldr;
-  }
+  gplan::set_epilogue(call, ep);
   call.workspace_bytes = workspace_bytes; call.allow_split = allow_split; call.pipe = gemm_pipe(); call.tn128 = tn128;
   pl = gplan::plan_gemm(call);
   if (pl.status == KRS_ERR_WORKSPACE)
@@ -1520,12 +1337,7 @@ int gemm_run(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ldb
   const krs_gemm_route& rt = pl.route;
   if (rt.kernel == KRS_GEMM_KERNEL_NONE) return KRS_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  GemmParams p{};
-  p.a = reinterpret_cast<const char*>(a); p.lda = lda; p.a_km = call.a_km;
-  p.b = reinterpret_cast<const char*>(b); p.ldb = ldb; p.b_nk = call.b_nk;
-  p.c = reinterpret_cast<char*>(c); p.ldc = ldc; p.m = m; p.n = n; p.k = k; p.out_dtype = out_dtype;
-  p.has_ep = epilogue != nullptr;
-  if (epilogue) p.ep = *epilogue; else memset(&p.ep, 0, sizeof(p.ep));
+  GemmParams p = gemm_params(a, lda, call.a_km, b, ldb, call.b_nk, c, ldc, m, n, k, out_dtype, epilogue);
   p.splits = rt.splits; p.k_per_split = pl.k_per_split; p.ep_vec = rt.ep_vec;
   p.slabs = rt.splits > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
   if (int rc = call.es == 2 ? gemm_launch<2>(p, pl, in_dtype, st) : gemm_launch<4>(p, pl, in_dtype, st)) return rc;
@@ -1635,13 +1447,8 @@ static int cross_bwd(const char* who, bool dense, const void* a, int64_t lda, co
     return krs_cross_epilogue_bwd(g_out, u, x0, x0, dz, dx0, dx0_accumulate, fold_direct ? dx0 : nullptr, dbias, m, n,
                                   ld, 0.0f, act, dtype, workspace, workspace_bytes, stream);
   }
-  GemmParams p{};
-  p.a = reinterpret_cast<const char*>(a); p.lda = lda; p.a_km = 0;
-  p.b = reinterpret_cast<const char*>(bt); p.ldb = ldb; p.b_nk = 1;
-  p.c = reinterpret_cast<char*>(g_out); p.ldc = ldg; p.m = m; p.n = n; p.k = k; p.out_dtype = KRS_BF16;
-  p.has_ep = 1;
-  p.ep = ep;
-  p.splits = 1; p.k_per_split = k; p.slabs = nullptr; p.ep_vec = 1;
+  GemmParams p = gemm_params(a, lda, false, bt, ldb, true, g_out, ldg, m, n, k, KRS_BF16, &ep);   // (one pass over K)
+  p.ep_vec = 1;
   p.f_x0 = x0; p.f_u = u; p.f_uup = u_upper; p.f_dz = dz; p.f_dx0 = dx0; p.f_ld = ld; p.f_act = act; p.f_fold = fold_direct != 0;
   p.f_partial = dbias ? reinterpret_cast<float*>(workspace) : nullptr;
   // the fused epilogue of this form (EPI 3 .. 10 of both ring kernels) on the ring the planner gives the product (the 64-k

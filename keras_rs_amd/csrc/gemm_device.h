@@ -1,10 +1,12 @@
-// Device pieces shared by the GEMM translation units (gemm.hip, gemm_q8.hip): the kernel parameter block, the epilogue of
+// Device pieces shared by the GEMM translation units (gemm.hip, gemm_q8.hip): the kernel parameter block and its host-side
+// fill, the register staging of a K-contiguous 128-row tile, the epilogue of
 // one element and of eight consecutive columns (bias, activation, cross form, residual, one rounding to the output dtype),
 // the wave epilogue that stages accumulators through LDS (general, cross and residual builds), and the wait / barrier forms
 // of the LDS-DMA rings.  One copy of the epilogue arithmetic: every product kernel calls these.
 #ifndef KRS_GEMM_DEVICE_H_
 #define KRS_GEMM_DEVICE_H_
 
+#include "gemm_plan.h"
 #include "krs_dense_common.h"
 
 namespace krs {
@@ -28,6 +30,57 @@ struct GemmParams {
   // fused cross-backward epilogue (EPI 3 .. 8 of gemm_pp256_kernel, krs_gemm_cross_bwd): operands of the layer below
   const void* f_x0; const void* f_u; const void* f_uup; void* f_dz; void* f_dx0; float* f_partial; int64_t f_ld; int f_act; int f_fold;
 };
+
+// operands, shape and epilogue of a product (host); the caller then sets what is its own: splits, slabs, ep_vec, the f_* fields
+inline GemmParams gemm_params(const void* a, int64_t lda, bool a_km, const void* b, int64_t ldb, bool b_nk, void* c, int64_t ldc,
+                              int64_t m, int64_t n, int64_t k, int out_dtype, const krs_gemm_epilogue* ep) {
+  GemmParams p{};
+  p.a = reinterpret_cast<const char*>(a); p.lda = lda; p.a_km = a_km;
+  p.b = reinterpret_cast<const char*>(b); p.ldb = ldb; p.b_nk = b_nk;
+  p.c = reinterpret_cast<char*>(c); p.ldc = ldc; p.m = m; p.n = n; p.k = k; p.out_dtype = out_dtype;
+  p.has_ep = ep != nullptr;
+  if (ep) p.ep = *ep;
+  p.splits = 1; p.k_per_split = k;
+  return p;
+}
+
+// ---- staging of a 128-row tile: HBM -> registers -> LDS ([row][k] with 144-byte rows) ---------
+// operand stored K-contiguous, ES bytes per element: elem(row, k) at base + (row*ld + k)*ES.  `row0` tile origin along the
+// operand's row axis (m for A, n for B), `k0` along K; rows/kk are the operand extents.  A thread takes 16-byte chunk (t & 7)
+// of rows (t >> 3) + 32 i; a chunk at or beyond kk and a row beyond the operand are zero.
+template <int ES>
+__device__ __forceinline__ void load_kcontig(const char* base, int64_t ld, int64_t row0, int64_t k0,
+                                             int64_t rows, int64_t kk, u32x4 (&r)[4]) {
+  const int t = threadIdx.x;
+  const int c = t & 7;
+  const int64_t kel = k0 + c * (16 / ES);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t row = row0 + (t >> 3) + 32 * i;
+    u32x4 v = {0, 0, 0, 0};
+    if (row < rows && kel < kk) v = *reinterpret_cast<const u32x4*>(base + (row * ld + kel) * ES);
+    r[i] = v;
+  }
+}
+// LDS address of 16-byte chunk `c` (0..7) of tile row `row`.
+//   K-contiguous staged operands: 144-byte rows, no swizzle: fragment reads (ds_read_b128) and
+//     the row-wise ds_write_b128 stores are both conflict-free;
+//   transposed-staged operands: 128-byte rows, chunk XOR (row >> 3): the column-wise
+//     ds_write_b64 / b128 stores drop from 16-way to the 2-way minimum of that access shape
+//     and fragment reads cost 2 cycles per lane group (scripts/lds_conflicts.py).
+template <bool KS>
+__device__ __forceinline__ int lds_chunk_off(int row, int c) {
+  if constexpr (KS) return row * gplan::kRowBytes + ((c ^ ((row >> 3) & 7)) << 4);
+  else return row * gplan::kLdsStride + (c << 4);
+}
+
+__device__ __forceinline__ void store_kcontig(char* tile, const u32x4 (&r)[4]) {
+  const int t = threadIdx.x;
+  const int c = t & 7;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    *reinterpret_cast<u32x4*>(tile + lds_chunk_off<false>((t >> 3) + 32 * i, c)) = r[i];
+}
 
 // epilogue of one element; `odt` = dtype of C, x0, x, u_out, r
 __device__ __forceinline__ void epilogue_store(const GemmParams& p, int64_t i, int64_t j, float v) {

@@ -16,6 +16,9 @@
 #include "../../include/krs.h"
 
 namespace krs {
+
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
 namespace gplan {
 
 // every threshold, once
@@ -52,6 +55,15 @@ struct GemmCall {
   int pipe = 4;                 // KRS_GEMM_OPT_PIPELINE: 4 | 5 | 0
   bool tn128 = false;           // development switch KRS_GEMM_TN128: weight gradients on the 128 x 128 gemm_tn_glds_kernel
 };
+
+// which epilogue operands a call brings and how they are aligned (ep NULL: no epilogue); pointer VALUES only
+inline void set_epilogue(GemmCall& c, const krs_gemm_epilogue* ep) {
+  if (!ep) return;
+  c.has_ep = true; c.act = ep->act; c.bias = ep->bias != nullptr; c.al_bias = al16(ep->bias);
+  c.x0 = ep->x0 != nullptr; c.al_x0 = al16(ep->x0); c.al_x = al16(ep->x); c.ldx = ep->ldx;
+  c.u_out = ep->u_out != nullptr; c.al_u = al16(ep->u_out); c.ldu = ep->ldu;
+  c.r = ep->r != nullptr; c.al_r = al16(ep->r); c.ldr = ep->ldr;
+}
 
 struct GemmPlan {
   krs_gemm_route route = {};    // all zero ("none") when nothing is launched: m == 0, n == 0 or a refused call

@@ -4,11 +4,10 @@
 // quantizer, krs_quantize_rows_q8), wq [N, K] int8 with one step per output channel, an exact int32 product,
 // z = fmul_rn(fmul_rn((float) idot, wstep_j), astep_i), then krs_gemm's epilogue (gemm_device.h: one copy of it).
 // Kernels, by shape (gemm_q8_plan.h decides, a pure host function):
-//   * gemm_q8_ring_kernel     gemm_pp64_kernel's ring with int32 accumulators: 256 x 256 tiles, eight waves as 2 x 4,
-//                             128-byte = 128-k pieces by LDS-DMA into five 32 KB slots, the same source-side swizzle,
-//                             fragment reads, ping-pong of the two wave groups and counted waits -- that kernel is written in
-//                             bytes, and a lane's 16-byte fragment is one v_mfma_i32_32x32x32_i8 here where it is one
-//                             v_mfma_f32_32x32x16_bf16 there (both operands take the same 16-byte chunk, so how the
+//   * gemm_q8_ring_kernel     gemm_pp64_kernel's main loop (gemm_ring64.h, one copy) with int32 accumulators: 256 x 256 tiles,
+//                             eight waves as 2 x 4, 128-byte = 128-k pieces by LDS-DMA into five 32 KB slots -- the loop is
+//                             written in bytes, and a lane's 16-byte fragment is one v_mfma_i32_32x32x32_i8 here where it is
+//                             one v_mfma_f32_32x32x16_bf16 there (both operands take the same 16-byte chunk, so how the
 //                             instruction deals k to lanes cannot matter to an integer sum);
 //   * gemm_q8_tile_kernel     128 x 128 tiles staged through registers (gemm_mfma_kernel's form), a K tail zero-filled in
 //                             LDS: zero bytes add exactly nothing;
@@ -18,10 +17,9 @@
 // epilogue_store_vec8.  A row whose astep is 0 (a non-finite activation row) is written as quiet NaNs instead.  The ring's
 // cross build (bf16 output: the FeatureCross product of a served model) scales in the accumulator layout and runs the wave
 // epilogue krs_gemm's rings run, x0 / x requested ahead of the staging.
-#include <cstring>
-
 #include "gemm_device.h"
 #include "gemm_q8_plan.h"
+#include "gemm_ring64.h"
 
 namespace krs {
 namespace {
@@ -142,28 +140,7 @@ __device__ __forceinline__ void q8_nan_rows_wave128(const Q8Params& q, int64_t w
 // ---- 128 x 128 tiles, 4 waves as 2 x 2, operands staged HBM -> registers -> LDS ([row][k], 144-byte rows) ----------------
 constexpr int BM = gplan::kTile, BN = gplan::kTile;
 constexpr int ROW_BYTES = gplan::kRowBytes;   // 128 k per tile row
-constexpr int LDS_STRIDE = gplan::kLdsStride;
 constexpr int TILE_BYTES = gplan::kTileBytes;
-
-// rows row0 .. row0+127 of a K-contiguous int8 operand, bytes k0 .. k0+127: a thread takes chunk (t & 7) of rows
-// (t >> 3) + 32 i.  kk is a multiple of 16, so a 16-byte chunk lies inside the row or is zero; rows beyond the operand are zero.
-__device__ __forceinline__ void q8_load_rows(const char* base, int64_t ld, int64_t row0, int64_t k0, int64_t rows, int64_t kk,
-                                             u32x4 (&r)[4]) {
-  const int t = threadIdx.x;
-  const int64_t kel = k0 + (t & 7) * 16;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t row = row0 + (t >> 3) + 32 * i;
-    u32x4 v = {0, 0, 0, 0};
-    if (row < rows && kel < kk) v = *reinterpret_cast<const u32x4*>(base + row * ld + kel);
-    r[i] = v;
-  }
-}
-__device__ __forceinline__ void q8_store_rows(char* tile, const u32x4 (&r)[4]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(tile + ((t >> 3) + 32 * i) * LDS_STRIDE + ((t & 7) << 4)) = r[i];
-}
 
 __global__ __launch_bounds__(256, 3) void gemm_q8_tile_kernel(const Q8Params q) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -192,16 +169,17 @@ __global__ __launch_bounds__(256, 3) void gemm_q8_tile_kernel(const Q8Params q) 
 
   u32x4 ra[4], rb[4];
   auto load_tiles = [&](int64_t t) {
-    q8_load_rows(p.a, p.lda, m0, t * ROW_BYTES, p.m, p.k, ra);
-    q8_load_rows(p.b, p.ldb, n0, t * ROW_BYTES, p.n, p.k, rb);
+    // (K is a multiple of 16, so a 16-byte chunk lies inside the row or is zero)
+    load_kcontig<1>(p.a, p.lda, m0, t * ROW_BYTES, p.m, p.k, ra);
+    load_kcontig<1>(p.b, p.ldb, n0, t * ROW_BYTES, p.n, p.k, rb);
   };
   if (ntiles > 0) load_tiles(0);
   const int frow = lane & 31;   // fragment row (m for A, n for B)
   const int fhalf = lane >> 5;  // which 16-byte half of a 32-byte K step this lane feeds
   for (int64_t t = 0; t < ntiles; ++t) {
     __syncthreads();  // every wave is done reading the previous tile
-    q8_store_rows(ta, ra);
-    q8_store_rows(tb, rb);
+    store_kcontig(ta, ra);
+    store_kcontig(tb, rb);
     __syncthreads();
     if (t + 1 < ntiles) load_tiles(t + 1);  // in flight under the MFMAs below
 #pragma unroll
@@ -209,8 +187,8 @@ __global__ __launch_bounds__(256, 3) void gemm_q8_tile_kernel(const Q8Params q) 
       u32x4 fa[2], fb[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        fa[i] = *reinterpret_cast<const u32x4*>(ta + (wm * 64 + i * 32 + frow) * LDS_STRIDE + ((ks * 2 + fhalf) << 4));
-        fb[i] = *reinterpret_cast<const u32x4*>(tb + (wn * 64 + i * 32 + frow) * LDS_STRIDE + ((ks * 2 + fhalf) << 4));
+        fa[i] = *reinterpret_cast<const u32x4*>(ta + lds_chunk_off<false>(wm * 64 + i * 32 + frow, ks * 2 + fhalf));
+        fb[i] = *reinterpret_cast<const u32x4*>(tb + lds_chunk_off<false>(wn * 64 + i * 32 + frow, ks * 2 + fhalf));
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -227,15 +205,10 @@ __global__ __launch_bounds__(256, 3) void gemm_q8_tile_kernel(const Q8Params q) 
   q8_epi_chunk(q, acc[1], stage, m0 + wm * 64 + 32, n0 + wn * 64);
 }
 
-// ---- the ring: gemm_pp64_kernel's schedule (gemm.hip has its derivation) on int8 operands --------------------------------
-// A piece is 256 rows x 128 bytes = 256 rows x 128 k = 32 KB, every row one whole 128-byte line; piece i (A of block kb =
-// 2 kb, B = 2 kb + 1) lives in slot i % 5.  Block kb is consumed in four phases of 32 bytes = 32 k (one MFMA per fragment
-// pair), issues piece 2kb+3 in its phases 0, 1 and piece 2kb+4 in its phases 2, 3 behind the 2nd and 5th MFMA, and waits once
-// (phase 3: vmcnt(2)).  Row image: 16-byte chunk c of row r at physical chunk c ^ ((r >> 1) & 7), applied to the SOURCE chunk
-// of the DMA.  Rows beyond M / N are clamped to the last row (their results are never stored).  The host guarantees
+// ---- the ring: the main loop of gemm_ring64.h (gemm_pp64_kernel's) on int8 operands ----------------------------------------
+// A 128-byte piece row is 128 k here, a phase's 32 bytes one v_mfma_i32_32x32x32_i8 per fragment pair.  The host guarantees
 // K = nb whole pieces, nb >= 3, bases on 16 bytes and lda, ldw multiples of 16.
-constexpr int SLOT = 32768, NSLOT = 5;
-static_assert(q8plan::kRingLds == NSLOT * SLOT && q8plan::kTileLds == 2 * TILE_BYTES, "the planner's LDS bytes");
+static_assert(q8plan::kRingLds == ring64::NSLOT * ring64::SLOT && q8plan::kTileLds == 2 * TILE_BYTES, "the planner's LDS bytes");
 static_assert(q8plan::kTileLds >= 4 * 32 * 68 * 4 && q8plan::kRingLds >= 8 * 32 * 68 * 4, "the epilogue's staging fits");
 
 // EPI: 0 = the general epilogue, 1 = cross (bf16 output, vector access everywhere), as gemm_pp64_kernel's builds 0 and 1.
@@ -243,51 +216,15 @@ template <int EPI>
 __global__ __launch_bounds__(512) void gemm_q8_ring_kernel(const Q8Params q, int nt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TM = 256, TN_ = 256;
-  typedef const __attribute__((address_space(1))) void* gptr;
-  typedef __attribute__((address_space(3))) void* lptr;
   const GemmParams& p = q.g;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int grp = wave >> 2;
-  const int wm = grp, wn = wave & 3;
+  const int wm = wave >> 2, wn = wave & 3;
   const int64_t xcd = blockIdx.x & 7, tslot = blockIdx.x >> 3;
   const int64_t m_tile = (tslot / nt) * 8 + xcd;
   if (m_tile * TM >= p.m) return;
   const int64_t m0 = m_tile * TM, n0 = (tslot % nt) * TN_;
   const int64_t nb = p.k / 128;   // whole pieces, at least three
-
-  // DMA sources: instruction q = wave*4 + i fills rows q*8 .. q*8+7 of a piece, lane = row*8 + physical chunk
-  const char* ap[4];
-  const char* bp[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = (wave * 4 + i) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    ap[i] = p.a + min(m0 + r, p.m - 1) * p.lda + c * 16;
-    bp[i] = p.b + min(n0 + r, p.n - 1) * p.ldb + c * 16;
-  }
-  const int dma_off = wave * 4096;  // + i*1024
-  auto issue_one = [&](const char* (&src)[4], int slot, int i) {
-    __builtin_amdgcn_global_load_lds((gptr)src[i], (lptr)(smem + slot * SLOT + dma_off + i * 1024), 16, 0, 0);
-    src[i] += 128;
-  };
-  auto issue_half = [&](const char* (&src)[4], int slot, int half) {
-    issue_one(src, slot, half * 2);
-    issue_one(src, slot, half * 2 + 1);
-  };
-  // fragment addresses inside a slot (phase hk: ^ hk*32)
-  const int frow = lane & 31, fhalf = lane >> 5, key = (frow >> 1) & 7;
-  const int a_lane = (wm * 128 + frow) * 128 + ((fhalf ^ key) << 4);
-  const int b_lane = (wn * 64 + frow) * 128 + ((fhalf ^ key) << 4);
-  auto load_frags = [&](int sa, int sb, int hk, u32x4(&fa)[4], u32x4(&fb)[2]) {
-    const char* pa = smem + sa * SLOT;
-    const char* pb = smem + sb * SLOT;
-    const int x = hk * 32;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const u32x4*>(pb + (b_lane ^ x) + j * 4096);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const u32x4*>(pa + (a_lane ^ x) + i * 4096);
-  };
 
   i32x16 acc[4][2];   // [32-row chunk of the wave's 128 rows][32-column half of its 64 columns]
 #pragma unroll
@@ -296,91 +233,13 @@ __global__ __launch_bounds__(512) void gemm_q8_ring_kernel(const Q8Params q, int
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
-#define KRS_Q8_MFMA(i, j)                                                                                                \
-  acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, fa[i]), __builtin_bit_cast(i32x4, fb[j]), \
-                                                    acc[i][j], 0, 0, 0)
-  auto mfma8 = [&](const u32x4(&fa)[4], const u32x4(&fb)[2]) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) KRS_Q8_MFMA(i, j);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  // the compute segment with the two LDS-DMA instructions of this phase's half piece behind its 2nd and 5th MFMA
-  auto mfma8_dma = [&](const u32x4(&fa)[4], const u32x4(&fb)[2], const char* (&src)[4], int slot, int half) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        KRS_Q8_MFMA(i, j);
-        if (i * 2 + j == 1) { __builtin_amdgcn_sched_barrier(0); issue_one(src, slot, half * 2); __builtin_amdgcn_sched_barrier(0); }
-        if (i * 2 + j == 4) { __builtin_amdgcn_sched_barrier(0); issue_one(src, slot, half * 2 + 1); __builtin_amdgcn_sched_barrier(0); }
-      }
-    __builtin_amdgcn_s_setprio(0);
-  };
-  // one phase of a block that issues half a piece
-  auto phase = [&](int sa, int sb, int hk, const char* (&src)[4], int slot, int half, bool last_of_block) {
-    u32x4 fa[4], fb[2];
-    load_frags(sa, sb, hk, fa, fb);
-    if (last_of_block) {
-      // pieces 2kb+2, 2kb+3 have landed (read from the next phase on); the first half of piece 2kb+4 may stay in flight
-      pp_vmcnt<2>();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this block's last reads are done before the barrier: its A slot is restaged next
-    }
-    pp_barrier();
-    mfma8_dma(fa, fb, src, slot, half);
-    pp_barrier();
-  };
-  auto step5 = [](int v, int by) { v += by; return v >= NSLOT ? v - NSLOT : v; };
-
-  {
-    // prologue: pieces 0 (A0), 1 (B0), 2 (A1) whole; block 0's operands must have landed, piece 2 may fly on
-    issue_half(ap, 0, 0); issue_half(ap, 0, 1);
-    issue_half(bp, 1, 0); issue_half(bp, 1, 1);
-    issue_half(ap, 2, 0); issue_half(ap, 2, 1);
-    pp_vmcnt<4>();
-    pp_barrier();
-    if (grp == 1) pp_barrier();  // rows 128..255 run one segment behind rows 0..127
-    int sa = 0, sb = 1, s3 = 3, s4 = 4;  // slots of pieces 2kb, 2kb+1, 2kb+3, 2kb+4
-    int64_t kb = 0;
-    for (; kb + 2 < nb; ++kb) {  // steady state: pieces 2kb+3 (B of kb+1) and 2kb+4 (A of kb+2) are issued
-      phase(sa, sb, 0, bp, s3, 0, false);
-      phase(sa, sb, 1, bp, s3, 1, false);
-      phase(sa, sb, 2, ap, s4, 0, false);
-      phase(sa, sb, 3, ap, s4, 1, true);
-      sa = step5(sa, 2); sb = step5(sb, 2); s3 = step5(s3, 2); s4 = step5(s4, 2);
-    }
-    // block nb-2: only B(nb-1) = piece 2kb+3 is left to issue
-    {
-      phase(sa, sb, 0, bp, s3, 0, false);
-      phase(sa, sb, 1, bp, s3, 1, false);
-      u32x4 fa[4], fb[2];
-      load_frags(sa, sb, 2, fa, fb);
-      pp_barrier();
-      mfma8(fa, fb);
-      pp_barrier();
-      load_frags(sa, sb, 3, fa, fb);
-      pp_vmcnt<0>();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      pp_barrier();
-      mfma8(fa, fb);
-      pp_barrier();
-      sa = step5(sa, 2); sb = step5(sb, 2);
-    }
-    // block nb-1: nothing in flight
-#pragma unroll
-    for (int hk = 0; hk < 4; ++hk) {
-      u32x4 fa[4], fb[2];
-      load_frags(sa, sb, hk, fa, fb);
-      pp_barrier();
-      mfma8(fa, fb);
-      pp_barrier();
-    }
-    if (grp == 0) pp_barrier();
-  }
-  lds_dma_retired<0>();
+  ring64_main_loop<1, 0>(
+      smem, p, m0, n0, 0, nb, lane, wave,
+      [&](int i, int j, const u32x4& fa, const u32x4& fb) {
+        acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, fa), __builtin_bit_cast(i32x4, fb), acc[i][j],
+                                                          0, 0, 0);
+      },
+      []() {});
   // every wave has passed the loop's last barrier: the slots are dead, a wave's staging words are its own
   int* stage = reinterpret_cast<int*>(smem) + wave * (32 * 68);
   const int64_t wm0 = m0 + wm * 128, wn0 = n0 + wn * 64;
@@ -426,8 +285,6 @@ __global__ __launch_bounds__(256) void gemm_q8_generic_kernel(const Q8Params q) 
 // where the calling thread's last krs_gemm_q8 ran: cleared when a call starts, written when its kernel is queued
 thread_local krs_gemm_q8_route g_route = {};
 
-bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 // krs_gemm_q8's argument checks (the shape checks first), then the call's plan.  Host memory only: pointer VALUES are read
 // for their alignment, the epilogue struct is read, no operand is dereferenced.
 int q8_plan(const int8_t* aq, int64_t lda, const float* astep, const int8_t* wq, int64_t ldw, const float* wstep, const void* c,
@@ -439,12 +296,7 @@ int q8_plan(const int8_t* aq, int64_t lda, const float* astep, const int8_t* wq,
   gplan::GemmCall call;
   call.m = m; call.n = n; call.k = k; call.a_km = false; call.b_nk = true; call.es = 1; call.out_dtype = out_dtype;
   call.lda = lda; call.ldb = ldw; call.ldc = ldc; call.al_a = al16(aq); call.al_b = al16(wq); call.al_c = al16(c);
-  if (ep) {
-    call.has_ep = true; call.act = ep->act; call.bias = ep->bias != nullptr; call.al_bias = al16(ep->bias);
-    call.x0 = ep->x0 != nullptr; call.al_x0 = al16(ep->x0); call.al_x = al16(ep->x); call.ldx = ep->ldx;
-    call.u_out = ep->u_out != nullptr; call.al_u = al16(ep->u_out); call.ldu = ep->ldu;
-    call.r = ep->r != nullptr; call.al_r = al16(ep->r); call.ldr = ep->ldr;
-  }
+  gplan::set_epilogue(call, ep);
   const q8plan::Q8Plan plan = q8plan::plan_gemm_q8(call);
   if (plan.status != KRS_OK) return fail(plan.status, "krs_gemm_q8: %s", plan.why);
   if (m == 0 || n == 0) return KRS_OK;
@@ -469,13 +321,8 @@ extern "C" int krs_gemm_q8(const int8_t* aq, int64_t lda, const float* astep, co
   if (rt.kernel == KRS_GEMM_Q8_KERNEL_NONE) return KRS_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   Q8Params q{};
-  GemmParams& p = q.g;
-  p.a = reinterpret_cast<const char*>(aq); p.lda = lda; p.a_km = 0;
-  p.b = reinterpret_cast<const char*>(wq); p.ldb = ldw; p.b_nk = 1;
-  p.c = reinterpret_cast<char*>(c); p.ldc = ldc; p.m = m; p.n = n; p.k = k; p.out_dtype = out_dtype;
-  p.has_ep = epilogue != nullptr;
-  if (epilogue) p.ep = *epilogue; else memset(&p.ep, 0, sizeof(p.ep));
-  p.splits = 1; p.k_per_split = k; p.ep_vec = rt.ep_vec;
+  q.g = gemm_params(aq, lda, false, wq, ldw, true, c, ldc, m, n, k, out_dtype, epilogue);   // (one pass over K)
+  q.g.ep_vec = rt.ep_vec;
   q.astep = astep; q.wstep = wstep; q.ws_vec = rt.ep_vec && al16(wstep);
   const dim3 grid((unsigned)pl.grid), block((unsigned)pl.block);
   int rc = KRS_OK;

@@ -614,6 +614,48 @@ int krs_dot_interaction_bwd_accumulate(const void* const* feats, const int64_t* 
                                        void* const* grad_feats, const int64_t* grad_feat_ld,
                                        uint64_t accumulate_mask, void* stream);
 
+/* Diagnostic, host only: where the CALLING THREAD's last krs_dot_interaction_fwd / _bwd / _bwd_accumulate ran.  Every
+ * field is 0 when there was no call yet, the call was refused (any return other than KRS_OK) or had nothing to do
+ * (batch == 0).
+ *   kernel     KRS_DOT_*: dot_fwd_mfma_kernel, dot_fwd_generic_kernel, dot_fwd_block_kernel, dot_bwd_mfma_kernel,
+ *              dot_bwd_valu_kernel, dot_bwd_generic_kernel, dot_bwd_block_kernel
+ *   dtype      the krs_dtype of the features
+ *   ks         forward MFMA only: k steps known at compile time, 8 (bf16, dim 128), 4 (bf16, dim 64) or 0 (run-time loop)
+ *   fr         feature rows the build provides for: 32 on the MFMA kernels, 28 or 32 on the vector-ALU backward, 64 on
+ *              the generic kernels, 0 (no limit) on the block kernels
+ *   self       backward MFMA / vector ALU: the SELF build (self_interaction); 0 where the kernel reads the flag at run time
+ *   multi      vector-ALU backward: the MULTI build (several samples per wave, or an [F, F] gradient of more columns
+ *              than the one-sample build loads)
+ *   acc        backward MFMA / vector ALU: the ACC build (accumulate_mask has a bit below n_feats)
+ *   ng         backward MFMA / vector ALU: gradient elements each lane loads per sample group (64 * ng columns)
+ *   lps_log2   vector-ALU backward: log2 of the lanes per sample (a lane owns two adjacent columns)
+ *   spw        vector-ALU backward: samples per wave, 1 .. 16
+ *   launches   kernel launches of the call: 1, or one per (32 features i, 128 features j) pair on the block kernels
+ *   lds_bytes  dynamic LDS of the launch (the backward MFMA and vector-ALU kernels; never above 64 KiB)
+ *   blocks     workgroups launched, summed over the launches
+ * Returns `kernel`; `route` may be NULL.  Lets tests prove which kernel they ran. */
+enum { KRS_DOT_NONE = 0, KRS_DOT_FWD_MFMA, KRS_DOT_FWD_GENERIC, KRS_DOT_FWD_BLOCK, KRS_DOT_BWD_MFMA, KRS_DOT_BWD_VALU,
+       KRS_DOT_BWD_GENERIC, KRS_DOT_BWD_BLOCK };
+typedef struct krs_dot_route {
+  int32_t kernel, dtype, ks, fr, self, multi, acc, ng, lps_log2, spw, launches, lds_bytes;
+  int64_t blocks;
+} krs_dot_route;
+int krs_dot_interaction_last_route(krs_dot_route* route);
+/* Diagnostic, host only, no GPU needed: where a krs_dot_interaction_fwd (backward == 0: grad_out / grad_ld stand for out /
+ * out_ld; grad_feats, grad_feat_ld and accumulate_mask are ignored) or a krs_dot_interaction_bwd_accumulate (backward != 0)
+ * with these arguments WOULD run (csrc/dot_plan.h, the planner the entries themselves run; KRS_DOT_BWD_VALU in the
+ * environment is honoured as they honour it).  The host tables feats, ld, grad_feats and grad_feat_ld are read; every
+ * device pointer is read as a VALUE only (nullness, alignment): nothing is dereferenced on the device side, no HIP call
+ * is made and the last-route record is untouched.  Fills *route (all zero when nothing would be launched) and returns
+ * what the entry returns before its first launch: KRS_OK or KRS_ERR_INVALID (a null table or pointer, n_feats <= 0,
+ * batch < 0, dim <= 0, a bad dtype). */
+int krs_dot_interaction_plan_route(int backward, const void* const* feats, const int64_t* ld, int n_feats,
+                                   int64_t batch, int dim, int dtype,
+                                   int self_interaction, int skip_gather,
+                                   const void* grad_out, int64_t grad_ld,
+                                   void* const* grad_feats, const int64_t* grad_feat_ld,
+                                   uint64_t accumulate_mask, krs_dot_route* route);
+
 /* ------------------------------------------------------------------------- *
  * K5  MOD bucketise for row-sharded tables
  *

@@ -70,6 +70,12 @@ class EmbedFwdRoute(C.Structure):
                 ("kernel", "lpr", "has_w", "stream", "hot_rows", "bpg", "table_dtype", "out_dtype")] + [("blocks", C.c_int64)]
 
 
+class DotRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in
+                ("kernel", "dtype", "ks", "fr", "self", "multi", "acc", "ng", "lps_log2", "spw", "launches",
+                 "lds_bytes")] + [("blocks", C.c_int64)]
+
+
 # Prototype of every entry point include/krs.h declares, in its order: name -> (restype, argtypes).  Any pointer is a
 # void* (pass L.ptr(t), an int or None; ctypes arrays and C.byref(struct) where the C side takes an array or a struct).
 # tests/test_capi_symbols.py parses the header and checks this table against it row by row.
@@ -121,6 +127,8 @@ PROTOTYPES = {
     "krs_dot_interaction_fwd": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P]),
     "krs_dot_interaction_bwd": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
     "krs_dot_interaction_bwd_accumulate": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _P, _U64, _P]),
+    "krs_dot_interaction_last_route": (_I, [_P]),
+    "krs_dot_interaction_plan_route": (_I, [_I, _P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _P, _U64, _P]),
     "krs_mod_bucketize_workspace_bytes": (_SZ, [_I64, _I]),
     "krs_mod_bucketize": (_I, [_P, _I, _I64, _I, _P, _P, _P, _P, _SZ, _P]),
     "krs_bce_fwd_bwd": (_I, [_P, _I, _P, _I64, _F, _F, _P, _P, _P, _P]),

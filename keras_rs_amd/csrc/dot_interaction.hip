@@ -13,9 +13,11 @@
 // row -> contiguous stores).  No LDS, no stack copy.
 // Backward: dX = (G + G^T) X per sample on the vector ALU (see dot_bwd_valu_kernel).
 // Shapes outside the fast path (32 < F <= 64, odd D, unaligned) use plain kernels.
+// Which kernel and build a call takes is decided in dot_plan.h (plan_dot); the entries below launch what it names.
 #include <algorithm>
 #include <type_traits>
 
+#include "dot_plan.h"
 #include "krs_common.h"
 
 namespace krs {
@@ -25,7 +27,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kMaxFast = 32;
+constexpr int kMaxFast = dplan::kMaxFast;
 
 struct DotParams {
   const void* feat[kMaxFast];
@@ -335,13 +337,23 @@ __global__ __launch_bounds__(64) void dot_bwd_valu_kernel(const DotParams p, int
   }
 }
 
+// the build the route names, on the plan's grid and LDS request (dot_plan.h restates the kernel's NG and LDS layout)
 template <int ES, int FR, bool SELF, bool MULTI>
-void launch_dot_bwd(const DotParams& p, int lps_log2, int spw, unsigned blocks, hipStream_t st) {
-  const size_t lds = 64 * 16 + (size_t)2 * spw * (tri_cols(FR, SELF) + 1) * sizeof(float);  // table + double buffer
-  if (p.acc_mask)
-    hipLaunchKernelGGL((dot_bwd_valu_kernel<ES, FR, SELF, MULTI, true>), dim3(blocks), dim3(64), lds, st, p, lps_log2, spw);
+void launch_dot_bwd(const DotParams& p, const dplan::DotPlan& pl, hipStream_t st) {
+  static_assert(dplan::valu_ng(FR, SELF, MULTI) == (MULTI ? 16 : (tri_cols(FR, SELF) + 63) / 64), "NG of dot_bwd_valu_kernel");
+  static_assert(dplan::valu_lds(FR, SELF, 1) == 64 * 16 + 2 * (tri_cols(FR, SELF) + 1) * 4, "table + double buffer");
+  const dim3 grid(pl.grid), block(pl.block);
+  const size_t lds = (size_t)pl.lds_bytes;
+  if (pl.route.acc)
+    hipLaunchKernelGGL((dot_bwd_valu_kernel<ES, FR, SELF, MULTI, true>), grid, block, lds, st, p, pl.lps_log2, pl.spw);
   else
-    hipLaunchKernelGGL((dot_bwd_valu_kernel<ES, FR, SELF, MULTI, false>), dim3(blocks), dim3(64), lds, st, p, lps_log2, spw);
+    hipLaunchKernelGGL((dot_bwd_valu_kernel<ES, FR, SELF, MULTI, false>), grid, block, lds, st, p, pl.lps_log2, pl.spw);
+}
+template <int ES, bool SELF>
+void launch_dot_bwd_rows(const DotParams& p, const dplan::DotPlan& pl, hipStream_t st) {
+  if (pl.route.multi) launch_dot_bwd<ES, 32, SELF, true>(p, pl, st);
+  else if (pl.route.fr == 28) launch_dot_bwd<ES, 28, SELF, false>(p, pl, st);
+  else launch_dot_bwd<ES, 32, SELF, false>(p, pl, st);
 }
 
 // ---- backward on the matrix cores (bf16, F <= 32, D a multiple of 32 up to 128, 16-byte aligned rows) ----
@@ -656,52 +668,88 @@ __global__ __launch_bounds__(256) void dot_bwd_block_kernel(const DotBlockParams
   }
 }
 
-// host side of the two: the launches of one call
-int run_dot_blocks(bool backward, const void* const* feats, const int64_t* ld, int n_feats, int64_t batch, int dim,
-                   int dtype, int self_interaction, int skip_gather, void* out, int64_t out_ld, void* const* grad_feats,
-                   const int64_t* grad_feat_ld, uint64_t accumulate_mask, hipStream_t st) {
-  for (int i0 = 0; i0 < n_feats; i0 += kBlockI) {
+static_assert(kMaxGeneric == dplan::kMaxGeneric && kBlockI == dplan::kBlockI && kBlockJ == dplan::kBlockJ,
+              "dot_plan.h plans for these table lengths");
+
+// where the calling thread's last krs_dot_interaction_* ran (krs_dot_interaction_last_route): cleared when an entry
+// starts, written when it has queued its kernels, so a refused call and an empty one leave "none"
+thread_local krs_dot_route g_route = {};
+
+// the call's plan (dot_plan.h); a refused plan leaves its message.  The host tables are read, device pointers as VALUES
+// only; no HIP call is made.  KRS_DOT_BWD_VALU is read here, not in the planner.
+int dot_plan(bool backward, const void* const* feats, const int64_t* ld, int n_feats, int64_t batch, int dim, int dtype,
+             int self_interaction, int skip_gather, const void* out, int64_t out_ld, void* const* grad_feats,
+             const int64_t* grad_feat_ld, uint64_t accumulate_mask, dplan::DotPlan& pl) {
+  dplan::DotCall call;
+  call.backward = backward; call.n_feats = n_feats; call.batch = batch; call.dim = dim; call.dtype = dtype;
+  call.self_interaction = self_interaction != 0; call.skip_gather = skip_gather != 0;
+  call.accumulate_mask = backward ? accumulate_mask : 0;
+  call.feats = feats; call.ld = ld; call.grad_feats = backward ? grad_feats : nullptr;
+  call.grad_feat_ld = backward ? grad_feat_ld : nullptr;
+  call.out_addr = reinterpret_cast<uintptr_t>(out); call.out_ld = out_ld;
+  call.force_valu = backward && getenv("KRS_DOT_BWD_VALU") != nullptr;
+  pl = dplan::plan_dot(call);
+  if (pl.status != KRS_OK) return fail(pl.status, "dot_interaction%s: %s", backward ? "_bwd" : "", pl.why);
+  return KRS_OK;
+}
+
+// the arguments of the MFMA forward and of both fast backward kernels; slots past F repeat the last feature, so that
+// the backward kernels' clamped loads stay valid
+DotParams fast_params(const dplan::DotPlan& pl, const void* const* feats, const int64_t* ld, int n_feats, int64_t batch,
+                      int dim, int self_interaction, int skip_gather, void* out, int64_t out_ld, void* const* grad_feats,
+                      const int64_t* grad_feat_ld) {
+  DotParams p{};
+  for (int f = 0; f < kMaxFast; ++f) {
+    const int q = std::min(f, n_feats - 1);
+    if (grad_feats) { p.feat[f] = feats[q]; p.ld[f] = ld[q]; p.gfeat[f] = grad_feats[q]; p.gld[f] = grad_feat_ld[q]; }
+    else if (f < n_feats) { p.feat[f] = feats[f]; p.ld[f] = ld[f]; }
+  }
+  p.n_feats = n_feats; p.batch = batch; p.dim = dim; p.self_inter = self_interaction != 0;
+  p.skip_gather = skip_gather != 0; p.out = out; p.out_ld = out_ld; p.acc_mask = (uint32_t)pl.acc_mask;
+  return p;
+}
+
+template <bool SELF, bool ACC>
+void launch_dot_bwd_mfma(const DotParams& p, const dplan::DotPlan& pl, hipStream_t st) {
+  const dim3 grid(pl.grid), block(pl.block);
+  const size_t lds = (size_t)pl.lds_bytes;
+  if (pl.route.ng == 16) hipLaunchKernelGGL((dot_bwd_mfma_kernel<SELF, ACC, 16, 4>), grid, block, lds, st, p, pl.x_bytes);
+  else hipLaunchKernelGGL((dot_bwd_mfma_kernel<SELF, ACC, 9, 4>), grid, block, lds, st, p, pl.x_bytes);
+}
+
+// the launches of one call of the block kernels, as the plan lists them
+int run_dot_blocks(const dplan::DotPlan& pl, bool backward, const void* const* feats, const int64_t* ld, int n_feats,
+                   int64_t batch, int dim, int dtype, int self_interaction, int skip_gather, void* out, int64_t out_ld,
+                   void* const* grad_feats, const int64_t* grad_feat_ld, hipStream_t st) {
+  for (const dplan::DotLaunch& l : pl.launches) {
     DotBlockParams p{};
-    p.i0 = i0; p.ni = std::min(kBlockI, n_feats - i0); p.n_feats = n_feats; p.batch = batch; p.dim = dim;
+    p.i0 = l.i0; p.ni = l.ni; p.j0 = l.j0; p.nj = l.nj; p.first_j = l.first_j;
+    p.n_feats = n_feats; p.batch = batch; p.dim = dim;
     p.self_inter = self_interaction != 0; p.skip_gather = skip_gather != 0; p.dtype = dtype; p.out = out; p.out_ld = out_ld;
-    for (int k = 0; k < p.ni; ++k) {
-      p.fi[k] = feats[i0 + k]; p.ldi[k] = ld[i0 + k];
-      if (backward) { p.gi[k] = grad_feats[i0 + k]; p.gldi[k] = grad_feat_ld[i0 + k]; }
-      if (i0 + k < 64 && ((accumulate_mask >> (i0 + k)) & 1ull)) p.acc_bits |= 1u << k;
+    for (int k = 0; k < l.ni; ++k) {
+      p.fi[k] = feats[l.i0 + k]; p.ldi[k] = ld[l.i0 + k];
+      if (backward) { p.gi[k] = grad_feats[l.i0 + k]; p.gldi[k] = grad_feat_ld[l.i0 + k]; }
+      if (l.i0 + k < 64 && ((pl.acc_mask >> (l.i0 + k)) & 1ull)) p.acc_bits |= 1u << k;
     }
-    // forward without skip_gather: pairs with j > i are not part of the output
-    const int j_end = (!backward && !skip_gather) ? std::min(n_feats, i0 + p.ni) : n_feats;
-    for (int j0 = 0; j0 < j_end; j0 += kBlockJ) {
-      p.j0 = j0; p.nj = std::min(kBlockJ, j_end - j0); p.first_j = j0 == 0;
-      for (int k = 0; k < p.nj; ++k) { p.fj[k] = feats[j0 + k]; p.ldj[k] = ld[j0 + k]; }
-      const int64_t work = backward ? batch * p.ni * dim : batch * p.ni * p.nj;
-      const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(work, 256), 65536);
-      if (backward) hipLaunchKernelGGL(dot_bwd_block_kernel, dim3(blocks), dim3(256), 0, st, p);
-      else hipLaunchKernelGGL(dot_fwd_block_kernel, dim3(blocks), dim3(256), 0, st, p);
-    }
+    for (int k = 0; k < l.nj; ++k) { p.fj[k] = feats[l.j0 + k]; p.ldj[k] = ld[l.j0 + k]; }
+    if (backward) hipLaunchKernelGGL(dot_bwd_block_kernel, dim3(l.blocks), dim3(pl.block), 0, st, p);
+    else hipLaunchKernelGGL(dot_fwd_block_kernel, dim3(l.blocks), dim3(pl.block), 0, st, p);
   }
   KRS_CHECK_LAUNCH("dot_interaction block kernels");
   return KRS_OK;
 }
 
-bool fast_ok(const void* const* feats, const int64_t* ld, int n_feats, int dim, int es) {
-  if (n_feats > kMaxFast) return false;
-  const int ve = 16 / es;
-  if (dim % ve) return false;
+DotGenericParams generic_params(const dplan::DotPlan& pl, const void* const* feats, const int64_t* ld, int n_feats,
+                                int64_t batch, int dim, int dtype, int self_interaction, int skip_gather, void* out,
+                                int64_t out_ld, void* const* grad_feats, const int64_t* grad_feat_ld) {
+  DotGenericParams g{};
   for (int f = 0; f < n_feats; ++f) {
-    if (reinterpret_cast<uintptr_t>(feats[f]) & 15) return false;
-    if (ld[f] % ve) return false;
+    g.feat[f] = feats[f]; g.ld[f] = ld[f];
+    if (grad_feats) { g.gfeat[f] = grad_feats[f]; g.gld[f] = grad_feat_ld[f]; }
   }
-  return true;
-}
-
-int check_args(const void* const* feats, const int64_t* ld, int n_feats, int64_t batch, int dim, int dtype,
-               const void* out) {
-  KRS_REQUIRE(feats && ld && out, "dot_interaction: null argument");
-  KRS_REQUIRE(n_feats > 0 && batch >= 0 && dim > 0, "dot_interaction: bad sizes");
-  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "dot_interaction: bad dtype");
-  for (int f = 0; f < n_feats; ++f) KRS_REQUIRE(feats[f], "dot_interaction: null feature pointer");
-  return KRS_OK;
+  g.n_feats = n_feats; g.batch = batch; g.dim = dim; g.self_inter = self_interaction != 0;
+  g.skip_gather = skip_gather != 0; g.out = out; g.out_ld = out_ld; g.dtype = dtype; g.acc_mask = pl.acc_mask;
+  return g;
 }
 
 }  // namespace
@@ -712,33 +760,39 @@ using namespace krs;
 extern "C" int krs_dot_interaction_fwd(const void* const* feats, const int64_t* ld, int n_feats, int64_t batch,
                                        int dim, int dtype, int self_interaction, int skip_gather, void* out,
                                        int64_t out_ld, void* stream) {
-  if (int rc = check_args(feats, ld, n_feats, batch, dim, dtype, out)) return rc;
-  if (batch == 0) return KRS_OK;
+  g_route = krs_dot_route{};
+  dplan::DotPlan pl;
+  if (int rc = dot_plan(false, feats, ld, n_feats, batch, dim, dtype, self_interaction, skip_gather, out, out_ld, nullptr,
+                        nullptr, 0, pl)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int es = dtype == KRS_BF16 ? 2 : 4;
-  if (fast_ok(feats, ld, n_feats, dim, es)) {
-    DotParams p{};
-    for (int f = 0; f < n_feats; ++f) { p.feat[f] = feats[f]; p.ld[f] = ld[f]; }
-    p.n_feats = n_feats; p.batch = batch; p.dim = dim; p.self_inter = self_interaction != 0;
-    p.skip_gather = skip_gather != 0; p.out = out; p.out_ld = out_ld;
-    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(batch, 4), 256 * 8);
-    if (es == 2 && dim == 128) hipLaunchKernelGGL((dot_fwd_mfma_kernel<2, 8>), dim3(blocks), dim3(256), 0, st, p);
-    else if (es == 2 && dim == 64) hipLaunchKernelGGL((dot_fwd_mfma_kernel<2, 4>), dim3(blocks), dim3(256), 0, st, p);
-    else if (es == 2) hipLaunchKernelGGL((dot_fwd_mfma_kernel<2, 0>), dim3(blocks), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((dot_fwd_mfma_kernel<4, 0>), dim3(blocks), dim3(256), 0, st, p);
-    KRS_CHECK_LAUNCH("dot_fwd_mfma_kernel");
-    return KRS_OK;
+  const dim3 grid(pl.grid), block(pl.block);
+  switch (pl.route.kernel) {
+    case KRS_DOT_NONE:
+      return KRS_OK;
+    case KRS_DOT_FWD_MFMA: {
+      const DotParams p = fast_params(pl, feats, ld, n_feats, batch, dim, self_interaction, skip_gather, out, out_ld, nullptr, nullptr);
+      if (dtype == KRS_F32) hipLaunchKernelGGL((dot_fwd_mfma_kernel<4, 0>), grid, block, 0, st, p);
+      else if (pl.route.ks == 8) hipLaunchKernelGGL((dot_fwd_mfma_kernel<2, 8>), grid, block, 0, st, p);
+      else if (pl.route.ks == 4) hipLaunchKernelGGL((dot_fwd_mfma_kernel<2, 4>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((dot_fwd_mfma_kernel<2, 0>), grid, block, 0, st, p);
+      KRS_CHECK_LAUNCH("dot_fwd_mfma_kernel");
+      break;
+    }
+    case KRS_DOT_FWD_GENERIC: {
+      const DotGenericParams g = generic_params(pl, feats, ld, n_feats, batch, dim, dtype, self_interaction, skip_gather, out,
+                                                out_ld, nullptr, nullptr);
+      hipLaunchKernelGGL(dot_fwd_generic_kernel, grid, block, 0, st, g);
+      KRS_CHECK_LAUNCH("dot_fwd_generic_kernel");
+      break;
+    }
+    case KRS_DOT_FWD_BLOCK:
+      if (int rc = run_dot_blocks(pl, false, feats, ld, n_feats, batch, dim, dtype, self_interaction, skip_gather, out, out_ld,
+                                  nullptr, nullptr, st)) return rc;
+      break;
+    default:
+      return fail(KRS_ERR_UNSUPPORTED, "dot_interaction: the plan names kernel %d", pl.route.kernel);
   }
-  if (n_feats > kMaxGeneric)
-    return run_dot_blocks(false, feats, ld, n_feats, batch, dim, dtype, self_interaction, skip_gather, out, out_ld,
-                          nullptr, nullptr, 0, st);
-  DotGenericParams g{};
-  for (int f = 0; f < n_feats; ++f) { g.feat[f] = feats[f]; g.ld[f] = ld[f]; }
-  g.n_feats = n_feats; g.batch = batch; g.dim = dim; g.self_inter = self_interaction != 0;
-  g.skip_gather = skip_gather != 0; g.out = out; g.out_ld = out_ld; g.dtype = dtype;
-  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(batch * n_feats * n_feats, 256), 65536);
-  hipLaunchKernelGGL(dot_fwd_generic_kernel, dim3(blocks), dim3(256), 0, st, g);
-  KRS_CHECK_LAUNCH("dot_fwd_generic_kernel");
+  g_route = pl.route;
   return KRS_OK;
 }
 
@@ -755,95 +809,62 @@ extern "C" int krs_dot_interaction_bwd_accumulate(const void* const* feats, cons
                                                   int skip_gather, const void* grad_out, int64_t grad_ld,
                                                   void* const* grad_feats, const int64_t* grad_feat_ld,
                                                   uint64_t accumulate_mask, void* stream) {
-  if (int rc = check_args(feats, ld, n_feats, batch, dim, dtype, grad_out)) return rc;
-  if (n_feats < 64) accumulate_mask &= (uint64_t(1) << n_feats) - 1;
-  KRS_REQUIRE(grad_feats && grad_feat_ld, "dot_interaction_bwd: null gradient outputs");
-  if (batch == 0) return KRS_OK;
+  g_route = krs_dot_route{};
+  dplan::DotPlan pl;
+  if (int rc = dot_plan(true, feats, ld, n_feats, batch, dim, dtype, self_interaction, skip_gather, grad_out, grad_ld,
+                        grad_feats, grad_feat_ld, accumulate_mask, pl)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int es = dtype == KRS_BF16 ? 2 : 4;
-  // pairs of adjacent columns per lane: rows 2*es-byte aligned, even D; 32-bit byte offsets
-  bool fast = n_feats <= kMaxFast && dim % 2 == 0;
-  for (int f = 0; fast && f < n_feats; ++f)
-    fast = !(reinterpret_cast<uintptr_t>(feats[f]) % (2 * es)) && !(reinterpret_cast<uintptr_t>(grad_feats[f]) % (2 * es)) &&
-           ld[f] % 2 == 0 && grad_feat_ld[f] % 2 == 0 && ld[f] > 0 && grad_feat_ld[f] > 0 &&
-           (batch * ld[f] + dim) * es < (int64_t(1) << 31) && (batch * grad_feat_ld[f] + dim) * es < (int64_t(1) << 31);
-  // matrix-core path: bf16, rows of whole 32-column blocks (one 16-lane group loads a row: D <= 128), 16-byte aligned rows
-  bool mfma_ok = es == 2 && n_feats <= kMaxFast && dim % 32 == 0 && dim <= 128 && !getenv("KRS_DOT_BWD_VALU") &&
-                 (skip_gather || tri_cols(n_feats, self_interaction != 0) > 0);
-  for (int f = 0; mfma_ok && f < n_feats; ++f)
-    mfma_ok = !(reinterpret_cast<uintptr_t>(feats[f]) % 16) && !(reinterpret_cast<uintptr_t>(grad_feats[f]) % 16) &&
-              ld[f] % 8 == 0 && grad_feat_ld[f] % 8 == 0 && ld[f] > 0 && grad_feat_ld[f] > 0 &&
-              ld[f] * 2 < (int64_t(1) << 32) && grad_feat_ld[f] * 2 < (int64_t(1) << 32);
-  if (mfma_ok) {
-    DotParams p{};
-    for (int f = 0; f < kMaxFast; ++f) {
-      const int q = std::min(f, n_feats - 1);
-      p.feat[f] = feats[q]; p.ld[f] = ld[q]; p.gfeat[f] = grad_feats[q]; p.gld[f] = grad_feat_ld[q];
+  void* gout = const_cast<void*>(grad_out);
+  const krs_dot_route& rt = pl.route;
+  switch (rt.kernel) {
+    case KRS_DOT_NONE:
+      return KRS_OK;
+    case KRS_DOT_BWD_MFMA: {
+      const DotParams p = fast_params(pl, feats, ld, n_feats, batch, dim, self_interaction, skip_gather, gout, grad_ld,
+                                      grad_feats, grad_feat_ld);
+      if (rt.self) { if (rt.acc) launch_dot_bwd_mfma<true, true>(p, pl, st); else launch_dot_bwd_mfma<true, false>(p, pl, st); }
+      else { if (rt.acc) launch_dot_bwd_mfma<false, true>(p, pl, st); else launch_dot_bwd_mfma<false, false>(p, pl, st); }
+      KRS_CHECK_LAUNCH("dot_bwd_mfma_kernel");
+      break;
     }
-    p.n_feats = n_feats; p.batch = batch; p.dim = dim; p.self_inter = self_interaction != 0;
-    p.skip_gather = skip_gather != 0; p.out = const_cast<void*>(grad_out); p.out_ld = grad_ld;
-    p.acc_mask = (uint32_t)accumulate_mask;
-    const int x_bytes = (dim + 127) / 128 * 8192;
-    const size_t lds = 64 * 16 + (size_t)2 * (x_bytes + 2048 + 32 * 36 * 4);
-    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(batch, 2), 256 * 8);
-    const bool self = self_interaction != 0, acc = accumulate_mask != 0;
-#define KRS_DOT_MFMA(SELF, ACC, NG, NB) \
-  hipLaunchKernelGGL((dot_bwd_mfma_kernel<SELF, ACC, NG, NB>), dim3(blocks), dim3(128), lds, st, p, x_bytes)
-#define KRS_DOT_MFMA_NB(SELF, ACC, NG) \
-  { KRS_DOT_MFMA(SELF, ACC, NG, 4); }
-#define KRS_DOT_MFMA_NG(SELF, ACC) \
-  { if (skip_gather) KRS_DOT_MFMA_NB(SELF, ACC, 16) else KRS_DOT_MFMA_NB(SELF, ACC, 9) }
-    if (self) { if (acc) KRS_DOT_MFMA_NG(true, true) else KRS_DOT_MFMA_NG(true, false) }
-    else { if (acc) KRS_DOT_MFMA_NG(false, true) else KRS_DOT_MFMA_NG(false, false) }
-#undef KRS_DOT_MFMA_NG
-#undef KRS_DOT_MFMA_NB
-#undef KRS_DOT_MFMA
-    KRS_CHECK_LAUNCH("dot_bwd_mfma_kernel");
-    return KRS_OK;
-  }
-  if (fast) {
-    DotParams p{};
-    for (int f = 0; f < kMaxFast; ++f) {
-      const int q = std::min(f, n_feats - 1);  // slots past F repeat the last feature: loads stay valid
-      p.feat[f] = feats[q]; p.ld[f] = ld[q]; p.gfeat[f] = grad_feats[q]; p.gld[f] = grad_feat_ld[q];
+    case KRS_DOT_BWD_VALU: {
+      const DotParams p = fast_params(pl, feats, ld, n_feats, batch, dim, self_interaction, skip_gather, gout, grad_ld,
+                                      grad_feats, grad_feat_ld);
+      if (dtype == KRS_BF16) { if (rt.self) launch_dot_bwd_rows<2, true>(p, pl, st); else launch_dot_bwd_rows<2, false>(p, pl, st); }
+      else { if (rt.self) launch_dot_bwd_rows<4, true>(p, pl, st); else launch_dot_bwd_rows<4, false>(p, pl, st); }
+      KRS_CHECK_LAUNCH("dot_bwd_valu_kernel");
+      break;
     }
-    p.n_feats = n_feats; p.batch = batch; p.dim = dim; p.self_inter = self_interaction != 0;
-    p.skip_gather = skip_gather != 0; p.out = const_cast<void*>(grad_out); p.out_ld = grad_ld;
-    p.acc_mask = (uint32_t)accumulate_mask;
-    const int ncols = skip_gather ? n_feats * n_feats : tri_cols(n_feats, self_interaction != 0);
-    int lps_log2 = 0;
-    while ((2 << lps_log2) < dim && lps_log2 < 6) ++lps_log2;     // lanes per sample: dim/2 up to 64
-    const int spw = std::min(64 >> lps_log2, std::max(1, 1024 / std::max(ncols, 1)));
-    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(batch, spw), 256 * 64);
-    // one sample per wave: rows rounded up to 28 (the 26 + 1 features of DLRM) or 32; several
-    // samples per wave (small D) and the [F, F] layout always take the 32-row build
-    const bool multi = spw > 1 || ncols > 64 * ((tri_cols(kMaxFast, true) + 63) / 64);
-    const bool self = self_interaction != 0;
-#define KRS_DOT_BWD(ES)                                                                        \
-  if (multi) { if (self) launch_dot_bwd<ES, 32, true, true>(p, lps_log2, spw, blocks, st);      \
-               else launch_dot_bwd<ES, 32, false, true>(p, lps_log2, spw, blocks, st); }        \
-  else if (n_feats <= 28 && !skip_gather) {                                                     \
-               if (self) launch_dot_bwd<ES, 28, true, false>(p, lps_log2, spw, blocks, st);     \
-               else launch_dot_bwd<ES, 28, false, false>(p, lps_log2, spw, blocks, st); }       \
-  else {       if (self) launch_dot_bwd<ES, 32, true, false>(p, lps_log2, spw, blocks, st);     \
-               else launch_dot_bwd<ES, 32, false, false>(p, lps_log2, spw, blocks, st); }
-    if (es == 2) { KRS_DOT_BWD(2) } else { KRS_DOT_BWD(4) }
-#undef KRS_DOT_BWD
-    KRS_CHECK_LAUNCH("dot_bwd_valu_kernel");
-    return KRS_OK;
+    case KRS_DOT_BWD_GENERIC: {
+      const DotGenericParams g = generic_params(pl, feats, ld, n_feats, batch, dim, dtype, self_interaction, skip_gather, gout,
+                                                grad_ld, grad_feats, grad_feat_ld);
+      hipLaunchKernelGGL(dot_bwd_generic_kernel, dim3(pl.grid), dim3(pl.block), 0, st, g);
+      KRS_CHECK_LAUNCH("dot_bwd_generic_kernel");
+      break;
+    }
+    case KRS_DOT_BWD_BLOCK:
+      if (int rc = run_dot_blocks(pl, true, feats, ld, n_feats, batch, dim, dtype, self_interaction, skip_gather, gout, grad_ld,
+                                  grad_feats, grad_feat_ld, st)) return rc;
+      break;
+    default:
+      return fail(KRS_ERR_UNSUPPORTED, "dot_interaction_bwd: the plan names kernel %d", rt.kernel);
   }
-  if (n_feats > kMaxGeneric)
-    return run_dot_blocks(true, feats, ld, n_feats, batch, dim, dtype, self_interaction, skip_gather,
-                          const_cast<void*>(grad_out), grad_ld, grad_feats, grad_feat_ld, accumulate_mask, st);
-  DotGenericParams g{};
-  for (int f = 0; f < n_feats; ++f) {
-    g.feat[f] = feats[f]; g.ld[f] = ld[f]; g.gfeat[f] = grad_feats[f]; g.gld[f] = grad_feat_ld[f];
-  }
-  g.n_feats = n_feats; g.batch = batch; g.dim = dim; g.self_inter = self_interaction != 0;
-  g.skip_gather = skip_gather != 0; g.out = const_cast<void*>(grad_out); g.out_ld = grad_ld; g.dtype = dtype;
-  g.acc_mask = accumulate_mask;
-  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(batch * n_feats * dim, 256), 65536);
-  hipLaunchKernelGGL(dot_bwd_generic_kernel, dim3(blocks), dim3(256), 0, st, g);
-  KRS_CHECK_LAUNCH("dot_bwd_generic_kernel");
+  g_route = rt;
   return KRS_OK;
+}
+
+extern "C" int krs_dot_interaction_plan_route(int backward, const void* const* feats, const int64_t* ld, int n_feats,
+                                              int64_t batch, int dim, int dtype, int self_interaction, int skip_gather,
+                                              const void* grad_out, int64_t grad_ld, void* const* grad_feats,
+                                              const int64_t* grad_feat_ld, uint64_t accumulate_mask, krs_dot_route* route) {
+  dplan::DotPlan pl;
+  const int rc = dot_plan(backward != 0, feats, ld, n_feats, batch, dim, dtype, self_interaction, skip_gather, grad_out,
+                          grad_ld, grad_feats, grad_feat_ld, accumulate_mask, pl);
+  if (route) *route = pl.route;
+  return rc;
+}
+
+extern "C" int krs_dot_interaction_last_route(krs_dot_route* route) {
+  if (route) *route = g_route;
+  return g_route.kernel;
 }

@@ -509,6 +509,45 @@ def dot_interaction_bwd(feats: Sequence[torch.Tensor], grad_out: torch.Tensor, s
     return grads
 
 
+DOT_KERNELS = {0: None, 1: "fwd_mfma", 2: "fwd_generic", 3: "fwd_block", 4: "bwd_mfma", 5: "bwd_valu", 6: "bwd_generic",
+               7: "bwd_block"}
+DOT_DTYPES = {L.F32: "f32", L.BF16: "bf16"}
+
+
+def _dot_route_dict(rt) -> dict:
+    d = {name: int(getattr(rt, name)) for name, _ in L.DotRoute._fields_}
+    d["kernel"] = DOT_KERNELS[rt.kernel]
+    d["dtype"] = DOT_DTYPES[rt.dtype] if rt.kernel else None
+    return d
+
+
+def dot_last_route() -> dict:
+    """Where the calling thread's last krs_dot_interaction_* ran (krs_dot_interaction_last_route): the fields of
+    krs_dot_route, kernel as a DOT_KERNELS name and dtype as "f32" / "bf16" (both None when no launch was made).  Reads a
+    host-side record, no device sync."""
+    rt = L.DotRoute()
+    L.lib().krs_dot_interaction_last_route(C.byref(rt))
+    return _dot_route_dict(rt)
+
+
+def dot_plan_route(backward, feat_ptrs, lds, batch, dim, dtype, self_interaction, skip_gather, out, out_ld,
+                   grad_ptrs=None, grad_lds=None, accumulate_mask=0):
+    """(status, route) a krs_dot_interaction_fwd (backward false) / _bwd_accumulate with these arguments would have
+    (krs_dot_interaction_plan_route; needs no GPU).  feat_ptrs / grad_ptrs are sequences of addresses (ints: only
+    nullness and alignment are read) or None, lds / grad_lds the row strides, out the address of the output (forward) or
+    of the incoming gradient; route is the dict of dot_last_route()."""
+    def table(values, ctype):
+        return None if values is None else (ctype * len(values))(*values)
+
+    n = len(feat_ptrs) if feat_ptrs is not None else (len(lds) if lds is not None else 0)
+    rt = L.DotRoute()
+    rc = L.lib().krs_dot_interaction_plan_route(int(bool(backward)), table(feat_ptrs, C.c_void_p), table(lds, C.c_int64), n,
+                                                int(batch), int(dim), int(dtype), int(self_interaction), int(skip_gather),
+                                                out, int(out_ld), table(grad_ptrs, C.c_void_p),
+                                                table(grad_lds, C.c_int64), int(accumulate_mask), C.byref(rt))
+    return int(rc), _dot_route_dict(rt)
+
+
 def mod_bucketize(ids: torch.Tensor, n_shards: int):
     """Stable grouping of ids by id % n_shards.  Returns (local_ids, perm, bucket_counts[int64])."""
     L.require_device(ids, "ids")

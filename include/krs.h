@@ -1207,6 +1207,66 @@ int krs_gemm_q8_plan_route(const int8_t* aq, int64_t lda, const float* astep, co
                            const float* wstep, const void* c, int64_t ldc, int64_t m, int64_t n, int64_t k, int out_dtype,
                            const krs_gemm_epilogue* epilogue, krs_gemm_q8_route* route);
 
+/* ------------------------------------------------------------------------- *
+ * K19  Fused multi-head self-attention over [b, l] token sequences: the score matrix, the probabilities and the
+ *      dropout mask are never stored
+ *
+ * q, k, v hold one row per token: token (bi, i) is row bi * l + i, head hi starts at column hi * dh, rows are ldq / ldk /
+ * ldv elements apart (>= h * dh; the three may be column slices of one packed [b * l, 3 h dh] projection output).  out,
+ * dout, dq, dk, dv have the same layout with strides of their own.  dtype (KRS_F32 / KRS_BF16) is the type of all of
+ * them; lse is fp32 [b, h, l].  Per (bi, hi), query i and key j, in fp32:
+ *     s_ij      = scale * sum_d q_id k_jd                                         (fp32 accumulate)
+ *     allowed   = (!causal || j <= i) && (key_valid == NULL || key_valid[bi, j])   (key_valid: uint8 [b, l], 1 = token)
+ *     m_i = max_allowed s_ij,  Z_i = sum_allowed exp(s_ij - m_i),  lse_i = m_i + log Z_i
+ *     P_ij      = exp(s_ij - lse_i) for allowed j, else 0
+ *     P~_ij     = keep_ij * P_ij / (1 - p)                                         (p = dropout_p, 0 <= p < 1)
+ *     o_i       = sum_j P~_ij v_j
+ *     delta_i   = sum_d dO_id o_id,   dP~_ij = dO_i . v_j,   dS_ij = P_ij (keep_ij / (1 - p) * dP~_ij - delta_i)
+ *     dV_j      = sum_i P~_ij dO_i,   dQ_i = scale sum_j dS_ij k_j,   dK_j = scale sum_i dS_ij q_i
+ * A decision: a row with no allowed key (left padding, an all-padding sequence) has o_i = 0 and lse_i = -inf and
+ * contributes exactly zero to dq, dk and dv; no NaN appears.  (Keras adds -1e9 to masked scores, which gives such a
+ * row the uniform average over all keys, future ones included.)  Inputs must be finite.
+ *
+ * The dropout mask is a pure function of (seed, *draw, bi, hi, i, j), 32-bit unsigned arithmetic throughout:
+ *     mix(x)    : x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *     base      = mix(mix(mix(mix(mix(seed_lo ^ 0x9e3779b9) ^ seed_hi) ^ draw_lo) ^ draw_hi) ^ (bi * h + hi))
+ *     keep_ij   <=> mix(base + ((i << 12) | j)) >= floor(p * 2^32)
+ * The forward and both backward sweeps recompute it.  draw is a device int64 the call only READS (the caller advances
+ * it with a device-side add after the forward, so a step can be captured in a graph); NULL when dropout_p == 0.
+ *
+ * Routes (csrc/seq_attn_plan.h decides, a pure host function):
+ *   KRS_SEQ_ATTN_FAST     bf16, dh <= 128 (dpad 32 / 64 / 128).  Scores on v_mfma_f32_32x32x16_bf16 with an online
+ *                         softmax over key tiles; P~ and dS are rounded to bf16 (nearest even) for the second products;
+ *                         fp32 accumulate; outputs rounded once to bf16.  Rows that are not whole 16-byte chunks on
+ *                         16-byte boundaries (dh = 50, odd strides) load element-wise.
+ *   KRS_SEQ_ATTN_GENERIC  fp32 at any dh <= 256, bf16 at 128 < dh <= 256: fp32 FMA throughout, outputs rounded once.
+ * One owner per output element and no float atomics on either route: bit-identical from call to call.
+ * Known divergence: Keras' MultiHeadAttention multiplies q by 1 / sqrt(key_dim) in the compute dtype before the
+ * product; here the fp32 score is scaled.
+ *
+ * krs_seq_attn_fwd writes out and lse.  krs_seq_attn_bwd takes them back with dout and writes dq, dk, dv (any may be
+ * NULL to skip it, not all); it needs krs_seq_attn_workspace_bytes of workspace (delta, fp32 [b, h, l]; it need not be
+ * initialised; too little is KRS_ERR_WORKSPACE); the forward uses none.  No host synchronisation.
+ * b == 0 or l == 0 is a successful no-op.  b < 0, h < 1, l < 0, dh < 1, a bad dtype, dropout_p outside [0, 1), a stride
+ * below h * dh, a null operand or output, and dropout without draw are KRS_ERR_INVALID.  l > 4096, dh > 256 and
+ * b * h * l > 2^31 - 1 (the launch grid) are KRS_ERR_UNSUPPORTED with a message naming the limit.
+ * krs_seq_attn_last_route: the route of the process's last krs_seq_attn_fwd / _bwd call, whichever thread made it (an
+ * autograd engine runs the backward on a thread of its own): kernel, and dpad on the fast route, else 0; both zero
+ * after a refused call or a no-op.  Returns kernel.
+ * ------------------------------------------------------------------------- */
+enum { KRS_SEQ_ATTN_NONE = 0, KRS_SEQ_ATTN_FAST = 1, KRS_SEQ_ATTN_GENERIC = 2 };
+size_t krs_seq_attn_workspace_bytes(int64_t b, int64_t h, int64_t l, int64_t dh, int dtype);
+int krs_seq_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int dtype,
+                     int64_t b, int64_t h, int64_t l, int64_t dh, const uint8_t* key_valid, int causal, float scale,
+                     float dropout_p, uint64_t seed, const int64_t* draw, void* out, int64_t ldo, float* lse,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int krs_seq_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int dtype,
+                     int64_t b, int64_t h, int64_t l, int64_t dh, const uint8_t* key_valid, int causal, float scale,
+                     float dropout_p, uint64_t seed, const int64_t* draw, const void* out, int64_t ldo, const void* dout,
+                     int64_t lddo, const float* lse, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                     int64_t lddv, void* workspace, size_t workspace_bytes, void* stream);
+int krs_seq_attn_last_route(int* kernel, int* dpad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,12 @@ PROTOTYPES = {
     "krs_gemm_q8": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _P]),
     "krs_gemm_q8_last_route": (_I, [_P]),
     "krs_gemm_q8_plan_route": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _P]),
+    "krs_seq_attn_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
+    "krs_seq_attn_fwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I64, _I64, _I64, _I64, _P, _I, _F, _F, _U64, _P, _P,
+                              _I64, _P, _P, _SZ, _P]),
+    "krs_seq_attn_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I64, _I64, _I64, _I64, _P, _I, _F, _F, _U64, _P, _P,
+                              _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P]),
+    "krs_seq_attn_last_route": (_I, [_P, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

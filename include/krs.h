@@ -459,6 +459,11 @@ int krs_gemm_cross_bwd_plan_route(const void* a, int64_t lda, const void* bt, in
  *   ep_vec      1 when every epilogue operand allowed 8-wide vector access
  *   thin_width  gemm_thin_kernel only: its width build (1, 4, 8, 16), else 0
  *   thin_is_a   gemm_thin_kernel only: 1 when A was the thin operand (m <= n), 0 when B was
+ *   schedule    gemm_pp64_kernel with epilogue build 1 or 2 only, else 0: KRS_GEMM_SCHED_* bits of the epilogue schedule
+ *               the launch took under KRS_GEMM_OPT_EPI_SCHEDULE -- LDS_LANDING (cross build: chunk 2 of x0 / x lands in the
+ *               dead ring LDS), X_IS_X0 (cross build with x == x0: the operand is loaded once, all four chunks under the
+ *               main loop's tail), STAGGER (rotated tile order of odd M panels and a half-period start offset of every
+ *               other first-round workgroup).  `epilogue` stays 1 for every cross build: the arithmetic is one.
  * The two-call form of krs_gemm_cross_bwd / krs_gemm_dense_bwd runs krs_gemm's body and therefore leaves a record too;
  * their fused form does not touch it.  Returns `kernel`; `route` may be NULL.  Lets tests prove which kernel they ran. */
 enum {
@@ -475,7 +480,9 @@ typedef struct krs_gemm_route {
   int32_t ep_vec;
   int32_t thin_width;
   int32_t thin_is_a;
+  int32_t schedule;
 } krs_gemm_route;
+enum { KRS_GEMM_SCHED_LDS_LANDING = 1, KRS_GEMM_SCHED_STAGGER = 2, KRS_GEMM_SCHED_X_IS_X0 = 4 };
 int krs_gemm_last_route(krs_gemm_route* route);
 /* Diagnostic, host only, no GPU needed: where a krs_gemm with these arguments (krs_gemm's, without the workspace pointer
  * and the stream) WOULD run under the pipeline option in force.  The decision is a pure function of sizes, strides, dtypes,
@@ -494,8 +501,17 @@ int krs_gemm_plan_route(const void* a, int64_t lda, int a_is_km, const void* b, 
  *   5 = the 32-k ring (gemm_pp256_kernel) also for the K-contiguous products that take the 64-k ring (gemm_pp64_kernel) by
  *   default: the A/B switch of round 6.
  *   (Rounds 2-4 used 5 / 6 / 7 for a five-stage ring, a prefetch schedule and a deep ring on 128x128 tiles; measured no
- *   faster and deleted in round 5.) */
-enum { KRS_GEMM_OPT_PIPELINE = 0 };
+ *   faster and deleted in round 5.)
+ *   KRS_GEMM_OPT_EPI_SCHEDULE (or the environment variable KRS_GEMM_EPI_SCHEDULE at first use): how gemm_pp64_kernel's
+ *   streaming epilogues (cross, residual, fused cross backward) request their operands and order their tiles --
+ *   0 = two chunks of x0 / x ahead, every workgroup starts at once, tiles in panel order: the reference schedule;
+ *   1 = (default) the cross build keeps its bias in registers, lands chunk 2 of x0 / x in the dead ring LDS and asks for
+ *       chunk 3 one chunk earlier, and a call with x == x0 takes a build that loads the operand once;
+ *   2 = stagger: odd M panels start half way round their N tiles and every other workgroup of the first round starts
+ *       half a tile period late, so that epilogues of some CUs meet main loops of others;
+ *   3 = both; -1 = back to the default (the environment variable, else the built-in value).  Which tile a workgroup
+ *   computes and when an operand is requested change speed only, never a bit. */
+enum { KRS_GEMM_OPT_PIPELINE = 0, KRS_GEMM_OPT_EPI_SCHEDULE = 1 };
 int krs_gemm_set_option(int key, int value);
 
 /* Tuning switches of krs_embed_bag_fwd / krs_embed_bag_bwd_* (process-wide; results never depend on them).

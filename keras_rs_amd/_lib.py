@@ -58,7 +58,12 @@ class GemmEpilogue(C.Structure):
 
 class GemmRoute(C.Structure):
     _fields_ = [(name, C.c_int32) for name in
-                ("kernel", "splits", "reduce", "epilogue", "ep_vec", "thin_width", "thin_is_a")]
+                ("kernel", "splits", "reduce", "epilogue", "ep_vec", "thin_width", "thin_is_a", "schedule")]
+
+
+# krs_gemm_set_option keys, and the bits of GemmRoute.schedule (include/krs.h)
+GEMM_OPT_PIPELINE, GEMM_OPT_EPI_SCHEDULE = 0, 1
+GEMM_SCHED_LDS_LANDING, GEMM_SCHED_STAGGER, GEMM_SCHED_X_IS_X0 = 1, 2, 4
 
 
 class GemmQ8Route(C.Structure):

@@ -102,18 +102,116 @@ __device__ __forceinline__ void store_kstrided(char* tile, const u32x4 (&r)[4]) 
   }
 }
 
+// Takes a chunk's operands as arrived at THIS point (empty statements that name the registers: hipcc waits here, once).
+// hipcc cannot count an epilogue's stores -- each sits behind a branch over its lanes -- so a wait of its own for operands
+// still in flight allows only the LOADS behind them to stay outstanding: consumed step by step that is vmcnt(6), (4), (2),
+// (0), and every step waits for the acknowledgement of the stores before it.  One wait where the operands are due anyway
+// leaves the steps behind it without any.  X0: the chunk holds x0 as well as x.
+template <bool X0>
+__device__ __forceinline__ void epi_settle(EpiOperands& o) {
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    asm volatile("" : "+v"(o.ex[it].x), "+v"(o.ex[it].y), "+v"(o.ex[it].z), "+v"(o.ex[it].w));
+    if constexpr (X0) asm volatile("" : "+v"(o.ex0[it].x), "+v"(o.ex0[it].y), "+v"(o.ex0[it].z), "+v"(o.ex0[it].w));
+  }
+}
+
 // gemm_epilogue_wave128 (gemm_device.h) with the operands of the first NPFC chunks already requested by the caller (under the tail of its
-// main loop): 4 = all of them (residual form: one operand), 2 = the first two (cross form: x0 and x)
-template <int EPI, int NPFC>
+// main loop): 4 = all of them (residual form, cross form with x == x0: one operand), 2 = the first two (cross form: x0 and x)
+// (PREBIAS: the bias values are in `pre_bias`, see epi_process; the builds that have them also settle their four chunks,
+//  requested under the tail, before the first store)
+template <int EPI, int NPFC, bool PREBIAS = false>
 __device__ __forceinline__ void gemm_epilogue_wave128_pre(const GemmParams& p, f32x16 (&acc)[2][2][2], float* stage,
-                                                          int64_t wm0, int64_t wn0, int split, EpiOperands (&o)[4]) {
+                                                          int64_t wm0, int64_t wn0, int split, EpiOperands (&o)[4],
+                                                          const float* pre_bias = nullptr) {
   static_assert(NPFC == 2 || NPFC == 4, "two or four chunks of operands are fetched ahead");
-  epi_process<EPI>(p, acc[0][0], o[0], stage, wm0, wn0, split);
+  if constexpr (PREBIAS && NPFC == 4) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) epi_settle<EPI == 1>(o[c]);
+  }
+  epi_process<EPI, PREBIAS>(p, acc[0][0], o[0], stage, wm0, wn0, split, pre_bias);
   if constexpr (NPFC == 2) epi_prefetch<EPI>(p, o[2], wm0 + 64, wn0);
-  epi_process<EPI>(p, acc[0][1], o[1], stage, wm0 + 32, wn0, split);
+  epi_process<EPI, PREBIAS>(p, acc[0][1], o[1], stage, wm0 + 32, wn0, split, pre_bias);
   if constexpr (NPFC == 2) epi_prefetch<EPI>(p, o[3], wm0 + 96, wn0);
-  epi_process<EPI>(p, acc[1][0], o[2], stage, wm0 + 64, wn0, split);
-  epi_process<EPI>(p, acc[1][1], o[3], stage, wm0 + 96, wn0, split);
+  epi_process<EPI, PREBIAS>(p, acc[1][0], o[2], stage, wm0 + 64, wn0, split, pre_bias);
+  epi_process<EPI, PREBIAS>(p, acc[1][1], o[3], stage, wm0 + 96, wn0, split, pre_bias);
+}
+
+// ---- the cross epilogue of the 64-k ring with chunk 2 of x0 / x landed in the dead ring LDS (KRS_GEMM_SCHED_LDS_LANDING) --------
+// gemm_epilogue_wave128_pre<1, 2> keeps two chunks of x0 / x in registers and asks for chunks 2 and 3 one epi_process before
+// each is needed; the registers for a third chunk do not exist (232 VGPRs).  The LDS does: in the epilogue the ring is dead
+// and only its first kEpiStageBytes stage accumulators.  So chunk 2 is requested at epilogue ENTRY by LDS-DMA into the
+// wave's own kEpiLandWaveBytes behind the staging area (x: 4 instructions of 1 KB, then x0: 4), and chunk 3 goes into the
+// registers chunk 0 frees, one chunk earlier than before.  Lanes land linearly, at the clamped addresses of epi_prefetch, so
+// a lane reads back ITS 16 bytes (one ds_read_b128, no swizzle, no other wave involved): the values, and with them every
+// bit of the result, are those of the register path.
+// The DMA and its wait are assembly statements hipcc does not count: a DMA it CAN see makes it fence the next LDS access --
+// the staging stores of chunk 0 -- with vmcnt(0) (the comment at lds_dma_retired), which would put the whole HBM latency in
+// front of the epilogue.  The counted wait is ours: memory operations retire in order, and what is issued between the DMA and
+// the wait cannot leave that span (both statements clobber memory): the eight loads of chunk 3 always, the stores of chunks
+// 0 and 1 where the tile is whole (gemm_epilogue_wave128_land counts them).  A wait that allows no more than those has
+// retired the DMA.  What hipcc waits for on its own account can only be stricter than it thinks (eight more operations are
+// in flight than it counts) -- which is why no wait of its own may fall between the DMA and ours: chunks 0 and 1 are
+// settled in front of the DMA, and the bias, which epi_process would load step by step, comes in registers.
+// M0 (the DMA's LDS base) belongs to the compiler: saved and restored inside the statement that sets it.
+__device__ __forceinline__ void epi_land_issue(const GemmParams& p, uint32_t land, int64_t row0, int64_t wn0) {
+  const int lane = threadIdx.x & 63;
+  const int64_t gnc = min(wn0 + (lane & 7) * 8, p.n - 8);
+  const uint16_t* src[8];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int64_t gmc = min(row0 + it * 8 + (lane >> 3), p.m - 1);
+    src[it] = reinterpret_cast<const uint16_t*>(p.ep.x) + gmc * p.ep.ldx + gnc;
+    src[4 + it] = reinterpret_cast<const uint16_t*>(p.ep.x0) + gmc * p.ep.ldx + gnc;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(src[i]), "s"(land + i * 1024)
+                 : "memory");
+  }
+}
+// the landed chunk into a chunk's registers; behind epi_land_issue at least BEHIND memory operations have been issued
+template <int BEHIND>
+__device__ __forceinline__ void epi_land_read(const char* land, EpiOperands& o) {
+  static_assert(BEHIND >= 8 && BEHIND < 64, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BEHIND) : "memory");
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    o.ex[it] = *reinterpret_cast<const uint4*>(land + it * 1024 + lane * 16);
+    o.ex0[it] = *reinterpret_cast<const uint4*>(land + 4096 + it * 1024 + lane * 16);
+  }
+}
+// `o`: chunks 0 and 1 requested by the caller under the tail of its main loop; `land`: the wave's kEpiLandWaveBytes;
+// `pre_bias`: epi_load_bias's values (a bias load inside epi_process, younger than the DMA, would wait for it at once)
+__device__ __forceinline__ void gemm_epilogue_wave128_land(const GemmParams& p, f32x16 (&acc)[2][2][2], float* stage, char* land,
+                                                           int64_t wm0, int64_t wn0, int split, EpiOperands (&o)[4],
+                                                           const float* pre_bias) {
+  const uint32_t land_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)land);
+  // Chunks 0 and 1 are taken as arrived HERE (they were requested most of two 64-k blocks ago): hipcc's wait for chunk 1 in
+  // front of its epi_process would allow the operations hipcc counts behind it -- the stores of chunk 0, the loads of
+  // chunk 3 -- and, not knowing of the DMA between, retire the DMA with chunk 1.
+  epi_settle<true>(o[0]);
+  epi_settle<true>(o[1]);
+  epi_land_issue(p, land_lds, wm0 + 64, wn0);
+  epi_process<1, true>(p, acc[0][0], o[0], stage, wm0, wn0, split, pre_bias);
+  epi_prefetch<1>(p, o[0], wm0 + 96, wn0);      // chunk 3: eight loads, whatever the tile
+  epi_process<1, true>(p, acc[0][1], o[1], stage, wm0 + 32, wn0, split, pre_bias);
+  // Behind the DMA: the stores of chunks 0 and 1 and the loads of chunk 3.  Where the wave's first 64 rows and its 64 columns
+  // lie inside C every lane stores -- four steps per chunk, y and (with u_out) u -- so that many operations are certain
+  // and chunk 3 may stay in flight with them; on an edge of C only the eight loads are.  (Wave-uniform: scalar branches.)
+  if (wm0 + 64 <= p.m && wn0 + 64 <= p.n) {
+    if (p.ep.u_out) epi_land_read<8 + 16>(land, o[1]);
+    else epi_land_read<8 + 8>(land, o[1]);
+  } else {
+    epi_land_read<8>(land, o[1]);
+  }
+  epi_process<1, true>(p, acc[1][0], o[1], stage, wm0 + 64, wn0, split, pre_bias);
+  epi_settle<true>(o[0]);
+  epi_process<1, true>(p, acc[1][1], o[0], stage, wm0 + 96, wn0, split, pre_bias);
 }
 
 // 128x128 workgroup tile, 4 waves as 2x2
@@ -654,7 +752,8 @@ struct RingMmaBf16 {
 };
 // epilogue operands fetched under the tail of the main loop: 32-row chunks (residual form: all four of R; cross form: x0 and x
 // of the first two), and how many load instructions that is
-template <int EPI> constexpr int kRingEpiChunks = EPI == 2 ? 4 : EPI == 1 ? 2 : 0;
+// (the cross form with x == x0 loads one operand: all four chunks fit the registers the cross form spends on two)
+template <int EPI> constexpr int kRingEpiChunks = EPI == 2 || EPI == kEpiCrossXIsX0 ? 4 : EPI == 1 ? 2 : 0;
 template <int EPI> constexpr int kRingEpiLoads = kRingEpiChunks<EPI> * (EPI == 1 ? 8 : 4);
 // (The accumulator zeroing and the epilogue dispatch stay written out in both kernels: as shared functions, forced inline or
 //  not, they made hipcc reschedule every build of gemm_pp256_kernel -- docs/measurement_log.md, "One ring main loop".)
@@ -926,10 +1025,27 @@ __global__ __launch_bounds__(512) void gemm_pp256_kernel(const GemmParams p, int
 // gemm_pp256_kernel's tile, accumulators and epilogues on the main loop of gemm_ring64.h (the schedule and its derivation are
 // there; gemm_q8.hip's gemm_q8_ring_kernel runs the same loop): a piece is 256 rows x 64 k, the epilogue's operands are
 // requested at the loop's tail point.
-template <int EPI>
+// SCHED (KRS_GEMM_SCHED_* bits, the streaming epilogue builds only; 0 = the reference schedule):
+//   LDS_LANDING  build 1: gemm_epilogue_wave128_land instead of gemm_epilogue_wave128_pre;
+//   STAGGER      The reading it was built on: the 3584 equal tiles of a C3 product start together on 256 CUs and stay in step
+//                for all 14 rounds, every CU streaming its epilogue while no CU needs HBM for a main loop.  Here odd M panels
+//                start half way round their N tiles (gplan::ring_tile_of_slot) and, of the first round (one workgroup per
+//                CU), every other workgroup of an XCD starts half a tile period late, so that the epilogues of half the
+//                CUs fall on the main loops of the other half.  The period is an estimate (a 64-k block of the main loop
+//                at 1.56 us, a 128 KB epilogue stream at 5.2 us: the C3 shapes' own timings); a wrong one costs phase, not
+//                bits, and the wait is bounded by iterations as well as by the clock.
+//                MEASURED NEGATIVE (profiles/gemm_epi_schedule_ab.txt): dx unchanged, the cross form 9 us slower alone and
+//                8 - 17 us slower on top of LDS_LANDING / X_IS_X0 -- the half period is spent and not returned.  Not the
+//                default; kept behind the switch so the reading can be repeated.
+template <int EPI> constexpr int kRingEpiStreams = EPI == 1 ? 4 : EPI == kEpiCrossXIsX0 ? 3 : EPI == 2 ? 2 : 6;
+template <int EPI, int SCHED>
 __global__ __launch_bounds__(512) void gemm_pp64_kernel(const GemmParams p, int nt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TM = 256, TN_ = 256;
+  constexpr bool LAND = (SCHED & KRS_GEMM_SCHED_LDS_LANDING) != 0, STAGGER = (SCHED & KRS_GEMM_SCHED_STAGGER) != 0;
+  static_assert(!LAND || EPI == 1, "only the cross build lands operands in LDS");
+  static_assert(!STAGGER || EPI != 0, "the general build keeps the panel order");
+  static_assert(gplan::kEpiStageBytes + gplan::kEpiLandBytes <= gplan::kRing64Lds, "the landing region lies inside the ring");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 2, wn = wave & 3;
@@ -940,9 +1056,17 @@ __global__ __launch_bounds__(512) void gemm_pp64_kernel(const GemmParams p, int 
   const int split = (int)(slot_id - tslot * p.splits);
   const int64_t m_tile = (tslot / nt) * 8 + xcd;
   if (m_tile * TM >= p.m) return;
-  const int64_t m0 = m_tile * TM, n0 = (tslot % nt) * TN_;
+  // (panel order written out as it always was -- the same numbers as ring_tile_of_slot(tslot, nt, false), which as a call
+  //  made hipcc reallocate the registers of the general build)
+  const int64_t m0 = m_tile * TM, n0 = (STAGGER ? gplan::ring_tile_of_slot(tslot, nt, true).n_tile : tslot % nt) * TN_;
   const int64_t kbeg = (int64_t)split * p.k_per_split;
   const int64_t nb = (min(p.k, kbeg + p.k_per_split) - kbeg) / 64;     // 64-k blocks (the host guarantees >= 3, whole)
+  if constexpr (STAGGER) {
+    if (blockIdx.x < gplan::kCUs && (slot_id & 1)) {
+      const uint64_t half_period = (uint64_t)nb * 78 + kRingEpiStreams<EPI> * 260, t0 = wall_clock64();   // 10 ns ticks
+      for (int i = 0; i < 256 && wall_clock64() - t0 < half_period; ++i) __builtin_amdgcn_s_sleep(16);
+    }
+  }
 
   f32x16 acc[2][2][2];
 #pragma unroll
@@ -955,19 +1079,27 @@ __global__ __launch_bounds__(512) void gemm_pp64_kernel(const GemmParams p, int 
         for (int r = 0; r < 16; ++r) acc[h][i][j][r] = 0.0f;
   constexpr int NPFC = kRingEpiChunks<EPI>;
   EpiOperands opf[4];
-  ring64_main_loop<2, kRingEpiLoads<EPI>>(smem, p, m0, n0, kbeg, nb, lane, wave, RingMmaBf16{acc}, [&]() {
+  // the builds of KRS_GEMM_OPT_EPI_SCHEDULE 1 request the lane's bias values with the epilogue operands, two more loads
+  // under the tail, instead of loading them in every step of the epilogue (epi_process, PREBIAS)
+  constexpr bool PREBIAS = LAND || EPI == kEpiCrossXIsX0;
+  float pre_bias[8];
+  ring64_main_loop<2, kRingEpiLoads<EPI> + (PREBIAS ? 2 : 0)>(smem, p, m0, n0, kbeg, nb, lane, wave, RingMmaBf16{acc}, [&]() {
+    if constexpr (PREBIAS) epi_load_bias(p, n0 + wn * 64, pre_bias);
 #pragma unroll
     for (int c = 0; c < NPFC; ++c) epi_prefetch<EPI>(p, opf[c], m0 + wm * 128 + c * 32, n0 + wn * 64);
   });
   float* stage_f = reinterpret_cast<float*>(smem) + wave * (32 * 68);
-  if constexpr (EPI >= 3) {
+  if constexpr (EPI >= 3 && EPI <= 10) {
     gemm_epilogue_wave128_crossbwd<(EPI == 4 || EPI == 6) ? 1 : (EPI == 7 ? 2 : (EPI >= 8 ? 3 : 0)),
                                    EPI == 3 || EPI == 4 || EPI == 7, EPI < 9, EPI != 9>(
         p, acc, stage_f, m0 + wm * 128, n0 + wn * 64, (m0 >> 8) * 2 + wm);
     return;
   }
-  if constexpr (NPFC > 0)
-    gemm_epilogue_wave128_pre<EPI, NPFC>(p, acc, stage_f, m0 + wm * 128, n0 + wn * 64, split, opf);
+  if constexpr (LAND)
+    gemm_epilogue_wave128_land(p, acc, stage_f, smem + gplan::kEpiStageBytes + wave * gplan::kEpiLandWaveBytes, m0 + wm * 128,
+                               n0 + wn * 64, split, opf, pre_bias);
+  else if constexpr (NPFC > 0)
+    gemm_epilogue_wave128_pre<EPI, NPFC, PREBIAS>(p, acc, stage_f, m0 + wm * 128, n0 + wn * 64, split, opf, pre_bias);
   else
     gemm_epilogue_wave128<EPI>(p, acc, stage_f, m0 + wm * 128, n0 + wn * 64, split);
 }
@@ -1210,6 +1342,19 @@ int gemm_pipe() {
   }
   return g_pipe;
 }
+// Epilogue schedule of gemm_pp64_kernel's streaming builds (krs.h, KRS_GEMM_OPT_EPI_SCHEDULE): 0 = the reference schedule,
+// 1 = LDS landing + the x == x0 build, 2 = stagger, 3 = both.  krs_gemm_set_option / environment KRS_GEMM_EPI_SCHEDULE
+// (read once).  What each measured: docs/measurement_log.md, "Cross GEMM epilogue schedules".
+constexpr int kEpiSchedDefault = 1;      // (the stagger measured no gain alone and a loss with 1: it stays behind the switch)
+int g_epi_sched = -1;
+int gemm_epi_sched() {
+  if (g_epi_sched < 0) {
+    const char* e = getenv("KRS_GEMM_EPI_SCHEDULE");
+    g_epi_sched = e ? atoi(e) : kEpiSchedDefault;
+    if (g_epi_sched < 0 || g_epi_sched > 3) g_epi_sched = kEpiSchedDefault;
+  }
+  return g_epi_sched;
+}
 
 // f(std::integral_constant<int, E>()) for the epilogue number e, First <= e <= Last: a kernel's EPI template argument
 // picked at run time
@@ -1230,6 +1375,11 @@ extern "C" int krs_gemm_set_option(int key, int value) {
   if (key == KRS_GEMM_OPT_PIPELINE) {
     KRS_REQUIRE(value == 0 || value == 4 || value == 5, "krs_gemm_set_option: pipeline must be 0, 4 or 5");
     g_pipe = value;
+    return KRS_OK;
+  }
+  if (key == KRS_GEMM_OPT_EPI_SCHEDULE) {
+    KRS_REQUIRE(value >= -1 && value <= 3, "krs_gemm_set_option: epilogue schedule must be 0, 1, 2, 3 or -1 (the default)");
+    g_epi_sched = value;      // (-1: gemm_epi_sched() reads the environment / the built-in default again)
     return KRS_OK;
   }
   return fail(KRS_ERR_INVALID, "krs_gemm_set_option: unknown key %d", key);
@@ -1264,6 +1414,7 @@ int gemm_plan(const void* a, int64_t lda, int a_is_km, const void* b, int64_t ld
   call.lda = lda; call.ldb = ldb; call.ldc = ldc; call.al_a = al16(a); call.al_b = al16(b); call.al_c = al16(c);
   gplan::set_epilogue(call, ep);
   call.workspace_bytes = workspace_bytes; call.allow_split = allow_split; call.pipe = gemm_pipe(); call.tn128 = tn128;
+  call.epi_sched = gemm_epi_sched();
   pl = gplan::plan_gemm(call);
   if (pl.status == KRS_ERR_WORKSPACE)
     return fail(pl.status, "krs_gemm: split-K needs %zu workspace bytes, got %zu", pl.need, workspace_bytes);
@@ -1277,10 +1428,27 @@ int gemm_launch(const GemmParams& p, const gplan::GemmPlan& pl, int in_dtype, hi
   const krs_gemm_route& rt = pl.route;
   const dim3 grid((unsigned)pl.grid[0], (unsigned)pl.grid[1], (unsigned)pl.grid[2]), block((unsigned)pl.block);
   switch (rt.kernel) {
-    case KRS_GEMM_KERNEL_PP64:
-      return with_epilogue<0, 2>(rt.epilogue, [&](auto E) {
-        return launch_lds<gemm_pp64_kernel<E>>("gemm_pp64_kernel", grid, block, pl.lds, st, p, pl.nt);
-      });
+    case KRS_GEMM_KERNEL_PP64: {
+      // the build the plan's schedule bits name (LDS_LANDING and X_IS_X0 exclude each other and come with build 1 only)
+      constexpr int LAND = KRS_GEMM_SCHED_LDS_LANDING, STAG = KRS_GEMM_SCHED_STAGGER, X0 = kEpiCrossXIsX0;
+      const bool stag = (rt.schedule & STAG) != 0;
+      auto run = [&](auto E, auto S) {
+        return launch_lds<gemm_pp64_kernel<E, S>>("gemm_pp64_kernel", grid, block, pl.lds, st, p, pl.nt);
+      };
+      using std::integral_constant;
+      if (rt.epilogue == 0) return run(integral_constant<int, 0>(), integral_constant<int, 0>());
+      if (rt.epilogue == 2)
+        return stag ? run(integral_constant<int, 2>(), integral_constant<int, STAG>())
+                    : run(integral_constant<int, 2>(), integral_constant<int, 0>());
+      if (rt.schedule & KRS_GEMM_SCHED_X_IS_X0)
+        return stag ? run(integral_constant<int, X0>(), integral_constant<int, STAG>())
+                    : run(integral_constant<int, X0>(), integral_constant<int, 0>());
+      if (rt.schedule & LAND)
+        return stag ? run(integral_constant<int, 1>(), integral_constant<int, LAND | STAG>())
+                    : run(integral_constant<int, 1>(), integral_constant<int, LAND>());
+      return stag ? run(integral_constant<int, 1>(), integral_constant<int, STAG>())
+                  : run(integral_constant<int, 1>(), integral_constant<int, 0>());
+    }
     case KRS_GEMM_KERNEL_PP256:
       return with_epilogue<0, 2>(rt.epilogue, [&](auto E) {
         return launch_lds<gemm_pp256_kernel<false, 4, E>>("gemm_pp256_kernel", grid, block, pl.lds, st, p, 0, pl.nt);
@@ -1419,7 +1587,7 @@ static int cross_bwd(const char* who, bool dense, const void* a, int64_t lda, co
     if (int rc = gemm_plan(a, lda, 0, bt, ldb, 1, g_out, ldg, m, n, k, dtype, dtype, r ? &ep : nullptr, 0, false, call, cb.product))
       return rc;
     gplan::plan_cross_bwd(cb, r != nullptr, ld, al16(x0) && al16(u) && al16(dz) && al16(dx0) && al16(u_upper), dense, store_g,
-                          dx0 != nullptr, dx0_accumulate != 0, u_upper != nullptr);
+                          dx0 != nullptr, dx0_accumulate != 0, u_upper != nullptr, gemm_epi_sched());
   }
   if (plan_only) { *plan_only = cb; return KRS_OK; }
   if (dbias) KRS_REQUIRE(workspace_bytes >= krs_gemm_cross_bwd_workspace_bytes(m, n) && (workspace || m == 0 || n == 0),
@@ -1457,10 +1625,13 @@ static int cross_bwd(const char* who, bool dense, const void* a, int64_t lda, co
   const dim3 grid256((unsigned)pl.grid[0]), block((unsigned)pl.block);
   cb_route = cb.route; cb_epilogue = cb.epilogue;
   const int rc = with_epilogue<3, 10>(cb.epilogue, [&](auto E) {
-    return cb.route == KRS_CROSS_BWD_PP64
-               ? launch_lds<gemm_pp64_kernel<E>>("gemm_pp64_kernel (fused cross backward)", grid256, block, pl.lds, st, p, pl.nt)
-               : launch_lds<gemm_pp256_kernel<false, 4, E>>("gemm_pp256_kernel (fused cross backward)", grid256, block, pl.lds,
-                                                            st, p, 0, pl.nt);
+    if (cb.route == KRS_CROSS_BWD_PP64)
+      return cb.stagger ? launch_lds<gemm_pp64_kernel<E, KRS_GEMM_SCHED_STAGGER>>("gemm_pp64_kernel (fused cross backward)",
+                                                                                  grid256, block, pl.lds, st, p, pl.nt)
+                        : launch_lds<gemm_pp64_kernel<E, 0>>("gemm_pp64_kernel (fused cross backward)", grid256, block, pl.lds,
+                                                             st, p, pl.nt);
+    return launch_lds<gemm_pp256_kernel<false, 4, E>>("gemm_pp256_kernel (fused cross backward)", grid256, block, pl.lds, st,
+                                                      p, 0, pl.nt);
   });
   if (rc != KRS_OK) return rc;
   return dbias ? finish_colsum(p.f_partial, 2 * ceil_div(m, 256), n, dbias, st) : KRS_OK;

@@ -192,16 +192,21 @@ __device__ __forceinline__ void epilogue_store_vec8(const GemmParams& p, int64_t
 struct EpiOperands {
   uint4 ex[4], ex0[4];
 };
+// The cross form of a call whose x IS its x0 (the planner's KRS_GEMM_SCHED_X_IS_X0, gemm_pp64_kernel only): build 1's
+// arithmetic on ONE loaded operand -- ex0 is never touched, so a chunk costs half the registers.
+constexpr int kEpiCrossXIsX0 = 11;
 
 template <int EPI>
 __device__ __forceinline__ void epi_prefetch(const GemmParams& p, EpiOperands& o, int64_t row0, int64_t wn0) {
-  if constexpr (EPI == 1 || EPI == 2) {
+  if constexpr (EPI == 1 || EPI == 2 || EPI == kEpiCrossXIsX0) {
     const int lane = threadIdx.x & 63;
     const int64_t gnc = min(wn0 + (lane & 7) * 8, p.n - 8);
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int64_t gmc = min(row0 + it * 8 + (lane >> 3), p.m - 1);
-      if constexpr (EPI == 1) {
+      if constexpr (EPI == kEpiCrossXIsX0) {
+        o.ex[it] = load8_bf16_nt(p.ep.x, gmc * p.ep.ldx + gnc);
+      } else if constexpr (EPI == 1) {
         o.ex[it] = load8_bf16_nt(p.ep.x, gmc * p.ep.ldx + gnc);
         // (unconditional even when x is x0: a predicated load makes hipcc drain the whole load queue)
         o.ex0[it] = load8_bf16_nt(p.ep.x0, gmc * p.ep.ldx + gnc);
@@ -212,11 +217,26 @@ __device__ __forceinline__ void epi_prefetch(const GemmParams& p, EpiOperands& o
   }
 }
 
+// The lane's eight bias values (columns wn0 + (lane & 7) * 8 .. + 7, the same for every row of the wave's block; the column
+// clamped as epi_prefetch clamps it: a lane beyond n stores nothing), loaded once for epi_process<EPI, true>.  Needs n >= 8
+// and the bias on 16 bytes, which the specialised builds have (ep_vec).  Always TWO load instructions, so that a ring's
+// counted waits can count them: without a bias they read the first 32 bytes of B (any readable address would do) and
+// epi_process never looks at the values.
+__device__ __forceinline__ void epi_load_bias(const GemmParams& p, int64_t wn0, float (&b)[8]) {
+  const float* src = p.ep.bias ? p.ep.bias + min(wn0 + (threadIdx.x & 7) * 8, p.n - 8) : reinterpret_cast<const float*>(p.b);
+  const float4 b0 = *reinterpret_cast<const float4*>(src);
+  const float4 b1 = *reinterpret_cast<const float4*>(src + 4);
+  b[0] = b0.x; b[1] = b0.y; b[2] = b0.z; b[3] = b0.w; b[4] = b1.x; b[5] = b1.y; b[6] = b1.z; b[7] = b1.w;
+}
+
 // acc2: the chunk's two 32x32 accumulator fragments (columns 0..31 / 32..63); `stage`: the wave's
 // private 32 x SST floats of LDS; (row0, wn0): origin of the chunk in C.
-template <int EPI>
+// PREBIAS (cross builds): the lane's eight bias values are in `pre_bias` (epi_load_bias) instead of being loaded here, per
+// eight-row step.  Such a load is the youngest memory operation when it is used, so hipcc waits vmcnt(0) for it: every
+// step then also waits for the operands requested ahead and for the acknowledgement of every earlier store.
+template <int EPI, bool PREBIAS = false>
 __device__ __forceinline__ void epi_process(const GemmParams& p, f32x16 (&acc2)[2], const EpiOperands& o, float* stage,
-                                            int64_t row0, int64_t wn0, int split) {
+                                            int64_t row0, int64_t wn0, int split, const float* pre_bias = nullptr) {
   const int lane = threadIdx.x & 63;
   const int frow = lane & 31;
   const int fhalf = lane >> 5;
@@ -238,12 +258,17 @@ __device__ __forceinline__ void epi_process(const GemmParams& p, f32x16 (&acc2)[
     const float4 v0 = *reinterpret_cast<const float4*>(stage + er * SST + ec);
     const float4 v1 = *reinterpret_cast<const float4*>(stage + er * SST + ec + 4);
     v[0] = v0.x; v[1] = v0.y; v[2] = v0.z; v[3] = v0.w; v[4] = v1.x; v[5] = v1.y; v[6] = v1.z; v[7] = v1.w;
-    if constexpr (EPI == 1) {
+    if constexpr (EPI == 1 || EPI == kEpiCrossXIsX0) {
       if (p.ep.bias) {
-        const float4 b0 = *reinterpret_cast<const float4*>(p.ep.bias + gn);
-        const float4 b1 = *reinterpret_cast<const float4*>(p.ep.bias + gn + 4);
-        v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
-        v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
+        if constexpr (PREBIAS) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) v[q] += pre_bias[q];
+        } else {
+          const float4 b0 = *reinterpret_cast<const float4*>(p.ep.bias + gn);
+          const float4 b1 = *reinterpret_cast<const float4*>(p.ep.bias + gn + 4);
+          v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
+          v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
+        }
       }
       if (p.ep.act != KRS_ACT_NONE) {
 #pragma unroll
@@ -252,7 +277,7 @@ __device__ __forceinline__ void epi_process(const GemmParams& p, f32x16 (&acc2)[
       if (p.ep.u_out) store8_bf16_nt(p.ep.u_out, gm * p.ep.ldu + gn, v);
       float xv[8], x0v[8];
       unpack_bf16x8(o.ex[it], xv);
-      unpack_bf16x8(o.ex0[it], x0v);
+      unpack_bf16x8(EPI == 1 ? o.ex0[it] : o.ex[it], x0v);
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = x0v[q] * (v[q] + p.ep.diag_scale * xv[q]) + xv[q];
       store8_bf16_nt(p.c, gm * p.ldc + gn, v);

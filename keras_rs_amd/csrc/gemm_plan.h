@@ -39,6 +39,24 @@ constexpr int kRowdotMaxN = 8, kRowdotMinK = 32, kRowdotMinM = 1024, kRowdotRows
 constexpr int kSmallkMaxK = 16, kSmallkMaxN = 1024, kSmallkRows = 64, kSmallkMinMN = 1 << 16;   // B [K, N] fp32 in <= 64 KB LDS
 constexpr size_t kRingLds = 4 * 32768, kRing64Lds = 5 * 32768, kGldsLds = 4 * kTile * kRowBytes;   // stages x (A + B)
 constexpr int64_t kMaxGridThreads = 0xffffffffll, kMaxGridYZ = 65535;   // launch limits: threads along x, blocks along y / z
+// The ring's LDS in the epilogue (every slot is dead): eight waves stage 32 x 68 floats of accumulators each from byte 0 on;
+// under KRS_GEMM_SCHED_LDS_LANDING a wave's 32-row chunk of x and of x0 (32 rows x 128 bytes each) lands behind that.
+constexpr size_t kEpiStageBytes = 8 * 32 * 68 * sizeof(float), kEpiLandWaveBytes = 2 * 32 * 128;
+constexpr size_t kEpiLandBytes = 8 * kEpiLandWaveBytes;
+
+// gemm_pp64_kernel's work items.  Workgroup b runs on XCD b % 8 and is that XCD's item b / 8 = tslot * splits + split; tile
+// tslot of an XCD lies in its M panel g = tslot / nt (tile row g * 8 + XCD of C) at N tile j:
+//   panel order   j = tslot % nt: the N tiles of a panel back to back, sharing A in the XCD's L2;
+//   staggered     the same panels, but an odd panel starts half way round: j = (tslot % nt + nt / 2) % nt.
+// Either way tslot -> (g, j) is a bijection onto [0, panels) x [0, nt): a rotation inside each panel (the lattice walk of
+// tests/host/gemm_epi_schedule_check.cpp counts every tile once).  Which workgroup computes a tile changes speed, never bits.
+struct RingTile { int64_t panel; int n_tile; };
+constexpr RingTile ring_tile_of_slot(int64_t tslot, int nt, bool stagger) {
+  const int64_t g = tslot / nt;
+  int j = (int)(tslot - g * nt);
+  if (stagger && (g & 1)) j = j + nt / 2 >= nt ? j + nt / 2 - nt : j + nt / 2;
+  return RingTile{g, j};
+}
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t round_up(int64_t a, int64_t b) { return cdiv(a, b) * b; }
@@ -54,6 +72,8 @@ struct GemmCall {
   bool allow_split = true;      // false: one pass over K (the two-call form of krs_gemm_cross_bwd has no slab workspace)
   int pipe = 4;                 // KRS_GEMM_OPT_PIPELINE: 4 | 5 | 0
   bool tn128 = false;           // development switch KRS_GEMM_TN128: weight gradients on the 128 x 128 gemm_tn_glds_kernel
+  bool x_is_x0 = false;         // the cross epilogue's x IS its x0 (one pointer, one stride: the first layer of a stack)
+  int epi_sched = 0;            // KRS_GEMM_OPT_EPI_SCHEDULE: 0 | 1 | 2 | 3
 };
 
 // which epilogue operands a call brings and how they are aligned (ep NULL: no epilogue); pointer VALUES only
@@ -61,6 +81,7 @@ inline void set_epilogue(GemmCall& c, const krs_gemm_epilogue* ep) {
   if (!ep) return;
   c.has_ep = true; c.act = ep->act; c.bias = ep->bias != nullptr; c.al_bias = al16(ep->bias);
   c.x0 = ep->x0 != nullptr; c.al_x0 = al16(ep->x0); c.al_x = al16(ep->x); c.ldx = ep->ldx;
+  c.x_is_x0 = c.x0 && ep->x == ep->x0;     // (x0 and x share ldx)
   c.u_out = ep->u_out != nullptr; c.al_u = al16(ep->u_out); c.ldu = ep->ldu;
   c.r = ep->r != nullptr; c.al_r = al16(ep->r); c.ldr = ep->ldr;
 }
@@ -192,6 +213,12 @@ inline GemmPlan plan_gemm(const GemmCall& c) {
       if (c.x0 && !c.r) rt.epilogue = 1;
       else if (c.r && !c.x0 && !c.bias && c.act == KRS_ACT_NONE) rt.epilogue = 2;
     }
+    // the epilogue schedules of gemm_pp64_kernel's streaming builds (KRS_GEMM_OPT_EPI_SCHEDULE); the landing region lies
+    // inside the ring's LDS (kEpiStageBytes + kEpiLandBytes <= kRing64Lds, asserted next to the kernel and by the lattice walk)
+    if (rt.kernel == KRS_GEMM_KERNEL_PP64 && rt.epilogue != 0) {
+      if ((c.epi_sched & 1) && rt.epilogue == 1) rt.schedule |= c.x_is_x0 ? KRS_GEMM_SCHED_X_IS_X0 : KRS_GEMM_SCHED_LDS_LANDING;
+      if (c.epi_sched & 2) rt.schedule |= KRS_GEMM_SCHED_STAGGER;
+    }
     const bool vec4 = !c.has_ep && c.out_dtype == KRS_F32 && n % 4 == 0 && c.ldc % 4 == 0 && c.al_c;
     if (s > 1) rt.reduce = vec4 ? KRS_GEMM_REDUCE_VEC4 : (rt.ep_vec ? KRS_GEMM_REDUCE_VEC8 : KRS_GEMM_REDUCE_SCALAR);
   } else if (tn && thin_shape(m, n, k)) {
@@ -223,6 +250,7 @@ inline GemmPlan plan_gemm(const GemmCall& c) {
 
 struct CrossBwdPlan {
   int route = KRS_CROSS_BWD_NONE, epilogue = 0;   // KRS_CROSS_BWD_*; the fused epilogue number 3 .. 10, else 0
+  bool stagger = false;                           // fused on the 64-k ring under KRS_GEMM_OPT_EPI_SCHEDULE 2 / 3
   GemmPlan product;                               // fused: grid, LDS bytes and nt of the ring launch
 };
 
@@ -231,7 +259,7 @@ struct CrossBwdPlan {
 // Fused exactly where plan_gemm gave that product a ring kernel -- the same predicate, not a restatement -- and every
 // stream is vector-accessible; the ring (64-k under pipeline 4, 32-k under 5) is the one plan_gemm named.
 inline void plan_cross_bwd(CrossBwdPlan& cb, bool has_r, int64_t ld, bool al_streams, bool dense, bool store_g, bool has_dx0,
-                           bool dx0_accumulate, bool has_u_upper) {
+                           bool dx0_accumulate, bool has_u_upper, int epi_sched = 0) {
   const krs_gemm_route& rt = cb.product.route;
   cb.route = rt.kernel == KRS_GEMM_KERNEL_PP64 ? KRS_CROSS_BWD_PP64 : KRS_CROSS_BWD_PP256;
   cb.epilogue = 0;
@@ -242,6 +270,7 @@ inline void plan_cross_bwd(CrossBwdPlan& cb, bool has_r, int64_t ld, bool al_str
   else if (has_u_upper) cb.epilogue = 7;
   else if (has_r) cb.epilogue = dx0_accumulate ? 4 : 3;
   else cb.epilogue = !has_dx0 ? 8 : (dx0_accumulate ? 6 : 5);
+  cb.stagger = cb.route == KRS_CROSS_BWD_PP64 && (epi_sched & 2);
 }
 
 }  // namespace gplan

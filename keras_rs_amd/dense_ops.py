@@ -235,6 +235,30 @@ def last_gemm_route() -> dict:
     return _route_dict(rt)
 
 
+def _schedule_set(rt) -> frozenset:
+    names = ((L.GEMM_SCHED_LDS_LANDING, "lds_landing"), (L.GEMM_SCHED_STAGGER, "stagger"), (L.GEMM_SCHED_X_IS_X0, "x_is_x0"))
+    return frozenset(name for bit, name in names if rt.schedule & bit)
+
+
+def last_gemm_schedule() -> frozenset:
+    """The epilogue schedule of the calling thread's last krs_gemm (the `schedule` field of krs_gemm_last_route): a subset
+    of {"lds_landing", "stagger", "x_is_x0"}, empty off gemm_pp64_kernel's cross / residual builds and under
+    KRS_GEMM_OPT_EPI_SCHEDULE 0.  Kept out of last_gemm_route(): the record of WHERE a product ran does not depend on
+    the schedule option."""
+    rt = L.GemmRoute()
+    L.lib().krs_gemm_last_route(C.byref(rt))
+    return _schedule_set(rt)
+
+
+def plan_gemm_schedule(a, lda, a_is_km, b, ldb, b_is_nk, c, ldc, m, n, k, in_dtype, out_dtype, epilogue=None,
+                       workspace_bytes=0) -> frozenset:
+    """last_gemm_schedule() of the call plan_gemm_route() describes, from krs_gemm_plan_route (no GPU)."""
+    rt = L.GemmRoute()
+    L.lib().krs_gemm_plan_route(a, lda, int(a_is_km), b, ldb, int(b_is_nk), c, ldc, m, n, k, in_dtype, out_dtype,
+                                C.byref(epilogue) if epilogue is not None else None, int(workspace_bytes), C.byref(rt))
+    return _schedule_set(rt)
+
+
 def plan_gemm_route(a, lda, a_is_km, b, ldb, b_is_nk, c, ldc, m, n, k, in_dtype, out_dtype, epilogue=None,
                     workspace_bytes=0):
     """(status, route) a krs_gemm with these arguments would have (krs_gemm_plan_route; needs no GPU): a, b, c are

@@ -42,6 +42,8 @@ cases = [
     ("fwd1  h = x U        (K=3456,N=512)", lambda: D.gemm(x, Ut, b_is_nk=True), F, (B * d + B * p) * 2),
     ("fwd2  y = cross(hV)  (K=512,N=3456)", lambda: D.gemm(h, Vt, b_is_nk=True, bias=bias, x0=x0, x=x, want_u=True), F,
      (B * p + 4 * B * d) * 2),
+    ("fwd2' y = cross(hV), x is x0 (first layer)", lambda: D.gemm(h, Vt, b_is_nk=True, bias=bias, x0=x0, x=x0, want_u=True), F,
+     (B * p + 3 * B * d) * 2),
     ("bwd   elementwise dz, dx0", lambda: D.cross_epilogue_bwd(gy, u, x0, x, 0.0, want_dxd=False), 0, 6 * B * d * 2),
     ("dK    = h^T dz       (split-K)", lambda: D.gemm(h, dz, a_is_km=True, out_dtype=torch.float32), F, (B * p + B * d) * 2),
     ("dh    = dz V^T       (K=3456,N=512)", lambda: D.gemm(dz, V, b_is_nk=True), F, (B * d + B * p) * 2),

@@ -1,16 +1,24 @@
 """torch.autograd.Function wrappers: one per op of the hot path, each calling the
 HIP kernels through the C ABI (embedding_ops / dense_ops).  Gradients follow
 SURVEY.md section 8 rows a4 (embedding), a9 (FeatureCross) and a11 (DotInteraction).
+The relays and records the dense backward's hand-offs pass around are in relays.py, the opt-in second stream for the
+cross layers' weight gradients in wgrad_side.py; the switches of both stay here and are read here, at call time.
 """
 
 from __future__ import annotations
 
+import os
 import weakref
+from typing import NamedTuple
 
 import torch
 
 from keras_rs_amd import _lib as L
 from keras_rs_amd import dense_ops as D
+from keras_rs_amd import wgrad_side
+from keras_rs_amd.relays import (CrossLower, DenseActRelay, DenseLower, Dx0Relay, Handoff, SlabGradRelay,  # noqa: F401
+                                 graph_task)
+from keras_rs_amd.wgrad_side import wgrad_stream_sync  # noqa: F401  (dp.GradAllReduce and callers know it under this name)
 
 
 _SIDE_STREAMS: dict = {}
@@ -24,69 +32,30 @@ def _side_stream(device) -> "torch.cuda.Stream":
     return st
 
 
-# Weight-gradient GEMMs of the cross layers on a second stream (see CrossLayerFn.backward): they are off the critical
-# path, and started behind a layer's dx product they run beside the HBM-bound dz / dx0 pass of the layer below (or the
-# DotInteraction gradient and the table update behind the bottom layer) -- an elementwise pass and a ring GEMM do overlap
-# a little on this part (scripts/exp/overlap_probe2.py: 563 + 271 us apart, 707 together), two GEMMs or a GEMM and the
-# table update do not.  Measured in the step: 10.31-10.48 -> 10.20-10.29 ms.  Deferring all six to the table update was
-# slower (10.49).
-# OPT-IN since round 4 (`set_wgrad_side_stream(True)` or KRS_WGRAD_SIDE=1), and no longer used by bench.py / the example:
-# with the elementwise backward inside the data-gradient products (krs_gemm_cross_bwd) the pass these GEMMs overlapped
-# with is gone -- beside the next layer's ring GEMMs they measured 10.26 against 10.13-10.18 ms
-# (profiles/archive/r4k_wgrad_side_ab.txt).  Also: a gradient produced on a private stream is only safe when NOTHING but the end-of-backward rejoin reads
-# it, and a backward function cannot see every reader -- a second gradient contribution to the same weight (a manual
-# L2 term, a weight shared by two layers) is summed by autograd's input buffer on the main stream with nothing ordering
-# it behind this stream.  The owner of the training step can promise that; a library default cannot.  What the
-# function can see it still checks (`_wgrad_side_ok`): an accumulated .grad, tensor hooks, foreign post-accumulate
-# hooks, a regulariser on the weight (layers.base marks it: its penalty is a second contribution), the weight used by
-# more than one pending CrossLayerFn.
-WGRAD_SIDE_STREAM = bool(int(__import__("os").environ.get("KRS_WGRAD_SIDE", "0")))
+def _switch(value: str) -> bool:
+    """An on / off switch from its environment string, "0" or "1"."""
+    return bool(int(value))
+
+
+# The cross layers' weight-gradient GEMMs on a second stream: opt-in, see wgrad_side.py (`set_wgrad_side_stream(True)` or
+# KRS_WGRAD_SIDE=1); taken from WGRAD_SIDE_MIN_ROWS rows on.
+WGRAD_SIDE_STREAM = _switch(os.environ.get("KRS_WGRAD_SIDE", "0"))
 WGRAD_SIDE_MIN_ROWS = 32768
-_WGRAD_STREAMS: dict = {}
-_WGRAD_SYNC_QUEUED: set = set()
+# Round 4: dx = dh U^T + g of a layer IS dL/dy of the layer below it in the stack, whose elementwise backward starts
+# by re-reading it.  krs_gemm_cross_bwd does that pass in the product's epilogue (one 453 MB stream less per layer at C3,
+# and the other streams at the epilogue's rate): environment KRS_FUSE_CROSS_BWD=0 switches it off (A/B).
+FUSE_CROSS_BWD = _switch(os.environ.get("KRS_FUSE_CROSS_BWD", "1"))
+# ... and the TOP layer's own term of dL/dx0 is computed in that epilogue too (it writes dz only): KRS_FUSE_TOP_DX0=0 for A/B
+FUSE_TOP_DX0 = _switch(os.environ.get("KRS_FUSE_TOP_DX0", "1"))
+# development switch: 0 = every Dense layer runs its own activation backward (krs_dense_act_bwd), as before round 6
+FUSE_DENSE_BWD = _switch(os.environ.get("KRS_FUSE_DENSE_BWD", "1"))
 
 
 def set_wgrad_side_stream(on: bool) -> bool:
-    """Switch the second stream for the cross layers' weight gradients on or off (see above); returns the old value."""
+    """Switch the second stream for the cross layers' weight gradients on or off (wgrad_side.py); returns the old value."""
     global WGRAD_SIDE_STREAM
     old, WGRAD_SIDE_STREAM = WGRAD_SIDE_STREAM, bool(on)
     return old
-
-
-def _wgrad_stream(device) -> "torch.cuda.Stream":
-    key = str(device)
-    st = _WGRAD_STREAMS.get(key)
-    if st is None:
-        st = _WGRAD_STREAMS[key] = torch.cuda.Stream(device=device)
-    return st
-
-
-def _wgrad_side_ok(w) -> bool:
-    """May this weight's gradient come off the second stream?  Only when nothing reads it before the end of the backward
-    pass: no gradient to accumulate into yet (the first accumulation is an assignment, a later one is an add kernel on
-    the main stream), no tensor hooks, no post-accumulate hooks other than ones that rejoin the stream themselves
-    (dp.GradAllReduce marks its parameters), no second consumer this function knows of (a regulariser attached by
-    `Layer.add_weight`, a second CrossLayerFn whose backward is still pending)."""
-    if w is None:
-        return True
-    if w.grad is not None or w._backward_hooks:
-        return False
-    if getattr(w, "_krs_has_regularizer", False) or getattr(w, "_krs_pending_cross", 1) != 1:
-        return False
-    hooks = getattr(w, "_post_accumulate_grad_hooks", None)
-    return not hooks or bool(getattr(w, "_krs_hooks_rejoin_wgrad_stream", False))
-
-
-def _release_pending_cross(w_refs, counted) -> None:
-    """Gives back one pending use of each weight of a CrossLayerFn call, once: from its backward, or from the finalizer
-    of its graph node when the graph is dropped without a backward pass."""
-    if not counted[0]:
-        return
-    counted[0] = False
-    for r in w_refs:
-        w = r()
-        if w is not None:
-            w._krs_pending_cross = max(0, getattr(w, "_krs_pending_cross", 1) - 1)
 
 
 def _release_plan_ws(bags_ref, owns) -> None:
@@ -98,29 +67,6 @@ def _release_plan_ws(bags_ref, owns) -> None:
     bags = bags_ref()
     if bags is not None:
         bags._plan_ws_busy = False
-
-
-def wgrad_stream_sync() -> None:
-    """The current stream waits for the weight-gradient stream(s): before anything reads those gradients (the end of
-    the backward pass does it by itself; dp.GradAllReduce calls it before it reduces a gradient)."""
-    for st in _WGRAD_STREAMS.values():
-        torch.cuda.current_stream(st.device).wait_stream(st)
-
-
-def _queue_wgrad_sync(task: int) -> None:
-    """Once per backward pass: rejoin the main stream when the graph task ends."""
-    if task in _WGRAD_SYNC_QUEUED:
-        return
-    if task == -1:          # not inside a backward pass (a direct call): rejoin at once
-        wgrad_stream_sync()
-        return
-    _WGRAD_SYNC_QUEUED.add(task)
-
-    def done():
-        _WGRAD_SYNC_QUEUED.discard(task)
-        wgrad_stream_sync()
-
-    torch.autograd.Variable._execution_engine.queue_callback(done)
 
 
 def _split_columns(out: torch.Tensor, n: int, dim: int, lead: int = 0):
@@ -157,84 +103,21 @@ def _gather_feature_grads(grads, batch: int, dim: int, dtype, device):
     return torch.cat(parts, dim=1)
 
 
-class Dx0Relay:
-    """Carries dL/dx0 down a stack of cross layers that share x0 (`xl = layer(x0, xl)` repeated,
-    examples/ml_perf/model.py:332-336).  Every layer of the stack contributes a [B, d] term to dL/dx0;
-    left to autograd these are summed by separate elementwise adds (1.4 GB of traffic each at C3).
-    Instead the layer whose backward runs first writes its term into a buffer and leaves it here, on the
-    relay it shares with the layer that produced its `x`; that layer's backward -- which autograd is bound
-    to run next on this path, since it is handed dL/dx -- accumulates into the buffer inside its
-    elementwise kernel (`dx0_accumulate` of krs_cross_epilogue_bwd) and passes it on, and the bottom layer
-    of the stack returns the total.  `task` is the autograd graph-task id of the pass that filled `buf`:
-    a buffer left over from another backward pass is ignored."""
-
-    __slots__ = ("x0", "buf", "task", "lower", "fused")
-
-    def __init__(self, x0: torch.Tensor):
-        self.x0, self.buf, self.task = x0, None, -1
-        # lower: what the consumer of y needs to run THIS layer's elementwise backward inside its own data-gradient
-        #   product (krs_gemm_cross_bwd): (u, act, diag_scale, has_bias, x_is_x0, x0 in the compute dtype, (relay of the
-        #   layer that produced this layer's x | None, dtype of that x)), left by this layer's forward;
-        # fused: (G, version of G, dz, dbias, task, deferred) left by that consumer's backward when it did so -- `buf` then
-        #   already holds this layer's term of dL/dx0 as well, unless `deferred`: then this layer's own data-gradient
-        #   product computes it (u_upper) and no matrix exists yet.
-        self.lower, self.fused = None, None
-
-    def matches(self, x0: torch.Tensor) -> bool:
-        a = self.x0
-        return (a.data_ptr() == x0.data_ptr() and a.shape == x0.shape and a.stride() == x0.stride()
-                and a.dtype == x0.dtype and a._version == x0._version)
-
-
-class SlabGradRelay:
-    """Lets the gradient of DotInteraction join the gradient of the concat of the same features inside the
-    DotInteraction backward kernel instead of in a separate 1.4 GB add.  `layers.concat_features([dense,
-    *embeddings])` returns the lookup slab itself, so the gradient of the concat IS the gradient of the slab: its
-    backward (SlabFillFn) leaves that matrix here; when DotInteraction's backward runs later in the same pass --
-    it does whenever the interaction was called before the concat, as in a DLRM forward -- and its trailing
-    inputs are exactly the slab's feature views, it adds their gradients into the matrix
-    (krs_dot_interaction_bwd_accumulate) and returns no gradient for them.  The leading inputs (the bottom-MLP
-    output) keep their ordinary gradient tensors, so whatever else consumes them is unaffected.  Not used when
-    the concat result is still referenced and retains its gradient or has hooks (its .grad would show the joined
-    value), nor when one of the slab's feature views does (it would see no gradient from the interaction), nor once
-    the slab has a second consumer (a second concat of the same features).  Known limit: a gradient of the concat
-    result CAPTURED by torch.autograd.grad(..., inputs=[concat_out]) is the very tensor the interaction adds into,
-    so it shows the joined value (the engine exposes no way to see a capture from inside a backward)."""
-
-    __slots__ = ("buf", "task", "out_ref", "disabled")
-    joined = 0   # times the in-kernel path was taken (read by the tests)
-
-    def __init__(self):
-        self.buf, self.task, self.out_ref = None, -1, None
-        # set when the slab got a second consumer (a second concat of the same features): autograd then sums the two
-        # gradients of the slab in a buffer of its own, and an in-place add into the first one could be lost
-        self.disabled = False
-
-
-# Round 4: dx = dh U^T + g of a layer IS dL/dy of the layer below it in the stack, whose elementwise backward starts
-# by re-reading it.  krs_gemm_cross_bwd does that pass in the product's epilogue (one 453 MB stream less per layer at C3,
-# and the other streams at the epilogue's rate): environment KRS_FUSE_CROSS_BWD=0 switches it off (A/B).
-FUSE_CROSS_BWD = bool(int(__import__("os").environ.get("KRS_FUSE_CROSS_BWD", "1")))
-# ... and the TOP layer's own term of dL/dx0 is computed in that epilogue too (it writes dz only): KRS_FUSE_TOP_DX0=0 for A/B
-FUSE_TOP_DX0 = bool(int(__import__("os").environ.get("KRS_FUSE_TOP_DX0", "1")))
-
-
 def _fusable_below(up, a, x_dtype, task) -> bool:
     """May the product `a @ Bt^T` run the elementwise backward of the cross layer behind relay `up` in its epilogue?"""
     low = up.lower if up is not None else None
-    return not (low is None or task == -1 or not FUSE_CROSS_BWD or low[2] != 0.0 or a.dtype != torch.bfloat16
+    return not (low is None or task == -1 or not FUSE_CROSS_BWD or low.diag_scale != 0.0 or a.dtype != torch.bfloat16
                 or x_dtype != a.dtype       # (the product is handed to autograd as it is: a cast would be a different tensor)
-                or low[5].dtype != a.dtype or (up.buf is not None and up.task == task))
+                or low.x0c.dtype != a.dtype or (up.buf is not None and up.task == task))
 
 
 def _dense_fusable_below(rel, dz, x_dtype, task) -> bool:
     """May the product `dz @ K^T` run the activation backward of the Dense layer behind relay `rel` in its epilogue?"""
     if rel is None or rel.lower is None or not FUSE_DENSE_BWD or task == -1 or x_dtype != dz.dtype:
         return False
-    act_low, bias_low = rel.lower
-    if act_low == L.ACT_NONE and not bias_low:
+    if rel.lower.act == L.ACT_NONE and not rel.lower.has_bias:
         return False            # (nothing to do below: a plain product)
-    if rel.fused is not None and rel.fused[4] == task:
+    if rel.fused is not None and rel.fused.task == task:
         return False            # (another consumer of that output already did it in this pass)
     out = rel.out_ref() if rel.out_ref is not None else None
     # (the output keeps its .grad: the launches of the unfused pass, so that every gradient of the step matches that pass
@@ -242,27 +125,124 @@ def _dense_fusable_below(rel, dz, x_dtype, task) -> bool:
     return out is None or not out.retains_grad
 
 
+class _CrossMeta(NamedTuple):
+    diag_scale: float
+    act: int
+    x_is_x0: bool
+    low_rank: bool
+    has_bias: bool
+    x0_dtype: torch.dtype
+    x_dtype: torch.dtype
+    down_dtype: torch.dtype | None
+    kernel_dtype: torch.dtype
+
+
+def _take_handed_down(rin, x0c, task):
+    """Empties the relay a consumer of y may have filled and returns what it left during THIS backward pass:
+    (incoming, extra, handoff) -- dL/dx0 of the layers above as a buffer this layer can accumulate into, or (`extra`) as
+    one it can only add; the Handoff of a consumer that ran this layer's elementwise backward (not yet checked)."""
+    if rin is None:
+        return None, None, None
+    handoff, rin.fused = rin.fused, None
+    incoming, extra = None, None
+    if rin.buf is not None:
+        if rin.task == task and task != -1:
+            if rin.buf.dtype == x0c.dtype and rin.buf.shape == x0c.shape and rin.buf.is_contiguous():
+                incoming = rin.buf
+            else:
+                extra = rin.buf
+        rin.buf = None
+    return incoming, extra, handoff
+
+
+def _cross_elementwise(ctx, saved, g, task, incoming, extra, handoff):
+    """The elementwise part of a cross layer's backward in one of four forms.  Returns (dz, dx0, dxd, dbias, defer_dx0);
+    defer_dx0: no dL/dx0 exists yet, this layer's term g * u joins it inside its data-gradient product (u_upper)."""
+    x0c, xc, _, u, _, _ = saved
+    m = ctx.meta
+    same, diag, act = m.x_is_x0, m.diag_scale, m.act
+    # (in both uses of is_gradient below g has been through .to(x0c.dtype).contiguous() and G is a fresh contiguous
+    #  matrix of that dtype: the stride and dtype it compares add nothing to pointer, shape and version here)
+    if handoff is not None and handoff.deferred:
+        # deferred: the consumer (a Dense layer) ran this layer's elementwise backward but left its term of dL/dx0 to
+        # THIS layer's data-gradient product (u_upper).  Anything that is not the plain case -- another consumer's
+        # buffer, a summed gradient, the layer below no longer fusable -- redoes this layer from g in the forms below.
+        if not (incoming is None and extra is None and handoff.is_gradient(g, task)
+                and _fusable_below(ctx.relay_up, g, m.x_dtype, task)):
+            handoff = None
+    elif handoff is not None and (incoming is None or handoff.task != task):
+        handoff = None
+    if handoff is not None and handoff.deferred:
+        return handoff.dz, None, None, handoff.dbias, True
+    if handoff is not None:
+        # The consumer of y ran this layer's elementwise backward inside its data-gradient product
+        # (krs_gemm_cross_bwd): `incoming` already holds this layer's term, dz and dbias are done.  That is only
+        # right when its G is ALL of dL/dy -- the very tensor autograd hands over, untouched.  If y had another
+        # consumer the engine summed their gradients (a new tensor, or in place: the version moves): the difference
+        # goes through the elementwise kernel (linear in g), dz and dbias are redone.
+        if handoff.is_gradient(g, task):
+            return handoff.dz, incoming, (incoming if same else None), handoff.dbias, False
+        delta = (g.float() - handoff.g.float()).to(g.dtype)
+        _, dx0, _, _ = D.cross_epilogue_bwd(delta, u, x0c, xc, diag, act=act, want_du=False, want_dxd=False,
+                                            want_dbias=False, fold_direct=same, dx0_into=incoming)
+        dz, _, _, dbias = D.cross_epilogue_bwd(g, u, x0c, xc, diag, act=act, want_dxd=False,
+                                               want_dbias=m.has_bias, want_dx0=False)
+        return dz, dx0, (dx0 if same else None), dbias, False
+    if (incoming is None and extra is None and not same and m.low_rank and not diag and FUSE_TOP_DX0
+            and _fusable_below(ctx.relay_up, g, m.x_dtype, task)):
+        # The TOP layer of a stack (nothing above it left a dL/dx0) whose data-gradient product is going to run the
+        # layer below's elementwise backward: its own term g * u is computed THERE (g is that product's residual, already
+        # in registers), so this pass writes dz only -- three [B, d] streams instead of five, and no matrix for dL/dx0 is
+        # written here and read back there.
+        dz, _, dxd, dbias = D.cross_epilogue_bwd(g, u if act != L.ACT_NONE else None, x0c, xc, diag, act=act,
+                                                 want_dxd=False, want_dbias=m.has_bias, want_dx0=False)
+        return dz, None, dxd, dbias, True
+    # x is x0 (the first layer of a stack): both halves of dL/dx0 go through one buffer, which
+    # the data-gradient GEMM then takes as its residual -- no separate add.
+    dz, dx0, dxd, dbias = D.cross_epilogue_bwd(g, u, x0c, xc, diag, act=act, want_dxd=bool(diag) and not same,
+                                               want_dbias=m.has_bias, fold_direct=same, dx0_into=incoming)
+    return dz, dx0, dxd, dbias, False
+
+
 def _dx_product(ctx, dh, dc, direct, dx0, x0c, task, u_own=None):
     """dx = dh U^T + direct.  When x was produced by a cross layer on the same x0 (ctx.relay_up) whose elementwise
     backward can ride in this product's epilogue, it does: that layer's dz / dbias and its term of dL/dx0 (added into
     this layer's dx0 buffer) are left on its relay.  Returns (dx, dx0).
-    dx0 None + u_own (the TOP layer of a stack, see CrossLayerFn.backward): this layer wrote no dL/dx0 of its own; its term
-    direct * u_own starts the matrix inside the fused epilogue."""
+    dx0 None + u_own (the TOP layer of a stack, see _cross_elementwise): this layer wrote no dL/dx0 of its own -- it chose
+    that because the layer below is fusable -- and its term direct * u_own starts the matrix inside the fused epilogue."""
     up = ctx.relay_up
-    if dx0 is None:
-        u_low, act_low, _, bias_low, same_low = up.lower[:5]
-        dx, dz_low, dx0, db_low = D.gemm_cross_bwd(dh, dc, direct, x0c, u_low, act=act_low, want_dbias=bias_low,
-                                                   fold_direct=same_low, u_upper=u_own)
-        up.fused = (dx, dx._version, dz_low, db_low, task, False)
-        return dx, dx0
-    if not _fusable_below(up, dh, ctx.meta[6], task) or not dx0.is_contiguous() or dx0.dtype != dh.dtype:
+    if dx0 is not None and (not _fusable_below(up, dh, ctx.meta.x_dtype, task) or not dx0.is_contiguous()
+                            or dx0.dtype != dh.dtype):
         dx, _ = D.gemm(dh, dc, b_is_nk=True, r=direct, beta=1.0)
         return dx, dx0
-    u_low, act_low, _, bias_low, same_low = up.lower[:5]
-    dx, dz_low, dx0, db_low = D.gemm_cross_bwd(dh, dc, direct, x0c, u_low, act=act_low, dx0_into=dx0,
-                                               want_dbias=bias_low, fold_direct=same_low)
-    up.fused = (dx, dx._version, dz_low, db_low, task, False)
+    low = up.lower
+    dx, dz_low, dx0, db_low = D.gemm_cross_bwd(dh, dc, direct, x0c, low.u, act=low.act, dx0_into=dx0,
+                                               want_dbias=low.has_bias, fold_direct=low.x_is_x0, u_upper=u_own)
+    up.fused = Handoff(dx, dx._version, dz_low, db_low, task)
     return dx, dx0
+
+
+def _cross_products(ctx, saved, dz, direct, dx0, u_own, task):
+    """The data- and weight-gradient products of a cross layer.  Returns (dx, dx0, dK, dU | None)."""
+    x0c, xc, h, _, dc, kc = saved
+    m = ctx.meta
+    side = wgrad_side.may_use(ctx.uses, task, dz, enabled=m.low_rank and WGRAD_SIDE_STREAM, min_rows=WGRAD_SIDE_MIN_ROWS)
+    if not m.low_rank:
+        dk, _ = D.gemm(xc, dz, a_is_km=True, out_dtype=torch.float32)      # dK = x^T dz     [d, d]
+        dx, _ = D.gemm(dz, kc, b_is_nk=True, r=direct, beta=1.0)           # dx = dz K^T + direct
+        return dx, dx0, dk, None
+    if side:
+        # Data-gradient path first; the two weight gradients (off the critical path: only the optimizer reads them)
+        # go to the second stream, which starts when dx is done
+        dh, _ = D.gemm(dz, kc, b_is_nk=True)                               # dh = dz K^T     [B, p]
+        dx, dx0 = _dx_product(ctx, dh, dc, direct, dx0, x0c, task, u_own)  # dx = dh U^T + direct
+        dk, dd = wgrad_side.weight_grads(h, dz, xc, dh, m.kernel_dtype, m.down_dtype, task)
+        return dx, dx0, dk, dd
+    dk, _ = D.gemm(h, dz, a_is_km=True, out_dtype=torch.float32)           # dK = h^T dz     [p, d]
+    dh, _ = D.gemm(dz, kc, b_is_nk=True)                                   # dh = dz K^T     [B, p]
+    dd, _ = D.gemm(xc, dh, a_is_km=True, out_dtype=torch.float32)          # dU = x^T dh     [d, p]
+    dx, dx0 = _dx_product(ctx, dh, dc, direct, dx0, x0c, task, u_own)      # dx = dh U^T + direct
+    return dx, dx0, dk, dd
 
 
 class CrossLayerFn(torch.autograd.Function):
@@ -294,148 +274,35 @@ class CrossLayerFn(torch.autograd.Function):
         y, u = D.gemm(h, kct, b_is_nk=True, bias=bias, act=act, diag_scale=diag_scale,
                       x0=x0c, x=xc, want_u=True)
         ctx.save_for_backward(x0c, xc, h if down is not None else None, u, dc, kc)
-        ctx.meta = (diag_scale, act, same, down is not None, bias is not None,
-                    x0.dtype, x.dtype, None if down is None else down.dtype, kernel.dtype)
+        ctx.meta = _CrossMeta(diag_scale, act, same, down is not None, bias is not None,
+                              x0.dtype, x.dtype, None if down is None else down.dtype, kernel.dtype)
         ctx.relay_in = relay_in
         both = ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
         ctx.relay_up = relay_up if (relay_up is not None and not same and both and relay_up.matches(x0)) else None
         if relay_in is not None and FUSE_CROSS_BWD and down is not None:
-            relay_in.lower = (u, act, float(diag_scale or 0.0), bias is not None, same, x0c, (ctx.relay_up, x.dtype))
-        ctx.w_refs = tuple(weakref.ref(w) for w in (down, kernel) if w is not None)
-        # pending uses of each weight (a weight shared by two layer calls gets two gradient contributions)
-        # (the count is given back by the backward -- or, when no backward ever runs on this graph (a grad-enabled
-        #  validation pass, an exception, a discarded output), by the finalizer of the graph node: a count left above one
-        #  would keep the weight off the second stream for good, silently)
-        ctx.counted = [any(ctx.needs_input_grad[i] for i in (2, 3))]
-        if ctx.counted[0]:
-            for w in (down, kernel):
-                if w is not None:
-                    w._krs_pending_cross = getattr(w, "_krs_pending_cross", 0) + 1
-            weakref.finalize(ctx, _release_pending_cross, ctx.w_refs, ctx.counted)
+            relay_in.lower = CrossLower(u, act, float(diag_scale or 0.0), bias is not None, same, x0c, ctx.relay_up, x.dtype)
+        ctx.uses = wgrad_side.PendingUses(ctx, (down, kernel), any(ctx.needs_input_grad[i] for i in (2, 3)))
         return y
 
     @staticmethod
     def backward(ctx, g):
-        x0c, xc, h, u, dc, kc = ctx.saved_tensors
-        diag, act, same, low_rank, has_bias, x0_dt, x_dt, down_dt, k_dt = ctx.meta
+        saved = ctx.saved_tensors
+        x0c, _, _, u, _, _ = saved
+        m = ctx.meta
+        same = m.x_is_x0
         g = g.to(x0c.dtype).contiguous()
-        need_dxd = bool(diag) and not same
-        task = torch._C._current_graph_task_id()
+        task = graph_task()
         # dL/dx0 of the layers above, left by the consumer of y during this backward pass
-        incoming, extra = None, None
-        rin = ctx.relay_in
-        fused = None
-        if rin is not None:
-            fused, rin.fused = rin.fused, None
-        if rin is not None and rin.buf is not None:
-            if rin.task == task and task != -1:
-                if rin.buf.dtype == x0c.dtype and rin.buf.shape == x0c.shape and rin.buf.is_contiguous():
-                    incoming = rin.buf
-                else:
-                    extra = rin.buf
-            rin.buf = None
-        if fused is not None and fused[5]:
-            # deferred: the consumer (a Dense layer) ran this layer's elementwise backward but left its term of dL/dx0 to
-            # THIS layer's data-gradient product (u_upper).  Anything that is not the plain case -- another consumer's
-            # buffer, a summed gradient, the layer below no longer fusable -- redoes this layer from g in the branches below.
-            if not (incoming is None and extra is None and fused[4] == task and g.data_ptr() == fused[0].data_ptr()
-                    and g.shape == fused[0].shape and g._version == fused[1]
-                    and _fusable_below(ctx.relay_up, g, x_dt, task)):
-                fused = None
-        elif fused is not None and (incoming is None or fused[4] != task):
-            fused = None
-        defer_dx0 = False
-        if fused is not None and fused[5]:
-            dz, dbias = fused[2], fused[3]
-            dx0, dxd, defer_dx0 = None, None, True
-        elif fused is not None:
-            # The consumer of y ran this layer's elementwise backward inside its data-gradient product
-            # (krs_gemm_cross_bwd): `incoming` already holds this layer's term, dz and dbias are done.  That is only
-            # right when its G is ALL of dL/dy -- the very tensor autograd hands over, untouched.  If y had another
-            # consumer the engine summed their gradients (a new tensor, or in place: the version moves): the difference
-            # goes through the elementwise kernel (linear in g), dz and dbias are redone.
-            G, g_version, dz, dbias = fused[:4]
-            if g.data_ptr() == G.data_ptr() and g.shape == G.shape and g._version == g_version:
-                dx0, dxd = incoming, (incoming if same else None)
-            else:
-                delta = (g.float() - G.float()).to(g.dtype)
-                _, dx0, _, _ = D.cross_epilogue_bwd(delta, u, x0c, xc, diag, act=act, want_du=False, want_dxd=False,
-                                                    want_dbias=False, fold_direct=same, dx0_into=incoming)
-                dz, _, _, dbias = D.cross_epilogue_bwd(g, u, x0c, xc, diag, act=act, want_dxd=False,
-                                                       want_dbias=has_bias, want_dx0=False)
-                dxd = dx0 if same else None
-        elif (incoming is None and extra is None and not same and low_rank and not diag and FUSE_TOP_DX0
-              and _fusable_below(ctx.relay_up, g, x_dt, task)):
-            # The TOP layer of a stack (nothing above it left a dL/dx0) whose data-gradient product is going to run the
-            # layer below's elementwise backward: its own term g * u is computed THERE (g is that product's residual, already
-            # in registers), so this pass writes dz only -- three [B, d] streams instead of five, and no matrix for dL/dx0 is
-            # written here and read back there.
-            dz, _, dxd, dbias = D.cross_epilogue_bwd(g, u if act != L.ACT_NONE else None, x0c, xc, diag, act=act,
-                                                     want_dxd=False, want_dbias=has_bias, want_dx0=False)
-            dx0, defer_dx0 = None, True
-        else:
-            # x is x0 (the first layer of a stack): both halves of dL/dx0 go through one buffer, which
-            # the data-gradient GEMM then takes as its residual -- no separate add.
-            dz, dx0, dxd, dbias = D.cross_epilogue_bwd(g, u, x0c, xc, diag, act=act, want_dxd=need_dxd,
-                                                       want_dbias=has_bias, fold_direct=same, dx0_into=incoming)
+        incoming, extra, handoff = _take_handed_down(ctx.relay_in, x0c, task)
+        dz, dx0, dxd, dbias, defer_dx0 = _cross_elementwise(ctx, saved, g, task, incoming, extra, handoff)
         if extra is not None:
             dx0 = dx0 + extra.to(dx0.dtype)
-        u_own = u if defer_dx0 else None
-        direct = dx0 if same else (dxd if need_dxd else g)  # dL/dx through "+ x" and "diag * x"
-        # (worth it when the kernels are long against a launch: at a per-rank batch of 8192 the step is bound by the
-        #  host's enqueue rate and the extra events cost more than the overlap returns: 2.42 -> 2.54 ms)
-        # a weight with several pending uses gets several contributions in THIS pass (summed by autograd's input buffer
-        # on the main stream): the first backward that runs sees the full count and marks the pass, the later ones --
-        # which see a count of one again -- read the mark
-        shared = False
-        for r in ctx.w_refs:
-            w = r()
-            if w is None:
-                continue
-            if getattr(w, "_krs_pending_cross", 1) != 1:
-                w._krs_shared_in_task = task
-            shared = shared or (task != -1 and getattr(w, "_krs_shared_in_task", None) == task)
-        side_ok = low_rank and WGRAD_SIDE_STREAM and dz.is_cuda and dz.shape[0] >= WGRAD_SIDE_MIN_ROWS and \
-            not shared and all(_wgrad_side_ok(r()) for r in ctx.w_refs)
-        _release_pending_cross(ctx.w_refs, ctx.counted)
-        if side_ok:
-            # Data-gradient path first; the two weight gradients (off the critical path: only the optimizer reads them)
-            # go to a second stream that starts when dx is done -- i.e. beside the HBM-bound kernel that follows on the
-            # main stream (the dz / dx0 pass of the layer below, or the DotInteraction gradient and the table update
-            # behind the bottom layer).  The main stream rejoins at the end of the backward pass (wgrad_stream_sync).
-            dh, _ = D.gemm(dz, kc, b_is_nk=True)                               # dh = dz K^T     [B, p]
-            dx, dx0 = _dx_product(ctx, dh, dc, direct, dx0, x0c, task, u_own)  # dx = dh U^T + direct
-            main = torch.cuda.current_stream()
-            side = _wgrad_stream(dz.device)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            dk = torch.empty((h.shape[1], dz.shape[1]), dtype=torch.float32, device=dz.device)
-            dd = torch.empty((xc.shape[1], dh.shape[1]), dtype=torch.float32, device=dz.device)
-
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                D.gemm(h, dz, a_is_km=True, out_dtype=torch.float32, out=dk)   # dK = h^T dz     [p, d]
-                D.gemm(xc, dh, a_is_km=True, out_dtype=torch.float32, out=dd)  # dU = x^T dh     [d, p]
-                # the casts to the weights' dtype (bf16 variables) belong to this stream too: on the main stream they
-                # would read dk / dd with nothing ordering them behind the two products
-                dk_out, dd_out = dk.to(k_dt), dd.to(down_dt)
-            for t in (h, dz, xc, dh, dk, dd, dk_out, dd_out):
-                t.record_stream(side)
-            dk, dd = dk_out, dd_out
-            _queue_wgrad_sync(task)
-        elif low_rank:
-            dk, _ = D.gemm(h, dz, a_is_km=True, out_dtype=torch.float32)      # dK = h^T dz     [p, d]
-            dh, _ = D.gemm(dz, kc, b_is_nk=True)                               # dh = dz K^T     [B, p]
-            dd, _ = D.gemm(xc, dh, a_is_km=True, out_dtype=torch.float32)      # dU = x^T dh     [d, p]
-            dx, dx0 = _dx_product(ctx, dh, dc, direct, dx0, x0c, task, u_own)  # dx = dh U^T + direct
-        else:
-            dk, _ = D.gemm(xc, dz, a_is_km=True, out_dtype=torch.float32)      # dK = x^T dz     [d, d]
-            dd = None
-            dx, _ = D.gemm(dz, kc, b_is_nk=True, r=direct, beta=1.0)           # dx = dz K^T + direct
+        direct = dx0 if same else (dxd if m.diag_scale else g)  # dL/dx through "+ x" and "diag * x"
+        dx, dx0, dk, dd = _cross_products(ctx, saved, dz, direct, dx0, u if defer_dx0 else None, task)
         if same:
-            gx0, gx = dx.to(x0_dt), None
+            gx0, gx = dx.to(m.x0_dtype), None
         else:
-            gx, up = dx.to(x_dt), ctx.relay_up
+            gx, up = dx.to(m.x_dtype), ctx.relay_up
             if up is not None and task != -1:
                 # the producer of x takes it from here (its backward runs later in this pass: it is owed dL/dx)
                 if up.buf is not None and up.task == task:
@@ -443,35 +310,61 @@ class CrossLayerFn(torch.autograd.Function):
                 up.buf, up.task = dx0, task
                 gx0 = None
             else:
-                gx0 = dx0.to(x0_dt)
-        return (gx0, gx, None if dd is None else dd.to(down_dt), dk.to(k_dt),
-                dbias if has_bias else None, None, None, None, None, None)
+                gx0 = dx0.to(m.x0_dtype)
+        return (gx0, gx, None if dd is None else dd.to(m.down_dtype), dk.to(m.kernel_dtype),
+                dbias if m.has_bias else None, None, None, None, None, None)
 
 
-# development switch: 0 = every Dense layer runs its own activation backward (krs_dense_act_bwd), as before round 6
-FUSE_DENSE_BWD = bool(int(__import__("os").environ.get("KRS_FUSE_DENSE_BWD", "1")))
+def cross_layer(x0, x, down, kernel, bias, diag_scale, act, compute_dtype):
+    """CrossLayerFn on inputs of any rank, wired into the hand-offs as every layer class wires it: dL/dx0 travels down a
+    stack of layers on the same x0 through relays instead of autograd adds -- this call's relay goes on its output, where
+    the next layer (or a Dense layer, DenseFn) finds it; the relay of the layer that produced `x` is read off `x`."""
+    lead, d = x0.shape[:-1], x0.shape[-1]
+    same = x is x0
+    x02 = x0.reshape(-1, d)
+    x2 = x02 if same else x.reshape(-1, d)
+    relay = Dx0Relay(x02)
+    y = CrossLayerFn.apply(x02, x2, down, kernel, bias, diag_scale, act, compute_dtype, relay,
+                           None if same else getattr(x, "_krs_dx0_relay", None))
+    out = y.reshape(*lead, d)
+    out._krs_dx0_relay = relay
+    return out
 
 
-class DenseActRelay:
-    """Hand-off between two STACKED Dense layers (examples/ml_perf/model.py:214-262: `x = dense(x)` repeated): the upper
-    layer's data-gradient product G = dz K^T is the lower layer's dL/dy, and the lower layer's first backward step --
-    dz_low = dL/dy * act'(y_low), dbias_low = column sums -- rides in that product's epilogue (krs_gemm_cross_bwd, dense
-    form): dL/dy is not read back for it.
-      lower  (act, has_bias) of the layer whose output carries this relay -- set by its forward (no tensor: the output
-             holds the relay as an attribute, a reference back would be a cycle that only the cyclic collector frees; the
-             upper layer has that output anyway -- it is its saved input);
-      fused  (G, its version, dz_low, dbias_low, graph task) -- set by the upper layer's backward, taken by the lower one's.
-    What autograd receives from the upper layer is G itself, the true dL/dy, so everything that observes the output's
-    gradient -- autograd.grad / backward(inputs=...) captures, tensor and node hooks, retain_grad -- sees the right value.
-    The lower backward takes dz_low and dbias_low only when what it is handed IS that G, untouched (pointer, shape, version:
-    the relay keeps G alive, so its memory cannot be reused meanwhile); anything else -- a second consumer's gradient summed
-    in, a hook's replacement or in-place change -- goes through its own derivative.
-      out_ref  weak reference to that output (`_dense_fusable_below`: one that retains its .grad is not fused)."""
+class _DenseMeta(NamedTuple):
+    act: int
+    has_bias: bool
+    x_dtype: torch.dtype
+    kernel_dtype: torch.dtype
 
-    __slots__ = ("lower", "fused", "out_ref")
 
-    def __init__(self):
-        self.lower, self.fused, self.out_ref = None, None, None
+def _dense_dx_product(ctx, xc, kc, dz, task):
+    """dx = dz K^T of a Dense layer, with the first backward step of the layer that produced x in its epilogue when
+    that is a cross layer (ctx.relay_up) or a Dense layer (ctx.dense_up) and the hand-off is legal."""
+    x_dt, up = ctx.meta.x_dtype, ctx.relay_up
+    if _fusable_below(up, dz, x_dt, task):
+        # x is the output of a cross layer: dx = dz K^T is its dL/dy, and its elementwise backward (dz, its
+        # term of dL/dx0, bias gradient) rides in the epilogue of this product
+        low = up.lower
+        # (that layer's own term of dL/dx0 waits for ITS data-gradient product when that one is going to be a fused
+        #  launch as well: u_upper there, one [B, d] matrix less written here and read there)
+        defer = FUSE_TOP_DX0 and not low.x_is_x0 and _fusable_below(low.below, dz, low.x_dtype, task)
+        dx, dz_low, dx0, db_low = D.gemm_cross_bwd(dz, kc, None, low.x0c, low.u, act=low.act, want_dbias=low.has_bias,
+                                                   fold_direct=low.x_is_x0, want_dx0=not defer)
+        if not defer:
+            up.buf, up.task = dx0, task
+        up.fused = Handoff(dx, dx._version, dz_low, db_low, task, defer)
+        return dx
+    if _dense_fusable_below(ctx.dense_up, dz, x_dt, task):
+        # x is the output of a Dense layer: its activation backward and bias gradient ride in this product's epilogue;
+        # what goes back to autograd is dx itself, the true dL/dy of that output (its backward recognises it)
+        below = ctx.dense_up
+        # (xc IS the lower layer's output y)
+        dz_low, db_low, dx = D.gemm_dense_bwd(dz, kc, xc, below.lower.act, want_dbias=below.lower.has_bias, want_g=True)
+        below.fused = Handoff(dx, dx._version, dz_low, db_low, task)
+        return dx
+    dx, _ = D.gemm(dz, kc, b_is_nk=True)                               # [B, in]
+    return dx.to(x_dt)
 
 
 class DenseFn(torch.autograd.Function):
@@ -482,72 +375,64 @@ class DenseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, kernel, bias, act, compute_dtype, relay_up=None, dense_up=None, relay_out=None):
-        # relay_up: the Dx0Relay of the cross layer that produced x (layers.Dense reads it off its input): this layer's
+        # relay_up: the Dx0Relay of the cross layer that produced x (dense_layer reads it off its input): this layer's
         # data-gradient product then runs that layer's elementwise backward in its epilogue (krs_gemm_cross_bwd)
         # dense_up / relay_out: the DenseActRelay of the Dense layer that produced x / of this layer's own output
         xc = x.to(compute_dtype).contiguous()
         kc, kct = D.cast_transpose(kernel, compute_dtype)
         y, _ = D.gemm(xc, kct, b_is_nk=True, bias=bias, act=act)
         ctx.save_for_backward(xc, kc, y if act != L.ACT_NONE else None)
-        ctx.meta = (act, bias is not None, x.dtype, kernel.dtype)
+        ctx.meta = _DenseMeta(act, bias is not None, x.dtype, kernel.dtype)
         ctx.relay_up = relay_up if ctx.needs_input_grad[0] else None
         # (the lower layer's saved output is this layer's saved input when no cast / copy came between)
         ctx.dense_up = dense_up if (ctx.needs_input_grad[0] and xc.data_ptr() == x.data_ptr() and xc.dtype == x.dtype) else None
         ctx.relay_out = relay_out
         if relay_out is not None:
-            relay_out.lower = (act, bias is not None)
+            relay_out.lower = DenseLower(act, bias is not None)
         return y
 
     @staticmethod
     def backward(ctx, g):
         xc, kc, y = ctx.saved_tensors
-        act, has_bias, x_dt, k_dt = ctx.meta
-        task = torch._C._current_graph_task_id()
-        rel, fused = ctx.relay_out, None
+        m = ctx.meta
+        task = graph_task()
+        rel, handoff = ctx.relay_out, None
         if rel is not None:
-            fused, rel.fused = rel.fused, None
-        if fused is not None:
-            # the consumer of y ran this layer's activation backward inside its data-gradient product: right only when
-            # what arrives is that product's G, untouched (no second consumer summed in, no hook replaced or changed it)
-            G, version = fused[:2]
-            if not (fused[4] == task and g.data_ptr() == G.data_ptr() and g.shape == G.shape and g.stride() == G.stride()
-                    and g._version == version and g.dtype == G.dtype):
-                fused = None
-        if fused is not None:
-            dz, db = fused[2], fused[3]
+            handoff, rel.fused = rel.fused, None
+        # the consumer of y ran this layer's activation backward inside its data-gradient product: right only when
+        # what arrives is that product's G, untouched (no second consumer summed in, no hook replaced or changed it)
+        if handoff is not None and handoff.is_gradient(g, task):
+            dz, db = handoff.dz, handoff.dbias
         else:
             g = g.to(xc.dtype)
             # dz = g * act'(y) and the bias gradient in one pass (krs_dense_act_bwd)
-            dz, db = D.dense_act_bwd(g, y, act, want_dbias=has_bias)
+            dz, db = D.dense_act_bwd(g, y, m.act, want_dbias=m.has_bias)
         dz = dz.contiguous()
         dk, _ = D.gemm(xc, dz, a_is_km=True, out_dtype=torch.float32)            # [in, units]
-        dx = None
-        if ctx.needs_input_grad[0]:
-            up, task = ctx.relay_up, torch._C._current_graph_task_id()
-            if _fusable_below(up, dz, x_dt, task):
-                # x is the output of a cross layer: dx = dz K^T is its dL/dy, and its elementwise backward (dz, its
-                # term of dL/dx0, bias gradient) rides in the epilogue of this product
-                u_low, act_low, _, bias_low, same_low, x0c, (below, x_dt_low) = up.lower
-                # (that layer's own term of dL/dx0 waits for ITS data-gradient product when that one is going to be a fused
-                #  launch as well: u_upper there, one [B, d] matrix less written here and read there)
-                defer = FUSE_TOP_DX0 and not same_low and _fusable_below(below, dz, x_dt_low, task)
-                dx, dz_low, dx0, db_low = D.gemm_cross_bwd(dz, kc, None, x0c, u_low, act=act_low, want_dbias=bias_low,
-                                                           fold_direct=same_low, want_dx0=not defer)
-                if not defer:
-                    up.buf, up.task = dx0, task
-                up.fused = (dx, dx._version, dz_low, db_low, task, defer)
-            elif _dense_fusable_below(ctx.dense_up, dz, x_dt, task):
-                # x is the output of a Dense layer: its activation backward and bias gradient ride in this product's epilogue;
-                # what goes back to autograd is dx itself, the true dL/dy of that output (its backward recognises it)
-                below = ctx.dense_up
-                act_low, bias_low = below.lower
-                # (xc IS the lower layer's output y)
-                dz_low, db_low, dx = D.gemm_dense_bwd(dz, kc, xc, act_low, want_dbias=bias_low, want_g=True)
-                below.fused = (dx, dx._version, dz_low, db_low, task)
-            else:
-                dx, _ = D.gemm(dz, kc, b_is_nk=True)                               # [B, in]
-                dx = dx.to(x_dt)
-        return dx, dk.to(k_dt), db, None, None, None, None, None
+        dx = _dense_dx_product(ctx, xc, kc, dz, task) if ctx.needs_input_grad[0] else None
+        return dx, dk.to(m.kernel_dtype), db, None, None, None, None, None
+
+
+def dense_layer(x, kernel, bias, act, compute_dtype, host_activation=None):
+    """DenseFn on an input of any rank, wired into the hand-offs as layers.Dense wires it.  A 2-D input that is the output
+    of a FeatureCross stack carries that layer's relay: the data gradient of this layer then runs the cross layer's
+    elementwise backward in its epilogue.  Likewise one that is the output of another Dense layer carries a DenseActRelay:
+    that layer's activation backward and bias gradient then ride in this layer's data-gradient product; this layer's own
+    output gets one -- unless `host_activation` (a callable applied to the product's output: `act` is ACT_NONE then)
+    stands between the product and the output."""
+    lead, d = x.shape[:-1], x.shape[-1]
+    two_d = x.dim() == 2
+    relay_out = DenseActRelay() if (two_d and host_activation is None) else None
+    y = DenseFn.apply(x.reshape(-1, d), kernel, bias, act, compute_dtype,
+                      getattr(x, "_krs_dx0_relay", None) if two_d else None,
+                      getattr(x, "_krs_dense_relay", None) if two_d else None, relay_out)
+    if host_activation is not None:
+        y = host_activation(y)
+    y = y.reshape(*lead, kernel.shape[1])
+    if relay_out is not None:
+        relay_out.out_ref = weakref.ref(y)
+        y._krs_dense_relay = relay_out
+    return y
 
 
 class BinaryCrossentropyFn(torch.autograd.Function):
@@ -604,7 +489,7 @@ class DotInteractionFn(torch.autograd.Function):
         relay = ctx.relay
         watched = any((t := r()) is not None and (t.retains_grad or t._backward_hooks) for r in ctx.view_refs)
         if relay is not None and relay.buf is not None and not watched:
-            buf, task = relay.buf, torch._C._current_graph_task_id()
+            buf, task = relay.buf, graph_task()
             n, (batch, dim) = len(feats), feats[0].shape
             if (relay.task == task and task != -1 and tuple(buf.shape) == (batch, n * dim) and buf.is_contiguous()
                     and buf.dtype == feats[0].dtype and g.dtype == buf.dtype):
@@ -653,7 +538,7 @@ class EmbedBagFn(torch.autograd.Function):
 
 
 # development switch (A/B of the two orders, see EmbedBagFusedFn.forward)
-_PLAN_AFTER_GATHER = bool(int(__import__("os").environ.get("KRS_PLAN_AFTER_GATHER", "0")))
+_PLAN_AFTER_GATHER = _switch(os.environ.get("KRS_PLAN_AFTER_GATHER", "0"))
 
 
 class EmbedBagFusedFn(torch.autograd.Function):
@@ -771,6 +656,6 @@ class SlabFillFn(torch.autograd.Function):
             # (a concat result nobody holds any more cannot show its .grad to anyone)
             out = relay.out_ref() if relay.out_ref is not None else None
             plain = (out is None or (not out.retains_grad and not out._backward_hooks)) and not relay.disabled
-            task = torch._C._current_graph_task_id()
+            task = graph_task()
             relay.buf, relay.task = (g, task) if (plain and task != -1 and g.is_contiguous()) else (None, -1)
         return (g, None) + tuple(g[:, a:b] for a, b in ctx.cols)

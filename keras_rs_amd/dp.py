@@ -41,7 +41,7 @@ class GradAllReduce:
             return
         if p.grad.is_cuda:
             # a cross layer's weight gradients come off a second stream (autograd.WGRAD_SIDE_STREAM)
-            from keras_rs_amd.autograd import wgrad_stream_sync
+            from keras_rs_amd.wgrad_side import wgrad_stream_sync
 
             wgrad_stream_sync()
         op = dist.ReduceOp.AVG if self._avg_op else dist.ReduceOp.SUM

@@ -33,7 +33,7 @@ def make_layers(keras) -> types.SimpleNamespace:
     import torch
 
     from keras_rs_amd import _lib as L
-    from keras_rs_amd.autograd import CrossEpilogueFn, CrossLayerFn, DotInteractionFn, Dx0Relay
+    from keras_rs_amd.autograd import CrossEpilogueFn, DotInteractionFn, cross_layer
     from keras_rs_amd.layers import distributed_embedding as de_torch
     from keras_rs_amd.layers.feature_cross import _Linear
 
@@ -87,10 +87,6 @@ def make_layers(keras) -> types.SimpleNamespace:
                 raise ValueError("`x0` and `x` should have the same shape. Received: "
                                  f"`x.shape` = {tuple(x.shape)}, `x0.shape` = {tuple(x0.shape)}")
             L.require_device(x0, "FeatureCross input")
-            lead, d = x0.shape[:-1], x0.shape[-1]
-            same = x is x0
-            x02 = x0.reshape(-1, d)
-            x2 = x02 if same else x.reshape(-1, d)
             diag = float(self.diag_scale) if self.diag_scale else 0.0
             cd = compute_dtype(self)
             down = None if self.down_kernel is None else _tensor(self.down_kernel)
@@ -98,12 +94,10 @@ def make_layers(keras) -> types.SimpleNamespace:
             bias = None if self.bias is None else _tensor(self.bias).float()
             act_id = self._pre_activation_id
             if act_id is None or (isinstance(act_id, str) and act_id in fused_acts):
-                relay = Dx0Relay(x02)
-                y = CrossLayerFn.apply(x02, x2, down, kernel, bias, diag, fused_acts[act_id], cd, relay,
-                                       None if same else getattr(x, "_krs_dx0_relay", None))
-                out = y.reshape(*lead, d)
-                out._krs_dx0_relay = relay
-                return out
+                return cross_layer(x0, x, down, kernel, bias, diag, fused_acts[act_id], cd)
+            lead, d = x0.shape[:-1], x0.shape[-1]
+            x02 = x0.reshape(-1, d)
+            x2 = x02 if x is x0 else x.reshape(-1, d)
             h = x2.to(cd)                       # arbitrary callable: GEMMs on MFMA, the callable in between
             if down is not None:
                 h = _Linear.apply(h, down, None, cd)

@@ -12,7 +12,7 @@ from typing import Any
 import torch
 
 from keras_rs_amd import _lib as L
-from keras_rs_amd.autograd import DenseActRelay, DenseFn
+from keras_rs_amd.autograd import dense_layer
 from keras_rs_amd.layers import base
 from keras_rs_amd.layers.embed_reduce import (check_quantize_request, keep_fp32_steps, quantize_rows_checked,
                                                restore_fp32_steps)
@@ -110,29 +110,13 @@ class Dense(base.Layer):
         L.require_device(x, "Dense input")
         if self.quantization_mode:
             return self._call_quantized(x)
-        lead, d = x.shape[:-1], x.shape[-1]
-        if d != self.kernel.shape[0]:
-            raise ValueError(f"Dense: input feature size {d} does not match the kernel {tuple(self.kernel.shape)}")
-        fused = self.activation in _FUSED_ACTS
-        # (an input that is the output of a FeatureCross stack carries that layer's relay: the data gradient of this
-        #  layer then runs the cross layer's elementwise backward in its epilogue, autograd.DenseFn)
-        # (likewise an input that is the output of another Dense layer carries a DenseActRelay: that layer's activation
-        #  backward and bias gradient then ride in this layer's data-gradient product; this layer's own output gets one)
-        two_d = x.dim() == 2
-        relay_out = DenseActRelay() if (two_d and fused) else None
-        y = DenseFn.apply(x.reshape(-1, d), self.kernel, self.bias,
-                          _FUSED_ACTS[self.activation] if fused else L.ACT_NONE, self.compute_dtype,
-                          getattr(x, "_krs_dx0_relay", None) if two_d else None,
-                          getattr(x, "_krs_dense_relay", None) if two_d else None, relay_out)
-        if not fused:
-            y = self.activation(y)
-        y = y.reshape(*lead, self.units)
-        if relay_out is not None:
-            import weakref
-
-            relay_out.out_ref = weakref.ref(y)
-            y._krs_dense_relay = relay_out
-        return y
+        if x.shape[-1] != self.kernel.shape[0]:
+            raise ValueError(f"Dense: input feature size {x.shape[-1]} does not match the kernel {tuple(self.kernel.shape)}")
+        # (the hand-offs of the backward pass -- from a FeatureCross stack or another Dense layer below, to a Dense layer
+        #  above -- are wired by autograd.dense_layer)
+        if self.activation in _FUSED_ACTS:
+            return dense_layer(x, self.kernel, self.bias, _FUSED_ACTS[self.activation], self.compute_dtype)
+        return dense_layer(x, self.kernel, self.bias, L.ACT_NONE, self.compute_dtype, host_activation=self.activation)
 
     def compute_output_shape(self, input_shape):
         return tuple(input_shape[:-1]) + (self.units,)

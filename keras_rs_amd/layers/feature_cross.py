@@ -12,7 +12,7 @@ from typing import Any
 import torch
 
 from keras_rs_amd import _lib as L
-from keras_rs_amd.autograd import CrossEpilogueFn, CrossLayerFn, Dx0Relay
+from keras_rs_amd.autograd import CrossEpilogueFn, cross_layer
 from keras_rs_amd.layers import base
 from keras_rs_amd.layers.dense import quantize_kernel, refuse_grad_input
 from keras_rs_amd.layers.embed_reduce import check_quantize_request, keep_fp32_steps, restore_fp32_steps
@@ -77,29 +77,21 @@ class FeatureCross(base.Layer):
         L.require_device(x0, "FeatureCross input")
         if self.quantization_mode:
             return self._call_quantized(x0, x)
-        lead, d = x0.shape[:-1], x0.shape[-1]
-        same = x is x0
-        x02 = x0.reshape(-1, d)
-        x2 = x02 if same else x.reshape(-1, d)
         diag = float(self.diag_scale) if self.diag_scale else 0.0
         act = self.pre_activation
         if act in _FUSED_ACTS:
-            # dL/dx0 travels down a stack of layers on the same x0 through relays instead of autograd adds
-            relay = Dx0Relay(x02)
-            y = CrossLayerFn.apply(x02, x2, self.down_kernel, self.kernel, self.bias, diag, _FUSED_ACTS[act],
-                                   self.compute_dtype, relay, None if same else getattr(x, "_krs_dx0_relay", None))
-            out = y.reshape(*lead, d)
-            out._krs_dx0_relay = relay
-            return out
-        else:
-            # arbitrary callable: GEMM(+bias) on MFMA, the callable on the host framework, cross kernel fused
-            cd = self.compute_dtype
-            h = x2.to(cd)
-            if self.down_kernel is not None:
-                h = _Linear.apply(h, self.down_kernel, None, cd)
-            z = _Linear.apply(h, self.kernel, self.bias, cd)
-            u = act(z).to(cd)
-            y = CrossEpilogueFn.apply(u, x02.to(cd), x2.to(cd), diag)
+            return cross_layer(x0, x, self.down_kernel, self.kernel, self.bias, diag, _FUSED_ACTS[act], self.compute_dtype)
+        # arbitrary callable: GEMM(+bias) on MFMA, the callable on the host framework, cross kernel fused
+        lead, d = x0.shape[:-1], x0.shape[-1]
+        x02 = x0.reshape(-1, d)
+        x2 = x02 if x is x0 else x.reshape(-1, d)
+        cd = self.compute_dtype
+        h = x2.to(cd)
+        if self.down_kernel is not None:
+            h = _Linear.apply(h, self.down_kernel, None, cd)
+        z = _Linear.apply(h, self.kernel, self.bias, cd)
+        u = act(z).to(cd)
+        y = CrossEpilogueFn.apply(u, x02.to(cd), x2.to(cd), diag)
         return y.reshape(*lead, d)
 
     # ---- int8 for inference (what keras' quantize("int8") does to the layer's two Dense sublayers) -----------------------

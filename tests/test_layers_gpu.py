@@ -957,6 +957,7 @@ def test_second_stream_is_opt_in_and_keeps_away_from_weights_with_a_second_reade
     import os
 
     from keras_rs_amd import autograd as A
+    from keras_rs_amd import wgrad_side as W
     from keras_rs_amd.layers import base as kl_base
 
     kl = _layers()
@@ -969,13 +970,13 @@ def test_second_stream_is_opt_in_and_keeps_away_from_weights_with_a_second_reade
     old_rows = A.WGRAD_SIDE_MIN_ROWS
     A.WGRAD_SIDE_MIN_ROWS = 1024
     used = []
-    real_stream = A._wgrad_stream
+    real_stream = W._wgrad_stream
 
     def spy(device):
         used.append(1)
         return real_stream(device)
 
-    A._wgrad_stream = spy
+    W._wgrad_stream = spy
     try:
         def run(side, dtype, reg=None, twice=False):
             old = A.set_wgrad_side_stream(side)
@@ -1018,7 +1019,7 @@ def test_second_stream_is_opt_in_and_keeps_away_from_weights_with_a_second_reade
         sum(layer.losses).backward()
         torch.testing.assert_close(layer.kernel.grad, 0.02 * layer.kernel.detach(), rtol=1e-6, atol=1e-9)
     finally:
-        A._wgrad_stream = real_stream
+        W._wgrad_stream = real_stream
         A.WGRAD_SIDE_MIN_ROWS = old_rows
 
 

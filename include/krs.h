@@ -1283,6 +1283,62 @@ int krs_seq_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, con
                      int64_t lddv, void* workspace, size_t workspace_bytes, void* stream);
 int krs_seq_attn_last_route(int* kernel, int* dpad);
 
+/* ------------------------------------------------------------------------- *
+ * K20  The recurrence of a GRU layer (keras.layers.GRU: reset_after=True, tanh, sigmoid), all l steps in one launch
+ *
+ * Weights in Keras' shapes and gate order z, r, h: kernel [d, 3u], recurrent_kernel [u, 3u], bias [2, 3u] (row 0 the
+ * input bias, row 1 the recurrent bias rb).  The input projection runs OUTSIDE these entries, as a Dense product:
+ * xz = x . kernel + bias[0], one row of 3u per token, token (bi, t) at row bi * l + t, rows ldxz elements apart
+ * (>= 3u: a view of a wider buffer qualifies).  At a valid step, with h the carried state, in fp32:
+ *     a  = h . recurrent_kernel                          (slices a_z, a_r, a_h; fp32 accumulate)
+ *     z  = sigmoid(xz_z + a_z + rb_z)      r = sigmoid(xz_r + a_r + rb_r)
+ *     q  = a_h + rb_h                      c = tanh(xz_h + r * q)
+ *     h' = z * h + (1 - z) * c
+ * At a masked step (valid[bi, t] == 0; valid: uint8 [b, l] or NULL = every step valid) the state is carried unchanged
+ * and the step's sequence output is the previous step's output: zeros before the first valid step, even when h0 is
+ * not zero (the rule of Keras' backend rnn); from the first valid step on the output equals the state.
+ * Backward, with g the gradient arriving at h' (this step's output gradient plus the carried one):
+ *     dh  = g * z              dc_pre = g * (1 - z) * (1 - c^2)          dz_pre = g * (h - c) * z * (1 - z)
+ *     dq  = dc_pre * r         dr_pre = dc_pre * q * r * (1 - r)
+ *     dxz = (dz_pre, dr_pre, dc_pre)      da = (dz_pre, dr_pre, dq)      dh += da . recurrent_kernel^T
+ * A masked step passes g through and contributes zeros to dxz and da; the gradient of an output before the first
+ * valid step goes nowhere.
+ *
+ * dtype (KRS_F32 / KRS_BF16) is the type of xz, recurrent_kernel, h0, hs, h_last, the reserve and every gradient;
+ * recurrent_bias is fp32 [3u] or NULL.  hs [b, l, u] is the sequence output, h_last [b, u] the final STATE (an
+ * all-padding sequence: h0); either may be NULL, not both.  reserve [b, l, 4u] (krs_gru_reserve_bytes) receives
+ * z, r, c, q of every step for the backward and needs hs; with reserve NULL (inference) only the outputs are written,
+ * and they are bit for bit those of the training forward.
+ * krs_gru_bwd reads recurrent_kernel, valid, h0, hs and the reserve back with dhs [b, l, u] and dh_last [b, u] (either
+ * may be NULL = zeros) and writes dxz [b, l, 3u], da [b, l, 3u], h_prev [b, l, u] (NULL to skip: the h_{t-1} each step
+ * used, the left operand of d recurrent_kernel = h_prev^T . da) and dh0 [b, u] (NULL to skip).  The weight gradients
+ * are products and column sums of these, outside: d recurrent_kernel as one krs_gemm, d bias[1] = krs_colsum(da).
+ *
+ * Routes (csrc/gru_plan.h decides, a pure host function):
+ *   KRS_GRU_FAST     bf16, u <= 128 (upad 32 / 64 / 128).  A workgroup owns 32 batch rows and walks every step alone;
+ *                    the recurrent kernel is staged once into LDS as bf16; h . U and da . U^T run on
+ *                    v_mfma_f32_32x32x16_bf16.  Rounded to bf16 (nearest even): recurrent_kernel and xz as given, the
+ *                    A-operand copy of h, da, the reserve, the outputs.  The carried state, the carried dh and the
+ *                    accumulators stay fp32.  The backward reads h_{t-1} from hs (bf16).
+ *   KRS_GRU_GENERIC  fp32 at any u <= 1024, bf16 at 128 < u <= 1024: fp32 FMA, the carried state in LDS (never
+ *                    rounded), the recurrent kernel read through L2 each step; 4 batch rows per workgroup.
+ * One owner per output element and no atomics on either route: bit-identical from call to call.  No workgroup waits
+ * on another: no grid barrier, no cooperative launch, no flags.  No host synchronisation.
+ * b == 0 or l == 0 is a successful no-op.  b < 0, l < 0, u < 1, a bad dtype, a null operand, ldxz < 3u and a call that
+ * wants no output are KRS_ERR_INVALID; u > 1024 is KRS_ERR_UNSUPPORTED with a message naming the limit.
+ * krs_gru_last_route: the route of the process's last krs_gru_fwd / _bwd call, whichever thread made it: kernel, and
+ * upad on the fast route, else 0; both zero after a refused call or a no-op.  Returns kernel.
+ * ------------------------------------------------------------------------- */
+enum { KRS_GRU_NONE = 0, KRS_GRU_FAST = 1, KRS_GRU_GENERIC = 2 };
+size_t krs_gru_reserve_bytes(int64_t b, int64_t l, int64_t u, int dtype);
+int krs_gru_fwd(const void* xz, int64_t ldxz, const void* recurrent_kernel, const float* recurrent_bias,
+                const uint8_t* valid, const void* h0, int dtype, int64_t b, int64_t l, int64_t u, void* hs,
+                void* h_last, void* reserve, void* stream);
+int krs_gru_bwd(const void* recurrent_kernel, const uint8_t* valid, const void* h0, const void* hs,
+                const void* reserve, const void* dhs, const void* dh_last, int dtype, int64_t b, int64_t l, int64_t u,
+                void* dxz, void* da, void* h_prev, void* dh0, void* stream);
+int krs_gru_last_route(int* kernel, int* upad);
+
 #ifdef __cplusplus
 }
 #endif

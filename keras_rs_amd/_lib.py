@@ -183,6 +183,10 @@ PROTOTYPES = {
     "krs_seq_attn_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I64, _I64, _I64, _I64, _P, _I, _F, _F, _U64, _P, _P,
                               _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _SZ, _P]),
     "krs_seq_attn_last_route": (_I, [_P, _P]),
+    "krs_gru_reserve_bytes": (_SZ, [_I64, _I64, _I64, _I]),
+    "krs_gru_fwd": (_I, [_P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "krs_gru_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    "krs_gru_last_route": (_I, [_P, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

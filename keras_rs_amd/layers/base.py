@@ -166,6 +166,30 @@ class LecunNormal(VarianceScaling):
         return {"seed": self.seed}
 
 
+class Orthogonal(Initializer):
+    """keras.initializers.Orthogonal: the Q of a QR decomposition of a normal [max(rows, cols), min(rows, cols)] matrix
+    (rows = the product of the leading axes), signs fixed by R's diagonal, times `gain`."""
+
+    def __init__(self, gain=1.0, seed=None):
+        self.gain, self.seed = gain, seed
+
+    def __call__(self, shape, dtype=torch.float32, device=None):
+        shape = tuple(shape)
+        if len(shape) < 2:
+            raise ValueError(f"The tensor to initialize must be at least two-dimensional. Received: shape={shape}")
+        rows, cols = math.prod(shape[:-1]), shape[-1]
+        g = None if self.seed is None else torch.Generator().manual_seed(int(self.seed))
+        a = torch.randn((max(rows, cols), min(rows, cols)), generator=g, dtype=torch.float64)
+        q, r = torch.linalg.qr(a)
+        q = q * torch.sign(torch.diagonal(r))
+        if rows < cols:
+            q = q.t()
+        return (float(self.gain) * q.reshape(shape)).to(dtype).to(device)
+
+    def get_config(self):
+        return {"gain": self.gain, "seed": self.seed}
+
+
 class CallableInitializer(Initializer):
     """Wraps a user callable `(shape, dtype) -> array-like`."""
 
@@ -187,6 +211,7 @@ _INITIALIZERS = {
     "glorot_uniform": GlorotUniform, "variance_scaling": VarianceScaling, "lecun_normal": LecunNormal,
     "Zeros": Zeros, "Ones": Ones, "RandomUniform": RandomUniform, "GlorotUniform": GlorotUniform,
     "VarianceScaling": VarianceScaling, "LecunNormal": LecunNormal, "Constant": Constant,
+    "orthogonal": Orthogonal, "Orthogonal": Orthogonal,
 }
 
 

@@ -7,7 +7,7 @@
 //     v_mfma_f32_32x32x16_bf16 whose A operand is the h tile (32 rows x UPAD, bf16, LDS) and whose B operand is the
 //     recurrent kernel, staged once into LDS with the contraction axis contiguous (forward: [gate column][k];
 //     backward: [unit][gate column]).  The unit is on the lane and the batch row on the 16 accumulator registers
-//     (row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)), so z, r, q of one (row, unit) sit in the same register of three
+//     (row acc_row(r, lane >> 5) of krs_owner_tile.h), so z, r, q of one (row, unit) sit in the same register of three
 //     accumulators and the gate arithmetic needs no exchange;
 //   * the z / r accumulators start at xz + rb, the h accumulator at rb_h;
 //   * the carried state is fp32 in those 16 registers for all l steps; it is rounded to bf16 only into the next step's A
@@ -23,14 +23,10 @@
 #include <atomic>
 
 #include "gru_plan.h"
-#include "krs_common.h"
+#include "krs_owner_tile.h"   // the vector types and acc_row, the batch row of an accumulator register
 
 namespace krs {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 using gru::kFastRows;
 using gru::kGenRows;
@@ -59,9 +55,6 @@ struct Params {
 __device__ __forceinline__ float sigmoid_fast(float x) { return 1.0f / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanh_fast(float x) { return 1.0f - 2.0f / (1.0f + __expf(2.0f * x)); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// batch row (inside the workgroup's 32) of accumulator register i on this lane
-__device__ __forceinline__ int acc_row(int i, int fhalf) { return (i & 3) + 8 * (i >> 2) + 4 * fhalf; }
 
 // the first valid step of a row (l when it has none; 0 without a mask)
 __device__ __forceinline__ int first_valid(const uint8_t* valid, int64_t row, int l) {

@@ -31,16 +31,14 @@
 #include <algorithm>
 
 #include "krs_list.h"
+#include "krs_owner_tile.h"   // the vector types and acc_row, the query row of an accumulator register
 #include "krs_q8.h"
 
 namespace krs {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSortMax = 2048;    // longest list sorted in LDS (16 KB of pairs)
 constexpr int kQM = 32;           // query rows of a stage-1 workgroup (one MFMA block)
@@ -405,12 +403,12 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
   int pos_reg[16];
   if constexpr (MINE) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) pos_reg[r] = posr[(r & 3) + 8 * (r >> 2) + 4 * fhalf];
+    for (int r = 0; r < 16; ++r) pos_reg[r] = posr[acc_row(r, fhalf)];
   }
   float qs_reg[16];
   if constexpr (ES == 1) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) qs_reg[r] = qstep[(r & 3) + 8 * (r >> 2) + 4 * fhalf];
+    for (int r = 0; r < 16; ++r) qs_reg[r] = qstep[acc_row(r, fhalf)];
   }
 
   for (int64_t blk = s0; blk < s1; blk += kCB) {
@@ -480,7 +478,7 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = __fmul_rn(__fmul_rn((float)iacc[r], cstep), qs_reg[r]);
     }
-    // acc[r] = score of query row (r & 3) + 8 (r >> 2) + 4 fhalf against candidate `cand`
+    // acc[r] = score of query row acc_row(r, fhalf) against candidate `cand`
     if constexpr (MINE) {
       float bias = 0.0f;
       int64_t cid = 0;
@@ -492,7 +490,7 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * fhalf;
+        const int row = acc_row(r, fhalf);
         const int pr = pos_reg[r];
         const bool is_pos = cand == (int64_t)pr;
         float s = acc[r];
@@ -513,7 +511,7 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
     } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * fhalf;
+        const int row = acc_row(r, fhalf);
         const uint32_t key = order_key(acc[r]);
         if (cvalid && q0 + row < p.b && key > t_reg[r]) {
           const int s = atomicAdd(&cnt[row], 1);
@@ -536,7 +534,7 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) t_reg[r] = thr[(r & 3) + 8 * (r >> 2) + 4 * fhalf];
+    for (int r = 0; r < 16; ++r) t_reg[r] = thr[acc_row(r, fhalf)];
   }
 
   // the slice's k best pairs per row (zeros where the slice had fewer than k candidates)

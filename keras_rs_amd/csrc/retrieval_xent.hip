@@ -4,24 +4,22 @@
 // reference's retrieval examples (scores = q c^T, labels = eye(B, N), SamplingProbabilityCorrection,
 // RemoveAccidentalHits, CategoricalCrossentropy(from_logits=True)); the arithmetic is fixed in include/krs.h (K13).
 //
-// One body, xent_kernel<DPAD, MODE, VEC>, "owner on the lane":
+// One body, xent_kernel<DPAD, MODE, VEC>, "owner on the lane" (krs_owner_tile.h: the tile image, the chunk loads, the
+// accumulator-row rule, the packing and the transposed read are that header's, shared with K19; the score chain and the
+// gather's addresses are written out here as they are there):
 //   * a wave owns 32 rows of one side (its bf16 rows live in registers as the B operand of the score product), a
 //     workgroup of 4 waves 128 rows; the other side is streamed through LDS in tiles of 32 rows, double-buffered:
 //     the next tile's global loads are issued before the current tile is computed and written to the other buffer
 //     after, one barrier per tile;
-//   * score tile X[t][o] = sum_k T[t][k] O[o][k]: one v_mfma_f32_32x32x16_bf16 chain, A = the streamed tile (16-byte
-//     row reads from LDS), B = the owner fragments.  The owner index is on the lane, the streamed index on the 16
-//     registers (row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)), so the owner's constants (m, Z, lse, g, pos) are plain
-//     per-lane values and the streamed rows' constants are read from LDS by register index;
+//   * score tile X[t][o] = sum_k T[t][k] O[o][k], one MFMA chain.  The owner index is on the lane, the streamed index on
+//     the 16 registers, so the owner's constants (m, Z, lse, g, pos) are plain per-lane values and the streamed rows'
+//     constants are read from LDS by register index;
 //   * MODE_FWD (owner = queries): online {m, Z, S, A} of K11's RowStats per lane over its 16 rows of each tile; the two
 //     lanes of a query are merged once at the end;
 //   * MODE_DQ (owner = queries) and MODE_DC (owner = candidates): P = g (exp(s - lse) - y') in the same registers,
-//     rounded pairwise to bf16 (round to nearest even), IS the A operand of the gradient product
-//     Z[o][d] += sum_t P[t][o] T[t][d]; its k order inside a step is the accumulator's row order, so the B operand
-//     is gathered from the same LDS tile in that order with ds_read_b64_tr_b16.  Z stays in DPAD / 32 accumulator
-//     tiles per wave and is stored once.
-// The LDS tile is one image for both kinds of read: 16-byte chunk ch of row r of a 128-column block sits at
-// 256 r + 16 (ch ^ (((r & 3) << 2) | ((r >> 2) & 3))) (narrower tiles: the XOR masked to the row).
+//     rounded pairwise to bf16, IS the A operand of the gradient product Z[o][d] += sum_t P[t][o] T[t][d], its B
+//     operand gathered from the same LDS tile by transposed reads.  Z stays in DPAD / 32 accumulator tiles per wave and
+//     is stored once.
 //
 // Slices: when the owner side alone gives too few workgroups, the streamed side is cut into S slices
 // (retrieval_xent_plan.h, from (b, n) alone); a workgroup then writes its slice's partial -- (m, Z, S, A) per query,
@@ -41,7 +39,7 @@
 //     exact in any order.
 #include <algorithm>
 
-#include "krs_common.h"
+#include "krs_owner_tile.h"
 #include "retrieval_xent_plan.h"
 
 namespace krs {
@@ -50,14 +48,9 @@ namespace {
 using xent::kOwnRows;
 using xent::kTile;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+static_assert(kTile == kOwnerTile, "the streamed tile is krs_owner_tile.h's");
 
 constexpr int kThreads = 256;
-constexpr float kNegInf = -__builtin_inff();
 enum { MODE_FWD = 0, MODE_DQ = 1, MODE_DC = 2, MODE_POS = 3, MODE_RANK = 4 };
 
 struct Params {
@@ -115,31 +108,6 @@ __device__ __forceinline__ RowC load_rowc(const Params& p, int64_t i, bool valid
   rc.idlo = (uint32_t)(uint64_t)id;
   rc.idhi = (uint32_t)((uint64_t)id >> 32);
   return rc;
-}
-
-// 8 bf16 of a row from element e0 (`at` points at that element), zero beyond d and for a row that does not exist.
-// VEC: every row is whole 16-byte chunks on 16-byte boundaries (d % 8 == 0 included), so a chunk is whole or absent.
-template <bool VEC>
-__device__ __forceinline__ u32x4 load_chunk(const uint16_t* at, int e0, int d, bool valid) {
-  u32x4 v = {0u, 0u, 0u, 0u};
-  if (!valid || e0 >= d) return v;
-  if constexpr (VEC) {
-    return *reinterpret_cast<const u32x4*>(at);
-  } else {
-    uint32_t h[8];
-#pragma unroll
-    for (int x = 0; x < 8; ++x) h[x] = e0 + x < d ? at[x] : 0u;
-    v = (u32x4){h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
-    return v;
-  }
-}
-
-// byte offset of 16-byte chunk ch of row `row` in the LDS image of a [kTile][DPAD] bf16 tile
-template <int DPAD>
-__device__ __forceinline__ int tile_off(int row, int ch) {
-  constexpr int CH = DPAD / 8, CHB = CH < 16 ? CH : 16;
-  const int swz = (((row & 3) << 2) | ((row >> 2) & 3)) & (CHB - 1);
-  return (ch / CHB) * (kTile * CHB * 16) + row * (CHB * 16) + 16 * ((ch % CHB) ^ swz);
 }
 
 // K11's online row statistics (softmax_xent.hip): every term stays non-negative
@@ -280,6 +248,8 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
     if (more) stage_load(t0 + kTile);
 
     // ---- scores of this wave's 32 owners against the tile's 32 rows ----
+    // (the same chain as attn_kernel's, a second copy: as a shared function it changed the code hipcc lays out for the
+    //  MODE_POS builds at DPAD = 256, docs/measurement_log.md section 28)
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -323,8 +293,7 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
         }
       }
     }
-    // ---- corrected score, smoothed label and what MODE makes of them; register r is tile row
-    //      (r & 3) + 8 (r >> 2) + 4 fhalf ----
+    // ---- corrected score, smoothed label and what MODE makes of them; register r is tile row acc_row(r, fhalf) ----
     float sv[16], yv[16];
     if constexpr (XENT) {
 #pragma unroll
@@ -394,30 +363,21 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
         st.a += valid ? yv[r] * (st.m - sv[r]) : 0.0f;
       }
     } else if constexpr (GRAD) {
-      // ---- Z[o][d] += sum_t P[t][o] T[t][d]: P's registers 8s .. 8s+7 are k-step s of the A operand, element j of
-      //      lane half h being tile row 16 s + 8 (j >> 2) + 4 h + (j & 3); the B operand takes the same rows of
-      //      column 32 dt + (lane & 31) with two transposed reads of 4 rows each ----
+      // ---- Z[o][d] += sum_t P[t][o] T[t][d]: P is the A operand, the tile it was scored against the B operand.  The
+      //      addresses are krs_owner_tile.h's gather_at (row, chunk, byte), written out -- a second copy, with
+      //      attn_kernel's, of what tests/host/owner_tile_check.cpp checks: taken from gather_at, or as a shared gather,
+      //      they made hipcc reschedule the dq / dc builds, which then ran 0.2 - 0.4 % slower
+      //      (docs/measurement_log.md section 28).  Change the three together. ----
       u32x4 pa[2];
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
-        pa[s2] = (u32x4){pack_bf16x2(sv[8 * s2], sv[8 * s2 + 1]), pack_bf16x2(sv[8 * s2 + 2], sv[8 * s2 + 3]),
-                         pack_bf16x2(sv[8 * s2 + 4], sv[8 * s2 + 5]), pack_bf16x2(sv[8 * s2 + 6], sv[8 * s2 + 7])};
+      pack16(sv, pa);
       const int li = lane & 15, tq = li >> 2, tp = li & 3, chalf = (lane >> 4) & 1;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-          u32x2 lo, hi;
-          {
-            const int r0 = 16 * s2 + 4 * fhalf;
-            const int ch = 4 * dt + 2 * chalf + (tp >> 1);
-            const char* a0 = &tile[buf][tile_off<DPAD>(r0 + tq, ch) + 8 * (tp & 1)];
-            const char* a1 = &tile[buf][tile_off<DPAD>(r0 + 8 + tq, ch) + 8 * (tp & 1)];
-            lo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                               (__attribute__((address_space(3))) s16x4*)(a0)));
-            hi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                                               (__attribute__((address_space(3))) s16x4*)(a1)));
-          }
+          const int r0 = 16 * s2 + 4 * fhalf, ch = 4 * dt + 2 * chalf + (tp >> 1);
+          const u32x2 lo = lds_read_tr16(&tile[buf][tile_off<DPAD>(r0 + tq, ch) + 8 * (tp & 1)]);
+          const u32x2 hi = lds_read_tr16(&tile[buf][tile_off<DPAD>(r0 + 8 + tq, ch) + 8 * (tp & 1)]);
           const u32x4 fb = {lo[0], lo[1], hi[0], hi[1]};
           dacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pa[s2]),
                                                              __builtin_bit_cast(bf16x8, fb), dacc[dt], 0, 0, 0);
@@ -455,7 +415,7 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
       else p.rank[orow] = mine.idx < 0 ? -1 : ahead;
     }
   } else {
-    // Z tile dt: column 32 dt + (lane & 31), owner row (r & 3) + 8 (r >> 2) + 4 fhalf of the wave's 32
+    // Z tile dt: column 32 dt + (lane & 31), owner row acc_row(r, fhalf) of the wave's 32
     const int64_t obase = oblock * kOwnRows + wave * 32;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
@@ -463,7 +423,7 @@ __global__ __launch_bounds__(kThreads) void xent_kernel(const Params p) {
       if (col >= p.d) continue;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t row = obase + (r & 3) + 8 * (r >> 2) + 4 * fhalf;
+        const int64_t row = obase + acc_row(r, fhalf);
         if (row >= RO) continue;
         if (p.S > 1) p.dpart[(slice * RO + row) * p.d + col] = dacc[dt][r];
         else p.dout[row * p.ldd + col] = f32_to_bf16(dacc[dt][r]);
@@ -511,8 +471,6 @@ __global__ __launch_bounds__(256) void combine_rank_kernel(const int32_t* __rest
   const int64_t ps = pos ? (int64_t)pos[i] : i;
   rank[i] = (ps < 0 || ps >= n) ? -1 : v;
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <int MODE>
 void launch_sweep(const Params& p, unsigned groups, hipStream_t st) {

@@ -1,7 +1,9 @@
 // K19 -- fused multi-head self-attention over [B, L] token sequences with a causal and a padding mask; the score
 // matrix and the dropout mask are never stored.  The arithmetic is fixed in include/krs.h (K19).
 //
-// Fast path (bf16, dh <= 128), attn_kernel<DPAD, MODE, VEC>: K13's body ("owner on the lane") batched over (b, h).
+// Fast path (bf16, dh <= 128), attn_kernel<DPAD, MODE, VEC>: K13's body ("owner on the lane") batched over (b, h).  The
+// tile image, the chunk loads, the accumulator-row rule, the packing and the transposed read are krs_owner_tile.h's,
+// shared with K13; the score chain and the gather's addresses are written out here as they are there.
 //   * a wave owns 32 rows of one side as B operands of the score product, a workgroup of 4 waves 128 rows of one
 //     (b, h); the other side streams through LDS in double-buffered tiles of 32 rows, TWO tiles per step (X and Y):
 //       MODE_FWD  owner = queries (q);       X = keys, Y = values
@@ -9,7 +11,7 @@
 //       MODE_DKV  owner = keys (k, v);       X = queries, Y = dO
 //   * score tile S[t][o] = X[t] . own1[o] and, in the backward, dP[t][o] = Y[t] . own2[o]: v_mfma_f32_32x32x16_bf16
 //     chains whose A operand is the streamed tile.  The owner is on the lane and the streamed row on the 16
-//     registers (row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)), so m, Z, lse, delta of the owner are per-lane values;
+//     registers (row acc_row(r, lane >> 5)), so m, Z, lse, delta of the owner are per-lane values;
 //   * the tile's probabilities (or dS), rounded pairwise to bf16, ARE the A operand of the second product
 //     (O += P~ V;  dQ += dS K;  dV += P~ dO, dK += dS Q); its B operand is gathered from the same LDS tile with
 //     ds_read_b64_tr_b16 in the accumulator's row order (K13);
@@ -26,7 +28,7 @@
 // delta_i = sum_d dO_id o_id is written to the workspace by a small kernel before either backward sweep.
 #include <atomic>
 
-#include "krs_common.h"
+#include "krs_owner_tile.h"
 #include "seq_attn_plan.h"
 
 namespace krs {
@@ -35,14 +37,9 @@ namespace {
 using seqattn::kOwnRows;
 using seqattn::kTile;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+static_assert(kTile == kOwnerTile, "the streamed tile is krs_owner_tile.h's");
 
 constexpr int kThreads = 256;
-constexpr float kNegInf = -__builtin_inff();
 enum { MODE_FWD = 0, MODE_DQ = 1, MODE_DKV = 2 };
 
 struct Params {
@@ -76,31 +73,6 @@ __device__ __forceinline__ uint32_t hash_base_of(const Params& p, int64_t bh) {
 __device__ __forceinline__ float keep_factor(const Params& p, uint32_t base, int i, int j) {
   if (!p.dropout) return 1.0f;
   return seqattn::hash_ij(base, (uint32_t)i, (uint32_t)j) >= p.thr ? p.inv_keep : 0.0f;
-}
-
-// 8 bf16 of a row from element e0 (`at` points at that element), zero beyond d and for a row that does not exist.
-// VEC: every row is whole 16-byte chunks on 16-byte boundaries, so a chunk is whole or absent.
-template <bool VEC>
-__device__ __forceinline__ u32x4 load_chunk(const uint16_t* at, int e0, int d, bool valid) {
-  u32x4 v = {0u, 0u, 0u, 0u};
-  if (!valid || e0 >= d) return v;
-  if constexpr (VEC) {
-    return *reinterpret_cast<const u32x4*>(at);
-  } else {
-    uint32_t h[8];
-#pragma unroll
-    for (int x = 0; x < 8; ++x) h[x] = e0 + x < d ? at[x] : 0u;
-    v = (u32x4){h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
-    return v;
-  }
-}
-
-// byte offset of 16-byte chunk ch of row `row` in the LDS image of a [kTile][DPAD] bf16 tile (K13's image)
-template <int DPAD>
-__device__ __forceinline__ int tile_off(int row, int ch) {
-  constexpr int CH = DPAD / 8, CHB = CH < 16 ? CH : 16;
-  const int swz = (((row & 3) << 2) | ((row >> 2) & 3)) & (CHB - 1);
-  return (ch / CHB) * (kTile * CHB * 16) + row * (CHB * 16) + 16 * ((ch % CHB) ^ swz);
 }
 
 template <int DPAD, int MODE, bool VEC>
@@ -216,26 +188,21 @@ __global__ __launch_bounds__(kThreads) void attn_kernel(const Params p) {
     }
   float m_run = kNegInf, z_run = 0.0f;   // MODE_FWD: this lane's 16 rows of every tile (m shared by the two lanes)
 
-  // B operand of the second product from a tile: rows 16 s2 + 8 (j >> 2) + 4 fhalf + (j & 3), column 32 dt + frow
+  // B operand of the second product from a tile: rows 16 s2 + acc_row(j, fhalf), column 32 dt + frow.  The addresses
+  // are krs_owner_tile.h's gather_at (row, chunk, byte), written out -- a second copy, with K13's, of what
+  // tests/host/owner_tile_check.cpp checks: through gather_at, or with the header's gather composed of it, hipcc
+  // rescheduled all 18 builds and two rows of the benchmark ran slower (docs/measurement_log.md section 28).  So are the
+  // score chains and the product loops below.  Change the three together.
   const int li = lane & 15, tq = li >> 2, tp = li & 3, chalf = (lane >> 4) & 1;
   auto gather_b = [&](const char* tile, int dt, int s2) -> u32x4 {
     const int r0 = 16 * s2 + 4 * fhalf;
     const int ch = 4 * dt + 2 * chalf + (tp >> 1);
     const char* a0 = tile + tile_off<DPAD>(r0 + tq, ch) + 8 * (tp & 1);
     const char* a1 = tile + tile_off<DPAD>(r0 + 8 + tq, ch) + 8 * (tp & 1);
-    const u32x2 lo = __builtin_bit_cast(
-        u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0)));
-    const u32x2 hi2 = __builtin_bit_cast(
-        u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a1)));
+    const u32x2 lo = lds_read_tr16(a0), hi2 = lds_read_tr16(a1);
     return (u32x4){lo[0], lo[1], hi2[0], hi2[1]};
   };
-  auto pack16 = [&](const float* sv, u32x4* pa) {
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-      pa[s2] = (u32x4){pack_bf16x2(sv[8 * s2], sv[8 * s2 + 1]), pack_bf16x2(sv[8 * s2 + 2], sv[8 * s2 + 3]),
-                       pack_bf16x2(sv[8 * s2 + 4], sv[8 * s2 + 5]), pack_bf16x2(sv[8 * s2 + 6], sv[8 * s2 + 7])};
-  };
-  // a per-owner value (the same on both lanes of an owner) by accumulator register: row (r & 3) + 8 (r >> 2) + 4 fhalf
+  // a per-owner value (the same on both lanes of an owner) by accumulator register: row acc_row(r, fhalf)
   auto lane_to_reg = [&](float v, float* byreg) {
     __builtin_amdgcn_wave_barrier();
     if (fhalf == 0) xch[wave][frow] = v;
@@ -281,7 +248,7 @@ __global__ __launch_bounds__(kThreads) void attn_kernel(const Params p) {
         }
       }
 
-      // ---- per element: register r is streamed row t0 + (r & 3) + 8 (r >> 2) + 4 fhalf ----
+      // ---- per element: register r is streamed row t0 + acc_row(r, fhalf) ----
       float sv[16], sw[KOWN ? 16 : 1];
       float kf[MODE == MODE_FWD ? 16 : 1];
 #pragma unroll
@@ -375,7 +342,7 @@ __global__ __launch_bounds__(kThreads) void attn_kernel(const Params p) {
     __syncthreads();
   }
 
-  // ---- results: accumulator tile dt holds column 32 dt + frow of owner rows (r & 3) + 8 (r >> 2) + 4 fhalf ----
+  // ---- results: accumulator tile dt holds column 32 dt + frow of owner rows acc_row(r, fhalf) ----
   float rowf[16];
   if constexpr (MODE == MODE_FWD) {
     const float z = z_run + __shfl_xor(z_run, 32, 64);
@@ -394,7 +361,7 @@ __global__ __launch_bounds__(kThreads) void attn_kernel(const Params p) {
       if (col >= dh) continue;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = wfirst + (r & 3) + 8 * (r >> 2) + 4 * fhalf;
+        const int row = wfirst + acc_row(r, fhalf);
         if (row >= l) continue;
         out[(tok0 + row) * ldd + col] = f32_to_bf16(scaled ? acc[dt][r] * rowf[r] : acc[dt][r]);
       }
@@ -596,7 +563,6 @@ __global__ __launch_bounds__(kGenThreads) void gen_dkv_kernel(const Params p) {
 std::atomic<uint32_t> g_route{0};
 inline void set_route(int kernel, int dpad) { g_route.store((uint32_t)kernel << 16 | (uint32_t)dpad); }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool vec_ok(const void* p, int64_t ld) { return !p || (aligned16(p) && ld % 8 == 0); }
 
 template <int MODE>

@@ -332,8 +332,6 @@ __global__ __launch_bounds__(kThreads) void remove_accidental_hits_kernel(const 
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 inline int rows_per_block(int64_t cols) { return ListPack((int)cols).lpb; }   // (cols <= 2^30)
 
 int check_matrix(const char* what, const void* logits, int64_t ld, int dtype, int64_t rows, int64_t cols) {

@@ -1339,6 +1339,56 @@ int krs_gru_bwd(const void* recurrent_kernel, const uint8_t* valid, const void* 
                 void* dxz, void* da, void* h_prev, void* dh0, void* stream);
 int krs_gru_last_route(int* kernel, int* upad);
 
+/* ------------------------------------------------------------------------- *
+ * K21  Partitioned (IVF) retrieval: K8's score + top-k over the candidates of the best few leaves only
+ *
+ * The partitioning stage of ScaNN on float rows (the serving side of keras_rs_amd.layers.PartitionedRetrieval).
+ *   Index       centroids [leaves, d] with row stride ldm; the candidate rows c [n, d] (row stride ldc) REGROUPED so that
+ *               leaf l owns the stored rows [leaf_offsets[l], leaf_offsets[l+1]) (leaf_offsets int32 [leaves + 1],
+ *               ascending, from 0 to n; trusted); row_index int32 [n], the original candidate index of each stored
+ *               row, ASCENDING INSIDE EVERY LEAF; ids int32 [n] INDEXED BY ORIGINAL INDEX, or NULL.
+ *   Probe       The probed leaves of query row i are the krs_retrieval_topk result for q_i against the centroids with
+ *               k = probes: K8's order, score descending, leaf index ascending, NaN above +inf.  out_leaves
+ *               [b, probes] int32 receives them when not NULL.
+ *   Select      The result is K8's top-k over the candidates of the probed leaves only, in K8's total order: the fp32
+ *               score descending, then the ORIGINAL candidate index ascending, -0.0 as +0.0.  out_ids [b, k] is
+ *               ids[original index], or the original index when ids is NULL; out_scores [b, k] (or NULL) is the fp32
+ *               score rounded once to dtype.
+ *   Short       If the probed leaves of a query hold m < k candidates, slots m .. k-1 hold id -1 (also with ids) and
+ *               score -inf.
+ *   Bits        A (query, candidate) score leaves the MFMA chain of krs_retrieval_topk (same K steps, same
+ *               instructions, same zeroed K tail), whatever tile the query lands in.  So with probes == leaves the ids and
+ *               score bits are those of krs_retrieval_topk on the same candidates in their original order, and with
+ *               fewer probes those of krs_retrieval_topk on the rows of the probed leaves gathered in ascending
+ *               original index with ids = those indices.
+ *   Shapes      q, centroids and c share dtype (KRS_F32 / KRS_BF16).  1 <= probes <= min(leaves, 128), 1 <= k <=
+ *               min(n, 128), 1 <= d <= 512, n <= INT32_MAX, b >= 0, b * probes <= INT32_MAX, row strides >= d.
+ *               probes > 128 (with probes <= leaves), k > 128 (with k <= n), d > 512 and b * probes > 2^31 - 1 are
+ *               KRS_ERR_UNSUPPORTED with a message naming the limit: there is no slab path.  Other bad shapes, a bad
+ *               dtype, a row stride below d and a null q, centroids, c, leaf_offsets, row_index or out_ids (b > 0) are
+ *               KRS_ERR_INVALID, the shape checks first; too little workspace is KRS_ERR_WORKSPACE; every refusal comes
+ *               before the first launch.  b == 0 is a successful no-op.
+ *   Execution   On `stream`: (a) the probe, krs_retrieval_topk on the centroids; (b) the inversion of the b * probes
+ *               (query, slot) pairs into per-leaf pair lists: an integer histogram, an exclusive scan of the counts and
+ *               one of the tile counts ceil(count / 32), then each pair into its leaf's segment; (c) the scan, K8's
+ *               stage 1 per (leaf, tile of <= 32 pairs): the query tile gathered through the list, the candidate loop
+ *               over the leaf's stored rows, the queued pair carrying row_index, k pairs written per (query, slot); the
+ *               grid is the static bound ceil(b * probes / 32) + min(leaves, b * probes) and a workgroup finds its leaf
+ *               by binary search in the tile scan; (d) K8's merge of the probes lists of each query.  Integer atomics
+ *               place a pair inside its leaf's list; no result depends on that place.  Bit-identical from call to call,
+ *               no allocation, no host wait: graph-capturable.
+ * krs_retrieval_ivf_workspace_bytes: the probe's K8 workspace and its [b, probes] result, five int32 arrays of
+ * leaves + 1 and the scan's partial sums, the b * probes pair list, the b * probes * k (score, index) pairs of 8 bytes,
+ * and b * pow2(k) pairs for the merge when probes * k > 2048; each rounded up to 256.  The pairs dominate: this is more
+ * than K8's b * S * k as soon as probes > S.  > 0 for b > 0 on a supported shape, 0 otherwise.  It need not be
+ * initialised.
+ * ------------------------------------------------------------------------- */
+size_t krs_retrieval_ivf_workspace_bytes(int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k, int dtype);
+int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroids, int64_t ldm, const void* c, int64_t ldc,
+                      const int32_t* leaf_offsets, const int32_t* row_index, const int32_t* ids, int dtype, int64_t b,
+                      int64_t n, int64_t d, int64_t leaves, int probes, int k, void* out_scores, int32_t* out_ids,
+                      int32_t* out_leaves, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,9 @@ PROTOTYPES = {
     "krs_gru_fwd": (_I, [_P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _P, _P, _P, _P]),
     "krs_gru_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     "krs_gru_last_route": (_I, [_P, _P]),
+    "krs_retrieval_ivf_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I, _I, _I]),
+    "krs_retrieval_ivf": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I, _I64, _I64, _I64, _I64, _I, _I, _P, _P, _P,
+                               _P, _SZ, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -28,11 +28,16 @@
 //   * krs_retrieval_mine      the same two stages for the hard negatives of the in-batch softmax loss: stage 1 ranks
 //                             K13's corrected score (bias, accidental hits) and leaves each row's positive out of the
 //                             queue, storing its score instead.
+//   * krs_retrieval_ivf       the same two stages over the best few leaves of a partitioned index: krs_retrieval_topk on
+//                             the centroids picks each query's leaves, the (query, leaf) pairs are inverted into per-leaf
+//                             lists (histogram, two scans, fill), stage 1 runs per (leaf, tile of 32 pairs) and writes k
+//                             pairs per (query, leaf), stage 2 merges them per query.
 #include <algorithm>
 
 #include "krs_list.h"
 #include "krs_owner_tile.h"   // the vector types and acc_row, the query row of an accumulator register
 #include "krs_q8.h"
+#include "krs_scan.h"
 
 namespace krs {
 namespace {
@@ -87,12 +92,14 @@ struct Out {
   const int32_t* ids;
   int k;
   int64_t row0;
-  int64_t n;   // columns / candidates: a padding pair (never selected while n >= k) maps to -1
+  int64_t n;   // columns / candidates: a padding pair (never selected while the row has k real pairs) maps to
+               // index -1 and value -inf (krs_retrieval_ivf: the probed leaves may hold fewer than k candidates)
   __device__ __forceinline__ void emit(int64_t r, int j, uint64_t e) const {
     const uint32_t i = pair_index(e);
     const int64_t o = (row0 + r) * k + j;
-    idx[o] = (int64_t)i >= n ? -1 : ids ? ids[i] : (int32_t)i;
-    if (val) st_elem(val, val_dtype, o, key_value((uint32_t)(e >> 32)));
+    const bool pad = (int64_t)i >= n;
+    idx[o] = pad ? -1 : ids ? ids[i] : (int32_t)i;
+    if (val) st_elem(val, val_dtype, o, pad ? __uint_as_float(0xff800000u) : key_value((uint32_t)(e >> 32)));
   }
 };
 
@@ -146,7 +153,9 @@ __global__ __launch_bounds__(kListThreads) void topk_small_kernel(Src src, int64
 }
 
 // longer rows: MSD radix select of the k-th largest pair T (8-bit digits, one workgroup per row), then every pair >= T
-// -- exactly k of them, pairs are unique -- into the row's list of P slots, the rest of the list zeroed
+// -- exactly k of them, real pairs are unique -- into the row's list of P slots, the rest of the list zeroed.  A row
+// with m < k real pairs (krs_retrieval_ivf) ends with T = 0: its padding pairs, which are all equal, are left out of the
+// race for the k slots and the list is zeroed from slot m on
 template <class Src>
 __global__ __launch_bounds__(1024) void radix_select_kernel(Src src, int64_t len, int k, uint64_t* list, int64_t P) {
   __shared__ uint32_t hist[16][256];
@@ -196,12 +205,13 @@ __global__ __launch_bounds__(1024) void radix_select_kernel(Src src, int64_t len
   uint64_t* g = list + row * P;
   for (int64_t i = tid; i < len; i += blockDim.x) {
     const uint64_t e = src.pair(row, i);
-    if (e >= T) {
+    if (e >= T && e != 0) {
       const uint32_t pos = atomicAdd(&s_cnt, 1u);
-      if (pos < (uint32_t)k) g[pos] = e;   // (exactly k pass: pairs are unique)
+      if (pos < (uint32_t)k) g[pos] = e;   // (at most k pass: real pairs are unique)
     }
   }
-  for (int64_t j = k + tid; j < P; j += blockDim.x) g[j] = 0;
+  __syncthreads();
+  for (int64_t j = std::min<int64_t>(s_cnt, k) + tid; j < P; j += blockDim.x) g[j] = 0;
 }
 
 inline size_t select_list_bytes(int64_t rows, int64_t len, int k) {
@@ -266,6 +276,16 @@ struct Mine {
 struct Q8Scale {
   const float* cstep;   // [n]
   const float* qstep;   // [b]
+};
+// what the partitioned variant of stage 1 adds (krs_retrieval_ivf): the work item is (leaf, tile of <= 32 of the
+// (query, probe slot) pairs that chose the leaf) instead of (slice, query tile)
+struct Ivf {
+  const int32_t* tile_start;     // [leaves + 1] exclusive scan of ceil(count / 32); [leaves] = tiles in all
+  const int32_t* list_start;     // [leaves + 1] exclusive scan of the leaves' pair counts
+  const int32_t* list;           // [b * probes] pairs (query * probes + slot), leaf by leaf
+  const int32_t* leaf_offsets;   // [leaves + 1] stored rows of a leaf
+  const int32_t* row_index;      // [n] original index of a stored row, ascending inside a leaf
+  int leaves, probes;
 };
 
 // one wave sorts a row queue of m <= 256 pairs (4 per lane, descending), keeps the first k and returns the new
@@ -334,8 +354,14 @@ __device__ uint32_t wave_compact(uint64_t* q, int m, int k, int lane) {
 // row stride of row_bytes and a zeroed K tail; a 32-byte K step is one v_mfma_i32_32x32x32_i8 (both operands take their
 // 16 bytes from the same chunk, so how the instruction deals k to lanes does not matter), and the exact int32 dot
 // product becomes the fp32 score fmul(fmul((float)idot, cstep[cand]), qstep[row]) before it is ranked.
-template <int ES, bool VEC, bool MINE>
-__device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, const Q8Scale& q8 = Q8Scale{}) {
+// IVF (krs_retrieval_ivf): grid = an upper bound of the tiles; workgroup w finds its leaf by binary search in tile_start
+// and leaves when w is past the total.  The query tile is gathered through the leaf's pair list, the candidate loop runs
+// over the leaf's stored rows, a queued pair carries row_index[stored row] (ascending inside a leaf, so the queue cut's
+// tie argument holds), and the k pairs of tile row r go to out[pair_r].  The K loop is untouched: a (query, candidate)
+// score leaves the MFMA chain of K8 whatever tile row the query sits in.
+template <int ES, bool VEC, bool MINE, bool IVF = false>
+__device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, const Q8Scale& q8 = Q8Scale{},
+                                            const Ivf& iv = Ivf{}) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lstride = p.row_bytes + 16;
   char* qt = smem;                                                           // [kQM][lstride]
@@ -345,30 +371,62 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
   int64_t* pid = reinterpret_cast<int64_t*>(thr + kQM);                      // [kQM]  MINE: id of the row's positive
   int* posr = reinterpret_cast<int*>(pid + kQM);                             // [kQM]  MINE: the row's positive, or -1
   float* qstep = reinterpret_cast<float*>(thr + kQM);                        // [kQM]  ES == 1 (never with MINE)
+  int* qpair = reinterpret_cast<int*>(thr + kQM);                            // [kQM]  IVF: the row's pair, or -1
+  int* qrow = qpair + kQM;                                                   // [kQM]  IVF: the row's query
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int frow = lane & 31, fhalf = lane >> 5;
-  const int64_t xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int64_t slice = (slot / p.qtiles) * 8 + xcd;
-  const int64_t qtile = slot % p.qtiles;
-  if (slice >= p.S) return;
-  const int64_t q0 = qtile * kQM;
-  const int64_t s0 = std::min<int64_t>(slice * p.slice, p.n), s1 = std::min<int64_t>(s0 + p.slice, p.n);
+  int64_t slice = 0, q0 = 0, s0, s1;
+  int nq = kQM;                       // IVF: pairs of this tile
+  if constexpr (IVF) {
+    const int w = (int)blockIdx.x;
+    if (w >= iv.tile_start[iv.leaves]) return;
+    int lo = 0, hi = iv.leaves;       // tile_start[lo] <= w < tile_start[hi]: empty and unprobed leaves own no w
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (iv.tile_start[mid] <= w) lo = mid;
+      else hi = mid;
+    }
+    const int l0 = iv.list_start[lo] + (w - iv.tile_start[lo]) * kQM;
+    nq = std::min(kQM, iv.list_start[lo + 1] - l0);
+    s0 = iv.leaf_offsets[lo];
+    s1 = iv.leaf_offsets[lo + 1];
+    if (threadIdx.x < kQM) {
+      const int pr = (int)threadIdx.x < nq ? iv.list[l0 + threadIdx.x] : -1;
+      qpair[threadIdx.x] = pr;
+      qrow[threadIdx.x] = pr < 0 ? 0 : pr / iv.probes;
+    }
+    __syncthreads();
+  } else {
+    const int64_t xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    slice = (slot / p.qtiles) * 8 + xcd;
+    const int64_t qtile = slot % p.qtiles;
+    if (slice >= p.S) return;
+    q0 = qtile * kQM;
+    s0 = std::min<int64_t>(slice * p.slice, p.n);
+    s1 = std::min<int64_t>(s0 + p.slice, p.n);
+  }
+  // is tile row `row` a query?
+  auto live = [&](int row) -> bool {
+    if constexpr (IVF) return row < nq;
+    else return q0 + row < p.b;
+  };
 
   // query tile -> LDS, zero beyond b rows and d columns
   const int row_elems = p.row_bytes / (ES == 1 ? 4 : ES);
   for (int i = threadIdx.x; i < kQM * row_elems; i += blockDim.x) {
     const int r = i / row_elems, e = i % row_elems;
-    const bool ok = q0 + r < p.b && e < p.d;
+    const int64_t qr = IVF ? (int64_t)qrow[r] : q0 + r;   // the tile row's query
+    const bool ok = live(r) && e < p.d;
     if constexpr (ES == 1) {
       // e counts 4-byte words: a workspace row is row_bytes long on a 256-byte boundary and zero beyond d
       const uint32_t v = q0 + r < p.b ? *reinterpret_cast<const uint32_t*>(p.q + (q0 + r) * p.ldq + e * 4) : 0u;
       *reinterpret_cast<uint32_t*>(qt + r * lstride + e * 4) = v;
     } else if constexpr (ES == 2) {
-      const uint16_t v = ok ? reinterpret_cast<const uint16_t*>(p.q)[(q0 + r) * p.ldq + e] : 0;
+      const uint16_t v = ok ? reinterpret_cast<const uint16_t*>(p.q)[qr * p.ldq + e] : 0;
       *reinterpret_cast<uint16_t*>(qt + r * lstride + e * 2) = v;
     } else {
-      const float v = ok ? reinterpret_cast<const float*>(p.q)[(q0 + r) * p.ldq + e] : 0.0f;
+      const float v = ok ? reinterpret_cast<const float*>(p.q)[qr * p.ldq + e] : 0.0f;
       *reinterpret_cast<float*>(qt + r * lstride + e * 4) = v;
     }
   }
@@ -425,6 +483,8 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
       for (int r = 0; r < 16; ++r) iacc[r] = 0;
       if (cvalid) cstep = q8.cstep[cand];     // consecutive lanes, consecutive candidates: one coalesced load
     }
+    uint32_t cidx = (uint32_t)cand;           // the index a queued pair carries
+    if constexpr (IVF) cidx = cvalid ? (uint32_t)iv.row_index[cand] : 0u;
     for (int ks0 = 0; ks0 < nks; ks0 += 8) {
       u32x4 fb[8];
 #pragma unroll
@@ -513,9 +573,9 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
       for (int r = 0; r < 16; ++r) {
         const int row = acc_row(r, fhalf);
         const uint32_t key = order_key(acc[r]);
-        if (cvalid && q0 + row < p.b && key > t_reg[r]) {
+        if (cvalid && live(row) && key > t_reg[r]) {
           const int s = atomicAdd(&cnt[row], 1);
-          queue[row * p.cap + s] = pair_key(key, (uint32_t)cand);
+          queue[row * p.cap + s] = pair_key(key, cidx);
         }
       }
     }
@@ -539,11 +599,11 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
 
   // the slice's k best pairs per row (zeros where the slice had fewer than k candidates)
   for (int row = wave; row < kQM; row += 4) {
-    if (q0 + row >= p.b) continue;
+    if (!live(row)) continue;
     const int m = cnt[row];
     wave_compact(queue + row * p.cap, m, p.k, lane);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    uint64_t* o = p.out + ((q0 + row) * p.S + slice) * p.k;
+    uint64_t* o = p.out + (IVF ? (int64_t)qpair[row] : (q0 + row) * p.S + slice) * p.k;
     for (int j = lane; j < p.k; j += 64) o[j] = j < m ? queue[row * p.cap + j] : 0;
   }
 }
@@ -594,6 +654,34 @@ __global__ __launch_bounds__(256) void retr_stage1_q8_kernel(const Stage1 p, con
 template <int ES, bool VEC>
 __global__ __launch_bounds__(256) void retr_mine_stage1_kernel(const Stage1 p, const Mine mn) {
   stage1_body<ES, VEC, true>(p, mn);
+}
+template <int ES, bool VEC>
+__global__ __launch_bounds__(256) void retr_ivf_scan_kernel(const Stage1 p, const Ivf iv) {
+  stage1_body<ES, VEC, false, true>(p, Mine{}, Q8Scale{}, iv);
+}
+
+// ---- the inversion of krs_retrieval_ivf: (query, slot) pairs -> per-leaf pair lists ------------------------------------
+// count[leaf] += 1 per pair (integer atomics: exact whatever the order)
+__global__ __launch_bounds__(256) void ivf_count_kernel(const int32_t* probe, int64_t pairs, int leaves, int32_t* count) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= pairs) return;
+  const int leaf = probe[t];
+  if (leaf >= 0 && leaf < leaves) atomicAdd(&count[leaf], 1);
+}
+// tiles[leaf] = ceil(count / 32); entry [leaves] of both arrays stays 0, so their scans end with the totals
+__global__ __launch_bounds__(256) void ivf_tiles_kernel(const int32_t* count, int leaves, int32_t* tiles) {
+  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l > leaves) return;
+  tiles[l] = l < leaves ? (count[l] + kQM - 1) / kQM : 0;
+}
+// each pair into its leaf's segment; the place inside the segment is whatever the atomic hands out (every pair owns
+// its output list and a score does not depend on its tile row, so the result does not depend on the place)
+__global__ __launch_bounds__(256) void ivf_fill_kernel(const int32_t* probe, int64_t pairs, int leaves,
+                                                       const int32_t* list_start, int32_t* cursor, int32_t* list) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= pairs) return;
+  const int leaf = probe[t];
+  if (leaf >= 0 && leaf < leaves) list[list_start[leaf] + atomicAdd(&cursor[leaf], 1)] = (int32_t)t;
 }
 
 // stage-1 geometry of a fused call
@@ -893,4 +981,145 @@ extern "C" int krs_retrieval_mine(const void* q, int64_t ldq, const void* c, int
   uint64_t* list = reinterpret_cast<uint64_t*>(ws + align256((size_t)b * len * sizeof(uint64_t)));
   const Out out{out_idx, out_scores, KRS_F32, nullptr, k, 0, n};
   return select_rows(PairSrc{p.out, len}, b, len, k, out, list, st);
+}
+
+// ---- the partitioned index (K21) ----------------------------------------------------------------------------------------
+namespace krs {
+namespace {
+constexpr int kIvfMaxProbes = 128;
+// workspace of a krs_retrieval_ivf call, each part on a 256-byte boundary: the probe's own K8 workspace and its result,
+// the inversion arrays (count and cursor are zeroed by every call; [leaves + 1] each), the per-pair lists of the scan and
+// the merge's list
+struct IvfWorkspace {
+  size_t probe_ws, probe_ws_bytes, probe, count, cursor, tiles, list_start, tile_start, sums, list, pairs, merge, total;
+};
+inline IvfWorkspace ivf_workspace(int64_t b, int64_t leaves, int probes, int k) {
+  IvfWorkspace w;
+  const size_t ints = align256((size_t)(leaves + 1) * sizeof(int32_t));
+  const size_t bp = (size_t)b * probes;
+  w.probe_ws = 0;
+  w.probe_ws_bytes = fused_bytes(b, leaves, probes);
+  w.probe = w.probe_ws + w.probe_ws_bytes;
+  w.count = w.probe + align256(bp * sizeof(int32_t));
+  w.cursor = w.count + ints;
+  w.tiles = w.cursor + ints;
+  w.list_start = w.tiles + ints;
+  w.tile_start = w.list_start + ints;
+  w.sums = w.tile_start + ints;
+  w.list = w.sums + align256(scan::workspace_bytes(leaves + 1));
+  w.pairs = w.list + align256(bp * sizeof(int32_t));
+  w.merge = w.pairs + align256(bp * k * sizeof(uint64_t));
+  w.total = w.merge + align256(select_list_bytes(b, (int64_t)probes * k, k));
+  return w;
+}
+// the argument checks of both entry points; 0 when the shape is served
+inline int ivf_check(int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k, int dtype) {
+  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1 && leaves >= 1, "krs_retrieval_ivf: bad shape b=%lld n=%lld d=%lld leaves=%lld",
+              (long long)b, (long long)n, (long long)d, (long long)leaves);
+  KRS_REQUIRE(n <= INT32_MAX && leaves < INT32_MAX, "krs_retrieval_ivf: more than 2^31 - 1 candidates or leaves");
+  KRS_REQUIRE(probes >= 1 && probes <= leaves, "krs_retrieval_ivf: probes = %d outside [1, leaves = %lld]", probes,
+              (long long)leaves);
+  KRS_REQUIRE(k >= 1 && k <= n, "krs_retrieval_ivf: k = %d outside [1, %lld]", k, (long long)n);
+  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "krs_retrieval_ivf: bad dtype");
+  if (probes > kIvfMaxProbes)
+    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_ivf: probes = %d above the limit of %d", probes, kIvfMaxProbes);
+  if (k > kFusedMaxK)
+    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_ivf: k = %d above the limit of %d (there is no slab path)", k,
+                kFusedMaxK);
+  if (d > kFusedMaxD)
+    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_ivf: d = %lld above the limit of %d (there is no slab path)",
+                (long long)d, kFusedMaxD);
+  if (b * probes > INT32_MAX)
+    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_ivf: b * probes = %lld above 2^31 - 1", (long long)(b * probes));
+  return KRS_OK;
+}
+}  // namespace
+}  // namespace krs
+
+extern "C" size_t krs_retrieval_ivf_workspace_bytes(int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k,
+                                                    int dtype) {
+  using namespace krs;
+  if (b <= 0 || ivf_check(b, n, d, leaves, probes, k, dtype) != KRS_OK) return 0;
+  return ivf_workspace(b, leaves, probes, k).total;
+}
+
+extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroids, int64_t ldm, const void* c,
+                                 int64_t ldc, const int32_t* leaf_offsets, const int32_t* row_index, const int32_t* ids,
+                                 int dtype, int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k,
+                                 void* out_scores, int32_t* out_ids, int32_t* out_leaves, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  using namespace krs;
+  const int rc = ivf_check(b, n, d, leaves, probes, k, dtype);
+  if (rc != KRS_OK) return rc;
+  KRS_REQUIRE(ldq >= d && ldm >= d && ldc >= d, "krs_retrieval_ivf: row stride below d");
+  if (b == 0) return KRS_OK;
+  KRS_REQUIRE(q && centroids && c && leaf_offsets && row_index && out_ids, "krs_retrieval_ivf: null operand");
+  const IvfWorkspace w = ivf_workspace(b, leaves, probes, k);
+  if (!workspace || workspace_bytes < w.total)
+    return fail(KRS_ERR_WORKSPACE, "krs_retrieval_ivf: needs %zu workspace bytes, got %zu", w.total, workspace_bytes);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int es = dtype == KRS_BF16 ? 2 : 4;
+  char* ws = reinterpret_cast<char*>(workspace);
+  int32_t* probe = out_leaves ? out_leaves : reinterpret_cast<int32_t*>(ws + w.probe);
+  int32_t* count = reinterpret_cast<int32_t*>(ws + w.count);
+  int32_t* cursor = reinterpret_cast<int32_t*>(ws + w.cursor);
+  int32_t* tiles = reinterpret_cast<int32_t*>(ws + w.tiles);
+  int32_t* list_start = reinterpret_cast<int32_t*>(ws + w.list_start);
+  int32_t* tile_start = reinterpret_cast<int32_t*>(ws + w.tile_start);
+  int32_t* sums = reinterpret_cast<int32_t*>(ws + w.sums);
+  int32_t* list = reinterpret_cast<int32_t*>(ws + w.list);
+  uint64_t* pairs = reinterpret_cast<uint64_t*>(ws + w.pairs);
+  const int64_t bp = b * probes;
+
+  // a. probe: K8 on the centroids, k = probes (probes <= leaves: no padding, every id a leaf)
+  const int rp = krs_retrieval_topk(q, ldq, centroids, ldm, nullptr, dtype, b, leaves, d, probes, nullptr, probe,
+                                    ws + w.probe_ws, w.probe_ws_bytes, stream);
+  if (rp != KRS_OK) return rp;
+
+  // b. invert: histogram over leaves, the two exclusive scans, every pair into its leaf's segment
+  KRS_HIP(hipMemsetAsync(count, 0, w.tiles - w.count, st));   // count and cursor
+  const dim3 pgrid((unsigned)ceil_div(bp, 256));
+  hipLaunchKernelGGL(ivf_count_kernel, pgrid, dim3(256), 0, st, probe, bp, (int)leaves, count);
+  KRS_CHECK_LAUNCH("ivf_count_kernel");
+  hipLaunchKernelGGL(ivf_tiles_kernel, dim3((unsigned)ceil_div(leaves + 1, 256)), dim3(256), 0, st, count, (int)leaves,
+                     tiles);
+  KRS_CHECK_LAUNCH("ivf_tiles_kernel");
+  scan::exclusive(count, list_start, leaves + 1, sums, nullptr, st);
+  scan::exclusive(tiles, tile_start, leaves + 1, sums, nullptr, st);
+  KRS_CHECK_LAUNCH("scan::exclusive");
+  hipLaunchKernelGGL(ivf_fill_kernel, pgrid, dim3(256), 0, st, probe, bp, (int)leaves, list_start, cursor, list);
+  KRS_CHECK_LAUNCH("ivf_fill_kernel");
+
+  // c. scan: sum_l ceil(count_l / 32) <= floor(bp / 32) + (leaves with a pair) <= the grid launched
+  Stage1 p;
+  p.q = reinterpret_cast<const char*>(q); p.ldq = ldq;
+  p.c = reinterpret_cast<const char*>(c); p.ldc = ldc;
+  p.b = b; p.n = n; p.d = d; p.k = k; p.cap = kQueue;
+  p.slice = 0; p.S = 1; p.qtiles = 1;
+  p.row_bytes = (int)(ceil_div(d * es, 32) * 32);
+  p.out = pairs;
+  const Ivf iv{tile_start, list_start, list, leaf_offsets, row_index, (int)leaves, probes};
+  // the query tile, the row queues, cnt and thr as in krs_retrieval_topk, then the rows' pairs and queries
+  const size_t lds = (size_t)kQM * (p.row_bytes + 16) + (size_t)kQM * p.cap * sizeof(uint64_t) + 4 * kQM * sizeof(int);
+  const bool vec = (d * es) % 16 == 0 && (ldc * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(c) & 15) == 0;
+  const dim3 grid((unsigned)(ceil_div(bp, kQM) + std::min<int64_t>(leaves, bp)));
+#define KRS_IVF_SCAN(ES_, VEC_)                                                                                    \
+  {                                                                                                                \
+    auto kern = retr_ivf_scan_kernel<ES_, VEC_>;                                                                   \
+    KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                (int)lds));                                                                        \
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, iv);                                                     \
+  }
+  if (es == 2) {
+    if (vec) KRS_IVF_SCAN(2, true) else KRS_IVF_SCAN(2, false)
+  } else {
+    if (vec) KRS_IVF_SCAN(4, true) else KRS_IVF_SCAN(4, false)
+  }
+#undef KRS_IVF_SCAN
+  KRS_CHECK_LAUNCH("retr_ivf_scan_kernel");
+
+  // d. merge: the probes lists of each query; a query whose leaves hold fewer than k candidates ends in padding pairs
+  const int64_t len = (int64_t)probes * k;
+  const Out out{out_ids, out_scores, dtype, ids, k, 0, n};
+  return select_rows(PairSrc{pairs, len}, b, len, k, out, reinterpret_cast<uint64_t*>(ws + w.merge), st);
 }

@@ -8,6 +8,9 @@ from the two embedding matrices without storing the scores (K13: krs_retrieval_x
 FactorizedTopK, the evaluation metric that goes with it: every top-k accuracy and the mean reciprocal rank from the
 positive's rank among all candidates, again without the scores (K15: krs_retrieval_rank).  BruteForceRetrieval also has a
 serving form, `quantize("int8")`: an int8 candidate index scored on the int8 matrix cores (K17: krs_retrieval_topk_q8).
+PartitionedRetrieval is the approximate index: the candidates are partitioned into leaves by spherical k-means and a query
+is scored against the candidates of its best few leaves only (K21: krs_retrieval_ivf), the partitioning stage of the
+ScaNN index the reference's examples/scann.py serves from.
 
 Selection order: score descending, then candidate index ascending (-0.0 as +0.0, NaN above +inf); rows come back
 sorted.  Known divergence: for bf16 inputs keras.ops.matmul rounds the scores to bf16 before top_k, so among
@@ -33,6 +36,17 @@ def _as_tensor(x, device=None) -> torch.Tensor:
     if isinstance(x, torch.Tensor):
         return x
     return torch.as_tensor(np.asarray(x), device=device)
+
+
+def _int32_ids(ids: torch.Tensor) -> torch.Tensor:
+    """Candidate ids as an int32 vector (what the kernels' `ids` operand is)."""
+    if ids.dim() != 1:
+        raise ValueError(f"`candidate_ids` must be a tensor of rank 1, received shape {tuple(ids.shape)}")
+    if ids.dtype != torch.int32:
+        if ids.dtype.is_floating_point or (ids.numel() and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31)):
+            raise ValueError("`candidate_ids` must be integers that fit int32")
+        ids = ids.to(torch.int32)
+    return ids
 
 
 class Retrieval(base.Layer):
@@ -104,12 +118,7 @@ class BruteForceRetrieval(Retrieval):
         if emb.dtype not in (torch.float32, torch.bfloat16):
             emb = emb.to(torch.float32)
         if ids is not None:
-            if ids.dim() != 1:
-                raise ValueError(f"`candidate_ids` must be a tensor of rank 1, received shape {tuple(ids.shape)}")
-            if ids.dtype != torch.int32:
-                if ids.dtype.is_floating_point or (ids.numel() and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31)):
-                    raise ValueError("`candidate_ids` must be integers that fit int32")
-                ids = ids.to(torch.int32)
+            ids = _int32_ids(ids)
         if self.quantization_mode:
             return self._update_quantized(emb, ids)
         with torch.no_grad():
@@ -238,6 +247,226 @@ class BruteForceRetrieval(Retrieval):
         if self.return_scores:
             return scores, top_ids
         return top_ids
+
+
+def partition_layout(assignments: torch.Tensor, num_leaves: int):
+    """The stored layout of a partition: (row_index int32 [N], leaf_offsets int32 [num_leaves + 1]).  row_index is a
+    stable sort of the original indices by leaf, so it ascends inside every leaf; leaf l owns the stored rows
+    [leaf_offsets[l], leaf_offsets[l + 1]).  Torch ops on the assignments' device."""
+    a = assignments.to(torch.int64)
+    row_index = torch.sort(a, stable=True).indices.to(torch.int32)
+    counts = torch.bincount(a, minlength=num_leaves)
+    leaf_offsets = torch.zeros((num_leaves + 1,), dtype=torch.int64, device=a.device)
+    leaf_offsets[1:] = torch.cumsum(counts, 0)
+    return row_index, leaf_offsets.to(torch.int32)
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+class PartitionedRetrieval(Retrieval):
+    """Approximate top-k retrieval over a partitioned candidate set (the tree stage of ScaNN, which the reference's
+    examples/scann.py serves from): the candidates are grouped into `num_leaves` leaves, a query ranks the leaves by
+    q . centroid and is scored against the candidates of its `num_leaves_to_search` best leaves only (include/krs.h,
+    K21).  Inside those leaves the result is BruteForceRetrieval's: fp32 score descending, then candidate index
+    ascending.  With num_leaves_to_search == num_leaves it IS BruteForceRetrieval's, bit for bit.  A query whose leaves
+    hold fewer than k candidates ends in id -1, score -inf.  k <= 128, D <= 512, num_leaves_to_search <= 128.
+
+    `update_candidates` builds the index and is not capturable (it waits on the host): spherical k-means, ScaNN's choice
+    for dot products.  The first centroids are `num_leaves` candidates drawn on the host from `seed`, normalized; each of
+    the `training_iterations` Lloyd steps assigns every candidate to its best centroid with K8 (k = 1: a tie goes to the
+    lowest leaf) and replaces a centroid by the normalized sum of its members, summed in stored order by K1's CSR bags (a
+    fixed order: the same input and seed give the same assignments); an empty leaf keeps its centroid.
+    `from_partition` takes a clustering made elsewhere.  state_dict() holds the index (`candidate_rows` regrouped leaf
+    by leaf, `leaf_offsets`, `row_index`, `centroids`, `candidate_ids`); loading it restores the index without training.
+    `call` reads nothing back and replays from a captured graph."""
+
+    _INDEX = ("candidate_rows", "leaf_offsets", "row_index", "centroids", "candidate_ids")
+    _ASSIGN_CHUNK = 1 << 18       # candidates per assignment call: 64 workspace bytes each
+
+    def __init__(self, candidate_embeddings=None, candidate_ids=None, k: int = 10, return_scores: bool = True,
+                 num_leaves: int | None = None, num_leaves_to_search: int | None = None, training_iterations: int = 12,
+                 seed: int = 0, **kwargs: Any):
+        super().__init__(k=k, return_scores=return_scores, **kwargs)
+        if not _is_int(k) or not 1 <= k <= retrieval_ops.IVF_MAX_K:
+            raise ValueError(f"`k` should be an integer in [1, {retrieval_ops.IVF_MAX_K}]. Received: k={k!r}")
+        if num_leaves is not None and (not _is_int(num_leaves) or num_leaves < 1):
+            raise ValueError(f"`num_leaves` should be an integer >= 1 or None. Received: num_leaves={num_leaves!r}")
+        if num_leaves_to_search is not None and (
+                not _is_int(num_leaves_to_search) or not 1 <= num_leaves_to_search <= retrieval_ops.IVF_MAX_PROBES
+                or (num_leaves is not None and num_leaves_to_search > num_leaves)):
+            raise ValueError("`num_leaves_to_search` should be an integer in [1, min(num_leaves, "
+                             f"{retrieval_ops.IVF_MAX_PROBES})] or None. Received: "
+                             f"num_leaves_to_search={num_leaves_to_search!r}, num_leaves={num_leaves!r}")
+        if not _is_int(training_iterations) or training_iterations < 0:
+            raise ValueError("`training_iterations` should be an integer >= 0. Received: "
+                             f"training_iterations={training_iterations!r}")
+        if not _is_int(seed):
+            raise ValueError(f"`seed` should be an integer. Received: seed={seed!r}")
+        self.num_leaves, self.num_leaves_to_search = num_leaves, num_leaves_to_search
+        self.training_iterations, self.seed = int(training_iterations), int(seed)
+        for name in self._INDEX:
+            self.register_buffer(name, None, persistent=True)
+        self._converted: dict[torch.dtype, tuple] = {}     # (rows, centroids) in another query dtype
+        if candidate_embeddings is None:
+            if candidate_ids is not None:
+                raise ValueError("You cannot provide `candidate_ids` without providing `candidate_embeddings`")
+        else:
+            self.update_candidates(candidate_embeddings, candidate_ids)
+
+    @classmethod
+    def from_partition(cls, candidate_embeddings, centroids, assignments, candidate_ids=None, **kwargs: Any):
+        """An index over a clustering made elsewhere: centroids [leaves, D], assignments integer [N] in [0, leaves), the
+        leaf of each candidate.  No training; the other arguments are the constructor's (num_leaves is the centroids')."""
+        cen = _as_tensor(centroids)
+        if cen.dim() != 2 or cen.shape[0] < 1:
+            raise ValueError(f"`centroids` must be a tensor of rank 2 (num_leaves, embedding_size), received shape "
+                             f"{tuple(cen.shape)}")
+        if kwargs.setdefault("num_leaves", cen.shape[0]) != cen.shape[0]:
+            raise ValueError(f"`num_leaves` = {kwargs['num_leaves']} differs from the {cen.shape[0]} rows of `centroids`")
+        layer = cls(**kwargs)
+        emb, ids = layer._checked_candidates(candidate_embeddings, candidate_ids)
+        if cen.shape[1] != emb.shape[1]:
+            raise ValueError(f"`centroids` has {cen.shape[1]} columns, `candidate_embeddings` has {emb.shape[1]}")
+        a = _as_tensor(assignments)
+        if a.dtype.is_floating_point or a.dtype == torch.bool or tuple(a.shape) != (emb.shape[0],):
+            raise ValueError(f"`assignments` should be {emb.shape[0]} integers, one leaf per candidate. Received: "
+                             f"`assignments.shape` = {tuple(a.shape)}, dtype {a.dtype}")
+        if a.numel() and (int(a.min()) < 0 or int(a.max()) >= cen.shape[0]):
+            raise ValueError(f"`assignments` should be inside [0, {cen.shape[0]}). Received values from {int(a.min())} "
+                             f"to {int(a.max())}")
+        layer._set_index(emb, cen.detach().to(emb.device, emb.dtype), a.detach().to(emb.device), ids)
+        return layer
+
+    def _checked_candidates(self, candidate_embeddings, candidate_ids):
+        self._validate_candidate_embeddings_and_ids(candidate_embeddings, candidate_ids)
+        emb = _as_tensor(candidate_embeddings).detach()
+        ids = None if candidate_ids is None else _int32_ids(_as_tensor(candidate_ids).detach())
+        if emb.dtype not in (torch.float32, torch.bfloat16):
+            emb = emb.to(torch.float32)
+        if emb.shape[1] > retrieval_ops.IVF_MAX_D:
+            raise ValueError(f"The partitioned index takes embeddings of at most D = {retrieval_ops.IVF_MAX_D} columns, "
+                             f"the candidates have D = {emb.shape[1]}.")
+        return emb.to(self._device), None if ids is None else ids.to(self._device)
+
+    def _leaves_for(self, n: int) -> int:
+        leaves = self.num_leaves if self.num_leaves is not None else max(1, int(round(float(np.sqrt(n)))))
+        if leaves > n:
+            raise ValueError(f"`num_leaves` = {leaves} is more than the number of candidates ({n}).")
+        return leaves
+
+    def probes(self) -> int:
+        """Leaves searched per query: num_leaves_to_search, or max(1, leaves // 10) capped at 128."""
+        leaves = self.centroids.shape[0] if self.centroids is not None else self.num_leaves
+        if self.num_leaves_to_search is not None:
+            return self.num_leaves_to_search
+        return min(retrieval_ops.IVF_MAX_PROBES, max(1, leaves // 10))
+
+    def update_candidates(self, candidate_embeddings, candidate_ids=None) -> None:
+        emb, ids = self._checked_candidates(candidate_embeddings, candidate_ids)
+        leaves = self._leaves_for(emb.shape[0])
+        L.require_device(emb, "PartitionedRetrieval candidates")
+        centroids, assignments = self._train(emb, leaves)
+        self._set_index(emb, centroids, assignments, ids)
+
+    def _assign(self, emb: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+        out = torch.empty((emb.shape[0],), dtype=torch.int32, device=emb.device)
+        for r0 in range(0, emb.shape[0], self._ASSIGN_CHUNK):
+            r1 = min(emb.shape[0], r0 + self._ASSIGN_CHUNK)
+            out[r0:r1] = retrieval_ops.retrieval_topk(emb[r0:r1], centroids, 1, want_scores=False)[1][:, 0]
+        return out
+
+    def _train(self, emb: torch.Tensor, leaves: int):
+        """Spherical k-means (class docstring).  Returns (centroids [leaves, D] in emb's dtype, assignments int32 [N])."""
+        from keras_rs_amd import embedding_ops
+
+        n = emb.shape[0]
+        sample = np.sort(np.random.default_rng(self.seed).choice(n, size=leaves, replace=False))
+        cen32 = torch.nn.functional.normalize(emb[torch.as_tensor(sample, device=emb.device)].to(torch.float32), dim=1)
+        bags = embedding_ops.FusedBags([emb.contiguous()], [(0, "sum", 0)])
+        for _ in range(self.training_iterations):
+            a = self._assign(emb, cen32.to(emb.dtype))
+            row_index, leaf_offsets = partition_layout(a, leaves)
+            sums, _ = bags.forward(row_index, leaves, offsets=leaf_offsets, out_dtype=torch.float32)
+            filled = (leaf_offsets[1:] > leaf_offsets[:-1])[:, None]
+            cen32 = torch.where(filled, torch.nn.functional.normalize(sums, dim=1), cen32)
+        centroids = cen32.to(emb.dtype)
+        return centroids, self._assign(emb, centroids)
+
+    def _set_index(self, emb, centroids, assignments, ids) -> None:
+        leaves = centroids.shape[0]
+        if self.num_leaves_to_search is not None and self.num_leaves_to_search > leaves:
+            raise ValueError(f"`num_leaves_to_search` = {self.num_leaves_to_search} is more than the {leaves} leaves.")
+        row_index, leaf_offsets = partition_layout(assignments, leaves)
+        self.candidate_rows = emb[row_index.to(torch.int64)].contiguous()
+        self.leaf_offsets, self.row_index = leaf_offsets, row_index
+        self.centroids = centroids.contiguous()
+        self.candidate_ids = None if ids is None else ids.contiguous()
+        self._converted.clear()
+        self.built = True
+
+    @property
+    def assignments(self) -> torch.Tensor:
+        """The leaf of every candidate, int32 [N] by original index (read off the stored layout)."""
+        counts = (self.leaf_offsets[1:] - self.leaf_offsets[:-1]).to(torch.int64)
+        leaf = torch.repeat_interleave(torch.arange(counts.shape[0], dtype=torch.int32, device=counts.device), counts)
+        out = torch.empty_like(leaf)
+        out[self.row_index.to(torch.int64)] = leaf
+        return out
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        """A saved index replaces whatever the layer holds: the buffers take the saved shapes and dtypes."""
+        for name in self._INDEX:
+            saved = state_dict.get(prefix + name)
+            if saved is not None:
+                setattr(self, name, torch.empty_like(saved, device=self._device))
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        self._converted.clear()
+        self.built = self.candidate_rows is not None
+
+    def _apply(self, fn, recurse=True):
+        self._converted.clear()       # (.to() / .cuda(): the converted copies follow the buffers at the next call)
+        return super()._apply(fn, recurse)
+
+    def quantize(self, mode: str = "int8") -> None:
+        raise NotImplementedError("PartitionedRetrieval has no quantized form: the int8 candidate index lives in "
+                                  "BruteForceRetrieval.quantize('int8') (K17, krs_retrieval_topk_q8).")
+
+    def _index_as(self, dtype: torch.dtype):
+        if self.candidate_rows.dtype == dtype:
+            return self.candidate_rows, self.centroids
+        conv = self._converted.get(dtype)
+        if conv is None:
+            conv = self._converted[dtype] = (self.candidate_rows.to(dtype), self.centroids.to(dtype))
+        return conv
+
+    def call(self, inputs, return_leaves: bool = False):
+        if self.candidate_rows is None:
+            raise ValueError("No candidates: call `update_candidates` before using the layer.")
+        q = _as_tensor(inputs)
+        if q.dim() != 2 or q.shape[1] != self.candidate_rows.shape[1]:
+            raise ValueError(f"The query must have shape (batch, {self.candidate_rows.shape[1]}), "
+                             f"received {tuple(q.shape)}")
+        L.require_device(q, "PartitionedRetrieval query")
+        L.require_device(self.candidate_rows, "PartitionedRetrieval candidates")
+        # keras.ops.matmul promotion: float32 x bfloat16 -> float32
+        dt = torch.promote_types(q.dtype, self.candidate_rows.dtype)
+        if dt not in (torch.float32, torch.bfloat16):
+            raise L.KrsError(f"PartitionedRetrieval: unsupported query dtype {q.dtype} (float32 / bfloat16)")
+        rows, centroids = self._index_as(dt)
+        out = retrieval_ops.retrieval_ivf(q.detach().to(dt), centroids, rows, self.leaf_offsets, self.row_index, self.k,
+                                          self.probes(), ids=self.candidate_ids, want_scores=self.return_scores,
+                                          want_leaves=return_leaves)
+        if return_leaves:          # (an extension: the probed leaves [batch, probes] as a last item)
+            return (out[0], out[1], out[2]) if self.return_scores else (out[1], out[2])
+        return (out[0], out[1]) if self.return_scores else out[1]
+
+    def get_config(self) -> dict:
+        config = super().get_config()
+        config.update({"num_leaves": self.num_leaves, "num_leaves_to_search": self.num_leaves_to_search,
+                       "training_iterations": self.training_iterations, "seed": self.seed})
+        return config
 
 
 class HardNegativeMining(base.Layer):

@@ -1,5 +1,6 @@
-"""Host side of K8, K11, K13, K14, K15 and K17: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and
-mining), over krs_retrieval_topk_q8 (serving from an int8 index), over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored
+"""Host side of K8, K11, K13, K14, K15, K17 and K21: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and
+mining), over krs_retrieval_topk_q8 (serving from an int8 index), over krs_retrieval_ivf (serving from a partitioned
+index), over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored
 scores), over krs_retrieval_xent_fwd / krs_retrieval_xent_bwd (the in-batch softmax loss that never stores the scores),
 over krs_retrieval_mine (the same loss on each row's hardest negatives) and over krs_retrieval_rank (the positive's
 rank among all candidates, for evaluation), all of include/krs.h.
@@ -126,6 +127,59 @@ def retrieval_topk_q8(query: torch.Tensor, cand_q: torch.Tensor, cand_step: torc
                                        ws.numel(), L.stream_ptr())
     L.check(rc, "krs_retrieval_topk_q8")
     return scores, out_ids
+
+
+# ---- K21: K8 over the best few leaves of a partitioned index ------------------------------------------------------------
+IVF_MAX_K = 128            # most results per query of krs_retrieval_ivf (there is no slab path)
+IVF_MAX_D = 512            # its widest embedding
+IVF_MAX_PROBES = 128       # most leaves searched per query
+
+
+def retrieval_ivf_workspace_bytes(b: int, n: int, d: int, leaves: int, probes: int, k: int, dtype: torch.dtype) -> int:
+    dt = L.BF16 if dtype == torch.bfloat16 else L.F32
+    return int(L.lib().krs_retrieval_ivf_workspace_bytes(b, n, d, leaves, probes, k, dt))
+
+
+def _int32_vector(t: torch.Tensor, length: int, what: str) -> None:
+    L.require_device(t, what)
+    if t.dtype != torch.int32 or tuple(t.shape) != (length,) or not t.is_contiguous():
+        raise L.KrsError(f"{what} must be a contiguous int32 vector of {length} entries, got {t.dtype} {tuple(t.shape)}")
+
+
+def retrieval_ivf(query: torch.Tensor, centroids: torch.Tensor, rows: torch.Tensor, leaf_offsets: torch.Tensor,
+                  row_index: torch.Tensor, k: int, probes: int, *, ids: torch.Tensor | None = None,
+                  want_scores: bool = True, want_leaves: bool = False):
+    """Top-k of query [B, D] over the candidates of its `probes` best leaves (include/krs.h, K21).  centroids
+    [leaves, D] and rows [N, D] (the candidates regrouped leaf by leaf) share the query's dtype (fp32 / bf16);
+    leaf_offsets int32 [leaves + 1], row_index int32 [N] (original index of a stored row, ascending inside a leaf), ids
+    int32 [N] by original index or None.  Returns (scores [B, k] in the input dtype or None, int32 ids [B, k]), and the
+    probed leaves int32 [B, probes] as a third item with want_leaves.  A query whose leaves hold fewer than k candidates
+    ends in id -1, score -inf."""
+    q = L.rowmajor(query, "retrieval_ivf query")
+    m = L.rowmajor(centroids, "retrieval_ivf centroids")
+    c = L.rowmajor(rows, "retrieval_ivf rows")
+    if q.dtype != c.dtype or q.dtype != m.dtype:
+        raise L.KrsError("retrieval_ivf: query, centroids and rows must share a dtype")
+    b, d = q.shape
+    n, leaves = c.shape[0], m.shape[0]
+    if c.shape[1] != d or m.shape[1] != d:
+        raise L.KrsError(f"retrieval_ivf: query width {d} differs from the index width ({m.shape[1]} centroids, "
+                         f"{c.shape[1]} rows)")
+    _int32_vector(leaf_offsets, leaves + 1, "retrieval_ivf: leaf_offsets")
+    _int32_vector(row_index, n, "retrieval_ivf: row_index")
+    if ids is not None:
+        _int32_vector(ids, n, "retrieval_ivf: ids")
+    scores = torch.empty((b, k), dtype=q.dtype, device=q.device) if want_scores else None
+    out_ids = torch.empty((b, k), dtype=torch.int32, device=q.device)
+    out_leaves = torch.empty((b, probes), dtype=torch.int32, device=q.device) if want_leaves else None
+    ws = torch.empty(max(1, retrieval_ivf_workspace_bytes(b, n, d, leaves, probes, k, q.dtype)), dtype=torch.uint8,
+                     device=q.device)
+    rc = L.lib().krs_retrieval_ivf(L.ptr(q), q.stride(0) if b > 1 else d, L.ptr(m), m.stride(0) if leaves > 1 else d,
+                                   L.ptr(c), c.stride(0) if n > 1 else d, L.ptr(leaf_offsets), L.ptr(row_index),
+                                   L.ptr(ids), L.fdtype(q), b, n, d, leaves, probes, k, L.ptr(scores), L.ptr(out_ids),
+                                   L.ptr(out_leaves), L.ptr(ws), ws.numel(), L.stream_ptr())
+    L.check(rc, "krs_retrieval_ivf")
+    return (scores, out_ids, out_leaves) if want_leaves else (scores, out_ids)
 
 
 # ---- K11: the training head ---------------------------------------------------------------------------------------

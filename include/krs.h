@@ -835,6 +835,54 @@ int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int64_t ldc, c
                        int dtype, int64_t b, int64_t n, int64_t d, int k,
                        void* out_scores, int32_t* out_ids,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* KRS_RETRIEVAL_SLAB_BYTES in the environment, read on each call: a positive integer replaces the two-step path's slab
+ * budget of 1 GiB (the fp32 score slab plus the selection lists of one query chunk) for krs_retrieval_topk and
+ * krs_retrieval_topk_workspace_bytes; a chunk is never shorter than one query row.  A diagnostic: with a budget of a few
+ * kilobytes a small call runs the chunk loop several times.  The size query and the call must see the same value.
+ *
+ * Diagnostic: where the calling thread's last krs_topk_rows, krs_retrieval_topk, krs_retrieval_topk_q8 or
+ * krs_retrieval_mine ran, as planned by csrc/retrieval_plan.h (the planner the four entries themselves run).  All zero
+ * after a refused call, a call with no query rows and before the first call.  (The probe of krs_retrieval_ivf is a
+ * krs_retrieval_topk call and leaves its record; krs_retrieval_ivf plans its own scan and merge and records nothing.)
+ *   kernel           KRS_RETR_FUSED   stage 1 (a 32-query tile against a candidate slice, row queues in LDS) and the merge
+ *                                     of the S slice lists of each row
+ *                    KRS_RETR_SLAB    krs_gemm into an fp32 slab of chunk_rows query rows, then the row selection, per chunk
+ *                    KRS_RETR_ROWS    krs_topk_rows: the row selection alone
+ *   variant          KRS_RETR_VARIANT_TOPK / _Q8 / _MINE / _ROWS: the entry
+ *   es               bytes of an input element: 4, 2, or 1 (the int8 index)
+ *   vec              FUSED: the VEC build of stage 1 (16-byte candidate loads: d * es and ldc * es multiples of 16, the
+ *                    candidates on a 16-byte boundary); 0 = element loads
+ *   S, qtiles, slice FUSED: candidate slices (a multiple of 8), query tiles of 32 rows, candidates per slice (a multiple
+ *                    of 128); S * slice >= n
+ *   row_bytes        FUSED: K extent of the LDS query tile, d * es rounded up to 32 bytes
+ *   lds_bytes        FUSED: dynamic LDS of the stage-1 launch
+ *   blocks           FUSED: workgroups of the stage-1 launch, S * qtiles
+ *   select           the selection: KRS_SELECT_LDS (rows of at most 2048 pairs: one LDS sort per row), KRS_SELECT_RADIX
+ *                    (radix select of the k best, one LDS sort of them) or KRS_SELECT_RADIX_MERGE (k > 2048: blocks of 2048
+ *                    sorted in LDS, merged in global memory)
+ *   select_len       pairs per selected row: S * k (FUSED), n (SLAB), cols (ROWS)
+ *   select_p         slots sorted per row, a power of two: at or above select_len on KRS_SELECT_LDS, at or above k else
+ *   select_launches  kernel launches of one selection (SLAB: per chunk)
+ *   chunks           SLAB: query chunks, each one krs_gemm and one selection
+ *   chunk_rows       SLAB: query rows of a full chunk (the last chunk has b - (chunks - 1) * chunk_rows)
+ * Fields that do not apply are 0.  krs_retrieval_last_route returns `kernel`; `route` may be NULL. */
+enum { KRS_RETR_NONE = 0, KRS_RETR_FUSED, KRS_RETR_SLAB, KRS_RETR_ROWS };
+enum { KRS_RETR_VARIANT_NONE = 0, KRS_RETR_VARIANT_TOPK, KRS_RETR_VARIANT_Q8, KRS_RETR_VARIANT_MINE, KRS_RETR_VARIANT_ROWS };
+enum { KRS_SELECT_NONE = 0, KRS_SELECT_LDS, KRS_SELECT_RADIX, KRS_SELECT_RADIX_MERGE };
+typedef struct krs_retrieval_route {
+  int32_t kernel, variant, es, vec, S, qtiles, row_bytes, lds_bytes, select, select_launches;
+  int64_t slice, blocks, select_len, select_p, chunks, chunk_rows;
+} krs_retrieval_route;
+int krs_retrieval_last_route(krs_retrieval_route* route);
+/* Diagnostic, host only, no GPU needed: where the entry `variant` names WOULD run with these arguments
+ * (KRS_RETRIEVAL_SLAB_BYTES is honoured as the entry honours it).  KRS_RETR_VARIANT_ROWS reads b as rows, n as cols, ldc
+ * as ld and c as x; d and ldq are ignored.  KRS_RETR_VARIANT_Q8 reads dtype as the query dtype and c as the int8 rows.
+ * q and c are read as VALUES only (nullness, alignment); the operands the planner does not look at (outputs, steps,
+ * ids, the workspace) are taken as given and large enough.  No HIP call is made and the last-route record is untouched.
+ * Fills *route (all zero when nothing would be launched) and returns what the entry returns before its first launch:
+ * KRS_OK, KRS_ERR_INVALID or KRS_ERR_UNSUPPORTED. */
+int krs_retrieval_plan_route(int variant, const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b,
+                             int64_t n, int64_t d, int k, krs_retrieval_route* route);
 
 /* ------------------------------------------------------------------------- *
  * K9  Ranking losses (keras_rs.losses): unreduced loss and logit gradient in one pass

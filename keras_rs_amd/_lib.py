@@ -81,6 +81,13 @@ class DotRoute(C.Structure):
                  "lds_bytes")] + [("blocks", C.c_int64)]
 
 
+class RetrievalRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in
+                ("kernel", "variant", "es", "vec", "S", "qtiles", "row_bytes", "lds_bytes", "select",
+                 "select_launches")] + [(name, C.c_int64) for name in
+                                        ("slice", "blocks", "select_len", "select_p", "chunks", "chunk_rows")]
+
+
 # Prototype of every entry point include/krs.h declares, in its order: name -> (restype, argtypes).  Any pointer is a
 # void* (pass L.ptr(t), an int or None; ctypes arrays and C.byref(struct) where the C side takes an array or a struct).
 # tests/test_capi_symbols.py parses the header and checks this table against it row by row.
@@ -151,6 +158,8 @@ PROTOTYPES = {
     "krs_topk_rows": (_I, [_P, _P, _F, _I64, _I, _I64, _I64, _I, _P, _P, _P, _SZ, _P]),
     "krs_retrieval_topk_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I, _I]),
     "krs_retrieval_topk": (_I, [_P, _I64, _P, _I64, _P, _I, _I64, _I64, _I64, _I, _P, _P, _P, _SZ, _P]),
+    "krs_retrieval_last_route": (_I, [_P]),
+    "krs_retrieval_plan_route": (_I, [_I, _P, _I64, _P, _I64, _I, _I64, _I64, _I64, _I, _P]),
     "krs_pairwise_loss": (_I, [_I, _P, _I64, _I, _P, _P, _P, _F, _F, _I64, _I64, _P, _P, _P]),
     "krs_listmle_loss": (_I, [_P, _I64, _I, _P, _P, _P, _F, _F, _I64, _I64, _P, _P, _P]),
     "krs_ranking_metrics": (_I, [_P, _I64, _I, _P, _P, _P, _I64, _I64, _F, _P, _P, _I64, _I, _U64, _P, _P, _P, _I, _I64,

@@ -32,12 +32,19 @@
 //                             the centroids picks each query's leaves, the (query, leaf) pairs are inverted into per-leaf
 //                             lists (histogram, two scans, fill), stage 1 runs per (leaf, tile of 32 pairs) and writes k
 //                             pairs per (query, leaf), stage 2 merges them per query.
+//
+// Every shape decision of the four planned entries (krs_topk_rows, krs_retrieval_topk, _q8, _mine) -- the path, stage 1's
+// geometry, build, LDS and grid, the chunks, the workspace sections, the selection route -- is made by retrieval_plan.h, a
+// host-only header; this file checks arguments, plans there and launches what the plan names, and records the plan's route
+// for krs_retrieval_last_route.  krs_retrieval_ivf keeps its own geometry and takes the shared arithmetic only.
 #include <algorithm>
+#include <cstdlib>
 
 #include "krs_list.h"
 #include "krs_owner_tile.h"   // the vector types and acc_row, the query row of an accumulator register
 #include "krs_q8.h"
 #include "krs_scan.h"
+#include "retrieval_plan.h"
 
 namespace krs {
 namespace {
@@ -45,15 +52,13 @@ namespace {
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kSortMax = 2048;    // longest list sorted in LDS (16 KB of pairs)
-constexpr int kQM = 32;           // query rows of a stage-1 workgroup (one MFMA block)
-constexpr int kCB = 128;          // candidates per stage-1 step (4 waves x 32)
-constexpr int kFusedMaxK = 128;   // k + kCB <= kQueue
-constexpr int kQueue = 256;       // per-row queue slots: one wave sorts a queue in registers (4 pairs per lane)
-constexpr int kFusedMaxD = 512;
-constexpr int kStage1Groups = 2048;                   // target workgroups of stage 1
-constexpr int kMinSlice = 8192;                       // shortest slice once the target is met
-constexpr size_t kSlabBudget = size_t(1) << 30;       // two-step path: fp32 slab + sort lists per chunk
+// every constant and shape decision of K8 lives in retrieval_plan.h
+using rplan::kCB;
+using rplan::kFusedMaxD;
+using rplan::kFusedMaxK;
+using rplan::kQM;
+using rplan::kQueue;
+using rplan::kSortMax;
 
 __device__ __forceinline__ float key_value(uint32_t k) {
   if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
@@ -214,37 +219,30 @@ __global__ __launch_bounds__(1024) void radix_select_kernel(Src src, int64_t len
   for (int64_t j = std::min<int64_t>(s_cnt, k) + tid; j < P; j += blockDim.x) g[j] = 0;
 }
 
-inline size_t select_list_bytes(int64_t rows, int64_t len, int k) {
-  if (len <= kSortMax) return 0;
-  return (size_t)rows * (size_t)pow2_at_least<int64_t>(k) * sizeof(uint64_t);
-}
-
-// top-k of `rows` rows of `len` pairs each -> out; `list` = select_list_bytes of workspace
+// top-k of `rows` rows of sel.len pairs each -> out, by the launches sel names (rplan::plan_select); `list` = the
+// rplan::select_list_bytes of workspace
 template <class Src>
-int select_rows(const Src& src, int64_t rows, int64_t len, int k, const Out& out, uint64_t* list, hipStream_t st) {
+int select_rows(const Src& src, int64_t rows, const rplan::Select& sel, int k, const Out& out, uint64_t* list,
+                hipStream_t st) {
   if (rows <= 0) return KRS_OK;
-  if (len <= kSortMax) {
-    hipLaunchKernelGGL(topk_small_kernel<Src>, dim3((unsigned)rows), dim3(kListThreads), 0, st, src, len,
-                       (int)pow2_at_least(len), out);
+  if (sel.route == KRS_SELECT_LDS) {
+    hipLaunchKernelGGL(topk_small_kernel<Src>, dim3((unsigned)rows), dim3(kListThreads), 0, st, src, sel.len, sel.sort_n,
+                       out);
     KRS_CHECK_LAUNCH("topk_small_kernel");
     return KRS_OK;
   }
-  const int64_t P = pow2_at_least<int64_t>(k);
-  hipLaunchKernelGGL(radix_select_kernel<Src>, dim3((unsigned)rows), dim3(1024), 0, st, src, len, k, list, P);
+  const int64_t P = sel.P;
+  hipLaunchKernelGGL(radix_select_kernel<Src>, dim3((unsigned)rows), dim3(1024), 0, st, src, sel.len, k, list, P);
   KRS_CHECK_LAUNCH("radix_select_kernel");
-  const int64_t n = std::min<int64_t>(P, kSortMax);
-  const unsigned sblocks = (unsigned)(rows * (P / n));
-  hipLaunchKernelGGL(sort_block_kernel, dim3(sblocks), dim3(kListThreads), 0, st, list, P, (int64_t)0);
-  KRS_CHECK_LAUNCH("sort_block_kernel");
-  for (int64_t kk = 2 * n; kk <= P; kk <<= 1) {
-    for (int64_t j = kk >> 1; j >= n; j >>= 1) {
-      hipLaunchKernelGGL(sort_step_kernel, dim3((unsigned)ceil_div(rows * (P / 2), 256)), dim3(256), 0, st, list, rows,
-                         P, kk, j);
-      KRS_CHECK_LAUNCH("sort_step_kernel");
-    }
-    hipLaunchKernelGGL(sort_block_kernel, dim3(sblocks), dim3(kListThreads), 0, st, list, P, kk);
-    KRS_CHECK_LAUNCH("sort_block_kernel");
-  }
+  const unsigned sblocks = (unsigned)(rows * (P / sel.sort_n));
+  rplan::for_each_sort_launch(sel, [&](int64_t kk, int64_t j) {
+    if (j == 0)
+      hipLaunchKernelGGL(sort_block_kernel, dim3(sblocks), dim3(kListThreads), 0, st, list, P, kk);
+    else
+      hipLaunchKernelGGL(sort_step_kernel, dim3((unsigned)ceil_div(rows * (P / 2), 256)), dim3(256), 0, st, list, rows, P,
+                         kk, j);
+  });
+  KRS_CHECK_LAUNCH("sort_block_kernel / sort_step_kernel");
   hipLaunchKernelGGL(emit_kernel, dim3((unsigned)ceil_div(rows * k, 256)), dim3(256), 0, st, list, rows, P, out);
   KRS_CHECK_LAUNCH("emit_kernel");
   return KRS_OK;
@@ -684,175 +682,214 @@ __global__ __launch_bounds__(256) void ivf_fill_kernel(const int32_t* probe, int
   if (leaf >= 0 && leaf < leaves) list[list_start[leaf] + atomicAdd(&cursor[leaf], 1)] = (int32_t)t;
 }
 
-// stage-1 geometry of a fused call
-struct Plan {
-  int S, qtiles;
-  int64_t slice;
-};
-inline Plan fused_plan(int64_t b, int64_t n) {
-  Plan pl;
-  pl.qtiles = (int)ceil_div(b, kQM);
-  int64_t s = ceil_div(kStage1Groups, pl.qtiles);
-  s = std::min(s, ceil_div(n, kMinSlice));   // few query tiles: longer slices, fewer lists for the merge
-  s = std::max<int64_t>(8, ceil_div(s, 8) * 8);
-  pl.slice = ceil_div(ceil_div(n, s), kCB) * kCB;
-  pl.S = (int)(ceil_div(ceil_div(n, pl.slice), 8) * 8);
-  return pl;
-}
-inline bool fused_path(int64_t d, int k) { return k <= kFusedMaxK && d <= kFusedMaxD; }
+// ---- the four planned entries: check, plan (retrieval_plan.h), launch what the plan names ---------------------------------
+// where the calling thread's last planned entry ran (krs_retrieval_last_route): cleared when an entry starts, written when
+// it has queued its last kernel, so a refused call and a call without query rows leave "none"
+thread_local krs_retrieval_route g_route = {};
 
-inline size_t fused_bytes(int64_t b, int64_t n, int k) {
-  const Plan pl = fused_plan(b, n);
-  const int64_t len = (int64_t)pl.S * k;
-  return align256((size_t)b * len * sizeof(uint64_t)) + align256(select_list_bytes(b, len, k));
+// the two-step path's budget: KRS_RETRIEVAL_SLAB_BYTES when it is a positive integer, read on each call
+inline int64_t slab_budget() {
+  const char* e = getenv("KRS_RETRIEVAL_SLAB_BYTES");
+  if (e && *e) {
+    char* end = nullptr;
+    const long long v = strtoll(e, &end, 10);
+    if (end != e && *end == 0 && v > 0) return (int64_t)v;
+  }
+  return rplan::kSlabBudget;
 }
-// rows of one chunk of the two-step path
-inline int64_t chunk_rows(int64_t b, int64_t n, int k) {
-  const size_t per_row = (size_t)n * sizeof(float) + select_list_bytes(1, n, k);
-  return std::max<int64_t>(1, std::min<int64_t>(b, (int64_t)(kSlabBudget / per_row)));
+
+inline const char* entry_name(int variant) {
+  switch (variant) {
+    case KRS_RETR_VARIANT_TOPK: return "krs_retrieval_topk";
+    case KRS_RETR_VARIANT_Q8: return "krs_retrieval_topk_q8";
+    case KRS_RETR_VARIANT_MINE: return "krs_retrieval_mine";
+    default: return "krs_topk_rows";
+  }
 }
+inline rplan::Call make_call(int variant, int es, const void* c, int64_t ldc, int64_t b, int64_t n, int64_t d, int k) {
+  rplan::Call call;
+  call.variant = variant;
+  call.b = b; call.n = n; call.d = d; call.k = k;
+  call.es = es;
+  call.ldc = ldc;
+  call.c_addr = (uint64_t)reinterpret_cast<uintptr_t>(c);
+  call.slab_budget = slab_budget();
+  return call;
+}
+
+// What an entry checks before its first launch, apart from the operands the planner never looks at (outputs, steps, ids,
+// the workspace), and the call's plan.  krs_retrieval_plan_route answers from this alone.  ROWS: q is unused, c = x,
+// ldc = ld, b = rows, n = cols.  Q8: dtype is the query's.  pl is "none" unless KRS_OK is returned with b > 0.
+inline int check_and_plan(int variant, const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b,
+                          int64_t n, int64_t d, int k, rplan::Plan& pl) {
+  pl = rplan::Plan();
+  const char* who = entry_name(variant);
+  int es = dtype == KRS_BF16 ? 2 : 4;
+  if (variant == KRS_RETR_VARIANT_ROWS) {
+    KRS_REQUIRE(b >= 0 && n >= 1, "krs_topk_rows: bad shape [%lld, %lld]", (long long)b, (long long)n);
+    KRS_REQUIRE(n <= INT32_MAX, "krs_topk_rows: more than 2^31 - 1 columns");
+    KRS_REQUIRE(k >= 1 && k <= n, "krs_topk_rows: k = %d outside [1, %lld]", k, (long long)n);
+    KRS_REQUIRE(ldc >= n, "krs_topk_rows: ld < cols");
+    KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "krs_topk_rows: bad dtype");
+    if (b == 0) return KRS_OK;
+    KRS_REQUIRE(c, "krs_topk_rows: null operand");
+    d = 0;
+  } else {
+    KRS_REQUIRE(variant == KRS_RETR_VARIANT_TOPK || variant == KRS_RETR_VARIANT_Q8 || variant == KRS_RETR_VARIANT_MINE,
+                "krs_retrieval_plan_route: bad variant %d", variant);
+    const int64_t kmax = variant == KRS_RETR_VARIANT_MINE ? n - 1 : n;   // mining leaves the positive out
+    KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1, "%s: bad shape b=%lld n=%lld d=%lld", who, (long long)b, (long long)n,
+                (long long)d);
+    KRS_REQUIRE(n <= INT32_MAX, "%s: more than 2^31 - 1 candidates", who);
+    KRS_REQUIRE(k >= 1 && k <= kmax, "%s: k = %d outside [1, %lld]", who, k, (long long)kmax);
+    if (variant == KRS_RETR_VARIANT_MINE)
+      KRS_REQUIRE(rplan::fused_path(d, k), "krs_retrieval_mine: k = %d above %d or d = %lld above %d", k, kFusedMaxK,
+                  (long long)d, kFusedMaxD);
+    KRS_REQUIRE(ldq >= d && ldc >= d, "%s: row stride below d", who);
+    KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "%s: bad %sdtype", who, variant == KRS_RETR_VARIANT_Q8 ? "query " : "");
+    if (variant == KRS_RETR_VARIANT_Q8) {
+      es = 1;
+      if (k > kFusedMaxK)
+        return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_topk_q8: k = %d above the limit of %d (there is no slab path)", k,
+                    kFusedMaxK);
+      if (d > kFusedMaxD)
+        return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_topk_q8: d = %lld above the limit of %d (there is no slab path)",
+                    (long long)d, kFusedMaxD);
+    }
+    if (b == 0) return KRS_OK;
+    KRS_REQUIRE(q && c, "%s: null operand", who);
+  }
+  pl = rplan::plan_retrieval(make_call(variant, es, c, ldc, b, n, d, k));
+  if (pl.status != KRS_OK) return fail(pl.status, "%s: %s", who, pl.why);
+  return KRS_OK;
+}
+
+// stage 1's arguments from the plan; the slice lists go to the start of the workspace
+inline Stage1 stage1_args(const rplan::Plan& pl, const void* q, int64_t ldq, const void* c, int64_t ldc, int64_t b,
+                          int64_t n, int64_t d, int k, char* ws) {
+  Stage1 p;
+  p.q = reinterpret_cast<const char*>(q); p.ldq = ldq;
+  p.c = reinterpret_cast<const char*>(c); p.ldc = ldc;
+  p.b = b; p.n = n; p.d = d; p.k = k; p.cap = kQueue;
+  p.slice = pl.slice; p.S = pl.S; p.qtiles = pl.qtiles;
+  p.row_bytes = pl.row_bytes;
+  p.out = reinterpret_cast<uint64_t*>(ws + pl.off_lists);
+  return p;
+}
+// one stage-1 launch with the plan's grid and dynamic LDS
+#define KRS_STAGE1_LAUNCH(KERN, ...)                                                                               \
+  {                                                                                                                \
+    auto kern = KERN;                                                                                              \
+    KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                (int)pl.lds_bytes));                                                               \
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.blocks), dim3(256), (size_t)pl.lds_bytes, st, __VA_ARGS__);         \
+  }
+// the (ES, VEC) build the plan names
+#define KRS_STAGE1_BUILD(KERN, ...)                                                                                \
+  if (pl.route.es == 2) {                                                                                          \
+    if (pl.vec) KRS_STAGE1_LAUNCH((KERN<2, true>), __VA_ARGS__) else KRS_STAGE1_LAUNCH((KERN<2, false>), __VA_ARGS__) \
+  } else {                                                                                                         \
+    if (pl.vec) KRS_STAGE1_LAUNCH((KERN<4, true>), __VA_ARGS__) else KRS_STAGE1_LAUNCH((KERN<4, false>), __VA_ARGS__) \
+  }
 
 }  // namespace
 }  // namespace krs
 
-// krs_gemm workspace of the largest chunk product (full chunks and the last, shorter one)
-static size_t gemm_chunk_bytes(int64_t b, int64_t bc, int64_t n, int64_t d) {
-  const size_t full = krs_gemm_workspace_bytes(bc, n, d, 0);
-  const size_t tail = b % bc ? krs_gemm_workspace_bytes(b % bc, n, d, 0) : 0;
-  return krs::align256(std::max(full, tail));
+extern "C" int krs_retrieval_last_route(krs_retrieval_route* route) {
+  if (route) *route = krs::g_route;
+  return krs::g_route.kernel;
+}
+
+extern "C" int krs_retrieval_plan_route(int variant, const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype,
+                                        int64_t b, int64_t n, int64_t d, int k, krs_retrieval_route* route) {
+  krs::rplan::Plan pl;
+  const int rc = krs::check_and_plan(variant, q, ldq, c, ldc, dtype, b, n, d, k, pl);
+  if (route) *route = pl.route;
+  return rc;
 }
 
 extern "C" size_t krs_topk_rows_workspace_bytes(int64_t rows, int64_t cols, int k) {
   using namespace krs;
   if (rows <= 0 || cols <= 0 || k < 1) return 0;
-  return select_list_bytes(rows, cols, k);
+  return (size_t)rplan::plan_retrieval(make_call(KRS_RETR_VARIANT_ROWS, 4, nullptr, cols, rows, cols, 0, k)).total;
 }
 
 extern "C" int krs_topk_rows(const void* x, const void* boost, float boost_scale, int64_t ld, int dtype, int64_t rows,
                              int64_t cols, int k, int32_t* out_idx, float* out_keys, void* workspace,
                              size_t workspace_bytes, void* stream) {
   using namespace krs;
-  KRS_REQUIRE(rows >= 0 && cols >= 1, "krs_topk_rows: bad shape [%lld, %lld]", (long long)rows, (long long)cols);
-  KRS_REQUIRE(cols <= INT32_MAX, "krs_topk_rows: more than 2^31 - 1 columns");
-  KRS_REQUIRE(k >= 1 && k <= cols, "krs_topk_rows: k = %d outside [1, %lld]", k, (long long)cols);
-  KRS_REQUIRE(ld >= cols, "krs_topk_rows: ld < cols");
-  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "krs_topk_rows: bad dtype");
-  if (rows == 0) return KRS_OK;
-  KRS_REQUIRE(x && out_idx, "krs_topk_rows: null operand");
-  const size_t need = krs_topk_rows_workspace_bytes(rows, cols, k);
+  g_route = krs_retrieval_route{};
+  rplan::Plan pl;
+  const int rc = check_and_plan(KRS_RETR_VARIANT_ROWS, nullptr, 0, x, ld, dtype, rows, cols, 0, k, pl);
+  if (rc != KRS_OK || rows == 0) return rc;
+  KRS_REQUIRE(out_idx, "krs_topk_rows: null operand");
+  const size_t need = (size_t)pl.total;
   if (need && (!workspace || workspace_bytes < need))
     return fail(KRS_ERR_WORKSPACE, "krs_topk_rows: needs %zu workspace bytes, got %zu", need, workspace_bytes);
   const MatSrc src{x, boost, ld, dtype, boost_scale, 0};
   const Out out{out_idx, out_keys, KRS_F32, nullptr, k, 0, cols};
-  return select_rows(src, rows, cols, k, out, reinterpret_cast<uint64_t*>(workspace),
-                     reinterpret_cast<hipStream_t>(stream));
+  const int rs = select_rows(src, rows, pl.sel, k, out, reinterpret_cast<uint64_t*>(workspace),
+                             reinterpret_cast<hipStream_t>(stream));
+  if (rs == KRS_OK) g_route = pl.route;
+  return rs;
 }
 
 extern "C" size_t krs_retrieval_topk_workspace_bytes(int64_t b, int64_t n, int64_t d, int k, int dtype) {
   using namespace krs;
-  (void)dtype;
   if (b <= 0 || n <= 0 || d <= 0 || k < 1) return 0;
-  if (fused_path(d, k)) return fused_bytes(b, n, k);
-  const int64_t bc = chunk_rows(b, n, k);
-  return align256((size_t)bc * n * sizeof(float)) + align256(select_list_bytes(bc, n, k)) + gemm_chunk_bytes(b, bc, n, d);
+  return (size_t)rplan::plan_retrieval(make_call(KRS_RETR_VARIANT_TOPK, dtype == KRS_BF16 ? 2 : 4, nullptr, d, b, n, d, k))
+      .total;
 }
 
 extern "C" int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int64_t ldc, const int32_t* ids, int dtype,
                                   int64_t b, int64_t n, int64_t d, int k, void* out_scores, int32_t* out_ids,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   using namespace krs;
-  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1, "krs_retrieval_topk: bad shape b=%lld n=%lld d=%lld", (long long)b,
-              (long long)n, (long long)d);
-  KRS_REQUIRE(n <= INT32_MAX, "krs_retrieval_topk: more than 2^31 - 1 candidates");
-  KRS_REQUIRE(k >= 1 && k <= n, "krs_retrieval_topk: k = %d outside [1, %lld]", k, (long long)n);
-  KRS_REQUIRE(ldq >= d && ldc >= d, "krs_retrieval_topk: row stride below d");
-  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "krs_retrieval_topk: bad dtype");
-  if (b == 0) return KRS_OK;
-  KRS_REQUIRE(q && c && out_ids, "krs_retrieval_topk: null operand");
-  const size_t need = krs_retrieval_topk_workspace_bytes(b, n, d, k, dtype);
+  g_route = krs_retrieval_route{};
+  rplan::Plan pl;
+  const int rc = check_and_plan(KRS_RETR_VARIANT_TOPK, q, ldq, c, ldc, dtype, b, n, d, k, pl);
+  if (rc != KRS_OK || b == 0) return rc;
+  KRS_REQUIRE(out_ids, "krs_retrieval_topk: null operand");
+  const size_t need = (size_t)pl.total;
   if (!workspace || workspace_bytes < need)
     return fail(KRS_ERR_WORKSPACE, "krs_retrieval_topk: needs %zu workspace bytes, got %zu", need, workspace_bytes);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int es = dtype == KRS_BF16 ? 2 : 4;
   char* ws = reinterpret_cast<char*>(workspace);
+  uint64_t* list = reinterpret_cast<uint64_t*>(ws + pl.off_merge);
 
-  if (fused_path(d, k)) {
-    const Plan pl = fused_plan(b, n);
-    Stage1 p;
-    p.q = reinterpret_cast<const char*>(q); p.ldq = ldq;
-    p.c = reinterpret_cast<const char*>(c); p.ldc = ldc;
-    p.b = b; p.n = n; p.d = d; p.k = k; p.cap = kQueue;
-    p.slice = pl.slice; p.S = pl.S; p.qtiles = pl.qtiles;
-    p.row_bytes = (int)(ceil_div(d * es, 32) * 32);
-    p.out = reinterpret_cast<uint64_t*>(ws);
-    const size_t lds = (size_t)kQM * (p.row_bytes + 16) + (size_t)kQM * p.cap * sizeof(uint64_t) + 2 * kQM * sizeof(int);
-    const bool vec = (d * es) % 16 == 0 && (ldc * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(c) & 15) == 0;
-    const dim3 grid((unsigned)((int64_t)pl.S * pl.qtiles));
-#define KRS_STAGE1(ES_, VEC_)                                                                                      \
-  {                                                                                                                \
-    auto kern = retr_stage1_kernel<ES_, VEC_>;                                                                     \
-    KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                (int)lds));                                                                        \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);                                                         \
-  }
-    if (es == 2) {
-      if (vec) KRS_STAGE1(2, true) else KRS_STAGE1(2, false)
-    } else {
-      if (vec) KRS_STAGE1(4, true) else KRS_STAGE1(4, false)
-    }
-#undef KRS_STAGE1
+  if (pl.route.kernel == KRS_RETR_FUSED) {
+    const Stage1 p = stage1_args(pl, q, ldq, c, ldc, b, n, d, k, ws);
+    KRS_STAGE1_BUILD(retr_stage1_kernel, p)
     KRS_CHECK_LAUNCH("retr_stage1_kernel");
-    const int64_t len = (int64_t)pl.S * k;
-    uint64_t* list = reinterpret_cast<uint64_t*>(ws + align256((size_t)b * len * sizeof(uint64_t)));
     const Out out{out_ids, out_scores, dtype, ids, k, 0, n};
-    return select_rows(PairSrc{p.out, len}, b, len, k, out, list, st);
+    const int rs = select_rows(PairSrc{p.out, pl.sel.len}, b, pl.sel, k, out, list, st);
+    if (rs == KRS_OK) g_route = pl.route;
+    return rs;
   }
 
-  // two-step path: krs_gemm into an fp32 slab of bc query rows, then the row selection
-  const int64_t bc = chunk_rows(b, n, k);
-  float* slab = reinterpret_cast<float*>(ws);
-  char* after = ws + align256((size_t)bc * n * sizeof(float));
-  uint64_t* list = reinterpret_cast<uint64_t*>(after);
-  char* gws = after + align256(select_list_bytes(bc, n, k));
-  const size_t gws_bytes = gemm_chunk_bytes(b, bc, n, d);
-  for (int64_t r0 = 0; r0 < b; r0 += bc) {
-    const int64_t rows = std::min(bc, b - r0);
-    const int rc = krs_gemm(reinterpret_cast<const char*>(q) + r0 * ldq * es, ldq, 0, c, ldc, 1, slab, n, rows, n, d,
-                            dtype, KRS_F32, nullptr, gws, gws_bytes, stream);
-    if (rc != KRS_OK) return rc;
+  // two-step path: krs_gemm into an fp32 slab of the chunk's query rows, then the row selection
+  float* slab = reinterpret_cast<float*>(ws + pl.off_slab);
+  for (int64_t i = 0; i < pl.chunks; ++i) {
+    const int64_t r0 = rplan::chunk_row0(pl, i), rows = rplan::chunk_len(pl, i, b);
+    const int rg = krs_gemm(reinterpret_cast<const char*>(q) + r0 * ldq * pl.route.es, ldq, 0, c, ldc, 1, slab, n, rows, n,
+                            d, dtype, KRS_F32, nullptr, ws + pl.off_gemm, (size_t)pl.gemm_bytes, stream);
+    if (rg != KRS_OK) return rg;
     const MatSrc src{slab, nullptr, n, KRS_F32, 0.0f, 0};
     const Out out{out_ids, out_scores, dtype, ids, k, r0, n};
-    const int rc2 = select_rows(src, rows, n, k, out, list, st);
-    if (rc2 != KRS_OK) return rc2;
+    const int rs = select_rows(src, rows, pl.sel, k, out, list, st);
+    if (rs != KRS_OK) return rs;
   }
+  g_route = pl.route;
   return KRS_OK;
 }
 
 // ---- the int8 candidate index (K17) ------------------------------------------------------------------------------------
-namespace krs {
-namespace {
-// workspace of a krs_retrieval_topk_q8 call: the slice lists and the merge list of the fused path, then the quantized
-// query rows (row_bytes each) and their steps
-struct Q8Workspace {
-  int row_bytes;
-  size_t lists, qq, qstep, total;
-};
-inline Q8Workspace q8_workspace(int64_t b, int64_t n, int64_t d, int k) {
-  Q8Workspace w;
-  w.row_bytes = (int)(ceil_div(d, 32) * 32);
-  w.lists = fused_bytes(b, n, k);
-  w.qq = w.lists;
-  w.qstep = w.qq + align256((size_t)b * w.row_bytes);
-  w.total = w.qstep + align256((size_t)b * sizeof(float));
-  return w;
-}
-}  // namespace
-}  // namespace krs
-
+// workspace: the slice lists and the merge list of the fused path, then the quantized query rows (row_bytes each) and
+// their steps (the plan's off_qq, off_qstep)
 extern "C" size_t krs_retrieval_topk_q8_workspace_bytes(int64_t b, int64_t n, int64_t d, int k) {
   using namespace krs;
-  if (b <= 0 || n <= 0 || d <= 0 || k < 1 || !fused_path(d, k)) return 0;
-  return q8_workspace(b, n, d, k).total;
+  if (b <= 0 || n <= 0 || d <= 0 || k < 1 || !rplan::fused_path(d, k)) return 0;
+  return (size_t)rplan::plan_retrieval(make_call(KRS_RETR_VARIANT_Q8, 1, nullptr, d, b, n, d, k)).total;
 }
 
 extern "C" int krs_retrieval_topk_q8(const void* q, int64_t ldq, int q_dtype, const int8_t* cq, int64_t ldc,
@@ -860,69 +897,40 @@ extern "C" int krs_retrieval_topk_q8(const void* q, int64_t ldq, int q_dtype, co
                                      void* out_scores, int out_dtype, int32_t* out_ids, int* err_flag, void* workspace,
                                      size_t workspace_bytes, void* stream) {
   using namespace krs;
-  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1, "krs_retrieval_topk_q8: bad shape b=%lld n=%lld d=%lld", (long long)b,
-              (long long)n, (long long)d);
-  KRS_REQUIRE(n <= INT32_MAX, "krs_retrieval_topk_q8: more than 2^31 - 1 candidates");
-  KRS_REQUIRE(k >= 1 && k <= n, "krs_retrieval_topk_q8: k = %d outside [1, %lld]", k, (long long)n);
-  KRS_REQUIRE(ldq >= d && ldc >= d, "krs_retrieval_topk_q8: row stride below d");
-  KRS_REQUIRE(q_dtype == KRS_F32 || q_dtype == KRS_BF16, "krs_retrieval_topk_q8: bad query dtype");
+  g_route = krs_retrieval_route{};
   KRS_REQUIRE(out_dtype == KRS_F32 || out_dtype == KRS_BF16, "krs_retrieval_topk_q8: bad output dtype");
-  if (k > kFusedMaxK)
-    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_topk_q8: k = %d above the limit of %d (there is no slab path)", k,
-                kFusedMaxK);
-  if (d > kFusedMaxD)
-    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_topk_q8: d = %lld above the limit of %d (there is no slab path)",
-                (long long)d, kFusedMaxD);
-  if (b == 0) return KRS_OK;
-  KRS_REQUIRE(q && cq && cstep && out_ids, "krs_retrieval_topk_q8: null operand");
-  const Q8Workspace w = q8_workspace(b, n, d, k);
-  if (!workspace || workspace_bytes < w.total)
-    return fail(KRS_ERR_WORKSPACE, "krs_retrieval_topk_q8: needs %zu workspace bytes, got %zu", w.total, workspace_bytes);
+  rplan::Plan pl;
+  const int rc = check_and_plan(KRS_RETR_VARIANT_Q8, q, ldq, cq, ldc, q_dtype, b, n, d, k, pl);
+  if (rc != KRS_OK || b == 0) return rc;
+  KRS_REQUIRE(cstep && out_ids, "krs_retrieval_topk_q8: null operand");
+  const size_t need = (size_t)pl.total;
+  if (!workspace || workspace_bytes < need)
+    return fail(KRS_ERR_WORKSPACE, "krs_retrieval_topk_q8: needs %zu workspace bytes, got %zu", need, workspace_bytes);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
-  int8_t* qq = reinterpret_cast<int8_t*>(ws + w.qq);
-  float* qstep = reinterpret_cast<float*>(ws + w.qstep);
+  int8_t* qq = reinterpret_cast<int8_t*>(ws + pl.off_qq);
+  float* qstep = reinterpret_cast<float*>(ws + pl.off_qstep);
 
   hipLaunchKernelGGL(quantize_queries_q8_kernel, dim3((unsigned)ceil_div(b, 4)), dim3(256), 0, st, q, ldq, q_dtype, b,
-                     (int)d, w.row_bytes, qq, qstep, err_flag);
+                     (int)d, pl.row_bytes, qq, qstep, err_flag);
   KRS_CHECK_LAUNCH("quantize_queries_q8_kernel");
 
-  const Plan pl = fused_plan(b, n);
-  Stage1 p;
-  p.q = reinterpret_cast<const char*>(qq); p.ldq = w.row_bytes;
-  p.c = reinterpret_cast<const char*>(cq); p.ldc = ldc;
-  p.b = b; p.n = n; p.d = d; p.k = k; p.cap = kQueue;
-  p.slice = pl.slice; p.S = pl.S; p.qtiles = pl.qtiles;
-  p.row_bytes = w.row_bytes;
-  p.out = reinterpret_cast<uint64_t*>(ws);
+  const Stage1 p = stage1_args(pl, qq, pl.row_bytes, cq, ldc, b, n, d, k, ws);
   const Q8Scale q8{cstep, qstep};
-  // the query tile, the row queues, cnt and thr as in krs_retrieval_topk, then the query steps
-  const size_t lds = (size_t)kQM * (p.row_bytes + 16) + (size_t)kQM * p.cap * sizeof(uint64_t) + 2 * kQM * sizeof(int) +
-                     kQM * sizeof(float);
-  const bool vec = d % 16 == 0 && ldc % 16 == 0 && (reinterpret_cast<uintptr_t>(cq) & 15) == 0;
-  const dim3 grid((unsigned)((int64_t)pl.S * pl.qtiles));
-#define KRS_STAGE1_Q8(VEC_)                                                                                        \
-  {                                                                                                                \
-    auto kern = retr_stage1_q8_kernel<VEC_>;                                                                       \
-    KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                (int)lds));                                                                        \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, q8);                                                     \
-  }
-  if (vec) KRS_STAGE1_Q8(true) else KRS_STAGE1_Q8(false)
-#undef KRS_STAGE1_Q8
+  if (pl.vec) KRS_STAGE1_LAUNCH(retr_stage1_q8_kernel<true>, p, q8) else KRS_STAGE1_LAUNCH(retr_stage1_q8_kernel<false>, p, q8)
   KRS_CHECK_LAUNCH("retr_stage1_q8_kernel");
-  const int64_t len = (int64_t)pl.S * k;
-  uint64_t* list = reinterpret_cast<uint64_t*>(ws + align256((size_t)b * len * sizeof(uint64_t)));
   const Out out{out_ids, out_scores, out_dtype, ids, k, 0, n};
-  return select_rows(PairSrc{p.out, len}, b, len, k, out, list, st);
+  const int rs = select_rows(PairSrc{p.out, pl.sel.len}, b, pl.sel, k, out, reinterpret_cast<uint64_t*>(ws + pl.off_merge), st);
+  if (rs == KRS_OK) g_route = pl.route;
+  return rs;
 }
 
 // ---- hard-negative mining of the in-batch softmax loss (K14) ---------------------------------------------------------
 extern "C" size_t krs_retrieval_mine_workspace_bytes(int64_t b, int64_t n, int64_t d, int k, int dtype) {
   using namespace krs;
-  (void)dtype;
-  if (b <= 0 || n <= 1 || d <= 0 || k < 1 || !fused_path(d, k)) return 0;
-  return fused_bytes(b, n, k);
+  if (b <= 0 || n <= 1 || d <= 0 || k < 1 || !rplan::fused_path(d, k)) return 0;
+  return (size_t)rplan::plan_retrieval(make_call(KRS_RETR_VARIANT_MINE, dtype == KRS_BF16 ? 2 : 4, nullptr, d, b, n, d, k))
+      .total;
 }
 
 extern "C" int krs_retrieval_mine(const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b, int64_t n,
@@ -930,58 +938,30 @@ extern "C" int krs_retrieval_mine(const void* q, int64_t ldq, const void* c, int
                                   int id_dtype, float hit_value, int32_t* out_idx, float* out_scores, float* pos_score,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   using namespace krs;
-  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1, "krs_retrieval_mine: bad shape b=%lld n=%lld d=%lld", (long long)b,
-              (long long)n, (long long)d);
-  KRS_REQUIRE(n <= INT32_MAX, "krs_retrieval_mine: more than 2^31 - 1 candidates");
-  KRS_REQUIRE(k >= 1 && k <= n - 1, "krs_retrieval_mine: k = %d outside [1, n - 1 = %lld]", k, (long long)(n - 1));
-  KRS_REQUIRE(fused_path(d, k), "krs_retrieval_mine: k = %d above %d or d = %lld above %d", k, kFusedMaxK, (long long)d,
-              kFusedMaxD);
-  KRS_REQUIRE(ldq >= d && ldc >= d, "krs_retrieval_mine: row stride below d");
-  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "krs_retrieval_mine: bad dtype");
+  g_route = krs_retrieval_route{};
   KRS_REQUIRE(id_dtype == KRS_I32 || id_dtype == KRS_I64, "krs_retrieval_mine: bad id dtype");
-  if (b == 0) return KRS_OK;
-  KRS_REQUIRE(q && c && out_idx && out_scores && pos_score, "krs_retrieval_mine: null operand");
-  const size_t need = krs_retrieval_mine_workspace_bytes(b, n, d, k, dtype);
+  rplan::Plan pl;
+  const int rc = check_and_plan(KRS_RETR_VARIANT_MINE, q, ldq, c, ldc, dtype, b, n, d, k, pl);
+  if (rc != KRS_OK || b == 0) return rc;
+  KRS_REQUIRE(out_idx && out_scores && pos_score, "krs_retrieval_mine: null operand");
+  const size_t need = (size_t)pl.total;
   if (!workspace || workspace_bytes < need)
     return fail(KRS_ERR_WORKSPACE, "krs_retrieval_mine: needs %zu workspace bytes, got %zu", need, workspace_bytes);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int es = dtype == KRS_BF16 ? 2 : 4;
   char* ws = reinterpret_cast<char*>(workspace);
 
-  const Plan pl = fused_plan(b, n);
-  Stage1 p;
-  p.q = reinterpret_cast<const char*>(q); p.ldq = ldq;
-  p.c = reinterpret_cast<const char*>(c); p.ldc = ldc;
-  p.b = b; p.n = n; p.d = d; p.k = k; p.cap = kQueue;
-  p.slice = pl.slice; p.S = pl.S; p.qtiles = pl.qtiles;
-  p.row_bytes = (int)(ceil_div(d * es, 32) * 32);
-  p.out = reinterpret_cast<uint64_t*>(ws);
+  const Stage1 p = stage1_args(pl, q, ldq, c, ldc, b, n, d, k, ws);
   const Mine mn{pos, cand_bias, cand_ids, id_dtype == KRS_I64, hit_value, pos_score};
-  // the query tile, the row queues, cnt and thr as in krs_retrieval_topk, then the positives' ids and the positives
-  const size_t lds = (size_t)kQM * (p.row_bytes + 16) + (size_t)kQM * p.cap * sizeof(uint64_t) + 2 * kQM * sizeof(int) +
-                     kQM * sizeof(int64_t) + kQM * sizeof(int);
-  const bool vec = (d * es) % 16 == 0 && (ldc * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(c) & 15) == 0;
-  const dim3 grid((unsigned)((int64_t)pl.S * pl.qtiles));
-#define KRS_MINE1(ES_, VEC_)                                                                                       \
-  {                                                                                                                \
-    auto kern = retr_mine_stage1_kernel<ES_, VEC_>;                                                                \
-    KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                (int)lds));                                                                        \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, mn);                                                     \
-  }
-  if (es == 2) {
-    if (vec) KRS_MINE1(2, true) else KRS_MINE1(2, false)
-  } else {
-    if (vec) KRS_MINE1(4, true) else KRS_MINE1(4, false)
-  }
-#undef KRS_MINE1
+  KRS_STAGE1_BUILD(retr_mine_stage1_kernel, p, mn)
   KRS_CHECK_LAUNCH("retr_mine_stage1_kernel");
   // the slice merge: every row has n - 1 >= k queued candidates in all, so no padding pair is selected
-  const int64_t len = (int64_t)pl.S * k;
-  uint64_t* list = reinterpret_cast<uint64_t*>(ws + align256((size_t)b * len * sizeof(uint64_t)));
   const Out out{out_idx, out_scores, KRS_F32, nullptr, k, 0, n};
-  return select_rows(PairSrc{p.out, len}, b, len, k, out, list, st);
+  const int rs = select_rows(PairSrc{p.out, pl.sel.len}, b, pl.sel, k, out, reinterpret_cast<uint64_t*>(ws + pl.off_merge), st);
+  if (rs == KRS_OK) g_route = pl.route;
+  return rs;
 }
+#undef KRS_STAGE1_BUILD
+#undef KRS_STAGE1_LAUNCH
 
 // ---- the partitioned index (K21) ----------------------------------------------------------------------------------------
 namespace krs {
@@ -993,12 +973,12 @@ constexpr int kIvfMaxProbes = 128;
 struct IvfWorkspace {
   size_t probe_ws, probe_ws_bytes, probe, count, cursor, tiles, list_start, tile_start, sums, list, pairs, merge, total;
 };
-inline IvfWorkspace ivf_workspace(int64_t b, int64_t leaves, int probes, int k) {
+inline IvfWorkspace ivf_workspace(int64_t b, int64_t d, int64_t leaves, int probes, int k, int dtype) {
   IvfWorkspace w;
   const size_t ints = align256((size_t)(leaves + 1) * sizeof(int32_t));
   const size_t bp = (size_t)b * probes;
   w.probe_ws = 0;
-  w.probe_ws_bytes = fused_bytes(b, leaves, probes);
+  w.probe_ws_bytes = krs_retrieval_topk_workspace_bytes(b, leaves, d, probes, dtype);   // (a multiple of 256)
   w.probe = w.probe_ws + w.probe_ws_bytes;
   w.count = w.probe + align256(bp * sizeof(int32_t));
   w.cursor = w.count + ints;
@@ -1009,7 +989,7 @@ inline IvfWorkspace ivf_workspace(int64_t b, int64_t leaves, int probes, int k) 
   w.list = w.sums + align256(scan::workspace_bytes(leaves + 1));
   w.pairs = w.list + align256(bp * sizeof(int32_t));
   w.merge = w.pairs + align256(bp * k * sizeof(uint64_t));
-  w.total = w.merge + align256(select_list_bytes(b, (int64_t)probes * k, k));
+  w.total = w.merge + align256((size_t)rplan::select_list_bytes(b, rplan::plan_select((int64_t)probes * k, k)));
   return w;
 }
 // the argument checks of both entry points; 0 when the shape is served
@@ -1040,7 +1020,7 @@ extern "C" size_t krs_retrieval_ivf_workspace_bytes(int64_t b, int64_t n, int64_
                                                     int dtype) {
   using namespace krs;
   if (b <= 0 || ivf_check(b, n, d, leaves, probes, k, dtype) != KRS_OK) return 0;
-  return ivf_workspace(b, leaves, probes, k).total;
+  return ivf_workspace(b, d, leaves, probes, k, dtype).total;
 }
 
 extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroids, int64_t ldm, const void* c,
@@ -1054,7 +1034,7 @@ extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroi
   KRS_REQUIRE(ldq >= d && ldm >= d && ldc >= d, "krs_retrieval_ivf: row stride below d");
   if (b == 0) return KRS_OK;
   KRS_REQUIRE(q && centroids && c && leaf_offsets && row_index && out_ids, "krs_retrieval_ivf: null operand");
-  const IvfWorkspace w = ivf_workspace(b, leaves, probes, k);
+  const IvfWorkspace w = ivf_workspace(b, d, leaves, probes, k, dtype);
   if (!workspace || workspace_bytes < w.total)
     return fail(KRS_ERR_WORKSPACE, "krs_retrieval_ivf: needs %zu workspace bytes, got %zu", w.total, workspace_bytes);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1096,12 +1076,12 @@ extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroi
   p.c = reinterpret_cast<const char*>(c); p.ldc = ldc;
   p.b = b; p.n = n; p.d = d; p.k = k; p.cap = kQueue;
   p.slice = 0; p.S = 1; p.qtiles = 1;
-  p.row_bytes = (int)(ceil_div(d * es, 32) * 32);
+  p.row_bytes = rplan::row_bytes(d, es);
   p.out = pairs;
   const Ivf iv{tile_start, list_start, list, leaf_offsets, row_index, (int)leaves, probes};
   // the query tile, the row queues, cnt and thr as in krs_retrieval_topk, then the rows' pairs and queries
-  const size_t lds = (size_t)kQM * (p.row_bytes + 16) + (size_t)kQM * p.cap * sizeof(uint64_t) + 4 * kQM * sizeof(int);
-  const bool vec = (d * es) % 16 == 0 && (ldc * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(c) & 15) == 0;
+  const size_t lds = (size_t)rplan::stage1_lds(p.row_bytes, KRS_RETR_VARIANT_TOPK, 2 * kQM);
+  const bool vec = rplan::vec_loads(d, es, ldc, (uint64_t)reinterpret_cast<uintptr_t>(c));
   const dim3 grid((unsigned)(ceil_div(bp, kQM) + std::min<int64_t>(leaves, bp)));
 #define KRS_IVF_SCAN(ES_, VEC_)                                                                                    \
   {                                                                                                                \
@@ -1119,7 +1099,7 @@ extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroi
   KRS_CHECK_LAUNCH("retr_ivf_scan_kernel");
 
   // d. merge: the probes lists of each query; a query whose leaves hold fewer than k candidates ends in padding pairs
-  const int64_t len = (int64_t)probes * k;
+  const rplan::Select sel = rplan::plan_select((int64_t)probes * k, k);
   const Out out{out_ids, out_scores, dtype, ids, k, 0, n};
-  return select_rows(PairSrc{pairs, len}, b, len, k, out, reinterpret_cast<uint64_t*>(ws + w.merge), st);
+  return select_rows(PairSrc{pairs, sel.len}, b, sel, k, out, reinterpret_cast<uint64_t*>(ws + w.merge), st);
 }

@@ -11,6 +11,8 @@ be captured into a HIP graph.
 
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -80,6 +82,43 @@ def retrieval_topk(query: torch.Tensor, candidates: torch.Tensor, k: int, *, ids
                                     L.stream_ptr())
     L.check(rc, "krs_retrieval_topk")
     return scores, out_ids
+
+
+RETR_KERNELS = {0: None, 1: "fused", 2: "slab", 3: "rows"}               # KRS_RETR_*
+RETR_VARIANTS = {0: None, 1: "topk", 2: "q8", 3: "mine", 4: "rows"}       # KRS_RETR_VARIANT_*
+RETR_SELECTS = {0: None, 1: "lds", 2: "radix", 3: "radix_merge"}          # KRS_SELECT_*
+_VARIANT_CODES = {name: code for code, name in RETR_VARIANTS.items() if name}
+
+
+def _route_dict(rt) -> dict:
+    d = {name: int(getattr(rt, name)) for name, _ in L.RetrievalRoute._fields_}
+    d["kernel"] = RETR_KERNELS[rt.kernel]
+    d["variant"] = RETR_VARIANTS[rt.variant]
+    d["select"] = RETR_SELECTS[rt.select]
+    return d
+
+
+def last_route() -> dict:
+    """Where the calling thread's last topk_rows / retrieval_topk / retrieval_topk_q8 / retrieval_mine ran
+    (krs_retrieval_last_route): the fields of krs_retrieval_route with kernel, variant and select as names (None when no
+    launch was made).  Reads a host-side record, no device sync."""
+    rt = L.RetrievalRoute()
+    L.lib().krs_retrieval_last_route(C.byref(rt))
+    return _route_dict(rt)
+
+
+def plan_route(variant: str, b: int, n: int, d: int, k: int, dtype: torch.dtype, *, ldq: int | None = None,
+               ldc: int | None = None, q: int | None = 0x7F0000100000, c: int | None = 0x7E0000100000):
+    """(status, route) the entry `variant` ("topk", "q8", "mine", "rows") would have with these arguments
+    (krs_retrieval_plan_route; needs no GPU).  q and c are addresses (ints: only nullness and alignment are read), ldq /
+    ldc the row strides (default: d, or n for "rows", where b is rows, n is cols and c stands for x); route is the dict
+    of last_route().  KRS_RETRIEVAL_SLAB_BYTES is honoured as the entry honours it."""
+    width = n if variant == "rows" else d
+    rt = L.RetrievalRoute()
+    rc = L.lib().krs_retrieval_plan_route(_VARIANT_CODES[variant], q, width if ldq is None else ldq, c,
+                                          width if ldc is None else ldc, L.BF16 if dtype == torch.bfloat16 else L.F32,
+                                          b, n, d, k, C.byref(rt))
+    return int(rc), _route_dict(rt)
 
 
 # ---- K17: the same over an int8 candidate index ------------------------------------------------------------------------

@@ -6,19 +6,10 @@ import torch
 
 from keras_rs_amd import retrieval_ops
 from keras_rs_amd.layers import HardNegativeMining
+from tests.retrieval_restatement import order_key as _order_key
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _order_key(x: np.ndarray) -> np.ndarray:
-    """The contract's total order as uint32 (-0.0 == +0.0, NaN above +inf)."""
-    u = x.astype(np.float32).view(np.uint32).copy()
-    nan = np.isnan(x)
-    u[u == 0x80000000] = 0
-    key = np.where(u & 0x80000000, ~u, u | 0x80000000).astype(np.uint32)
-    key[nan] = 0xFFFFFFFF
-    return key
 
 
 def _expected(keys: np.ndarray, k: int) -> np.ndarray:

@@ -316,6 +316,8 @@ def test_row_strides_larger_than_d(dtype):
     ops = retrieval_ops._xent_operands(wide_q, wide_c, _dev(pos), _dev(bias), _dev(ids))
     assert ops[0].stride(0) == d + 3 and ops[1].stride(0) == d + 12          # (no copy was made)
     idx, val, ps = retrieval_ops.retrieval_mine(ops[0], ops[1], k, ops[2], ops[3], ops[4], HIT)
+    # (40 bytes of bf16 per row: element loads; 80 bytes of fp32 on a stride of 128: 16-byte loads)
+    assert [retrieval_ops.last_route()[f] for f in ("kernel", "variant", "vec")] == ["fused", "mine", int(dtype == torch.float32)]
     assert torch.equal(idx.cpu().to(torch.int64), ref["idx"]) and torch.equal(val.cpu(), ref["scores"].float())
     assert torch.equal(ps.cpu(), ref["pos_score"].float())
     qd, cd = wide_q.detach().requires_grad_(True), wide_c.detach().requires_grad_(True)

@@ -155,6 +155,7 @@ def test_strided_operands_and_forced_byte_loads():
     _assert_equal(*_call(wide_q[:, :d], wide_c[:, :d], _dev(cstep), k), refs[False], "ldq > d, ldc % 16 != 0")
     # the wrapper passes the same strides on
     s, i = retrieval_ops.retrieval_topk_q8(wide_q[:, :d], wide_c[:, :d], _dev(cstep), k)
+    assert [retrieval_ops.last_route()[f] for f in ("kernel", "variant", "es", "vec", "row_bytes")] == ["fused", "q8", 1, 0, d]
     torch.cuda.synchronize()
     _assert_equal(s.cpu().numpy(), i.cpu().numpy(), refs[False], "wrapper")
 

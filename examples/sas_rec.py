@@ -1,8 +1,9 @@
 """SASRec (self-attentive sequential recommendation), the model of the reference's examples/sas_rec.py, on this
 project's kernels: the item table on K1 / K2 (layers.Embedding), a learned position embedding, dropout,
 N pre-norm TransformerDecoder blocks whose causal self-attention is K19 (the scores and the dropout mask are never
-stored) and whose projections and feed-forward are krs_gemm, a final layer norm with epsilon 1e-8, and
-BruteForceRetrieval (K8) over the item table for serving, on the last non-padding token.
+stored), whose projections and feed-forward are krs_gemm and whose layer norms, residual adds and residual dropout
+are K22 (one fused kernel each), a final layer norm with epsilon 1e-8 (K22 too), and BruteForceRetrieval (K8) over the
+item table for serving, on the last non-padding token.
 
 Training follows the reference's compute_loss: positive and negative logits are row dot products of the sequence
 embedding with the embedded positive / negative items, and the loss is the sample-weighted mean of the binary

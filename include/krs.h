@@ -1437,6 +1437,62 @@ int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroids, int64_t
                       int64_t n, int64_t d, int64_t leaves, int probes, int k, void* out_scores, int32_t* out_ids,
                       int32_t* out_leaves, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * K22  Fused residual add + dropout + layer norm over the rows of [n, d], forward and backward
+ *
+ * x, residual, y, sum (and s, dy, dsum, dx, dres of the backward) are [n, d] matrices of one dtype (KRS_F32 /
+ * KRS_BF16), each with a row stride of its own (>= d); gamma, beta, mean, rstd, dgamma, dbeta are fp32.  Per row i, in
+ * fp32, with round() the rounding to dtype (nearest even; nothing in fp32):
+ *     s_ij   = round( residual_ij + x_ij * keep_ij / (1 - p) )        residual NULL = 0; p = 0: keep = 1
+ *              (1 / (1 - p) is the fp32 quotient 1.0f / (1.0f - p); the sum is ONE fused multiply-add, so s is the
+ *               exactly rounded value of the line above however residual and x cancel)
+ *     mean_i = (1/d) sum_j s_ij        var_i = (1/d) sum_j (s_ij - mean_i)^2        rstd_i = 1 / sqrt(var_i + eps)
+ *     y_ij   = round( gamma_j * (s_ij - mean_i) * rstd_i + beta_j )   gamma NULL = 1, beta NULL = 0
+ * The statistics are taken from the ROUNDED s (what an unfused composition does, and what the backward reloads), in two
+ * passes over the row held in registers.  With residual NULL and p == 0, s is x itself.
+ * Forms of krs_ln_fwd, by its pointers: norm (y only), add-norm (y and sum: s is written to sum, the next residual and
+ * what the backward needs), add (sum only, y NULL: no statistics; gamma, beta, mean, rstd must be NULL).  mean and rstd
+ * [n] may be NULL when no backward follows.
+ * Dropout keeps element (i, j) by K19's hash (mix and base as written there, the row index in place of bi * h + hi):
+ *     keep_ij <=> mix(base(seed, *draw, (uint32) i) + j) >= floor(p * 2^32)
+ * The forward and the backward recompute it; no mask is stored.  draw is a device int64 the call only READS; NULL
+ * when dropout_p == 0.
+ *
+ * krs_ln_bwd, with xh = (s - mean) * rstd and g = dy * gamma, all fp32:
+ *     ds_ij    = rstd_i * ( g_ij - mean_j(g_i.) - xh_ij * mean_j(g_i. xh_i.) ) + dsum_ij     dy NULL: first term 0;
+ *     dres     = round(ds)      dx = round(ds * keep / (1 - p))                              dsum NULL: 0
+ *     dgamma_j = sum_i dy_ij xh_ij        dbeta_j = sum_i dy_ij
+ * s is the forward's sum (x in the norm form).  Every output may be NULL to skip it, not all; with p == 0, dx and dres
+ * are equal: ask for one.  dgamma / dbeta need dy and krs_ln_workspace_bytes(n, d) of workspace (it need not be
+ * initialised; too little is KRS_ERR_WORKSPACE): every workgroup adds the rows it owns, in a fixed order, into one fp32
+ * partial row per vector, and a second kernel adds the partial rows in workgroup order.  No atomics anywhere:
+ * bit-identical from call to call.  No host synchronisation.
+ *
+ * Routes (csrc/ln_plan.h decides, a pure host function).  lanes_per_row = 8 (d <= 64), 16 (<= 128), 32 (<= 256) or 64
+ * lanes of one wave own a row, 8 registers a lane up to d = 512, then 16, 32, 64; a workgroup of 4 waves has
+ * 256 / lanes_per_row rows in flight and owns a contiguous block of rows.
+ *   KRS_LN_VEC    every base on 16 bytes, every stride and d a whole number of 16-byte chunks (8 bf16, 4 fp32): a lane
+ *                 moves 16 bytes per access.
+ *   KRS_LN_ELEM   anything else (d = 50, odd strides): element accesses, consecutive lanes on consecutive columns.
+ * The two routes add a row's elements in different orders; each is bit-identical to itself.
+ * n == 0 is a successful no-op.  n < 0, d < 1, a bad dtype, dropout_p outside [0, 1), eps < 0, a stride below d, a
+ * null x, a call that wants no output, dropout without draw, dy without s / mean / rstd, dgamma or dbeta without dy, and
+ * a backward with neither dy nor dsum are KRS_ERR_INVALID.  d > 4096 (the row lives in a wave's registers) and
+ * n > 2^31 - 1 are KRS_ERR_UNSUPPORTED with a message naming the limit.
+ * krs_ln_last_route: the route of the process's last krs_ln_fwd / _bwd call, whichever thread made it: kernel,
+ * lanes_per_row and vec; all zero after a refused call or a no-op.  Returns kernel.
+ * ------------------------------------------------------------------------- */
+enum { KRS_LN_NONE = 0, KRS_LN_VEC = 1, KRS_LN_ELEM = 2 };
+size_t krs_ln_workspace_bytes(int64_t n, int64_t d);
+int krs_ln_fwd(const void* x, int64_t ldx, const void* residual, int64_t ldr, const float* gamma, const float* beta,
+               int dtype, int64_t n, int64_t d, float eps, float dropout_p, uint64_t seed, const int64_t* draw, void* y,
+               int64_t ldy, void* sum, int64_t lds, float* mean, float* rstd, void* stream);
+int krs_ln_bwd(const void* s, int64_t lds, const void* dy, int64_t lddy, const void* dsum, int64_t lddsum,
+               const float* gamma, const float* mean, const float* rstd, int dtype, int64_t n, int64_t d, float dropout_p,
+               uint64_t seed, const int64_t* draw, void* dx, int64_t lddx, void* dres, int64_t lddres, float* dgamma,
+               float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+int krs_ln_last_route(int* kernel, int* lanes_per_row, int* vec);
+
 #ifdef __cplusplus
 }
 #endif

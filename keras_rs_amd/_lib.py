@@ -199,6 +199,11 @@ PROTOTYPES = {
     "krs_retrieval_ivf_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I, _I, _I]),
     "krs_retrieval_ivf": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I, _I64, _I64, _I64, _I64, _I, _I, _P, _P, _P,
                                _P, _SZ, _P]),
+    "krs_ln_workspace_bytes": (_SZ, [_I64, _I64]),
+    "krs_ln_fwd": (_I, [_P, _I64, _P, _I64, _P, _P, _I, _I64, _I64, _F, _F, _U64, _P, _P, _I64, _P, _I64, _P, _P, _P]),
+    "krs_ln_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I, _I64, _I64, _F, _U64, _P, _P, _I64, _P, _I64, _P,
+                        _P, _P, _SZ, _P]),
+    "krs_ln_last_route": (_I, [_P, _P, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

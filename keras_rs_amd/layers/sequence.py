@@ -1,21 +1,28 @@
 """Sequence layers for the reference's sequential recommenders (examples/sas_rec.py): MultiHeadAttention and the
 decoder-only TransformerDecoder block, on K19 (sequence_ops.seq_attention: the scores, the probabilities and the
-dropout mask are never stored) and krs_gemm (the projections and the feed-forward).  Layer norm, the residual adds and
-the residual dropout are torch ops.
+dropout mask are never stored), krs_gemm (the projections and the feed-forward) and K22 (norm_ops.residual_layer_norm:
+each residual add, its dropout and the layer norm that follows in one kernel; no dropout mask is stored either).
+KRS_FUSE_NORM=0 (or FUSE_NORM = False here, read at every call) puts the torch composition back for A/B.
 """
 
 from __future__ import annotations
 
 import math
+import os
 from typing import Any
 
 import torch
 
 from keras_rs_amd import _lib as L
-from keras_rs_amd import sequence_ops
-from keras_rs_amd.autograd import DenseFn
+from keras_rs_amd import norm_ops, sequence_ops
+from keras_rs_amd.autograd import DenseFn, _switch
 from keras_rs_amd.layers import base
 from keras_rs_amd.layers.dense import Dense
+
+# 1: layer norm, the residual adds and the residual dropout run on K22; 0: the torch composition of before K22 (A/B)
+FUSE_NORM = _switch(os.environ.get("KRS_FUSE_NORM", "1"))
+# what the decoder adds to its seed for its two residual dropouts (the attention layer hashes the seed itself)
+_ATTN_RESIDUAL_SEED, _FF_RESIDUAL_SEED = 0x5851F42D4C957F2D, 0x14057B7EF767814F
 
 
 def _keras_fans_init(init: base.Initializer, shape) -> base.Initializer:
@@ -129,32 +136,47 @@ class MultiHeadAttention(base.Layer):
         return config
 
 
-class _LayerNorm(base.Layer):
-    """keras.layers.LayerNormalization(axis=-1): gamma, beta in fp32; the arithmetic is torch's, in fp32."""
+class LayerNormalization(base.Layer):
+    """keras.layers.LayerNormalization over the last axis: gamma (scale=True) and beta (center=True) in fp32, on K22.  An
+    input K22 does not take (more than 4096 columns, a tensor off the device) keeps torch's arithmetic, in fp32."""
 
-    def __init__(self, epsilon: float = 1e-3, **kwargs: Any):
+    def __init__(self, epsilon: float = 1e-3, *, axis=-1, center: bool = True, scale: bool = True,
+                 rms_scaling: bool = False, gamma_initializer="ones", beta_initializer="zeros", **kwargs: Any):
         super().__init__(**kwargs)
+        if isinstance(axis, (list, tuple)) and len(axis) == 1:
+            axis = axis[0]
+        if axis != -1:
+            raise NotImplementedError(f"axis={axis}: K22 normalises the last axis only (axis=-1)")
+        if rms_scaling:
+            raise NotImplementedError("rms_scaling=True: K22 has no RMS norm")
         self.epsilon = float(epsilon)
+        self.center, self.scale = bool(center), bool(scale)
+        self.gamma_initializer = base.get_initializer(gamma_initializer)
+        self.beta_initializer = base.get_initializer(beta_initializer)
         for w in ("gamma", "beta"):
             self.register_parameter(w, None)
 
     def build(self, input_shape, *_) -> None:
         d = int(input_shape[-1])
-        self.gamma = self.add_weight((d,), "ones", "gamma", dtype=torch.float32)
-        self.beta = self.add_weight((d,), "zeros", "beta", dtype=torch.float32)
+        if self.scale:
+            self.gamma = self.add_weight((d,), base.clone_initializer(self.gamma_initializer), "gamma", dtype=torch.float32)
+        if self.center:
+            self.beta = self.add_weight((d,), base.clone_initializer(self.beta_initializer), "beta", dtype=torch.float32)
         self.built = True
 
     def call(self, x):
+        xc = x.to(self.compute_dtype)
+        if FUSE_NORM and norm_ops.supported(xc):
+            return norm_ops.residual_layer_norm(xc, None, self.gamma, self.beta, epsilon=self.epsilon)
         y = torch.nn.functional.layer_norm(x.float(), (x.shape[-1],), self.gamma, self.beta, self.epsilon)
         return y.to(self.compute_dtype)
 
     def get_config(self) -> dict:
         config = super().get_config()
-        config["epsilon"] = self.epsilon
+        config.update({"epsilon": self.epsilon, "center": self.center, "scale": self.scale,
+                       "gamma_initializer": self.gamma_initializer.serialize(),
+                       "beta_initializer": self.beta_initializer.serialize()})
         return config
-
-
-LayerNormalization = _LayerNorm
 
 
 class TransformerDecoder(base.Layer):
@@ -162,7 +184,10 @@ class TransformerDecoder(base.Layer):
     self-attention with a padding mask, dropout, residual, layer norm; then Dense(intermediate_dim, activation),
     Dense(hidden), dropout, residual, layer norm.  normalize_first=True norms each sublayer's INPUT instead.
     key_dim = hidden // num_heads.  Weights: the attention's eight, its layer norm's gamma / beta, the two Dense
-    layers' kernel / bias, the feed-forward layer norm's gamma / beta."""
+    layers' kernel / bias, the feed-forward layer norm's gamma / beta.
+    Each `dropout, residual, layer norm` is one K22 call (post-norm: two launches for the block's glue; pre-norm: the
+    norm form, K19, add-norm, the feed-forward, the add form).  The two residual dropouts hash the attention layer's
+    `seed` plus two fixed offsets with one draw counter of the decoder's own; the attention keeps its counter."""
 
     def __init__(self, intermediate_dim: int, num_heads: int, dropout: float = 0.0, activation="relu",
                  layer_norm_epsilon: float = 1e-5, kernel_initializer="glorot_uniform", bias_initializer="zeros",
@@ -179,6 +204,13 @@ class TransformerDecoder(base.Layer):
         self.normalize_first = bool(normalize_first)
         self._seed_given = seed
         self.self_attention = None
+        self._draw = None
+
+    def draw_counter(self) -> torch.Tensor:
+        """The device int64 that numbers the residual dropout masks; each of the two advances it on the device."""
+        if self._draw is None:
+            self._draw = torch.zeros(1, dtype=torch.int64, device=self._device)
+        return self._draw
 
     def build(self, decoder_sequence_shape, *_) -> None:
         hidden = int(decoder_sequence_shape[-1])
@@ -189,7 +221,7 @@ class TransformerDecoder(base.Layer):
                                                  kernel_initializer=base.clone_initializer(self.kernel_initializer),
                                                  bias_initializer=base.clone_initializer(self.bias_initializer),
                                                  seed=self._seed_given, name=f"{self.name}_self_attention", **sub)
-        self.self_attention_layer_norm = _LayerNorm(self.layer_norm_epsilon, name=f"{self.name}_self_attention_norm", **sub)
+        self.self_attention_layer_norm = LayerNormalization(self.layer_norm_epsilon, name=f"{self.name}_self_attention_norm", **sub)
         self.feedforward_intermediate_dense = Dense(self.intermediate_dim, activation=self.activation,
                                                     kernel_initializer=base.clone_initializer(self.kernel_initializer),
                                                     bias_initializer=base.clone_initializer(self.bias_initializer),
@@ -197,7 +229,7 @@ class TransformerDecoder(base.Layer):
         self.feedforward_output_dense = Dense(hidden, kernel_initializer=base.clone_initializer(self.kernel_initializer),
                                               bias_initializer=base.clone_initializer(self.bias_initializer),
                                               name=f"{self.name}_ff_output", **sub)
-        self.feedforward_layer_norm = _LayerNorm(self.layer_norm_epsilon, name=f"{self.name}_ff_norm", **sub)
+        self.feedforward_layer_norm = LayerNormalization(self.layer_norm_epsilon, name=f"{self.name}_ff_norm", **sub)
         shape = tuple(decoder_sequence_shape)
         self.self_attention.build(shape)
         self.self_attention_layer_norm.build(shape)
@@ -213,6 +245,8 @@ class TransformerDecoder(base.Layer):
         if encoder_sequence is not None:
             raise NotImplementedError("an encoder_sequence (cross-attention) is not supported: decoder-only blocks")
         x = decoder_sequence.to(self.compute_dtype)
+        if FUSE_NORM and norm_ops.supported(x):
+            return self._call_fused(x, decoder_padding_mask, training)
         residual = x
         if self.normalize_first:
             x = self.self_attention_layer_norm(x)
@@ -228,6 +262,22 @@ class TransformerDecoder(base.Layer):
         if not self.normalize_first:
             x = self.feedforward_layer_norm(x)
         return x
+
+    def _call_fused(self, x, padding_mask, training):
+        p = self.dropout if training else 0.0
+        seed = self.self_attention.seed
+        drop = lambda offset: dict(dropout_p=p, seed=seed + offset, draw=self.draw_counter() if p > 0.0 else None)
+        attn_norm, ff_norm = self.self_attention_layer_norm, self.feedforward_layer_norm
+        attend = lambda t: self.self_attention(t, padding_mask=padding_mask, use_causal_mask=True, training=training)
+        feed = lambda t: self.feedforward_output_dense(self.feedforward_intermediate_dense(t))
+        fused = norm_ops.residual_layer_norm
+        if self.normalize_first:
+            h = fused(x, None, attn_norm.gamma, attn_norm.beta, epsilon=attn_norm.epsilon)
+            h, s = fused(attend(h), x, ff_norm.gamma, ff_norm.beta, epsilon=ff_norm.epsilon, return_sum=True,
+                         **drop(_ATTN_RESIDUAL_SEED))
+            return fused(feed(h), s, norm=False, epsilon=0.0, **drop(_FF_RESIDUAL_SEED))
+        x = fused(attend(x), x, attn_norm.gamma, attn_norm.beta, epsilon=attn_norm.epsilon, **drop(_ATTN_RESIDUAL_SEED))
+        return fused(feed(x), x, ff_norm.gamma, ff_norm.beta, epsilon=ff_norm.epsilon, **drop(_FF_RESIDUAL_SEED))
 
     def get_config(self) -> dict:
         config = super().get_config()

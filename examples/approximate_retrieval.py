@@ -4,9 +4,13 @@ embeddings plus copies of them scaled by uniform noise), then serve the same que
 from PartitionedRetrieval and print both times and the recall of the approximate top-k against the exact one.
 
     python examples/approximate_retrieval.py          # needs an MI355X; no dataset is downloaded
+    python examples/approximate_retrieval.py --ah [--reorder R]
 
 The reference serves from the ScaNN library; PartitionedRetrieval is its partitioning ("tree") stage on float rows, with
 the reference's settings: num_leaves=100, num_leaves_to_search=30, training_iterations=12 (include/krs.h, K21).
+`--ah` also serves the same candidates from AsymmetricHashingRetrieval, the reference's other two stages
+(score_ah(dimensions_per_block=2) and, with `--reorder R`, reorder(R); include/krs.h, K23), and prints the bytes of each
+index beside its time and recall.
 """
 
 from __future__ import annotations
@@ -62,7 +66,26 @@ def serve_both(query_emb: torch.Tensor, candidates: torch.Tensor, k: int = 10, n
             "ids": got}
 
 
-def main(steps: int = 20, batch: int = 256, users: int = 1000, items: int = 2000, dim: int = 32, copies: int = 100):
+def serve_ah(query_emb: torch.Tensor, candidates: torch.Tensor, reorder: int | None = None, k: int = 10,
+             num_leaves: int = 100, num_leaves_to_search: int = 30, training_iterations: int = 12) -> dict:
+    """The same queries from the asymmetric-hashing index: {"recall" against the exact top-k, "ah_s": seconds per call,
+    "build_s", "index_bytes", "float_bytes": what the partitioned index stores for the same candidates, "ids"}."""
+    want = kl.BruteForceRetrieval(candidates, k=k, return_scores=False, device=candidates.device)(query_emb)
+    t0 = time.perf_counter()
+    index = kl.AsymmetricHashingRetrieval(candidates, k=k, return_scores=False, num_leaves=num_leaves,
+                                          num_leaves_to_search=num_leaves_to_search,
+                                          training_iterations=training_iterations, dimensions_per_block=2,
+                                          num_reordering_candidates=reorder, device=candidates.device)
+    torch.cuda.synchronize()
+    build_s = time.perf_counter() - t0
+    got, ah_s = timed(index, query_emb)
+    hits = (want[:, :, None] == got[:, None, :]).any(dim=2).float().sum(dim=1)
+    return {"recall": float((hits / k).mean()), "ah_s": ah_s, "build_s": build_s, "index_bytes": index.index_bytes(),
+            "float_bytes": candidates.numel() * candidates.element_size(), "ids": got}
+
+
+def main(steps: int = 20, batch: int = 256, users: int = 1000, items: int = 2000, dim: int = 32, copies: int = 100,
+         ah: bool = False, reorder: int | None = None):
     dev = torch.device("cuda", torch.cuda.current_device())
     query_tower = kl.Embedding(users, dim, device=dev)
     cand_tower = kl.Embedding(items, dim, device=dev)
@@ -85,8 +108,23 @@ def main(steps: int = 20, batch: int = 256, users: int = 1000, items: int = 2000
     print(f"Time taken by partitioned layer (sec): {served['partitioned_s']:.6f}   (index build: "
           f"{served['build_s']:.3f} s)")
     print(f"recall of the partitioned top-10 against the exact one: {served['recall']:.4f}")
+    if ah:
+        hashed = serve_ah(query_tower(user_ids).detach(), candidates, reorder=reorder)
+        stage = "without reordering" if reorder is None else f"reordering {reorder} candidates"
+        print(f"Time taken by asymmetric hashing layer (sec), {stage}: {hashed['ah_s']:.6f}   (index build: "
+              f"{hashed['build_s']:.3f} s)")
+        print(f"index bytes: {hashed['index_bytes']} (asymmetric hashing) against {hashed['float_bytes']} of float rows")
+        print(f"recall of the asymmetric hashing top-10 against the exact one: {hashed['recall']:.4f}")
+        served["ah"] = hashed
     return served
 
 
 if __name__ == "__main__":
-    main()
+    import argparse
+
+    parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    parser.add_argument("--ah", action="store_true", help="also serve from AsymmetricHashingRetrieval")
+    parser.add_argument("--reorder", type=int, default=None, metavar="R",
+                        help="with --ah: rescore the best R candidates exactly (k <= R <= 128)")
+    args = parser.parse_args()
+    main(ah=args.ah, reorder=args.reorder)

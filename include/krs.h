@@ -1493,6 +1493,83 @@ int krs_ln_bwd(const void* s, int64_t lds, const void* dy, int64_t lddy, const v
                float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
 int krs_ln_last_route(int* kernel, int* lanes_per_row, int* vec);
 
+/* ------------------------------------------------------------------------- *
+ * K23  Asymmetric hashing over K21's partition, and the reorder stage (ScaNN's score_ah(...) and reorder(...); the
+ *      serving side of keras_rs_amd.layers.AsymmetricHashingRetrieval)
+ *
+ *   Index       K21's centroids [leaves, d], leaf_offsets [leaves + 1], row_index [n] and ids [n], unchanged, and in
+ *               place of K21's regrouped float rows:
+ *                 codebooks  bf16 [blocks][16][m], blocks = ceil(d / m), m = dimensions per block in {2, 4, 8}: 16 centres
+ *                            per block, contiguous.  Columns at or beyond d of the last block are zero (the kernels read
+ *                            them as zero whatever they hold).
+ *                 codes      uint8 [n, ldcode], STORED (leaf) order like K21's rows, on a 4-byte boundary.  A row holds one
+ *                            4-bit code per block: block j is nibble j, nibble j sits in byte j / 2, the even j in the low
+ *                            four bits.  A row is krs_ah_code_bytes(d, m) = 4 * ceil(blocks / 8) bytes, the nibbles from
+ *                            `blocks` on being zero; ldcode (bytes) is at least that and a multiple of 4.
+ *                 rows       the float rows [n, d] in ORIGINAL order with row stride ldr, only for reordering.
+ *   Residual    What a code quantizes is e = x - centroid[leaf(x)].  decode(code row) is the d-vector whose block j is
+ *               codebooks[j][nibble j].
+ *
+ * krs_ah_encode: codes of n stored rows.  Stored row s is x[row_index[s]] (x[s] when row_index is NULL; x is [n, d] with
+ * row stride ldx, KRS_F32 / KRS_BF16, centroids of the same dtype) and belongs to leaf row_leaf[s].  Per element
+ * e = fsub(float(x), float(centroid)); per block and centre dist = 0, then for t = 0 .. m-1 in order u = fsub(e_t,
+ * float(c_t)), dist = fadd(dist, fmul(u, u)), every operation rounded to fp32 on its own, nothing contracted; columns
+ * at or beyond d count as e = 0, c = 0.  The code is the centre with the least dist, the LOWEST code on a tie: numpy
+ * float32 reproduces the codes bit for bit.  A row_index outside [0, n) reads as a zero row and a row_leaf outside
+ * [0, leaves) as a zero centroid.  One pass: a thread owns 8 columns of a row (16-byte loads when x, centroids, their
+ * strides and d allow, element loads otherwise), the codebooks sit in LDS, m lanes OR their bits into one 4-byte store.
+ * n == 0 is a successful no-op; d > 512 is KRS_ERR_UNSUPPORTED; a bad shape, dtype, m, stride, alignment or a null
+ * operand is KRS_ERR_INVALID.
+ *
+ * krs_retrieval_rescore: the k best of each query's r listed candidates by their EXACT scores.  idx int32 [b, r] (row
+ * stride ldi) holds original candidate indices; an entry outside [0, n), -1 by convention, is padding.  The result is
+ * BruteForceRetrieval's order over the listed candidates: the fp32 score descending, then the index ascending, out_ids
+ * = ids[index] (the index when ids is NULL), out_scores (or NULL) rounded once to dtype; id -1 and score -inf where
+ * fewer than k entries are real.  Indices listed twice come back twice.
+ *   Bits        A rescored score leaves K8's MFMA chain: one wave takes (query, 32 candidates), the query row is the A
+ *               fragment of all 32 tile rows, the gathered rows are the B fragment, the instruction, the K-step order and
+ *               the zeroed K tail are krs_retrieval_topk's for both dtypes.  So the score of (query, candidate) has the
+ *               bits krs_retrieval_topk gives it.
+ *   Shapes      q [b, d] and rows [n, d] share dtype; 1 <= k <= r <= 128, d <= 512 (beyond: KRS_ERR_UNSUPPORTED).
+ *               Workspace: b * r pairs of 8 bytes, rounded up to 256 (0 for an unsupported shape).  The selection is
+ *               K8's LDS route.  No host wait, no allocation: graph-capturable.  b == 0 is a successful no-op.
+ *
+ * krs_retrieval_ivf_ah: krs_retrieval_ivf with the scan over the codes.  On `stream`: (a) K21's probe, keeping its fp32
+ * scores; (b) K21's inversion; (c) the scan, K21's work item (leaf, tile of <= 32 pairs) on K8's stage 1 with the B
+ * fragment decoded from the codebooks in LDS, r pairs written per (query, slot); (d) K8's merge to r pairs per query;
+ * (e) rows == NULL: r must equal k and the merged pairs are the result; rows != NULL: k <= r <= 128 and the merged
+ * indices go through krs_retrieval_rescore's launches.
+ *   AH score    of query i and a candidate of probed leaf l:
+ *                   fadd( chain(bf16(q_i), decode(code)), probe_score(i, l) )
+ *               chain is K8's bf16 MFMA chain (v_mfma_f32_32x32x16_bf16, K8's K steps, zeroed K tail); probe_score is
+ *               the fp32 score step (a) has for (q_i, centroid_l), not rounded to dtype; fp32 queries are rounded to
+ *               bf16 (nearest even) for the scan only -- probe and reorder run in `dtype`, as K21 does.
+ *   Result      Without rows: K21's outputs with AH scores (order: AH score descending, original index ascending).  With
+ *               rows: exact scores in krs_retrieval_rescore's order.  Short results end in id -1, score -inf.
+ *   Shapes      K21's limits and refusals under this entry's name, and: m not in {2, 4, 8}, r < k, r != k without rows,
+ *               a code stride below krs_ah_code_bytes or not a multiple of 4, codes off a 4-byte boundary are
+ *               KRS_ERR_INVALID; r > 128 is KRS_ERR_UNSUPPORTED.  Required pointers (b > 0): q, centroids, codebooks,
+ *               codes, leaf_offsets, row_index, out_ids.  b == 0 is a successful no-op.  Bit-identical from call to
+ *               call, graph-capturable.
+ * krs_retrieval_ivf_ah_workspace_bytes: krs_retrieval_ivf_workspace_bytes with k = r, plus b * probes fp32 probe scores,
+ * plus, with reorder != 0, b * r int32 indices and b * r pairs; each rounded up to 256.  0 for b <= 0 or a refused shape.
+ * ------------------------------------------------------------------------- */
+int64_t krs_ah_code_bytes(int64_t d, int m);
+int krs_ah_encode(const void* x, int64_t ldx, const int32_t* row_index, const int32_t* row_leaf, const void* centroids,
+                  int64_t ldm, int dtype, const void* codebooks, int64_t n, int64_t d, int64_t leaves, int m,
+                  uint8_t* codes, int64_t ldcode, void* stream);
+size_t krs_retrieval_rescore_workspace_bytes(int64_t b, int r, int k);
+int krs_retrieval_rescore(const void* q, int64_t ldq, const void* rows, int64_t ldr, const int32_t* idx, int64_t ldi,
+                          const int32_t* ids, int dtype, int64_t b, int64_t n, int64_t d, int r, int k, void* out_scores,
+                          int32_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
+size_t krs_retrieval_ivf_ah_workspace_bytes(int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k, int r,
+                                            int m, int reorder, int dtype);
+int krs_retrieval_ivf_ah(const void* q, int64_t ldq, const void* centroids, int64_t ldm, const void* codebooks, int m,
+                         const uint8_t* codes, int64_t ldcode, const int32_t* leaf_offsets, const int32_t* row_index,
+                         const void* rows, int64_t ldr, const int32_t* ids, int dtype, int64_t b, int64_t n, int64_t d,
+                         int64_t leaves, int probes, int k, int r, void* out_scores, int32_t* out_ids, int32_t* out_leaves,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

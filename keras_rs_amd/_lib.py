@@ -204,6 +204,13 @@ PROTOTYPES = {
     "krs_ln_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I, _I64, _I64, _F, _U64, _P, _P, _I64, _P, _I64, _P,
                         _P, _P, _SZ, _P]),
     "krs_ln_last_route": (_I, [_P, _P, _P]),
+    "krs_ah_code_bytes": (_I64, [_I64, _I]),
+    "krs_ah_encode": (_I, [_P, _I64, _P, _P, _P, _I64, _I, _P, _I64, _I64, _I64, _I, _P, _I64, _P]),
+    "krs_retrieval_rescore_workspace_bytes": (_SZ, [_I64, _I, _I]),
+    "krs_retrieval_rescore": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I, _I64, _I64, _I64, _I, _I, _P, _P, _P, _SZ, _P]),
+    "krs_retrieval_ivf_ah_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I, _I, _I, _I, _I, _I]),
+    "krs_retrieval_ivf_ah": (_I, [_P, _I64, _P, _I64, _P, _I, _P, _I64, _P, _P, _P, _I64, _P, _I, _I64, _I64, _I64, _I64,
+                                  _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -32,6 +32,11 @@
 //                             the centroids picks each query's leaves, the (query, leaf) pairs are inverted into per-leaf
 //                             lists (histogram, two scans, fill), stage 1 runs per (leaf, tile of 32 pairs) and writes k
 //                             pairs per (query, leaf), stage 2 merges them per query.
+//   * krs_retrieval_ivf_ah    krs_retrieval_ivf over 4-bit codes: stage 1's B fragment is decoded from codebooks in LDS and
+//                             the probe's fp32 score is added to the chain's result; optionally the merged candidates go
+//                             through krs_retrieval_rescore.  krs_ah_encode writes the codes.
+//   * krs_retrieval_rescore   the exact scores of each query's listed candidates on stage 1's MFMA chain (the query row as
+//                             the A fragment of every tile row), then the LDS selection.
 //
 // Every shape decision of the four planned entries (krs_topk_rows, krs_retrieval_topk, _q8, _mine) -- the path, stage 1's
 // geometry, build, LDS and grid, the chunks, the workspace sections, the selection route -- is made by retrieval_plan.h, a
@@ -285,6 +290,17 @@ struct Ivf {
   const int32_t* row_index;      // [n] original index of a stored row, ascending inside a leaf
   int leaves, probes;
 };
+// what the asymmetric-hashing variant of the partitioned scan adds (krs_retrieval_ivf_ah): the B operand is decoded from
+// 4-bit codes through the codebooks in LDS, and the (query, leaf) probe score is added to the chain's result
+struct Ah {
+  const uint8_t* codes;          // [n, ldcode] bytes, stored order; nibble j of a row (low nibble of byte j / 2 first) = block j
+  int64_t ldcode;                // bytes, a multiple of 4
+  int cwords;                    // 4-byte words of a code row that hold nibbles
+  const uint16_t* codebooks;     // [blocks][16][M] bf16
+  int blocks;
+  const float* probe_score;      // [b * probes] fp32, by pair
+  int q_f32;                     // the queries are fp32: rounded to bf16 (nearest even) as the tile is filled
+};
 
 // one wave sorts a row queue of m <= 256 pairs (4 per lane, descending), keeps the first k and returns the new
 // threshold key (0 while fewer than k pairs were seen); `q` is rewritten with the kept pairs
@@ -341,6 +357,32 @@ __device__ uint32_t wave_compact(uint64_t* q, int m, int k, int lane) {
   return thr;
 }
 
+// the 16-byte chunk `ch` of K of a row of ES-byte elements that is d long: what a lane hands the matrix cores for one K
+// step.  VEC: the row is whole 16-byte chunks on a 16-byte boundary; else element loads, the K tail zeroed.
+template <int ES, bool VEC>
+__device__ __forceinline__ u32x4 load_k_chunk(const char* crow, int ch, int d) {
+  const int e0 = ch * (16 / ES);
+  u32x4 v = {0, 0, 0, 0};
+  if constexpr (VEC) {
+    if (e0 < d) v = *reinterpret_cast<const u32x4*>(crow + ch * 16);
+  } else if constexpr (ES == 1) {
+    const uint8_t* cr = reinterpret_cast<const uint8_t*>(crow);
+#pragma unroll
+    for (int x = 0; x < 16; ++x) v[x >> 2] |= (e0 + x < d ? (uint32_t)cr[e0 + x] : 0u) << (8 * (x & 3));
+  } else if constexpr (ES == 2) {
+    const uint16_t* cr = reinterpret_cast<const uint16_t*>(crow);
+    uint32_t h[8];
+#pragma unroll
+    for (int x = 0; x < 8; ++x) h[x] = e0 + x < d ? cr[e0 + x] : 0;
+    v = (u32x4){h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+  } else {
+    const uint32_t* cr = reinterpret_cast<const uint32_t*>(crow);
+#pragma unroll
+    for (int x = 0; x < 4; ++x) v[x] = e0 + x < d ? cr[e0 + x] : 0;
+  }
+  return v;
+}
+
 // grid: S * qtiles workgroups of 256 threads.  The query tiles of one slice run back to back on one XCD (workgroup
 // ids are dealt round-robin to the 8 XCDs), so a slice is read from HBM about once and from that XCD's L2 after.
 // VEC: every candidate row is whole 16-byte chunks on a 16-byte boundary (else element loads, K tail zeroed).
@@ -357,9 +399,15 @@ __device__ uint32_t wave_compact(uint64_t* q, int m, int k, int lane) {
 // over the leaf's stored rows, a queued pair carries row_index[stored row] (ascending inside a leaf, so the queue cut's
 // tie argument holds), and the k pairs of tile row r go to out[pair_r].  The K loop is untouched: a (query, candidate)
 // score leaves the MFMA chain of K8 whatever tile row the query sits in.
-template <int ES, bool VEC, bool MINE, bool IVF = false>
+// AH = M in {2, 4, 8} (krs_retrieval_ivf_ah; IVF, ES == 2): the lane's 16-byte B chunk is not loaded but decoded: the
+// chunk's 8 / M nibbles come from the candidate's code row (the words of 8 K steps are loaded at once) and each selects
+// one centre of M bf16 from the codebooks, staged into LDS once per workgroup as [block][code][M] and zeroed beyond d.
+// Lanes 0-31 and 32-63 each read one block, so at most 16 distinct, consecutive centres.  The probe score of the tile
+// row's (query, leaf) pair is added to the chain's result, one rounded fp32 addition, before the score is ranked.
+template <int ES, bool VEC, bool MINE, bool IVF = false, int AH = 0>
 __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, const Q8Scale& q8 = Q8Scale{},
-                                            const Ivf& iv = Ivf{}) {
+                                            const Ivf& iv = Ivf{}, const Ah& ah = Ah{}) {
+  static_assert(AH == 0 || (IVF && ES == 2 && !MINE), "the AH operand belongs to the partitioned bf16 scan");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lstride = p.row_bytes + 16;
   char* qt = smem;                                                           // [kQM][lstride]
@@ -371,6 +419,7 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
   float* qstep = reinterpret_cast<float*>(thr + kQM);                        // [kQM]  ES == 1 (never with MINE)
   int* qpair = reinterpret_cast<int*>(thr + kQM);                            // [kQM]  IVF: the row's pair, or -1
   int* qrow = qpair + kQM;                                                   // [kQM]  IVF: the row's query
+  char* cb = reinterpret_cast<char*>(qrow + kQM);                            // [row_bytes * 16]  AH: the codebooks
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int frow = lane & 31, fhalf = lane >> 5;
@@ -421,7 +470,13 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
       const uint32_t v = q0 + r < p.b ? *reinterpret_cast<const uint32_t*>(p.q + (q0 + r) * p.ldq + e * 4) : 0u;
       *reinterpret_cast<uint32_t*>(qt + r * lstride + e * 4) = v;
     } else if constexpr (ES == 2) {
-      const uint16_t v = ok ? reinterpret_cast<const uint16_t*>(p.q)[qr * p.ldq + e] : 0;
+      uint16_t v = 0;
+      if constexpr (AH != 0) {
+        if (ok) v = ah.q_f32 ? f32_to_bf16(reinterpret_cast<const float*>(p.q)[qr * p.ldq + e])
+                             : reinterpret_cast<const uint16_t*>(p.q)[qr * p.ldq + e];
+      } else {
+        v = ok ? reinterpret_cast<const uint16_t*>(p.q)[qr * p.ldq + e] : 0;
+      }
       *reinterpret_cast<uint16_t*>(qt + r * lstride + e * 2) = v;
     } else {
       const float v = ok ? reinterpret_cast<const float*>(p.q)[qr * p.ldq + e] : 0.0f;
@@ -450,6 +505,14 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
       pid[threadIdx.x] = id;
     }
   }
+  if constexpr (AH != 0) {
+    // the codebooks over the tile's whole K extent: zero from block `blocks` on and in the columns from d on
+    uint16_t* cbw = reinterpret_cast<uint16_t*>(cb);
+    for (int i = threadIdx.x; i < p.row_bytes * 8; i += blockDim.x) {
+      const int blk = i / (16 * AH), col = blk * AH + i % AH;
+      cbw[i] = blk < ah.blocks && col < p.d ? ah.codebooks[i] : (uint16_t)0;
+    }
+  }
   __syncthreads();
 
   const int nks = p.row_bytes / 32;  // 32-byte K steps (one bf16 MFMA / four fp32 MFMAs each)
@@ -465,6 +528,14 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
   if constexpr (ES == 1) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) qs_reg[r] = qstep[acc_row(r, fhalf)];
+  }
+  float ps_reg[16];                    // AH: the probe score of the tile row's pair
+  if constexpr (AH != 0) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int pr = qpair[acc_row(r, fhalf)];
+      ps_reg[r] = pr < 0 ? 0.0f : ah.probe_score[pr];
+    }
   }
 
   for (int64_t blk = s0; blk < s1; blk += kCB) {
@@ -485,12 +556,41 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
     if constexpr (IVF) cidx = cvalid ? (uint32_t)iv.row_index[cand] : 0u;
     for (int ks0 = 0; ks0 < nks; ks0 += 8) {
       u32x4 fb[8];
+      // AH: a chunk is 32 / AH code bits, so the 8 K steps of this round (both halves) are 16 / AH words of the code row
+      uint32_t cw[AH != 0 ? 16 / AH : 1];
+      if constexpr (AH != 0) {
+        const uint32_t* cr = reinterpret_cast<const uint32_t*>(ah.codes + (cvalid ? cand : 0) * ah.ldcode);
+#pragma unroll
+        for (int w = 0; w < 16 / AH; ++w) {
+          const int wi = ks0 * 2 / AH + w;
+          cw[w] = cvalid && wi < ah.cwords ? cr[wi] : 0u;
+        }
+      }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int ch = (ks0 + u) * 2 + fhalf;      // 16-byte chunk of K
-        const int e0 = ch * (16 / ES);
+        [[maybe_unused]] const int e0 = ch * (16 / ES);
         u32x4 v = {0, 0, 0, 0};
-        if (ks0 + u < nks && cvalid) {
+        if constexpr (AH != 0) {
+          if (ks0 + u < nks) {
+            const uint32_t field = cw[u * 2 / AH] >> (((u * 2 + fhalf) * (32 / AH)) & 31);
+            const char* blk = cb + (size_t)ch * (8 / AH) * 16 * AH * 2;      // the chunk's first block
+            if constexpr (AH == 2) {
+#pragma unroll
+              for (int x = 0; x < 4; ++x)
+                v[x] = *reinterpret_cast<const uint32_t*>(blk + (x * 16 + ((field >> (4 * x)) & 15u)) * 4);
+            } else if constexpr (AH == 4) {
+#pragma unroll
+              for (int x = 0; x < 2; ++x) {
+                const u32x2 c2 = *reinterpret_cast<const u32x2*>(blk + (x * 16 + ((field >> (4 * x)) & 15u)) * 8);
+                v[2 * x] = c2[0];
+                v[2 * x + 1] = c2[1];
+              }
+            } else {
+              v = *reinterpret_cast<const u32x4*>(blk + (field & 15u) * 16);
+            }
+          }
+        } else if (ks0 + u < nks && cvalid) {
           if constexpr (VEC) {
             if (e0 < p.d) v = *reinterpret_cast<const u32x4*>(crow + ch * 16);
           } else {
@@ -535,6 +635,10 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
       // |idot| <= 512 * 128 * 128 = 2^23: the conversion is exact; two separately rounded multiplies, nothing contracted
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = __fmul_rn(__fmul_rn((float)iacc[r], cstep), qs_reg[r]);
+    }
+    if constexpr (AH != 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = __fadd_rn(acc[r], ps_reg[r]);
     }
     // acc[r] = score of query row acc_row(r, fhalf) against candidate `cand`
     if constexpr (MINE) {
@@ -656,6 +760,11 @@ __global__ __launch_bounds__(256) void retr_mine_stage1_kernel(const Stage1 p, c
 template <int ES, bool VEC>
 __global__ __launch_bounds__(256) void retr_ivf_scan_kernel(const Stage1 p, const Ivf iv) {
   stage1_body<ES, VEC, false, true>(p, Mine{}, Q8Scale{}, iv);
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void retr_ivf_ah_scan_kernel(const Stage1 p, const Ivf iv, const Ah ah) {
+  stage1_body<2, false, false, true, M>(p, Mine{}, Q8Scale{}, iv, ah);
 }
 
 // ---- the inversion of krs_retrieval_ivf: (query, slot) pairs -> per-leaf pair lists ------------------------------------
@@ -841,9 +950,11 @@ extern "C" size_t krs_retrieval_topk_workspace_bytes(int64_t b, int64_t n, int64
       .total;
 }
 
-extern "C" int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int64_t ldc, const int32_t* ids, int dtype,
-                                  int64_t b, int64_t n, int64_t d, int k, void* out_scores, int32_t* out_ids,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
+// krs_retrieval_topk with the dtype of out_scores as an argument: the entry passes `dtype`, the probe of
+// krs_retrieval_ivf_ah KRS_F32 (it adds the unrounded fp32 probe score to every candidate score of the leaf)
+static int retrieval_topk_impl(const void* q, int64_t ldq, const void* c, int64_t ldc, const int32_t* ids, int dtype,
+                               int64_t b, int64_t n, int64_t d, int k, void* out_scores, int val_dtype, int32_t* out_ids,
+                               void* workspace, size_t workspace_bytes, void* stream) {
   using namespace krs;
   g_route = krs_retrieval_route{};
   rplan::Plan pl;
@@ -861,7 +972,7 @@ extern "C" int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int
     const Stage1 p = stage1_args(pl, q, ldq, c, ldc, b, n, d, k, ws);
     KRS_STAGE1_BUILD(retr_stage1_kernel, p)
     KRS_CHECK_LAUNCH("retr_stage1_kernel");
-    const Out out{out_ids, out_scores, dtype, ids, k, 0, n};
+    const Out out{out_ids, out_scores, val_dtype, ids, k, 0, n};
     const int rs = select_rows(PairSrc{p.out, pl.sel.len}, b, pl.sel, k, out, list, st);
     if (rs == KRS_OK) g_route = pl.route;
     return rs;
@@ -875,12 +986,19 @@ extern "C" int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int
                             d, dtype, KRS_F32, nullptr, ws + pl.off_gemm, (size_t)pl.gemm_bytes, stream);
     if (rg != KRS_OK) return rg;
     const MatSrc src{slab, nullptr, n, KRS_F32, 0.0f, 0};
-    const Out out{out_ids, out_scores, dtype, ids, k, r0, n};
+    const Out out{out_ids, out_scores, val_dtype, ids, k, r0, n};
     const int rs = select_rows(src, rows, pl.sel, k, out, list, st);
     if (rs != KRS_OK) return rs;
   }
   g_route = pl.route;
   return KRS_OK;
+}
+
+extern "C" int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int64_t ldc, const int32_t* ids, int dtype,
+                                  int64_t b, int64_t n, int64_t d, int k, void* out_scores, int32_t* out_ids,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  return retrieval_topk_impl(q, ldq, c, ldc, ids, dtype, b, n, d, k, out_scores, dtype, out_ids, workspace,
+                             workspace_bytes, stream);
 }
 
 // ---- the int8 candidate index (K17) ------------------------------------------------------------------------------------
@@ -993,54 +1111,29 @@ inline IvfWorkspace ivf_workspace(int64_t b, int64_t d, int64_t leaves, int prob
   return w;
 }
 // the argument checks of both entry points; 0 when the shape is served
-inline int ivf_check(int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k, int dtype) {
-  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1 && leaves >= 1, "krs_retrieval_ivf: bad shape b=%lld n=%lld d=%lld leaves=%lld",
+inline int ivf_check(const char* who, int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k, int dtype) {
+  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1 && leaves >= 1, "%s: bad shape b=%lld n=%lld d=%lld leaves=%lld", who,
               (long long)b, (long long)n, (long long)d, (long long)leaves);
-  KRS_REQUIRE(n <= INT32_MAX && leaves < INT32_MAX, "krs_retrieval_ivf: more than 2^31 - 1 candidates or leaves");
-  KRS_REQUIRE(probes >= 1 && probes <= leaves, "krs_retrieval_ivf: probes = %d outside [1, leaves = %lld]", probes,
+  KRS_REQUIRE(n <= INT32_MAX && leaves < INT32_MAX, "%s: more than 2^31 - 1 candidates or leaves", who);
+  KRS_REQUIRE(probes >= 1 && probes <= leaves, "%s: probes = %d outside [1, leaves = %lld]", who, probes,
               (long long)leaves);
-  KRS_REQUIRE(k >= 1 && k <= n, "krs_retrieval_ivf: k = %d outside [1, %lld]", k, (long long)n);
-  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "krs_retrieval_ivf: bad dtype");
+  KRS_REQUIRE(k >= 1 && k <= n, "%s: k = %d outside [1, %lld]", who, k, (long long)n);
+  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "%s: bad dtype", who);
   if (probes > kIvfMaxProbes)
-    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_ivf: probes = %d above the limit of %d", probes, kIvfMaxProbes);
+    return fail(KRS_ERR_UNSUPPORTED, "%s: probes = %d above the limit of %d", who, probes, kIvfMaxProbes);
   if (k > kFusedMaxK)
-    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_ivf: k = %d above the limit of %d (there is no slab path)", k,
+    return fail(KRS_ERR_UNSUPPORTED, "%s: k = %d above the limit of %d (there is no slab path)", who, k,
                 kFusedMaxK);
   if (d > kFusedMaxD)
-    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_ivf: d = %lld above the limit of %d (there is no slab path)",
+    return fail(KRS_ERR_UNSUPPORTED, "%s: d = %lld above the limit of %d (there is no slab path)", who,
                 (long long)d, kFusedMaxD);
   if (b * probes > INT32_MAX)
-    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_ivf: b * probes = %lld above 2^31 - 1", (long long)(b * probes));
+    return fail(KRS_ERR_UNSUPPORTED, "%s: b * probes = %lld above 2^31 - 1", who, (long long)(b * probes));
   return KRS_OK;
 }
-}  // namespace
-}  // namespace krs
-
-extern "C" size_t krs_retrieval_ivf_workspace_bytes(int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k,
-                                                    int dtype) {
-  using namespace krs;
-  if (b <= 0 || ivf_check(b, n, d, leaves, probes, k, dtype) != KRS_OK) return 0;
-  return ivf_workspace(b, d, leaves, probes, k, dtype).total;
-}
-
-extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroids, int64_t ldm, const void* c,
-                                 int64_t ldc, const int32_t* leaf_offsets, const int32_t* row_index, const int32_t* ids,
-                                 int dtype, int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k,
-                                 void* out_scores, int32_t* out_ids, int32_t* out_leaves, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-  using namespace krs;
-  const int rc = ivf_check(b, n, d, leaves, probes, k, dtype);
-  if (rc != KRS_OK) return rc;
-  KRS_REQUIRE(ldq >= d && ldm >= d && ldc >= d, "krs_retrieval_ivf: row stride below d");
-  if (b == 0) return KRS_OK;
-  KRS_REQUIRE(q && centroids && c && leaf_offsets && row_index && out_ids, "krs_retrieval_ivf: null operand");
-  const IvfWorkspace w = ivf_workspace(b, d, leaves, probes, k, dtype);
-  if (!workspace || workspace_bytes < w.total)
-    return fail(KRS_ERR_WORKSPACE, "krs_retrieval_ivf: needs %zu workspace bytes, got %zu", w.total, workspace_bytes);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int es = dtype == KRS_BF16 ? 2 : 4;
-  char* ws = reinterpret_cast<char*>(workspace);
-  int32_t* probe = out_leaves ? out_leaves : reinterpret_cast<int32_t*>(ws + w.probe);
+// step (b) of krs_retrieval_ivf: the bp (query, slot) pairs of `probe` into per-leaf pair lists -- a histogram over the
+// leaves, the two exclusive scans, every pair into its leaf's segment
+inline int ivf_invert(const int32_t* probe, int64_t bp, int64_t leaves, char* ws, const IvfWorkspace& w, hipStream_t st) {
   int32_t* count = reinterpret_cast<int32_t*>(ws + w.count);
   int32_t* cursor = reinterpret_cast<int32_t*>(ws + w.cursor);
   int32_t* tiles = reinterpret_cast<int32_t*>(ws + w.tiles);
@@ -1048,15 +1141,6 @@ extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroi
   int32_t* tile_start = reinterpret_cast<int32_t*>(ws + w.tile_start);
   int32_t* sums = reinterpret_cast<int32_t*>(ws + w.sums);
   int32_t* list = reinterpret_cast<int32_t*>(ws + w.list);
-  uint64_t* pairs = reinterpret_cast<uint64_t*>(ws + w.pairs);
-  const int64_t bp = b * probes;
-
-  // a. probe: K8 on the centroids, k = probes (probes <= leaves: no padding, every id a leaf)
-  const int rp = krs_retrieval_topk(q, ldq, centroids, ldm, nullptr, dtype, b, leaves, d, probes, nullptr, probe,
-                                    ws + w.probe_ws, w.probe_ws_bytes, stream);
-  if (rp != KRS_OK) return rp;
-
-  // b. invert: histogram over leaves, the two exclusive scans, every pair into its leaf's segment
   KRS_HIP(hipMemsetAsync(count, 0, w.tiles - w.count, st));   // count and cursor
   const dim3 pgrid((unsigned)ceil_div(bp, 256));
   hipLaunchKernelGGL(ivf_count_kernel, pgrid, dim3(256), 0, st, probe, bp, (int)leaves, count);
@@ -1069,6 +1153,50 @@ extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroi
   KRS_CHECK_LAUNCH("scan::exclusive");
   hipLaunchKernelGGL(ivf_fill_kernel, pgrid, dim3(256), 0, st, probe, bp, (int)leaves, list_start, cursor, list);
   KRS_CHECK_LAUNCH("ivf_fill_kernel");
+  return KRS_OK;
+}
+}  // namespace
+}  // namespace krs
+
+extern "C" size_t krs_retrieval_ivf_workspace_bytes(int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k,
+                                                    int dtype) {
+  using namespace krs;
+  if (b <= 0 || ivf_check("krs_retrieval_ivf", b, n, d, leaves, probes, k, dtype) != KRS_OK) return 0;
+  return ivf_workspace(b, d, leaves, probes, k, dtype).total;
+}
+
+extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroids, int64_t ldm, const void* c,
+                                 int64_t ldc, const int32_t* leaf_offsets, const int32_t* row_index, const int32_t* ids,
+                                 int dtype, int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k,
+                                 void* out_scores, int32_t* out_ids, int32_t* out_leaves, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  using namespace krs;
+  const int rc = ivf_check("krs_retrieval_ivf", b, n, d, leaves, probes, k, dtype);
+  if (rc != KRS_OK) return rc;
+  KRS_REQUIRE(ldq >= d && ldm >= d && ldc >= d, "krs_retrieval_ivf: row stride below d");
+  if (b == 0) return KRS_OK;
+  KRS_REQUIRE(q && centroids && c && leaf_offsets && row_index && out_ids, "krs_retrieval_ivf: null operand");
+  const IvfWorkspace w = ivf_workspace(b, d, leaves, probes, k, dtype);
+  if (!workspace || workspace_bytes < w.total)
+    return fail(KRS_ERR_WORKSPACE, "krs_retrieval_ivf: needs %zu workspace bytes, got %zu", w.total, workspace_bytes);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int es = dtype == KRS_BF16 ? 2 : 4;
+  char* ws = reinterpret_cast<char*>(workspace);
+  int32_t* probe = out_leaves ? out_leaves : reinterpret_cast<int32_t*>(ws + w.probe);
+  int32_t* list_start = reinterpret_cast<int32_t*>(ws + w.list_start);
+  int32_t* tile_start = reinterpret_cast<int32_t*>(ws + w.tile_start);
+  int32_t* list = reinterpret_cast<int32_t*>(ws + w.list);
+  uint64_t* pairs = reinterpret_cast<uint64_t*>(ws + w.pairs);
+  const int64_t bp = b * probes;
+
+  // a. probe: K8 on the centroids, k = probes (probes <= leaves: no padding, every id a leaf)
+  const int rp = krs_retrieval_topk(q, ldq, centroids, ldm, nullptr, dtype, b, leaves, d, probes, nullptr, probe,
+                                    ws + w.probe_ws, w.probe_ws_bytes, stream);
+  if (rp != KRS_OK) return rp;
+
+  // b. invert
+  const int ri = ivf_invert(probe, bp, leaves, ws, w, st);
+  if (ri != KRS_OK) return ri;
 
   // c. scan: sum_l ceil(count_l / 32) <= floor(bp / 32) + (leaves with a pair) <= the grid launched
   Stage1 p;
@@ -1102,4 +1230,364 @@ extern "C" int krs_retrieval_ivf(const void* q, int64_t ldq, const void* centroi
   const rplan::Select sel = rplan::plan_select((int64_t)probes * k, k);
   const Out out{out_ids, out_scores, dtype, ids, k, 0, n};
   return select_rows(PairSrc{pairs, sel.len}, b, sel, k, out, reinterpret_cast<uint64_t*>(ws + w.merge), st);
+}
+
+// ---- asymmetric hashing and the reorder stage (K23) ---------------------------------------------------------------------
+namespace krs {
+namespace {
+constexpr int kAhMaxR = 128;          // most candidates handed to the reorder stage (the LDS route of the selection)
+constexpr int kAhEncodeGroups = 2048; // workgroups of the encoder: each stages the codebooks once and strides over the rows
+
+inline bool ah_m_ok(int m) { return m == 2 || m == 4 || m == 8; }
+inline int64_t ah_blocks(int64_t d, int m) { return ceil_div(d, m); }
+// bytes of a code row that hold nibbles: one nibble per block, rounded up to whole 4-byte words
+inline int64_t ah_code_bytes(int64_t d, int m) { return ceil_div(ah_blocks(d, m), 8) * 4; }
+
+// dist + (a - b)^2 in three rounded fp32 operations.  The pragma keeps the product out of a fused multiply-add: the
+// compiler's default contracts across statements, and the __f*_rn intrinsics are plain operators to it.
+__device__ __forceinline__ float add_square(float dist, float a, float b) {
+#pragma clang fp contract(off)
+  const float w = a - b;
+  const float p = w * w;
+  return dist + p;
+}
+
+// 8 consecutive elements from e0 of a row that is d long, as floats; zero from d on
+template <int ES, bool VEC>
+__device__ __forceinline__ void load8(const char* row, int e0, int d, float (&v)[8]) {
+  if constexpr (ES == 2) {
+    const u32x4 w = load_k_chunk<2, VEC>(row, e0 / 8, d);
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      v[2 * x] = __uint_as_float(w[x] << 16);
+      v[2 * x + 1] = __uint_as_float(w[x] & 0xffff0000u);
+    }
+  } else {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const u32x4 w = load_k_chunk<4, VEC>(row, e0 / 4 + h, d);
+#pragma unroll
+      for (int x = 0; x < 4; ++x) v[4 * h + x] = __uint_as_float(w[x]);
+    }
+  }
+}
+
+// krs_ah_encode: a thread owns 8 consecutive columns of one stored row, so 8 / M blocks and 32 / M code bits; M
+// neighbouring lanes (the row has a whole number of words, so they never straddle a row or a wave) OR their bits into one
+// 4-byte word of the code row.  The codebooks sit in LDS as fp32, transposed to [code][column], so the lanes of a wave read
+// consecutive addresses for one code.  grid-stride: `total` = n * units rounded up to a wave, so every shuffle is whole.
+template <int ES, bool VEC, int M>
+__global__ __launch_bounds__(256) void ah_encode_kernel(const char* x, int64_t ldx, const int32_t* row_index,
+                                                        const int32_t* row_leaf, const char* cen, int64_t ldm,
+                                                        const uint16_t* codebooks, int64_t n, int d, int leaves, int blocks,
+                                                        int units, uint8_t* codes, int64_t ldcode, int64_t total) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* cbs = reinterpret_cast<float*>(smem);       // [16][kpad]
+  const int kpad = units * 8;
+  for (int i = threadIdx.x; i < 16 * kpad; i += blockDim.x) {
+    const int c = i / kpad, col = i % kpad, blk = col / M;
+    cbs[i] = blk < blocks && col < d ? bf16_to_f32(codebooks[(blk * 16 + c) * M + col % M]) : 0.0f;
+  }
+  __syncthreads();
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t s = t / units;
+    const int u = (int)(t % units);
+    uint32_t bits = 0;
+    if (s < n) {
+      const int64_t src = row_index ? (int64_t)row_index[s] : s;
+      const int leaf = row_leaf[s];
+      float xv[8], cv[8], e[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) xv[i] = cv[i] = 0.0f;
+      if (src >= 0 && src < n) load8<ES, VEC>(x + src * ldx * ES, u * 8, d, xv);
+      if (leaf >= 0 && leaf < leaves) load8<ES, VEC>(cen + (int64_t)leaf * ldm * ES, u * 8, d, cv);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) e[i] = __fsub_rn(xv[i], cv[i]);
+#pragma unroll
+      for (int bi = 0; bi < 8 / M; ++bi) {
+        uint32_t best = 0;
+        float bd = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+          float dist = 0.0f;
+#pragma unroll
+          for (int i = 0; i < M; ++i) dist = add_square(dist, e[bi * M + i], cbs[c * kpad + u * 8 + bi * M + i]);
+          if (c == 0 || dist < bd) {       // strict: a tie stays with the lowest code
+            bd = dist;
+            best = (uint32_t)c;
+          }
+        }
+        bits |= best << (4 * bi);
+      }
+      bits <<= (u % M) * (32 / M);
+    }
+#pragma unroll
+    for (int o = 1; o < M; o <<= 1) bits |= (uint32_t)__shfl_xor((int)bits, o, 64);
+    if (s < n && u % M == 0) *reinterpret_cast<uint32_t*>(codes + s * ldcode + (u / M) * 4) = bits;
+  }
+}
+
+// krs_retrieval_rescore: workgroup = one query, wave w = its candidates idx[32 w .. 32 w + 31].  The query row is the A
+// fragment of all 32 tile rows and the gathered candidate rows are the B fragment, in the K steps of stage1_body, so every
+// accumulator row holds K8's score of (query, candidate) and register 0 is taken.  An index outside [0, n) is padding.
+template <int ES, bool VEC>
+__global__ __launch_bounds__(256) void retr_rescore_kernel(const char* q, int64_t ldq, const char* rows, int64_t ldr,
+                                                           const int32_t* idx, int64_t ldi, int64_t n, int d, int r,
+                                                           int row_bytes, uint64_t* pairs) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int frow = lane & 31, fhalf = lane >> 5;
+  if (wave * 32 >= r) return;             // wave-uniform; the kernel has no barrier
+  const int64_t row = blockIdx.x;
+  const int j = wave * 32 + frow;
+  const int64_t i = j < r ? (int64_t)idx[row * ldi + j] : -1;
+  const bool valid = i >= 0 && i < n;
+  const char* crow = rows + (valid ? i : 0) * ldr * ES;
+  const char* qrow = q + row * ldq * ES;
+  f32x16 acc;
+#pragma unroll
+  for (int x = 0; x < 16; ++x) acc[x] = 0.0f;
+  const int nks = row_bytes / 32;
+  for (int ks = 0; ks < nks; ++ks) {
+    const int ch = ks * 2 + fhalf;
+    const u32x4 fa = load_k_chunk<ES, VEC>(qrow, ch, d);
+    u32x4 fb = {0, 0, 0, 0};
+    if (valid) fb = load_k_chunk<ES, VEC>(crow, ch, d);
+    if constexpr (ES == 2) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fb), acc, 0,
+                                                    0, 0);
+    } else {
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(fa[x]), __uint_as_float(fb[x]), acc, 0, 0, 0);
+    }
+  }
+  if (fhalf == 0 && j < r) pairs[row * r + j] = valid ? pair_key(order_key(acc[0]), (uint32_t)i) : 0;
+}
+
+// the launches of krs_retrieval_rescore after its checks: the scores as pairs [b, r], then the selection's LDS route
+inline int rescore_launch(const void* q, int64_t ldq, const void* rows, int64_t ldr, const int32_t* idx, int64_t ldi,
+                          const int32_t* ids, int dtype, int64_t b, int64_t n, int64_t d, int r, int k, void* out_scores,
+                          int32_t* out_ids, uint64_t* pairs, hipStream_t st) {
+  const int es = dtype == KRS_BF16 ? 2 : 4;
+  const bool vec = rplan::vec_loads(d, es, ldr, (uint64_t)reinterpret_cast<uintptr_t>(rows)) &&
+                   rplan::vec_loads(d, es, ldq, (uint64_t)reinterpret_cast<uintptr_t>(q));
+  const int rb = rplan::row_bytes(d, es);
+#define KRS_RESCORE(ES_, VEC_)                                                                                       \
+  hipLaunchKernelGGL((retr_rescore_kernel<ES_, VEC_>), dim3((unsigned)b), dim3(256), 0, st,                          \
+                     reinterpret_cast<const char*>(q), ldq, reinterpret_cast<const char*>(rows), ldr, idx, ldi, n,   \
+                     (int)d, r, rb, pairs)
+  if (es == 2) {
+    if (vec) KRS_RESCORE(2, true); else KRS_RESCORE(2, false);
+  } else {
+    if (vec) KRS_RESCORE(4, true); else KRS_RESCORE(4, false);
+  }
+#undef KRS_RESCORE
+  KRS_CHECK_LAUNCH("retr_rescore_kernel");
+  const rplan::Select sel = rplan::plan_select(r, k);      // r <= 128: the LDS route, no list
+  const Out out{out_ids, out_scores, dtype, ids, k, 0, n};
+  return select_rows(PairSrc{pairs, sel.len}, b, sel, k, out, nullptr, st);
+}
+
+inline int rescore_check(int64_t b, int64_t n, int64_t d, int r, int k, int dtype) {
+  KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1, "krs_retrieval_rescore: bad shape b=%lld n=%lld d=%lld", (long long)b,
+              (long long)n, (long long)d);
+  KRS_REQUIRE(n <= INT32_MAX && b <= INT32_MAX, "krs_retrieval_rescore: more than 2^31 - 1 candidates or queries");
+  KRS_REQUIRE(r >= 1 && k >= 1 && k <= r, "krs_retrieval_rescore: k = %d outside [1, r = %d]", k, r);
+  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "krs_retrieval_rescore: bad dtype");
+  if (r > kAhMaxR)
+    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_rescore: r = %d above the limit of %d", r, kAhMaxR);
+  if (d > kFusedMaxD)
+    return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_rescore: d = %lld above the limit of %d", (long long)d, kFusedMaxD);
+  return KRS_OK;
+}
+
+// workspace of a krs_retrieval_ivf_ah call: krs_retrieval_ivf's with k = r, then the fp32 probe scores [b, probes], and
+// with reordering the merged indices [b, r] and the rescored pairs [b, r]
+struct AhWorkspace {
+  IvfWorkspace ivf;
+  size_t pscore, idx, rpairs, total;
+};
+inline AhWorkspace ah_workspace(int64_t b, int64_t d, int64_t leaves, int probes, int r, int dtype, bool reorder) {
+  AhWorkspace w;
+  w.ivf = ivf_workspace(b, d, leaves, probes, r, dtype);
+  w.pscore = w.ivf.total;
+  w.idx = w.pscore + align256((size_t)b * probes * sizeof(float));
+  w.rpairs = w.idx + (reorder ? align256((size_t)b * r * sizeof(int32_t)) : 0);
+  w.total = w.rpairs + (reorder ? align256((size_t)b * r * sizeof(uint64_t)) : 0);
+  return w;
+}
+// the shape checks of krs_retrieval_ivf_ah and its workspace function; r is the list length of the scan and the merge
+inline int ah_check(int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k, int r, int m, bool reorder,
+                    int dtype) {
+  const int rc = ivf_check("krs_retrieval_ivf_ah", b, n, d, leaves, probes, k, dtype);
+  if (rc != KRS_OK) return rc;
+  KRS_REQUIRE(ah_m_ok(m), "krs_retrieval_ivf_ah: dimensions_per_block = %d, not 2, 4 or 8", m);
+  KRS_REQUIRE(reorder ? r >= k : r == k, "krs_retrieval_ivf_ah: r = %d %s k = %d", r,
+              reorder ? "below" : "differs (without float rows) from", k);
+  if (r > kAhMaxR) return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_ivf_ah: r = %d above the limit of %d", r, kAhMaxR);
+  return KRS_OK;
+}
+}  // namespace
+}  // namespace krs
+
+extern "C" int64_t krs_ah_code_bytes(int64_t d, int m) {
+  using namespace krs;
+  return d >= 1 && d <= kFusedMaxD && ah_m_ok(m) ? ah_code_bytes(d, m) : 0;
+}
+
+extern "C" int krs_ah_encode(const void* x, int64_t ldx, const int32_t* row_index, const int32_t* row_leaf,
+                             const void* centroids, int64_t ldm, int dtype, const void* codebooks, int64_t n, int64_t d,
+                             int64_t leaves, int m, uint8_t* codes, int64_t ldcode, void* stream) {
+  using namespace krs;
+  KRS_REQUIRE(n >= 0 && d >= 1 && leaves >= 1, "krs_ah_encode: bad shape n=%lld d=%lld leaves=%lld", (long long)n,
+              (long long)d, (long long)leaves);
+  KRS_REQUIRE(n <= INT32_MAX && leaves < INT32_MAX, "krs_ah_encode: more than 2^31 - 1 rows or leaves");
+  KRS_REQUIRE(ah_m_ok(m), "krs_ah_encode: dimensions_per_block = %d, not 2, 4 or 8", m);
+  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "krs_ah_encode: bad dtype");
+  if (d > kFusedMaxD)
+    return fail(KRS_ERR_UNSUPPORTED, "krs_ah_encode: d = %lld above the limit of %d", (long long)d, kFusedMaxD);
+  const int64_t cbytes = ah_code_bytes(d, m);
+  KRS_REQUIRE(ldx >= d && ldm >= d, "krs_ah_encode: row stride below d");
+  KRS_REQUIRE(ldcode >= cbytes && ldcode % 4 == 0, "krs_ah_encode: code row stride %lld below %lld or not a multiple of 4",
+              (long long)ldcode, (long long)cbytes);
+  if (n == 0) return KRS_OK;
+  KRS_REQUIRE(x && row_leaf && centroids && codebooks && codes, "krs_ah_encode: null operand");
+  KRS_REQUIRE((reinterpret_cast<uintptr_t>(codes) & 3) == 0, "krs_ah_encode: codes not on a 4-byte boundary");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int es = dtype == KRS_BF16 ? 2 : 4;
+  const bool vec = rplan::vec_loads(d, es, ldx, (uint64_t)reinterpret_cast<uintptr_t>(x)) &&
+                   rplan::vec_loads(d, es, ldm, (uint64_t)reinterpret_cast<uintptr_t>(centroids));
+  const int units = (int)(cbytes / 4) * m;                 // 8-column units of a row: its code words times M
+  const int64_t total = ceil_div(n * units, 64) * 64;
+  const size_t lds = (size_t)16 * units * 8 * sizeof(float);
+  const dim3 grid((unsigned)std::min<int64_t>(ceil_div(total, 256), kAhEncodeGroups));
+#define KRS_AH_ENCODE(ES_, VEC_, M_)                                                                                 \
+  hipLaunchKernelGGL((ah_encode_kernel<ES_, VEC_, M_>), grid, dim3(256), lds, st, reinterpret_cast<const char*>(x), \
+                     ldx, row_index, row_leaf, reinterpret_cast<const char*>(centroids), ldm,                       \
+                     reinterpret_cast<const uint16_t*>(codebooks), n, (int)d, (int)leaves, (int)ah_blocks(d, m),     \
+                     units, codes, ldcode, total)
+#define KRS_AH_ENCODE_M(ES_, VEC_)                                                                                   \
+  {                                                                                                                  \
+    if (m == 2) KRS_AH_ENCODE(ES_, VEC_, 2);                                                                         \
+    else if (m == 4) KRS_AH_ENCODE(ES_, VEC_, 4);                                                                    \
+    else KRS_AH_ENCODE(ES_, VEC_, 8);                                                                                \
+  }
+  if (es == 2) {
+    if (vec) KRS_AH_ENCODE_M(2, true) else KRS_AH_ENCODE_M(2, false)
+  } else {
+    if (vec) KRS_AH_ENCODE_M(4, true) else KRS_AH_ENCODE_M(4, false)
+  }
+#undef KRS_AH_ENCODE_M
+#undef KRS_AH_ENCODE
+  KRS_CHECK_LAUNCH("ah_encode_kernel");
+  return KRS_OK;
+}
+
+extern "C" size_t krs_retrieval_rescore_workspace_bytes(int64_t b, int r, int k) {
+  using namespace krs;
+  if (b <= 0 || r < 1 || r > kAhMaxR || k < 1 || k > r) return 0;
+  return align256((size_t)b * r * sizeof(uint64_t));
+}
+
+extern "C" int krs_retrieval_rescore(const void* q, int64_t ldq, const void* rows, int64_t ldr, const int32_t* idx,
+                                     int64_t ldi, const int32_t* ids, int dtype, int64_t b, int64_t n, int64_t d, int r,
+                                     int k, void* out_scores, int32_t* out_ids, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  using namespace krs;
+  const int rc = rescore_check(b, n, d, r, k, dtype);
+  if (rc != KRS_OK) return rc;
+  KRS_REQUIRE(ldq >= d && ldr >= d, "krs_retrieval_rescore: row stride below d");
+  KRS_REQUIRE(ldi >= r, "krs_retrieval_rescore: index row stride below r");
+  if (b == 0) return KRS_OK;
+  KRS_REQUIRE(q && rows && idx && out_ids, "krs_retrieval_rescore: null operand");
+  const size_t need = krs_retrieval_rescore_workspace_bytes(b, r, k);
+  if (!workspace || workspace_bytes < need)
+    return fail(KRS_ERR_WORKSPACE, "krs_retrieval_rescore: needs %zu workspace bytes, got %zu", need, workspace_bytes);
+  return rescore_launch(q, ldq, rows, ldr, idx, ldi, ids, dtype, b, n, d, r, k, out_scores, out_ids,
+                        reinterpret_cast<uint64_t*>(workspace), reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t krs_retrieval_ivf_ah_workspace_bytes(int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k,
+                                                       int r, int m, int reorder, int dtype) {
+  using namespace krs;
+  if (b <= 0 || ah_check(b, n, d, leaves, probes, k, r, m, reorder != 0, dtype) != KRS_OK) return 0;
+  return ah_workspace(b, d, leaves, probes, r, dtype, reorder != 0).total;
+}
+
+extern "C" int krs_retrieval_ivf_ah(const void* q, int64_t ldq, const void* centroids, int64_t ldm, const void* codebooks,
+                                    int m, const uint8_t* codes, int64_t ldcode, const int32_t* leaf_offsets,
+                                    const int32_t* row_index, const void* rows, int64_t ldr, const int32_t* ids, int dtype,
+                                    int64_t b, int64_t n, int64_t d, int64_t leaves, int probes, int k, int r,
+                                    void* out_scores, int32_t* out_ids, int32_t* out_leaves, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  using namespace krs;
+  const bool reorder = rows != nullptr;
+  const int rc = ah_check(b, n, d, leaves, probes, k, r, m, reorder, dtype);
+  if (rc != KRS_OK) return rc;
+  KRS_REQUIRE(ldq >= d && ldm >= d && (!reorder || ldr >= d), "krs_retrieval_ivf_ah: row stride below d");
+  const int64_t cbytes = ah_code_bytes(d, m);
+  KRS_REQUIRE(ldcode >= cbytes && ldcode % 4 == 0,
+              "krs_retrieval_ivf_ah: code row stride %lld below %lld or not a multiple of 4", (long long)ldcode,
+              (long long)cbytes);
+  if (b == 0) return KRS_OK;
+  KRS_REQUIRE(q && centroids && codebooks && codes && leaf_offsets && row_index && out_ids,
+              "krs_retrieval_ivf_ah: null operand");
+  KRS_REQUIRE((reinterpret_cast<uintptr_t>(codes) & 3) == 0, "krs_retrieval_ivf_ah: codes not on a 4-byte boundary");
+  const AhWorkspace w = ah_workspace(b, d, leaves, probes, r, dtype, reorder);
+  if (!workspace || workspace_bytes < w.total)
+    return fail(KRS_ERR_WORKSPACE, "krs_retrieval_ivf_ah: needs %zu workspace bytes, got %zu", w.total, workspace_bytes);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* ws = reinterpret_cast<char*>(workspace);
+  int32_t* probe = out_leaves ? out_leaves : reinterpret_cast<int32_t*>(ws + w.ivf.probe);
+  float* pscore = reinterpret_cast<float*>(ws + w.pscore);
+  uint64_t* pairs = reinterpret_cast<uint64_t*>(ws + w.ivf.pairs);
+  const int64_t bp = b * probes;
+
+  // a. probe, as krs_retrieval_ivf's, keeping the fp32 scores
+  const int rp = retrieval_topk_impl(q, ldq, centroids, ldm, nullptr, dtype, b, leaves, d, probes, pscore, KRS_F32, probe,
+                                     ws + w.ivf.probe_ws, w.ivf.probe_ws_bytes, stream);
+  if (rp != KRS_OK) return rp;
+  // b. invert
+  const int ri = ivf_invert(probe, bp, leaves, ws, w.ivf, st);
+  if (ri != KRS_OK) return ri;
+
+  // c. scan over the codes: krs_retrieval_ivf's work items and grid, r pairs per (query, slot)
+  Stage1 p;
+  p.q = reinterpret_cast<const char*>(q); p.ldq = ldq;
+  p.c = nullptr; p.ldc = 0;
+  p.b = b; p.n = n; p.d = d; p.k = r; p.cap = kQueue;
+  p.slice = 0; p.S = 1; p.qtiles = 1;
+  p.row_bytes = rplan::row_bytes(d, 2);
+  p.out = pairs;
+  const Ivf iv{reinterpret_cast<const int32_t*>(ws + w.ivf.tile_start), reinterpret_cast<const int32_t*>(ws + w.ivf.list_start),
+               reinterpret_cast<const int32_t*>(ws + w.ivf.list), leaf_offsets, row_index, (int)leaves, probes};
+  const Ah ah{codes, ldcode, (int)(cbytes / 4), reinterpret_cast<const uint16_t*>(codebooks), (int)ah_blocks(d, m), pscore,
+              dtype == KRS_F32};
+  // krs_retrieval_ivf's LDS, then the codebooks over the tile's K extent: 16 centres of 2 bytes per column
+  const size_t lds = (size_t)rplan::stage1_lds(p.row_bytes, KRS_RETR_VARIANT_TOPK, 2 * kQM) + (size_t)p.row_bytes * 16;
+  const dim3 grid((unsigned)(ceil_div(bp, kQM) + std::min<int64_t>(leaves, bp)));
+#define KRS_AH_SCAN(M_)                                                                                              \
+  {                                                                                                                  \
+    auto kern = retr_ivf_ah_scan_kernel<M_>;                                                                         \
+    KRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,    \
+                                (int)lds));                                                                          \
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p, iv, ah);                                                   \
+  }
+  if (m == 2) KRS_AH_SCAN(2) else if (m == 4) KRS_AH_SCAN(4) else KRS_AH_SCAN(8)
+#undef KRS_AH_SCAN
+  KRS_CHECK_LAUNCH("retr_ivf_ah_scan_kernel");
+
+  // d. merge to r pairs per query; e. without float rows they are the result, else their exact scores choose the k
+  const rplan::Select sel = rplan::plan_select((int64_t)probes * r, r);
+  uint64_t* list = reinterpret_cast<uint64_t*>(ws + w.ivf.merge);
+  if (!reorder) {
+    const Out out{out_ids, out_scores, dtype, ids, r, 0, n};
+    return select_rows(PairSrc{pairs, sel.len}, b, sel, r, out, list, st);
+  }
+  int32_t* idx = reinterpret_cast<int32_t*>(ws + w.idx);
+  const Out merged{idx, nullptr, KRS_F32, nullptr, r, 0, n};
+  const int rs = select_rows(PairSrc{pairs, sel.len}, b, sel, r, merged, list, st);
+  if (rs != KRS_OK) return rs;
+  return rescore_launch(q, ldq, rows, ldr, idx, r, ids, dtype, b, n, d, r, k, out_scores, out_ids,
+                        reinterpret_cast<uint64_t*>(ws + w.rpairs), st);
 }

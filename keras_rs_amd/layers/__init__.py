@@ -12,11 +12,11 @@ from keras_rs_amd.layers.losses import (BinaryCrossentropy, CategoricalCrossentr
 from keras_rs_amd.layers.metrics import (AUC, BinaryAccuracy, BinaryMetricGroup, SparseTopKCategoricalAccuracy,
                                          auc_from_confusion)
 from keras_rs_amd.layers.recurrent import GRU
-from keras_rs_amd.layers.retrieval import (BruteForceRetrieval, FactorizedTopK, HardNegativeMining, InBatchSoftmaxLoss,
-                                           PartitionedRetrieval, RemoveAccidentalHits, Retrieval,
-                                           SamplingProbabilityCorrection)
+from keras_rs_amd.layers.retrieval import (AsymmetricHashingRetrieval, BruteForceRetrieval, FactorizedTopK,
+                                           HardNegativeMining, InBatchSoftmaxLoss, PartitionedRetrieval,
+                                           RemoveAccidentalHits, Retrieval, SamplingProbabilityCorrection)
 from keras_rs_amd.layers.sequence import LayerNormalization, MultiHeadAttention, TransformerDecoder
 
-__all__ = ["AUC", "Adagrad", "Adam", "BinaryAccuracy", "BinaryCrossentropy", "BinaryMetricGroup", "auc_from_confusion", "binary_crossentropy", "BruteForceRetrieval", "CategoricalCrossentropy", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
+__all__ = ["AUC", "Adagrad", "Adam", "AsymmetricHashingRetrieval", "BinaryAccuracy", "BinaryCrossentropy", "BinaryMetricGroup", "auc_from_confusion", "binary_crossentropy", "BruteForceRetrieval", "CategoricalCrossentropy", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
            "FactorizedTopK", "FeatureCross", "Ftrl", "GRU", "HardNegativeMining", "InBatchSoftmaxLoss", "LayerNormalization", "MultiHeadAttention", "PartitionedRetrieval", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SamplingProbabilityCorrection",
            "SparseCategoricalCrossentropy", "SparseTopKCategoricalAccuracy", "TableConfig", "TransformerDecoder", "concat_features"]

@@ -10,7 +10,9 @@ positive's rank among all candidates, again without the scores (K15: krs_retriev
 serving form, `quantize("int8")`: an int8 candidate index scored on the int8 matrix cores (K17: krs_retrieval_topk_q8).
 PartitionedRetrieval is the approximate index: the candidates are partitioned into leaves by spherical k-means and a query
 is scored against the candidates of its best few leaves only (K21: krs_retrieval_ivf), the partitioning stage of the
-ScaNN index the reference's examples/scann.py serves from.
+ScaNN index the reference's examples/scann.py serves from.  AsymmetricHashingRetrieval adds that index's other two stages on
+the same partition: 4-bit codes scored on the matrix cores and an exact rescoring of the best few (K23: krs_ah_encode,
+krs_retrieval_ivf_ah, krs_retrieval_rescore).
 
 Selection order: score descending, then candidate index ascending (-0.0 as +0.0, NaN above +inf); rows come back
 sorted.  Known divergence: for bf16 inputs keras.ops.matmul rounds the scores to bf16 before top_k, so among
@@ -466,6 +468,194 @@ class PartitionedRetrieval(Retrieval):
         config = super().get_config()
         config.update({"num_leaves": self.num_leaves, "num_leaves_to_search": self.num_leaves_to_search,
                        "training_iterations": self.training_iterations, "seed": self.seed})
+        return config
+
+
+def unpack_codes(codes: torch.Tensor, blocks: int) -> torch.Tensor:
+    """The nibbles of code rows uint8 [N, bytes] as int64 [N, blocks]: block j is nibble j, the low half of byte j // 2
+    for even j (include/krs.h, K23)."""
+    c = codes.to(torch.int64)
+    return torch.stack((c & 15, c >> 4), dim=2).reshape(codes.shape[0], -1)[:, :blocks]
+
+
+class AsymmetricHashingRetrieval(PartitionedRetrieval):
+    """PartitionedRetrieval with ScaNN's other two stages (the reference's examples/scann.py: tree(...),
+    score_ah(dimensions_per_block), reorder(n)); include/krs.h, K23.  A candidate is stored as one 4-bit code per block
+    of `dimensions_per_block` columns of its residual x - centroid[leaf(x)]: 16 centres per block, so D / (2 m) bytes a
+    row instead of D floats.  A query is scored against the codes of its best leaves, q . decode(code) + q . centroid
+    (the AH score), on the matrix cores.
+
+    * `num_reordering_candidates=None`: `call` returns K21's tuple and THE SCORES ARE AH SCORES, approximations of
+      q . x, ranked as they are (AH score descending, candidate index ascending).  The float rows are not kept: not on
+      the device, not in state_dict().
+    * `num_reordering_candidates=R` (k <= R <= 128): the best R by AH score are rescored against the float rows and the k
+      best of those returned: the scores are exact (K8's bits), the order is BruteForceRetrieval's over those R.
+
+    `update_candidates` partitions as PartitionedRetrieval does, then trains the codebooks (not capturable, host-driven):
+    Lloyd's k-means with Euclidean distance, per block, on the residuals of `training_sample_size` rows drawn on the host
+    from `seed`; the first centres of every block are the sub-vectors of 16 sampled residuals; each of the
+    `training_iterations` steps codes the sample with krs_ah_encode (the lowest code on a tie) and replaces a centre by
+    the float64 mean of its members, summed by a plain reduction over the sample axis (a fixed order: the same input and
+    seed give the same codebooks and codes); an empty centre keeps its value.  Then every row is coded in one pass.
+    `from_codebooks` takes partition and codebooks from outside and only encodes.  state_dict() holds the index
+    (`centroids`, `leaf_offsets`, `row_index`, `candidate_ids`, `codebooks`, `codes`, and `float_rows` in ORIGINAL order
+    only when reordering); loading it restores the index without training.  `anisotropic_quantization_threshold` other
+    than None raises NotImplementedError: the codebooks minimise the plain reconstruction error."""
+
+    _INDEX = ("leaf_offsets", "row_index", "centroids", "candidate_ids", "codebooks", "codes", "float_rows")
+
+    def __init__(self, candidate_embeddings=None, candidate_ids=None, k: int = 10, return_scores: bool = True,
+                 num_leaves: int | None = None, num_leaves_to_search: int | None = None, training_iterations: int = 12,
+                 seed: int = 0, dimensions_per_block: int = 2, num_reordering_candidates: int | None = None,
+                 training_sample_size: int = 100_000, anisotropic_quantization_threshold=None, **kwargs: Any):
+        super().__init__(k=k, return_scores=return_scores, num_leaves=num_leaves,
+                         num_leaves_to_search=num_leaves_to_search, training_iterations=training_iterations, seed=seed,
+                         **kwargs)
+        if not _is_int(dimensions_per_block) or dimensions_per_block not in retrieval_ops.AH_BLOCK_DIMS:
+            raise ValueError(f"`dimensions_per_block` should be one of {retrieval_ops.AH_BLOCK_DIMS}. Received: "
+                             f"dimensions_per_block={dimensions_per_block!r}")
+        if num_reordering_candidates is not None and (
+                not _is_int(num_reordering_candidates) or not k <= num_reordering_candidates <= retrieval_ops.AH_MAX_R):
+            raise ValueError(f"`num_reordering_candidates` should be None or an integer in [k = {k}, "
+                             f"{retrieval_ops.AH_MAX_R}]. Received: num_reordering_candidates="
+                             f"{num_reordering_candidates!r}")
+        if not _is_int(training_sample_size) or training_sample_size < 16:
+            raise ValueError("`training_sample_size` should be an integer >= 16. Received: "
+                             f"training_sample_size={training_sample_size!r}")
+        if anisotropic_quantization_threshold is not None:
+            raise NotImplementedError("`anisotropic_quantization_threshold`: the score-aware quantization loss is not "
+                                      "implemented; pass None (plain reconstruction error).")
+        self.dimensions_per_block = int(dimensions_per_block)
+        self.num_reordering_candidates = None if num_reordering_candidates is None else int(num_reordering_candidates)
+        self.training_sample_size = int(training_sample_size)
+        self.anisotropic_quantization_threshold = None
+        self._converted: dict[torch.dtype, tuple] = {}     # (centroids, float rows or None) in another query dtype
+        if candidate_embeddings is None:
+            if candidate_ids is not None:
+                raise ValueError("You cannot provide `candidate_ids` without providing `candidate_embeddings`")
+        else:
+            self.update_candidates(candidate_embeddings, candidate_ids)
+
+    @classmethod
+    def from_codebooks(cls, candidate_embeddings, centroids, assignments, codebooks, candidate_ids=None, **kwargs: Any):
+        """An index over a partition AND codebooks made elsewhere: centroids and assignments as from_partition's,
+        codebooks [ceil(D / m), 16, m] (rounded to bfloat16).  Nothing is trained: the rows are encoded, that is all."""
+        cb = _as_tensor(codebooks).detach()
+        if cb.dim() != 3 or cb.shape[1] != 16 or cb.shape[2] not in retrieval_ops.AH_BLOCK_DIMS:
+            raise ValueError("`codebooks` must have shape (blocks, 16, dimensions_per_block) with dimensions_per_block in "
+                             f"{retrieval_ops.AH_BLOCK_DIMS}, received shape {tuple(cb.shape)}")
+        if kwargs.setdefault("dimensions_per_block", cb.shape[2]) != cb.shape[2]:
+            raise ValueError(f"`dimensions_per_block` = {kwargs['dimensions_per_block']} differs from the codebooks' "
+                             f"{cb.shape[2]}")
+        d = _as_tensor(candidate_embeddings).shape[-1]
+        if cb.shape[0] != -(-d // cb.shape[2]):
+            raise ValueError(f"`codebooks` has {cb.shape[0]} blocks, D = {d} columns in blocks of {cb.shape[2]} need "
+                             f"{-(-d // cb.shape[2])}")
+        cls._next_codebooks = cb
+        try:
+            return cls.from_partition(candidate_embeddings, centroids, assignments, candidate_ids, **kwargs)
+        finally:
+            cls._next_codebooks = None
+
+    _next_codebooks = None        # from_codebooks -> the _set_index of the layer from_partition makes
+
+    def _train_codebooks(self, emb: torch.Tensor, centroids: torch.Tensor, assignments: torch.Tensor) -> torch.Tensor:
+        """Lloyd's k-means per block (class docstring).  Returns the codebooks bfloat16 [blocks, 16, m]."""
+        n, d = emb.shape
+        m = self.dimensions_per_block
+        blocks = -(-d // m)
+        rng = np.random.default_rng(self.seed)
+        s = min(n, self.training_sample_size)
+        sample = torch.as_tensor(np.sort(rng.choice(n, size=s, replace=False)), device=emb.device)
+        first = torch.as_tensor(rng.choice(s, size=16, replace=s < 16), device=emb.device)
+        x = emb[sample].contiguous()
+        leaf = assignments[sample].to(torch.int32).contiguous()
+        res = torch.zeros((s, blocks * m), dtype=torch.float64, device=emb.device)
+        res[:, :d] = (x.to(torch.float32) - centroids[leaf.to(torch.int64)].to(torch.float32)).to(torch.float64)
+        res = res.view(s, blocks, m)
+        cb = res[first].permute(1, 0, 2).contiguous()                        # [blocks, 16, m] float64
+        for _ in range(self.training_iterations):
+            codes = unpack_codes(retrieval_ops.ah_encode(x, leaf, centroids, cb.to(torch.bfloat16)), blocks)
+            for c in range(16):
+                member = (codes == c)[:, :, None]                            # [s, blocks, 1]
+                count = member.sum(0)                                        # [blocks, 1]
+                mean = (res * member).sum(0) / count.clamp(min=1)
+                cb[:, c, :] = torch.where(count > 0, mean, cb[:, c, :])
+        return cb.to(torch.bfloat16).contiguous()
+
+    def _set_index(self, emb, centroids, assignments, ids) -> None:
+        leaves = centroids.shape[0]
+        if self.num_leaves_to_search is not None and self.num_leaves_to_search > leaves:
+            raise ValueError(f"`num_leaves_to_search` = {self.num_leaves_to_search} is more than the {leaves} leaves.")
+        L.require_device(emb, "AsymmetricHashingRetrieval candidates")
+        given = type(self)._next_codebooks
+        centroids = centroids.contiguous()
+        codebooks = (self._train_codebooks(emb, centroids, assignments) if given is None
+                     else given.to(emb.device, torch.bfloat16).contiguous())
+        row_index, leaf_offsets = partition_layout(assignments, leaves)
+        row_leaf = assignments.to(torch.int32)[row_index.to(torch.int64)].contiguous()
+        self.codes = retrieval_ops.ah_encode(emb, row_leaf, centroids, codebooks, row_index=row_index)
+        self.codebooks = codebooks
+        self.leaf_offsets, self.row_index = leaf_offsets, row_index
+        self.centroids = centroids
+        self.candidate_ids = None if ids is None else ids.contiguous()
+        self.float_rows = emb.contiguous() if self.num_reordering_candidates is not None else None
+        self._converted.clear()
+        self.built = True
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        """A saved index replaces whatever the layer holds: the buffers take the saved shapes and dtypes."""
+        for name in self._INDEX:
+            saved = state_dict.get(prefix + name)
+            setattr(self, name, None if saved is None else torch.empty_like(saved, device=self._device))
+        torch.nn.Module._load_from_state_dict(self, state_dict, prefix, *args, **kwargs)
+        self._converted.clear()
+        self.built = self.codes is not None
+
+    def index_bytes(self) -> int:
+        """Bytes of the stored index (every buffer of state_dict())."""
+        return sum(t.numel() * t.element_size() for t in self.state_dict().values())
+
+    def _index_as(self, dtype: torch.dtype):
+        if self.centroids.dtype == dtype:
+            return self.centroids, self.float_rows
+        conv = self._converted.get(dtype)
+        if conv is None:
+            conv = self._converted[dtype] = (self.centroids.to(dtype),
+                                             None if self.float_rows is None else self.float_rows.to(dtype))
+        return conv
+
+    def call(self, inputs, return_leaves: bool = False):
+        if self.codes is None:
+            raise ValueError("No candidates: call `update_candidates` before using the layer.")
+        d = self.centroids.shape[1]
+        q = _as_tensor(inputs)
+        if q.dim() != 2 or q.shape[1] != d:
+            raise ValueError(f"The query must have shape (batch, {d}), received {tuple(q.shape)}")
+        L.require_device(q, "AsymmetricHashingRetrieval query")
+        reorder = self.num_reordering_candidates is not None
+        if reorder and self.float_rows is None:
+            raise ValueError("`num_reordering_candidates` is set but the index holds no float rows (it was built or saved "
+                             "without reordering): rebuild it with `update_candidates`.")
+        dt = torch.promote_types(q.dtype, self.centroids.dtype)
+        if dt not in (torch.float32, torch.bfloat16):
+            raise L.KrsError(f"AsymmetricHashingRetrieval: unsupported query dtype {q.dtype} (float32 / bfloat16)")
+        centroids, rows = self._index_as(dt)
+        out = retrieval_ops.retrieval_ivf_ah(q.detach().to(dt), centroids, self.codebooks, self.codes, self.leaf_offsets,
+                                             self.row_index, self.k, self.probes(), rows=rows if reorder else None,
+                                             num_reordering_candidates=self.num_reordering_candidates,
+                                             ids=self.candidate_ids, want_scores=self.return_scores,
+                                             want_leaves=return_leaves)
+        if return_leaves:
+            return (out[0], out[1], out[2]) if self.return_scores else (out[1], out[2])
+        return (out[0], out[1]) if self.return_scores else out[1]
+
+    def get_config(self) -> dict:
+        config = super().get_config()
+        config.update({"dimensions_per_block": self.dimensions_per_block,
+                       "num_reordering_candidates": self.num_reordering_candidates,
+                       "training_sample_size": self.training_sample_size,
+                       "anisotropic_quantization_threshold": self.anisotropic_quantization_threshold})
         return config
 
 

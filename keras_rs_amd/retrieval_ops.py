@@ -1,6 +1,6 @@
-"""Host side of K8, K11, K13, K14, K15, K17 and K21: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and
+"""Host side of K8, K11, K13, K14, K15, K17, K21 and K23: thin torch wrappers over krs_topk_rows and krs_retrieval_topk (serving and
 mining), over krs_retrieval_topk_q8 (serving from an int8 index), over krs_retrieval_ivf (serving from a partitioned
-index), over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored
+index), over krs_ah_encode, krs_retrieval_ivf_ah and krs_retrieval_rescore (serving from 4-bit codes, with exact rescoring), over krs_softmax_xent, krs_sampling_correction and krs_remove_accidental_hits (the training head on stored
 scores), over krs_retrieval_xent_fwd / krs_retrieval_xent_bwd (the in-batch softmax loss that never stores the scores),
 over krs_retrieval_mine (the same loss on each row's hardest negatives) and over krs_retrieval_rank (the positive's
 rank among all candidates, for evaluation), all of include/krs.h.
@@ -218,6 +218,150 @@ def retrieval_ivf(query: torch.Tensor, centroids: torch.Tensor, rows: torch.Tens
                                    L.ptr(ids), L.fdtype(q), b, n, d, leaves, probes, k, L.ptr(scores), L.ptr(out_ids),
                                    L.ptr(out_leaves), L.ptr(ws), ws.numel(), L.stream_ptr())
     L.check(rc, "krs_retrieval_ivf")
+    return (scores, out_ids, out_leaves) if want_leaves else (scores, out_ids)
+
+
+# ---- K23: asymmetric hashing over K21's partition, and the reorder stage ---------------------------------------------------
+AH_MAX_R = 128             # most candidates handed to the reorder stage
+AH_BLOCK_DIMS = (2, 4, 8)  # dimensions per block
+
+
+def ah_code_bytes(d: int, m: int) -> int:
+    """Bytes of a code row: one nibble per block of m columns, rounded up to whole 4-byte words (0: unsupported d, m)."""
+    return int(L.lib().krs_ah_code_bytes(d, m))
+
+
+def _dt(dtype: torch.dtype) -> int:
+    return L.BF16 if dtype == torch.bfloat16 else L.F32
+
+
+def _codebooks(codebooks: torch.Tensor, d: int, what: str) -> int:
+    """Checks codebooks bf16 [blocks, 16, m] against d; returns m."""
+    L.require_device(codebooks, what)
+    m = codebooks.shape[2] if codebooks.dim() == 3 else 0
+    if (codebooks.dtype != torch.bfloat16 or m not in AH_BLOCK_DIMS or not codebooks.is_contiguous()
+            or tuple(codebooks.shape) != (-(-d // m), 16, m)):
+        raise L.KrsError(f"{what} must be contiguous bfloat16 [ceil({d} / m), 16, m] with m in {AH_BLOCK_DIMS}, got "
+                         f"{codebooks.dtype} {tuple(codebooks.shape)}")
+    return m
+
+
+def _codes(codes: torch.Tensor, n: int, d: int, m: int, what: str) -> None:
+    L.require_device(codes, what)
+    if (codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[0] != n or codes.shape[1] != ah_code_bytes(d, m)
+            or codes.stride(1) != 1 or (n > 1 and (codes.stride(0) < codes.shape[1] or codes.stride(0) % 4))):
+        raise L.KrsError(f"{what} must be uint8 [{n}, {ah_code_bytes(d, m)}] with a row stride that is a multiple of 4, "
+                         f"got {codes.dtype} {tuple(codes.shape)} strides {tuple(codes.stride())}")
+
+
+def ah_encode(x: torch.Tensor, row_leaf: torch.Tensor, centroids: torch.Tensor, codebooks: torch.Tensor, *,
+              row_index: torch.Tensor | None = None) -> torch.Tensor:
+    """The 4-bit codes uint8 [N, ah_code_bytes(D, m)] of N stored rows (include/krs.h, K23): stored row s is
+    x[row_index[s]] (x[s] without row_index; x [N, D] fp32 / bf16) and belongs to leaf row_leaf[s] (int32 [N]); what is
+    coded is its residual against centroids[leaf] (the dtype of x), block by block against codebooks bf16
+    [blocks, 16, m]: the nearest centre, the lowest code on a tie."""
+    x = L.rowmajor(x, "ah_encode x")
+    cen = L.rowmajor(centroids, "ah_encode centroids")
+    if x.dtype != cen.dtype:
+        raise L.KrsError("ah_encode: x and centroids must share a dtype")
+    n, d = x.shape
+    if cen.shape[1] != d:
+        raise L.KrsError(f"ah_encode: x has {d} columns, centroids {cen.shape[1]}")
+    m = _codebooks(codebooks, d, "ah_encode: codebooks")
+    _int32_vector(row_leaf, n, "ah_encode: row_leaf")
+    if row_index is not None:
+        _int32_vector(row_index, n, "ah_encode: row_index")
+    codes = torch.empty((n, ah_code_bytes(d, m)), dtype=torch.uint8, device=x.device)
+    rc = L.lib().krs_ah_encode(L.ptr(x), x.stride(0) if n > 1 else d, L.ptr(row_index), L.ptr(row_leaf), L.ptr(cen),
+                               cen.stride(0) if cen.shape[0] > 1 else d, L.fdtype(x), L.ptr(codebooks), n, d,
+                               cen.shape[0], m, L.ptr(codes), codes.shape[1], L.stream_ptr())
+    L.check(rc, "krs_ah_encode")
+    return codes
+
+
+def retrieval_rescore_workspace_bytes(b: int, r: int, k: int) -> int:
+    return int(L.lib().krs_retrieval_rescore_workspace_bytes(b, r, k))
+
+
+def retrieval_rescore(query: torch.Tensor, rows: torch.Tensor, idx: torch.Tensor, k: int, *,
+                      ids: torch.Tensor | None = None, want_scores: bool = True):
+    """The k best of each query's listed candidates by exact score (include/krs.h, K23): idx int32 [B, R] holds
+    candidate indices into rows [N, D] (the query's dtype), -1 is padding.  Returns (scores [B, k] in the input dtype or
+    None, int32 ids [B, k]) in BruteForceRetrieval's order, with K8's score bits; -1 / -inf where fewer than k are real."""
+    q = L.rowmajor(query, "retrieval_rescore query")
+    c = L.rowmajor(rows, "retrieval_rescore rows")
+    if q.dtype != c.dtype:
+        raise L.KrsError("retrieval_rescore: query and rows must share a dtype")
+    b, d = q.shape
+    n = c.shape[0]
+    if c.shape[1] != d:
+        raise L.KrsError(f"retrieval_rescore: query width {d} differs from row width {c.shape[1]}")
+    L.require_device(idx, "retrieval_rescore idx")
+    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != b or (idx.shape[1] > 1 and idx.stride(1) != 1):
+        raise L.KrsError(f"retrieval_rescore: idx must be int32 [{b}, R] with contiguous rows, got {idx.dtype} "
+                         f"{tuple(idx.shape)}")
+    r = idx.shape[1]
+    if ids is not None:
+        _int32_vector(ids, n, "retrieval_rescore: ids")
+    scores = torch.empty((b, k), dtype=q.dtype, device=q.device) if want_scores else None
+    out_ids = torch.empty((b, k), dtype=torch.int32, device=q.device)
+    ws = torch.empty(max(1, retrieval_rescore_workspace_bytes(b, r, k)), dtype=torch.uint8, device=q.device)
+    rc = L.lib().krs_retrieval_rescore(L.ptr(q), q.stride(0) if b > 1 else d, L.ptr(c), c.stride(0) if n > 1 else d,
+                                       L.ptr(idx), idx.stride(0) if b > 1 else r, L.ptr(ids), L.fdtype(q), b, n, d, r, k,
+                                       L.ptr(scores), L.ptr(out_ids), L.ptr(ws), ws.numel(), L.stream_ptr())
+    L.check(rc, "krs_retrieval_rescore")
+    return scores, out_ids
+
+
+def retrieval_ivf_ah_workspace_bytes(b: int, n: int, d: int, leaves: int, probes: int, k: int, r: int, m: int,
+                                     reorder: bool, dtype: torch.dtype) -> int:
+    return int(L.lib().krs_retrieval_ivf_ah_workspace_bytes(b, n, d, leaves, probes, k, r, m, int(reorder), _dt(dtype)))
+
+
+def retrieval_ivf_ah(query: torch.Tensor, centroids: torch.Tensor, codebooks: torch.Tensor, codes: torch.Tensor,
+                     leaf_offsets: torch.Tensor, row_index: torch.Tensor, k: int, probes: int, *,
+                     rows: torch.Tensor | None = None, num_reordering_candidates: int | None = None,
+                     ids: torch.Tensor | None = None, want_scores: bool = True, want_leaves: bool = False):
+    """Top-k of query [B, D] over the 4-bit codes of its `probes` best leaves (include/krs.h, K23).  centroids
+    [leaves, D] share the query's dtype; codebooks bf16 [blocks, 16, m]; codes uint8 [N, ah_code_bytes(D, m)] in stored
+    order; leaf_offsets, row_index and ids as retrieval_ivf's.  Without `rows` the scores are AH scores,
+    q . decode(code) + q . centroid.  With rows [N, D] (ORIGINAL order, the query's dtype) the best
+    `num_reordering_candidates` (default k) by AH score are rescored exactly and the k best of those returned.  Returns
+    retrieval_ivf's tuple."""
+    q = L.rowmajor(query, "retrieval_ivf_ah query")
+    cen = L.rowmajor(centroids, "retrieval_ivf_ah centroids")
+    if q.dtype != cen.dtype:
+        raise L.KrsError("retrieval_ivf_ah: query and centroids must share a dtype")
+    b, d = q.shape
+    leaves, n = cen.shape[0], codes.shape[0]
+    if cen.shape[1] != d:
+        raise L.KrsError(f"retrieval_ivf_ah: query width {d} differs from the centroids' {cen.shape[1]}")
+    m = _codebooks(codebooks, d, "retrieval_ivf_ah: codebooks")
+    _codes(codes, n, d, m, "retrieval_ivf_ah: codes")
+    _int32_vector(leaf_offsets, leaves + 1, "retrieval_ivf_ah: leaf_offsets")
+    _int32_vector(row_index, n, "retrieval_ivf_ah: row_index")
+    if ids is not None:
+        _int32_vector(ids, n, "retrieval_ivf_ah: ids")
+    r = k if num_reordering_candidates is None else num_reordering_candidates
+    c = None
+    if rows is not None:
+        c = L.rowmajor(rows, "retrieval_ivf_ah rows")
+        if c.dtype != q.dtype or tuple(c.shape) != (n, d):
+            raise L.KrsError(f"retrieval_ivf_ah: rows must be {q.dtype} [{n}, {d}], got {c.dtype} {tuple(c.shape)}")
+    elif r != k:
+        raise L.KrsError("retrieval_ivf_ah: num_reordering_candidates needs the float rows")
+    scores = torch.empty((b, k), dtype=q.dtype, device=q.device) if want_scores else None
+    out_ids = torch.empty((b, k), dtype=torch.int32, device=q.device)
+    out_leaves = torch.empty((b, probes), dtype=torch.int32, device=q.device) if want_leaves else None
+    ws = torch.empty(max(1, retrieval_ivf_ah_workspace_bytes(b, n, d, leaves, probes, k, r, m, c is not None, q.dtype)),
+                     dtype=torch.uint8, device=q.device)
+    rc = L.lib().krs_retrieval_ivf_ah(L.ptr(q), q.stride(0) if b > 1 else d, L.ptr(cen),
+                                      cen.stride(0) if leaves > 1 else d, L.ptr(codebooks), m, L.ptr(codes),
+                                      codes.stride(0) if n > 1 else codes.shape[1], L.ptr(leaf_offsets), L.ptr(row_index),
+                                      L.ptr(c), 0 if c is None else (c.stride(0) if n > 1 else d), L.ptr(ids),
+                                      L.fdtype(q), b, n, d, leaves, probes, k, r, L.ptr(scores), L.ptr(out_ids),
+                                      L.ptr(out_leaves), L.ptr(ws), ws.numel(), L.stream_ptr())
+    L.check(rc, "krs_retrieval_ivf_ah")
     return (scores, out_ids, out_leaves) if want_leaves else (scores, out_ids)
 
 

@@ -594,6 +594,42 @@ int krs_dense_adagrad(float* const* params, const float* const* grads, float* co
 int krs_colsum(const void* a, int64_t lda, int64_t m, int64_t n, int dtype,
                float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Diagnostic, host only: how the CALLING THREAD's last krs_cross_epilogue_fwd / _bwd, krs_dense_act_bwd or krs_colsum
+ * walked its operand (csrc/dense_walk_plan.h, the one planner of the four entries and of krs_colsum_workspace_bytes).
+ * Every field is 0 when there was no call yet, the call was refused (any return other than KRS_OK) or had nothing to do
+ * (m == 0 or n == 0).
+ *   kernel          KRS_DENSE_WALK_VEC: a thread owns v adjacent columns and moves them in 16 bytes (n and every leading
+ *                   dimension a multiple of v, every non-null operand on 16 bytes); KRS_DENSE_WALK_SCALAR otherwise
+ *   v               columns a thread owns: 4 (fp32) or 8 (bf16) on the vector kernels, 1 on the scalar ones
+ *   acc             krs_cross_epilogue_bwd, vector kernel: the ACC build (dx0 given with dx0_accumulate)
+ *   two_stage       the column sums went through the workspace and colsum_finish_kernel (run-to-run identical bits);
+ *                   0: fp32 atomics, or no column sums were asked for
+ *   rows_per_block  consecutive rows one wave (vector) / one workgroup (scalar) walks: a chunk
+ *   strips          grid.x: strips of 64 threads (64 * v columns)
+ *   chunks          row chunks: rows_per_block * chunks >= m > rows_per_block * (chunks - 1)
+ *   grid_y          grid.y, and the rows of partial sums in the workspace: ceil(chunks / 4) on the vector kernels (one
+ *                   chunk per wave), chunks on the scalar ones
+ * krs_cross_epilogue_fwd has no row walk: it records kernel and v alone.
+ * Returns `kernel`; `route` may be NULL.  Lets tests prove which kernel they ran. */
+enum { KRS_DENSE_WALK_NONE = 0, KRS_DENSE_WALK_VEC, KRS_DENSE_WALK_SCALAR };
+enum { KRS_DENSE_WALK_CROSS_FWD = 0, KRS_DENSE_WALK_CROSS_BWD, KRS_DENSE_WALK_DENSE_ACT_BWD, KRS_DENSE_WALK_COLSUM };
+typedef struct krs_dense_walk_route {
+  int32_t kernel, v, acc, two_stage, rows_per_block, reserved;
+  int64_t strips, chunks, grid_y;
+} krs_dense_walk_route;
+int krs_dense_walk_last_route(krs_dense_walk_route* route);
+/* Diagnostic, host only, no GPU needed: how entry `entry` (KRS_DENSE_WALK_CROSS_FWD ...) WOULD walk an [m, n] operand
+ * of `dtype`.  ld: host array of the n_ld leading dimensions of the call's non-null matrices (krs_colsum: none, its lda
+ * takes no part); ptrs: host array of its n_ptrs matrix operands, read as VALUES only (alignment; NULL entries are
+ * skipped).  want_dbias / has_workspace: whether column sums are asked for (always, on krs_colsum) and a workspace is
+ * given; dx0_accumulate: krs_cross_epilogue_bwd with dx0 != NULL and the flag set.  No HIP call is made and the
+ * last-route record is untouched.  Fills *route (all zero when nothing would be launched) and returns what the entry
+ * returns for these sizes before its first launch: KRS_OK, KRS_ERR_INVALID (a negative size, a leading dimension below
+ * n, a bad dtype or entry) or KRS_ERR_UNSUPPORTED (m above 2^31 - 1). */
+int krs_dense_walk_plan_route(int entry, int64_t m, int64_t n, int dtype, const int64_t* ld, int n_ld,
+                              const void* const* ptrs, int n_ptrs, int want_dbias, int has_workspace,
+                              int dx0_accumulate, krs_dense_walk_route* route);
+
 /* ------------------------------------------------------------------------- *
  * K4  DotInteraction
  *

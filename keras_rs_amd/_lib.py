@@ -81,6 +81,16 @@ class DotRoute(C.Structure):
                  "lds_bytes")] + [("blocks", C.c_int64)]
 
 
+class DenseWalkRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("kernel", "v", "acc", "two_stage", "rows_per_block", "reserved")] + \
+               [(name, C.c_int64) for name in ("strips", "chunks", "grid_y")]
+
+
+# krs_dense_walk_route.kernel and the `entry` of krs_dense_walk_plan_route (include/krs.h)
+WALK_NONE, WALK_VEC, WALK_SCALAR = 0, 1, 2
+WALK_CROSS_FWD, WALK_CROSS_BWD, WALK_DENSE_ACT_BWD, WALK_COLSUM = 0, 1, 2, 3
+
+
 class RetrievalRoute(C.Structure):
     _fields_ = [(name, C.c_int32) for name in
                 ("kernel", "variant", "es", "vec", "S", "qtiles", "row_bytes", "lds_bytes", "select",
@@ -136,6 +146,8 @@ PROTOTYPES = {
     "krs_dense_act_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _P, _SZ, _P]),
     "krs_dense_adagrad": (_I, [_P, _P, _P, _P, _I, _F, _F, _P]),
     "krs_colsum": (_I, [_P, _I64, _I64, _I64, _I, _P, _P, _SZ, _P]),
+    "krs_dense_walk_last_route": (_I, [_P]),
+    "krs_dense_walk_plan_route": (_I, [_I, _I64, _I64, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     "krs_dot_interaction_fwd": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P]),
     "krs_dot_interaction_bwd": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
     "krs_dot_interaction_bwd_accumulate": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I64, _P, _P, _U64, _P]),

@@ -220,32 +220,19 @@ __global__ __launch_bounds__(1024) void colsum_finish_kernel(const float* partia
   }
 }
 
-bool vec_ok(const CrossParams& p, int v, std::initializer_list<const void*> ptrs) {
-  if (p.n % v || p.ld % v) return false;
-  for (const void* q : ptrs)
-    if (q && (reinterpret_cast<uintptr_t>(q) & 15)) return false;
-  return true;
+// where the calling thread's last dense walk ran (krs_dense_walk_last_route)
+thread_local krs_dense_walk_route g_route = {};
+
+// the call's plan (dense_walk_plan.h); a refused plan leaves its message
+int walk_plan(const char* what, const dwalk::Call& call, dwalk::Plan& pl) {
+  pl = dwalk::plan(call);
+  if (pl.status != KRS_OK) return fail(pl.status, "%s: %s", what, pl.why);
+  return KRS_OK;
 }
 
 }  // namespace
 
-// row chunks of the column-sum walks: enough to fill the chip, few enough to keep the second stage cheap
-ColChunks col_chunks(int64_t m, int64_t cols) {
-  const int64_t strips = ceil_div(cols, 64);
-  int64_t chunks = ceil_div(4096, strips);
-  if (chunks > m) chunks = m;
-  ColChunks c;
-  c.rows_per_block = (int)ceil_div(m, chunks);
-  c.chunks = ceil_div(m, c.rows_per_block);
-  c.groups4 = ceil_div(c.chunks, 4);
-  return c;
-}
-// groups of partial sums the launch will write for an [m, n] operand walked V columns per thread
-int64_t colsum_groups(int64_t m, int64_t n, int v) {
-  if (m <= 0 || n <= 0) return 0;
-  const ColChunks c = col_chunks(m, v > 1 ? n / v : n);
-  return v > 1 ? c.groups4 : c.chunks;
-}
+void set_dense_walk_route(const krs_dense_walk_route& route) { g_route = route; }
 int finish_colsum(float* partial, int64_t groups, int64_t n, float* out, hipStream_t st) {
   hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)ceil_div(n, 32)), dim3(1024), 0, st, partial, groups, n, out);
   KRS_CHECK_LAUNCH("colsum_finish_kernel");
@@ -258,15 +245,21 @@ using namespace krs;
 
 extern "C" int krs_cross_epilogue_fwd(const void* u, const void* x0, const void* x, void* y, int64_t m,
                                       int64_t n, int64_t ld, float diag_scale, int dtype, void* stream) {
+  g_route = krs_dense_walk_route{};
   KRS_REQUIRE(u && x0 && x && y, "cross_epilogue_fwd: null operand");
-  KRS_REQUIRE(m >= 0 && n >= 0 && ld >= n, "cross_epilogue_fwd: bad sizes");
-  if (m == 0 || n == 0) return KRS_OK;
+  const void* ptrs[] = {u, x0, x, y};
+  dwalk::Call call;
+  call.entry = KRS_DENSE_WALK_CROSS_FWD; call.m = m; call.n = n; call.dtype = dtype;
+  call.ld = &ld; call.n_ld = 1; call.ptrs = ptrs; call.n_ptrs = 4;
+  dwalk::Plan pl;
+  if (int rc = walk_plan("cross_epilogue_fwd", call, pl)) return rc;
+  const krs_dense_walk_route& rt = pl.route;
+  if (rt.kernel == KRS_DENSE_WALK_NONE) return KRS_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   CrossParams p{};
   p.u = u; p.x0 = x0; p.x = x; p.y = y; p.m = m; p.n = n; p.ld = ld; p.diag = diag_scale; p.dtype = dtype;
-  const int v = dtype == KRS_BF16 ? 8 : 4;
-  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(m * n / (vec_ok(p, v, {u, x0, x, y}) ? v : 1), 256), 16384);
-  if (vec_ok(p, v, {u, x0, x, y})) {
+  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(m * n / rt.v, 256), 16384);
+  if (rt.kernel == KRS_DENSE_WALK_VEC) {
     if (dtype == KRS_BF16)
       hipLaunchKernelGGL((cross_fwd_vec_kernel<uint16_t, 8>), dim3(blocks), dim3(256), 0, st, p);
     else
@@ -275,72 +268,98 @@ extern "C" int krs_cross_epilogue_fwd(const void* u, const void* x0, const void*
     hipLaunchKernelGGL(cross_fwd_scalar_kernel, dim3(blocks), dim3(256), 0, st, p);
   }
   KRS_CHECK_LAUNCH("cross_fwd_kernel");
+  g_route = rt;
   return KRS_OK;
 }
 
-extern "C" size_t krs_colsum_workspace_bytes(int64_t m, int64_t n) {
-  if (m <= 0 || n <= 0) return 0;
-  int64_t g = colsum_groups(m, n, 1);
-  if (n % 4 == 0) g = std::max(g, colsum_groups(m, n, 4));
-  if (n % 8 == 0) g = std::max(g, colsum_groups(m, n, 8));
-  return (size_t)g * (size_t)n * sizeof(float);
+extern "C" size_t krs_colsum_workspace_bytes(int64_t m, int64_t n) { return dwalk::workspace_bytes(m, n); }
+
+extern "C" int krs_dense_walk_last_route(krs_dense_walk_route* route) {
+  if (route) *route = g_route;
+  return g_route.kernel;
+}
+
+extern "C" int krs_dense_walk_plan_route(int entry, int64_t m, int64_t n, int dtype, const int64_t* ld, int n_ld,
+                                         const void* const* ptrs, int n_ptrs, int want_dbias, int has_workspace,
+                                         int dx0_accumulate, krs_dense_walk_route* route) {
+  dwalk::Call call;
+  call.entry = entry; call.m = m; call.n = n; call.dtype = dtype; call.ld = ld; call.n_ld = n_ld;
+  call.ptrs = ptrs; call.n_ptrs = n_ptrs; call.want_dbias = want_dbias != 0; call.has_workspace = has_workspace != 0;
+  call.dx0_accumulate = dx0_accumulate != 0;
+  dwalk::Plan pl;
+  const int rc = walk_plan("dense_walk_plan_route", call, pl);
+  if (route) *route = pl.route;
+  return rc;
 }
 
 extern "C" int krs_cross_epilogue_bwd(const void* g, const void* u, const void* x0, const void* x, void* du,
                                       void* dx0, int dx0_accumulate, void* dxd, float* dbias, int64_t m,
                                       int64_t n, int64_t ld, float diag_scale, int act, int dtype,
                                       void* workspace, size_t workspace_bytes, void* stream) {
+  g_route = krs_dense_walk_route{};
   KRS_REQUIRE(g && x0, "cross_epilogue_bwd: null g/x0");
   KRS_REQUIRE(act == KRS_ACT_NONE || u, "cross_epilogue_bwd: an activation needs the saved u");
   KRS_REQUIRE(!dx0 || (u && x), "cross_epilogue_bwd: dx0 needs u and x");
-  KRS_REQUIRE(m >= 0 && n >= 0 && ld >= n, "cross_epilogue_bwd: bad sizes");
+  const void* ptrs[] = {g, u, x0, x, du, dx0, dxd};
+  dwalk::Call call;
+  call.entry = KRS_DENSE_WALK_CROSS_BWD; call.m = m; call.n = n; call.dtype = dtype;
+  call.ld = &ld; call.n_ld = 1; call.ptrs = ptrs; call.n_ptrs = 7;
+  call.want_dbias = dbias != nullptr; call.has_workspace = workspace != nullptr;
+  call.dx0_accumulate = dx0 && dx0_accumulate;
+  dwalk::Plan pl;
+  if (int rc = walk_plan("cross_epilogue_bwd", call, pl)) return rc;
+  const krs_dense_walk_route& rt = pl.route;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool two_stage = dbias && workspace && m > 0 && n > 0;
-  if (two_stage) KRS_REQUIRE(workspace_bytes >= krs_colsum_workspace_bytes(m, n), "cross_epilogue_bwd: workspace too small");
+  const bool two_stage = rt.two_stage != 0;
+  if (two_stage) KRS_REQUIRE(workspace_bytes >= dwalk::workspace_bytes(m, n), "cross_epilogue_bwd: workspace too small");
   if (dbias && !two_stage) KRS_HIP(hipMemsetAsync(dbias, 0, (size_t)n * sizeof(float), st));
-  if (m == 0 || n == 0) return KRS_OK;
+  if (rt.kernel == KRS_DENSE_WALK_NONE) return KRS_OK;
   CrossParams p{};
   p.g = g; p.u = u; p.x0 = x0; p.x = x; p.du = du; p.dx0 = dx0; p.dxd = dxd; p.dbias = dbias;
   p.partial = two_stage ? reinterpret_cast<float*>(workspace) : nullptr;
   p.dx0_acc = dx0_accumulate; p.m = m; p.n = n; p.ld = ld; p.diag = diag_scale; p.act = act; p.dtype = dtype;
-  const int v = dtype == KRS_BF16 ? 8 : 4;
-  const bool vec = vec_ok(p, v, {g, u, x0, x, du, dx0, dxd});
-  const ColChunks cc = col_chunks(m, vec ? n / v : n);
-  const int64_t strips = ceil_div(vec ? n / v : n, 64);
-  const int rows_per_block = cc.rows_per_block;
-  if (vec) {
-    const dim3 grid4((unsigned)strips, (unsigned)cc.groups4);  // four chunks per workgroup
-    const bool acc = p.dx0 && p.dx0_acc;
+  const dim3 grid((unsigned)rt.strips, (unsigned)rt.grid_y);
+  const int rows_per_block = rt.rows_per_block;
+  if (rt.kernel == KRS_DENSE_WALK_VEC) {   // four chunks per workgroup
     if (dtype == KRS_BF16) {
-      if (acc) hipLaunchKernelGGL((cross_bwd_vec_kernel<uint16_t, 8, true>), grid4, dim3(256), 0, st, p, rows_per_block);
-      else hipLaunchKernelGGL((cross_bwd_vec_kernel<uint16_t, 8, false>), grid4, dim3(256), 0, st, p, rows_per_block);
+      if (rt.acc) hipLaunchKernelGGL((cross_bwd_vec_kernel<uint16_t, 8, true>), grid, dim3(256), 0, st, p, rows_per_block);
+      else hipLaunchKernelGGL((cross_bwd_vec_kernel<uint16_t, 8, false>), grid, dim3(256), 0, st, p, rows_per_block);
     } else {
-      if (acc) hipLaunchKernelGGL((cross_bwd_vec_kernel<float, 4, true>), grid4, dim3(256), 0, st, p, rows_per_block);
-      else hipLaunchKernelGGL((cross_bwd_vec_kernel<float, 4, false>), grid4, dim3(256), 0, st, p, rows_per_block);
+      if (rt.acc) hipLaunchKernelGGL((cross_bwd_vec_kernel<float, 4, true>), grid, dim3(256), 0, st, p, rows_per_block);
+      else hipLaunchKernelGGL((cross_bwd_vec_kernel<float, 4, false>), grid, dim3(256), 0, st, p, rows_per_block);
     }
   } else {
-    hipLaunchKernelGGL(cross_bwd_scalar_kernel, dim3((unsigned)strips, (unsigned)cc.chunks), dim3(64), 0, st, p, rows_per_block);
+    hipLaunchKernelGGL(cross_bwd_scalar_kernel, grid, dim3(64), 0, st, p, rows_per_block);
   }
   KRS_CHECK_LAUNCH("cross_bwd_kernel");
-  if (two_stage) return finish_colsum(p.partial, vec ? cc.groups4 : cc.chunks, n, dbias, st);
+  if (two_stage)
+    if (int rc = finish_colsum(p.partial, rt.grid_y, n, dbias, st)) return rc;
+  g_route = rt;
   return KRS_OK;
 }
 
 extern "C" int krs_colsum(const void* a, int64_t lda, int64_t m, int64_t n, int dtype, float* out,
                           void* workspace, size_t workspace_bytes, void* stream) {
+  g_route = krs_dense_walk_route{};
   KRS_REQUIRE(a && out, "colsum: null operand");
-  KRS_REQUIRE(m >= 0 && n >= 0, "colsum: bad sizes");
+  dwalk::Call call;
+  call.entry = KRS_DENSE_WALK_COLSUM; call.m = m; call.n = n; call.dtype = dtype;
+  call.want_dbias = true; call.has_workspace = workspace != nullptr;
+  dwalk::Plan pl;
+  if (int rc = walk_plan("colsum", call, pl)) return rc;
+  const krs_dense_walk_route& rt = pl.route;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (n == 0) return KRS_OK;
-  const bool two_stage = workspace && m > 0;
-  if (two_stage) KRS_REQUIRE(workspace_bytes >= krs_colsum_workspace_bytes(m, n), "colsum: workspace too small");
+  const bool two_stage = rt.two_stage != 0;
+  if (two_stage) KRS_REQUIRE(workspace_bytes >= dwalk::workspace_bytes(m, n), "colsum: workspace too small");
   if (!two_stage) KRS_HIP(hipMemsetAsync(out, 0, (size_t)n * sizeof(float), st));
-  if (m == 0) return KRS_OK;
-  const ColChunks cc = col_chunks(m, n);
+  if (rt.kernel == KRS_DENSE_WALK_NONE) return KRS_OK;
   float* partial = two_stage ? reinterpret_cast<float*>(workspace) : nullptr;
-  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)ceil_div(n, 64), (unsigned)cc.chunks), dim3(64), 0, st, a, lda, m, n, dtype,
-                     out, partial, cc.rows_per_block);
+  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)rt.strips, (unsigned)rt.grid_y), dim3(64), 0, st, a, lda, m, n, dtype,
+                     out, partial, rt.rows_per_block);
   KRS_CHECK_LAUNCH("colsum_kernel");
-  if (two_stage) return finish_colsum(partial, cc.chunks, n, out, st);
+  if (two_stage)
+    if (int rc = finish_colsum(partial, rt.grid_y, n, out, st)) return rc;
+  g_route = rt;
   return KRS_OK;
 }

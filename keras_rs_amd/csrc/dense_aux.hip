@@ -97,31 +97,37 @@ __global__ __launch_bounds__(64) void dense_act_bwd_scalar_kernel(const DenseBwd
 extern "C" int krs_dense_act_bwd(const void* g, int64_t ld_g, const void* y, int64_t ld_y, void* dz, int64_t ld_dz,
                                  float* dbias, int64_t m, int64_t n, int act, int dtype, void* workspace,
                                  size_t workspace_bytes, void* stream) {
+  set_dense_walk_route(krs_dense_walk_route{});
   KRS_REQUIRE(g && (dz || dbias), "dense_act_bwd: null operand");
   KRS_REQUIRE(act == KRS_ACT_NONE || y, "dense_act_bwd: an activation needs the saved output y");
-  KRS_REQUIRE(m >= 0 && n >= 0 && ld_g >= n && (!y || ld_y >= n) && (!dz || ld_dz >= n), "dense_act_bwd: bad sizes");
-  KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "dense_act_bwd: dtype must be f32 or bf16");
+  const void* ptrs[] = {g, y, dz};
+  int64_t lds[3] = {ld_g, 0, 0};
+  dwalk::Call call;
+  call.entry = KRS_DENSE_WALK_DENSE_ACT_BWD; call.m = m; call.n = n; call.dtype = dtype;
+  call.ld = lds; call.n_ld = 1; call.ptrs = ptrs; call.n_ptrs = 3;
+  if (y) lds[call.n_ld++] = ld_y;
+  if (dz) lds[call.n_ld++] = ld_dz;
+  call.want_dbias = dbias != nullptr; call.has_workspace = workspace != nullptr;
+  const dwalk::Plan pl = dwalk::plan(call);
+  if (pl.status != KRS_OK) return fail(pl.status, "dense_act_bwd: %s", pl.why);
+  const krs_dense_walk_route& rt = pl.route;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool two_stage = dbias && workspace && m > 0 && n > 0;
-  if (two_stage) KRS_REQUIRE(workspace_bytes >= krs_colsum_workspace_bytes(m, n), "dense_act_bwd: workspace too small");
+  const bool two_stage = rt.two_stage != 0;
+  if (two_stage) KRS_REQUIRE(workspace_bytes >= dwalk::workspace_bytes(m, n), "dense_act_bwd: workspace too small");
   if (dbias && !two_stage) KRS_HIP(hipMemsetAsync(dbias, 0, (size_t)n * sizeof(float), st));
-  if (m == 0 || n == 0) return KRS_OK;
+  if (rt.kernel == KRS_DENSE_WALK_NONE) return KRS_OK;
   DenseBwdParams p{g, y, dz, dbias, two_stage ? reinterpret_cast<float*>(workspace) : nullptr, m, n, ld_g, ld_y, ld_dz, act, dtype};
-  const int v = dtype == KRS_BF16 ? 8 : 4;
-  bool vec = n % v == 0 && ld_g % v == 0 && (!y || ld_y % v == 0) && (!dz || ld_dz % v == 0);
-  for (const void* q : {g, y, (const void*)dz}) vec = vec && reinterpret_cast<uintptr_t>(q) % 16 == 0;
-  const ColChunks cc = col_chunks(m, vec ? n / v : n);
-  const int64_t strips = ceil_div(vec ? n / v : n, 64);
-  if (vec) {
-    const dim3 grid4((unsigned)strips, (unsigned)cc.groups4);
-    if (dtype == KRS_BF16) hipLaunchKernelGGL((dense_act_bwd_vec_kernel<uint16_t, 8>), grid4, dim3(256), 0, st, p, cc.rows_per_block);
-    else hipLaunchKernelGGL((dense_act_bwd_vec_kernel<float, 4>), grid4, dim3(256), 0, st, p, cc.rows_per_block);
+  const dim3 grid((unsigned)rt.strips, (unsigned)rt.grid_y);
+  if (rt.kernel == KRS_DENSE_WALK_VEC) {
+    if (dtype == KRS_BF16) hipLaunchKernelGGL((dense_act_bwd_vec_kernel<uint16_t, 8>), grid, dim3(256), 0, st, p, rt.rows_per_block);
+    else hipLaunchKernelGGL((dense_act_bwd_vec_kernel<float, 4>), grid, dim3(256), 0, st, p, rt.rows_per_block);
   } else {
-    hipLaunchKernelGGL(dense_act_bwd_scalar_kernel, dim3((unsigned)strips, (unsigned)cc.chunks), dim3(64), 0, st, p,
-                       cc.rows_per_block);
+    hipLaunchKernelGGL(dense_act_bwd_scalar_kernel, grid, dim3(64), 0, st, p, rt.rows_per_block);
   }
   KRS_CHECK_LAUNCH("dense_act_bwd_kernel");
-  if (two_stage) return finish_colsum(p.partial, vec ? cc.groups4 : cc.chunks, n, dbias, st);
+  if (two_stage)
+    if (int rc = finish_colsum(p.partial, rt.grid_y, n, dbias, st)) return rc;
+  set_dense_walk_route(rt);
   return KRS_OK;
 }
 

@@ -1,22 +1,18 @@
 // Pieces shared by the dense translation units (gemm.hip, cross_epilogue.hip, dense_aux.hip; one file until round 5):
 // activation helpers, the row-vector access forms of the elementwise passes, and the host side of the two-stage
-// deterministic column sums (defined once, in cross_epilogue.hip).
+// deterministic column sums and of the route record (defined once, in cross_epilogue.hip; the walk itself is planned in
+// dense_walk_plan.h).
 #ifndef KRS_DENSE_COMMON_H_
 #define KRS_DENSE_COMMON_H_
 
+#include "dense_walk_plan.h"
 #include "krs_common.h"
 
 namespace krs {
 
-// row chunks of the column-sum walks: enough to fill the chip, few enough to keep the second stage cheap
-struct ColChunks {
-  int rows_per_block;
-  int64_t chunks;      // = grid.y of the scalar kernels
-  int64_t groups4;     // = grid.y of the vector kernels (four chunks, one per wave, per workgroup)
-};
-ColChunks col_chunks(int64_t m, int64_t cols);
-// groups of partial sums the launch will write for an [m, n] operand walked V columns per thread
-int64_t colsum_groups(int64_t m, int64_t n, int v);
+// the calling thread's krs_dense_walk_last_route record (cross_epilogue.hip): an entry clears it when it starts and
+// writes its plan's route when it has queued its kernels, so a refused call and an empty one leave "none"
+void set_dense_walk_route(const krs_dense_walk_route& route);
 // out[c] = sum over the row groups of partial[g][c] in a fixed order (colsum_finish_kernel)
 int finish_colsum(float* partial, int64_t groups, int64_t n, float* out, hipStream_t st);
 

@@ -98,6 +98,17 @@ class RetrievalRoute(C.Structure):
                                         ("slice", "blocks", "select_len", "select_p", "chunks", "chunk_rows")]
 
 
+class RegressionRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("kernel", "v", "blocks", "launches")]
+
+
+# krs_regression_kind, krs_regression_reduction and krs_regression_route.kernel (include/krs.h)
+REG_MSE, REG_MAE, REG_HUBER = 0, 1, 2
+REG_NONE, REG_SUM, REG_SUM_OVER_BATCH_SIZE, REG_MEAN_WITH_SAMPLE_WEIGHT = 0, 1, 2, 3
+REG_ROUTE_NONE, REG_VEC, REG_ELEM = 0, 1, 2
+REG_MAX_BLOCKS, REG_THREADS = 256, 1024
+
+
 # Prototype of every entry point include/krs.h declares, in its order: name -> (restype, argtypes).  Any pointer is a
 # void* (pass L.ptr(t), an int or None; ctypes arrays and C.byref(struct) where the C side takes an array or a struct).
 # tests/test_capi_symbols.py parses the header and checks this table against it row by row.
@@ -223,6 +234,11 @@ PROTOTYPES = {
     "krs_retrieval_ivf_ah_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I, _I, _I, _I, _I, _I]),
     "krs_retrieval_ivf_ah": (_I, [_P, _I64, _P, _I64, _P, _I, _P, _I64, _P, _P, _P, _I64, _P, _I, _I64, _I64, _I64, _I64,
                                   _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "krs_regression_workspace_bytes": (_SZ, [_I64, _I64]),
+    "krs_regression_fwd_bwd": (_I, [_I, _F, _I, _P, _I64, _I, _P, _I64, _P, _I64, _I64, _P, _F, _P, _P, _I64, _P, _P, _SZ,
+                                    _P]),
+    "krs_regression_last_route": (_I, [_P]),
+    "krs_regression_plan_route": (_I, [_I, _P, _I64, _I, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -7,10 +7,14 @@ from keras_rs_amd.layers.distributed_embedding_config import FeatureConfig, Tabl
 from keras_rs_amd.layers.dot_interaction import DotInteraction
 from keras_rs_amd.layers.embed_reduce import EmbedReduce, Embedding, Ragged
 from keras_rs_amd.layers.feature_cross import FeatureCross
-from keras_rs_amd.layers.losses import (BinaryCrossentropy, CategoricalCrossentropy, SparseCategoricalCrossentropy,
-                                        binary_crossentropy)
-from keras_rs_amd.layers.metrics import (AUC, BinaryAccuracy, BinaryMetricGroup, SparseTopKCategoricalAccuracy,
-                                         auc_from_confusion)
+from keras_rs_amd.layers.losses import (BinaryCrossentropy, CategoricalCrossentropy, Huber, MeanAbsoluteError,
+                                        MeanSquaredError, SparseCategoricalCrossentropy, binary_crossentropy)
+# (keras keeps the two MeanSquaredError / MeanAbsoluteError in keras.losses and keras.metrics; here the bare names are the
+#  losses and the metrics carry a suffix -- keras_rs_amd.layers.metrics has them under keras' names)
+from keras_rs_amd.layers.metrics import (AUC, BinaryAccuracy, BinaryMetricGroup, RegressionMetricGroup,
+                                         RootMeanSquaredError, SparseTopKCategoricalAccuracy, auc_from_confusion)
+from keras_rs_amd.layers.metrics import MeanAbsoluteError as MeanAbsoluteErrorMetric
+from keras_rs_amd.layers.metrics import MeanSquaredError as MeanSquaredErrorMetric
 from keras_rs_amd.layers.recurrent import GRU
 from keras_rs_amd.layers.retrieval import (AsymmetricHashingRetrieval, BruteForceRetrieval, FactorizedTopK,
                                            HardNegativeMining, InBatchSoftmaxLoss, PartitionedRetrieval,
@@ -18,5 +22,5 @@ from keras_rs_amd.layers.retrieval import (AsymmetricHashingRetrieval, BruteForc
 from keras_rs_amd.layers.sequence import LayerNormalization, MultiHeadAttention, TransformerDecoder
 
 __all__ = ["AUC", "Adagrad", "Adam", "AsymmetricHashingRetrieval", "BinaryAccuracy", "BinaryCrossentropy", "BinaryMetricGroup", "auc_from_confusion", "binary_crossentropy", "BruteForceRetrieval", "CategoricalCrossentropy", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
-           "FactorizedTopK", "FeatureCross", "Ftrl", "GRU", "HardNegativeMining", "InBatchSoftmaxLoss", "LayerNormalization", "MultiHeadAttention", "PartitionedRetrieval", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SamplingProbabilityCorrection",
+           "FactorizedTopK", "FeatureCross", "Ftrl", "GRU", "HardNegativeMining", "Huber", "MeanAbsoluteError", "MeanAbsoluteErrorMetric", "MeanSquaredError", "MeanSquaredErrorMetric", "RegressionMetricGroup", "RootMeanSquaredError", "InBatchSoftmaxLoss", "LayerNormalization", "MultiHeadAttention", "PartitionedRetrieval", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SamplingProbabilityCorrection",
            "SparseCategoricalCrossentropy", "SparseTopKCategoricalAccuracy", "TableConfig", "TransformerDecoder", "concat_features"]

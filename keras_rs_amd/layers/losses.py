@@ -1,12 +1,16 @@
 """The loss of the DLRM step on MI355X: `keras.losses.BinaryCrossentropy()` as the reference's ml_perf example compiles
 it (examples/ml_perf/main.py:201-210: probabilities in -- the top MLP ends in a sigmoid, model.py:105-163 --, mean over
-the batch), forward and backward in ONE pass over the predictions (krs_bce_fwd_bwd, csrc/loss.hip)."""
+the batch), forward and backward in ONE pass over the predictions (krs_bce_fwd_bwd, csrc/loss.hip); the softmax
+crossentropies of the retrieval examples (K11); and the regression losses of the rating examples -- MeanSquaredError,
+MeanAbsoluteError, Huber -- with every Keras reduction, sample weights and the regression metrics' update from one
+pass over the predictions (K24, krs_regression_fwd_bwd, csrc/regression.hip)."""
 
 from __future__ import annotations
 
 import torch
 
 from keras_rs_amd import losses as _reductions
+from keras_rs_amd import regression_ops as _regression
 from keras_rs_amd.autograd import BinaryCrossentropyFn
 from keras_rs_amd.retrieval_ops import SoftmaxCrossentropyFn
 
@@ -128,3 +132,89 @@ class SparseCategoricalCrossentropy(_SoftmaxCrossentropy):
 
     def get_config(self) -> dict:
         return {"name": self.name, "reduction": self.reduction, "from_logits": True, "ignore_class": None}
+
+
+# ---- K24: the regression losses --------------------------------------------------------------------------------------
+class _RegressionLoss:
+    """What MeanSquaredError, MeanAbsoluteError and Huber share: loss(y_true, y_pred, sample_weight=None), one
+    krs_regression_fwd_bwd call (csrc/regression.hip) that reads y_pred once and leaves the reduced loss, the gradient
+    and -- with `metrics` -- the batch sums the regression metrics add to their states.
+
+    Shapes: y_pred [..., C] is fp32 or bf16 (computed on in fp32), the per-row value is the mean over the last axis
+    and the rows are weighted by sample_weight (a scalar, the leading shape, or one weight per batch row).  The ranks
+    of y_true and y_pred may differ by one when the longer shape ends in 1 (y_true [B] with y_pred [B, 1]); after
+    that the shapes must be equal, else ValueError.  This DIVERGES from the raw Keras ops, which broadcast [B]
+    against [B, 1] into [B, B]: that is never what a rating model means, and it is refused here.  Rank-1 inputs are
+    one row, whose sample_weight must be a scalar.  y_true gets no gradient.
+
+    metrics: a RegressionMetricGroup or one regression metric (here, or per call): its update_state runs from the
+    same kernel call as the loss and the gradient."""
+    _kind = ""
+    _delta = 1.0
+
+    def __init__(self, reduction: str | None = "sum_over_batch_size", name: str | None = None, dtype=None,
+                 metrics=None):
+        if reduction not in _reductions.REDUCTIONS:
+            raise ValueError(f"Invalid value for argument `reduction`. Expected one of {_reductions.REDUCTIONS}. "
+                             f"Received: reduction={reduction}")
+        if dtype not in (None, "float32", torch.float32):
+            raise ValueError(f"{type(self).__name__}: the loss is computed in float32; dtype={dtype} is not supported")
+        self.reduction = reduction
+        self.name = name or _reductions._snake(type(self).__name__)
+        self.metrics = _as_metric_group(metrics)
+
+    def __call__(self, y_true, y_pred, sample_weight=None, metrics=None) -> torch.Tensor:
+        group = self.metrics if metrics is None else _as_metric_group(metrics)
+        target, pred, w, shape = _regression.standardize(y_true, y_pred, sample_weight, type(self).__name__)
+        sums = None if group is None else group._batch_sums(pred.device)
+        reduction = "none" if self.reduction is None else self.reduction
+        out = _regression.RegressionLossFn.apply(pred, target, w, self._kind, self._delta, reduction, sums)
+        if group is not None:
+            group._add(sums)
+        return out.reshape(shape) if reduction == "none" else out
+
+    def get_config(self) -> dict:
+        return {"name": self.name, "reduction": self.reduction, "dtype": "float32"}
+
+    @classmethod
+    def from_config(cls, config: dict):
+        return cls(**config)
+
+
+def _as_metric_group(metrics):
+    if metrics is None:
+        return None
+    from keras_rs_amd.layers.metrics import RegressionMetricGroup, _RegressionMetric
+    if isinstance(metrics, RegressionMetricGroup):
+        return metrics
+    if isinstance(metrics, _RegressionMetric):
+        return RegressionMetricGroup([metrics])
+    raise ValueError("`metrics` should be a RegressionMetricGroup or one of RootMeanSquaredError, MeanSquaredError "
+                     f"and MeanAbsoluteError from keras_rs_amd.layers. Received: {metrics!r}")
+
+
+class MeanSquaredError(_RegressionLoss):
+    """Callable like keras.losses.MeanSquaredError: per row mean((y_pred - y_true)^2) over the last axis."""
+    _kind = "mse"
+
+
+class MeanAbsoluteError(_RegressionLoss):
+    """Callable like keras.losses.MeanAbsoluteError: per row mean(|y_pred - y_true|) over the last axis.  The gradient
+    at y_pred == y_true is 0 (sign(0) = 0, as autodiff of abs gives in every Keras backend)."""
+    _kind = "mae"
+
+
+class Huber(_RegressionLoss):
+    """Callable like keras.losses.Huber(delta): with e = y_pred - y_true, per element 0.5 e^2 where |e| <= delta and
+    delta |e| - 0.5 delta^2 beyond, then the mean over the last axis.  The two gradients agree at |e| == delta."""
+    _kind = "huber"
+
+    def __init__(self, delta: float = 1.0, reduction: str | None = "sum_over_batch_size", name: str | None = None,
+                 dtype=None, metrics=None):
+        if not float(delta) > 0.0:
+            raise ValueError(f"`delta` should be a positive float. Received: delta={delta}")
+        super().__init__(reduction=reduction, name=name or "huber_loss", dtype=dtype, metrics=metrics)
+        self._delta = self.delta = float(delta)
+
+    def get_config(self) -> dict:
+        return {**super().get_config(), "delta": self.delta}

@@ -342,3 +342,123 @@ class BinaryMetricGroup:
     def __call__(self, y_true, y_pred, sample_weight=None) -> dict:
         self.update_state(y_true, y_pred, sample_weight)
         return self.result()
+
+
+# ---- K24: the regression metrics -------------------------------------------------------------------------------------
+class _RegressionMetric:
+    """keras.metrics.Mean's {total, count} as a device fp32 tensor, fed by the batch sums of krs_regression_fwd_bwd
+    (csrc/regression.hip): {sum_b w_b mean_c e^2, sum_b w_b mean_c |e|, sum_b w_b} with sample weights, the plain
+    element sums and the element count without.  update_state takes the inputs of the regression losses (the same
+    shape rule), waits for nothing and can be captured in a HIP graph."""
+    _total = 0            # which batch sum is the total: 0 squared, 1 absolute
+    _default_name = ""
+    _state = None
+
+    def __init__(self, name: str | None = None, dtype: Any = None):
+        _check_dtype(self, dtype)
+        self.name = name or self._default_name
+
+    def _device_state(self, device) -> torch.Tensor:
+        if self._state is None or self._state.device != device:
+            self._state = torch.zeros((2,), dtype=torch.float32, device=device)
+        return self._state
+
+    def update_state(self, y_true, y_pred, sample_weight=None) -> None:
+        RegressionMetricGroup([self]).update_state(y_true, y_pred, sample_weight)
+
+    def _value(self) -> torch.Tensor:
+        if self._state is None:
+            return torch.zeros((), dtype=torch.float32)
+        return _divide_no_nan(self._state[0], self._state[1])
+
+    def result(self) -> torch.Tensor:
+        return self._value()
+
+    @property
+    def variables(self) -> list:
+        state = self._device_state(torch.device("cpu") if self._state is None else self._state.device)
+        return [state[0], state[1]]
+
+    def reset_state(self) -> None:
+        if self._state is not None:
+            self._state.zero_()
+
+    def __call__(self, y_true, y_pred, sample_weight=None) -> torch.Tensor:
+        self.update_state(y_true, y_pred, sample_weight)
+        return self.result()
+
+    def get_config(self) -> dict:
+        return {"name": self.name, "dtype": "float32"}
+
+    @classmethod
+    def from_config(cls, config: dict):
+        return cls(**config)
+
+
+class MeanSquaredError(_RegressionMetric):
+    """keras.metrics.MeanSquaredError: the weighted mean of mean((y_pred - y_true)^2, axis=-1)."""
+    _total, _default_name = 0, "mean_squared_error"
+
+
+class RootMeanSquaredError(_RegressionMetric):
+    """keras.metrics.RootMeanSquaredError: sqrt(total / count) of MeanSquaredError's state."""
+    _total, _default_name = 0, "root_mean_squared_error"
+
+    def result(self) -> torch.Tensor:
+        return torch.sqrt(self._value())
+
+
+class MeanAbsoluteError(_RegressionMetric):
+    """keras.metrics.MeanAbsoluteError: the weighted mean of mean(|y_pred - y_true|, axis=-1)."""
+    _total, _default_name = 1, "mean_absolute_error"
+
+
+class RegressionMetricGroup:
+    """Any number of regression metrics updated from ONE krs_regression_fwd_bwd call: the call writes the three batch
+    sums once and every member adds its two to its own state, so a member's state after a group update is
+    bit-identical to its state after updating it alone.  The regression losses take a group (or one metric) as
+    `metrics=` and then update it from the call that computes the loss and the gradient.  result() is {name: tensor},
+    so the members' names must differ."""
+
+    def __init__(self, metrics):
+        metrics = list(metrics)
+        for m in metrics:
+            if not isinstance(m, _RegressionMetric):
+                raise ValueError("RegressionMetricGroup takes RootMeanSquaredError, MeanSquaredError and "
+                                 f"MeanAbsoluteError objects. Received: {m!r}")
+        if not metrics:
+            raise ValueError("RegressionMetricGroup needs at least one metric.")
+        if len({m.name for m in metrics}) != len(metrics):
+            raise ValueError(f"The metrics of a RegressionMetricGroup need distinct names. Received: "
+                             f"{[m.name for m in metrics]}.")
+        self.metrics = metrics
+        self._sums = None
+
+    def _batch_sums(self, device) -> torch.Tensor:
+        """the [3] tensor the kernel writes (kept: a captured update replays into the same memory)"""
+        if self._sums is None or self._sums.device != device:
+            self._sums = torch.zeros((3,), dtype=torch.float32, device=device)
+        return self._sums
+
+    def _add(self, sums: torch.Tensor) -> None:
+        for m in self.metrics:
+            m._device_state(sums.device).add_(sums[m._total::2 - m._total])   # {total, count} = sums[0 or 1], sums[2]
+
+    def update_state(self, y_true, y_pred, sample_weight=None) -> None:
+        from keras_rs_amd import regression_ops
+        target, pred, w, _ = regression_ops.standardize(y_true, y_pred, sample_weight, "update_state")
+        L.require_device(pred, "update_state")
+        sums = self._batch_sums(pred.device)
+        regression_ops.regression(pred.detach(), target, w, "mse", want_loss=False, want_grad=False, sums=sums)
+        self._add(sums)
+
+    def result(self) -> dict:
+        return {m.name: m.result() for m in self.metrics}
+
+    def reset_state(self) -> None:
+        for m in self.metrics:
+            m.reset_state()
+
+    def __call__(self, y_true, y_pred, sample_weight=None) -> dict:
+        self.update_state(y_true, y_pred, sample_weight)
+        return self.result()

@@ -7,7 +7,9 @@ softmax (scores = q c^T against eye(batch) through CategoricalCrossentropy(from_
 Every example is a context of up to 10 items, right-padded with item 0, and the item that follows it.  As in the
 reference the GRU reads the padding like any other item (its Embedding passes no mask).  Sequences are synthetic (sas_rec.synthetic_sequences' walk); nothing is downloaded.
 
-    python examples/sequential_retrieval.py --steps 30 --dtype bf16 [--fused]
+    python examples/sequential_retrieval.py --steps 30 --dtype bf16 [--fused] [--cell lstm]
+
+--cell lstm swaps the GRU for layers.LSTM (K25); the default run is the GRU's.
 """
 
 import argparse
@@ -39,25 +41,26 @@ def synthetic_examples(count: int, vocabulary_size: int, length: int = MAX_CONTE
 
 class SequentialRetrievalModel(base.Layer):
     def __init__(self, movies_count: int, embedding_dimension: int = 32, k: int = 10, fused: bool = False,
-                 **kwargs):
+                 cell: str = "gru", **kwargs):
         super().__init__(**kwargs)
         sub = dict(dtype=self.dtype_policy, device=self._device)
         self.movies_count, self.embedding_dimension = movies_count, embedding_dimension
         self.fused = bool(fused)
         self.query_embedding = kl.Embedding(movies_count + 1, embedding_dimension, name="query_embedding", **sub)
-        self.gru = kl.GRU(embedding_dimension, name="gru", **sub)
+        self.cell = cell                                # "gru" (K20) or "lstm" (K25); the layer is self.gru / self.lstm
+        setattr(self, cell, {"gru": kl.GRU, "lstm": kl.LSTM}[cell](embedding_dimension, name=cell, **sub))
         self.candidate_model = kl.Embedding(movies_count + 1, embedding_dimension, name="candidate_embedding", **sub)
         self.retrieval = kl.BruteForceRetrieval(k=k, return_scores=False, device=self._device)
         self.loss_fn = kl.InBatchSoftmaxLoss() if fused else kl.CategoricalCrossentropy(from_logits=True)
         self.built = True
 
     def train_weights(self):
-        """The query table, the GRU's kernel, recurrent_kernel and bias, the candidate table."""
-        return self.query_embedding.weights + self.gru.weights + self.candidate_model.weights
+        """The query table, the recurrent layer's kernel, recurrent_kernel and bias, the candidate table."""
+        return self.query_embedding.weights + getattr(self, self.cell).weights + self.candidate_model.weights
 
     def query_model(self, context):
         x = self.query_embedding(context).to(self.compute_dtype)
-        return self.gru(x)
+        return getattr(self, self.cell)(x)
 
     def call(self, inputs, training: bool = False):
         query_embeddings = self.query_model(inputs)
@@ -81,11 +84,11 @@ class SequentialRetrievalModel(base.Layer):
 
 def main(steps: int = 30, batch: int = 4096, vocabulary_size: int = 3000, hidden_dim: int = 32,
          length: int = MAX_CONTEXT_LENGTH, dtype: str = "bf16", lr: float = 0.005, fused: bool = False,
-         seed: int = 0, quiet: bool = False):
+         seed: int = 0, quiet: bool = False, cell: str = "gru"):
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(seed)
     policy = {"bf16": "mixed_bfloat16", "fp32": "float32"}[dtype]
-    model = SequentialRetrievalModel(vocabulary_size, hidden_dim, fused=fused, dtype=policy, device=dev)
+    model = SequentialRetrievalModel(vocabulary_size, hidden_dim, fused=fused, cell=cell, dtype=policy, device=dev)
     context, label = (torch.from_numpy(a).to(dev) for a in synthetic_examples(batch, vocabulary_size, length, seed))
     model.compute_loss(label, model(context, training=True))                                      # (builds every weight)
     opt = torch.optim.AdamW(model.weights, lr=lr)
@@ -115,5 +118,7 @@ if __name__ == "__main__":
     ap.add_argument("--hidden", type=int, default=32)
     ap.add_argument("--vocabulary", type=int, default=3000)
     ap.add_argument("--fused", action="store_true")
+    ap.add_argument("--cell", choices=("gru", "lstm"), default="gru", help="the recurrent layer of the query tower")
     a = ap.parse_args()
-    main(steps=a.steps, batch=a.batch, vocabulary_size=a.vocabulary, hidden_dim=a.hidden, dtype=a.dtype, fused=a.fused)
+    main(steps=a.steps, batch=a.batch, vocabulary_size=a.vocabulary, hidden_dim=a.hidden, dtype=a.dtype, fused=a.fused,
+         cell=a.cell)

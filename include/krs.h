@@ -1688,6 +1688,68 @@ int krs_regression_plan_route(int reduction, const void* pred, int64_t ld_pred, 
                               int64_t ld_target, const float* sample_weight, int64_t b, int64_t c, const float* g,
                               const float* loss, const void* dpred, int64_t ld_dpred, krs_regression_route* route);
 
+/* ------------------------------------------------------------------------- *
+ * K25  The recurrence of an LSTM layer (keras.layers.LSTM: tanh, sigmoid), all l steps in one launch per sweep
+ *
+ * Weights in Keras' shapes and gate order i, f, c, o (the candidate is written g below): kernel [d, 4u],
+ * recurrent_kernel [u, 4u], bias [4u].  The input projection runs OUTSIDE these entries, as a Dense product, and
+ * carries the only bias: xz = x . kernel + bias, one row of 4u per token, token (bi, t) at row bi * l + t, rows ldxz
+ * elements apart (>= 4u: a view of a wider buffer qualifies).  At a valid step, with h and c the carried states, in fp32:
+ *     a  = h . recurrent_kernel                          (slices a_i, a_f, a_g, a_o; fp32 accumulate)
+ *     i  = sigmoid(xz_i + a_i)             f = sigmoid(xz_f + a_f)
+ *     g  = tanh   (xz_g + a_g)             o = sigmoid(xz_o + a_o)
+ *     c' = f * c + i * g                   h' = o * tanh(c')
+ * At a masked step (valid[bi, t] == 0; valid: uint8 [b, l] or NULL = every step valid) BOTH states are carried
+ * unchanged and the step's sequence output is the previous step's output: zeros before the first valid step, even when
+ * h0 is not zero (the rule of Keras' backend rnn, K20's rule); from the first valid step on the output equals h.
+ * Backward, per valid step, with dh and dc carried in fp32:
+ *     dh_t = dh carried + the gradient arriving at hs_t         dc_t = dc carried + dh_t * o * (1 - tanh(c')^2)
+ *     da_o = dh_t * tanh(c') * o * (1 - o)                      da_i = dc_t * g * i * (1 - i)
+ *     da_f = dc_t * c * f * (1 - f)                             da_g = dc_t * i * (1 - g^2)
+ *     dc carried to t-1 = dc_t * f                              dh carried to t-1 = da . recurrent_kernel^T
+ * dxz IS da = (da_i, da_f, da_g, da_o): there is no reset-after asymmetry, so one output serves the input
+ * projection's backward and the recurrent weight gradient.  A masked step passes dh and dc through and contributes
+ * zeros to dxz; the gradient of an output before the first valid step goes nowhere.
+ *
+ * dtype (KRS_F32 / KRS_BF16) is the type of xz, recurrent_kernel, h0, c0, hs, h_last, c_last and every gradient.  hs
+ * [b, l, u] is the sequence output, h_last and c_last [b, u] the final STATES (an all-padding sequence: h0, c0); any
+ * may be NULL, not all three.  h0, c0 NULL = zeros.  reserve (krs_lstm_reserve_bytes; its layout is private to the
+ * kernels) receives the gates and the carried c of every step for the backward and needs hs; with reserve NULL
+ * (inference) only the outputs are written, and they are bit for bit those of the training forward.  It holds i and g
+ * in dtype and f, o, c in fp32 -- 16u bytes a token in bf16, 20u in fp32: a gate near 1 stored as bf16 loses the
+ * 1 - gate that da_f and da_o multiply by, and c is carried over many steps.
+ * krs_lstm_bwd reads recurrent_kernel, valid, h0, c0, hs and the reserve back with dhs [b, l, u], dh_last and dc_last
+ * [b, u] (each may be NULL = zeros) and writes dxz [b, l, 4u], hprev [b, l, u] (NULL to skip: the h_{t-1} each step
+ * used, the left operand of d recurrent_kernel = hprev^T . dxz, one krs_gemm outside), dh0 and dc0 [b, u] (NULL to skip).
+ *
+ * Routes (csrc/lstm_plan.h decides, a pure host function):
+ *   KRS_LSTM_FAST     bf16, u <= 128 (upad 32 / 64 / 128).  A workgroup owns 32 batch rows and walks every step alone;
+ *                     a wave owns 32 units of all four gates, so a lane holds i, f, g, o, c and h of its (row, unit)
+ *                     pairs; h . U and da . U^T run on v_mfma_f32_32x32x16_bf16.  Forward: the recurrent kernel is
+ *                     staged once into LDS as bf16.  Backward: every lane keeps its share of the recurrent kernel in
+ *                     registers (upad VGPRs) and LDS holds only the double-buffered da.  Rounded to bf16 (nearest even):
+ *                     recurrent_kernel and xz as given, the A-operand copy of h, da, i and g in the reserve, the
+ *                     outputs.  The carried h, c, dh, dc and the accumulators stay fp32.  The backward reads h_{t-1}
+ *                     from hs (bf16) and c_{t-1} from the reserve (fp32).
+ *   KRS_LSTM_GENERIC  fp32 at any u <= 1024, bf16 at 128 < u <= 1024: fp32 FMA, the carried states in LDS (never
+ *                     rounded), the recurrent kernel read through L2 each step; 4 batch rows per workgroup.
+ * One owner per output element and no atomics on either route: bit-identical from call to call.  No workgroup waits
+ * on another: no grid barrier, no cooperative launch, no flags.  No host synchronisation: a step captures into a graph.
+ * b == 0 or l == 0 is a successful no-op.  b < 0, l < 0, u < 1, a bad dtype, a null operand, ldxz < 4u and a call that
+ * wants no output are KRS_ERR_INVALID; u > 1024 is KRS_ERR_UNSUPPORTED with a message naming the limit.
+ * krs_lstm_last_route: the route of the process's last krs_lstm_fwd / _bwd call, whichever thread made it: kernel, and
+ * upad on the fast route, else 0; both zero after a refused call or a no-op.  Returns kernel.
+ * ------------------------------------------------------------------------- */
+enum { KRS_LSTM_NONE = 0, KRS_LSTM_FAST = 1, KRS_LSTM_GENERIC = 2 };
+size_t krs_lstm_reserve_bytes(int64_t b, int64_t l, int64_t u, int dtype);
+int krs_lstm_fwd(const void* xz, int64_t ldxz, const void* recurrent_kernel, const uint8_t* valid, const void* h0,
+                 const void* c0, int dtype, int64_t b, int64_t l, int64_t u, void* hs, void* h_last, void* c_last,
+                 void* reserve, void* stream);
+int krs_lstm_bwd(const void* recurrent_kernel, const uint8_t* valid, const void* h0, const void* c0, const void* hs,
+                 const void* reserve, const void* dhs, const void* dh_last, const void* dc_last, int dtype, int64_t b,
+                 int64_t l, int64_t u, void* dxz, void* hprev, void* dh0, void* dc0, void* stream);
+int krs_lstm_last_route(int* kernel, int* upad);
+
 #ifdef __cplusplus
 }
 #endif

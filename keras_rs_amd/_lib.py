@@ -239,6 +239,10 @@ PROTOTYPES = {
                                     _P]),
     "krs_regression_last_route": (_I, [_P]),
     "krs_regression_plan_route": (_I, [_I, _P, _I64, _I, _P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "krs_lstm_reserve_bytes": (_SZ, [_I64, _I64, _I64, _I]),
+    "krs_lstm_fwd": (_I, [_P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    "krs_lstm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    "krs_lstm_last_route": (_I, [_P, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

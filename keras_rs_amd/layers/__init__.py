@@ -15,12 +15,12 @@ from keras_rs_amd.layers.metrics import (AUC, BinaryAccuracy, BinaryMetricGroup,
                                          RootMeanSquaredError, SparseTopKCategoricalAccuracy, auc_from_confusion)
 from keras_rs_amd.layers.metrics import MeanAbsoluteError as MeanAbsoluteErrorMetric
 from keras_rs_amd.layers.metrics import MeanSquaredError as MeanSquaredErrorMetric
-from keras_rs_amd.layers.recurrent import GRU
+from keras_rs_amd.layers.recurrent import GRU, LSTM
 from keras_rs_amd.layers.retrieval import (AsymmetricHashingRetrieval, BruteForceRetrieval, FactorizedTopK,
                                            HardNegativeMining, InBatchSoftmaxLoss, PartitionedRetrieval,
                                            RemoveAccidentalHits, Retrieval, SamplingProbabilityCorrection)
 from keras_rs_amd.layers.sequence import LayerNormalization, MultiHeadAttention, TransformerDecoder
 
 __all__ = ["AUC", "Adagrad", "Adam", "AsymmetricHashingRetrieval", "BinaryAccuracy", "BinaryCrossentropy", "BinaryMetricGroup", "auc_from_confusion", "binary_crossentropy", "BruteForceRetrieval", "CategoricalCrossentropy", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
-           "FactorizedTopK", "FeatureCross", "Ftrl", "GRU", "HardNegativeMining", "Huber", "MeanAbsoluteError", "MeanAbsoluteErrorMetric", "MeanSquaredError", "MeanSquaredErrorMetric", "RegressionMetricGroup", "RootMeanSquaredError", "InBatchSoftmaxLoss", "LayerNormalization", "MultiHeadAttention", "PartitionedRetrieval", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SamplingProbabilityCorrection",
+           "FactorizedTopK", "FeatureCross", "Ftrl", "GRU", "HardNegativeMining", "Huber", "MeanAbsoluteError", "MeanAbsoluteErrorMetric", "MeanSquaredError", "MeanSquaredErrorMetric", "RegressionMetricGroup", "RootMeanSquaredError", "InBatchSoftmaxLoss", "LSTM", "LayerNormalization", "MultiHeadAttention", "PartitionedRetrieval", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SamplingProbabilityCorrection",
            "SparseCategoricalCrossentropy", "SparseTopKCategoricalAccuracy", "TableConfig", "TransformerDecoder", "concat_features"]

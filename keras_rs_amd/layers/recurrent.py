@@ -1,6 +1,6 @@
-"""Recurrent layers for the reference's sequential recommenders (examples/sequential_retrieval.py): GRU, on K20
-(recurrent_ops.gru: all steps of the recurrence in one launch) and krs_gemm (the input projection, a DenseFn call on
-the [B L, D] view).
+"""Recurrent layers for the reference's sequential recommenders (examples/sequential_retrieval.py): GRU, on K20, and
+LSTM, on K25 (recurrent_ops.gru / .lstm: all steps of the recurrence in one launch), with krs_gemm for the input
+projection (a DenseFn call on the [B L, D] view).
 """
 
 from __future__ import annotations
@@ -100,5 +100,95 @@ class GRU(base.Layer):
             "bias_initializer": self.bias_initializer.serialize(), "dropout": 0.0, "recurrent_dropout": 0.0,
             "return_sequences": self.return_sequences, "return_state": self.return_state, "go_backwards": False,
             "stateful": False, "unroll": False, "reset_after": True,
+        })
+        return config
+
+
+class LSTM(base.Layer):
+    """keras.layers.LSTM with its defaults (tanh, sigmoid).  Weights, in Keras' order and shapes and gate order
+    i, f, c, o: kernel [D, 4 units], recurrent_kernel [units, 4 units], bias [4 units] (fp32; with unit_forget_bias its
+    forget slice starts at ones over the bias_initializer).  call(sequences [B, L, D], initial_state [h0, c0] each
+    [B, units], mask [B, L]) returns the last output [B, units], or the sequence output [B, L, units] with
+    return_sequences; with return_state a triple (output, final h, final c).  A masked step carries both states and
+    repeats the previous output (zeros before the first valid step), as Keras' backend rnn does (include/krs.h, K25)."""
+
+    def __init__(self, units: int, activation="tanh", recurrent_activation="sigmoid", use_bias: bool = True,
+                 kernel_initializer="glorot_uniform", recurrent_initializer="orthogonal", bias_initializer="zeros",
+                 unit_forget_bias: bool = True, dropout: float = 0.0, recurrent_dropout: float = 0.0,
+                 return_sequences: bool = False, return_state: bool = False, go_backwards: bool = False,
+                 stateful: bool = False, unroll: bool = False, **kwargs: Any):
+        super().__init__(**kwargs)
+        if int(units) <= 0:
+            raise ValueError(f"`units` must be a positive integer. Received: units={units}")
+        if base.get_activation(activation) is not base.tanh:
+            raise NotImplementedError(f"activation={activation!r} is not supported: K25 fuses tanh")
+        if base.get_activation(recurrent_activation) is not base.sigmoid:
+            raise NotImplementedError(f"recurrent_activation={recurrent_activation!r} is not supported: K25 fuses sigmoid")
+        if float(dropout) != 0.0:
+            raise NotImplementedError(f"dropout={dropout} is not supported: K25 has no input dropout mask")
+        if float(recurrent_dropout) != 0.0:
+            raise NotImplementedError(f"recurrent_dropout={recurrent_dropout} is not supported: K25 has no mask on the "
+                                      "carried state")
+        if go_backwards:
+            raise NotImplementedError("go_backwards=True is not supported: K25 walks t = 0 .. L - 1")
+        if stateful:
+            raise NotImplementedError("stateful=True is not supported: pass the previous call's states as initial_state")
+        if unroll:
+            raise NotImplementedError("unroll=True is not supported: K25 is one launch for all steps already")
+        self.units = int(units)
+        self.activation, self.recurrent_activation = base.tanh, base.sigmoid
+        self.use_bias, self.unit_forget_bias = bool(use_bias), bool(unit_forget_bias)
+        self.kernel_initializer = base.get_initializer(kernel_initializer)
+        self.recurrent_initializer = base.get_initializer(recurrent_initializer)
+        self.bias_initializer = base.get_initializer(bias_initializer)
+        self.return_sequences, self.return_state = bool(return_sequences), bool(return_state)
+        for w in ("kernel", "recurrent_kernel", "bias"):
+            self.register_parameter(w, None)
+
+    def build(self, sequences_shape, *_) -> None:
+        d, u = int(sequences_shape[-1]), self.units
+        self.kernel = self.add_weight((d, 4 * u), base.clone_initializer(self.kernel_initializer), "kernel")
+        self.recurrent_kernel = self.add_weight((u, 4 * u), base.clone_initializer(self.recurrent_initializer),
+                                                "recurrent_kernel")
+        if self.use_bias:
+            self.bias = self.add_weight((4 * u,), base.clone_initializer(self.bias_initializer), "bias",
+                                        dtype=torch.float32)
+            if self.unit_forget_bias:
+                with torch.no_grad():
+                    self.bias[u:2 * u] = 1.0
+        self.built = True
+
+    def call(self, sequences, initial_state=None, mask=None, training: bool = False):
+        if sequences.dim() != 3:
+            raise ValueError(f"LSTM takes [B, L, D] sequences, got {tuple(sequences.shape)}")
+        L.require_device(sequences, "LSTM sequences")
+        b, l, d = sequences.shape
+        if d != self.kernel.shape[0]:
+            raise ValueError(f"LSTM: input feature size {d} does not match the kernel {tuple(self.kernel.shape)}")
+        if initial_state is not None and len(initial_state) != 2:
+            raise ValueError(f"LSTM: initial_state is [h0, c0], got {len(initial_state)} tensors")
+        u = self.units
+        xz = DenseFn.apply(sequences.reshape(b * l, d), self.kernel, self.bias, L.ACT_NONE, self.compute_dtype, None,
+                           None, None)
+        out, h, c = recurrent_ops.lstm(xz.view(b, l, 4 * u), self.recurrent_kernel, mask=mask,
+                                       initial_state=None if initial_state is None else tuple(initial_state),
+                                       return_sequences=self.return_sequences)
+        return (out, h, c) if self.return_state else out
+
+    def compute_output_shape(self, sequences_shape):
+        b, l = sequences_shape[0], sequences_shape[1]
+        out = (b, l, self.units) if self.return_sequences else (b, self.units)
+        return (out, (b, self.units), (b, self.units)) if self.return_state else out
+
+    def get_config(self) -> dict:
+        config = super().get_config()
+        config.update({
+            "units": self.units, "activation": base.serialize_activation(self.activation),
+            "recurrent_activation": base.serialize_activation(self.recurrent_activation), "use_bias": self.use_bias,
+            "kernel_initializer": self.kernel_initializer.serialize(),
+            "recurrent_initializer": self.recurrent_initializer.serialize(),
+            "bias_initializer": self.bias_initializer.serialize(), "unit_forget_bias": self.unit_forget_bias,
+            "dropout": 0.0, "recurrent_dropout": 0.0, "return_sequences": self.return_sequences,
+            "return_state": self.return_state, "go_backwards": False, "stateful": False, "unroll": False,
         })
         return config

@@ -1,7 +1,8 @@
-"""K20: the recurrence of a GRU layer, all steps in one launch per sweep (csrc/gru.hip; the arithmetic is fixed in
-include/krs.h).  The input projection xz = x . kernel + bias[0] is the caller's (layers.GRU runs it as a Dense
+"""K20 and K25: the recurrence of a GRU and of an LSTM layer, all steps in one launch per sweep (csrc/gru.hip,
+csrc/lstm.hip; the arithmetic is fixed in include/krs.h).  The input projection xz = x . kernel + bias[0] is the caller's (layers.GRU runs it as a Dense
 product); the weight gradients of the recurrent kernel and bias are one krs_gemm and one krs_colsum on what the
-backward sweep wrote."""
+backward sweep wrote.  The LSTM's one bias rides in its projection, and its dxz is the right operand of the recurrent
+kernel's gradient as it stands."""
 
 import ctypes as C
 
@@ -9,7 +10,7 @@ import torch
 
 from . import _lib as L
 
-FAST, GENERIC = 1, 2          # krs_gru_last_route's kernels (KRS_GRU_*)
+FAST, GENERIC = 1, 2          # krs_gru_last_route's and krs_lstm_last_route's kernels (KRS_GRU_*, KRS_LSTM_*)
 
 
 def gru_reserve_bytes(b: int, l: int, u: int, dtype: torch.dtype = torch.bfloat16) -> int:
@@ -21,6 +22,18 @@ def last_route() -> tuple:
     """(kernel, upad) of the last forward or backward call."""
     kernel, upad = C.c_int(0), C.c_int(0)
     L.lib().krs_gru_last_route(C.addressof(kernel), C.addressof(upad))
+    return kernel.value, upad.value
+
+
+def lstm_reserve_bytes(b: int, l: int, u: int, dtype: torch.dtype = torch.bfloat16) -> int:
+    dt = L.BF16 if dtype == torch.bfloat16 else L.F32
+    return int(L.lib().krs_lstm_reserve_bytes(b, l, u, dt))
+
+
+def lstm_last_route() -> tuple:
+    """(kernel, upad) of the last LSTM forward or backward call."""
+    kernel, upad = C.c_int(0), C.c_int(0)
+    L.lib().krs_lstm_last_route(C.addressof(kernel), C.addressof(upad))
     return kernel.value, upad.value
 
 
@@ -143,3 +156,106 @@ def gru(xz: torch.Tensor, recurrent_kernel: torch.Tensor, recurrent_bias: torch.
         return state, state
     # the last step's OUTPUT: the state, except for a sequence with no valid step at all (zeros)
     return state * mask.any(dim=1, keepdim=True).to(state.dtype), state
+
+
+class _LSTM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xz, rk, valid, h0, c0, want_seq):
+        xz = _tokens(xz)
+        b, l, u4 = xz.shape
+        u = u4 // 4
+        dt, dev = xz.dtype, xz.device
+        rkc = rk.to(dt).contiguous()
+        h0c = None if h0 is None else h0.to(dt).contiguous()
+        c0c = None if c0 is None else c0.to(dt).contiguous()
+        train = any(ctx.needs_input_grad)
+        hs = torch.empty((b, l, u), dtype=dt, device=dev) if (want_seq or train) else None
+        h_last = torch.empty((b, u), dtype=dt, device=dev)
+        c_last = torch.empty((b, u), dtype=dt, device=dev)
+        reserve = torch.empty((lstm_reserve_bytes(b, l, u, dt),), dtype=torch.uint8, device=dev) if train else None
+        if b == 0 or l == 0:       # (nothing to walk: the states are the initial states)
+            h_last = torch.zeros((b, u), dtype=dt, device=dev) if h0c is None else h0c.clone()
+            c_last = torch.zeros((b, u), dtype=dt, device=dev) if c0c is None else c0c.clone()
+        else:
+            rc = L.lib().krs_lstm_fwd(L.ptr(xz), _ld(xz), L.ptr(rkc), L.ptr(valid), L.ptr(h0c), L.ptr(c0c), L.fdtype(xz),
+                                      b, l, u, L.ptr(hs), L.ptr(h_last), L.ptr(c_last), L.ptr(reserve), L.stream_ptr())
+            L.check(rc, "krs_lstm_fwd")
+        ctx.save_for_backward(rkc, valid, h0c, c0c, hs, reserve)
+        ctx.dims = (b, l, u)
+        ctx.dtypes = (rk.dtype, None if h0 is None else h0.dtype, None if c0 is None else c0.dtype)
+        ctx.set_materialize_grads(False)
+        if hs is None:
+            hs = torch.empty((b, 0, u), dtype=dt, device=dev)
+            ctx.mark_non_differentiable(hs)
+        return hs, h_last, c_last
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dhs, dh_last, dc_last):
+        from . import dense_ops as D
+
+        rkc, valid, h0c, c0c, hs, reserve = ctx.saved_tensors
+        b, l, u = ctx.dims
+        rk_dt, h0_dt, c0_dt = ctx.dtypes
+        want_xz, want_rk, _, want_h0, want_c0 = ctx.needs_input_grad[:5]
+        dt, dev = rkc.dtype, rkc.device
+        if b == 0 or l == 0:
+            z = lambda shape, d: torch.zeros(shape, dtype=d, device=dev)  # noqa: E731
+            through = lambda g, d: z((b, u), d) if g is None else g.to(d)  # noqa: E731
+            return (z((b, l, 4 * u), dt) if want_xz else None, z((u, 4 * u), rk_dt) if want_rk else None, None,
+                    through(dh_last, h0_dt) if want_h0 else None, through(dc_last, c0_dt) if want_c0 else None, None)
+        dhs = None if dhs is None else dhs.to(dt).contiguous()
+        dh_last = None if dh_last is None else dh_last.to(dt).contiguous()
+        dc_last = None if dc_last is None else dc_last.to(dt).contiguous()
+        dxz = torch.empty((b, l, 4 * u), dtype=dt, device=dev)
+        hprev = torch.empty((b, l, u), dtype=dt, device=dev) if want_rk else None
+        dh0 = torch.empty((b, u), dtype=dt, device=dev) if want_h0 else None
+        dc0 = torch.empty((b, u), dtype=dt, device=dev) if want_c0 else None
+        rc = L.lib().krs_lstm_bwd(L.ptr(rkc), L.ptr(valid), L.ptr(h0c), L.ptr(c0c), L.ptr(hs), L.ptr(reserve), L.ptr(dhs),
+                                  L.ptr(dh_last), L.ptr(dc_last), L.fdtype(rkc), b, l, u, L.ptr(dxz), L.ptr(hprev),
+                                  L.ptr(dh0), L.ptr(dc0), L.stream_ptr())
+        L.check(rc, "krs_lstm_bwd")
+        drk = None
+        if want_rk:      # sum_t h_{t-1}^T da_t as ONE weight-gradient product over all b * l tokens (da is dxz)
+            drk, _ = D.gemm(hprev.view(b * l, u), dxz.view(b * l, 4 * u), a_is_km=True, out_dtype=torch.float32)
+            drk = drk.to(rk_dt)
+        return (dxz if want_xz else None, drk, None, None if dh0 is None else dh0.to(h0_dt),
+                None if dc0 is None else dc0.to(c0_dt), None)
+
+
+def lstm(xz: torch.Tensor, recurrent_kernel: torch.Tensor, *, mask: torch.Tensor | None = None,
+         initial_state: tuple | None = None, return_sequences: bool = False):
+    """The recurrence of keras.layers.LSTM (tanh, sigmoid) over projected inputs.  xz: [B, L, 4U] = x . kernel + bias,
+    float32 or bfloat16, gates in Keras' order i, f, c, o (a view with a row stride is read in place);
+    recurrent_kernel [U, 4U]; mask [B, L], truthy = a real step; initial_state (h0, c0), each [B, U] or None (zeros).
+    Returns (outputs, h, c): outputs is the sequence output [B, L, U] with return_sequences, else the last step's
+    output [B, U]; h and c are the final states [B, U].  A masked step carries both states and repeats the previous
+    output, which is zeros before the first valid step.  No host synchronisation; differentiable in xz,
+    recurrent_kernel, h0 and c0, any subset, with gradients arriving at any of the three results."""
+    what = "lstm"
+    L.require_device(xz, f"{what}: xz")
+    if xz.dim() != 3 or xz.shape[2] % 4:
+        raise L.KrsError(f"{what}: xz must be [B, L, 4U], got shape {tuple(xz.shape)}")
+    L.fdtype(xz)
+    b, l, u4 = xz.shape
+    u = u4 // 4
+    if tuple(recurrent_kernel.shape) != (u, u4) or recurrent_kernel.device != xz.device:
+        raise L.KrsError(f"{what}: recurrent_kernel must be [U, 4U] = {(u, u4)} on {xz.device}, got "
+                         f"{tuple(recurrent_kernel.shape)} on {recurrent_kernel.device}")
+    if mask is not None:
+        if tuple(mask.shape) != (b, l) or mask.device != xz.device:
+            raise L.KrsError(f"{what}: mask must be [B, L] = {(b, l)} on {xz.device}, got {tuple(mask.shape)} on "
+                             f"{mask.device}")
+        mask = (mask != 0).to(torch.uint8).contiguous()
+    h0, c0 = (None, None) if initial_state is None else initial_state
+    for name, s0 in (("h0", h0), ("c0", c0)):
+        if s0 is not None and (tuple(s0.shape) != (b, u) or s0.device != xz.device):
+            raise L.KrsError(f"{what}: initial_state {name} must be [B, U] = {(b, u)} on {xz.device}, got "
+                             f"{tuple(s0.shape)} on {s0.device}")
+    hs, h, c = _LSTM.apply(xz, recurrent_kernel, mask, h0, c0, bool(return_sequences))
+    if return_sequences:
+        return hs, h, c
+    if mask is None:
+        return h, h, c
+    # the last step's OUTPUT: the state h, except for a sequence with no valid step at all (zeros)
+    return h * mask.any(dim=1, keepdim=True).to(h.dtype), h, c

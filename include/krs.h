@@ -1750,6 +1750,85 @@ int krs_lstm_bwd(const void* recurrent_kernel, const uint8_t* valid, const void*
                  int64_t l, int64_t u, void* dxz, void* hprev, void* dh0, void* dc0, void* stream);
 int krs_lstm_last_route(int* kernel, int* upad);
 
+/* ------------------------------------------------------------------------- *
+ * K26  Vocabulary lookup on a device hash table (keras.layers.IntegerLookup / StringLookup in output_mode "int"):
+ *      raw int64 tokens -> the row numbers every other kernel starts from
+ *
+ * Table     one device buffer of int64 words on a 16-byte boundary: a header of KRS_VOCAB_HEADER_BYTES, then `slots`
+ *           slots of KRS_VOCAB_SLOT_BYTES = { int64 key, int64 payload }.  One probe is one 16-byte load; eight slots
+ *           are one 128-byte line (on a 128-byte base).  slots is a multiple of 8; krs_vocab_table_bytes(n_tokens)
+ *           sizes it as slots = max(8, 2 * n_tokens rounded up to 8), so the load stays <= 0.5: 32 bytes a token.
+ *           An empty slot's key word is INT64_MIN.  Every int64 is a legal token: the TOKEN INT64_MIN is kept in the
+ *           header's side slot.  Header words: [0] the number of distinct tokens (side slot included), [1] 1 when the
+ *           side slot is taken, [2] the side slot's payload, [3..15] zero.
+ * Home slot krs_vocab_home_slot(key, slots), a host function the kernels share (csrc/vocab_plan.h), on uint64
+ *           arithmetic modulo 2^64:
+ *               x = key;  x ^= x >> 30;  x *= 0xbf58476d1ce4e5b9;  x ^= x >> 27;  x *= 0x94d049bb133111eb;
+ *               x ^= x >> 31;            home = (x * slots) >> 64          (the high word of the 128-bit product)
+ *           Linear probing from there, one slot at a time, wrapping from slots - 1 to 0.
+ * Upsert    krs_vocab_upsert is the only writer.  keys [n] (keys_itype; int32 keys are sign-extended), payloads [n]
+ *           int64 or NULL.  init != 0 first clears the header and every slot (a kernel of the call; the buffer need
+ *           not be initialised).  A slot is claimed by a 64-bit atomicCAS on its key word.
+ *               KRS_VOCAB_SET  payload = payloads[i], or i when NULL: the token's place in the vocabulary.  A key
+ *                              already in the table (from this call or before it) raises KRS_FLAG_DUPLICATE_TOKEN and
+ *                              leaves the stored payload alone.
+ *               KRS_VOCAB_ADD  payload += payloads[i], or 1 when NULL, by an integer atomic add: a count.  Exact and
+ *                              the same from run to run; it is also the rehash (upsert an export into a larger table).
+ *           A key that finds neither itself nor an empty slot in `slots` probes raises KRS_FLAG_TABLE_FULL.  The caller
+ *           keeps n_tokens <= slots / 2.
+ * Lookup    krs_vocab_lookup maps ids [n] (ids_itype) to out [n] (out_itype) under Keras' index layout
+ *           [mask][OOV slots][vocabulary]:  with base = has_mask + num_oov,
+ *               has_mask and id == mask_token          0
+ *               id in the table                        base + payload
+ *               otherwise, num_oov == 1                has_mask
+ *                          num_oov  > 1                has_mask + floormod(id, num_oov)      (a floor modulus: >= 0)
+ *                          num_oov == 0                -1, and KRS_FLAG_OOV_TOKEN is OR'ed into err_flag
+ *           err_flag is an optional device int.  No host wait, no allocation: a call captures into a HIP graph.
+ *           Routes (csrc/vocab_plan.h decides; route_hint KRS_VOCAB_AUTO, or KRS_VOCAB_LDS / KRS_VOCAB_GLOBAL to force
+ *           one; ids_per_lane 0 = the planner's, or 1 / 2 / 4 / 8 on the global route):
+ *               KRS_VOCAB_LDS     slots * 16 <= 160 KB: every workgroup stages the table into LDS with 16-byte loads,
+ *                                 then walks a grid-strided span of ids, 4 a lane, probing in LDS.  It lost to the
+ *                                 global route at every measured point, so KRS_VOCAB_AUTO never takes it; the hint does.
+ *               KRS_VOCAB_GLOBAL  a lane owns ids_per_lane consecutive ids (the planner's choice is 1, the measured
+ *                                 winner); their first probes are issued back to back before any is examined, then
+ *                                 each chain continues slot by slot.
+ *           vec: ids and out start on 16 bytes and a lane's ids and indices are whole 16-byte pieces -- they move in
+ *           16-byte loads and stores (the last, partial lane by elements); otherwise by elements.
+ * Export    krs_vocab_export compacts the occupied slots into keys [cap] and payloads [cap] in slot order, the side
+ *           slot last, and writes the number of items to out_count (device int64).  Items beyond cap are dropped, not
+ *           written.  workspace: krs_vocab_export_workspace_bytes(slots) bytes, uninitialised.
+ * Refusals  (KRS_ERR_INVALID, before any launch) a NULL table, keys, ids or out with n > 0, NULL export outputs, a
+ *           table off a 16-byte boundary, slots < 8 or not a multiple of 8, an itype outside its enum, n < 0, a bad mode,
+ *           num_oov < 0, a bad hint, KRS_VOCAB_LDS forced on a table that does not fit; too little workspace is
+ *           KRS_ERR_WORKSPACE.  n == 0 is a successful no-op (with init, the table is still cleared).
+ * krs_vocab_last_route: how the calling thread's last krs_vocab_lookup ran (all 0 before the first call, after a
+ * refusal or for n == 0); returns `route`.  krs_vocab_plan_route: the same answer without a GPU.
+ * ------------------------------------------------------------------------- */
+#define KRS_VOCAB_HEADER_BYTES 128
+#define KRS_VOCAB_SLOT_BYTES 16
+#define KRS_FLAG_OOV_TOKEN 16         /* krs_vocab_lookup: a token outside the vocabulary with num_oov == 0 (index -1) */
+#define KRS_FLAG_DUPLICATE_TOKEN 32   /* krs_vocab_upsert, KRS_VOCAB_SET: a key was already in the table */
+#define KRS_FLAG_TABLE_FULL 64        /* krs_vocab_upsert: no slot left for a key (it was dropped) */
+enum { KRS_VOCAB_SET = 0, KRS_VOCAB_ADD = 1 };
+enum { KRS_VOCAB_AUTO = 0, KRS_VOCAB_LDS = 1, KRS_VOCAB_GLOBAL = 2 };
+typedef struct krs_vocab_route {
+  int32_t route, ids_per_lane, vec, lds_bytes;
+  int64_t slots, blocks;
+} krs_vocab_route;
+size_t krs_vocab_table_bytes(int64_t n_tokens);
+int64_t krs_vocab_home_slot(int64_t key, int64_t slots);
+int krs_vocab_upsert(void* table, int64_t slots, const void* keys, int keys_itype, const int64_t* payloads, int64_t n,
+                     int mode, int init, int* err_flag, void* stream);
+int krs_vocab_lookup(const void* table, int64_t slots, const void* ids, int ids_itype, int64_t n, int has_mask,
+                     int64_t mask_token, int num_oov, void* out, int out_itype, int* err_flag, int route_hint,
+                     int ids_per_lane, void* stream);
+int krs_vocab_last_route(krs_vocab_route* route);
+int krs_vocab_plan_route(const void* table, int64_t slots, const void* ids, int ids_itype, int64_t n, int num_oov,
+                         const void* out, int out_itype, int route_hint, int ids_per_lane, krs_vocab_route* route);
+size_t krs_vocab_export_workspace_bytes(int64_t slots);
+int krs_vocab_export(const void* table, int64_t slots, int64_t* keys, int64_t* payloads, int64_t cap,
+                     int64_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,9 @@ FLAG_ID_OUT_OF_RANGE = 1
 FLAG_BAD_OFFSETS = 2
 FLAG_CAPACITY_OVERFLOW = 4
 FLAG_NONFINITE_ROW = 8
+FLAG_OOV_TOKEN = 16
+FLAG_DUPLICATE_TOKEN = 32
+FLAG_TABLE_FULL = 64
 MAX_LIST = 4096   # KRS_RANK_MAX_LIST
 
 # struct layouts of include/krs.h
@@ -107,6 +110,17 @@ REG_MSE, REG_MAE, REG_HUBER = 0, 1, 2
 REG_NONE, REG_SUM, REG_SUM_OVER_BATCH_SIZE, REG_MEAN_WITH_SAMPLE_WEIGHT = 0, 1, 2, 3
 REG_ROUTE_NONE, REG_VEC, REG_ELEM = 0, 1, 2
 REG_MAX_BLOCKS, REG_THREADS = 256, 1024
+
+
+class VocabRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("route", "ids_per_lane", "vec", "lds_bytes")] + \
+               [(name, C.c_int64) for name in ("slots", "blocks")]
+
+
+# K26 (include/krs.h): upsert modes, krs_vocab_route.route / route_hint, and the table's layout in int64 words
+VOCAB_SET, VOCAB_ADD = 0, 1
+VOCAB_AUTO, VOCAB_LDS, VOCAB_GLOBAL = 0, 1, 2
+VOCAB_HEADER_WORDS, VOCAB_EMPTY = 16, -(1 << 63)
 
 
 # Prototype of every entry point include/krs.h declares, in its order: name -> (restype, argtypes).  Any pointer is a
@@ -243,6 +257,14 @@ PROTOTYPES = {
     "krs_lstm_fwd": (_I, [_P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     "krs_lstm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     "krs_lstm_last_route": (_I, [_P, _P]),
+    "krs_vocab_table_bytes": (_SZ, [_I64]),
+    "krs_vocab_home_slot": (_I64, [_I64, _I64]),
+    "krs_vocab_upsert": (_I, [_P, _I64, _P, _I, _P, _I64, _I, _I, _P, _P]),
+    "krs_vocab_lookup": (_I, [_P, _I64, _P, _I, _I64, _I, _I64, _I, _P, _I, _P, _I, _I, _P]),
+    "krs_vocab_last_route": (_I, [_P]),
+    "krs_vocab_plan_route": (_I, [_P, _I64, _P, _I, _I64, _I, _P, _I, _I, _I, _P]),
+    "krs_vocab_export_workspace_bytes": (_SZ, [_I64]),
+    "krs_vocab_export": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _SZ, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -70,6 +70,7 @@ class SasRec(base.Layer):
             for i in range(num_layers)]
         self.layer_norm = kl.LayerNormalization(1e-8, name="layer_norm", **sub)
         self.retrieval = kl.BruteForceRetrieval(k=k, return_scores=False, device=self._device)
+        self.exclude_history = False       # serve and evaluate without the items of the input sequence
         self.built = True
 
     def sequence_embedding(self, item_ids, padding_mask, training: bool = False):
@@ -97,7 +98,10 @@ class SasRec(base.Layer):
             table = self.item_embedding.weights[0].detach()
             ids = torch.arange(self.vocabulary_size, device=table.device, dtype=torch.int32)
             self.retrieval.update_candidates(table.to(self.compute_dtype), ids)
-            result["predictions"] = self.retrieval(self.last_non_padding_token(emb, padding_mask).detach())
+            # exclude_history (K27): a user's own sequence never comes back, and k stays k inside the fused kernel
+            seen = torch.where(padding_mask, item_ids, -1) if self.exclude_history else None
+            result["predictions"] = self.retrieval(self.last_non_padding_token(emb, padding_mask).detach(),
+                                                   exclusions=seen)
         return result
 
     def compute_loss(self, y, y_pred, sample_weight):
@@ -115,7 +119,7 @@ class SasRec(base.Layer):
 
 def main(steps: int = 30, batch: int = 64, vocabulary_size: int = 500, length: int = 50, hidden_dim: int = 50,
          num_heads: int = 1, num_layers: int = 2, dropout: float = 0.2, dtype: str = "bf16", lr: float = 0.005,
-         seed: int = 0, quiet: bool = False):
+         seed: int = 0, quiet: bool = False, exclude_history: bool = False):
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(seed)
     policy = {"bf16": "mixed_bfloat16", "fp32": "float32"}[dtype]
@@ -136,6 +140,7 @@ def main(steps: int = 30, batch: int = 64, vocabulary_size: int = 500, length: i
         losses.append(float(loss.detach()))
         if not quiet:
             print(f"step {step}: loss {losses[-1]:.4f}")
+    model.exclude_history = exclude_history
     with torch.no_grad():
         out = model(inputs, training=False)
     if not quiet:
@@ -153,6 +158,8 @@ if __name__ == "__main__":
     ap.add_argument("--heads", type=int, default=1)
     ap.add_argument("--layers", type=int, default=2)
     ap.add_argument("--vocabulary", type=int, default=500)
+    ap.add_argument("--exclude-history", action="store_true",
+                    help="leave each user's input sequence out of the served top-k (K27)")
     a = ap.parse_args()
     main(steps=a.steps, batch=a.batch, vocabulary_size=a.vocabulary, length=a.length, hidden_dim=a.hidden,
-         num_heads=a.heads, num_layers=a.layers, dtype=a.dtype)
+         num_heads=a.heads, num_layers=a.layers, dtype=a.dtype, exclude_history=a.exclude_history)

@@ -51,6 +51,7 @@ class SequentialRetrievalModel(base.Layer):
         setattr(self, cell, {"gru": kl.GRU, "lstm": kl.LSTM}[cell](embedding_dimension, name=cell, **sub))
         self.candidate_model = kl.Embedding(movies_count + 1, embedding_dimension, name="candidate_embedding", **sub)
         self.retrieval = kl.BruteForceRetrieval(k=k, return_scores=False, device=self._device)
+        self.exclude_history = False       # serve and evaluate without the items of the input context
         self.loss_fn = kl.InBatchSoftmaxLoss() if fused else kl.CategoricalCrossentropy(from_logits=True)
         self.built = True
 
@@ -69,7 +70,9 @@ class SequentialRetrievalModel(base.Layer):
             table = self.candidate_model.weights[0].detach()
             ids = torch.arange(self.movies_count + 1, device=table.device, dtype=torch.int32)
             self.retrieval.update_candidates(table.to(self.compute_dtype), ids)
-            result["predictions"] = self.retrieval(query_embeddings.detach())
+            # exclude_history (K27): a user's own context never comes back (0 pads a context), and k stays k
+            seen = torch.where(inputs > 0, inputs, -1) if self.exclude_history else None
+            result["predictions"] = self.retrieval(query_embeddings.detach(), exclusions=seen)
         return result
 
     def compute_loss(self, y, y_pred):
@@ -84,7 +87,7 @@ class SequentialRetrievalModel(base.Layer):
 
 def main(steps: int = 30, batch: int = 4096, vocabulary_size: int = 3000, hidden_dim: int = 32,
          length: int = MAX_CONTEXT_LENGTH, dtype: str = "bf16", lr: float = 0.005, fused: bool = False,
-         seed: int = 0, quiet: bool = False, cell: str = "gru"):
+         seed: int = 0, quiet: bool = False, cell: str = "gru", exclude_history: bool = False):
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(seed)
     policy = {"bf16": "mixed_bfloat16", "fp32": "float32"}[dtype]
@@ -102,6 +105,7 @@ def main(steps: int = 30, batch: int = 4096, vocabulary_size: int = 3000, hidden
         losses.append(float(loss.detach()))
         if not quiet:
             print(f"step {step}: loss {losses[-1]:.4f}")
+    model.exclude_history = exclude_history
     with torch.no_grad():
         out = model(context, training=False)
     if not quiet:
@@ -119,6 +123,8 @@ if __name__ == "__main__":
     ap.add_argument("--vocabulary", type=int, default=3000)
     ap.add_argument("--fused", action="store_true")
     ap.add_argument("--cell", choices=("gru", "lstm"), default="gru", help="the recurrent layer of the query tower")
+    ap.add_argument("--exclude-history", action="store_true",
+                    help="leave each user's input context out of the served top-k (K27)")
     a = ap.parse_args()
     main(steps=a.steps, batch=a.batch, vocabulary_size=a.vocabulary, hidden_dim=a.hidden, dtype=a.dtype, fused=a.fused,
-         cell=a.cell)
+         cell=a.cell, exclude_history=a.exclude_history)

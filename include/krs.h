@@ -903,7 +903,8 @@ int krs_retrieval_topk(const void* q, int64_t ldq, const void* c, int64_t ldc, c
  *   chunk_rows       SLAB: query rows of a full chunk (the last chunk has b - (chunks - 1) * chunk_rows)
  * Fields that do not apply are 0.  krs_retrieval_last_route returns `kernel`; `route` may be NULL. */
 enum { KRS_RETR_NONE = 0, KRS_RETR_FUSED, KRS_RETR_SLAB, KRS_RETR_ROWS };
-enum { KRS_RETR_VARIANT_NONE = 0, KRS_RETR_VARIANT_TOPK, KRS_RETR_VARIANT_Q8, KRS_RETR_VARIANT_MINE, KRS_RETR_VARIANT_ROWS };
+enum { KRS_RETR_VARIANT_NONE = 0, KRS_RETR_VARIANT_TOPK, KRS_RETR_VARIANT_Q8, KRS_RETR_VARIANT_MINE, KRS_RETR_VARIANT_ROWS,
+       KRS_RETR_VARIANT_TOPK_EXCL, KRS_RETR_VARIANT_Q8_EXCL /* K27: the entries with exclusion lists, e > 0 */ };
 enum { KRS_SELECT_NONE = 0, KRS_SELECT_LDS, KRS_SELECT_RADIX, KRS_SELECT_RADIX_MERGE };
 typedef struct krs_retrieval_route {
   int32_t kernel, variant, es, vec, S, qtiles, row_bytes, lds_bytes, select, select_launches;
@@ -1252,7 +1253,58 @@ int krs_retrieval_topk_q8(const void* q, int64_t ldq, int q_dtype, const int8_t*
                           int32_t* out_ids, int* err_flag, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
- * K18  Dense and FeatureCross in int8: C = epilogue(scale(Aq . Wq^T)) on v_mfma_i32_32x32x32_i8
+ * K27  Per-query exclusion lists inside the fused top-k: krs_retrieval_topk and krs_retrieval_topk_q8 that leave out,
+ *      for each query row, the candidates the row names (what a served recommender has already shown its user)
+ *
+ * Both entries take their parent's arguments, then the list:
+ *   excl        int32 [b, e] with row stride ldx >= e (elements): candidate ROW INDICES in [0, n), never identifiers (the
+ *               `ids` operand only renames what is returned).  A value < 0 (-1 is the padding) or >= n is ignored;
+ *               duplicates are allowed.  The tensor is only read: the call works on a sorted copy in the workspace, so a
+ *               captured call replays with whatever the tensor holds then.
+ *   e           1 <= e <= 2048 exclusions per row.  e > 2048 is KRS_ERR_UNSUPPORTED with a message naming the limit
+ *               (a row is sorted in LDS).  e == 0 IS the parent call -- its launches, its result bit for bit, its route
+ *               record -- and excl is then not looked at; e < 0, ldx < e and a NULL excl with e > 0 are KRS_ERR_INVALID.
+ *   Result      The parent's top-k over the candidates the row does not exclude, in the parent's total order (score
+ *               descending, index ascending, NaN above +inf).  A surviving candidate's score has exactly the bits the
+ *               parent gives it: exclusion happens after the score is formed, at the threshold test.  A row with m < k
+ *               survivors returns them in its first m columns and id -1 / score -inf in the rest (krs_retrieval_ivf's
+ *               convention); k <= n stays the argument rule.  An excluded candidate is never returned, whatever its
+ *               score: on the slab path it is marked in the score slab with the bit pattern 0xffffffff, which the
+ *               selection reads as "no candidate" (below a real -inf); no arithmetic on the GPU produces that NaN, so
+ *               only a caller that stores this very pattern in an fp32 operand can have a score taken for a mark.
+ *   Execution   excl_prepare_kernel, one workgroup of 1024 threads per query row: the row into LDS as keys (ignored
+ *               entries as 0), krs_list.h's bitonic sort, then the ascending row, its count of valid entries and -- on
+ *               the fused path -- for each of the S candidate slices the number of entries below the slice's first
+ *               candidate go to the workspace.  Stage 1 (the EXCL build of the parent's kernel, same geometry) gives
+ *               tile row r to lane r of wave 0: the lane keeps the row's cursor and its next entry in registers, and
+ *               between the two barriers a 128-candidate step already has it moves the cursor over the entries of the
+ *               NEXT step, setting their bits in a [32][4]-word mask in LDS.  A ballot over the 32 owners gives the
+ *               workgroup-wide flag "some row excludes something in that step"; a step without it (nearly all: e
+ *               entries among n / 128 steps) costs the owners one compare and nobody a mask access.  In a flagged step
+ *               a lane reads one mask word per accumulator row and an excluded (row, candidate) is not queued: it
+ *               takes no queue slot and never moves the row's threshold, so the queue cut keeps its invariant.  No
+ *               search per (query, candidate); the mask has one owner per word, no atomics; no barrier is added.
+ *               Slab path (krs_retrieval_topk_excl with k > 128 or d > 512): excl_slab_kernel, one thread per (row of
+ *               the chunk, list entry), marks the slab between krs_gemm and the selection; a repeated entry is written
+ *               by its first occurrence only.  No allocation, no host wait; graph-capturable.
+ *   Route       krs_retrieval_last_route / krs_retrieval_plan_route report KRS_RETR_VARIANT_TOPK_EXCL / _Q8_EXCL with the
+ *               parent's geometry (S, slice, qtiles, vec) and lds_bytes = the parent's + 528 (the mask and the flag).
+ *               krs_retrieval_plan_route has no e: it plans these variants for e = 1 (nothing it reports depends on e).
+ * Workspace: the parent's sections, then the sorted rows (4 b e bytes), the counts (4 b) and on the fused path the slice
+ * cursors (4 b S), each rounded up to 256.  e == 0 asks for the parent's size; e > 2048 and unsupported shapes for 0.
+ * ------------------------------------------------------------------------- */
+size_t krs_retrieval_topk_excl_workspace_bytes(int64_t b, int64_t n, int64_t d, int k, int dtype, int64_t e);
+int krs_retrieval_topk_excl(const void* q, int64_t ldq, const void* c, int64_t ldc, const int32_t* ids, int dtype,
+                            int64_t b, int64_t n, int64_t d, int k, void* out_scores, int32_t* out_ids, void* workspace,
+                            size_t workspace_bytes, void* stream, const int32_t* excl, int64_t ldx, int64_t e);
+size_t krs_retrieval_topk_q8_excl_workspace_bytes(int64_t b, int64_t n, int64_t d, int k, int64_t e);
+int krs_retrieval_topk_q8_excl(const void* q, int64_t ldq, int q_dtype, const int8_t* cq, int64_t ldc, const float* cstep,
+                               const int32_t* ids, int64_t b, int64_t n, int64_t d, int k, void* out_scores, int out_dtype,
+                               int32_t* out_ids, int* err_flag, void* workspace, size_t workspace_bytes, void* stream,
+                               const int32_t* excl, int64_t ldx, int64_t e);
+
+/* ------------------------------------------------------------------------- *
+ * K18 Dense and FeatureCross in int8: C = epilogue(scale(Aq . Wq^T)) on v_mfma_i32_32x32x32_i8
  *
  * The serving form of keras.layers.Dense.quantize("int8"): int8 weights with one step per output channel, activations
  * quantized per row on the way in, an exact int32 product, two fp32 scalings, then krs_gemm's epilogue.  All pinned:

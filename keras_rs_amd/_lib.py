@@ -220,6 +220,12 @@ PROTOTYPES = {
     "krs_retrieval_rank": (_I, [_P, _I64, _P, _I64, _I, _I64, _I64, _I64, _P, _P, _I, _P, _P, _P, _SZ, _P]),
     "krs_retrieval_topk_q8_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I]),
     "krs_retrieval_topk_q8": (_I, [_P, _I64, _I, _P, _I64, _P, _P, _I64, _I64, _I64, _I, _P, _I, _P, _P, _P, _SZ, _P]),
+    "krs_retrieval_topk_excl_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I, _I, _I64]),
+    "krs_retrieval_topk_excl": (_I, [_P, _I64, _P, _I64, _P, _I, _I64, _I64, _I64, _I, _P, _P, _P, _SZ, _P, _P, _I64,
+                                     _I64]),
+    "krs_retrieval_topk_q8_excl_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I, _I64]),
+    "krs_retrieval_topk_q8_excl": (_I, [_P, _I64, _I, _P, _I64, _P, _P, _I64, _I64, _I64, _I, _P, _I, _P, _P, _P, _SZ, _P,
+                                        _P, _I64, _I64]),
     "krs_gemm_q8": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _P]),
     "krs_gemm_q8_last_route": (_I, [_P]),
     "krs_gemm_q8_plan_route": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _P]),

@@ -42,10 +42,15 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if s in ("lstm.hip", "vocab.hip"):   # (K25's gate arithmetic is one scalar fp32 operation per register, K26 is
             # integer work: no packed fp32)
             parts = [("", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
+        deps = [src]
+        if s == "retrieval_excl.hip":        # (K27: a second translation unit of retrieval.hip, which it includes, so
+            # that K8's own object compiles exactly as before; the mask walk and the list kernels are integer work)
+            parts = [("", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
+            deps.append(os.path.join(CSRC, "retrieval.hip"))
         for suffix, defs in parts:
             obj = os.path.join(OBJ, s[:-4] + suffix + ".o")
             objs.append(obj)
-            if force or _newer(obj, [src] + hdrs):
+            if force or _newer(obj, deps + hdrs):
                 jobs.append([HIPCC] + FLAGS + defs + ["-c", src, "-o", obj])
 
     def run(cmd):

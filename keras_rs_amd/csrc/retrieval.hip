@@ -87,6 +87,17 @@ struct MatSrc {
     return pair_key(order_key(v), (uint32_t)i);
   }
 };
+// K27: a row of the fp32 score slab in which excl_slab_kernel has marked the row's excluded candidates: a mark is no
+// candidate at all (pair 0, below a real -inf)
+constexpr uint32_t kExclMark = 0xffffffffu;
+struct MarkedSlabSrc {
+  const uint32_t* x;   // the slab's fp32 words
+  int64_t ld;
+  __device__ __forceinline__ uint64_t pair(int64_t r, int64_t i) const {
+    const uint32_t u = x[r * ld + i];
+    return u == kExclMark ? 0 : pair_key(order_key(__uint_as_float(u)), (uint32_t)i);
+  }
+};
 // the per-slice lists stage 1 wrote: [rows, len] pairs
 struct PairSrc {
   const uint64_t* p;
@@ -302,6 +313,14 @@ struct Ah {
   int q_f32;                     // the queries are fp32: rounded to bf16 (nearest even) as the tile is filled
 };
 
+// what the exclusion variant of stage 1 adds (K27): excl_prepare_kernel's sorted copy of the rows' exclusion lists
+struct Excl {
+  const int32_t* list;    // [b, e] ascending candidate indices, the ignored entries (as -1) last
+  int64_t e;
+  const int32_t* count;   // [b] valid entries of a row
+  const int32_t* start;   // [b, S] entries of a row below the first candidate of slice s
+};
+
 // one wave sorts a row queue of m <= 256 pairs (4 per lane, descending), keeps the first k and returns the new
 // threshold key (0 while fewer than k pairs were seen); `q` is rewritten with the kept pairs
 __device__ uint32_t wave_compact(uint64_t* q, int m, int k, int lane) {
@@ -404,10 +423,18 @@ __device__ __forceinline__ u32x4 load_k_chunk(const char* crow, int ch, int d) {
 // one centre of M bf16 from the codebooks, staged into LDS once per workgroup as [block][code][M] and zeroed beyond d.
 // Lanes 0-31 and 32-63 each read one block, so at most 16 distinct, consecutive centres.  The probe score of the tile
 // row's (query, leaf) pair is added to the chain's result, one rounded fp32 addition, before the score is ranked.
-template <int ES, bool VEC, bool MINE, bool IVF = false, int AH = 0>
+// EXCL (K27, krs_retrieval_topk_excl / _q8_excl): lane r of wave 0 owns tile row r's sorted exclusion list -- its cursor
+// and the entry under it live in the lane's registers.  Between the two barriers of step i the owners move their cursors
+// over the entries that fall among step i + 1's candidates and write the row's 4 mask words (bit c = candidate blk + c);
+// their ballot is the workgroup's flag "step i + 1 excludes something".  Step i + 1 reads the flag, and only when it is
+// set one mask word per accumulator row: an excluded (row, candidate) is not queued.  The mask of step i is read before
+// barrier A of step i and rewritten after it, and read again after barrier B: no barrier is added.  A list entry is
+// visited once per slice it falls in, in order: no search per score.
+template <int ES, bool VEC, bool MINE, bool IVF = false, int AH = 0, bool EXCL = false>
 __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, const Q8Scale& q8 = Q8Scale{},
-                                            const Ivf& iv = Ivf{}, const Ah& ah = Ah{}) {
+                                            const Ivf& iv = Ivf{}, const Ah& ah = Ah{}, const Excl& ex = Excl{}) {
   static_assert(AH == 0 || (IVF && ES == 2 && !MINE), "the AH operand belongs to the partitioned bf16 scan");
+  static_assert(!EXCL || (!MINE && !IVF), "exclusion lists belong to krs_retrieval_topk and its int8 twin");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lstride = p.row_bytes + 16;
   char* qt = smem;                                                           // [kQM][lstride]
@@ -420,6 +447,8 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
   int* qpair = reinterpret_cast<int*>(thr + kQM);                            // [kQM]  IVF: the row's pair, or -1
   int* qrow = qpair + kQM;                                                   // [kQM]  IVF: the row's query
   char* cb = reinterpret_cast<char*>(qrow + kQM);                            // [row_bytes * 16]  AH: the codebooks
+  uint32_t* xmask = reinterpret_cast<uint32_t*>(thr + kQM) + (ES == 1 ? kQM : 0);   // [kQM][kCB / 32]  EXCL: the step mask
+  uint32_t* xflag = xmask + kQM * (kCB / 32);                                // EXCL: the step excludes something
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int frow = lane & 31, fhalf = lane >> 5;
@@ -505,6 +534,40 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
       pid[threadIdx.x] = id;
     }
   }
+  // EXCL, wave 0: lane r < kQM owns tile row r's list xl[xcur .. xend); xnext is the entry under the cursor (none: past
+  // every candidate).  excl_build(lo) consumes the entries below lo + kCB -- all of them are at or above lo -- into the
+  // mask of the step that starts at candidate lo.
+  [[maybe_unused]] const int32_t* xl = nullptr;
+  [[maybe_unused]] int xcur = 0, xend = 0;
+  [[maybe_unused]] int64_t xnext = INT64_MAX;
+  [[maybe_unused]] auto excl_build = [&](int64_t lo) {
+    const int64_t hi = lo + kCB;
+    const bool any = __ballot(xnext < hi) != 0;       // wave-uniform
+    if (any) {
+      uint32_t w[kCB / 32] = {0, 0, 0, 0};
+      while (xnext < hi) {
+        const int bit = (int)(xnext - lo);
+#pragma unroll
+        for (int x = 0; x < kCB / 32; ++x) w[x] |= (bit >> 5) == x ? 1u << (bit & 31) : 0u;
+        ++xcur;
+        xnext = xcur < xend ? (int64_t)xl[xcur] : INT64_MAX;
+      }
+      if (lane < kQM) *reinterpret_cast<u32x4*>(xmask + lane * (kCB / 32)) = (u32x4){w[0], w[1], w[2], w[3]};
+    }
+    if (lane == 0) *xflag = any ? 1u : 0u;
+  };
+  if constexpr (EXCL) {
+    if (wave == 0) {
+      if (lane < kQM && q0 + lane < p.b) {
+        const int64_t qr = q0 + lane;
+        xl = ex.list + qr * ex.e;
+        xend = ex.count[qr];
+        xcur = ex.start[qr * p.S + slice];
+        if (xcur < xend) xnext = xl[xcur];
+      }
+      excl_build(s0);
+    }
+  }
   if constexpr (AH != 0) {
     // the codebooks over the tile's whole K extent: zero from block `blocks` on and in the columns from d on
     uint16_t* cbw = reinterpret_cast<uint16_t*>(cb);
@@ -541,6 +604,8 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
   for (int64_t blk = s0; blk < s1; blk += kCB) {
     const int64_t cand = blk + wave * 32 + frow;  // this lane's candidate row (B fragment)
     const bool cvalid = cand < s1;
+    [[maybe_unused]] bool xstep = false;          // EXCL: some row excludes a candidate of this step
+    if constexpr (EXCL) xstep = *xflag != 0;
     const char* crow = p.c + (cvalid ? cand : 0) * p.ldc * ES;
     f32x16 acc;
 #pragma unroll
@@ -675,13 +740,18 @@ __device__ __forceinline__ void stage1_body(const Stage1& p, const Mine& mn, con
       for (int r = 0; r < 16; ++r) {
         const int row = acc_row(r, fhalf);
         const uint32_t key = order_key(acc[r]);
-        if (cvalid && live(row) && key > t_reg[r]) {
+        bool excluded = false;                    // EXCL: wave w holds candidates 32 w .. 32 w + 31 of the step, word w
+        if constexpr (EXCL) excluded = xstep && ((xmask[row * (kCB / 32) + wave] >> frow) & 1u) != 0;
+        if (cvalid && live(row) && key > t_reg[r] && !excluded) {
           const int s = atomicAdd(&cnt[row], 1);
           queue[row * p.cap + s] = pair_key(key, cidx);
         }
       }
     }
     __syncthreads();
+    if constexpr (EXCL) {
+      if (wave == 0 && blk + kCB < s1) excl_build(blk + kCB);
+    }
     // a queue that could overflow in the next step is cut back to its k best (candidates come in ascending index
     // order, so `key > threshold` keeps exactly the pairs that can still enter the top k)
     for (int row = wave; row < kQM; row += 4) {
@@ -794,7 +864,7 @@ __global__ __launch_bounds__(256) void ivf_fill_kernel(const int32_t* probe, int
 // ---- the four planned entries: check, plan (retrieval_plan.h), launch what the plan names ---------------------------------
 // where the calling thread's last planned entry ran (krs_retrieval_last_route): cleared when an entry starts, written when
 // it has queued its last kernel, so a refused call and a call without query rows leave "none"
-thread_local krs_retrieval_route g_route = {};
+[[maybe_unused]] thread_local krs_retrieval_route g_route = {};
 
 // the two-step path's budget: KRS_RETRIEVAL_SLAB_BYTES when it is a positive integer, read on each call
 inline int64_t slab_budget() {
@@ -812,11 +882,15 @@ inline const char* entry_name(int variant) {
     case KRS_RETR_VARIANT_TOPK: return "krs_retrieval_topk";
     case KRS_RETR_VARIANT_Q8: return "krs_retrieval_topk_q8";
     case KRS_RETR_VARIANT_MINE: return "krs_retrieval_mine";
+    case KRS_RETR_VARIANT_TOPK_EXCL: return "krs_retrieval_topk_excl";
+    case KRS_RETR_VARIANT_Q8_EXCL: return "krs_retrieval_topk_q8_excl";
     default: return "krs_topk_rows";
   }
 }
-inline rplan::Call make_call(int variant, int es, const void* c, int64_t ldc, int64_t b, int64_t n, int64_t d, int k) {
+inline rplan::Call make_call(int variant, int es, const void* c, int64_t ldc, int64_t b, int64_t n, int64_t d, int k,
+                             int64_t e = 0) {
   rplan::Call call;
+  call.e = rplan::is_excl(variant) ? e : 0;
   call.variant = variant;
   call.b = b; call.n = n; call.d = d; call.k = k;
   call.es = es;
@@ -829,8 +903,9 @@ inline rplan::Call make_call(int variant, int es, const void* c, int64_t ldc, in
 // What an entry checks before its first launch, apart from the operands the planner never looks at (outputs, steps, ids,
 // the workspace), and the call's plan.  krs_retrieval_plan_route answers from this alone.  ROWS: q is unused, c = x,
 // ldc = ld, b = rows, n = cols.  Q8: dtype is the query's.  pl is "none" unless KRS_OK is returned with b > 0.
+// e: exclusions per row of the _EXCL variants (krs_retrieval_plan_route, which has none, plans them for 1).
 inline int check_and_plan(int variant, const void* q, int64_t ldq, const void* c, int64_t ldc, int dtype, int64_t b,
-                          int64_t n, int64_t d, int k, rplan::Plan& pl) {
+                          int64_t n, int64_t d, int k, rplan::Plan& pl, int64_t e = 1) {
   pl = rplan::Plan();
   const char* who = entry_name(variant);
   int es = dtype == KRS_BF16 ? 2 : 4;
@@ -844,7 +919,8 @@ inline int check_and_plan(int variant, const void* q, int64_t ldq, const void* c
     KRS_REQUIRE(c, "krs_topk_rows: null operand");
     d = 0;
   } else {
-    KRS_REQUIRE(variant == KRS_RETR_VARIANT_TOPK || variant == KRS_RETR_VARIANT_Q8 || variant == KRS_RETR_VARIANT_MINE,
+    KRS_REQUIRE(variant == KRS_RETR_VARIANT_TOPK || variant == KRS_RETR_VARIANT_Q8 || variant == KRS_RETR_VARIANT_MINE ||
+                    rplan::is_excl(variant),
                 "krs_retrieval_plan_route: bad variant %d", variant);
     const int64_t kmax = variant == KRS_RETR_VARIANT_MINE ? n - 1 : n;   // mining leaves the positive out
     KRS_REQUIRE(b >= 0 && n >= 1 && d >= 1, "%s: bad shape b=%lld n=%lld d=%lld", who, (long long)b, (long long)n,
@@ -855,20 +931,20 @@ inline int check_and_plan(int variant, const void* q, int64_t ldq, const void* c
       KRS_REQUIRE(rplan::fused_path(d, k), "krs_retrieval_mine: k = %d above %d or d = %lld above %d", k, kFusedMaxK,
                   (long long)d, kFusedMaxD);
     KRS_REQUIRE(ldq >= d && ldc >= d, "%s: row stride below d", who);
-    KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "%s: bad %sdtype", who, variant == KRS_RETR_VARIANT_Q8 ? "query " : "");
-    if (variant == KRS_RETR_VARIANT_Q8) {
+    const bool q8 = variant == KRS_RETR_VARIANT_Q8 || variant == KRS_RETR_VARIANT_Q8_EXCL;
+    KRS_REQUIRE(dtype == KRS_F32 || dtype == KRS_BF16, "%s: bad %sdtype", who, q8 ? "query " : "");
+    if (q8) {
       es = 1;
       if (k > kFusedMaxK)
-        return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_topk_q8: k = %d above the limit of %d (there is no slab path)", k,
-                    kFusedMaxK);
+        return fail(KRS_ERR_UNSUPPORTED, "%s: k = %d above the limit of %d (there is no slab path)", who, k, kFusedMaxK);
       if (d > kFusedMaxD)
-        return fail(KRS_ERR_UNSUPPORTED, "krs_retrieval_topk_q8: d = %lld above the limit of %d (there is no slab path)",
-                    (long long)d, kFusedMaxD);
+        return fail(KRS_ERR_UNSUPPORTED, "%s: d = %lld above the limit of %d (there is no slab path)", who, (long long)d,
+                    kFusedMaxD);
     }
     if (b == 0) return KRS_OK;
     KRS_REQUIRE(q && c, "%s: null operand", who);
   }
-  pl = rplan::plan_retrieval(make_call(variant, es, c, ldc, b, n, d, k));
+  pl = rplan::plan_retrieval(make_call(variant, es, c, ldc, b, n, d, k, e));
   if (pl.status != KRS_OK) return fail(pl.status, "%s: %s", who, pl.why);
   return KRS_OK;
 }
@@ -902,6 +978,15 @@ inline Stage1 stage1_args(const rplan::Plan& pl, const void* q, int64_t ldq, con
   }
 
 }  // namespace
+}  // namespace krs
+
+// retrieval_excl.hip (K27) is a second translation unit of everything above -- stage 1 with EXCL on, the selection, the
+// planner glue -- built with its own compiler flags, so that the kernels of the entries below compile exactly as they did
+// before it existed.  It includes this file with KRS_RETRIEVAL_NO_ENTRIES defined and records its route through
+// retrieval_set_route.
+#ifndef KRS_RETRIEVAL_NO_ENTRIES
+namespace krs {
+void retrieval_set_route(const krs_retrieval_route& route) { g_route = route; }
 }  // namespace krs
 
 extern "C" int krs_retrieval_last_route(krs_retrieval_route* route) {
@@ -1591,3 +1676,4 @@ extern "C" int krs_retrieval_ivf_ah(const void* q, int64_t ldq, const void* cent
   return rescore_launch(q, ldq, rows, ldr, idx, r, ids, dtype, b, n, d, r, k, out_scores, out_ids,
                         reinterpret_cast<uint64_t*>(ws + w.rpairs), st);
 }
+#endif  // KRS_RETRIEVAL_NO_ENTRIES

@@ -4,6 +4,8 @@
 // tests/host/retrieval_plan_check.cpp walks it under the sanitizers and krs_retrieval_plan_route answers from it without
 // a GPU.  krs_topk_rows, krs_retrieval_topk, krs_retrieval_topk_q8, krs_retrieval_mine and their *_workspace_bytes plan
 // here and launch exactly what the plan names; retrieval.hip keeps the argument checks and no shape condition.
+// krs_retrieval_topk_excl and krs_retrieval_topk_q8_excl (K27) plan here too: their parent's plan, the mask words in stage
+// 1's LDS and the sorted-list sections at the end of the workspace.
 // krs_retrieval_ivf keeps its own geometry (its work item is a (leaf, tile of pairs), its workspace holds the inversion):
 // it takes the shared constants, row_bytes / stage1_lds / vec_loads as arithmetic and plan_select, nothing more.
 // A plan guarantees (the walk asserts it):
@@ -102,6 +104,11 @@ inline int64_t select_max_grid(int64_t rows, const Select& s, int k) {
 }
 
 // ---- stage 1 ----------------------------------------------------------------------------------------------------------
+// K27: the entries that take per-query exclusion lists, and what their stage 1 adds to the LDS: one bit per (tile row,
+// candidate of the step) and one flag word, padded to 16 bytes
+constexpr int kExclMax = kSortMax;                        // longest exclusion list: one LDS sort per query row
+constexpr int kExclLdsInts = kQM * (kCB / 32) + 4;
+inline bool is_excl(int variant) { return variant == KRS_RETR_VARIANT_TOPK_EXCL || variant == KRS_RETR_VARIANT_Q8_EXCL; }
 inline bool fused_path(int64_t d, int k) { return k <= kFusedMaxK && d <= kFusedMaxD; }
 // K extent of the LDS query tile in bytes: d * es rounded up to a 32-byte K step
 inline int row_bytes(int64_t d, int es) { return (int)(cdiv(d * es, 32) * 32); }
@@ -112,9 +119,11 @@ inline bool vec_loads(int64_t d, int es, int64_t ldc, uint64_t c_addr) {
 // the dynamic LDS of stage1_body: the query tile [kQM][row_bytes + 16], the row queues [kQM][kQueue] pairs, cnt and thr
 // [kQM] ints each, then what the variant adds -- the query steps [kQM] floats (q8), the positives' ids [kQM] int64 and
 // the positives [kQM] ints (mine), the rows' pairs and queries [kQM] ints each (krs_retrieval_ivf: extra_ints = 2 * kQM)
+// K27 (the _EXCL variants): after all that, the step mask [kQM][kCB / 32] words and the step flag (kExclLdsInts ints)
 inline int64_t stage1_lds(int row_bytes, int variant, int extra_ints = 0) {
   int64_t v = (int64_t)kQM * (row_bytes + 16) + (int64_t)kQM * kQueue * 8 + 2 * kQM * 4;
-  if (variant == KRS_RETR_VARIANT_Q8) v += kQM * 4;
+  if (variant == KRS_RETR_VARIANT_Q8 || variant == KRS_RETR_VARIANT_Q8_EXCL) v += kQM * 4;
+  if (is_excl(variant)) v += kExclLdsInts * 4;
   if (variant == KRS_RETR_VARIANT_MINE) v += kQM * 8 + kQM * 4;
   return v + (int64_t)extra_ints * 4;
 }
@@ -144,6 +153,7 @@ struct Call {
   int64_t ldc = 0;
   uint64_t c_addr = 0;              // the VALUE of the candidates' address
   int64_t slab_budget = kSlabBudget;   // KRS_RETRIEVAL_SLAB_BYTES when set (read by the entry)
+  int64_t e = 0;                    // _EXCL variants: exclusions per query row, 1 <= e (above kExclMax the plan is refused)
 };
 struct Plan {
   krs_retrieval_route route = {};   // all zero ("none") when nothing is launched: b == 0 or a refused call
@@ -163,6 +173,9 @@ struct Plan {
   int64_t off_merge = 0;            // the selection's lists (fused, two-step, ROWS at 0); empty on the LDS route
   int64_t off_gemm = 0;             // two-step: krs_gemm's own workspace
   int64_t off_qq = 0, off_qstep = 0;   // q8: the quantized query rows [b, row_bytes] and their steps [b]
+  // _EXCL: the sorted exclusion rows [b, e] int32, their counts of valid entries [b] and, on the fused path, each row's
+  // cursor at the start of every slice [b, S] (all after the parent variant's sections)
+  int64_t off_xlist = 0, off_xcount = 0, off_xstart = 0;
   int64_t total = 0;
 };
 inline int64_t chunk_row0(const Plan& p, int64_t i) { return i * p.chunk_rows; }
@@ -180,6 +193,9 @@ inline Plan plan_retrieval(const Call& c) {
   krs_retrieval_route& rt = p.route;
   rt.variant = c.variant;
   rt.es = c.es;
+  const bool excl = is_excl(c.variant);
+  if (excl && c.e > kExclMax) return refuse("e above the limit of 2048 exclusions per query");
+  if (excl && c.b > kMaxGrid) return refuse("a grid exceeds 2^32 - 1 workgroups");
 
   if (c.variant == KRS_RETR_VARIANT_ROWS) {
     p.sel = plan_select(c.n, c.k);
@@ -202,10 +218,16 @@ inline Plan plan_retrieval(const Call& c) {
     p.off_lists = 0;
     p.off_merge = align256(sat_mul(sat_mul(c.b, p.sel.len), 8));
     p.total = sat_add(p.off_merge, align256(select_list_bytes(c.b, p.sel)));
-    if (c.variant == KRS_RETR_VARIANT_Q8) {
+    if (c.variant == KRS_RETR_VARIANT_Q8 || c.variant == KRS_RETR_VARIANT_Q8_EXCL) {
       p.off_qq = p.total;
       p.off_qstep = sat_add(p.off_qq, align256(sat_mul(c.b, p.row_bytes)));
       p.total = sat_add(p.off_qstep, align256(sat_mul(c.b, 4)));
+    }
+    if (excl) {
+      p.off_xlist = p.total;
+      p.off_xcount = sat_add(p.off_xlist, align256(sat_mul(sat_mul(c.b, c.e), 4)));
+      p.off_xstart = sat_add(p.off_xcount, align256(sat_mul(c.b, 4)));
+      p.total = sat_add(p.off_xstart, align256(sat_mul(sat_mul(c.b, p.S), 4)));
     }
     if (p.total == INT64_MAX) return refuse("the workspace exceeds 2^63 bytes");
     rt.kernel = KRS_RETR_FUSED;
@@ -236,6 +258,12 @@ inline Plan plan_retrieval(const Call& c) {
     p.off_merge = align256(sat_mul(sat_mul(bc, c.n), 4));
     p.off_gemm = sat_add(p.off_merge, align256(select_list_bytes(bc, p.sel)));
     p.total = sat_add(p.off_gemm, p.gemm_bytes);
+    if (excl) {
+      if (cdiv(sat_mul(bc, c.e), 256) > kMaxGrid) return refuse("a grid exceeds 2^32 - 1 workgroups");
+      p.off_xlist = p.total;
+      p.off_xcount = sat_add(p.off_xlist, align256(sat_mul(sat_mul(c.b, c.e), 4)));
+      p.total = sat_add(p.off_xcount, align256(sat_mul(c.b, 4)));
+    }
     if (p.total == INT64_MAX) return refuse("the workspace exceeds 2^63 bytes");
     rt.kernel = KRS_RETR_SLAB;
     rt.chunks = p.chunks;

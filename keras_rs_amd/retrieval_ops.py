@@ -57,10 +57,34 @@ def topk_rows(x: torch.Tensor, k: int, *, boost: torch.Tensor | None = None, boo
     return (idx, keys) if want_keys else idx
 
 
+EXCL_MAX = 2048            # most exclusions per query row (K27: a row is sorted in LDS)
+
+
+def _exclusions(exclusions: torch.Tensor, b: int, what: str) -> torch.Tensor:
+    """The [B, E] exclusion operand of K27 as the int32 rows the kernel reads (values beyond int32 become -1: ignored)."""
+    L.require_device(exclusions, f"{what} exclusions")
+    if exclusions.dim() != 2 or exclusions.shape[0] != b or exclusions.dtype.is_floating_point:
+        raise L.KrsError(f"{what}: exclusions must be an integer tensor [{b}, E], got {exclusions.dtype} "
+                         f"{tuple(exclusions.shape)}")
+    if exclusions.shape[1] > EXCL_MAX:
+        raise L.KrsError(f"{what}: {exclusions.shape[1]} exclusions per query, above the limit of {EXCL_MAX}")
+    x = exclusions.detach()
+    if x.dtype != torch.int32:
+        x = torch.where((x >= 0) & (x < 2**31), x, -1).to(torch.int32)
+    return L.rowmajor(x, f"{what} exclusions")
+
+
+def retrieval_topk_excl_workspace_bytes(b: int, n: int, d: int, k: int, dtype: torch.dtype, e: int) -> int:
+    dt = L.BF16 if dtype == torch.bfloat16 else L.F32
+    return int(L.lib().krs_retrieval_topk_excl_workspace_bytes(b, n, d, k, dt, e))
+
+
 def retrieval_topk(query: torch.Tensor, candidates: torch.Tensor, k: int, *, ids: torch.Tensor | None = None,
-                   want_scores: bool = True):
+                   want_scores: bool = True, exclusions: torch.Tensor | None = None):
     """Top-k of query [B, D] . candidates [N, D]^T per query row (one dtype, fp32 / bf16).  Returns
-    (scores [B, k] in the input dtype or None, int32 ids [B, k]); ids = ids[index] when ids (int32 [N]) is given."""
+    (scores [B, k] in the input dtype or None, int32 ids [B, k]); ids = ids[index] when ids (int32 [N]) is given.
+    exclusions (integers [B, E], E <= 2048, K27): candidate ROW INDICES left out of row i's result; -1 pads, values
+    outside [0, N) are ignored.  A row with fewer than k candidates left ends in id -1 / score -inf."""
     q = L.rowmajor(query, "retrieval_topk query")
     c = L.rowmajor(candidates, "retrieval_topk candidates")
     if q.dtype != c.dtype:
@@ -75,6 +99,16 @@ def retrieval_topk(query: torch.Tensor, candidates: torch.Tensor, k: int, *, ids
             raise L.KrsError("retrieval_topk: ids must be a contiguous int32 vector of one id per candidate")
     scores = torch.empty((b, k), dtype=q.dtype, device=q.device) if want_scores else None
     out_ids = torch.empty((b, k), dtype=torch.int32, device=q.device)
+    if exclusions is not None:
+        x = _exclusions(exclusions, b, "retrieval_topk")
+        e = x.shape[1]
+        ws = torch.empty(max(1, retrieval_topk_excl_workspace_bytes(b, n, d, k, q.dtype, e)), dtype=torch.uint8,
+                         device=q.device)
+        rc = L.lib().krs_retrieval_topk_excl(L.ptr(q), q.stride(0) if b else d, L.ptr(c), c.stride(0), L.ptr(ids),
+                                             L.fdtype(q), b, n, d, k, L.ptr(scores), L.ptr(out_ids), L.ptr(ws),
+                                             ws.numel(), L.stream_ptr(), L.ptr(x), x.stride(0) if b > 1 else e, e)
+        L.check(rc, "krs_retrieval_topk_excl")
+        return scores, out_ids
     ws = torch.empty(max(1, retrieval_topk_workspace_bytes(b, n, d, k, q.dtype)), dtype=torch.uint8, device=q.device)
     rc = L.lib().krs_retrieval_topk(L.ptr(q), q.stride(0) if b else d, L.ptr(c), c.stride(0),
                                     L.ptr(ids), L.fdtype(q), b, n, d,
@@ -85,7 +119,7 @@ def retrieval_topk(query: torch.Tensor, candidates: torch.Tensor, k: int, *, ids
 
 
 RETR_KERNELS = {0: None, 1: "fused", 2: "slab", 3: "rows"}               # KRS_RETR_*
-RETR_VARIANTS = {0: None, 1: "topk", 2: "q8", 3: "mine", 4: "rows"}       # KRS_RETR_VARIANT_*
+RETR_VARIANTS = {0: None, 1: "topk", 2: "q8", 3: "mine", 4: "rows", 5: "topk_excl", 6: "q8_excl"}   # KRS_RETR_VARIANT_*
 RETR_SELECTS = {0: None, 1: "lds", 2: "radix", 3: "radix_merge"}          # KRS_SELECT_*
 _VARIANT_CODES = {name: code for code, name in RETR_VARIANTS.items() if name}
 
@@ -109,7 +143,7 @@ def last_route() -> dict:
 
 def plan_route(variant: str, b: int, n: int, d: int, k: int, dtype: torch.dtype, *, ldq: int | None = None,
                ldc: int | None = None, q: int | None = 0x7F0000100000, c: int | None = 0x7E0000100000):
-    """(status, route) the entry `variant` ("topk", "q8", "mine", "rows") would have with these arguments
+    """(status, route) the entry `variant` ("topk", "q8", "mine", "rows", "topk_excl", "q8_excl") would have with these arguments
     (krs_retrieval_plan_route; needs no GPU).  q and c are addresses (ints: only nullness and alignment are read), ldq /
     ldc the row strides (default: d, or n for "rows", where b is rows, n is cols and c stands for x); route is the dict
     of last_route().  KRS_RETRIEVAL_SLAB_BYTES is honoured as the entry honours it."""
@@ -130,14 +164,19 @@ def retrieval_topk_q8_workspace_bytes(b: int, n: int, d: int, k: int) -> int:
     return int(L.lib().krs_retrieval_topk_q8_workspace_bytes(b, n, d, k))
 
 
+def retrieval_topk_q8_excl_workspace_bytes(b: int, n: int, d: int, k: int, e: int) -> int:
+    return int(L.lib().krs_retrieval_topk_q8_excl_workspace_bytes(b, n, d, k, e))
+
+
 def retrieval_topk_q8(query: torch.Tensor, cand_q: torch.Tensor, cand_step: torch.Tensor, k: int, *,
                       ids: torch.Tensor | None = None, want_scores: bool = True,
-                      err_flag: torch.Tensor | None = None):
+                      err_flag: torch.Tensor | None = None, exclusions: torch.Tensor | None = None):
     """Top-k of query [B, D] (fp32 / bf16) against the int8 index cand_q [N, D], cand_step [N] fp32 (the output of
     embedding_ops.quantize_rows): the query rows are quantized on the way in and the scores are
     (qq . cq) * cand_step * query_step (include/krs.h, K17).  Returns (scores [B, k] in the query's dtype or None, int32
     ids [B, k]); ids = ids[index] when ids (int32 [N]) is given.  err_flag (int32 [1], optional) gets
-    FLAG_NONFINITE_ROW or-ed in when a query row holds a NaN or an infinity; such a row scores +0.0 everywhere."""
+    FLAG_NONFINITE_ROW or-ed in when a query row holds a NaN or an infinity; such a row scores +0.0 everywhere.
+    exclusions: as retrieval_topk's (K27)."""
     q = L.rowmajor(query, "retrieval_topk_q8 query")
     c = L.rowmajor(cand_q, "retrieval_topk_q8 cand_q")
     L.require_device(cand_step, "retrieval_topk_q8 cand_step")
@@ -159,6 +198,17 @@ def retrieval_topk_q8(query: torch.Tensor, cand_q: torch.Tensor, cand_step: torc
             raise L.KrsError("retrieval_topk_q8: err_flag must be an int32 tensor of at least one element")
     scores = torch.empty((b, k), dtype=q.dtype, device=q.device) if want_scores else None
     out_ids = torch.empty((b, k), dtype=torch.int32, device=q.device)
+    if exclusions is not None:
+        x = _exclusions(exclusions, b, "retrieval_topk_q8")
+        e = x.shape[1]
+        ws = torch.empty(max(1, retrieval_topk_q8_excl_workspace_bytes(b, n, d, k, e)), dtype=torch.uint8,
+                         device=q.device)
+        rc = L.lib().krs_retrieval_topk_q8_excl(L.ptr(q), q.stride(0) if b > 1 else d, L.fdtype(q), L.ptr(c),
+                                                c.stride(0) if n > 1 else d, L.ptr(cand_step), L.ptr(ids), b, n, d, k,
+                                                L.ptr(scores), L.fdtype(q), L.ptr(out_ids), L.ptr(err_flag), L.ptr(ws),
+                                                ws.numel(), L.stream_ptr(), L.ptr(x), x.stride(0) if b > 1 else e, e)
+        L.check(rc, "krs_retrieval_topk_q8_excl")
+        return scores, out_ids
     ws = torch.empty(max(1, retrieval_topk_q8_workspace_bytes(b, n, d, k)), dtype=torch.uint8, device=q.device)
     rc = L.lib().krs_retrieval_topk_q8(L.ptr(q), q.stride(0) if b > 1 else d, L.fdtype(q), L.ptr(c),
                                        c.stride(0) if n > 1 else d, L.ptr(cand_step), L.ptr(ids), b, n, d, k,

@@ -3,6 +3,7 @@ lists of 5 movies per user, trained once pointwise with MeanSquaredError (K24) a
 PairwiseHingeLoss (K9); both are evaluated with NDCG(k=5) (K10), the comparison the reference's file makes.
 
     python examples/listwise_ranking.py         # trains both models on synthetic lists (needs an MI355X)
+    python examples/listwise_ranking.py --lambda-weights   # the pairwise run weighs its pairs by NDCGLambdaWeight(topn=5) (K28)
 
 y_true and y_pred are [batch, 5]: MeanSquaredError takes the mean over the list as its last axis, which is what Keras
 does with the reference's lists.
@@ -20,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import keras_rs_amd.layers as kl  # noqa: E402
 from basic_ranking import RankingModel  # noqa: E402
-from keras_rs_amd.losses import PairwiseHingeLoss  # noqa: E402
+from keras_rs_amd.losses import NDCGLambdaWeight, PairwiseHingeLoss  # noqa: E402
 from keras_rs_amd.metrics import NDCG  # noqa: E402
 from keras_rs_amd.optim import Adagrad  # noqa: E402
 
@@ -71,16 +72,22 @@ def train(loss_fn, data, test, num_users, num_movies, embedding_dim, epochs, bat
 
 
 def main(epochs: int = 3, lists: int = 4096, batch: int = 512, num_users: int = 300, num_movies: int = 200,
-         embedding_dim: int = 32, learning_rate: float = 0.1, quiet: bool = False) -> dict:
+         embedding_dim: int = 32, learning_rate: float = 0.1, quiet: bool = False, lambda_weights: bool = False) -> dict:
     dev = torch.device("cuda", torch.cuda.current_device())
     held_out = max(batch, lists // 4)
     user, movie, rating = synthetic_lists(lists + held_out, num_users, num_movies, dev)
     data = (user[:lists], movie[:lists], rating[:lists])
     test = (user[lists:], movie[lists:], rating[lists:])       # other lists of the same users and movies
     args = (data, test, num_users, num_movies, embedding_dim, epochs, batch, learning_rate, dev)
+    # (lambda weights: every pair weighted by the change of the metric the run is evaluated with, NDCG@5)
+    hinge = PairwiseHingeLoss(lambda_weights=NDCGLambdaWeight(topn=LIST)) if lambda_weights else PairwiseHingeLoss()
     return {"mse": train(kl.MeanSquaredError(), *args, "MeanSquaredError", quiet),
-            "hinge": train(PairwiseHingeLoss(), *args, "PairwiseHingeLoss", quiet)}
+            "hinge": train(hinge, *args, "PairwiseHingeLoss" + (" + NDCGLambdaWeight" if lambda_weights else ""), quiet)}
 
 
 if __name__ == "__main__":
-    main()
+    import argparse
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lambda-weights", action="store_true", help="train the pairwise run with NDCGLambdaWeight(topn=5)")
+    main(lambda_weights=ap.parse_args().lambda_weights)

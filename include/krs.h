@@ -961,6 +961,36 @@ int krs_listmle_loss(const void* logits, int64_t ld, int dtype, const float* lab
                      float* list_loss, void* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * K28  LambdaRank pair weights on the pairwise losses (TF-Ranking's DCGLambdaWeight.pair_weights; the reference's
+ * pairwise_loss.py leaves them as a TODO)
+ *
+ * The operands, phi of `kind`, the validity rule, g / g_scale, the temperature and the NULL-output rule are K9's
+ * krs_pairwise_loss; KRS_RANK_MSE is refused.  Per list, V = the valid items:
+ *   rank r_i in 1..|V|: the valid items by score descending, ties to the lower index; the score is the stored fp32 /
+ *     bf16 value compared exactly (the order of K8 and K10: -0 == +0).  Invalid items have no rank and form no pairs.
+ *   G_i = gain[i] (gain [batch, list] fp32, contiguous; NULL = 2^y - 1, K10's default).
+ *   D(r), r = 1.., = discount[r - 1] (fp32, discount_len entries; NULL = 1 / log2(1 + r), K10's default).
+ *   topn >= 1 (0 = list);  D_cut(r) = D(r) for r <= topn, else 0.
+ *   normalized != 0:  Z = sum_{r = 1 .. min(topn, |V|)} G_(r) D(r), G_(r) the valid gains in descending order;
+ *     G_i <- G_i / Z, or 0 when Z <= 0.
+ *   sigma = smooth_fraction in [0, 1];  R(d) = |D(d) - D(d + 1)| for d >= 1 (the uncut table), R(0) = 0.
+ *   lambda_ij = |G_i - G_j| ((1 - sigma) |D_cut(r_i) - D_cut(r_j)| + sigma R(|r_i - r_j|)) [min(r_i, r_j) <= topn]
+ * A discount table needs discount_len >= list, and >= list + 1 when sigma > 0.
+ *
+ *   item_loss_k = sum_j I(y_k > y_j) lambda_kj phi((s_k - s_j) * inv_temperature)
+ *   dlogits     = d(sum_k g_k item_loss_k) / ds with lambda held constant: K9's gradient with w_kj lambda_kj for w_kj.
+ *
+ * KRS_ERR_INVALID with a message: KRS_RANK_MSE, list > KRS_RANK_MAX_LIST, a short discount table, smooth_fraction
+ * outside [0, 1].  fp32 arithmetic in a fixed order, one owner per output, no atomics: bit-identical from call to
+ * call; no host synchronisation, no workspace.
+ * ------------------------------------------------------------------------- */
+int krs_pairwise_lambda_loss(int kind, const void* logits, int64_t ld, int dtype, const float* labels,
+                             const uint8_t* mask, const float* gain, const float* discount, int64_t discount_len,
+                             int64_t topn, int normalized, float smooth_fraction, const float* g, float g_scale,
+                             float inv_temperature, int64_t batch, int64_t list, float* item_loss, void* dlogits,
+                             void* stream);
+
+/* ------------------------------------------------------------------------- *
  * K10  Ranking metrics (keras_rs.metrics): one sort of each list in LDS, up to KRS_METRIC_MAX_SPECS metrics from it
  *
  * scores [batch, list] fp32 / bf16 with row stride ld; labels, gain (NULL = 2^y - 1) [batch, list] fp32 and mask

@@ -1,5 +1,6 @@
 """keras_rs.losses on MI355X: the pairwise ranking losses and ListMLE (keras_rs/src/losses/), unreduced loss and
-logit gradient from one pass over each list (K9, csrc/ranking_loss.hip).
+logit gradient from one pass over each list (K9, csrc/ranking_loss.hip), and LambdaRank's pair weights for the
+pairwise losses (DCGLambdaWeight, NDCGLambdaWeight, PrecisionLambdaWeight; K28, csrc/ranking_lambda.hip).
 
 The classes are plain callables like layers.BinaryCrossentropy: loss(y_true, y_pred, sample_weight=None).
 
@@ -28,13 +29,87 @@ from __future__ import annotations
 
 import abc
 import re
-from typing import Any
+from typing import Any, Callable
 
 import torch
 
-from keras_rs_amd.ranking_ops import RankingLossFn
+from keras_rs_amd.ranking_ops import LambdaWeight, RankingLossFn
 
 REDUCTIONS = ("sum", "sum_over_batch_size", "mean", "mean_with_sample_weight", "none", None)
+
+
+class DCGLambdaWeight:
+    """LambdaRank's pair weight (TF-Ranking's DCGLambdaWeight) for `lambda_weights=` of the pairwise hinge, logistic
+    and soft zero-one losses: the pair (i, j) weighs
+        |G_i - G_j| ((1 - smooth_fraction) |D_cut(r_i) - D_cut(r_j)| + smooth_fraction |D(d) - D(d + 1)|),
+    d = |r_i - r_j|, r the rank by score (ties to the lower index; TF-Ranking shuffles them), D_cut = D up to rank
+    `topn` and 0 beyond, and 0 when both ranks lie beyond `topn`.  G = 2^y - 1 and D(r) = 1 / log2(1 + r) unless
+    `gain_fn` / `rank_discount_fn` replace them; `normalized` divides G by the list's ideal DCG at `topn`.  The weight
+    is a constant under differentiation.  Ranks, weights and pairs stay in LDS (K28, csrc/ranking_lambda.hip).
+
+    A callable is evaluated once per call with torch, gain_fn on the labels and rank_discount_fn on the ranks
+    1 .. list + 1 (fp32 tensors), and reaches the kernel as a tensor."""
+
+    def __init__(self, topn: int | None = None, gain_fn: Callable | None = None,
+                 rank_discount_fn: Callable | None = None, normalized: bool = False, smooth_fraction: float = 0.0):
+        if topn is not None and (int(topn) != topn or topn < 1):
+            raise ValueError(f"`topn` should be None or a positive integer. Received: `topn` = {topn}.")
+        if not 0.0 <= smooth_fraction <= 1.0:
+            raise ValueError(f"`smooth_fraction` should be in [0, 1]. Received: `smooth_fraction` = {smooth_fraction}.")
+        for fn, arg in ((gain_fn, "gain_fn"), (rank_discount_fn, "rank_discount_fn")):
+            if fn is not None and not callable(fn):
+                raise ValueError(f"`{arg}` should be None or a callable. Received: {fn!r}")
+        self.topn = None if topn is None else int(topn)
+        self.gain_fn, self.rank_discount_fn = gain_fn, rank_discount_fn
+        self.normalized, self.smooth_fraction = bool(normalized), float(smooth_fraction)
+
+    def operands(self, labels: torch.Tensor) -> LambdaWeight:
+        """What the kernel reads for labels [batch, list]."""
+        n = labels.shape[1]
+        gain = None if self.gain_fn is None else self.gain_fn(labels.to(torch.float32))
+        disc = None
+        if self.rank_discount_fn is not None:
+            disc = self.rank_discount_fn(torch.arange(1, n + 2, device=labels.device, dtype=torch.float32))
+        return LambdaWeight(gain, disc, self.topn or 0, self.normalized, self.smooth_fraction)
+
+    def get_config(self) -> dict:
+        for fn, arg in ((self.gain_fn, "gain_fn"), (self.rank_discount_fn, "rank_discount_fn")):
+            if fn is not None:
+                raise ValueError(f"{type(self).__name__}: a callable `{arg}` cannot be serialized")
+        return {"topn": self.topn, "normalized": self.normalized, "smooth_fraction": self.smooth_fraction}
+
+    @classmethod
+    def from_config(cls, config: dict):
+        return cls(**config)
+
+
+class NDCGLambdaWeight(DCGLambdaWeight):
+    """DCGLambdaWeight with normalized=True: the pair weight is the change of NDCG@topn under the swap."""
+
+    def __init__(self, topn: int | None = None, gain_fn: Callable | None = None,
+                 rank_discount_fn: Callable | None = None, normalized: bool = True, smooth_fraction: float = 0.0):
+        super().__init__(topn, gain_fn, rank_discount_fn, normalized, smooth_fraction)
+
+
+class PrecisionLambdaWeight(DCGLambdaWeight):
+    """TF-Ranking's PrecisionLambdaWeight on the same kernel: a pair weighs 1 when exactly one of its items is
+    positive (`positive_fn`, default y >= 1) and exactly one of its ranks is within `topn`: gain I(positive), table
+    I(r <= topn)."""
+
+    def __init__(self, topn: int, positive_fn: Callable | None = None):
+        if topn is None:
+            raise ValueError("`topn` is required by PrecisionLambdaWeight")
+        positive = positive_fn or (lambda y: y >= 1.0)
+        super().__init__(topn, lambda y: positive(y).to(torch.float32), lambda r: (r <= topn).to(torch.float32))
+        self.positive_fn = positive_fn
+
+    def get_config(self) -> dict:
+        if self.positive_fn is not None:
+            raise ValueError("PrecisionLambdaWeight: a callable `positive_fn` cannot be serialized")
+        return {"topn": self.topn}
+
+
+_LAMBDA_WEIGHTS = {c.__name__: c for c in (DCGLambdaWeight, NDCGLambdaWeight, PrecisionLambdaWeight)}
 
 
 def _snake(name: str) -> str:
@@ -99,9 +174,10 @@ def _sample_weight(sample_weight, shape, device) -> torch.Tensor | None:
 
 class _RankingLoss(abc.ABC):
     _kind = ""
+    _takes_lambda_weights = False
 
     def __init__(self, temperature: float = 1.0, reduction: str | None = "sum_over_batch_size",
-                 name: str | None = None, dtype: Any = None):
+                 name: str | None = None, dtype: Any = None, lambda_weights: DCGLambdaWeight | dict | None = None):
         if temperature <= 0.0:
             raise ValueError(f"`temperature` should be a positive float. Received: `temperature` = {temperature}.")
         if reduction not in REDUCTIONS:
@@ -112,6 +188,15 @@ class _RankingLoss(abc.ABC):
         self.temperature = float(temperature)
         self.reduction = reduction
         self.name = name or _snake(type(self).__name__)
+        if isinstance(lambda_weights, dict):          # (get_config's form)
+            lambda_weights = _LAMBDA_WEIGHTS[lambda_weights["class_name"]].from_config(lambda_weights["config"])
+        if lambda_weights is not None and not self._takes_lambda_weights:
+            raise NotImplementedError(f"{type(self).__name__}: `lambda_weights` is not supported (the hinge, logistic "
+                                      "and soft zero-one pairwise losses take it)")
+        if lambda_weights is not None and not isinstance(lambda_weights, DCGLambdaWeight):
+            raise ValueError("`lambda_weights` should be None, a DCGLambdaWeight, an NDCGLambdaWeight or a "
+                             f"PrecisionLambdaWeight. Received: {lambda_weights!r}")
+        self.lambda_weights = lambda_weights
 
     def _unreduced_shape(self, b: int, n: int):
         return (b,) if self._kind == "listmle" else (b, n)
@@ -121,10 +206,17 @@ class _RankingLoss(abc.ABC):
         w = _sample_weight(sample_weight, self._unreduced_shape(*logits.shape), logits.device)
         reduction = "none" if self.reduction is None else self.reduction
         inv_t = 1.0 if self._kind == "mse" else 1.0 / self.temperature
-        return RankingLossFn.apply(logits, labels, mask, w, self._kind, inv_t, reduction)
+        if self.lambda_weights is None:
+            return RankingLossFn.apply(logits, labels, mask, w, self._kind, inv_t, reduction)
+        return RankingLossFn.apply(logits, labels, mask, w, self._kind, inv_t, reduction,
+                                   self.lambda_weights.operands(labels))
 
     def get_config(self) -> dict:
-        return {"name": self.name, "reduction": self.reduction, "dtype": "float32", "temperature": self.temperature}
+        config = {"name": self.name, "reduction": self.reduction, "dtype": "float32", "temperature": self.temperature}
+        if self.lambda_weights is not None:
+            config["lambda_weights"] = {"class_name": type(self.lambda_weights).__name__,
+                                        "config": self.lambda_weights.get_config()}
+        return config
 
     @classmethod
     def from_config(cls, config: dict):
@@ -133,7 +225,9 @@ class _RankingLoss(abc.ABC):
 
 class PairwiseLoss(_RankingLoss):
     """Base of the pairwise ranking losses (pairwise_loss.py): per item i, sum_j I(y_i > y_j) valid_i valid_j
-    loss(x_ij), x_ij = (s_i - s_j) / temperature; unreduced shape [batch, list]."""
+    loss(x_ij), x_ij = (s_i - s_j) / temperature; unreduced shape [batch, list].  `lambda_weights` (a DCGLambdaWeight,
+    NDCGLambdaWeight or PrecisionLambdaWeight; hinge, logistic and soft zero-one) multiplies every pair by LambdaRank's
+    weight on K28; None is the constant weight, on K9."""
 
     @abc.abstractmethod
     def _pair_formula(self) -> str:
@@ -143,6 +237,7 @@ class PairwiseLoss(_RankingLoss):
 class PairwiseHingeLoss(PairwiseLoss):
     """keras_rs.losses.PairwiseHingeLoss: per pair relu(1 - x).  Gradient 0 at x == 1."""
     _kind = "hinge"
+    _takes_lambda_weights = True
 
     def _pair_formula(self) -> str:
         return "relu(1 - x)"
@@ -151,6 +246,7 @@ class PairwiseHingeLoss(PairwiseLoss):
 class PairwiseLogisticLoss(PairwiseLoss):
     """keras_rs.losses.PairwiseLogisticLoss: per pair relu(-x) + log(1 + exp(-|x|)).  Gradient 0 at a score tie."""
     _kind = "logistic"
+    _takes_lambda_weights = True
 
     def _pair_formula(self) -> str:
         return "relu(-x) + log(1 + exp(-|x|))"
@@ -159,6 +255,7 @@ class PairwiseLogisticLoss(PairwiseLoss):
 class PairwiseSoftZeroOneLoss(PairwiseLoss):
     """keras_rs.losses.PairwiseSoftZeroOneLoss: per pair where(x > 0, 1 - sigmoid(x), sigmoid(-x))."""
     _kind = "soft_zero_one"
+    _takes_lambda_weights = True
 
     def _pair_formula(self) -> str:
         return "where(x > 0, 1 - sigmoid(x), sigmoid(-x))"
@@ -183,5 +280,5 @@ class ListMLELoss(_RankingLoss):
     _kind = "listmle"
 
 
-__all__ = ["ListMLELoss", "PairwiseHingeLoss", "PairwiseLogisticLoss", "PairwiseLoss", "PairwiseMeanSquaredError",
-           "PairwiseSoftZeroOneLoss"]
+__all__ = ["DCGLambdaWeight", "ListMLELoss", "NDCGLambdaWeight", "PairwiseHingeLoss", "PairwiseLogisticLoss", "PairwiseLoss", "PairwiseMeanSquaredError",
+           "PairwiseSoftZeroOneLoss", "PrecisionLambdaWeight"]

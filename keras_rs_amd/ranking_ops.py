@@ -1,4 +1,5 @@
-"""Host side of K9: thin torch wrappers over krs_pairwise_loss and krs_listmle_loss (include/krs.h).
+"""Host side of K9 and K28: thin torch wrappers over krs_pairwise_loss, krs_pairwise_lambda_loss and krs_listmle_loss
+(include/krs.h).
 
 Both run on the current stream and never wait for the device, so forward and backward can be captured in a HIP
 graph.  Each returns (unreduced loss or None, dL/dlogits or None).
@@ -6,12 +7,23 @@ graph.  Each returns (unreduced loss or None, dL/dlogits or None).
 
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from keras_rs_amd import _lib as L
 
 MAX_LIST = L.MAX_LIST
 PAIRWISE_KINDS = {"hinge": 0, "logistic": 1, "soft_zero_one": 2, "mse": 3}   # krs_rank_loss
+
+
+class LambdaWeight(NamedTuple):
+    """The LambdaRank pair weight of one call as krs_pairwise_lambda_loss reads it (losses.DCGLambdaWeight builds it)."""
+    gain: torch.Tensor | None = None        # [B, L]; None = 2^y - 1
+    discount: torch.Tensor | None = None    # [>= L, or L + 1 with smooth_fraction > 0], D(1), D(2), ..; None = 1 / log2(1 + r)
+    topn: int = 0                           # 0 = the whole list
+    normalized: bool = False
+    smooth_fraction: float = 0.0
 
 
 def _operands(logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor | None, what: str):
@@ -34,14 +46,26 @@ def _weights(g: torch.Tensor | None, shape, device) -> torch.Tensor | None:
 
 def pairwise_loss(kind: str, logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor | None = None, *,
                   inv_temperature: float = 1.0, g: torch.Tensor | None = None, g_scale: float = 1.0,
-                  want_loss: bool = True, want_grad: bool = True):
+                  want_loss: bool = True, want_grad: bool = True, lambda_weight: LambdaWeight | None = None):
     """Per-item pairwise loss [B, L] fp32 and d(sum g * loss)/dlogits [B, L] in logits' dtype (g = g_scale * g,
-    g broadcast to [B, L]).  kind: one of PAIRWISE_KINDS."""
+    g broadcast to [B, L]).  kind: one of PAIRWISE_KINDS.  lambda_weight: every pair weighted by LambdaRank's
+    lambda (K28); None is K9's constant weight."""
     x, ld, y, m = _operands(logits, labels, mask, "pairwise_loss")
     b, n = x.shape
     gw = _weights(g, (b, n), x.device)
     loss = torch.empty((b, n), dtype=torch.float32, device=x.device) if want_loss else None
     dx = torch.empty((b, n), dtype=x.dtype, device=x.device) if want_grad else None
+    if lambda_weight is not None:
+        lw = lambda_weight
+        gain = None if lw.gain is None else _weights(lw.gain, (b, n), x.device)
+        disc = None if lw.discount is None else lw.discount.to(device=x.device, dtype=torch.float32).contiguous()
+        rc = L.lib().krs_pairwise_lambda_loss(PAIRWISE_KINDS[kind], L.ptr(x), ld, L.fdtype(x), L.ptr(y), L.ptr(m),
+                                              L.ptr(gain), L.ptr(disc), 0 if disc is None else disc.numel(),
+                                              int(lw.topn), int(bool(lw.normalized)), float(lw.smooth_fraction),
+                                              L.ptr(gw), g_scale, inv_temperature, b, n, L.ptr(loss), L.ptr(dx),
+                                              L.stream_ptr())
+        L.check(rc, "krs_pairwise_lambda_loss")
+        return loss, dx
     rc = L.lib().krs_pairwise_loss(PAIRWISE_KINDS[kind], L.ptr(x), ld, L.fdtype(x), L.ptr(y), L.ptr(m), L.ptr(gw),
                                    g_scale, inv_temperature, b, n, L.ptr(loss), L.ptr(dx), L.stream_ptr())
     L.check(rc, "krs_pairwise_loss")
@@ -77,14 +101,17 @@ class RankingLossFn(torch.autograd.Function):
 
     Scalar reductions: the forward knows every item's share g = weight / divisor of the result and takes loss and
     gradient from ONE launch; the backward only scales that gradient by the incoming scalar.  reduction "none": the
-    forward computes the losses alone and the backward runs a second launch with g = upstream * weight."""
+    forward computes the losses alone and the backward runs a second launch with g = upstream * weight.
+
+    lam, when given (an eighth argument), is the LambdaWeight of a pairwise loss: the same scheme on K28."""
 
     @staticmethod
-    def forward(ctx, y_pred, labels, mask, weight, kind, inv_t, reduction):
-        ctx.meta = (kind, inv_t, reduction)
+    def forward(ctx, y_pred, labels, mask, weight, kind, inv_t, reduction, *lam):
+        kw = {"lambda_weight": lam[0]} if lam and lam[0] is not None else {}
+        ctx.meta = (kind, inv_t, reduction, kw, (None,) * len(lam))
         want_grad = ctx.needs_input_grad[0]
         if reduction == "none":
-            v, _ = ranking_loss(kind, y_pred, labels, mask, inv_temperature=inv_t, want_grad=False)
+            v, _ = ranking_loss(kind, y_pred, labels, mask, inv_temperature=inv_t, want_grad=False, **kw)
             ctx.save_for_backward(y_pred, labels, mask, weight)
             return v if weight is None else v * weight
         shape = (y_pred.shape[0],) if kind == "listmle" else tuple(y_pred.shape)
@@ -96,19 +123,19 @@ class RankingLossFn(torch.autograd.Function):
         elif reduction != "sum":
             scale = 1.0 / numel if numel else 0.0
         v, dx = ranking_loss(kind, y_pred, labels, mask, inv_temperature=inv_t, g=g, g_scale=scale,
-                             want_grad=want_grad)
+                             want_grad=want_grad, **kw)
         ctx.save_for_backward(dx)
         return (v.sum() if g is None else (v * g).sum()) * scale
 
     @staticmethod
     def backward(ctx, up):
-        kind, inv_t, reduction = ctx.meta
+        kind, inv_t, reduction, kw, extra = ctx.meta
         if reduction != "none":
             (dx,) = ctx.saved_tensors
-            return dx * up.to(dx.dtype), None, None, None, None, None, None
+            return (dx * up.to(dx.dtype), None, None, None, None, None, None) + extra
         y_pred, labels, mask, weight = ctx.saved_tensors
         g = up.to(torch.float32)
         if weight is not None:
             g = g * weight
-        _, dx = ranking_loss(kind, y_pred, labels, mask, inv_temperature=inv_t, g=g, want_loss=False)
-        return dx, None, None, None, None, None, None
+        _, dx = ranking_loss(kind, y_pred, labels, mask, inv_temperature=inv_t, g=g, want_loss=False, **kw)
+        return (dx, None, None, None, None, None, None) + extra

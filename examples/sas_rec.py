@@ -6,9 +6,11 @@ are K22 (one fused kernel each), a final layer norm with epsilon 1e-8 (K22 too),
 item table for serving, on the last non-padding token.
 
 Training follows the reference's compute_loss: positive and negative logits are row dot products of the sequence
-embedding with the embedded positive / negative items, and the loss is the sample-weighted mean of the binary
-cross-entropy with logits over the [B, 2 L] logits (a few element-wise torch ops).  The reference's L2 regulariser on
-the item embeddings (0.001) is left out.  Sequences are synthetic (numpy.random.default_rng): every user walks the
+embedding with the positive / negative items' rows, and the loss is the sample-weighted mean of the binary
+cross-entropy with logits over the [B, 2 L] logits.  layers.SampledItemCrossentropy (K29) does all of it in one
+kernel that gathers every row once and stores neither the embedded items nor the logits; --stored puts the torch
+composition back (two lookups, three fp32 blocks, a dozen element-wise launches), and --negatives N draws N negatives
+per position instead of one.  The reference's L2 regulariser on the item embeddings (0.001) is left out.  Sequences are synthetic (numpy.random.default_rng): every user walks the
 item ids by a fixed map with a few random restarts, left-padded with item 0; nothing is downloaded.
 
     python examples/sas_rec.py --steps 30 --dtype bf16
@@ -25,13 +27,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from keras_rs_amd import layers as kl              # noqa: E402
 from keras_rs_amd.layers import base               # noqa: E402
+from keras_rs_amd.layers.losses import sampled_item_crossentropy_stored   # noqa: E402
 
 PAD_ITEM_ID = 0
 
 
-def synthetic_sequences(users: int, vocabulary_size: int, length: int, seed: int = 0):
+def synthetic_sequences(users: int, vocabulary_size: int, length: int, seed: int = 0, negatives: int = 1):
     """item_ids, positive, negative [users, length] int32 and padding_mask [users, length] bool (True = a real token);
-    sequences are left-padded.  The next item is (7 * item + 3) mod (V - 1) + 1, with a random restart now and then."""
+    sequences are left-padded.  negatives > 1: negative is [users, length, negatives].  The next item is (7 * item + 3) mod (V - 1) + 1, with a random restart now and then."""
     rng = np.random.default_rng(seed)
     v = vocabulary_size
     full = np.zeros((users, length + 1), dtype=np.int64)
@@ -49,6 +52,11 @@ def synthetic_sequences(users: int, vocabulary_size: int, length: int, seed: int
     negative = np.where(negative == positive, negative % (v - 1) + 1, negative)
     positive = np.where(padding_mask, positive, PAD_ITEM_ID)
     negative = np.where(padding_mask, negative, PAD_ITEM_ID)
+    if negatives > 1:        # (the first negative is the one a single-negative run draws)
+        more = rng.integers(1, v, positive.shape + (negatives - 1,))
+        more = np.where(more == positive[..., None], more % (v - 1) + 1, more)
+        more = np.where(padding_mask[..., None], more, PAD_ITEM_ID)
+        negative = np.concatenate([negative[..., None], more], axis=-1)
     return (item_ids.astype(np.int32), positive.astype(np.int32), negative.astype(np.int32), padding_mask)
 
 
@@ -71,6 +79,8 @@ class SasRec(base.Layer):
         self.layer_norm = kl.LayerNormalization(1e-8, name="layer_norm", **sub)
         self.retrieval = kl.BruteForceRetrieval(k=k, return_scores=False, device=self._device)
         self.exclude_history = False       # serve and evaluate without the items of the input sequence
+        self.loss = kl.SampledItemCrossentropy()
+        self.stored_loss = False           # True: the torch composition instead of the fused loss (K29)
         self.built = True
 
     def sequence_embedding(self, item_ids, padding_mask, training: bool = False):
@@ -105,28 +115,22 @@ class SasRec(base.Layer):
         return result
 
     def compute_loss(self, y, y_pred, sample_weight):
-        emb = y_pred["item_sequence_embedding"].float()
-        pos = self.item_embedding(y["positive_sequence"]).float()
-        neg = self.item_embedding(y["negative_sequence"]).float()
-        logits = torch.cat([(pos * emb).sum(-1), (neg * emb).sum(-1)], dim=1)                    # [B, 2 L]
-        half = logits.shape[1] // 2
-        labels = torch.cat([torch.ones_like(logits[:, :half]), torch.zeros_like(logits[:, half:])], dim=1)
-        weight = torch.cat([sample_weight, sample_weight], dim=1).float()
-        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, labels, reduction="none") * weight
-        total = weight.sum()
-        return torch.where(total > 0, loss.sum() / total.clamp_min(1e-30), torch.zeros_like(total))
+        args = (self.item_embedding, y_pred["item_sequence_embedding"], y["positive_sequence"], y["negative_sequence"],
+                sample_weight)
+        return sampled_item_crossentropy_stored(*args) if self.stored_loss else self.loss(*args)
 
 
 def main(steps: int = 30, batch: int = 64, vocabulary_size: int = 500, length: int = 50, hidden_dim: int = 50,
          num_heads: int = 1, num_layers: int = 2, dropout: float = 0.2, dtype: str = "bf16", lr: float = 0.005,
-         seed: int = 0, quiet: bool = False, exclude_history: bool = False):
+         seed: int = 0, quiet: bool = False, exclude_history: bool = False, stored: bool = False, negatives: int = 1):
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(seed)
     policy = {"bf16": "mixed_bfloat16", "fp32": "float32"}[dtype]
     model = SasRec(vocabulary_size, num_layers, num_heads, hidden_dim, dropout=dropout, max_sequence_length=length,
                    seed=seed, dtype=policy, device=dev)
+    model.stored_loss = stored
     item_ids, positive, negative, mask = (torch.from_numpy(a).to(dev) for a in
-                                          synthetic_sequences(batch, vocabulary_size, length, seed))
+                                          synthetic_sequences(batch, vocabulary_size, length, seed, negatives))
     inputs = {"item_ids": item_ids, "padding_mask": mask}
     y = {"positive_sequence": positive, "negative_sequence": negative}
     model(inputs, training=True)                                                                  # (builds every weight)
@@ -160,6 +164,10 @@ if __name__ == "__main__":
     ap.add_argument("--vocabulary", type=int, default=500)
     ap.add_argument("--exclude-history", action="store_true",
                     help="leave each user's input sequence out of the served top-k (K27)")
+    ap.add_argument("--stored", action="store_true",
+                    help="compute the loss with the stored torch composition instead of the fused kernel (K29)")
+    ap.add_argument("--negatives", type=int, default=1, help="sampled negatives per position")
     a = ap.parse_args()
     main(steps=a.steps, batch=a.batch, vocabulary_size=a.vocabulary, length=a.length, hidden_dim=a.hidden,
-         num_heads=a.heads, num_layers=a.layers, dtype=a.dtype, exclude_history=a.exclude_history)
+         num_heads=a.heads, num_layers=a.layers, dtype=a.dtype, exclude_history=a.exclude_history, stored=a.stored,
+         negatives=a.negatives)

@@ -1911,6 +1911,79 @@ size_t krs_vocab_export_workspace_bytes(int64_t slots);
 int krs_vocab_export(const void* table, int64_t slots, int64_t* keys, int64_t* payloads, int64_t cap,
                      int64_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * K29  Sampled-item binary cross-entropy of a sequence model (the SASRec loss: one positive and N sampled negative
+ *      items per token, scored by a dot product with the token's sequence embedding): gather, dot, BCE with logits,
+ *      the logit gradients and the gradient to the sequence embedding from ONE read of every row
+ *
+ * Operands  emb [t, d] fp32 / bf16 (emb_dtype), row stride ld_emb >= d; table [vocab, d] fp32 / bf16 (table_dtype,
+ *           independent of emb's), row stride ld_table >= d; pos [t] and neg [t, n] (contiguous) int32 / int64 (itype);
+ *           weight [t] fp32 or NULL (every w_t = 1).  0 <= t <= 2^31 - 1, 1 <= d <= KRS_SAMPLED_BCE_MAX_DIM,
+ *           0 <= n <= KRS_SAMPLED_BCE_MAX_NEGATIVES.  Item j of token t is id_t0 = pos[t], id_tj = neg[t, j - 1];
+ *           y_j = 1 for j = 0 and 0 otherwise.  t == 0 launches nothing and writes nothing (the loss of no token is 0,
+ *           the caller's to store).
+ * Logit     x_tj = emb_t . table[id_tj] in fp32.  A group of g lanes owns a token, g the smallest of 8, 16, 32, 64
+ *           with 8 * g >= d; lane l owns the columns 8l .. 8l + 7 (those >= d count as 0).  Its partial is
+ *           p = 0; p = p + e_c * r_c for its columns in column order (one rounded multiply, one rounded add); the
+ *           partials are added by a butterfly, p = p + p[lane ^ o] for o = g/2 .. 1.
+ * Element   a = |x|;  u = expf(-a);  s = 1 + u;  l = max(x, 0) - x * y + log1pf(u)   (keras' from_logits=True form;
+ *           the three terms added left to right);  sigma = x >= 0 ? 1 / s : u / s;  gr = sigma - y.
+ * Sums      S = sum_t w_t in the W pass's order (float(t) without weights);  W = float(1 + n) * S.
+ *           loss[0] = W != 0 ? (sum_t w_t * (l_t0 + l_t1 + ..)) / W : 0        (items added in item order from 0)
+ * Gradients glog [t, 1 + n] fp32 (contiguous, required): glog[t, j] = (w_t * gr_tj) / W.
+ *           demb [t, d] in emb's dtype with row stride ld_demb, or NULL (forward only):
+ *           demb[t, c] = round_to_dtype(0 + glog[t, 0] * r_0c + glog[t, 1] * r_1c + ..) in item order, each product
+ *           and each add rounded on its own.  They are the loss's gradients at unit upstream; d table is
+ *           krs_embed_bag_bwd_dense over one bag (pos, neg ..) per token with glog as the per-lookup weights and emb
+ *           as the bag gradient.
+ *           A token with w_t == 0, and every token when W == 0, requests no row and gets zeros in glog and demb (a
+ *           non-finite row under a zero weight cannot leak).  An id outside [0, vocab) ORs KRS_FLAG_ID_OUT_OF_RANGE
+ *           into err_flag (device int, optional), adds nothing to the loss, gets glog 0 and is never clamped.
+ *           Every operation above is one fp32 operation rounded on its own (the file is compiled with fp contract
+ *           off; divisions are correctly rounded), so glog and demb are pure functions of the inputs, bit for bit.
+ * Order     (fixed; no float atomics)  G = min(KRS_SAMPLED_BCE_MAX_BLOCKS, ceil(t / (KRS_SAMPLED_BCE_THREADS / g)))
+ *           workgroups; group q of workgroup b adds the tokens (b * THREADS / g + q), + G * THREADS / g, .. in that
+ *           order, from 0; the workgroup adds x[thread] (the group's sum at its first lane, 0 elsewhere) in a halving
+ *           tree (x[i] += x[i + o], o = THREADS / 2 .. 1); the G partials are added in workgroup order, by the main
+ *           kernel when G == 1 and by a finish launch otherwise.  W pass (with weights only): min(W_BLOCKS,
+ *           ceil(t / W_THREADS)) workgroups of W_THREADS threads, a grid-strided sum per thread, the same halving tree,
+ *           the partials added in workgroup order.
+ * Access    KRS_SAMPLED_BCE_VEC: d % 8 == 0, emb, table and demb on 16 bytes and their row strides multiples of 16
+ *           bytes: a lane's slice moves in 16-byte loads and stores (one for bf16, two for fp32).  KRS_SAMPLED_BCE_ELEM:
+ *           everything else, element by element.  Up to 4 item rows of a token are requested before the first dot;
+ *           the ids and the weight of a group's next token are loaded a token ahead.
+ * Launches  [W pass] + main + [finish].  No host wait, no allocation.
+ * workspace krs_sampled_bce_workspace_bytes(t) bytes on the device ((W_BLOCKS + MAX_BLOCKS) floats for t > 0, else 0),
+ *           uninitialised.  Too little is KRS_ERR_WORKSPACE.
+ * Refusals  (KRS_ERR_INVALID) d < 1 or > 512, n outside 0 .. 64, t < 0 or > 2^31 - 1, vocab < 0, a dtype or itype
+ *           outside its enum, a row stride below d, and for t > 0 a NULL emb, table, pos, glog, loss, or neg with n > 0.
+ *
+ * krs_sampled_bce_last_route: how the calling thread's last krs_sampled_bce_fwd_bwd ran (all 0 before the first call,
+ * after a refusal or for t == 0): kernel, g, blocks (G), launches.  Returns `kernel`; route may be NULL.
+ * krs_sampled_bce_plan_route: the same answer without a GPU and without touching the record; pointers are read as VALUES
+ * (nullness, alignment).  Returns what the entry returns before its first launch.
+ * ------------------------------------------------------------------------- */
+#define KRS_SAMPLED_BCE_MAX_DIM 512
+#define KRS_SAMPLED_BCE_MAX_NEGATIVES 64
+#define KRS_SAMPLED_BCE_THREADS 256
+#define KRS_SAMPLED_BCE_MAX_BLOCKS 1024
+#define KRS_SAMPLED_BCE_W_THREADS 1024
+#define KRS_SAMPLED_BCE_W_BLOCKS 64
+enum { KRS_SAMPLED_BCE_ROUTE_NONE = 0, KRS_SAMPLED_BCE_VEC = 1, KRS_SAMPLED_BCE_ELEM = 2 };
+typedef struct krs_sampled_bce_route {
+  int32_t kernel, g, blocks, launches;
+} krs_sampled_bce_route;
+size_t krs_sampled_bce_workspace_bytes(int64_t t);
+int krs_sampled_bce_fwd_bwd(const void* emb, int64_t ld_emb, int emb_dtype, const void* table, int64_t ld_table,
+                            int table_dtype, int64_t vocab, const void* pos, const void* neg, int itype,
+                            const float* weight, int64_t t, int64_t d, int64_t n, float* loss, float* glog, void* demb,
+                            int64_t ld_demb, int* err_flag, void* workspace, size_t workspace_bytes, void* stream);
+int krs_sampled_bce_last_route(krs_sampled_bce_route* route);
+int krs_sampled_bce_plan_route(const void* emb, int64_t ld_emb, int emb_dtype, const void* table, int64_t ld_table,
+                               int table_dtype, int64_t vocab, const void* pos, const void* neg, int itype,
+                               const float* weight, int64_t t, int64_t d, int64_t n, const float* glog,
+                               const void* demb, int64_t ld_demb, krs_sampled_bce_route* route);
+
 #ifdef __cplusplus
 }
 #endif

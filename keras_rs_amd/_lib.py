@@ -112,6 +112,15 @@ REG_ROUTE_NONE, REG_VEC, REG_ELEM = 0, 1, 2
 REG_MAX_BLOCKS, REG_THREADS = 256, 1024
 
 
+class SampledBceRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("kernel", "g", "blocks", "launches")]
+
+
+# krs_sampled_bce_route.kernel and the K29 limits (include/krs.h)
+SBCE_ROUTE_NONE, SBCE_VEC, SBCE_ELEM = 0, 1, 2
+SBCE_MAX_DIM, SBCE_MAX_NEGATIVES, SBCE_THREADS, SBCE_MAX_BLOCKS = 512, 64, 256, 1024
+
+
 class VocabRoute(C.Structure):
     _fields_ = [(name, C.c_int32) for name in ("route", "ids_per_lane", "vec", "lds_bytes")] + \
                [(name, C.c_int64) for name in ("slots", "blocks")]
@@ -273,6 +282,12 @@ PROTOTYPES = {
     "krs_vocab_plan_route": (_I, [_P, _I64, _P, _I, _I64, _I, _P, _I, _I, _I, _P]),
     "krs_vocab_export_workspace_bytes": (_SZ, [_I64]),
     "krs_vocab_export": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _SZ, _P]),
+    "krs_sampled_bce_workspace_bytes": (_SZ, [_I64]),
+    "krs_sampled_bce_fwd_bwd": (_I, [_P, _I64, _I, _P, _I64, _I, _I64, _P, _P, _I, _P, _I64, _I64, _I64, _P, _P, _P, _I64,
+                                     _P, _P, _SZ, _P]),
+    "krs_sampled_bce_last_route": (_I, [_P]),
+    "krs_sampled_bce_plan_route": (_I, [_P, _I64, _I, _P, _I64, _I, _I64, _P, _P, _I, _P, _I64, _I64, _I64, _P, _P, _I64,
+                                        _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -39,8 +39,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # (embed_bag_bwd.hip, the K2 apply kernels: ~590 instantiations -- four objects compiled side by side, see KRS_BWD_PART
         #  there; their plan is embed_bag_plan.hip, one object like every other source)
         parts = [(f"_p{i}", [f"-DKRS_BWD_PART={i}"]) for i in range(4)] if s == "embed_bag_bwd.hip" else [("", [])]
-        if s in ("lstm.hip", "vocab.hip", "ranking_lambda.hip"):   # (K25's gate arithmetic is one scalar fp32 operation
-            # per register, K26 is integer work, K28's pair walk is scalar fp32 per lane: no packed fp32)
+        if s in ("lstm.hip", "vocab.hip", "ranking_lambda.hip", "sampled_bce.hip"):   # (K25's gate arithmetic is one
+            # scalar fp32 operation per register, K26 is integer work, K28's pair walk and K29's dot, BCE and demb chains
+            # are scalar fp32 per lane in a pinned order: no packed fp32)
             parts = [("", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
         deps = [src]
         if s == "retrieval_excl.hip":        # (K27: a second translation unit of retrieval.hip, which it includes, so

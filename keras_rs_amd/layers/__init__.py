@@ -9,7 +9,8 @@ from keras_rs_amd.layers.embed_reduce import EmbedReduce, Embedding, Ragged
 from keras_rs_amd.layers.feature_cross import FeatureCross
 from keras_rs_amd.layers.lookup import IntegerLookup, StringLookup
 from keras_rs_amd.layers.losses import (BinaryCrossentropy, CategoricalCrossentropy, Huber, MeanAbsoluteError,
-                                        MeanSquaredError, SparseCategoricalCrossentropy, binary_crossentropy)
+                                        MeanSquaredError, SampledItemCrossentropy, SparseCategoricalCrossentropy,
+                                        binary_crossentropy)
 # (keras keeps the two MeanSquaredError / MeanAbsoluteError in keras.losses and keras.metrics; here the bare names are the
 #  losses and the metrics carry a suffix -- keras_rs_amd.layers.metrics has them under keras' names)
 from keras_rs_amd.layers.metrics import (AUC, BinaryAccuracy, BinaryMetricGroup, RegressionMetricGroup,
@@ -23,5 +24,5 @@ from keras_rs_amd.layers.retrieval import (AsymmetricHashingRetrieval, BruteForc
 from keras_rs_amd.layers.sequence import LayerNormalization, MultiHeadAttention, TransformerDecoder
 
 __all__ = ["AUC", "Adagrad", "Adam", "AsymmetricHashingRetrieval", "BinaryAccuracy", "BinaryCrossentropy", "BinaryMetricGroup", "auc_from_confusion", "binary_crossentropy", "BruteForceRetrieval", "CategoricalCrossentropy", "Dense", "DistributedEmbedding", "DotInteraction", "EmbedReduce", "Embedding", "FeatureConfig",
-           "FactorizedTopK", "FeatureCross", "Ftrl", "GRU", "HardNegativeMining", "Huber", "MeanAbsoluteError", "MeanAbsoluteErrorMetric", "MeanSquaredError", "MeanSquaredErrorMetric", "RegressionMetricGroup", "RootMeanSquaredError", "InBatchSoftmaxLoss", "IntegerLookup", "LSTM", "LayerNormalization", "MultiHeadAttention", "PartitionedRetrieval", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SamplingProbabilityCorrection",
+           "FactorizedTopK", "FeatureCross", "Ftrl", "GRU", "HardNegativeMining", "Huber", "MeanAbsoluteError", "MeanAbsoluteErrorMetric", "MeanSquaredError", "MeanSquaredErrorMetric", "RegressionMetricGroup", "RootMeanSquaredError", "InBatchSoftmaxLoss", "IntegerLookup", "LSTM", "LayerNormalization", "MultiHeadAttention", "PartitionedRetrieval", "Ragged", "RemoveAccidentalHits", "Retrieval", "RowwiseAdagrad", "SGD", "SampledItemCrossentropy", "SamplingProbabilityCorrection",
            "SparseCategoricalCrossentropy", "SparseTopKCategoricalAccuracy", "StringLookup", "TableConfig", "TransformerDecoder", "concat_features"]

@@ -3,16 +3,22 @@ it (examples/ml_perf/main.py:201-210: probabilities in -- the top MLP ends in a 
 the batch), forward and backward in ONE pass over the predictions (krs_bce_fwd_bwd, csrc/loss.hip); the softmax
 crossentropies of the retrieval examples (K11); and the regression losses of the rating examples -- MeanSquaredError,
 MeanAbsoluteError, Huber -- with every Keras reduction, sample weights and the regression metrics' update from one
-pass over the predictions (K24, krs_regression_fwd_bwd, csrc/regression.hip)."""
+pass over the predictions (K24, krs_regression_fwd_bwd, csrc/regression.hip); and the sampled-item binary
+cross-entropy of the sequence models (K29, krs_sampled_bce_fwd_bwd, csrc/sampled_bce.hip)."""
 
 from __future__ import annotations
 
+import os
+
 import torch
 
+from keras_rs_amd import _lib as L
 from keras_rs_amd import losses as _reductions
 from keras_rs_amd import regression_ops as _regression
-from keras_rs_amd.autograd import BinaryCrossentropyFn
+from keras_rs_amd.autograd import BinaryCrossentropyFn, _switch
+from keras_rs_amd.layers.embed_reduce import as_index_tensor
 from keras_rs_amd.retrieval_ops import SoftmaxCrossentropyFn
+from keras_rs_amd.sampled_ops import SampledItemBceFn
 
 
 class BinaryCrossentropy:
@@ -218,3 +224,90 @@ class Huber(_RegressionLoss):
 
     def get_config(self) -> dict:
         return {**super().get_config(), "delta": self.delta}
+
+
+# ---- K29: the sampled-item binary cross-entropy of a sequence model ----------------------------------------------------
+# 1: the fused kernel; 0: the stored torch composition (A/B).  The environment is read once, at import; the module
+# global is what every call looks at, as with sequence.FUSE_NORM
+FUSE_SAMPLED_BCE = _switch(os.environ.get("KRS_FUSE_SAMPLED_BCE", "1"))
+
+
+def sampled_item_crossentropy_stored(embedding_layer, sequence_embedding, positive, negative, sample_weight=None):
+    """The torch composition the fused loss replaces: two embedding lookups that store [B, L, d] and [B, L, N, d],
+    fp32 copies of the three blocks, the [B, (1 + N) L] logits and the element-wise BCE with logits, weighted and
+    divided by the sum of the weights (0 when that sum is 0)."""
+    emb = sequence_embedding.float()
+    b, length = positive.shape
+    neg_ids = negative.reshape(b, length, -1)
+    n = neg_ids.shape[2]
+    pos = embedding_layer(positive).float()
+    neg = embedding_layer(neg_ids.reshape(b, length * n)).float().reshape(b, length, n, -1)
+    logits = torch.cat([(pos * emb).sum(-1), (neg * emb.unsqueeze(2)).sum(-1).reshape(b, length * n)], dim=1)
+    labels = torch.cat([torch.ones_like(logits[:, :length]), torch.zeros_like(logits[:, length:])], dim=1)
+    w = torch.ones((b, length), device=emb.device) if sample_weight is None else sample_weight.float()
+    weight = torch.cat([w, w.repeat_interleave(n, dim=1)], dim=1)
+    loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, labels, reduction="none") * weight
+    total = weight.sum()
+    return torch.where(total > 0, loss.sum() / total.clamp_min(1e-30), torch.zeros_like(total))
+
+
+class SampledItemCrossentropy:
+    """The training loss of SASRec and its family: loss(embedding_layer, sequence_embedding [B, L, d], positive [B, L],
+    negative [B, L] or [B, L, N], sample_weight=None | [B, L] float or bool) -> scalar.  Every token scores its positive
+    item and its N sampled negatives by a dot product of its sequence embedding with the items' rows of
+    `embedding_layer` (a layers.Embedding); the loss is keras' binary cross-entropy from logits (label 1 for the
+    positive, 0 for a negative) weighted per token and divided by (1 + N) * sum(sample_weight), 0 when that is 0.
+
+    One kernel call (K29, csrc/sampled_bce.hip) gathers every row once and leaves the loss, the logit gradients and the
+    gradient to the sequence embedding; the table's gradient is one K2 call over the (1 + N) B L lookups.  An id outside
+    the table raises IndexError (one host read of the kernel's error word per call).  A quantized embedding layer,
+    d > 512 and KRS_FUSE_SAMPLED_BCE=0 take sampled_item_crossentropy_stored; N > 64 raises ValueError.
+
+    Three things to know.  The fused loss reads the layer's STORED rows (fp32 under "mixed_bfloat16"), where the stored
+    composition's lookups round every gathered row to the compute dtype first: under a mixed policy the two differ by
+    that rounding of the rows (2^-8 relative per element), the fused loss being the closer to exact arithmetic.  Its
+    gradient buffers are scaled in place by the upstream scalar, so it can be differentiated once: a second backward
+    (retain_graph=True) raises RuntimeError.  And it refuses a capturing stream (KrsError): a step that contains it
+    runs eagerly."""
+
+    def __init__(self, name: str | None = None):
+        self.name = name or "sampled_item_crossentropy"
+
+    def __call__(self, embedding_layer, sequence_embedding, positive, negative, sample_weight=None) -> torch.Tensor:
+        emb = sequence_embedding
+        if emb.dim() != 3 or tuple(positive.shape) != tuple(emb.shape[:2]):
+            raise ValueError("`sequence_embedding` should be [B, L, d] and `positive` [B, L]. Received: "
+                             f"{tuple(emb.shape)} and {tuple(positive.shape)}.")
+        b, length, d = emb.shape
+        if negative.dim() not in (2, 3) or tuple(negative.shape[:2]) != (b, length):
+            raise ValueError(f"`negative` should be [B, L] or [B, L, N]. Received: {tuple(negative.shape)}.")
+        if sample_weight is not None and tuple(sample_weight.shape) != (b, length):
+            raise ValueError(f"`sample_weight` should be [B, L]. Received: {tuple(sample_weight.shape)}.")
+        if not embedding_layer.built:
+            embedding_layer.build()
+        n = 1 if negative.dim() == 2 else negative.shape[2]
+        if n > L.SBCE_MAX_NEGATIVES:
+            raise ValueError(f"`negative` holds {n} items per position; at most {L.SBCE_MAX_NEGATIVES} are supported.")
+        if not FUSE_SAMPLED_BCE or embedding_layer.quantization_mode or d > L.SBCE_MAX_DIM:
+            return sampled_item_crossentropy_stored(embedding_layer, emb, positive, negative, sample_weight)
+        table = embedding_layer.embeddings
+        if table.shape[1] != d:
+            raise ValueError(f"`sequence_embedding` is {d} wide, the embedding layer's rows {table.shape[1]}.")
+        if emb.dtype not in (torch.float32, torch.bfloat16):
+            emb = emb.to(torch.float32)
+        tokens = b * length
+        pos = as_index_tensor(positive, table.device).reshape(tokens)
+        neg = as_index_tensor(negative, table.device).to(pos.dtype).reshape(tokens, n) if n else None
+        w = None if sample_weight is None else sample_weight.detach().to(torch.float32).reshape(tokens)
+        err = torch.zeros(1, dtype=torch.int32, device=table.device)
+        loss = SampledItemBceFn.apply(embedding_layer._fused("sum"), emb.reshape(tokens, d), pos, neg, w, err, table)
+        if int(err.item()) & L.FLAG_ID_OUT_OF_RANGE:
+            raise IndexError("embedding id out of range for its table (ids are never clamped)")
+        return loss
+
+    def get_config(self) -> dict:
+        return {"name": self.name}
+
+    @classmethod
+    def from_config(cls, config: dict):
+        return cls(**config)

@@ -81,6 +81,7 @@ class SasRec(base.Layer):
         self.exclude_history = False       # serve and evaluate without the items of the input sequence
         self.loss = kl.SampledItemCrossentropy()
         self.stored_loss = False           # True: the torch composition instead of the fused loss (K29)
+        self.softmax_loss = kl.SampledSoftmaxCrossentropy()   # --loss softmax (K30): negatives shared by a sequence
         self.built = True
 
     def sequence_embedding(self, item_ids, padding_mask, training: bool = False):
@@ -115,6 +116,9 @@ class SasRec(base.Layer):
         return result
 
     def compute_loss(self, y, y_pred, sample_weight):
+        if "shared_negatives" in y:        # the sampled softmax over the [B, N] negatives each sequence shares (K30)
+            return self.softmax_loss(self.item_embedding, y_pred["item_sequence_embedding"], y["positive_sequence"],
+                                     y["shared_negatives"], sample_weight)
         args = (self.item_embedding, y_pred["item_sequence_embedding"], y["positive_sequence"], y["negative_sequence"],
                 sample_weight)
         return sampled_item_crossentropy_stored(*args) if self.stored_loss else self.loss(*args)
@@ -122,7 +126,8 @@ class SasRec(base.Layer):
 
 def main(steps: int = 30, batch: int = 64, vocabulary_size: int = 500, length: int = 50, hidden_dim: int = 50,
          num_heads: int = 1, num_layers: int = 2, dropout: float = 0.2, dtype: str = "bf16", lr: float = 0.005,
-         seed: int = 0, quiet: bool = False, exclude_history: bool = False, stored: bool = False, negatives: int = 1):
+         seed: int = 0, quiet: bool = False, exclude_history: bool = False, stored: bool = False, negatives: int = 1,
+         loss: str = "bce", shared_negatives: int = 128):
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(seed)
     policy = {"bf16": "mixed_bfloat16", "fp32": "float32"}[dtype]
@@ -133,6 +138,10 @@ def main(steps: int = 30, batch: int = 64, vocabulary_size: int = 500, length: i
                                           synthetic_sequences(batch, vocabulary_size, length, seed, negatives))
     inputs = {"item_ids": item_ids, "padding_mask": mask}
     y = {"positive_sequence": positive, "negative_sequence": negative}
+    if loss == "softmax":
+        gen = torch.Generator().manual_seed(seed)
+        y["shared_negatives"] = torch.randint(1, vocabulary_size, (batch, shared_negatives), generator=gen,
+                                              dtype=torch.int32).to(dev)
     model(inputs, training=True)                                                                  # (builds every weight)
     opt = torch.optim.Adam(model.weights, lr=lr, betas=(0.9, 0.98))
     losses = []
@@ -167,7 +176,10 @@ if __name__ == "__main__":
     ap.add_argument("--stored", action="store_true",
                     help="compute the loss with the stored torch composition instead of the fused kernel (K29)")
     ap.add_argument("--negatives", type=int, default=1, help="sampled negatives per position")
+    ap.add_argument("--loss", choices=("bce", "softmax"), default="bce",
+                    help="bce: the sampled-item BCE (K29); softmax: the sampled softmax over shared negatives (K30)")
+    ap.add_argument("--shared-negatives", type=int, default=128, help="negatives a sequence shares under --loss softmax")
     a = ap.parse_args()
     main(steps=a.steps, batch=a.batch, vocabulary_size=a.vocabulary, length=a.length, hidden_dim=a.hidden,
          num_heads=a.heads, num_layers=a.layers, dtype=a.dtype, exclude_history=a.exclude_history, stored=a.stored,
-         negatives=a.negatives)
+         negatives=a.negatives, loss=a.loss, shared_negatives=a.shared_negatives)

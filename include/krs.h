@@ -1984,6 +1984,89 @@ int krs_sampled_bce_plan_route(const void* emb, int64_t ld_emb, int emb_dtype, c
                                const float* weight, int64_t t, int64_t d, int64_t n, const float* glog,
                                const void* demb, int64_t ld_demb, krs_sampled_bce_route* route);
 
+/* ------------------------------------------------------------------------- *
+ * K30  Shared-negative sampled softmax of a sequence model: every token scores its positive item and the N sampled
+ *      negatives its GROUP shares (a sequence, or the whole batch), so the scores are a [Lg, d] x [d, N] product per
+ *      group.  One call leaves the loss, lse, the positive's logit gradient, the gradient to the sequence embedding
+ *      and the gradient to the N shared rows; the [T, N] scores are never stored.
+ *
+ * Operands  emb [t, d] fp32 / bf16 (emb_dtype), row stride ld_emb >= d; table [vocab, d] fp32 / bf16 (table_dtype,
+ *           independent), row stride ld_table >= d; pos [t] and neg [g, n] (contiguous) int32 / int64 (itype);
+ *           t = g * lg, token i belongs to group i / lg.  weight [t] fp32 or NULL (w = 1); pos_logq [t] and
+ *           neg_logq [g, n] fp32, both or neither; remove_hits 0 / 1.
+ * Logits    x_t0 = e_t . table[pos_t] - pos_logq_t;  x_tj = e_t . table[neg_{g, j-1}] - neg_logq_{g, j-1}, fp32
+ *           accumulation.  With remove_hits a negative whose id equals pos_t is left out of token t's softmax
+ *           (probability 0, no gradient from that token).
+ * Loss      lse_t = log sum_j exp(x_tj) over the items that stay;  l_t = lse_t - x_t0;  S = sum_t w_t in the W pass's
+ *           order (float(t) without weights);  loss[0] = S != 0 ? (sum_t w_t l_t) / S : 0.
+ * Gradients (unit upstream)  c_t = w_t / S,  p_tj = exp(x_tj - lse_t):
+ *           gpos [t] fp32         = c_t (p_t0 - 1)
+ *           demb [t, d] emb dtype = gpos_t r_pos(t) + c_t sum_{j >= 1} p_tj r_j       (row stride ld_demb)
+ *           dneg [g, n, d] fp32   = sum_{t in g} c_t p_tj e_t                          (contiguous)
+ *           lse [t] fp32 is written too.  d table is krs_embed_bag_bwd_dense twice: the pos lookups with weights gpos
+ *           and bag gradient emb, the neg lookups with bag gradient dneg; duplicate ids are summed there.
+ * Dead      A token with w_t == 0, every token when S == 0, and a token whose positive id is out of range is DEAD: it
+ *           requests no row, adds nothing to the loss or to dneg, and gets exact zeros in lse, gpos and demb (a
+ *           non-finite row under a zero weight cannot leak).  A token all of whose negatives are removed has l_t = 0,
+ *           p_t0 = 1 and zero gradients.  An id outside [0, vocab) -- a negative's, or the positive's of a token with
+ *           w_t != 0 and S != 0 -- ORs KRS_FLAG_ID_OUT_OF_RANGE into err_flag (device int, optional); an out-of-range
+ *           negative takes no part in any softmax and its dneg row is zero.  Never clamped.  t == 0 launches nothing.
+ * Routes    KRS_SAMPLED_SOFTMAX_FAST: emb bf16, d <= 128, table bf16 or fp32.  Table rows, the positive's included,
+ *           are rounded to bf16 (nearest even) as they are staged; v_mfma_f32_32x32x16_bf16 with DPAD = 32 / 64 / 128.
+ *           vec = 1 when d % 8 == 0 and emb and table start on 16 bytes with row strides that are multiples of 16
+ *           bytes (16-byte loads), else element loads.  The probabilities are rounded to bf16 for the second product;
+ *           the positive's term gpos_t r_pos(t) is added in fp32.  Tokens sweep (owner = 128 tokens of one group, the
+ *           group's negatives streamed in tiles of 32, online (m, Z); the positive enters as the diagonal of one extra
+ *           tile per wave), then the negatives sweep (owner = 128 negatives of one group, the group's tokens streamed;
+ *           the tokens are dealt to `splits` workgroups in runs of whole tiles when the grid would be small, whose
+ *           partial dneg are added in split order by a reduce launch).
+ *           KRS_SAMPLED_SOFTMAX_GENERIC: everything else up to d = 512; fp32 FMA, rows as stored (no rounding), one
+ *           workgroup per token with its scores in LDS, then one workgroup per negative.
+ * Order     (fixed; no float atomics; every output element has one owner)  Every workgroup of the tokens sweep leaves
+ *           one partial sum_t w_t l_t: fast, its 128 tokens in a halving tree by token slot (x[i] += x[i + o],
+ *           o = 64 .. 1); generic, its one token.  The finish launch (always run) adds them: thread k of
+ *           KRS_SAMPLED_SOFTMAX_FINISH_THREADS adds the partials k, k + THREADS, .. in that order, the threads are
+ *           added by the same halving tree, then the division by S.  The W pass is K29's (KRS_SAMPLED_BCE_W_*).
+ *           Results are bit-identical from call to call.
+ * Launches  [W pass] + tokens sweep + negatives sweep + [reduce, splits > 1] + finish.  No host wait, no allocation.
+ * workspace krs_sampled_softmax_workspace_bytes(t, g, n, d, emb_dtype) device bytes, uninitialised: the W partials, c_t
+ *           [t], the loss partials and, with splits > 1, splits partial copies of dneg.  Too little: KRS_ERR_WORKSPACE.
+ * Refusals  (KRS_ERR_INVALID, the text names the limit)  n outside 1 .. KRS_SAMPLED_SOFTMAX_MAX_NEGATIVES, d outside
+ *           1 .. KRS_SAMPLED_SOFTMAX_MAX_DIM, g < 1 or t % g != 0, t or g * n above 2^31 - 1, one logq array without the
+ *           other, a dtype or itype outside its enum, vocab < 0, a row stride below d, and for t > 0 a NULL operand
+ *           or output.
+ *
+ * krs_sampled_softmax_last_route: how the calling thread's last krs_sampled_softmax_fwd_bwd ran (all 0 before the first
+ * call, after a refusal or for t == 0).  Returns `kernel`; route may be NULL.
+ * krs_sampled_softmax_plan_route: the same answer without a GPU and without touching the record; pointers are read as
+ * VALUES (nullness, alignment).  Returns what the entry returns before its first launch.
+ * ------------------------------------------------------------------------- */
+#define KRS_SAMPLED_SOFTMAX_MAX_DIM 512
+#define KRS_SAMPLED_SOFTMAX_FAST_MAX_DIM 128
+#define KRS_SAMPLED_SOFTMAX_MAX_NEGATIVES 4096
+#define KRS_SAMPLED_SOFTMAX_OWN_ROWS 128
+#define KRS_SAMPLED_SOFTMAX_TILE 32
+#define KRS_SAMPLED_SOFTMAX_MAX_SPLITS 64
+#define KRS_SAMPLED_SOFTMAX_FINISH_THREADS 1024
+enum { KRS_SAMPLED_SOFTMAX_ROUTE_NONE = 0, KRS_SAMPLED_SOFTMAX_FAST = 1, KRS_SAMPLED_SOFTMAX_GENERIC = 2 };
+typedef struct krs_sampled_softmax_route {
+  int32_t kernel, dpad, vec, grid_tokens, grid_negs, splits, split_tiles, launches;
+} krs_sampled_softmax_route;
+size_t krs_sampled_softmax_workspace_bytes(int64_t t, int64_t g, int64_t n, int64_t d, int emb_dtype);
+int krs_sampled_softmax_fwd_bwd(const void* emb, int64_t ld_emb, int emb_dtype, const void* table, int64_t ld_table,
+                                int table_dtype, int64_t vocab, const void* pos, const void* neg, int itype,
+                                const float* weight, const float* pos_logq, const float* neg_logq, int64_t t, int64_t g,
+                                int64_t n, int64_t d, int remove_hits, float* loss, float* lse, float* gpos, void* demb,
+                                int64_t ld_demb, float* dneg, int* err_flag, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int krs_sampled_softmax_last_route(krs_sampled_softmax_route* route);
+int krs_sampled_softmax_plan_route(const void* emb, int64_t ld_emb, int emb_dtype, const void* table, int64_t ld_table,
+                                   int table_dtype, int64_t vocab, const void* pos, const void* neg, int itype,
+                                   const float* weight, const float* pos_logq, const float* neg_logq, int64_t t,
+                                   int64_t g, int64_t n, int64_t d, int remove_hits, const float* lse,
+                                   const float* gpos, const void* demb, int64_t ld_demb, const float* dneg,
+                                   krs_sampled_softmax_route* route);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,16 @@ SBCE_ROUTE_NONE, SBCE_VEC, SBCE_ELEM = 0, 1, 2
 SBCE_MAX_DIM, SBCE_MAX_NEGATIVES, SBCE_THREADS, SBCE_MAX_BLOCKS = 512, 64, 256, 1024
 
 
+class SampledSoftmaxRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("kernel", "dpad", "vec", "grid_tokens", "grid_negs", "splits",
+                                               "split_tiles", "launches")]
+
+
+# krs_sampled_softmax_route.kernel and the K30 limits (include/krs.h)
+SSM_ROUTE_NONE, SSM_FAST, SSM_GENERIC = 0, 1, 2
+SSM_MAX_DIM, SSM_FAST_MAX_DIM, SSM_MAX_NEGATIVES, SSM_OWN_ROWS, SSM_TILE, SSM_MAX_SPLITS = 512, 128, 4096, 128, 32, 64
+
+
 class VocabRoute(C.Structure):
     _fields_ = [(name, C.c_int32) for name in ("route", "ids_per_lane", "vec", "lds_bytes")] + \
                [(name, C.c_int64) for name in ("slots", "blocks")]
@@ -288,6 +298,12 @@ PROTOTYPES = {
     "krs_sampled_bce_last_route": (_I, [_P]),
     "krs_sampled_bce_plan_route": (_I, [_P, _I64, _I, _P, _I64, _I, _I64, _P, _P, _I, _P, _I64, _I64, _I64, _P, _P, _I64,
                                         _P]),
+    "krs_sampled_softmax_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I]),
+    "krs_sampled_softmax_fwd_bwd": (_I, [_P, _I64, _I, _P, _I64, _I, _I64, _P, _P, _I, _P, _P, _P, _I64, _I64, _I64, _I64,
+                                         _I, _P, _P, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
+    "krs_sampled_softmax_last_route": (_I, [_P]),
+    "krs_sampled_softmax_plan_route": (_I, [_P, _I64, _I, _P, _I64, _I, _I64, _P, _P, _I, _P, _P, _P, _I64, _I64, _I64,
+                                            _I64, _I, _P, _P, _P, _I64, _P, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

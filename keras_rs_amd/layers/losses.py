@@ -3,8 +3,9 @@ it (examples/ml_perf/main.py:201-210: probabilities in -- the top MLP ends in a 
 the batch), forward and backward in ONE pass over the predictions (krs_bce_fwd_bwd, csrc/loss.hip); the softmax
 crossentropies of the retrieval examples (K11); and the regression losses of the rating examples -- MeanSquaredError,
 MeanAbsoluteError, Huber -- with every Keras reduction, sample weights and the regression metrics' update from one
-pass over the predictions (K24, krs_regression_fwd_bwd, csrc/regression.hip); and the sampled-item binary
-cross-entropy of the sequence models (K29, krs_sampled_bce_fwd_bwd, csrc/sampled_bce.hip)."""
+pass over the predictions (K24, krs_regression_fwd_bwd, csrc/regression.hip); and the two sampled-item losses of the
+sequence models: the binary cross-entropy over per-token negatives (K29, krs_sampled_bce_fwd_bwd, csrc/sampled_bce.hip)
+and the softmax over shared negatives (K30, krs_sampled_softmax_fwd_bwd, csrc/sampled_softmax.hip)."""
 
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ from keras_rs_amd import regression_ops as _regression
 from keras_rs_amd.autograd import BinaryCrossentropyFn, _switch
 from keras_rs_amd.layers.embed_reduce import as_index_tensor
 from keras_rs_amd.retrieval_ops import SoftmaxCrossentropyFn
-from keras_rs_amd.sampled_ops import SampledItemBceFn
+from keras_rs_amd.sampled_ops import SampledItemBceFn, SampledSoftmaxFn
 
 
 class BinaryCrossentropy:
@@ -307,6 +308,103 @@ class SampledItemCrossentropy:
 
     def get_config(self) -> dict:
         return {"name": self.name}
+
+    @classmethod
+    def from_config(cls, config: dict):
+        return cls(**config)
+
+
+# ---- K30: the sampled softmax over negatives a sequence, or the batch, shares -------------------------------------------
+FUSE_SAMPLED_SOFTMAX = _switch(os.environ.get("KRS_FUSE_SAMPLED_SOFTMAX", "1"))
+
+
+def sampled_softmax_crossentropy_stored(embedding_layer, sequence_embedding, positive, negative, sample_weight=None,
+                                        positive_log_q=None, negative_log_q=None, remove_accidental_hits=True):
+    """The torch composition the fused loss replaces, and its A/B baseline: two embedding lookups, the [B, L, 1 + N]
+    fp32 logits (a batched product with the shared rows), the log-q correction, the accidental hits masked to -inf, and
+    a log-softmax at the positive, weighted and divided by the sum of the weights (0 when that sum is 0).  Autograd
+    keeps the logits and their softmax."""
+    emb = sequence_embedding.float()
+    b, length, _ = emb.shape
+    neg_ids = negative.reshape(1, -1) if negative.dim() == 1 else negative
+    pos = embedding_layer(positive).float()
+    neg = embedding_layer(neg_ids).float()                                   # [B, N, d] or [1, N, d]
+    x0 = (pos * emb).sum(-1, keepdim=True)
+    xn = torch.matmul(emb, neg.transpose(1, 2))                              # [B, L, N]
+    if positive_log_q is not None:
+        x0 = x0 - positive_log_q.float().unsqueeze(-1)
+        xn = xn - negative_log_q.float().reshape(neg_ids.shape[0], 1, -1)
+    if remove_accidental_hits:
+        xn = xn.masked_fill(neg_ids.unsqueeze(1) == positive.unsqueeze(-1), float("-inf"))
+    per_token = torch.logsumexp(torch.cat([x0, xn], dim=-1), dim=-1) - x0.squeeze(-1)
+    w = torch.ones((b, length), device=emb.device) if sample_weight is None else sample_weight.float()
+    total = w.sum()
+    return torch.where(total > 0, (per_token * w).sum() / total.clamp_min(1e-30), torch.zeros_like(total))
+
+
+class SampledSoftmaxCrossentropy:
+    """The sampled softmax sequence models are mostly trained with: loss(embedding_layer, sequence_embedding [B, L, d],
+    positive [B, L], negative [B, N] (per sequence) or [N] (one set for the batch), sample_weight=None | [B, L],
+    positive_log_q=None | [B, L], negative_log_q=None | negative's shape) -> scalar.  Every token takes the softmax
+    cross-entropy of its positive item among it and the N shared negatives, scored by dot products with the rows of
+    `embedding_layer`; the log q (log of the sampling probability) are subtracted from the logits when given, both or
+    neither.  With remove_accidental_hits a negative that equals a token's positive is left out of that token's softmax.
+    Tokens are weighted and the sum divided by sum(sample_weight), 0 when that is 0.
+
+    K30 (csrc/sampled_softmax.hip): the scores are an MFMA product per group whose streamed side is gathered from the
+    table, never stored; one call leaves the loss, the gradient to the sequence embedding and to the N shared rows, and
+    the table's gradient is two K2 calls.  bf16 sequence embeddings up to d = 128 take the MFMA route -- the table may
+    be fp32, as under "mixed_bfloat16", its rows are rounded to bf16 on the way in --; fp32, or d up to 512, the fp32
+    route.  A quantized layer, d > 512 and KRS_FUSE_SAMPLED_SOFTMAX=0 take sampled_softmax_crossentropy_stored.
+    N > 4096 raises ValueError, an id outside the table IndexError.  As SampledItemCrossentropy, the loss can be
+    differentiated once and refuses a capturing stream (KrsError)."""
+
+    def __init__(self, remove_accidental_hits: bool = True, name: str | None = None):
+        self.remove_accidental_hits = bool(remove_accidental_hits)
+        self.name = name or "sampled_softmax_crossentropy"
+
+    def __call__(self, embedding_layer, sequence_embedding, positive, negative, sample_weight=None,
+                 positive_log_q=None, negative_log_q=None) -> torch.Tensor:
+        emb = sequence_embedding
+        if emb.dim() != 3 or tuple(positive.shape) != tuple(emb.shape[:2]):
+            raise ValueError("`sequence_embedding` should be [B, L, d] and `positive` [B, L]. Received: "
+                             f"{tuple(emb.shape)} and {tuple(positive.shape)}.")
+        b, length, d = emb.shape
+        if negative.dim() not in (1, 2) or (negative.dim() == 2 and negative.shape[0] != b) or negative.shape[-1] < 1:
+            raise ValueError(f"`negative` should be [B, N] or [N] with N >= 1. Received: {tuple(negative.shape)}.")
+        n = negative.shape[-1]
+        if n > L.SSM_MAX_NEGATIVES:
+            raise ValueError(f"`negative` holds {n} items; at most {L.SSM_MAX_NEGATIVES} are supported.")
+        if (positive_log_q is None) != (negative_log_q is None):
+            raise ValueError("`positive_log_q` and `negative_log_q` are given both or neither.")
+        for name, x, shape in (("sample_weight", sample_weight, (b, length)), ("positive_log_q", positive_log_q, (b, length)),
+                               ("negative_log_q", negative_log_q, tuple(negative.shape))):
+            if x is not None and tuple(x.shape) != shape:
+                raise ValueError(f"`{name}` should be {shape}. Received: {tuple(x.shape)}.")
+        if not embedding_layer.built:
+            embedding_layer.build()
+        if not FUSE_SAMPLED_SOFTMAX or embedding_layer.quantization_mode or d > L.SSM_MAX_DIM:
+            return sampled_softmax_crossentropy_stored(embedding_layer, emb, positive, negative, sample_weight,
+                                                       positive_log_q, negative_log_q, self.remove_accidental_hits)
+        table = embedding_layer.embeddings
+        if table.shape[1] != d:
+            raise ValueError(f"`sequence_embedding` is {d} wide, the embedding layer's rows {table.shape[1]}.")
+        if emb.dtype not in (torch.float32, torch.bfloat16):
+            emb = emb.to(torch.float32)
+        tokens = b * length
+        pos = as_index_tensor(positive, table.device).reshape(tokens)
+        neg = as_index_tensor(negative, table.device).to(pos.dtype).reshape(-1, n)
+        flat = lambda x, shape: None if x is None else x.detach().to(torch.float32).reshape(shape)      # noqa: E731
+        err = torch.zeros(1, dtype=torch.int32, device=table.device)
+        loss = SampledSoftmaxFn.apply(embedding_layer._fused("sum"), emb.reshape(tokens, d), pos, neg,
+                                      flat(sample_weight, (tokens,)), flat(positive_log_q, (tokens,)),
+                                      flat(negative_log_q, tuple(neg.shape)), self.remove_accidental_hits, err, table)
+        if int(err.item()) & L.FLAG_ID_OUT_OF_RANGE:
+            raise IndexError("embedding id out of range for its table (ids are never clamped)")
+        return loss
+
+    def get_config(self) -> dict:
+        return {"name": self.name, "remove_accidental_hits": self.remove_accidental_hits}
 
     @classmethod
     def from_config(cls, config: dict):

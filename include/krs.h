@@ -2067,6 +2067,70 @@ int krs_sampled_softmax_plan_route(const void* emb, int64_t ld_emb, int emb_dtyp
                                    const float* gpos, const void* demb, int64_t ld_demb, const float* dneg,
                                    krs_sampled_softmax_route* route);
 
+/* ------------------------------------------------------------------------- *
+ * K31  HSTU's pointwise attention (Zhai et al., ICML 2024) over [b, l] token sequences: SiLU in place of the softmax, a
+ *      learned relative-position bias inside it, padded queries masked as well as padded keys.  The scores, the weights
+ *      and an [h, l, l] expansion of the bias are never stored; the forward keeps nothing for the backward.
+ *
+ * Layout, strides and dtypes are K19's: token (bi, i) is row bi * l + i, head hi starts at column hi * dh, rows are ldq /
+ * ldk / ldv / ldo / lddo / lddq / lddk / lddv elements apart (>= h * dh; q, k, v may be column slices of one packed
+ * projection output).  dtype (KRS_F32 / KRS_BF16) is the type of all of them.  pos and dpos are fp32 [hb, 2l - 1] with
+ * hb = 1 (one row for all heads) or hb = h; hb is not read when pos is NULL.  valid is uint8 [b, l], 1 = a token.
+ * Per (bi, hi), query i and key j, in fp32, with hb_i = hb == 1 ? 0 : hi:
+ *     s_ij    = alpha * sum_d q_id k_jd + (pos ? pos[hb_i][i - j + l - 1] : 0)
+ *     allowed = (!causal || j <= i) && (valid == NULL || (valid[bi, i] && valid[bi, j]))
+ *     sg      = 1 / (1 + exp(-s_ij))
+ *     a_ij    = allowed ? s_ij * sg * inv_n : 0
+ *     o_i     = sum_j a_ij v_j
+ *     dA_ij   = dO_i . v_j
+ *     dS_ij   = allowed ? inv_n * dA_ij * sg * (1 + s_ij * (1 - sg)) : 0
+ *     dV_j    = sum_i a_ij dO_i      dQ_i = alpha * sum_j dS_ij k_j      dK_j = alpha * sum_i dS_ij q_i
+ *     dPos[hb_i][t + l - 1] = sum over bi, (hi when hb == 1), and i - j = t of dS_ij
+ * A query row with no allowed key has o_i = 0 and contributes exactly zero to every gradient.  Inputs must be finite.
+ * Not here: dropout on the weights (HSTU's dropout sits on the block output), the time-interval bias, a value width
+ * other than dh, jagged layouts.
+ *
+ * Routes (csrc/hstu_attn_plan.h decides, a pure host function):
+ *   KRS_HSTU_ATTN_FAST     bf16, dh <= 128 (dpad 32 / 64 / 128).  Scores on v_mfma_f32_32x32x16_bf16; the bias comes
+ *                          from a window in LDS; a and dS are rounded to bf16 (nearest even) for the second products;
+ *                          fp32 accumulate; outputs rounded once to bf16.  vec = 1 when every row is whole 16-byte
+ *                          chunks on 16-byte boundaries, else rows load element-wise (dh = 50, odd strides).
+ *   KRS_HSTU_ATTN_GENERIC  fp32 at any dh <= 256, bf16 at 128 < dh <= 256: fp32 FMA throughout, outputs rounded once.
+ * One owner per output element and no float atomics on either route, dpos included: every workgroup of the key sweep
+ * (fast) or of the offsets sweep (generic) leaves one partial table of offsets in the workspace, fp32 dS summed in a
+ * fixed order, and a reduce launch adds a head's tables in (bi, hi, owner block) order, in four runs added in order.
+ * Results are bit-identical from call to call.
+ *
+ * krs_hstu_attn_fwd writes out and uses no workspace.  krs_hstu_attn_bwd writes dq, dk, dv, dpos (any may be NULL to
+ * skip it, not all; dpos must be NULL when pos is); with dpos it needs krs_hstu_attn_workspace_bytes of workspace (the
+ * partial tables only; it need not be initialised; too little is KRS_ERR_WORKSPACE; hb = 0 asks for none).  No host
+ * synchronisation.  b == 0 or l == 0 is a successful no-op.  b < 0, h < 1, l < 0, dh < 1, a bad dtype, hb outside
+ * {1, h} with pos, a stride below h * dh, a null operand, dout or output, and dpos without pos are KRS_ERR_INVALID.
+ * l > 4096, dh > 256 and b * h * l > 2^31 - 1 (the launch grid) are KRS_ERR_UNSUPPORTED with a message naming the limit.
+ * krs_hstu_attn_last_route: the route of the process's last krs_hstu_attn_fwd / _bwd call, whichever thread made it:
+ * kernel, dpad and vec (fast route, else 0), and the LDS bytes of the widest workgroup the call launched; all zero
+ * after a refused call or a no-op.  Returns kernel; route may be NULL.
+ * krs_hstu_attn_plan_route: the same answer from the arguments alone, with no HIP call and without touching the record;
+ * pointers are read as VALUES (nullness, alignment).  dout NULL asks for the forward's record, else the backward's.
+ * ------------------------------------------------------------------------- */
+enum { KRS_HSTU_ATTN_NONE = 0, KRS_HSTU_ATTN_FAST = 1, KRS_HSTU_ATTN_GENERIC = 2 };
+typedef struct krs_hstu_attn_route {
+  int32_t kernel, dpad, vec, lds_bytes;
+} krs_hstu_attn_route;
+size_t krs_hstu_attn_workspace_bytes(int64_t b, int64_t h, int64_t l, int64_t dh, int dtype, int64_t hb);
+int krs_hstu_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int dtype,
+                      int64_t b, int64_t h, int64_t l, int64_t dh, const float* pos, int64_t hb, const uint8_t* valid,
+                      int causal, float alpha, float inv_n, void* out, int64_t ldo, void* stream);
+int krs_hstu_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int dtype,
+                      int64_t b, int64_t h, int64_t l, int64_t dh, const float* pos, int64_t hb, const uint8_t* valid,
+                      int causal, float alpha, float inv_n, const void* dout, int64_t lddo, void* dq, int64_t lddq,
+                      void* dk, int64_t lddk, void* dv, int64_t lddv, float* dpos, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int krs_hstu_attn_last_route(krs_hstu_attn_route* route);
+int krs_hstu_attn_plan_route(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int dtype,
+                             int64_t b, int64_t h, int64_t l, int64_t dh, const float* pos, int64_t hb, const void* dout,
+                             int64_t lddo, const float* dpos, krs_hstu_attn_route* route);
+
 #ifdef __cplusplus
 }
 #endif

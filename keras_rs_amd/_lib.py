@@ -131,6 +131,14 @@ SSM_ROUTE_NONE, SSM_FAST, SSM_GENERIC = 0, 1, 2
 SSM_MAX_DIM, SSM_FAST_MAX_DIM, SSM_MAX_NEGATIVES, SSM_OWN_ROWS, SSM_TILE, SSM_MAX_SPLITS = 512, 128, 4096, 128, 32, 64
 
 
+class HstuAttnRoute(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("kernel", "dpad", "vec", "lds_bytes")]
+
+
+# krs_hstu_attn_route.kernel (include/krs.h, K31)
+HSTU_ROUTE_NONE, HSTU_FAST, HSTU_GENERIC = 0, 1, 2
+
+
 class VocabRoute(C.Structure):
     _fields_ = [(name, C.c_int32) for name in ("route", "ids_per_lane", "vec", "lds_bytes")] + \
                [(name, C.c_int64) for name in ("slots", "blocks")]
@@ -304,6 +312,13 @@ PROTOTYPES = {
     "krs_sampled_softmax_last_route": (_I, [_P]),
     "krs_sampled_softmax_plan_route": (_I, [_P, _I64, _I, _P, _I64, _I, _I64, _P, _P, _I, _P, _P, _P, _I64, _I64, _I64,
                                             _I64, _I, _P, _P, _P, _I64, _P, _P]),
+    "krs_hstu_attn_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I, _I64]),
+    "krs_hstu_attn_fwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I64, _I64, _I64, _I64, _P, _I64, _P, _I, _F, _F, _P, _I64,
+                               _P]),
+    "krs_hstu_attn_bwd": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I64, _I64, _I64, _I64, _P, _I64, _P, _I, _F, _F, _P, _I64,
+                               _P, _I64, _P, _I64, _P, _I64, _P, _P, _SZ, _P]),
+    "krs_hstu_attn_last_route": (_I, [_P]),
+    "krs_hstu_attn_plan_route": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _P]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -1,8 +1,10 @@
 """K19: fused multi-head self-attention over token sequences (csrc/seq_attention.hip; the arithmetic is fixed in
-include/krs.h).  The score matrix, the probabilities and the dropout mask are never stored: the backward recomputes
+include/krs.h); K31, HSTU's pointwise attention, follows it below.  The score matrix, the probabilities and the dropout mask are never stored: the backward recomputes
 them from q, k, v, the saved output and one log-sum-exp per (b, h, row)."""
 
+import ctypes as C
 import math
+from typing import NamedTuple
 
 import torch
 
@@ -130,3 +132,119 @@ def seq_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, key_vali
         scale = 1.0 / math.sqrt(q.shape[3])
     out, lse = _SeqAttention.apply(q, k, v, key_valid, bool(causal), float(scale), float(dropout_p), int(seed), draw)
     return (out, lse) if return_lse else out
+
+
+# ---- K31: HSTU's pointwise attention (csrc/hstu_attention.hip; the arithmetic is fixed in include/krs.h) ----------------
+class _HstuMeta(NamedTuple):
+    """What the backward needs besides the saved tensors."""
+    causal: bool
+    alpha: float
+    inv_n: float
+    has_pos: bool
+    has_valid: bool
+
+
+def hstu_workspace_bytes(b: int, h: int, l: int, dh: int, dtype: torch.dtype = torch.bfloat16, hb: int = 0) -> int:
+    dt = L.BF16 if dtype == torch.bfloat16 else L.F32
+    return int(L.lib().krs_hstu_attn_workspace_bytes(b, h, l, dh, dt, hb))
+
+
+def hstu_last_route() -> L.HstuAttnRoute:
+    """The route record of the last hstu_attention forward or backward call."""
+    route = L.HstuAttnRoute()
+    L.lib().krs_hstu_attn_last_route(C.addressof(route))
+    return route
+
+
+def hstu_plan_route(b: int, h: int, l: int, dh: int, dtype: torch.dtype, *, ld: int | None = None, hb: int = 0,
+                    backward: bool = False, base: int = 256):
+    """(status, record) krs_hstu_attn_plan_route gives a call on q, k, v at addresses base, base + h dh, base + 2 h dh
+    elements (one packed buffer of stride ld; default: separate aligned tensors of stride h dh).  Needs no GPU."""
+    es = 2 if dtype == torch.bfloat16 else 4
+    width = h * dh
+    q, k, v = (base, base, base) if ld is None else (base, base + width * es, base + 2 * width * es)
+    ld = width if ld is None else ld
+    route = L.HstuAttnRoute()
+    flag = 256 if hb else None
+    rc = L.lib().krs_hstu_attn_plan_route(q, ld, k, ld, v, ld, L.BF16 if dtype == torch.bfloat16 else L.F32, b, h, l, dh,
+                                          flag, hb, 256 if backward else None, width, flag if backward else None,
+                                          C.addressof(route))
+    return rc, route
+
+
+def _hstu_args(q, k, v, pos, valid, m: _HstuMeta):
+    b, l, h, dh = q.shape
+    return (L.ptr(q), _ld(q), L.ptr(k), _ld(k), L.ptr(v), _ld(v), L.fdtype(q), b, h, l, dh, L.ptr(pos),
+            0 if pos is None else pos.shape[0], L.ptr(valid), int(m.causal), m.alpha, m.inv_n)
+
+
+class _HstuAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, pos, valid, causal, alpha, inv_n):
+        q, k, v = _tokens(q), _tokens(k), _tokens(v)
+        b, l, h, dh = q.shape
+        meta = _HstuMeta(causal, alpha, inv_n, pos is not None, valid is not None)
+        out = torch.empty((b, l, h, dh), dtype=q.dtype, device=q.device)
+        rc = L.lib().krs_hstu_attn_fwd(*_hstu_args(q, k, v, pos, valid, meta), L.ptr(out), h * dh, L.stream_ptr())
+        L.check(rc, "krs_hstu_attn_fwd")
+        ctx.save_for_backward(q, k, v, pos, valid)     # (no output, no statistics: the backward recomputes the weights)
+        ctx.meta = meta
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q, k, v, pos, valid = ctx.saved_tensors
+        m = ctx.meta
+        b, l, h, dh = q.shape
+        want = list(ctx.needs_input_grad[:4])
+        want[3] = want[3] and m.has_pos
+        grads = [torch.empty((b, l, h, dh), dtype=q.dtype, device=q.device) if w else None for w in want[:3]]
+        dpos = torch.zeros_like(pos) if want[3] else None
+        if q.numel() == 0 or not any(want):
+            return (*grads, dpos, None, None, None, None)
+        dout = _tokens(dout)
+        size = hstu_workspace_bytes(b, h, l, dh, q.dtype, pos.shape[0]) if want[3] else 0
+        ws = torch.empty(max(1, size), dtype=torch.uint8, device=q.device)
+        rc = L.lib().krs_hstu_attn_bwd(*_hstu_args(q, k, v, pos, valid, m), L.ptr(dout), _ld(dout), L.ptr(grads[0]), h * dh,
+                                       L.ptr(grads[1]), h * dh, L.ptr(grads[2]), h * dh, L.ptr(dpos), L.ptr(ws), size,
+                                       L.stream_ptr())
+        L.check(rc, "krs_hstu_attn_bwd")
+        return (*grads, dpos, None, None, None, None)
+
+
+def hstu_attention_stored(q, k, v, *, pos_bias=None, valid=None, causal=True, alpha, inv_n):
+    """The torch composition of hstu_attention, for A/B runs: it stores the [B, H, L, L] scores, their activation and the
+    [H, L, L] expansion of the bias, and pays an index-add for the bias gradient."""
+    b, l, h, _ = q.shape
+    i = torch.arange(l, device=q.device)
+    s = alpha * torch.einsum("bihd,bjhd->bhij", q, k).float()
+    if pos_bias is not None:
+        s = s + pos_bias[:, i[:, None] - i[None, :] + l - 1]
+    ok = (i[None, :] <= i[:, None]) if causal else torch.ones(l, l, dtype=torch.bool, device=q.device)
+    if valid is not None:
+        ok = ok & (valid != 0)[:, None, :, None] & (valid != 0)[:, None, None, :]
+    a = torch.where(ok, torch.nn.functional.silu(s) * inv_n, 0.0).to(q.dtype)
+    return torch.einsum("bhij,bjhd->bihd", a, v)
+
+
+def hstu_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, pos_bias: torch.Tensor | None = None,
+                   valid: torch.Tensor | None = None, causal: bool = True, alpha: float, inv_n: float) -> torch.Tensor:
+    """HSTU's pointwise attention: out_i = sum_j silu(alpha q_i . k_j + pos_bias[., i - j + L - 1]) * inv_n * v_j over the
+    allowed (i, j).  q, k, v: [B, L, H, Dh], float32 or bfloat16 (views into one packed projection output are read in
+    place); pos_bias: float32 [1 or H, 2 L - 1]; valid: [B, L], truthy = a real token (a padded query is masked as well
+    as a padded key).  A query with no allowed key gives a zero row and takes no part in any gradient.  Nothing of size
+    L x L is stored.  No host synchronisation; differentiable in q, k, v and pos_bias, any subset."""
+    what = "hstu_attention"
+    _check(q, k, v, valid, 0.0, None, what)
+    b, l, h, _ = q.shape
+    if pos_bias is not None:
+        L.require_device(pos_bias, f"{what}: pos_bias")
+        if pos_bias.dtype != torch.float32 or pos_bias.dim() != 2 or pos_bias.shape[0] not in (1, h) \
+                or pos_bias.shape[1] != 2 * l - 1 or pos_bias.device != q.device:
+            raise L.KrsError(f"{what}: pos_bias must be float32 [1 or {h}, {2 * l - 1}] on {q.device}, got "
+                             f"{pos_bias.dtype} {tuple(pos_bias.shape)} on {pos_bias.device}")
+        pos_bias = pos_bias.contiguous()
+    if valid is not None:
+        valid = (valid != 0).to(torch.uint8).contiguous()
+    return _HstuAttention.apply(q, k, v, pos_bias, valid, bool(causal), float(alpha), float(inv_n))
